@@ -8,6 +8,8 @@ The product's wave program runs on the host wave emulator (tests/emu) and is hel
   * the oracle's restatement of the same active-set rule (qp_mode 0): same sweeps, same sets, same numbers.
 tests/test_active_set_gpu.py repeats this through the C-ABI on the device.
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -15,6 +17,7 @@ from ndp_nmpc_qd_amd import synth
 from tests import ref_numpy as R
 from tests.emu import emu as E
 
+HERE = os.path.dirname(os.path.abspath(__file__))
 MIXED = dict(pos_sigma=0.5, vel_sigma=1.0, quat_sigma=0.15)        # bench.py's `mixed` workload: ~20 % of the instances hit an input bound
 
 
@@ -290,7 +293,7 @@ def test_weak_multipliers_fixture_twin_and_emulator(oracle):
     multiplier was negative (status 0, 2.5e-4 .. 1.6e-2 off the QP's solution) or cycled into the interior-point loop.  The
     re-centred pins (rti_wave.hpp: as_apply; oracle: qp_solve_ws) return delta = lambda / as_gamma itself: oracle twin and wave
     program on every case to 1e-9 of the exact solution, the exact active set, no interior-point iteration, the same sweeps."""
-    g = np.load("tests/golden/as_weak_multiplier_cases.npz")
+    g = np.load(os.path.join(HERE, "golden", "as_weak_multiplier_cases.npz"))
     n = len(g["n_active"])
     twin = oracle.default_cfg()
     twin.qp_mode = 0

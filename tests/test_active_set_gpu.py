@@ -7,6 +7,8 @@ The default mode of every handle (ndp_cfg.as_iter_max = 8).  Checked against
   * exact dense-KKT solutions on a sample (tests/ref_numpy.py).
 CPU twin on the wave emulator: tests/test_active_set.py.
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -15,6 +17,7 @@ from tests import ref_numpy as R
 
 pytestmark = pytest.mark.gpu
 
+HERE = os.path.dirname(os.path.abspath(__file__))
 MIXED = dict(pos_sigma=0.5, vel_sigma=1.0, quat_sigma=0.15)        # bench.py's `mixed` workload
 HARD = dict(pos_sigma=1.5, vel_sigma=3.0, quat_sigma=0.2)          # test_active_bounds_and_infeasible_start's
 
@@ -228,7 +231,7 @@ def test_weak_multipliers_fixture(ndp, oracle):
     round 6's first form of the pins kept a wrongly signed one or cycled (tests/test_active_set.py has the story).  One batch, the kept
     sets handed in (ndp_set_active_set): every instance to 1e-9 of the exact dense-KKT solution, the exact number of active bounds, no
     interior-point iteration; the twin agrees on sweeps and sets."""
-    g = np.load("tests/golden/as_weak_multiplier_cases.npz")
+    g = np.load(os.path.join(HERE, "golden", "as_weak_multiplier_cases.npz"))
     B = len(g["n_active"])
     eng = ndp.BatchedNMPC(B)
     eng.set_iterate(g["X"], g["U"])
