@@ -48,15 +48,23 @@ size_t ndp_cfg_size(void);
 
 #define NDP_QP_AUTO 0       /* exact early exit when no bound is active, else interior point */
 #define NDP_QP_IPM_ALWAYS 1 /* always run the interior-point loop (what HPIPM does) */
+#define NDP_AS_GAMMA_FLOOR 1e8 /* ndp_cfg.as_gamma >= NDP_AS_GAMMA_FLOOR * max_i(dt * Rd[i]) when as_iter_max > 0 (ndp_create) */
 
 #define NDP_PREC_F64 0        /* product path: v_mfma_f64_16x16x4_f64 */
 #define NDP_PREC_F32_STUDY 1  /* f64 kernel, operands of the sweeps' matrix instructions rounded to fp32 (numerics only) */
 #define NDP_PREC_BF16_STUDY 2 /* ... rounded to bf16 */
 #define NDP_PREC_F32_MFMA 3   /* the Riccati sweeps on v_mfma_f32_16x16x4_f32 */
 #define NDP_PREC_BF16_MFMA 4  /* the Riccati sweeps on v_mfma_f32_16x16x16_bf16 (bf16 in, fp32 accumulate) */
+/* What status 0 means in each mode: the step satisfies its QP's KKT conditions up to a relative residual (the largest of the
+ * equality residual and the input box's natural residual, each over the largest term that enters it; tests/kkt_certificate.py) of
+ *   NDP_PREC_F64 (and every mode for a QP it hands to the fp64 path): 1e-9 after the active-set iterations, 3e5 tol after the
+ *     interior-point loop (an answer mu / lambda inside a bound with a small multiplier lambda);
+ *   NDP_PREC_F32_MFMA 1e-3 (7e-5 measured);  NDP_PREC_BF16_MFMA 1 (0.71 measured: a bf16-operand sweep is not a solve);
+ *   NDP_PREC_COND_F32 / _BF16 0.3: a condensed result is kept only when its fp64 stationarity residual is at most 0.3, else the fp64
+ *     path solves the QP (fp32 results: <= 0.13 measured; bf16 results: >= 0.81, i.e. in practice never kept). */
 #define NDP_PREC_COND_F32 5   /* BASELINE configs[4] as worded -- "fp32 vs bf16 MFMA on the CONDENSED QP": the first solve of every QP in condensed
                                * form (prediction matrices, H = R + Gamma' Q Gamma and the gradient as tiled products on v_mfma_f32_16x16x4_f32, fp32
-                               * Cholesky in LDS, csrc/cond_qp.hpp); kept when it passes the fp64 inside-the-box test, else the fp64 Riccati path
+                               * Cholesky in LDS, csrc/cond_qp.hpp); kept when it passes the fp64 inside-the-box and stationarity tests, else the fp64 Riccati path
                                * solves the QP.  A STUDY mode (the reference does not condense: qp_solver_cond_N = N): N a multiple of 4, <= 40 */
 #define NDP_PREC_COND_BF16 6  /* ... the products on v_mfma_f32_16x16x16_bf16 (fp32 accumulate, fp32 Cholesky) */
 
@@ -117,7 +125,9 @@ typedef struct ndp_cfg {
      * auto_margin inside every bound, else the interior-point loop).  A violated VELOCITY bound, a set that does not settle, a failed
      * factorisation: the interior-point loop takes the QP, as before.  ndp_reset / ndp_set_iterate empty the kept sets.
      * as_gamma: the weight that holds a pinned input on its bound (default 1e12: the input is then within multiplier / 1e12 of
-     * the bound and set onto it exactly). */
+     * the bound and set onto it exactly).  With as_iter_max > 0, ndp_create refuses (-2) an as_gamma that is not finite or is below
+     * NDP_AS_GAMMA_FLOOR * max_i(dt * Rd[i]): a weaker pin leaves the rest of the QP solved as if the input were free (1e6 at the
+     * defaults: u off by 4e-6; 1e-3: off by 1.9), yet the input is written onto its bound with status 0. */
     int32_t as_iter_max;
     int32_t reserved0;
     double as_gamma;

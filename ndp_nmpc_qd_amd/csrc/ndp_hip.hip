@@ -2655,6 +2655,17 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
         g_create_err = "ndp_create: the condensed study (qp_precision 5 / 6) tiles the 4N x 4N Hessian by 16: N must be a multiple of 4, at most 40";
         return -2;
     }
+    if (cfg->as_iter_max > 0) {
+        // a pin is the weight as_gamma on its input: far below the input weights it holds nothing, yet as_check still writes the input onto
+        // its bound -- a wrong step with status 0 (NDP_AS_GAMMA_FLOOR in the header)
+        double rd = 0.0;
+        for (int i = 0; i < 4; ++i) rd = std::max(rd, std::fabs(cfg->dt * cfg->Rd[i]));
+        if (!std::isfinite(cfg->as_gamma) || !(cfg->as_gamma >= NDP_AS_GAMMA_FLOOR * rd)) {
+            g_create_err = "ndp_create: as_gamma must be finite and at least 1e8 * max(dt * Rd) when as_iter_max > 0 (a weaker pin does not hold "
+                           "its input on the bound)";
+            return -2;
+        }
+    }
     if (cfg->ipm_refine > 0 && (slots_for(cfg->N) > 3 || cfg->qp_precision != 0)) {
         // (rounds 4-5 accepted the setting and ignored it -- a getter nobody called said so)
         g_create_err = "ndp_create: ipm_refine > 0 is not served for this shape: the refinement path (stiff sweeps + second solves while a STATE bound's "
@@ -4269,6 +4280,9 @@ int ndp_xchg_tick_begin(ndp_xchg *x, ndp_handle *h, const void *d_t, int flags, 
     if ((rc = x->async_rc.load(std::memory_order_relaxed))) { h->err = "ndp_xchg_tick_begin: an earlier begin failed on the exchange's thread: " + x->err; return rc; }
     const RingGeom rg = ring_geom(h);
     if (d_t && rg.step < 2) { h->err = "ndp_xchg_tick_begin: the list's entries are one node spacing apart -- the advance would overwrite the window a control step may be reading (use the serial form: ndp_tick_advance_device, ndp_xchg_tick_windows, ndp_tick_step_device)"; return -17; }
+    // a second begin ahead writes list entry n + step N + 2 while the step on window n (entries n, n + step, ..., n + step N) may still
+    // run: with step 2 that entry lands in the same residue class as the window, i.e. on one of its nodes (RingGeom::slot)
+    if (d_t && x->ahead == 1 && rg.step < 3) { h->err = "ndp_xchg_tick_begin: the list's entries are two per node spacing -- a second begin ahead would overwrite the window the step before it may be reading (one begin ahead only: the two-buffer form)"; return -17; }
     const size_t B = h->cfg.batch, rows = B * (size_t)(h->cfg.N + 1);
     if (x->send_doubles < rows * 6) {
         while (x->done.load(std::memory_order_acquire) != x->posted.load(std::memory_order_relaxed)) __builtin_ia32_pause();

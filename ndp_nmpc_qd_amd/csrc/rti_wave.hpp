@@ -155,6 +155,11 @@ NDP_HD int act_pitch(int N) { return 4 * N; }      // bytes per instance of the 
 // *RtiIo::iters = interior-point iterations of the step (low half) + Riccati sweeps its QP_AUTO solves took before them (high half);
 // COND_ACCEPTED in the sweep count (config 5's study): a condensed solve's result was kept
 enum { ITERS_SWEEP_SHIFT = 16, ITERS_IPM_MASK = 0xffff, COND_ACCEPTED = 0x1000 };
+// config 5's study: a condensed result is kept only if its fp64 stationarity residual (RtiWave::cond_stationarity) is at most this
+// (include/ndp_nmpc.h, NDP_PREC_COND_*); above it the fp64 sweep solves the QP, as after a failed factorisation.  Measured on 1024
+// instances per shape: fp32 results 6e-5 .. 4e-3 (N = 20) and 2e-3 .. 0.13 (N = 40), the bf16 results that passed the box test
+// 0.81 .. 1.8 (u off by up to 4.5).
+constexpr double COND_STAT_MAX = 0.3;
 
 struct LdsMap {
     int KC, SC, XI, UI, ZX, ZU, CX, CU, ZD, MB, CB, KT, TXR, TUR, TF, AS, total;
@@ -1556,6 +1561,35 @@ struct RtiWave {
         }
         W::sync();
     }
+    // Config 5's study (COND != 0): is a condensed result the equality-constrained minimiser it claims to be?  Its reduced input
+    // gradient g_k = R du_k + r_k + B_k' lam_{k+1} must vanish, with the costates lam_N = Q_N dx_N + q_N, lam_k = Q_k dx_k + q_k + A_k' lam_{k+1}
+    // -- one backward pass in fp64 over the stage and cost blocks, which the condensed solve leaves untouched.  Lane c (0..15) forms row c
+    // of C~_k z~_k + M~_k' lam_{k+1}, z~_k = [dx_k; 1; 0; du_k]: rows 0..9 are lam_k, rows 12..15 g_k; the costates pass through the
+    // dump area ZD (nothing the sweep reads).  Returns max |g| over the largest term that enters g (R du, r, B' lam).
+    static NDP_D double cond_stationarity(const RtiParams &P, const LdsMap &m, lp lds)
+    {
+        const int N = horizon(P);
+        const vi c = W::lane_here() & 15;
+        const vb isu = c >= 12;
+        vd gmax = vd(0.0), tmax = vd(0.0);
+        for (int k = N; k >= 0; --k) {
+            vd rv = W::ld(lds, c_entry(m, c, vi(10)) + k * int(CB_STRIDE)), cz = vd(0.0), ml = vd(0.0);
+            for (int j = 0; j < NX; ++j)
+                cz = cz + W::ld(lds, c_entry(m, c, vi(j)) + k * int(CB_STRIDE)) * W::ld(lds, vi(m.ZX + k * NX + j));
+            if (k < N) {
+                for (int j = 0; j < NU; ++j)
+                    cz = cz + W::ld(lds, c_entry(m, c, vi(12 + j)) + k * int(CB_STRIDE)) * W::ld(lds, vi(m.ZU + k * NU + j));
+                for (int j = 0; j < NX; ++j)
+                    ml = ml + W::ld(lds, m_entry(m, vi(j), c) + k * int(MB_STRIDE)) * W::ld(lds, vi(m.ZD + j));
+                gmax = W::vmax(gmax, W::sel(isu, W::vabs(rv + cz + ml), vd(0.0)));
+                tmax = W::vmax(tmax, W::sel(isu, W::vmax(W::vabs(rv), W::vmax(W::vabs(cz), W::vabs(ml))), vd(0.0)));
+            }
+            W::sync();
+            W::stp(lds, vi(m.ZD) + c, rv + cz + ml, c < NX);
+            W::sync();
+        }
+        return W::wave_max(gmax) / fmax(W::wave_max(tmax), 1e-300);
+    }
     // The sweep's solution (ZX|ZU) against the set it was made with.  Returns 0: the set reproduces itself, every free input and every
     // velocity is inside its box (velocities by auto_margin) -- the QP is solved, pinned inputs are set onto their bounds; 1: the set
     // changed (A updated); 2: a velocity bound is violated or closer than auto_margin -- not this method's case.
@@ -2025,6 +2059,8 @@ struct RtiWave {
                         if (!pinned && sweeps == sweeps0) {       // the QP's first solve: condensed, fp32 / bf16 (a failed factorisation: the sweep)
                             condensed = W::template cond_solve<COND>(P, m, lds, N,
                                                                      [&](int r, int c) { return m_entry(m, r, c); }, [&](int r, int c) { return c_entry(m, r, c); });
+                            // ... and so is a result that is not the equality-constrained minimiser it claims to be (cond_stationarity)
+                            condensed = condensed && cond_stationarity(P, m, lds) <= COND_STAT_MAX;
                             ok = condensed;
                         }
                     }

@@ -14,6 +14,7 @@ import pytest
 
 from ndp_nmpc_qd_amd import synth
 from tests import ref_numpy as R
+from tests.kkt_certificate import certify_batch, worst
 
 pytestmark = pytest.mark.gpu
 
@@ -44,7 +45,8 @@ def test_mixed_workload_four_ticks_against_twin_and_interior_point(ndp, oracle):
     against the always-iterating oracle at tol 1e-11: u0 inside 1e-6 on EVERY instance (1.5e-7 measured).  At the oracle's default tol
     1e-8 the interior-point answer itself is 6e-5 .. 2e-4 away from its own converged (tol 1e-11) answer on one to three nearly
     degenerate instances of 1024 per tick: the device is never further from it than that converged answer is, and
-    inside the north star's 1e-5 on > 99.5 % of the instances.  No instance needs the interior-point loop; after the first tick most
+    inside the north star's 1e-5 on > 99.5 % of the instances.  The step satisfies its QP's KKT conditions to 1e-9 on EVERY instance
+    (tests/kkt_certificate.py).  No instance needs the interior-point loop; after the first tick most
     constrained instances take ONE sweep."""
     B = 1024
     eng = ndp.BatchedNMPC(B)
@@ -66,6 +68,8 @@ def test_mixed_workload_four_ticks_against_twin_and_interior_point(ndp, oracle):
         assert np.array_equal(sw, swo) and np.array_equal(act, acto)
         np.testing.assert_allclose(U, Uo, rtol=0, atol=1e-8)
         np.testing.assert_allclose(X, Xo, rtol=0, atol=1e-8)
+        cs = certify_batch(oracle, oracle.default_cfg(), b["x0"], b["xr"], b["ur"], None, Xp, Up, X, U)    # the QP's KKT conditions:
+        assert not any(c["flag"] for c in cs) and max(worst(c) for c in cs) <= 1e-9                         # EVERY instance
         ans = {}
         for cfg, name in ((tight, "tight"), (dflt, "dflt")):
             Xi, Ui = Xp.copy(), Up.copy()

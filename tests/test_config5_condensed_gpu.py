@@ -1,6 +1,6 @@
 """BASELINE configs[4] as worded -- "fp32 vs bf16 MFMA on the CONDENSED QP" -- the study modes qp_precision 5 / 6 (csrc/cond_qp.hpp):
 every QP's first solve in condensed form on v_mfma_f32_16x16x4_f32 / v_mfma_f32_16x16x16_bf16 with an fp32 Cholesky in LDS, kept when
-it passes the fp64 inside-the-box test, the fp64 Riccati path otherwise.  (VERDICT r5, row +: the study that had not been run.)
+it passes the fp64 inside-the-box and stationarity tests, the fp64 Riccati path otherwise.  (VERDICT r5, row +: the study that had not been run.)
 The reference does not condense (qp_solver_cond_N = N, nmpc_body_rate_ctl.py:79); the oracle here is the fp64 restatement at a tight
 tolerance, and the fp64 product engine on the same inputs."""
 import numpy as np
@@ -59,8 +59,9 @@ def test_condensed_modes_against_the_fp64_path(ndp, oracle, N, n_rti, B):
     if both.any():
         assert np.median(e6[both]) > np.median(e5)                                   # bf16 operands: worse than fp32 -- where the bf16
     assert np.isfinite(u6).all()                                                     # Hessian is positive definite at all (N = 40: never;
-    if N == 40:                                                                      # N = 20: a sixth of the instances, errors up to O(1))
-        assert not k6.any() and e6.max() < 1e-9
+    if N == 40:                                                                      # N = 20: a sixth of the instances, errors up to O(1)
+        assert not k6.any() and e6.max() < 1e-9                                      # -- those are not kept: their fp64 stationarity
+    assert e6.max() < 0.05, e6.max()                                                 # residual fails, rti_wave.hpp: cond_stationarity)
 
 
 def test_bounds_in_play_fall_back_to_the_fp64_path(ndp, oracle):

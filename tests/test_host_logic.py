@@ -327,3 +327,19 @@ def test_config4_exchange_world_size_3():
         p.join(timeout=60)
         assert p.exitcode == 0
     assert [r[0] for r in res] == [0, 1, 2] and all(r[1] for r in res)
+
+
+def test_weightless_pins_are_refused():
+    """ndp_create refuses (-2) an as_gamma that is not finite or below NDP_AS_GAMMA_FLOOR * max(dt * Rd) = 1e8 at the defaults, when the
+    active set is on: a weaker pin leaves the QP solved with the input free, yet writes it onto its bound with status 0
+    (tests/test_kkt_certificate.py: test_weightless_pins_are_rejected has the oracle twin's numbers).  Argument check: no device needed."""
+    import ndp_nmpc_qd_amd as ndp
+    for g in (float("nan"), float("inf"), 0.0, 1e-3, 1e6, 0.99e8):
+        with pytest.raises(ndp.NdpError, match=r"failed \(-2\).*as_gamma"):
+            ndp.BatchedNMPC(4, as_gamma=g)
+    with pytest.raises(ndp.NdpError, match=r"failed \(-2\).*as_gamma"):
+        ndp.BatchedNMPC(4, as_gamma=1.9e7, dt=0.02)           # the floor follows dt * Rd: 2e7 at dt = 0.02
+    if not _has_gpu():                                        # at or above the floor, or with the set off: past the argument checks
+        for kw in (dict(as_gamma=1e8), dict(as_gamma=2e7, dt=0.02), dict(as_iter_max=0, as_gamma=0.0)):
+            with pytest.raises(ndp.NdpError, match="no usable HIP device"):
+                ndp.BatchedNMPC(4, **kw)

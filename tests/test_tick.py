@@ -728,6 +728,91 @@ def test_remote_tick_with_the_exchange_one_period_ahead_equals_the_single_handle
     ex.close()
 
 
+def _ring_slot(step, np1, j):
+    """ndp_hip.hip: RingGeom::slot -- where list entry j lives (entries of one residue j mod step share a row of np1 nodes)."""
+    return (j % step) * 2 * np1 + (j // step) % np1
+
+
+def _begin_refused(step, ahead):
+    """ndp_xchg_tick_begin's -17 (with a list advance): `ahead` begins already outstanding when it is called."""
+    return step < 2 or (ahead == 1 and step < 3)
+
+
+def test_ring_aliasing_is_exactly_what_the_remote_begin_refuses():
+    """The reference list restated: the step on window n reads entries n, n + step, ..., n + step N; the begin of the window a periods
+    later writes entry n + a + step N.  Over step 1..6, N in {13, 20, 40} and one or two begins ahead of the step, that entry lands on a
+    node of window n exactly for the pairs ndp_xchg_tick_begin refuses (for every n, never for the others)."""
+    for N in (13, 20, 40):
+        np1 = N + 1
+        for step in range(1, 7):
+            ring = step * N + 1
+            for a in (1, 2):
+                hits = []
+                for n in range(3 * ring):
+                    window = {_ring_slot(step, np1, n + step * k) for k in range(np1)}
+                    assert len(window) == np1                        # the ring holds a window without collisions
+                    hits.append(_ring_slot(step, np1, n + a + step * N) in window)
+                assert all(hits) if _begin_refused(step, a - 1) else not any(hits), (N, step, a)
+
+
+@pytest.mark.gpu
+def test_remote_tick_at_two_list_entries_per_node_refuses_the_second_begin_ahead():
+    """dt = 2 ts_nmpc: the window is every second entry of the reference list.  A second begin ahead (the three-buffer form) would write
+    the entry n + 2N + 2, which RingGeom::slot puts on a node of window n that the step before it may still be reading: refused (-17,
+    tests/test_kkt_certificate.py restates the ring and shows that exactly the refused pairs alias).  The two-buffer form is bit-equal
+    with the one-launch tick of one handle over 10 ticks."""
+    import torch
+    import ndp_nmpc_qd_amd as ndp
+    from ndp_nmpc_qd_amd import dist as ndist
+    dev = torch.device("cuda", 0)
+    B, n = 64, 10
+    tr = synth.figure_eight_traj(B, seed=12, n_seg=16, t_seg=0.25, pairs=True)
+    oi = (np.arange(B) ^ 1).astype(np.int32)
+
+    def make():
+        e = ndp.BatchedNMPC(B, disturbance=True, dt=2 * CP.ts_nmpc)
+        e.ref_set_trajectory(*(tr[k] for k in ("coeff_x", "coeff_y", "coeff_z", "coeff_yaw", "time_cum", "time_seg", "final_pt")))
+        e.ref_list_reset()
+        e.throttle_reset()
+        return e
+    one, rem = make(), make()
+    one.tick_config(oi, gate=True)
+    one.tick_reset()
+    gathered = [torch.zeros(B, 21, 6, dtype=torch.float64, device=dev) for _ in range(3)]
+    rem.tick_config_remote(gathered[0], oi, gate=True)
+    rem.tick_reset()
+    try:
+        ex = ndist.RcclExchange(B, 20, 0)
+    except RuntimeError as e:
+        pytest.skip(f"RCCL could not be bound: {e}")
+    stream = torch.cuda.Stream(device=dev)
+    cmd1, u1 = torch.empty(B, 4, dtype=torch.float64, device=dev), torch.empty(B, 4, dtype=torch.float64, device=dev)
+    cmd2 = [torch.empty(B, 4, dtype=torch.float64, device=dev) for _ in range(n)]
+    u2 = [torch.empty(B, 4, dtype=torch.float64, device=dev) for _ in range(n)]
+    rng = np.random.default_rng(7)
+    xs, ref1 = [], []
+    for i in range(n):
+        xr, _ = one.ref_list_window(None)
+        x0 = xr[:, 1, :].copy()
+        x0[:, 0:3] += rng.normal(0.0, 0.03, size=(B, 3))
+        xs.append(torch.from_numpy(x0).to(dev))
+        one.tick_device(xs[i], cmd1, t=CP.ts_nmpc * (i + 1), estimate=True, u0_out=u1)
+        torch.cuda.synchronize()
+        ref1.append((cmd1.clone(), u1.clone()))
+    ex.tick_begin(rem, gathered[0], t=CP.ts_nmpc)
+    with pytest.raises(RuntimeError, match=r"failed \(-17\).*second begin ahead"):
+        ex.tick_begin(rem, gathered[1], t=2 * CP.ts_nmpc)
+    for i in range(n):                         # the two-buffer form: one begin ahead
+        ex.tick_step(rem, xs[i], cmd2[i], gathered[i % 2], stream, estimate=True, u0_out=u2[i])
+        if i + 1 < n:
+            ex.tick_begin(rem, gathered[(i + 1) % 2], t=CP.ts_nmpc * (i + 2))
+    torch.cuda.synchronize()
+    for i in range(n):
+        assert torch.equal(cmd2[i], ref1[i][0]) and torch.equal(u2[i], ref1[i][1]), i
+    assert np.array_equal(rem.throttle_state(), one.throttle_state())
+    ex.close()
+
+
 @pytest.mark.gpu
 def test_tick_with_inputs_on_their_bounds_one_launch_equals_three_stages():
     """Large odometry errors (1 m, 2 m/s): a third of the vehicles have inputs on their bounds, kept sets grow and shrink from tick to tick.
