@@ -279,6 +279,26 @@ int ndp_synchronize(ndp_handle *h);
 int ndp_refine_active(ndp_handle *h);        /* 1: cfg.ipm_refine > 0 and this handle's control steps carry the refinement path (see ndp_cfg.ipm_refine); 0: ignored */
 int ndp_work_queue_enabled(ndp_handle *h);   /* 1 if the handle's NEXT step runs the interior-point work list (cfg.work_queue; the automatic rule's current state) */
 
+/* Initial-state sensitivities (acados: eval_param_sens + get(stage, "sens_u" / "sens_x") with respect to x0).  The derivative of the
+ * QP each step solves with respect to x0 -- linearisation point, xr, ur and the force held fixed -- column j = d / dx0[j]:
+ *   - QP finished by the active set or the equality-constrained early exit: with the final set held fixed (exact: the solution is
+ *     piecewise affine in x0); the rows of pinned inputs are exactly 0;
+ *   - QP finished by the interior-point loop (ipm_iters > 0): the derivative of its last Newton system (barrier-smoothed, HPIPM's meaning);
+ *   - an instance with a nonzero status: NaN in all of its outputs.
+ * ndp_sens_enable: level 1 writes du0/dx0 [B][4][10] (the stage-0 gain of the last Riccati sweep); level 2 also runs a forward sweep with
+ * the 10-column right-hand side [I ; 0] and writes dU/dx0 [B][N][4][10] and dX/dx0 [B][N+1][10][10] (stage 0: the identity); 0 frees the
+ * buffers.  Served for N <= 27, qp_precision 0, n_rti = 1 (else -2 and ndp_last_error says why).  Every later in-place or work-list step
+ * (ndp_step*, ndp_step_begin / _end, ndp_step_device*, a graph captured around them) writes them; a captured graph keeps the form it was
+ * captured with.  With sensitivities on, ndp_step_device_prefetched, ndp_tick*, ndp_xchg_tick* and ndp_rollout_device return -2.
+ * ndp_get_sens: waits for the handle's work and copies; any pointer may be NULL; dU / dX on a level-1 handle: -2.
+ * ndp_device_sens_*: the device buffers (NULL when not allocated at the current level). */
+int ndp_sens_enable(ndp_handle *h, int level);
+int ndp_sens_level(ndp_handle *h);
+int ndp_get_sens(ndp_handle *h, double *du0_dx0, double *dU_dx0, double *dX_dx0);
+void *ndp_device_sens_u0(ndp_handle *h);
+void *ndp_device_sens_u(ndp_handle *h);
+void *ndp_device_sens_x(ndp_handle *h);
+
 /* Per-kernel timing with HIP events recorded on the stream each kernel is launched on:
  * on = n > 0 brackets every n-th launch of each kernel (n = 1: every launch), on = 0 stops and clears.
  * ndp_timing_read: name is "rti" or "mlp"; total over the bracketed launches.  Returns <0 if nothing was timed. */

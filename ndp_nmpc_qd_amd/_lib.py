@@ -53,6 +53,7 @@ EXPORTS = [
     "ndp_abi_version", "ndp_cfg_size",
     "ndp_step_ex_f64", "ndp_refine_active", "ndp_get_active_set", "ndp_set_active_set", "ndp_debug_host_info", "ndp_tick_config", "ndp_tick_reset", "ndp_tick_begin", "ndp_tick_end", "ndp_tick", "ndp_tick_device",
     "ndp_tick_config_remote", "ndp_tick_advance_device", "ndp_tick_window_pv_device", "ndp_tick_step_device", "ndp_xchg_tick_windows", "ndp_xchg_tick_begin", "ndp_xchg_tick_step", "ndp_xchg_tick_async",
+    "ndp_sens_enable", "ndp_sens_level", "ndp_get_sens", "ndp_device_sens_u0", "ndp_device_sens_u", "ndp_device_sens_x",
 ]
 
 _lib = None
@@ -123,6 +124,12 @@ def load():
     lib.ndp_xchg_tick_async.argtypes = [vp, C.c_int]
     lib.ndp_xchg_tick_step.argtypes = [vp] * 5 + [C.c_int] + [vp] * 4
     lib.ndp_get_active_set.argtypes = [vp] * 3
+    lib.ndp_sens_enable.argtypes = [vp, C.c_int]
+    lib.ndp_sens_level.argtypes = [vp]
+    lib.ndp_get_sens.argtypes = [vp] * 4
+    for name in ("ndp_device_sens_u0", "ndp_device_sens_u", "ndp_device_sens_x"):
+        getattr(lib, name).argtypes = [vp]
+        getattr(lib, name).restype = vp
     lib.ndp_set_active_set.argtypes = [vp] * 2
     lib.ndp_debug_host_info.argtypes = [vp, vp]
     lib.ndp_ref_list_reset.argtypes = [vp]

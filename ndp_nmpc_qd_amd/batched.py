@@ -426,6 +426,44 @@ class BatchedNMPC:
         self._check(self._lib.ndp_get_active_set(self._h, _lib.ptr(sw), None), "ndp_get_active_set")
         return (sw >> 12) & 0xf
 
+    # ------------------------------------------------------------------ initial-state sensitivities
+    def enable_sensitivity(self, level=1):
+        """Every later step also writes the derivative of its QP with respect to x0 (ndp_sens_enable; include/ndp_nmpc.h): level 1
+        du0/dx0, level 2 also dU/dx0 and dX/dx0, 0 off.  N <= 27, qp_precision 0 and n_rti = 1 only; with sensitivities on, the
+        tick, late-force and rollout entry points raise."""
+        self._check(self._lib.ndp_sens_enable(self._h, int(level)), "ndp_sens_enable")
+
+    @property
+    def sensitivity_level(self):
+        return int(self._lib.ndp_sens_level(self._h))
+
+    def sensitivity(self):
+        """(du0_dx0 [B,4,10], dU_dx0 [B,N,4,10], dX_dx0 [B,N+1,10,10]) of the last step, numpy float64; the last two are None at level 1.
+        Column j = d / dx0[j]; rows of pinned inputs are 0; an instance with a nonzero status is NaN throughout."""
+        lvl = self.sensitivity_level
+        if lvl < 1:
+            raise NdpError("sensitivities are not enabled (enable_sensitivity)")
+        du0 = np.empty((self.B, 4, 10))
+        dU = np.empty((self.B, self.N, 4, 10)) if lvl >= 2 else None
+        dX = np.empty((self.B, self.N + 1, 10, 10)) if lvl >= 2 else None
+        self._check(self._lib.ndp_get_sens(self._h, _lib.ptr(du0), _lib.ptr(dU), _lib.ptr(dX)), "ndp_get_sens")
+        return du0, dU, dX
+
+    def device_sensitivity(self):
+        """The device buffers as CUDA tensor views (no copy): (du0_dx0 [B,4,10], dU_dx0 [B,N,4,10] or None, dX_dx0 [B,N+1,10,10] or
+        None), float64.  Valid once the step's stream has reached them; the next step overwrites them."""
+        import torch
+        from .dist import _DevMem
+        if self.sensitivity_level < 1:
+            raise NdpError("sensitivities are not enabled (enable_sensitivity)")
+        dev = torch.device("cuda", self.cfg.device)
+        out = []
+        for fn, shape in ((self._lib.ndp_device_sens_u0, (self.B, 4, 10)), (self._lib.ndp_device_sens_u, (self.B, self.N, 4, 10)),
+                          (self._lib.ndp_device_sens_x, (self.B, self.N + 1, 10, 10))):
+            ptr = fn(self._h)
+            out.append(torch.as_tensor(_DevMem(ptr, shape), device=dev) if ptr else None)
+        return tuple(out)
+
     # ------------------------------------------------------------------ HBM-resident API (torch CUDA tensors)
     @staticmethod
     def _dptr(t, dtype, shape):

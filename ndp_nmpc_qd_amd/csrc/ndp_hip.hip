@@ -259,6 +259,11 @@ struct KernArgs {
     LateArgs la;
     TickArgs ta;            // read by the TICK instantiations only
 };
+// rti_sens_kernel's outputs (ndp_sens_enable): [B][4][10] always, [B][N][4][10] and [B][N+1][10][10] at level 2 (else null)
+struct SensArgs {
+    double *du0 = nullptr, *dU = nullptr, *dX = nullptr;
+    int level = 0;
+};
 
 // Arguments a kernel needs LATE (the tick's estimator constants, the list's geometry for the new entry's store, the trajectory arrays
 // of the rare slow path), fetched where they are used.  Read as ordinary members of `ka` the compiler requests every argument at the
@@ -302,245 +307,27 @@ template <class T> using gptr = __attribute__((address_space(1))) T *;
 #endif
 // TICK: the launch is a whole control tick of ndp_tick (see TickArgs): the wave makes its window's newest node -- and its neighbour's --
 // itself and runs the estimator; instantiated for the reference configuration's in-place and producer forms only.
+// The control step's statements are shared by rti_kernel and rti_sens_kernel through rti_kernel_body.inc (see there).
 template <int NSLOT, int WAVES, bool FUSED, int NC = 0, int PREC = 0, int NRC = (NC ? 1 : 0), int QMODE = 0, bool TICK = false>
 __global__ __launch_bounds__(64 * WAVES) NDP_RTI_ATTR void rti_kernel(KernArgs ka)
 {
-    static_assert(!(FUSED && QMODE == 2), "the consumer reads the force the producer left in global memory");
-    static_assert(!TICK || (QMODE <= 1 && NC > 0 && PREC == 0), "the one-launch tick exists for the compile-time horizon's in-place and producer forms");
+    constexpr bool SENS = false;
+    const SensArgs sa{};
     extern __shared__ __attribute__((aligned(16))) double smem[];
-#ifndef NDP_NO_KERNARG_WARM
-    {   // The argument block is ~1.2 KB = 19 scalar-cache lines, and the compiler fetches each field next to its first use, waiting for it
-        // there: every first touch of a line is a memory round trip of its own, one behind the other through the whole prologue.
-        // One dword of every line, requested together at the very top: one round trip, the later fetches hit the scalar cache.
-        typedef const __attribute__((address_space(4))) unsigned *kptr;
-        kptr kp = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
-        unsigned acc = 0;
-#pragma unroll
-        for (unsigned o = 0; o < (unsigned)sizeof(KernArgs); o += 64) acc |= kp[o / 4];
-        asm volatile("" : : "s"(acc));
-    }
-#endif
-    const RtiParams &P = ka.P;
-    const BatchPtrs &bp = ka.bp;
-    const MlpArgs &ma = ka.ma;
-    const QueueArgs &qa = ka.qa;
-    const int B = ka.B;
-    const int wave = (int)(threadIdx.x >> 6);
     __shared__ unsigned wg_done;     // prefetched-force launches: the workgroup's waves that hold their force values (see LateArgs)
-    if (!FUSED && (QMODE == 0 || QMODE == 3) && ka.la.proto) {
-        if (threadIdx.x == 0) wg_done = 0;
-        __syncthreads();             // (before any wave of a ragged last workgroup leaves)
-    }
-    int inst_raw = __builtin_amdgcn_readfirstlane((int)blockIdx.x * WAVES + wave);
-    if (QMODE == 2) {         // list entry -> instance; past the end of the list: nothing to do
-        const int n = (int)*qa.count;
-        if (inst_raw >= n) return;
-        inst_raw = __builtin_amdgcn_readfirstlane(qa.ids[inst_raw]);
-    }
-    const bool active = inst_raw < B;
-    if (!FUSED && !active) return;
-    const int inst = active ? inst_raw : B - 1;   // fused: idle waves of the last workgroup still take part in the barriers
-    const int N = NC ? NC : P.N;
-    const size_t nf = (size_t)(N + 1) * 3;
-    RtiIo io;
-    bind_instance(io, bp, inst, N);
-    if (NSLOT <= 3 && (QMODE == 0 || QMODE == 3)) io.ipm_ctr = qa.ipm_total;
-    if (NSLOT <= 3 && QMODE != 2 && blockIdx.x == 0 && threadIdx.x == 0 && qa.ipm_total)
-        __hip_atomic_fetch_add(qa.ipm_total + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (!FUSED && (QMODE == 0 || QMODE == 3) && ka.la.proto) {
-        // this launch is control step number t; its force was written into slot t & 1 by downwash launch t
-        const LateArgs &la = ka.la;
-        const unsigned long long t = la.proto[PF_RTI_C2] / la.groups_rti + 1;       // (plain load: see LateArgs)
-        const unsigned g = blockIdx.x % la.groups_rti;
-        const unsigned np1 = (unsigned)N + 1, row0 = (unsigned)inst * np1;
-        io.f_late = la.F[t & 1] + (size_t)inst * nf;
-        io.late_flag = la.proto + PF_EPOCH + (t & 1) * la.ntiles + row0 / 32;
-        io.late_flag2 = la.proto + PF_EPOCH + (t & 1) * la.ntiles + (row0 + np1 - 1) / 32;
-        io.late_want = t;
-        io.late_ready = la.proto[PF_MLP_DONE] >= t ? 1 : 0;                         // (plain load)
-        io.late_timeout_us = la.timeout_us;
-        io.late_missed = reinterpret_cast<int *>(la.proto + PF_MISSED);
-        io.late_slow = reinterpret_cast<int *>(la.proto + PF_SLOW);
-        io.late_cnt = reinterpret_cast<unsigned *>(la.proto + PF_RTI_C1 + PF_STRIDE * g);
-        io.late_done_word = la.proto + PF_RTI_C2;
-        io.late_gsize = pf_group_size(gridDim.x, la.groups_rti, g);
-        // (LDS offset + 1: the word may well sit at offset 0, and null means "no workgroup-level counter")
-        io.late_group = (void *)((size_t)(unsigned)(size_t)(__attribute__((address_space(3))) unsigned *)&wg_done + 1);
-        const int left = B - (int)blockIdx.x * WAVES;
-        io.late_group_size = (unsigned)(left < WAVES ? left : WAVES);
-    }
-    const int lpw = NC ? ((lds_doubles(NC) + 1) & ~1) : ka.lds_per_wave;
-    WaveGfx950::lds_ptr lds = (WaveGfx950::lds_ptr)(smem + (size_t)wave * lpw);
-    // PREC 0: the product path (f64 matrix instruction); 1 / 2: operand-rounding studies on it; 3 / 4: the sweeps on the real
-    // fp32 / bf16-input matrix instructions (BASELINE config 5)
-    using WB = std::conditional_t<PREC == 3, WaveGfx950F32, std::conditional_t<PREC == 4, WaveGfx950BF16, WaveGfx950>>;
-    // PREC 5 / 6: config 5's CONDENSED study (cond_qp.hpp) -- the f64 program with every QP's first solve in condensed form on the fp32 / bf16 instructions
-    using Prog = RtiWave<WB, NSLOT, NC, true, NRC, (PREC >= 3 ? 0 : PREC), QMODE == 3, (PREC == 5 ? 1 : (PREC == 6 ? 2 : 0))>;   // compile-time horizon and iteration count (NC = 0: both at run time)
-    if (NDP_RARELY(io.stamps && (threadIdx.x & 63u) == 0)) {    // profiling hook: real time (100 MHz) and shader clock at entry -> the clock the launch ran at
-        io.stamps[12] = (double)__builtin_amdgcn_s_memrealtime();
-        io.stamps[14] = (double)__builtin_amdgcn_s_memtime();
-    }
-    // fused, neighbour rows picked through other_index: the row number is the head of a dependent load chain (index -> window
-    // address -> window loads).  Fetch it before anything else is in the wave's in-order load queue and consume it here, so
-    // that the one unavoidable wait covers one load, not the seventeen input loads requested next.
-    // wg_nb: does ANY instance of this workgroup have a neighbour?  (Four scalar loads of the workgroup's own index entries, the
-    // same in every wave: no barrier.)  A workgroup of plain NMPC followers -- a rank's local order puts them behind its leaders,
-    // dist.config4_gids -- then skips the 70 KB weight transfer, both barriers and the network's input loads altogether.
-    int orow = inst;
-    bool wg_nb = true;
-    if (FUSED && ma.other_index) {
-        int any = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) {
-            const int iw = (int)blockIdx.x * WAVES + w;
-            any |= (ma.other_index[iw < B ? iw : B - 1] >= 0) ? 1 : 0;
-        }
-        orow = __builtin_amdgcn_readfirstlane(ma.other_index[inst]);
-        asm volatile("" : : "s"(orow));
-        wg_nb = __builtin_amdgcn_readfirstlane(any) != 0;
-    }
-    const bool advance = TICK && ka.ta.advance != 0;
-    TickEarly te;                            // (left as it is without `advance`: nothing looks at it then)
-    if (TICK && NDP_RARELY(io.stamps && (threadIdx.x & 63u) == 0)) io.stamps[16] = (double)__builtin_amdgcn_s_memtime();   // neighbour index known
-    if (TICK && advance) {
-        te = tick_early(ka.ta, inst, FUSED && wg_nb ? orow : -1, (int)(threadIdx.x & 63u));
-        __builtin_amdgcn_sched_barrier(0);   // (these two loads lead the wave's in-order load queue)
-    }
-    if (TICK && NDP_RARELY(io.stamps && (threadIdx.x & 63u) == 0)) io.stamps[22] = (double)__builtin_amdgcn_s_memtime();   // cache loads issued
-    typename Prog::InBuf inb;
-    double x0v;
-    Prog::issue_first(P, io, inb, x0v);      // every global input of the RTI step is now in flight (hidden under the MLP when fused)
-    __builtin_amdgcn_sched_barrier(0);       // do not let the scheduler sink those loads behind the MLP
-    if (TICK && NDP_RARELY(io.stamps && (threadIdx.x & 63u) == 0)) io.stamps[23] = (double)__builtin_amdgcn_s_memtime();   // input loads issued
-    // TICK: the newest list entry of this vehicle (x_new / u_new) and the position / velocity part of the neighbour's (nb_new).  Row N of
-    // both windows is NOT read from the list in this launch (the neighbour's wave writes its entry while this one runs): the ego's goes
-    // into the staged window through RtiIo::xrN, the pair into the network's input below.
-    double x_new[10], u_new[4], nb_new[6], seg_fill = 0.0, seg_cfill = 0.0;
-    int seg_refill = 0;
-    if (TICK && !(FUSED && wg_nb) && advance) {      // (fused with neighbours: made below, under the weight transfer)
-        tick_arrived(te);
-        seg_fill = tick_new_point(ka.ta, te, inst, (int)(threadIdx.x & 63u), active, x_new, u_new, nb_new, seg_refill, seg_cfill, io.stamps);
-#pragma unroll
-        for (int i = 0; i < 10; ++i) io.xrN[i] = x_new[i];
-        io.have_xrN = 1;
-    }
-    if (FUSED && !wg_nb) {          // no instance of the workgroup has a neighbour: zero force, nothing of the network runs
-        if (!active) return;
-        const int lane = (int)(threadIdx.x & 63u);
-        const LdsMap m = make_map(N);
-        if (lane < 3 * (N + 1)) {
-            lds[m.TF + lane] = 0.0;
-            ma.force_out[inst * nf + lane] = 0.0f;
-        }
-        if (3 * (N + 1) > 64 && lane + 64 < 3 * (N + 1)) {
-            lds[m.TF + lane + 64] = 0.0;
-            ma.force_out[inst * nf + lane + 64] = 0.0f;
-        }
-        WaveGfx950::sync();
-        io.f = nullptr;
-        io.f_in_lds = 1;
-    } else if (FUSED) {
-        const int lane = (int)(threadIdx.x & 63u), j = lane & 31, h = lane >> 5;
-        const int np1 = N + 1;
-        const int st = ma.other_stride;
-        const double *oth = ma.other + (size_t)(orow < 0 ? 0 : orow) * ma.other_pitch;
-        // the gate's four numbers are only REQUESTED here; the comparison comes after the barrier (consuming them here would
-        // park the wave on the whole in-order load queue -- s_waitcnt vmcnt(0) -- before the weight transfer is even issued)
-        const double *exy = ma.ego_xy ? ma.ego_xy + (size_t)inst * ma.ego_pitch : oth;
-        const int osys = ma.other_sys;
-        const double g_ox = ld_other(oth, osys), g_oy = ld_other(oth + 1, osys), g_ex = exy[0], g_ey = exy[1];
-        const int jr = j < np1 ? j : np1 - 1;
-        float zb[3], o[3];
-        // Network input (downwash_nn.py:22-23): columns 0..5 of (other - ego reference), rows 0..N, subtracted in fp64.  Lane
-        // (j, h) of the tile wants row j, columns 2s + h -- read that way it is an 8-byte load at an 80-byte lane stride (ten
-        // cache lines per quarter wave, six instructions).  Instead ONE 16-byte load per array covers a row's six columns with
-        // three adjacent lanes (lane l: row l / 3, columns 2 (l % 3), 2 (l % 3) + 1: 63 lanes for N = 20), and the tile's
-        // layout is made by a cross-lane gather of the fp32 differences (ds_bpermute: the LDS crossbar, no LDS storage).
-        typedef double d2_t __attribute__((ext_vector_type(2)));
-        constexpr int ZR = NC ? (3 * (NC + 1) + 63) / 64 : 2;      // load rounds: 3 (N+1) lanes, N + 1 <= 32
-        d2_t dv[ZR], ev[ZR];
-#pragma unroll
-        for (int t = 0; t < ZR; ++t) {
-            const int l3 = lane + 64 * t, r3 = l3 / 3, c3 = l3 - 3 * r3, rc = r3 < np1 ? r3 : np1 - 1;
-            dv[t] = ld_other2(oth + (size_t)rc * st + 2 * c3, osys);
-            ev[t] = *(const d2_t *)(io.xr + (size_t)rc * NX + 2 * c3);
-        }
-        const LdsMap m = make_map(N);
-        if (NDP_RARELY(io.dbg && lane == 0)) io.dbg[m.total + 9] = (double)__builtin_amdgcn_s_memtime();
-        if (NDP_RARELY(io.stamps && lane == 0)) io.stamps[9] = (double)__builtin_amdgcn_s_memtime();
-        // the whole workgroup's LDS is still unused: park the weight fragments there for the MLP phase
-        lds_f32 wl = (lds_f32)smem;
-        if (TICK) tick_arrived(te);               // (see there: the one wait of the prologue, in FRONT of the weight transfer; not under
-                                                  // `advance`: a path around it leaves the values pending in the compiler's books)
-        stage_fragments(ma.frag, wl, (int)threadIdx.x, 64 * WAVES);
-        if (TICK && advance) {                    // the polynomial work runs while the weights stream into LDS
-            seg_fill = tick_new_point(ka.ta, te, inst, lane, active, x_new, u_new, nb_new, seg_refill, seg_cfill, io.stamps);
-#pragma unroll
-            for (int i = 0; i < 10; ++i) io.xrN[i] = x_new[i];
-            io.have_xrN = 1;
-#pragma unroll
-            for (int t = 0; t < ZR; ++t) {        // row N of the network's input: the two new entries (downwash_nn.py:22: columns 0..5)
-                const int l3 = lane + 64 * t, r3 = l3 / 3, c3 = l3 - 3 * r3;
-                if (r3 == N) {
-                    dv[t][0] = c3 == 0 ? nb_new[0] : (c3 == 1 ? nb_new[2] : nb_new[4]);
-                    dv[t][1] = c3 == 0 ? nb_new[1] : (c3 == 1 ? nb_new[3] : nb_new[5]);
-                    ev[t][0] = c3 == 0 ? x_new[0] : (c3 == 1 ? x_new[2] : x_new[4]);
-                    ev[t][1] = c3 == 0 ? x_new[1] : (c3 == 1 ? x_new[3] : x_new[5]);
-                }
-            }
-        }
-        __syncthreads();
-        const double g_o[2] = {g_ox, g_oy}, g_e[2] = {g_ex, g_ey};
-        const bool open = orow >= 0 && (ma.ego_xy ? gate_open(g_o, g_e, ma.r2) : true);
-        {
-            float fx[ZR], fy[ZR];
-#pragma unroll
-            for (int t = 0; t < ZR; ++t) { fx[t] = (float)(dv[t][0] - ev[t][0]); fy[t] = (float)(dv[t][1] - ev[t][1]); }
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                const int src = 3 * jr + s, sl = (src & 63) << 2;
-                float vx = __int_as_float(__builtin_amdgcn_ds_bpermute(sl, __float_as_int(fx[0])));
-                float vy = __int_as_float(__builtin_amdgcn_ds_bpermute(sl, __float_as_int(fy[0])));
-                if (ZR > 1) {
-                    const float wx = __int_as_float(__builtin_amdgcn_ds_bpermute(sl, __float_as_int(fx[ZR - 1])));
-                    const float wy = __int_as_float(__builtin_amdgcn_ds_bpermute(sl, __float_as_int(fy[ZR - 1])));
-                    if (src >= 64) { vx = wx; vy = wy; }
-                }
-                zb[s] = h ? vy : vx;
-            }
-        }
-        if (NDP_RARELY(io.stamps && lane == 0)) io.stamps[11] = (double)__builtin_amdgcn_s_memtime();
-        // gate closed (or no neighbour): the force is zero and the reference does not evaluate the network either
-        // (ndp_nmpc_leader_node.py:66-76).  The test is the same in every lane: a wave-uniform branch around the tile.
-        o[0] = o[1] = o[2] = 0.0f;
-        if (__builtin_amdgcn_readfirstlane((int)open)) mlp_tile(wl, zb, lane, o);
-        __syncthreads();                              // every wave is done with the weights before LDS becomes RTI state
-        if (!active) return;
-        if (NDP_RARELY(io.dbg && lane == 0)) io.dbg[m.total + 10] = (double)__builtin_amdgcn_s_memtime();
-        if (NDP_RARELY(io.stamps && lane == 0)) io.stamps[10] = (double)__builtin_amdgcn_s_memtime();
-        if (j < np1 && h == 0) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float v = open ? o[c] : 0.0f;      // ndp_nmpc_leader_node.py:75-76
-                lds[m.TF + j * 3 + c] = (double)v;       // fp32 value promoted to fp64
-                ma.force_out[inst * nf + j * 3 + c] = v; // also what the consumer launch of the work list reads
-            }
-        }
-        WaveGfx950::sync();
-        io.f = nullptr;
-        io.f_in_lds = 1;
-    }
-    if (TICK && advance && active) tick_cache_store(ka.ta, te, inst, (int)(threadIdx.x & 63u), seg_refill, seg_fill, seg_cfill);   // (requested in the prologue: long there)
-    if (TICK && ka.ta.est && active) io.kthr = tick_estimator(ka.ta, inst, B, (int)(threadIdx.x & 63u));
-    const bool deferred = Prog::template run<QMODE == 1, QMODE == 0 || QMODE == 3>(P, io, lds, inb, x0v);
-    if (NDP_RARELY(io.stamps && (threadIdx.x & 63u) == 0)) {
-        io.stamps[13] = (double)__builtin_amdgcn_s_memrealtime();
-        io.stamps[15] = (double)__builtin_amdgcn_s_memtime();
-    }
-    if (QMODE == 1 && deferred && (threadIdx.x & 63u) == 0) {
-        const unsigned s = __hip_atomic_fetch_add(qa.count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        qa.ids[s] = inst;
-    }
+#include "rti_kernel_body.inc"
+}
+
+// The control step with its initial-state sensitivities (ndp_sens_enable): three-slot shapes (N <= 27), qp_precision 0, one RTI iteration,
+// in place or the work list's producer / consumer; the level (1 or 2) is a run-time uniform of SensArgs.
+template <int WAVES, bool FUSED, int NC, int QMODE>
+__global__ __launch_bounds__(64 * WAVES) void rti_sens_kernel(KernArgs ka, SensArgs sa)
+{
+    constexpr int NSLOT = 3, PREC = 0, NRC = NC ? 1 : 0;
+    constexpr bool TICK = false, SENS = true;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    __shared__ unsigned wg_done;
+#include "rti_kernel_body.inc"
 }
 
 // test hook: one v_mfma_f64_16x16x4_f64 / v_mfma_f64_4x4x4_4b_f64 with caller-chosen per-lane operands (pins the register maps)
@@ -1987,11 +1774,17 @@ template <int NSLOT, int WAVES, bool FUSED, int NC = 0, int PREC = 0, int NRC = 
 #endif
 struct RtiK { static constexpr auto fn = rti_kernel<3, (WAVES == 2 && NC == 20 ? 2 : 4), (FUSED && NC == 20 && QMODE == 0), 20, 0, 1, NDP_DEV_QMODE, (TICK && NC == 20 && QMODE == 0)>; };
 #define RTI_K(...) (RtiK<__VA_ARGS__>::fn)
+template <int WAVES, bool FUSED, int NC, int QMODE>
+struct RtiSensK { static constexpr auto fn = rti_sens_kernel<4, (FUSED && NC == 20 && QMODE == 0), 20, NDP_DEV_QMODE>; };
+#define RTI_SENS_K(...) (RtiSensK<__VA_ARGS__>::fn)
 #elif defined(NDP_DEV_COND_ONLY)
 // compile / register studies of the condensed study kernels: every instantiation collapses onto rti_kernel<5, 1, false, 0, 5 or 6>
 template <int NSLOT, int WAVES, bool FUSED, int NC = 0, int PREC = 0, int NRC = (NC ? 1 : 0), int QMODE = 0, bool TICK = false>
 struct RtiK { static constexpr auto fn = rti_kernel<5, 1, false, 0, (PREC == 6 ? 6 : 5)>; };
 #define RTI_K(...) (RtiK<__VA_ARGS__>::fn)
+template <int WAVES, bool FUSED, int NC, int QMODE>       // (and the sensitivity kernels onto one)
+struct RtiSensK { static constexpr auto fn = rti_sens_kernel<4, false, 20, 0>; };
+#define RTI_SENS_K(...) (RtiSensK<__VA_ARGS__>::fn)
 #elif defined(NDP_DEV_N40_ONLY)
 // register studies of config 5's shape (scripts/dev_regs.sh): every instantiation collapses onto rti_kernel<5, 2, false, 40, 0, 2, NDP_DEV_QMODE>
 #ifndef NDP_DEV_QMODE
@@ -2000,8 +1793,13 @@ struct RtiK { static constexpr auto fn = rti_kernel<5, 1, false, 0, (PREC == 6 ?
 template <int NSLOT, int WAVES, bool FUSED, int NC = 0, int PREC = 0, int NRC = (NC ? 1 : 0), int QMODE = 0, bool TICK = false>
 struct RtiK { static constexpr auto fn = rti_kernel<5, 2, false, 40, 0, 2, NDP_DEV_QMODE>; };
 #define RTI_K(...) (RtiK<__VA_ARGS__>::fn)
+template <int WAVES, bool FUSED, int NC, int QMODE>       // (and the sensitivity kernels onto one)
+struct RtiSensK { static constexpr auto fn = rti_sens_kernel<4, false, 20, 0>; };
+#define RTI_SENS_K(...) (RtiSensK<__VA_ARGS__>::fn)
 #else
 #define RTI_K(...) (rti_kernel<__VA_ARGS__>)
+// RTI_SENS_K(WAVES, FUSED, NC, QMODE): the rti_sens_kernel instantiation to reference (collapsed like RTI_K in development builds)
+#define RTI_SENS_K(...) (rti_sens_kernel<__VA_ARGS__>)
 #endif
 
 // ---- host pack threads.  A host-array step first moves the caller's (pageable) arrays into a page-locked mirror the kernel can
@@ -2121,6 +1919,9 @@ struct ndp_handle {
     double *dKC = nullptr;     // constants block of the LDS image (fill_kc)
     int *dTables = nullptr;    // per-lane index tables of the Riccati sweep (fill_tables)
     signed char *dAct = nullptr;   // [B][act_pitch(N)] QP_AUTO's active sets, kept between control steps (RtiIo::act); emptied by reset / set_iterate
+    // ndp_sens_enable: initial-state sensitivities of every step's QP (rti_sens_kernel): level 0 off, 1 du0/dx0, 2 also dU/dx0 and dX/dx0
+    int sens_level = 0;
+    double *dSensU0 = nullptr, *dSensU = nullptr, *dSensX = nullptr;   // [B][4][10], [B][N][4][10], [B][N+1][10][10] (the last two: level 2)
     double *dThr = nullptr;    // hover-throttle estimator state, SoA [8][B]
     double *dStamps = nullptr; // [B][NDP_NSTAMP] whole-batch phase stamps (ndp_debug_stamps)
     double *dTraj = nullptr;   // f1: [B][n_seg][28] coeff | [B][n_seg+1] time_cum | [B][n_seg] time_seg | [B][3] final_pt | [B][64] segment cache | int[B] segment hints
@@ -2232,6 +2033,14 @@ static size_t act_bytes(const ndp_handle *h) { return (size_t)h->cfg.batch * (si
 static void copy_ipm_iters(int32_t *dst, const int32_t *src, size_t n)
 {
     for (size_t i = 0; i < n; ++i) dst[i] = src[i] & ITERS_IPM_MASK;
+}
+
+// entry points that do not run the control step through rti_sens_kernel: refused on a handle with sensitivities on
+static int sens_refuse(ndp_handle *h, const char *what)
+{
+    h->err = std::string(what) + ": not available while initial-state sensitivities are enabled (ndp_sens_enable(h, 0) first): "
+             "only the in-place and work-list step forms compute them";
+    return -2;
 }
 
 // the shapes the work-queue form of rti_kernel is instantiated for (compile-time horizon and iteration count)
@@ -2566,6 +2375,7 @@ int ndp_xchg_end(ndp_xchg *x, void *stream)
 // are tracked (ndp_track_steps), else everything `stream` holds so far.
 int ndp_xchg_tick(ndp_xchg *x, ndp_handle *h, void *stream, const void *d_xr_next, size_t rows, void *d_gathered_next)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_xchg_tick");
     int rc = ndp_xchg_end(x, stream);
     if (rc) return rc;
     void *ev = nullptr;
@@ -2625,7 +2435,8 @@ int ndp_destroy(ndp_handle *h)
         if (e) (void)hipEventDestroy(e);
     h->pool.reset();
     void *ptrs[] = {h->dForceAB[0], h->dForceAB[1], h->dProto, h->dRingX, h->dTraj, h->dTables, h->dStamps, h->dRelay, h->dThr, h->sThr, h->dKC, h->dForce, h->dFrag,
-                    h->dIn, h->dOut, h->sdbg, h->dQctr, h->dQids, h->dTickIndex, h->dTickThrust, h->dAct};
+                    h->dIn, h->dOut, h->sdbg, h->dQctr, h->dQids, h->dTickIndex, h->dTickThrust, h->dAct,
+                    h->dSensU0, h->dSensU, h->dSensX};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &sl : h->slot) {
@@ -3004,6 +2815,44 @@ static int launch_rti(ndp_handle *h, const double *d_x0, const double *d_xr, con
     hipEvent_t stop = nullptr;
     if (so && so->done) stop = so->done;
     else if (h->track_steps) { stop = h->stepDone[++h->step_seq & 3]; h->last_step_tracked = true; }
+    if (h->sens_level > 0) {
+        // the same step through rti_sens_kernel (ndp_sens_enable admits three-slot shapes at qp_precision 0, one RTI iteration, 2 or 4
+        // instances per workgroup; the late-force and tick forms refuse such a handle before they get here)
+        if (prefetched || tick1) { h->err = "launch_rti: the late-force and tick forms have no sensitivity kernel"; return -2; }
+        const SensArgs sa{h->dSensU0, h->sens_level >= 2 ? h->dSensU : nullptr, h->sens_level >= 2 ? h->dSensX : nullptr, h->sens_level};
+#define LAUNCH_S(...)                                                                                                \
+    do {                                                                                                             \
+        if (ext_timing) {                                                                                            \
+            hipExtLaunchKernelGGL(RTI_SENS_K(__VA_ARGS__), grid, block, (std::uint32_t)shm, s, h->events.back().a, h->events.back().b, 0, ka, sa); \
+            h->timing_open = false;                                                                                  \
+        } else if (stop && !q) hipExtLaunchKernelGGL(RTI_SENS_K(__VA_ARGS__), grid, block, (std::uint32_t)shm, s, nullptr, stop, 0, ka, sa); \
+        else hipLaunchKernelGGL(RTI_SENS_K(__VA_ARGS__), grid, block, shm, s, ka, sa);                               \
+    } while (0)
+        if (q) {          // (work list: N = 20, as below)
+            KernArgs kc = ka;
+            kc.bp.f = fused ? h->dForce : d_f;
+            kc.ma.frag = nullptr; kc.ma.other = nullptr;
+            if (h->cfg.n_rti == 1 && h->cfg.as_iter_max <= 0) kc.P.qp_mode = QP_IPM_ALWAYS;
+            if (fused) LAUNCH_S(4, true, 20, 1); else LAUNCH_S(4, false, 20, 1);
+            NDP_HIP(h, hipGetLastError());
+            hipLaunchKernelGGL(RTI_SENS_K(4, false, 20, 2), grid, block, shm, s, kc, sa);
+            NDP_HIP(h, hipGetLastError());
+            if (stop) hipExtLaunchKernelGGL(queue_reset_kernel, dim3(1), dim3(64), 0, s, nullptr, stop, 0, h->dQctr, qa.ipm_total);
+            else hipLaunchKernelGGL(queue_reset_kernel, dim3(1), dim3(64), 0, s, h->dQctr, qa.ipm_total);
+            NDP_HIP(h, hipGetLastError());
+            const int rce = end_timing(h, s);
+            queue_policy(h, s);
+            return rce;
+        }
+        if (h->cfg.N == 20 && W == 4) { if (fused) LAUNCH_S(4, true, 20, 0); else LAUNCH_S(4, false, 20, 0); }
+        else if (W == 4) { if (fused) LAUNCH_S(4, true, 0, 0); else LAUNCH_S(4, false, 0, 0); }
+        else { if (fused) LAUNCH_S(2, true, 0, 0); else LAUNCH_S(2, false, 0, 0); }
+#undef LAUNCH_S
+        NDP_HIP(h, hipGetLastError());
+        const int rce = end_timing(h, s);
+        queue_policy(h, s);
+        return rce;
+    }
 #define LAUNCH(...)                                                                                                  \
     do {                                                                                                             \
         if (ext_timing) {                                                                                            \
@@ -3195,6 +3044,7 @@ int ndp_prefetch_join(ndp_handle *h, void *stream)
 
 int ndp_step_device_prefetched(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, void *d_u0, void *stream)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_step_device_prefetched");
     if (!h || !d_x0 || !d_xr || !d_ur || !d_u0) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
@@ -3952,6 +3802,7 @@ static int ensure_tick(ndp_handle *h)
 
 int ndp_tick_config(ndp_handle *h, const int32_t *other_index, int gate_on_odometry)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_config");
     if (!h) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     NDP_HIP(h, hipSetDevice(h->cfg.device));
@@ -3988,6 +3839,7 @@ int ndp_tick_config(ndp_handle *h, const int32_t *other_index, int gate_on_odome
 // Same arithmetic as the one-launch tick with the neighbour in the same handle (bit-equal: tests/test_tick.py).
 int ndp_tick_config_remote(ndp_handle *h, const void *d_windows, int stride, int64_t rows, const int32_t *other_index, int gate_on_odometry)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_config_remote");
     if (!h || !d_windows || !other_index) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     NDP_HIP(h, hipSetDevice(h->cfg.device));
@@ -4012,6 +3864,7 @@ int ndp_tick_config_remote(ndp_handle *h, const void *d_windows, int stride, int
 // nmpc_ctl.reset(*ref_pub.get_nmpc_ref_from_long_list()) (nmpc_node.py:92,151-152): the iterate := the list's current window
 int ndp_tick_reset(ndp_handle *h)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_reset");
     if (!h) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     NDP_HIP(h, hipSetDevice(h->cfg.device));
@@ -4110,6 +3963,7 @@ static int tick_enqueue(ndp_handle *h, hipStream_t s, const double *x_odom, bool
 
 int ndp_tick_advance_device(ndp_handle *h, const void *d_x_odom, const void *d_t, const void *d_vz, const void *d_throttle, int flags, void *stream)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_advance_device");
     if (!h || !d_x_odom) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
@@ -4145,6 +3999,7 @@ int ndp_tick_advance_device(ndp_handle *h, const void *d_x_odom, const void *d_t
 
 int ndp_tick_window_pv_device(ndp_handle *h, void *d_pv, void *stream)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_window_pv_device");
     if (!h || !d_pv) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
@@ -4163,6 +4018,7 @@ int ndp_tick_window_pv_device(ndp_handle *h, void *d_pv, void *stream)
 // front of ndp_tick_step_device by stream order alone (no event operation, no second stream: the tick's chain is serial anyway).
 int ndp_xchg_tick_windows(ndp_xchg *x, ndp_handle *h, void *d_gathered, void *stream)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_xchg_tick_windows");
     if (!x || !h || !d_gathered) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     if (x->device != h->cfg.device) { h->err = "ndp_xchg_tick_windows: the exchange and the handle live on different devices"; return -1; }
@@ -4202,6 +4058,7 @@ static int tick_step_enqueue(ndp_handle *h, hipStream_t s, const double *x_odom,
 
 int ndp_tick_step_device(ndp_handle *h, const void *d_x_odom, void *d_cmd, void *d_u0, void *stream)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_step_device");
     if (!h || !d_x_odom || !d_cmd) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
@@ -4268,6 +4125,7 @@ int ndp_xchg_tick_async(ndp_xchg *x, int on)
 
 int ndp_xchg_tick_begin(ndp_xchg *x, ndp_handle *h, const void *d_t, int flags, void *d_gathered)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_xchg_tick_begin");
     if (!x || !h || !d_gathered) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     if (x->device != h->cfg.device) { h->err = "ndp_xchg_tick_begin: the exchange and the handle live on different devices"; return -1; }
@@ -4347,6 +4205,7 @@ int ndp_xchg_tick_begin(ndp_xchg *x, ndp_handle *h, const void *d_t, int flags, 
 int ndp_xchg_tick_step(ndp_xchg *x, ndp_handle *h, const void *d_x_odom, const void *d_vz, const void *d_throttle, int flags,
                        void *d_cmd, void *d_u0, const void *d_gathered, void *stream)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_xchg_tick_step");
     if (!x || !h || !d_x_odom || !d_cmd || !d_gathered) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
@@ -4390,6 +4249,7 @@ int ndp_xchg_tick_step(ndp_xchg *x, ndp_handle *h, const void *d_x_odom, const v
 int ndp_tick_device(ndp_handle *h, const void *d_x_odom, const void *d_t, const void *d_vz, const void *d_throttle, int flags,
                     void *d_cmd, void *d_u0, void *stream)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_device");
     if (!h || !d_x_odom || !d_cmd) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
@@ -4471,6 +4331,7 @@ static int tick_end_locked(ndp_handle *h, double *cmd, double *u0, int32_t *stat
 
 int ndp_tick_begin(ndp_handle *h, const double *x_odom, const double *t, const double *vz, const double *throttle, int flags)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_begin");
     if (!h || !x_odom) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     return tick_begin_locked(h, x_odom, t, vz, throttle, flags);
@@ -4478,6 +4339,7 @@ int ndp_tick_begin(ndp_handle *h, const double *x_odom, const double *t, const d
 
 int ndp_tick_end(ndp_handle *h, double *cmd, double *u0, int32_t *status_out, int32_t *ipm_iters_out)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_end");
     if (!h || !cmd) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     return tick_end_locked(h, cmd, u0, status_out, ipm_iters_out);
@@ -4486,6 +4348,7 @@ int ndp_tick_end(ndp_handle *h, double *cmd, double *u0, int32_t *status_out, in
 int ndp_tick(ndp_handle *h, const double *x_odom, const double *t, const double *vz, const double *throttle, int flags,
              double *cmd, double *u0, int32_t *status_out, int32_t *ipm_iters_out)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_tick");
     if (!h || !x_odom || !cmd) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->slots_busy) { h->err = "ndp_tick: steps / ticks begun earlier are still in flight (end them first)"; return -14; }
@@ -4532,6 +4395,7 @@ int ndp_plant_step(ndp_handle *h, double *x, const double *u, const double *f, d
 // ---- f4: closed-loop rollout, everything enqueued back to back on one stream, nothing returns to the host in between
 int ndp_rollout_device(ndp_handle *h, int ticks, double t0, double dt_tick, int substeps, void *d_x, void *d_log, void *stream)
 {
+    if (h && h->sens_level) return sens_refuse(h, "ndp_rollout_device");
     if (!h || ticks < 1 || substeps < 1 || !d_x) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
@@ -4576,6 +4440,68 @@ void *ndp_device_iterate_x(ndp_handle *h) { return h ? h->dX : nullptr; }
 void *ndp_device_iterate_u(ndp_handle *h) { return h ? h->dU : nullptr; }
 void *ndp_device_force(ndp_handle *h) { return h ? h->dForce : nullptr; }
 int ndp_work_queue_enabled(ndp_handle *h) { return h ? (int)h->use_queue : -1; }
+
+// ---- initial-state sensitivities (rti_sens_kernel, RtiWave::sens_out)
+int ndp_sens_enable(ndp_handle *h, int level)
+{
+    if (!h) return -1;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (level < 0 || level > 2) { h->err = "ndp_sens_enable: level must be 0 (off), 1 (du0/dx0) or 2 (also dU/dx0 and dX/dx0)"; return -2; }
+    if (level > 0) {
+        if (slots_for(h->cfg.N) > 3) { h->err = "ndp_sens_enable: sensitivities are served for N <= 27 only (the five-slot kernels of N >= 28 have none)"; return -2; }
+        if (h->cfg.qp_precision != 0) { h->err = "ndp_sens_enable: sensitivities need qp_precision 0 (the fp64 product path)"; return -2; }
+        if (h->cfg.n_rti != 1) { h->err = "ndp_sens_enable: sensitivities need n_rti = 1 (the derivative of the step's one QP)"; return -2; }
+        if (h->waves != 4 && h->waves != 2) { h->err = "ndp_sens_enable: the sensitivity kernels run 2 or 4 instances per workgroup"; return -2; }
+    }
+    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    int rc = wait_all(h);                 // (steps in flight may still write the buffers)
+    if (rc) return rc;
+    const size_t B = h->cfg.batch, N = h->cfg.N;
+    const size_t n0 = B * (size_t)sens_u0_pitch(), nu = B * (size_t)sens_u_pitch((int)N), nx = B * (size_t)sens_x_pitch((int)N);
+    auto drop = [](double *&p) { if (p) (void)hipFree(p); p = nullptr; };
+    if (level < 2) { drop(h->dSensU); drop(h->dSensX); }
+    if (level == 0) { drop(h->dSensU0); h->sens_level = 0; return 0; }
+    // NaN until a step has written them
+    auto get = [&](double *&p, size_t n) -> int {
+        if (p) return 0;
+        NDP_HIP(h, hipMalloc((void **)&p, n * 8));
+        NDP_HIP(h, hipMemsetAsync(p, 0xff, n * 8, h->stream));
+        return 0;
+    };
+    if ((rc = get(h->dSensU0, n0))) return rc;
+    if (level == 2 && ((rc = get(h->dSensU, nu)) || (rc = get(h->dSensX, nx)))) return rc;
+    const int lds_bytes = (int)((size_t)h->lds_per_wave * sizeof(double) * h->waves);
+    const void *fns[] = {(const void *)RTI_SENS_K(4, false, 20, 0), (const void *)RTI_SENS_K(4, true, 20, 0),
+                         (const void *)RTI_SENS_K(4, false, 20, 1), (const void *)RTI_SENS_K(4, true, 20, 1), (const void *)RTI_SENS_K(4, false, 20, 2),
+                         (const void *)RTI_SENS_K(4, false, 0, 0), (const void *)RTI_SENS_K(4, true, 0, 0),
+                         (const void *)RTI_SENS_K(2, false, 0, 0), (const void *)RTI_SENS_K(2, true, 0, 0)};
+    for (const void *fn : fns) NDP_HIP(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    NDP_HIP(h, hipStreamSynchronize(h->stream));
+    h->sens_level = level;
+    return 0;
+}
+
+int ndp_sens_level(ndp_handle *h) { return h ? h->sens_level : -1; }
+
+int ndp_get_sens(ndp_handle *h, double *du0_dx0, double *dU_dx0, double *dX_dx0)
+{
+    if (!h) return -1;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->sens_level < 1) { h->err = "ndp_get_sens: sensitivities are not enabled (ndp_sens_enable)"; return -2; }
+    if ((dU_dx0 || dX_dx0) && h->sens_level < 2) { h->err = "ndp_get_sens: dU/dx0 and dX/dx0 need sensitivity level 2"; return -2; }
+    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    int rc = wait_all(h);
+    if (rc) return rc;
+    const size_t B = h->cfg.batch;
+    if (du0_dx0) NDP_HIP(h, hipMemcpy(du0_dx0, h->dSensU0, B * sens_u0_pitch() * 8, hipMemcpyDeviceToHost));
+    if (dU_dx0) NDP_HIP(h, hipMemcpy(dU_dx0, h->dSensU, B * sens_u_pitch(h->cfg.N) * 8, hipMemcpyDeviceToHost));
+    if (dX_dx0) NDP_HIP(h, hipMemcpy(dX_dx0, h->dSensX, B * sens_x_pitch(h->cfg.N) * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+void *ndp_device_sens_u0(ndp_handle *h) { return h ? h->dSensU0 : nullptr; }
+void *ndp_device_sens_u(ndp_handle *h) { return h ? h->dSensU : nullptr; }
+void *ndp_device_sens_x(ndp_handle *h) { return h ? h->dSensX : nullptr; }
 int ndp_refine_active(ndp_handle *h) { return h ? (int)(h->cfg.ipm_refine > 0 && slots_for(h->cfg.N) <= 3 && h->cfg.qp_precision == 0) : -1; }
 
 int ndp_synchronize(ndp_handle *h)

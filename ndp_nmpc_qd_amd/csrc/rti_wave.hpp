@@ -152,6 +152,16 @@ struct RtiIo {            // global-memory views of ONE instance
     signed char *act = nullptr;
 };
 NDP_HD int act_pitch(int N) { return 4 * N; }      // bytes per instance of the active-set record
+
+// Initial-state sensitivities of the step's QP (RtiWave::sens_out), one instance's views.  level 1: du0 [4][10] = du_0/dx_0;
+// level 2 also dU [N][4][10] = dU_k/dx_0 and dX [N+1][10][10] = dX_k/dx_0 (stage 0: the identity).  Column j: d/dx_0[j].
+struct SensIo {
+    double *du0, *dU, *dX;
+    int level;
+};
+NDP_HD int sens_u0_pitch() { return NU * NX; }
+NDP_HD int sens_u_pitch(int N) { return N * NU * NX; }
+NDP_HD int sens_x_pitch(int N) { return (N + 1) * NX * NX; }
 // *RtiIo::iters = interior-point iterations of the step (low half) + Riccati sweeps its QP_AUTO solves took before them (high half);
 // COND_ACCEPTED in the sweep count (config 5's study): a condensed solve's result was kept
 enum { ITERS_SWEEP_SHIFT = 16, ITERS_IPM_MASK = 0xffff, COND_ACCEPTED = 0x1000 };
@@ -1948,8 +1958,9 @@ struct RtiWave {
     // carries one is handed over before its first sweep (with the pins' code in it the kernel needed a scratch slot).
     // IPM_RARE (the in-place kernels): the interior-point loop is the exception -- see NDP_RARELY.  (The work list's consumer runs
     // nothing else.)
-    template <bool DEFER, bool IPM_RARE = false>
-    static NDP_D bool run(const RtiParams &P, const RtiIo &io, lp lds, InBuf &inb, vd x0v)
+    // SENS (rti_sens_kernel): after the step, the sensitivities of its last QP (sens_out) into *sens.  One RTI iteration only.
+    template <bool DEFER, bool IPM_RARE = false, bool SENS = false>
+    static NDP_D bool run(const RtiParams &P, const RtiIo &io, lp lds, InBuf &inb, vd x0v, const SensIo *sens = nullptr)
     {
         const int N = horizon(P);
         const LdsMap m = make_map(N);
@@ -2161,8 +2172,66 @@ struct RtiWave {
         W::gsti(io.iters, iters + ((sweeps + cond_kept) << int(ITERS_SWEEP_SHIFT)));
         // the kept set changed <=> a QP took more than its one sweep (a set that holds reproduces itself in the first one)
         if (NDP_RARELY(as_on && io.act && sweeps != n_rti)) as_store(P, m, lds, io, A);
+        if constexpr (SENS) {
+            if (sens && sens->level > 0) sens_out(P, m, T, lds, A, status != 0, *sens);
+        }
         if (io.f_late) W::late_publish(late_prev, io.late_gsize, io.late_done_word);
         return false;
+    }
+
+    // ---------------------------------------------------------------- initial-state sensitivities
+    // The step's last QP, differentiated with respect to x_0 with its linearisation, references and force held fixed.  Its last
+    // Riccati sweep left the gains K~_k (rows of the stage blocks' K~' area) and the forward operands [M~x ; K~] of every stage in
+    // LDS; nothing after the sweep writes the stage blocks.  Active set / early exit: the derivative with the final set fixed -- a
+    // pinned input does not move (its row is exactly 0; the sweep's value is ~ multiplier / as_gamma).  Interior point: the
+    // derivative of the last Newton system (barrier-smoothed).  A step with a nonzero status: NaN everywhere.
+    // Level 1: du_0/dx_0 = K~_0[:, 0..9].  Level 2: the forward sweep of riccati_sweep with a MATRIX right-hand side on the
+    // 16x16x4 instruction: Z_0 = [I_10 ; 0] (the affine row 10 is zero, so the defects drop out), per stage
+    //     Y = [M~x ; K~] Z_k (3 MFMAs): rows 12..15 = dU_k (pinned rows zeroed),  Z_{k+1} = Y + B~ dU_k (1 MFMA): rows 0..9 = dX_{k+1}
+    // with every result written from the registers it lands in (lane (g, j) holds row g + 4r, column j of accumulator r).
+    static NDP_D void sens_out(const RtiParams &P, const LdsMap &m, const Tables &T, lp lds, const ActSet &A, bool bad, const SensIo &so)
+    {
+        const int N = horizon(P);
+        vi lane = W::lane_here();
+        // the final set as 0 / 1 per input bound, element 4k + i, in CU (dead after the commit)
+        for (int t = 0; t < RUA; ++t) {
+            vi e = a_elem(P, lane, t);
+            W::st(lds, e + m.CU, W::sel(a_get(A, m, lds, t, e) == 0, vd(0.0), vd(1.0)));
+        }
+        W::sync();
+        const vd nan = vd(__builtin_nan(""));
+        {   // level 1: lane l < 40 holds du_0[i] / dx_0[j], i = l / 10, j = l % 10  (K~'[j][i] of stage 0)
+            vi i = (lane * 6554) >> 16, j = lane - i * 10;
+            vi ic = W::imin(i, vi(NU - 1));
+            vd v = W::ld(lds, j * 4 + ic + m.KT);
+            v = W::sel(W::ld(lds, ic + m.CU) == 0.0, v, vd(0.0));
+            W::gst(so.du0, lane, bad ? nan : v, lane < NU * NX);
+        }
+        if (so.level < 2) return;
+        vi g = lane >> 4, j = W::lcol(lane);
+        vb col = j < NX;
+        for (int t = 0; t * 64 < NX * NX; ++t) {      // dX_0 = I
+            vi e = lane + 64 * t, r = (e * 6554) >> 16;
+            W::gst(so.dX, e, bad ? nan : W::sel(e == r * 11, vd(1.0), vd(0.0)), e < NX * NX);
+        }
+        md zc[3];
+        for (int c = 0; c < 3; ++c) zc[c] = W::to_m(W::sel(col && (j == g + 4 * c), vd(1.0), vd(0.0)));
+        NDP_KEEP_LOOP
+        for (int k = 0; k < N; ++k) {
+            md fw[3];
+            for (int c = 0; c < 3; ++c) fw[c] = W::to_m(W::ld(lds, T.fw_off[c] + mb(k)));
+            const md mu = W::to_m(W::ld(lds, T.mu_off + mb(k)));
+            const vb pin = !(W::ld(lds, g + (m.CU + k * int(NU))) == 0.0);
+            md4 Y = mman<3>(fw, zc, W::mzero4());
+            const md du = W::msel(pin, W::to_m(vd(0.0)), Y.r[3]);
+            md4 xn = mma(mu, du, Y);
+            W::gst(so.dU, g * int(NX) + j + k * int(NU * NX), bad ? nan : W::to_d(du), col);
+            for (int c = 0; c < 3; ++c) {
+                zc[c] = xn.r[c];
+                vi r = g + 4 * c;
+                W::gst(so.dX, W::imin(r, vi(NX - 1)) * int(NX) + j + (k + 1) * int(NX * NX), bad ? nan : W::to_d(xn.r[c]), col && (r < NX));
+            }
+        }
     }
 };
 

@@ -7,9 +7,10 @@ from ..solver_facade import SolverFacade
 
 
 class NDPNMPCBodyRateController(object):
-    def __init__(self, is_build_acados=True, device=0):
+    def __init__(self, is_build_acados=True, device=0, param_sens=False):
         self._engine = BatchedNMPC(batch=1, N=CP.N_node, disturbance=True, device=device, load_mlp=False)
-        self.solver = SolverFacade(self._engine, disturbance=True)
+        # param_sens: acados' eval_param_sens / get(stage, "sens_x" | "sens_u") with respect to x0 (off: the reference's call)
+        self.solver = SolverFacade(self._engine, disturbance=True, param_sens=param_sens)
 
     def reset(self, xr, ur):
         for i in range(self.solver.N):

@@ -7,11 +7,12 @@ from ..solver_facade import SolverFacade
 
 
 class NMPCBodyRateController(object):
-    def __init__(self, is_build_acados=True, device=0):
+    def __init__(self, is_build_acados=True, device=0, param_sens=False):
         # is_build_acados is accepted for signature compatibility; there is nothing to generate or compile.
         # Deviations from the reference constructor: no os.chdir side effect, no ACADOS_SOURCE_DIR.
         self._engine = BatchedNMPC(batch=1, N=CP.N_node, disturbance=False, device=device)
-        self.solver = SolverFacade(self._engine, disturbance=False)
+        # param_sens: acados' eval_param_sens / get(stage, "sens_x" | "sens_u") with respect to x0 (off: the reference's call)
+        self.solver = SolverFacade(self._engine, disturbance=False, param_sens=param_sens)
 
     def reset(self, xr, ur):
         # reset x and u of the controller, which prevents warm-starting from the previous solution

@@ -10,10 +10,20 @@ import threading
 import numpy as np
 
 
+_SENS_OFF = ("initial-state sensitivities are off: build the controller with param_sens=True "
+             "(e.g. NMPCBodyRateController(param_sens=True)) to use eval_param_sens / get(stage, 'sens_x' | 'sens_u')")
+
+
 class SolverFacade:
-    def __init__(self, engine, disturbance):
+    def __init__(self, engine, disturbance, param_sens=False):
         self._eng = engine            # BatchedNMPC with batch = 1
         self.N = engine.N
+        # acados' eval_param_sens(index) + get(stage, "sens_x" / "sens_u"): every step writes dU/dx0 and dX/dx0 (level 2)
+        self._param_sens = bool(param_sens)
+        self._sens = None             # (dU [N,4,10], dX [N+1,10,10]) of the last eval_param_sens, and its column
+        self._sens_index = None
+        if self._param_sens:
+            engine.enable_sensitivity(2)
         self.status = 0
         self._np = 7 if disturbance else 4
         self._lock = threading.Lock()  # rospy calls update / reset / get from different threads (nmpc_node.py:94,152,237)
@@ -63,7 +73,35 @@ class SolverFacade:
                 return self._X[stage].copy()
             if field == "u":
                 return self._U[stage].copy()
+            if field in ("sens_x", "sens_u"):
+                if not self._param_sens:
+                    raise Exception(f"AcadosOcpSolver.get(): {field}: " + _SENS_OFF)
+                if self._sens is None:
+                    raise Exception(f"AcadosOcpSolver.get(): {field}: call eval_param_sens(index) after the solve first")
+                dU, dX = self._sens
+                if field == "sens_x":
+                    if not 0 <= stage <= self.N:
+                        raise Exception(f"AcadosOcpSolver.get(): sens_x: stage must be in 0..{self.N}")
+                    return dX[stage, :, self._sens_index].copy()
+                if not 0 <= stage < self.N:
+                    raise Exception(f"AcadosOcpSolver.get(): sens_u: stage must be in 0..{self.N - 1}")
+                return dU[stage, :, self._sens_index].copy()
         raise Exception(f"AcadosOcpSolver.get(): {field} is not supported by this drop-in")
+
+    # acados: solver.eval_param_sens(index, stage=0, field="ex"): the sensitivity of the last solution with respect to x0[index]
+    # (read with get(stage, "sens_x" / "sens_u")).  The device computed it with the step (ndp_sens_enable, level 2); this fetches it.
+    def eval_param_sens(self, index, stage=0, field="ex"):
+        if not self._param_sens:
+            raise Exception("AcadosOcpSolver.eval_param_sens(): " + _SENS_OFF)
+        if field != "ex" or stage != 0:
+            raise Exception("AcadosOcpSolver.eval_param_sens(): only field 'ex' at stage 0 (the initial state) is supported")
+        index = int(index)
+        if not 0 <= index < 10:
+            raise Exception("AcadosOcpSolver.eval_param_sens(): index must be in 0..9 (the state dimension)")
+        with self._lock:
+            _, dU, dX = self._eng.sensitivity()
+            self._sens = (dU[0], dX[0])
+            self._sens_index = index
 
     # acados: u0 = solver.solve_for_x0(x0)
     def solve_for_x0(self, x0):
