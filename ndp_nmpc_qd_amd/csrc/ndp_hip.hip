@@ -1924,7 +1924,7 @@ struct ndp_handle {
     double *dSensU0 = nullptr, *dSensU = nullptr, *dSensX = nullptr;   // [B][4][10], [B][N][4][10], [B][N+1][10][10] (the last two: level 2)
     double *dThr = nullptr;    // hover-throttle estimator state, SoA [8][B]
     double *dStamps = nullptr; // [B][NDP_NSTAMP] whole-batch phase stamps (ndp_debug_stamps)
-    double *dTraj = nullptr;   // f1: [B][n_seg][28] coeff | [B][n_seg+1] time_cum | [B][n_seg] time_seg | [B][3] final_pt | [B][64] segment cache | int[B] segment hints
+    double *dTraj = nullptr;   // f1: the trajectories and the tick's caches (layout: TrajView)
     int traj_seg = 0;
     double *dRingX = nullptr, *dRingU = nullptr;   // f1: the reference's sliding list of reference points, phase-major (RingGeom), one allocation (first use)
     unsigned long long list_n = 0;                 // absolute index of the list's oldest entry = control ticks since the list was built
@@ -2029,6 +2029,26 @@ static int usable_cores()
     return n < 1 ? 1 : n;
 }
 static size_t act_bytes(const ndp_handle *h) { return (size_t)h->cfg.batch * (size_t)act_pitch(h->cfg.N); }
+// The trajectory block dTraj (ndp_ref_set_trajectory), one allocation of `doubles`, in this order: coefficients [B][S][28] (x, y, z: 8
+// each, yaw: 4) | time_cum [B][S+1] | time_seg [B][S] | final_pt [B][3] | the one-launch tick's segment cache [B][SEGC_PER] (empty =
+// NaNs: tick_early) | the segment hints int[B] (ref_point) | the cache's second copy [B][SEGC_PER] (tick_cache_store).  base = null:
+// the size only.
+struct TrajView {
+    double *coeff, *tcum, *tseg, *fpt, *segc[2];
+    int *hint;
+    size_t doubles;
+};
+static TrajView traj_view(double *base, size_t B, size_t S)
+{
+    TrajView v;
+    size_t o = 0;
+    auto part = [&](size_t n) { double *p = base ? base + o : nullptr; o += n; return p; };
+    v.coeff = part(B * S * 28); v.tcum = part(B * (S + 1)); v.tseg = part(B * S); v.fpt = part(B * 3);
+    v.segc[0] = part(B * SEGC_PER); v.hint = reinterpret_cast<int *>(part((B * 4 + 7) / 8)); v.segc[1] = part(B * SEGC_PER);
+    v.doubles = o;
+    return v;
+}
+static TrajView traj_view(const ndp_handle *h) { return traj_view(h->dTraj, (size_t)h->cfg.batch, (size_t)h->traj_seg); }
 // the step's iteration words (RtiIo::iters) -> the caller's interior-point iteration counts
 static void copy_ipm_iters(int32_t *dst, const int32_t *src, size_t n)
 {
@@ -2049,6 +2069,47 @@ static bool queue_shape(const ndp_handle *h)
     return h->cfg.qp_precision == 0 &&
            ((h->cfg.N == 20 && h->cfg.n_rti == 1 && h->waves == 4) || (h->cfg.N == 40 && h->cfg.n_rti == 2 && h->waves == 2));
 }
+
+// Every control-step kernel the library launches, one entry per instantiation (RTI_K / RTI_SENS_K: collapsed in the development
+// builds).  rti_pick chooses the entry of a call; ndp_create / ndp_sens_enable give every plain / sensitivity entry its dynamic LDS.
+// (The order of the rows is the order the kernels lie in the code object.)
+struct RtiKern {
+    const void *fn;
+    int waves;                 // instances per workgroup: the launch geometry
+    bool sens;                 // rti_sens_kernel (KernArgs, SensArgs), else rti_kernel (KernArgs)
+};
+enum RtiId {
+    K3_4, K3_2, K3_1, K5_4, K5_2, K5_1, K3F_4, K3F_2, K3F_1,         // any horizon: 3 / 5 slots, fused downwash; 4, 2, 1 instances per group
+    K20, K20F, K20_W2, K20F_W2,                                       // the reference shape (N = 20, one RTI iteration)
+    K20_PROD, K20F_PROD, K20_CONS, K20_LATE,                          // ... work-list producer / consumer, late-force step
+    K20F_TICK, K20_TICK, K20F_PROD_TICK, K20_PROD_TICK,               // ... one-launch ticks
+    KPREC1, KPREC2, KPREC3, KPREC4, KPREC5, KPREC6,                   // precision studies, any horizon, one wave per group
+    K40_F32, K40_BF16, K40, K40_PROD, K40_CONS,                       // BASELINE config 5's shape (N = 40, two RTI iterations)
+    S20F_PROD, S20_PROD, S20_CONS, S20F, S20, SF_4, S_4, SF_2, S_2,   // sensitivities (three slots)
+    RTI_KERNELS
+};
+static const RtiKern k_rti[] = {
+    {(const void *)RTI_K(3, 4, false), 4}, {(const void *)RTI_K(3, 2, false), 2}, {(const void *)RTI_K(3, 1, false), 1},
+    {(const void *)RTI_K(5, 4, false), 4}, {(const void *)RTI_K(5, 2, false), 2}, {(const void *)RTI_K(5, 1, false), 1},
+    {(const void *)RTI_K(3, 4, true), 4}, {(const void *)RTI_K(3, 2, true), 2}, {(const void *)RTI_K(3, 1, true), 1},
+    {(const void *)RTI_K(3, 4, false, 20), 4}, {(const void *)RTI_K(3, 4, true, 20), 4},
+    {(const void *)RTI_K(3, 2, false, 20), 2}, {(const void *)RTI_K(3, 2, true, 20), 2},
+    {(const void *)RTI_K(3, 4, false, 20, 0, 1, 1), 4}, {(const void *)RTI_K(3, 4, true, 20, 0, 1, 1), 4},
+    {(const void *)RTI_K(3, 4, false, 20, 0, 1, 2), 4}, {(const void *)RTI_K(3, 4, false, 20, 0, 1, 3), 4},
+    {(const void *)RTI_K(3, 4, true, 20, 0, 1, 0, true), 4}, {(const void *)RTI_K(3, 4, false, 20, 0, 1, 0, true), 4},
+    {(const void *)RTI_K(3, 4, true, 20, 0, 1, 1, true), 4}, {(const void *)RTI_K(3, 4, false, 20, 0, 1, 1, true), 4},
+    {(const void *)RTI_K(5, 1, false, 0, 1), 1}, {(const void *)RTI_K(5, 1, false, 0, 2), 1}, {(const void *)RTI_K(5, 1, false, 0, 3), 1},
+    {(const void *)RTI_K(5, 1, false, 0, 4), 1}, {(const void *)RTI_K(5, 1, false, 0, 5), 1}, {(const void *)RTI_K(5, 1, false, 0, 6), 1},
+    {(const void *)RTI_K(5, 2, false, 40, 3, 2), 2}, {(const void *)RTI_K(5, 2, false, 40, 4, 2), 2},
+    {(const void *)RTI_K(5, 2, false, 40, 0, 2), 2}, {(const void *)RTI_K(5, 2, false, 40, 0, 2, 1), 2},
+    {(const void *)RTI_K(5, 2, false, 40, 0, 2, 2), 2},
+    {(const void *)RTI_SENS_K(4, true, 20, 1), 4, true}, {(const void *)RTI_SENS_K(4, false, 20, 1), 4, true},
+    {(const void *)RTI_SENS_K(4, false, 20, 2), 4, true},
+    {(const void *)RTI_SENS_K(4, true, 20, 0), 4, true}, {(const void *)RTI_SENS_K(4, false, 20, 0), 4, true},
+    {(const void *)RTI_SENS_K(4, true, 0, 0), 4, true}, {(const void *)RTI_SENS_K(4, false, 0, 0), 4, true},
+    {(const void *)RTI_SENS_K(2, true, 0, 0), 2, true}, {(const void *)RTI_SENS_K(2, false, 0, 0), 2, true},
+};
+static_assert(sizeof(k_rti) / sizeof(k_rti[0]) == RTI_KERNELS, "one row per RtiId");
 
 extern "C" {
 
@@ -2375,14 +2436,14 @@ int ndp_xchg_end(ndp_xchg *x, void *stream)
 // are tracked (ndp_track_steps), else everything `stream` holds so far.
 int ndp_xchg_tick(ndp_xchg *x, ndp_handle *h, void *stream, const void *d_xr_next, size_t rows, void *d_gathered_next)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_xchg_tick");
-    int rc = ndp_xchg_end(x, stream);
-    if (rc) return rc;
     void *ev = nullptr;
     if (h) {
         std::lock_guard<std::mutex> lk(h->mu);
+        if (h->sens_level) return sens_refuse(h, "ndp_xchg_tick");
         if (h->track_steps && h->step_seq && h->last_step_tracked) ev = (void *)h->stepDone[h->step_seq & 3];
     }
+    int rc = ndp_xchg_end(x, stream);
+    if (rc) return rc;
     return ndp_xchg_begin(x, d_xr_next, rows, d_gathered_next, ev ? nullptr : stream, ev);
 }
 
@@ -2598,25 +2659,11 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
     (void)hipMemsetAsync(h->dForce, 0, nfs(h) * 4, h->stream);
     // allow the big dynamic-LDS launches
     const int lds_bytes = (int)(per_wave_bytes * h->waves);
-    const void *fns[] = {(const void *)RTI_K(3, 4, false), (const void *)RTI_K(3, 2, false), (const void *)RTI_K(3, 1, false),
-                         (const void *)RTI_K(5, 4, false), (const void *)RTI_K(5, 2, false), (const void *)RTI_K(5, 1, false),
-                         (const void *)RTI_K(3, 4, true), (const void *)RTI_K(3, 2, true), (const void *)RTI_K(3, 1, true),
-                         (const void *)RTI_K(3, 4, false, 20), (const void *)RTI_K(3, 4, true, 20),
-                         (const void *)RTI_K(3, 2, false, 20), (const void *)RTI_K(3, 2, true, 20),
-                         (const void *)RTI_K(3, 4, false, 20, 0, 1, 1), (const void *)RTI_K(3, 4, true, 20, 0, 1, 1), (const void *)RTI_K(3, 4, false, 20, 0, 1, 2),
-                         (const void *)RTI_K(3, 4, false, 20, 0, 1, 3),
-                         (const void *)RTI_K(3, 4, true, 20, 0, 1, 0, true), (const void *)RTI_K(3, 4, false, 20, 0, 1, 0, true),
-                         (const void *)RTI_K(3, 4, true, 20, 0, 1, 1, true), (const void *)RTI_K(3, 4, false, 20, 0, 1, 1, true),
-                         (const void *)RTI_K(5, 1, false, 0, 1), (const void *)RTI_K(5, 1, false, 0, 2),
-                         (const void *)RTI_K(5, 1, false, 0, 3), (const void *)RTI_K(5, 1, false, 0, 4),
-                         (const void *)RTI_K(5, 1, false, 0, 5), (const void *)RTI_K(5, 1, false, 0, 6),
-                         (const void *)RTI_K(5, 2, false, 40, 3, 2), (const void *)RTI_K(5, 2, false, 40, 4, 2),
-                         (const void *)RTI_K(5, 2, false, 40, 0, 2), (const void *)RTI_K(5, 2, false, 40, 0, 2, 1), (const void *)RTI_K(5, 2, false, 40, 0, 2, 2)};
     if ((e = hipFuncSetAttribute((const void *)mlp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)(FR_TOTAL * sizeof(float)))) != hipSuccess)
         return fail("hipFuncSetAttribute(mlp_kernel)", e);
-    for (const void *fn : fns)
-        if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) != hipSuccess)
+    for (const RtiKern &k : k_rti)      // (the sensitivity kernels: ndp_sens_enable)
+        if (!k.sens && (e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) != hipSuccess)
             return fail("hipFuncSetAttribute", e);
     hipLaunchKernelGGL(throttle_reset_kernel, dim3((cfg->batch + 255) / 256), dim3(256), 0, h->stream, h->dThr, 50.0, cfg->batch);
     if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("hipStreamSynchronize", e);
@@ -2686,6 +2733,39 @@ static int wait_all(ndp_handle *h)
     return 0;
 }
 
+static int set_device(ndp_handle *h)
+{
+    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    return 0;
+}
+
+// The frame of a handle's entry point: h->mu is held for the whole call.  In this order: -1 for a null handle or missing arguments
+// (args false), -2 while sensitivities are on if the entry point does not compute them (refuse: its name), then the device is
+// selected and the stream resolved (null: the handle's own).  rc != 0: the call returns it.
+struct Entry {
+    ndp_handle *h;
+    std::unique_lock<std::mutex> lk;
+    hipStream_t s = nullptr;
+    int rc = -1;
+    Entry(ndp_handle *h_, bool args, void *stream = nullptr, const char *refuse = nullptr) : h(h_)
+    {
+        if (!h) return;
+        lk = std::unique_lock<std::mutex>(h->mu);
+        s = stream ? (hipStream_t)stream : h->stream;
+        if (refuse && h->sens_level) rc = sens_refuse(h, refuse);
+        else if (args) rc = set_device(h);
+    }
+    // the end of a form that enqueues on a caller's stream: the getters wait for that stream too
+    int noted(int r) { return r ? r : note_stream(h, s); }
+    // the end of a host-array form, behind its copies out: everything on the handle's stream has completed
+    int synced(int r)
+    {
+        if (r) return r;
+        NDP_HIP(h, hipStreamSynchronize(h->stream));
+        return 0;
+    }
+};
+
 struct Neigh {                 // neighbour windows of a step (device pointers)
     const double *other = nullptr;
     int stride = NX;           // doubles per node: 10 or 6
@@ -2748,6 +2828,52 @@ static void queue_policy(ndp_handle *h, hipStream_t s)
     if (hipMemcpyAsync(h->hIpm, reinterpret_cast<unsigned long long *>(h->dQctr + 16), 16, hipMemcpyDeviceToHost, s) != hipSuccess) (void)hipGetLastError();
 }
 
+// The kernel of one launch of a step.  phase: 0 the in-place step, 1 / 2 the work list's producer / consumer.  (The late-force and tick
+// forms have no sensitivity kernel: launch_rti refuses them first.)
+static RtiId rti_pick(const ndp_handle *h, bool fused, bool tick, bool prefetched, int phase)
+{
+    const int N = h->cfg.N, W = h->waves, pr = h->cfg.qp_precision, wi = W == 4 ? 0 : W == 2 ? 1 : 2;
+    const bool ref = N == 20 && h->cfg.n_rti == 1;     // the reference configuration (params/nmpc_params.py:9, 1 RTI iteration): compile-time instantiations
+    if (pr) {                                          // BASELINE config 5 (unfused; run ndp_downwash first for a force)
+        if (pr >= 3 && N == 40 && h->cfg.n_rti == 2 && W == 2) return pr == 3 ? K40_F32 : K40_BF16;   // config 5's own shape: 2 instances per workgroup
+        return (RtiId)(KPREC1 + pr - 1);               // any horizon: one wave per workgroup (5 / 6: the condensed study, fp32 / bf16 instruction)
+    }
+    if (h->sens_level > 0) {
+        // (ndp_sens_enable admits three-slot shapes at qp_precision 0, one RTI iteration, 2 or 4 instances per workgroup; work list: N = 20)
+        if (phase) return phase == 2 ? S20_CONS : fused ? S20F_PROD : S20_PROD;
+        if (N == 20 && W == 4) return fused ? S20F : S20;
+        if (W == 4) return fused ? SF_4 : S_4;
+        return fused ? SF_2 : S_2;
+    }
+    if (phase == 2) return N == 20 ? K20_CONS : K40_CONS;
+    if (phase == 1) {
+        if (N != 20) return K40_PROD;
+        if (tick) return fused ? K20F_PROD_TICK : K20_PROD_TICK;
+        return fused ? K20F_PROD : K20_PROD;
+    }
+    if (ref && W == 4) {
+        if (tick) return fused ? K20F_TICK : K20_TICK;
+        return fused ? K20F : prefetched ? K20_LATE : K20;
+    }
+    if (ref && W == 2) return fused ? K20F_W2 : K20_W2;     // (NDP_DEV_WAVES = 2: the same program, two instances per workgroup)
+    if (N == 40 && h->cfg.n_rti == 2 && W == 2 && !fused) return K40;   // BASELINE config 5's shape, compile-time as well
+    if (fused) return (RtiId)(K3F_4 + wi);
+    return (RtiId)((slots_for(N) <= 3 ? K3_4 : K5_4) + wi);
+}
+
+// One launch of a control-step kernel.  start / stop (either may be null): the timing pair or the step's completion event, carried
+// by the dispatch packet itself (hipExtLaunchKernel).  The caller checks hipGetLastError.
+static void launch_kern(const ndp_handle *h, RtiId id, hipStream_t s, KernArgs &ka, SensArgs &sa, hipEvent_t start = nullptr,
+                        hipEvent_t stop = nullptr)
+{
+    const RtiKern &k = k_rti[id];
+    const dim3 grid((h->cfg.batch + k.waves - 1) / k.waves), block(64 * k.waves);
+    const size_t shm = (size_t)h->lds_per_wave * sizeof(double) * k.waves;
+    void *args[] = {&ka, &sa};          // (rti_kernel takes the first only)
+    if (start || stop) (void)hipExtLaunchKernel(k.fn, grid, block, args, shm, s, start, stop, 0);
+    else (void)hipLaunchKernel(k.fn, grid, block, args, shm, s);
+}
+
 static int launch_rti(ndp_handle *h, const double *d_x0, const double *d_xr, const double *d_ur, const float *d_f,
                       double *d_u0, double *d_dbg, hipStream_t s, const Neigh *nb = nullptr, const StepOut *so = nullptr,
                       bool prefetched = false)
@@ -2764,14 +2890,12 @@ static int launch_rti(ndp_handle *h, const double *d_x0, const double *d_xr, con
                h->cfg.r_horiz * h->cfg.r_horiz, fused ? nb->stride : NX, fused ? nb->index : nullptr, fused ? peer_mapped(nb->other) : 0,
                fused && nb->pitch ? nb->pitch : (size_t)(h->cfg.N + 1) * (fused ? nb->stride : NX), fused && nb->ego_pitch ? nb->ego_pitch : (size_t)2};
     QueueArgs qa{h->dQctr, h->dQids, reinterpret_cast<unsigned long long *>(h->dQctr + 16)};
-    const int B = h->cfg.batch, W = h->waves;
     LateArgs la{prefetched ? h->dProto : nullptr, {h->dForceAB[0], h->dForceAB[1]}, h->prefetch_timeout_us,
                 h->pf_groups_rti, h->pf_ntiles};
-    KernArgs ka{h->P, bp, B, h->lds_per_wave, ma, qa, la, so && so->tick ? *so->tick : TickArgs{}};
+    KernArgs ka{h->P, bp, h->cfg.batch, h->lds_per_wave, ma, qa, la, so && so->tick ? *so->tick : TickArgs{}};
+    SensArgs sa{h->dSensU0, h->sens_level >= 2 ? h->dSensU : nullptr, h->sens_level >= 2 ? h->dSensX : nullptr, h->sens_level};
     const bool tick1 = so && so->tick;   // (tick_enqueue hands a TickArgs over only for the shapes the TICK kernels exist for)
-    const dim3 grid((B + W - 1) / W), block(64 * W);
-    const size_t shm = (size_t)h->lds_per_wave * sizeof(double) * W;
-    const int ns = slots_for(h->cfg.N);
+    const int pr = h->cfg.qp_precision;
     const bool q = h->use_queue && !d_dbg && !prefetched;      // (the late-force step is in place: its launch is the lean instantiation)
     // Tracked steps carry their completion event on a dispatch packet (hipExtLaunchKernel), which a stream capture cannot hold:
     // refuse instead of launching something the graph would silently drop the event of.
@@ -2788,79 +2912,19 @@ static int launch_rti(ndp_handle *h, const double *d_x0, const double *d_xr, con
     int rc = begin_timing(h, s, 0, true);
     if (rc) return rc;
     // timed launch of a single-kernel step: the pair rides on the dispatch packet (otherwise recorded around the launches)
-    const bool ext_timing = h->timing_open && !q && !h->cfg.qp_precision && !(so && so->done) && !h->track_steps;
+    const bool ext_timing = h->timing_open && !q && !pr && !(so && so->done) && !h->track_steps;
     if (h->timing_open && !ext_timing) NDP_HIP(h, hipEventRecord(h->events.back().a, s));
-    if (h->cfg.qp_precision) {      // BASELINE config 5 (unfused; run ndp_downwash first for a force)
-        if (fused) { h->err = "qp_precision != 0 supports f / no disturbance only (run ndp_downwash first)"; return -12; }
-        const size_t shm1 = (size_t)h->lds_per_wave * sizeof(double);
-        const int pr = h->cfg.qp_precision;
-        if (pr >= 3 && h->cfg.N == 40 && h->cfg.n_rti == 2 && W == 2) {   // config 5's own shape: compile-time horizon, 2 instances per workgroup
-            if (pr == 3) hipLaunchKernelGGL(RTI_K(5, 2, false, 40, 3, 2), grid, block, shm, s, ka);
-            else hipLaunchKernelGGL(RTI_K(5, 2, false, 40, 4, 2), grid, block, shm, s, ka);
-        } else if (pr == 1) hipLaunchKernelGGL(RTI_K(5, 1, false, 0, 1), dim3(B), dim3(64), shm1, s, ka);   // any horizon: one wave per workgroup
-        else if (pr == 2) hipLaunchKernelGGL(RTI_K(5, 1, false, 0, 2), dim3(B), dim3(64), shm1, s, ka);
-        else if (pr == 3) hipLaunchKernelGGL(RTI_K(5, 1, false, 0, 3), dim3(B), dim3(64), shm1, s, ka);
-        else if (pr == 4) hipLaunchKernelGGL(RTI_K(5, 1, false, 0, 4), dim3(B), dim3(64), shm1, s, ka);
-        else if (pr == 5) hipLaunchKernelGGL(RTI_K(5, 1, false, 0, 5), dim3(B), dim3(64), shm1, s, ka);     // config 5, condensed: fp32 instruction
-        else hipLaunchKernelGGL(RTI_K(5, 1, false, 0, 6), dim3(B), dim3(64), shm1, s, ka);                   // ... bf16 instruction
-        NDP_HIP(h, hipGetLastError());
-        if (so && so->done) NDP_HIP(h, hipEventRecord(so->done, s));
-        else if (h->track_steps) {          // (a recorded event here: the precision studies are not on the exchange's fast path)
-            NDP_HIP(h, hipEventRecord(h->stepDone[++h->step_seq & 3], s));
-            h->last_step_tracked = true;
-        }
-        return end_timing(h, s);
-    }
-    // tracked steps: the LAST launch of the step carries the completion event (in-place kernel, or the work list's reset launch)
+    if (pr && fused) { h->err = "qp_precision != 0 supports f / no disturbance only (run ndp_downwash first)"; return -12; }
+    // tracked steps: the LAST launch of the step carries the completion event (in-place kernel, or the work list's reset launch; the
+    // precision studies, not on the exchange's fast path, record it behind their launch)
     hipEvent_t stop = nullptr;
     if (so && so->done) stop = so->done;
     else if (h->track_steps) { stop = h->stepDone[++h->step_seq & 3]; h->last_step_tracked = true; }
-    if (h->sens_level > 0) {
-        // the same step through rti_sens_kernel (ndp_sens_enable admits three-slot shapes at qp_precision 0, one RTI iteration, 2 or 4
-        // instances per workgroup; the late-force and tick forms refuse such a handle before they get here)
-        if (prefetched || tick1) { h->err = "launch_rti: the late-force and tick forms have no sensitivity kernel"; return -2; }
-        const SensArgs sa{h->dSensU0, h->sens_level >= 2 ? h->dSensU : nullptr, h->sens_level >= 2 ? h->dSensX : nullptr, h->sens_level};
-#define LAUNCH_S(...)                                                                                                \
-    do {                                                                                                             \
-        if (ext_timing) {                                                                                            \
-            hipExtLaunchKernelGGL(RTI_SENS_K(__VA_ARGS__), grid, block, (std::uint32_t)shm, s, h->events.back().a, h->events.back().b, 0, ka, sa); \
-            h->timing_open = false;                                                                                  \
-        } else if (stop && !q) hipExtLaunchKernelGGL(RTI_SENS_K(__VA_ARGS__), grid, block, (std::uint32_t)shm, s, nullptr, stop, 0, ka, sa); \
-        else hipLaunchKernelGGL(RTI_SENS_K(__VA_ARGS__), grid, block, shm, s, ka, sa);                               \
-    } while (0)
-        if (q) {          // (work list: N = 20, as below)
-            KernArgs kc = ka;
-            kc.bp.f = fused ? h->dForce : d_f;
-            kc.ma.frag = nullptr; kc.ma.other = nullptr;
-            if (h->cfg.n_rti == 1 && h->cfg.as_iter_max <= 0) kc.P.qp_mode = QP_IPM_ALWAYS;
-            if (fused) LAUNCH_S(4, true, 20, 1); else LAUNCH_S(4, false, 20, 1);
-            NDP_HIP(h, hipGetLastError());
-            hipLaunchKernelGGL(RTI_SENS_K(4, false, 20, 2), grid, block, shm, s, kc, sa);
-            NDP_HIP(h, hipGetLastError());
-            if (stop) hipExtLaunchKernelGGL(queue_reset_kernel, dim3(1), dim3(64), 0, s, nullptr, stop, 0, h->dQctr, qa.ipm_total);
-            else hipLaunchKernelGGL(queue_reset_kernel, dim3(1), dim3(64), 0, s, h->dQctr, qa.ipm_total);
-            NDP_HIP(h, hipGetLastError());
-            const int rce = end_timing(h, s);
-            queue_policy(h, s);
-            return rce;
-        }
-        if (h->cfg.N == 20 && W == 4) { if (fused) LAUNCH_S(4, true, 20, 0); else LAUNCH_S(4, false, 20, 0); }
-        else if (W == 4) { if (fused) LAUNCH_S(4, true, 0, 0); else LAUNCH_S(4, false, 0, 0); }
-        else { if (fused) LAUNCH_S(2, true, 0, 0); else LAUNCH_S(2, false, 0, 0); }
-#undef LAUNCH_S
-        NDP_HIP(h, hipGetLastError());
-        const int rce = end_timing(h, s);
-        queue_policy(h, s);
-        return rce;
-    }
-#define LAUNCH(...)                                                                                                  \
-    do {                                                                                                             \
-        if (ext_timing) {                                                                                            \
-            hipExtLaunchKernelGGL(RTI_K(__VA_ARGS__), grid, block, (std::uint32_t)shm, s, h->events.back().a, h->events.back().b, 0, ka); \
-            h->timing_open = false;                                                                                  \
-        } else if (stop && !q) hipExtLaunchKernelGGL(RTI_K(__VA_ARGS__), grid, block, (std::uint32_t)shm, s, nullptr, stop, 0, ka); \
-        else hipLaunchKernelGGL(RTI_K(__VA_ARGS__), grid, block, shm, s, ka);                                        \
-    } while (0)
+    if (h->sens_level > 0 && (prefetched || tick1)) { h->err = "launch_rti: the late-force and tick forms have no sensitivity kernel"; return -2; }
+    launch_kern(h, rti_pick(h, fused, tick1, prefetched, q ? 1 : 0), s, ka, sa, ext_timing ? h->events.back().a : nullptr,
+                ext_timing ? h->events.back().b : q || pr ? nullptr : stop);
+    if (ext_timing) h->timing_open = false;     // (end_timing has nothing left to record)
+    NDP_HIP(h, hipGetLastError());
     if (q) {
         // work list: producer (every instance: one solve with the kept set's pins, done or defer), consumer (the deferred ones, from
         // scratch: active-set iterations, then the interior-point loop if need be; several RTI iterations: the automatic rule per
@@ -2872,35 +2936,15 @@ static int launch_rti(ndp_handle *h, const double *d_x0, const double *d_xr, con
         // (active-set iterations off: a listed instance needs the interior-point loop, the consumer goes straight to it; on: the
         // producer lists every instance whose first solve -- with the kept set's pins -- did not settle, the consumer iterates on the set)
         if (h->cfg.n_rti == 1 && h->cfg.as_iter_max <= 0) kc.P.qp_mode = QP_IPM_ALWAYS;
-        if (h->cfg.N == 20) {
-            if (tick1) { if (fused) LAUNCH(3, 4, true, 20, 0, 1, 1, true); else LAUNCH(3, 4, false, 20, 0, 1, 1, true); }
-            else if (fused) LAUNCH(3, 4, true, 20, 0, 1, 1); else LAUNCH(3, 4, false, 20, 0, 1, 1);
-            NDP_HIP(h, hipGetLastError());
-            hipLaunchKernelGGL(RTI_K(3, 4, false, 20, 0, 1, 2), grid, block, shm, s, kc);
-        } else {
-            LAUNCH(5, 2, false, 40, 0, 2, 1);
-            NDP_HIP(h, hipGetLastError());
-            hipLaunchKernelGGL(RTI_K(5, 2, false, 40, 0, 2, 2), grid, block, shm, s, kc);
-        }
+        launch_kern(h, rti_pick(h, fused, tick1, prefetched, 2), s, kc, sa);
         NDP_HIP(h, hipGetLastError());
         if (stop) hipExtLaunchKernelGGL(queue_reset_kernel, dim3(1), dim3(64), 0, s, nullptr, stop, 0, h->dQctr, qa.ipm_total);
         else hipLaunchKernelGGL(queue_reset_kernel, dim3(1), dim3(64), 0, s, h->dQctr, qa.ipm_total);
         NDP_HIP(h, hipGetLastError());
-        { const int rce = end_timing(h, s); queue_policy(h, s); return rce; }
-    }
-    if (h->cfg.N == 20 && h->cfg.n_rti == 1 && W == 4) {   // the reference configuration (params/nmpc_params.py:9, 1 RTI iteration): compile-time instantiation
-        if (tick1) { if (fused) LAUNCH(3, 4, true, 20, 0, 1, 0, true); else LAUNCH(3, 4, false, 20, 0, 1, 0, true); }
-        else if (fused) LAUNCH(3, 4, true, 20); else if (prefetched) LAUNCH(3, 4, false, 20, 0, 1, 3); else LAUNCH(3, 4, false, 20);
-    } else if (h->cfg.N == 20 && h->cfg.n_rti == 1 && W == 2) {   // (NDP_DEV_WAVES = 2: the same program, two instances per workgroup)
-        if (fused) LAUNCH(3, 2, true, 20); else LAUNCH(3, 2, false, 20);
-    } else if (h->cfg.N == 40 && h->cfg.n_rti == 2 && W == 2 && !fused) {   // BASELINE config 5's shape, compile-time as well
-        LAUNCH(5, 2, false, 40, 0, 2);
-    } else if (fused) { if (W == 4) LAUNCH(3, 4, true); else if (W == 2) LAUNCH(3, 2, true); else LAUNCH(3, 1, true); }
-    else if (ns <= 3) { if (W == 4) LAUNCH(3, 4, false); else if (W == 2) LAUNCH(3, 2, false); else LAUNCH(3, 1, false); }
-    else { if (W == 4) LAUNCH(5, 4, false); else if (W == 2) LAUNCH(5, 2, false); else LAUNCH(5, 1, false); }
-#undef LAUNCH
-    NDP_HIP(h, hipGetLastError());
-    { const int rce = end_timing(h, s); queue_policy(h, s); return rce; }
+    } else if (pr && stop) NDP_HIP(h, hipEventRecord(stop, s));
+    const int rce = end_timing(h, s);
+    queue_policy(h, s);
+    return rce;
 }
 
 // downwash inside the RTI launch when one 32-row tile covers the horizon; otherwise mlp_kernel first
@@ -2929,43 +2973,36 @@ static int enqueue_step(ndp_handle *h, const double *d_x0, const double *d_xr, c
 
 int ndp_reset_device(ndp_handle *h, const void *d_xr, const void *d_ur, void *stream)
 {
-    if (!h || !d_xr || !d_ur) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
-    NDP_HIP(h, hipMemcpyAsync(h->dX, d_xr, nxs(h) * 8, hipMemcpyDefault, s));
-    NDP_HIP(h, hipMemcpyAsync(h->dU, d_ur, nus(h) * 8, hipMemcpyDefault, s));
-    NDP_HIP(h, hipMemsetAsync(h->dAct, 0, act_bytes(h), s));      // a new iterate: the QPs start from an empty active set
-    return note_stream(h, s);
+    Entry g(h, d_xr && d_ur, stream);
+    if (g.rc) return g.rc;
+    NDP_HIP(h, hipMemcpyAsync(h->dX, d_xr, nxs(h) * 8, hipMemcpyDefault, g.s));
+    NDP_HIP(h, hipMemcpyAsync(h->dU, d_ur, nus(h) * 8, hipMemcpyDefault, g.s));
+    NDP_HIP(h, hipMemsetAsync(h->dAct, 0, act_bytes(h), g.s));      // a new iterate: the QPs start from an empty active set
+    return g.noted(0);
 }
 
 int ndp_reset(ndp_handle *h, const double *xr, const double *ur)
 {
-    if (!h || !xr || !ur) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, xr && ur);
+    if (g.rc) return g.rc;
     int rc = wait_all(h);
     if (rc) return rc;
     NDP_HIP(h, hipMemcpyAsync(h->dX, xr, nxs(h) * 8, hipMemcpyDefault, h->stream));
     NDP_HIP(h, hipMemcpyAsync(h->dU, ur, nus(h) * 8, hipMemcpyDefault, h->stream));
     NDP_HIP(h, hipMemsetAsync(h->dAct, 0, act_bytes(h), h->stream));
-    NDP_HIP(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return g.synced(0);
 }
 
 int ndp_step_device_ex(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
                        const void *d_other, int other_stride, const void *d_other_index, const void *d_ego_xy,
                        void *d_u0, void *stream)
 {
-    if (!h || !d_x0 || !d_xr || !d_ur || !d_u0) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, d_x0 && d_xr && d_ur && d_u0, stream);
+    if (g.rc) return g.rc;
     Neigh nb;
     nb.other = (const double *)d_other; nb.stride = other_stride; nb.index = (const int *)d_other_index; nb.ego_xy = (const double *)d_ego_xy;
-    int rc = enqueue_step(h, (const double *)d_x0, (const double *)d_xr, (const double *)d_ur, (const float *)d_f, nb,
-                          (double *)d_u0, nullptr, s);
-    return rc ? rc : note_stream(h, s);
+    return g.noted(enqueue_step(h, (const double *)d_x0, (const double *)d_xr, (const double *)d_ur, (const float *)d_f, nb,
+                                (double *)d_u0, nullptr, g.s));
 }
 
 int ndp_step_device(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
@@ -3009,9 +3046,8 @@ static int ensure_prefetch(ndp_handle *h)
 int ndp_downwash_prefetch_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index,
                                  const void *d_ego_ref, const void *d_ego_xy, void *after_stream, void *on_stream)
 {
-    if (!h || !d_other || !d_ego_ref) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, d_other && d_ego_ref);
+    if (g.rc) return g.rc;
     int rc = ensure_prefetch(h);
     if (rc) return rc;
     if (other_stride != 10 && other_stride != 6) { h->err = "ndp_downwash_prefetch_device: other_stride must be 10 or 6"; return -13; }
@@ -3044,16 +3080,12 @@ int ndp_prefetch_join(ndp_handle *h, void *stream)
 
 int ndp_step_device_prefetched(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, void *d_u0, void *stream)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_step_device_prefetched");
-    if (!h || !d_x0 || !d_xr || !d_ur || !d_u0) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, d_x0 && d_xr && d_ur && d_u0, stream, "ndp_step_device_prefetched");
+    if (g.rc) return g.rc;
     int rc = ensure_prefetch(h);
     if (rc) return rc;
-    rc = launch_rti(h, (const double *)d_x0, (const double *)d_xr, (const double *)d_ur, nullptr, (double *)d_u0, nullptr, s,
-                    nullptr, nullptr, true);
-    return rc ? rc : note_stream(h, s);
+    return g.noted(launch_rti(h, (const double *)d_x0, (const double *)d_xr, (const double *)d_ur, nullptr, (double *)d_u0, nullptr, g.s,
+                              nullptr, nullptr, true));
 }
 
 int ndp_prefetch_stats(ndp_handle *h, unsigned long long *out4 /* [5] */)
@@ -3300,14 +3332,11 @@ int ndp_step_debug(ndp_handle *h, const double *x0, const double *xr, const doub
 int ndp_downwash_device(ndp_handle *h, const void *d_other, const void *d_ego_ref, const void *d_ego_xy,
                         void *d_f_out, void *stream)
 {
-    if (!h || !d_other || !d_ego_ref || !d_f_out) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, d_other && d_ego_ref && d_f_out, stream);
+    if (g.rc) return g.rc;
     Neigh nb;
     nb.other = (const double *)d_other; nb.ego_xy = (const double *)d_ego_xy;
-    int rc = launch_mlp(h, nb, (const double *)d_ego_ref, (float *)d_f_out, s);
-    return rc ? rc : note_stream(h, s);
+    return g.noted(launch_mlp(h, nb, (const double *)d_ego_ref, (float *)d_f_out, g.s));
 }
 
 
@@ -3315,44 +3344,38 @@ int ndp_downwash_device(ndp_handle *h, const void *d_other, const void *d_ego_re
 int ndp_debug_downwash_stream_device(ndp_handle *h, const void *d_other, const void *d_ego_ref, const void *d_ego_xy,
                                      void *d_f_out, void *stream)
 {
-    if (!h || !d_other || !d_ego_ref || !d_f_out) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, d_other && d_ego_ref && d_f_out, stream);
+    if (g.rc) return g.rc;
     if (!h->have_mlp) { h->err = "downwash requested but ndp_set_mlp_weights was never called"; return -6; }
     const int np1 = h->cfg.N + 1, rows = h->cfg.batch * np1;
     const int ntiles = (rows + 31) / 32;
-    hipLaunchKernelGGL(mlp_stream_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, s, (const float *)h->dFrag, (const double *)d_other,
+    hipLaunchKernelGGL(mlp_stream_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, g.s, (const float *)h->dFrag, (const double *)d_other,
                        (const double *)d_ego_ref, (const double *)d_ego_xy, (float *)d_f_out, (float *)d_f_out, rows, np1,
                        h->cfg.r_horiz * h->cfg.r_horiz, NX, (const int *)nullptr, (unsigned long long *)nullptr, peer_mapped(d_other));
     NDP_HIP(h, hipGetLastError());
-    return note_stream(h, s);
+    return g.noted(0);
 }
 
 int ndp_downwash(ndp_handle *h, const double *other, const double *ego_ref, const double *ego_xy, float *f_out)
 {
-    if (!h || !other || !ego_ref || !f_out) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
+    Entry g(h, other && ego_ref && f_out);
+    if (g.rc) return g.rc;
     hipStream_t s = h->stream;
-    const size_t B = h->cfg.batch;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
     NDP_HIP(h, hipMemcpyAsync(h->sother, other, nxs(h) * 8, hipMemcpyHostToDevice, s));
     NDP_HIP(h, hipMemcpyAsync(h->sxr, ego_ref, nxs(h) * 8, hipMemcpyHostToDevice, s));
-    if (ego_xy) NDP_HIP(h, hipMemcpyAsync(h->sego, ego_xy, B * 2 * 8, hipMemcpyHostToDevice, s));
+    if (ego_xy) NDP_HIP(h, hipMemcpyAsync(h->sego, ego_xy, (size_t)h->cfg.batch * 2 * 8, hipMemcpyHostToDevice, s));
     Neigh nb;
     nb.other = h->sother; nb.ego_xy = ego_xy ? h->sego : nullptr;
     int rc = launch_mlp(h, nb, h->sxr, h->dForce, s);
     if (rc) return rc;
     NDP_HIP(h, hipMemcpyAsync(f_out, h->dForce, nfs(h) * 4, hipMemcpyDeviceToHost, s));
-    NDP_HIP(h, hipStreamSynchronize(s));
-    return 0;
+    return g.synced(0);
 }
 
 int ndp_get_iterate(ndp_handle *h, double *X, double *U)
 {
-    if (!h) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, true);
+    if (g.rc) return g.rc;
     int rc = wait_all(h);
     if (rc) return rc;
     if (X) NDP_HIP(h, hipMemcpy(X, h->dX, nxs(h) * 8, hipMemcpyDefault));
@@ -3362,9 +3385,8 @@ int ndp_get_iterate(ndp_handle *h, double *X, double *U)
 
 int ndp_set_iterate(ndp_handle *h, const double *X, const double *U)
 {
-    if (!h) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, true);
+    if (g.rc) return g.rc;
     int rc = wait_all(h);
     if (rc) return rc;
     if (X) NDP_HIP(h, hipMemcpy(h->dX, X, nxs(h) * 8, hipMemcpyDefault));
@@ -3375,9 +3397,8 @@ int ndp_set_iterate(ndp_handle *h, const double *X, const double *U)
 
 int ndp_get_active_set(ndp_handle *h, int32_t *sweeps, int8_t *act)
 {
-    if (!h) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, true);
+    if (g.rc) return g.rc;
     int rc = wait_all(h);
     if (rc) return rc;
     const size_t B = (size_t)h->cfg.batch;
@@ -3391,9 +3412,8 @@ int ndp_get_active_set(ndp_handle *h, int32_t *sweeps, int8_t *act)
 
 int ndp_set_active_set(ndp_handle *h, const int8_t *act)
 {
-    if (!h || !act) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, act);
+    if (g.rc) return g.rc;
     int rc = wait_all(h);
     if (rc) return rc;
     const size_t n = act_bytes(h);
@@ -3405,9 +3425,8 @@ int ndp_set_active_set(ndp_handle *h, const int8_t *act)
 
 int ndp_get_status(ndp_handle *h, int32_t *status, int32_t *ipm_iters)
 {
-    if (!h) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, true);
+    if (g.rc) return g.rc;
     int rc = wait_all(h);
     if (rc) return rc;
     if (status) NDP_HIP(h, hipMemcpy(status, h->lastStatus, (size_t)h->cfg.batch * 4, hipMemcpyDefault));
@@ -3434,13 +3453,11 @@ static ThrCfg thr_cfg(const ndp_handle *h)
 
 int ndp_throttle_reset(ndp_handle *h)
 {
-    if (!h) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, true);
+    if (g.rc) return g.rc;
     hipLaunchKernelGGL(throttle_reset_kernel, dim3((h->cfg.batch + 255) / 256), dim3(256), 0, h->stream, h->dThr, 50.0, h->cfg.batch);
     NDP_HIP(h, hipGetLastError());
-    NDP_HIP(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return g.synced(0);
 }
 
 // The host-pointer forms below hold the handle's lock from the first staging copy to the read-back: they share the
@@ -3454,27 +3471,22 @@ static int launch_throttle(ndp_handle *h, const double *d_vz, const double *d_th
 
 int ndp_throttle_update_device(ndp_handle *h, const void *d_vz, const void *d_throttle, void *d_k, void *stream)
 {
-    if (!h || !d_vz || !d_throttle || !d_k) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
-    int rc = launch_throttle(h, (const double *)d_vz, (const double *)d_throttle, (double *)d_k, s);
-    return rc ? rc : note_stream(h, s);
+    Entry g(h, d_vz && d_throttle && d_k, stream);
+    if (g.rc) return g.rc;
+    return g.noted(launch_throttle(h, (const double *)d_vz, (const double *)d_throttle, (double *)d_k, g.s));
 }
 
 int ndp_throttle_update(ndp_handle *h, const double *vz, const double *throttle, double *k)
 {
-    if (!h || !vz || !throttle || !k) return -1;
+    Entry g(h, vz && throttle && k);
+    if (g.rc) return g.rc;
     const size_t B = h->cfg.batch;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
     NDP_HIP(h, hipMemcpyAsync(h->sThr, vz, B * 8, hipMemcpyHostToDevice, h->stream));
     NDP_HIP(h, hipMemcpyAsync(h->sThr + B, throttle, B * 8, hipMemcpyHostToDevice, h->stream));
     int rc = launch_throttle(h, h->sThr, h->sThr + B, h->sThr + 2 * B, h->stream);
     if (rc) return rc;
     NDP_HIP(h, hipMemcpyAsync(k, h->sThr + 2 * B, B * 8, hipMemcpyDeviceToHost, h->stream));
-    NDP_HIP(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return g.synced(0);
 }
 
 static int launch_actuator(ndp_handle *h, const double *d_u0, const double *d_k, double *d_cmd, hipStream_t s)
@@ -3486,35 +3498,29 @@ static int launch_actuator(ndp_handle *h, const double *d_u0, const double *d_k,
 
 int ndp_actuator_cmd_device(ndp_handle *h, const void *d_u0, const void *d_k, void *d_cmd, void *stream)
 {
-    if (!h || !d_u0 || !d_k || !d_cmd) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
-    int rc = launch_actuator(h, (const double *)d_u0, (const double *)d_k, (double *)d_cmd, s);
-    return rc ? rc : note_stream(h, s);
+    Entry g(h, d_u0 && d_k && d_cmd, stream);
+    if (g.rc) return g.rc;
+    return g.noted(launch_actuator(h, (const double *)d_u0, (const double *)d_k, (double *)d_cmd, g.s));
 }
 
 int ndp_actuator_cmd(ndp_handle *h, const double *u0, const double *k, double *cmd)
 {
-    if (!h || !u0 || !k || !cmd) return -1;
+    Entry g(h, u0 && k && cmd);
+    if (g.rc) return g.rc;
     const size_t B = h->cfg.batch;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
     NDP_HIP(h, hipMemcpyAsync(h->sThr + 2 * B, k, B * 8, hipMemcpyHostToDevice, h->stream));
     NDP_HIP(h, hipMemcpyAsync(h->sThr + 3 * B, u0, B * 32, hipMemcpyHostToDevice, h->stream));
     int rc = launch_actuator(h, h->sThr + 3 * B, h->sThr + 2 * B, h->sThr + 7 * B, h->stream);
     if (rc) return rc;
     NDP_HIP(h, hipMemcpyAsync(cmd, h->sThr + 7 * B, B * 32, hipMemcpyDeviceToHost, h->stream));
-    NDP_HIP(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return g.synced(0);
 }
 
 int ndp_throttle_get_state(ndp_handle *h, double *state)
 {
-    if (!h || !state) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
+    Entry g(h, state);
+    if (g.rc) return g.rc;
     const size_t B = h->cfg.batch;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
     int rc = wait_all(h);
     if (rc) return rc;
     std::vector<double> soa(B * 8);
@@ -3527,32 +3533,26 @@ int ndp_throttle_get_state(ndp_handle *h, double *state)
 // ---- f2: follower reference relay
 int ndp_relay_reset(ndp_handle *h)
 {
-    if (!h) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, true);
+    if (g.rc) return g.rc;
     NDP_HIP(h, hipMemsetAsync(h->dRelay, 0, (size_t)h->cfg.batch * 32, h->stream));
-    NDP_HIP(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return g.synced(0);
 }
 
 int ndp_relay_formation(ndp_handle *h, const double *form, double *offset_out)
 {
-    if (!h || !form) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
+    Entry g(h, form);
+    if (g.rc) return g.rc;
     const size_t B = h->cfg.batch;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
     NDP_HIP(h, hipMemcpyAsync(h->sThr, form, B * 24, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(relay_formation_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, 0.8, h->dRelay, (const double *)h->sThr, (int)B);
     NDP_HIP(h, hipGetLastError());
-    if (offset_out) {
-        std::vector<double> st(B * 4);
-        NDP_HIP(h, hipMemcpyAsync(st.data(), h->dRelay, B * 32, hipMemcpyDeviceToHost, h->stream));
-        NDP_HIP(h, hipStreamSynchronize(h->stream));
-        for (size_t v = 0; v < B; ++v)
-            for (int a = 0; a < 3; ++a) offset_out[v * 3 + a] = st[v * 4 + a];
-    } else {
-        NDP_HIP(h, hipStreamSynchronize(h->stream));
-    }
+    std::vector<double> st(offset_out ? B * 4 : 0);
+    if (offset_out) NDP_HIP(h, hipMemcpyAsync(st.data(), h->dRelay, B * 32, hipMemcpyDeviceToHost, h->stream));
+    int rc = g.synced(0);
+    if (rc) return rc;
+    for (size_t v = 0; offset_out && v < B; ++v)
+        for (int a = 0; a < 3; ++a) offset_out[v * 3 + a] = st[v * 4 + a];
     return 0;
 }
 
@@ -3567,39 +3567,34 @@ static int launch_relay_reference(ndp_handle *h, const double *d_xr_lead, double
 
 int ndp_relay_reference_device(ndp_handle *h, const void *d_xr_lead, void *d_xr_out, void *stream)
 {
-    if (!h || !d_xr_lead || !d_xr_out) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
-    int rc = launch_relay_reference(h, (const double *)d_xr_lead, (double *)d_xr_out, s);
-    return rc ? rc : note_stream(h, s);
+    Entry g(h, d_xr_lead && d_xr_out, stream);
+    if (g.rc) return g.rc;
+    return g.noted(launch_relay_reference(h, (const double *)d_xr_lead, (double *)d_xr_out, g.s));
 }
 
 int ndp_relay_reference(ndp_handle *h, const double *xr_lead, double *xr_out)
 {
-    if (!h || !xr_lead || !xr_out) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, xr_lead && xr_out);
+    if (g.rc) return g.rc;
     NDP_HIP(h, hipMemcpyAsync(h->sother, xr_lead, nxs(h) * 8, hipMemcpyHostToDevice, h->stream));
     int rc = launch_relay_reference(h, h->sother, h->sxr, h->stream);
     if (rc) return rc;
     NDP_HIP(h, hipMemcpyAsync(xr_out, h->sxr, nxs(h) * 8, hipMemcpyDeviceToHost, h->stream));
-    NDP_HIP(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return g.synced(0);
 }
 
 // ---- f1: reference window generation
 int ndp_ref_set_trajectory(ndp_handle *h, int n_seg, const double *coeff_x, const double *coeff_y, const double *coeff_z,
                            const double *coeff_yaw, const double *time_cum, const double *time_seg, const double *final_pt)
 {
-    if (!h || n_seg < 1 || !coeff_x || !coeff_y || !coeff_z || !coeff_yaw || !time_cum || !time_seg || !final_pt) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
+    Entry g(h, n_seg >= 1 && coeff_x && coeff_y && coeff_z && coeff_yaw && time_cum && time_seg && final_pt);
+    if (g.rc) return g.rc;
     const size_t B = h->cfg.batch, S = (size_t)n_seg;
-    const size_t n_coeff = B * S * 28, n_cum = B * (S + 1), n_seg_t = B * S, total = n_coeff + n_cum + n_seg_t + B * 3;
-    std::vector<double> host(total);
+    std::vector<double> host(traj_view(nullptr, B, S).doubles);     // (the hints start at 0)
+    const TrajView v = traj_view(host.data(), B, S);
     for (size_t b = 0; b < B; ++b)
         for (size_t s = 0; s < S; ++s) {
-            double *d = host.data() + (b * S + s) * 28;          // interleave the four message arrays per segment
+            double *d = v.coeff + (b * S + s) * 28;          // interleave the four message arrays per segment
             for (int i = 0; i < 8; ++i) {
                 d[i] = coeff_x[(b * S + s) * 8 + i];
                 d[8 + i] = coeff_y[(b * S + s) * 8 + i];
@@ -3607,62 +3602,54 @@ int ndp_ref_set_trajectory(ndp_handle *h, int n_seg, const double *coeff_x, cons
             }
             for (int i = 0; i < 4; ++i) d[24 + i] = coeff_yaw[(b * S + s) * 4 + i];
         }
-    memcpy(host.data() + n_coeff, time_cum, n_cum * 8);
-    memcpy(host.data() + n_coeff + n_cum, time_seg, n_seg_t * 8);
-    memcpy(host.data() + n_coeff + n_cum + n_seg_t, final_pt, B * 3 * 8);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    memcpy(v.tcum, time_cum, B * (S + 1) * 8);
+    memcpy(v.tseg, time_seg, B * S * 8);
+    memcpy(v.fpt, final_pt, B * 3 * 8);
+    for (double *c : v.segc) memset(c, 0xFF, B * SEGC_PER * 8);
     int rc = wait_all(h);
     if (rc) return rc;
     if (h->dTraj) { (void)hipFree(h->dTraj); h->dTraj = nullptr; }
-    // (+ the one-launch tick's segment cache, [B][SEGC_PER] doubles, empty = NaNs: tick_early; + the segment hints, int[B]: ref_point;
-    //  + the cache's second copy behind them: tick_cache_store)
-    const size_t hint_doubles = (B * 4 + 7) / 8;
-    NDP_HIP(h, hipMalloc((void **)&h->dTraj, (total + 2 * B * SEGC_PER + hint_doubles) * 8));
-    NDP_HIP(h, hipMemcpy(h->dTraj, host.data(), total * 8, hipMemcpyHostToDevice));
-    NDP_HIP(h, hipMemset(h->dTraj + total, 0xFF, B * SEGC_PER * 8));
-    NDP_HIP(h, hipMemset(h->dTraj + total + B * SEGC_PER, 0, hint_doubles * 8));
-    NDP_HIP(h, hipMemset(h->dTraj + total + B * SEGC_PER + hint_doubles, 0xFF, B * SEGC_PER * 8));
+    NDP_HIP(h, hipMalloc((void **)&h->dTraj, v.doubles * 8));
+    NDP_HIP(h, hipMemcpy(h->dTraj, host.data(), v.doubles * 8, hipMemcpyHostToDevice));
     h->segc_par = 0;
     h->traj_seg = n_seg;
     return 0;
+}
+
+static RefCfg ref_cfg(const ndp_handle *h, double toff)
+{
+    return RefCfg{h->cfg.batch, h->cfg.N, h->traj_seg, h->cfg.dt, h->cfg.mass, h->cfg.gravity, toff};
 }
 
 // enqueue helper (no locking): windows at node-0 times d_t[b] (or 0 when null) + toff
 static int launch_ref_window(ndp_handle *h, const double *d_t, double toff, double *d_xr, double *d_ur, hipStream_t s)
 {
     if (!h->dTraj) { h->err = "ndp_ref_window: ndp_ref_set_trajectory was never called"; return -11; }
-    const size_t B = h->cfg.batch, S = (size_t)h->traj_seg;
-    const double *coeff = h->dTraj, *cum = coeff + B * S * 28, *seg = cum + B * (S + 1), *fpt = seg + B * S;
-    RefCfg cf{h->cfg.batch, h->cfg.N, h->traj_seg, h->cfg.dt, h->cfg.mass, h->cfg.gravity, toff};
+    const TrajView tv = traj_view(h);
     const int rows = h->cfg.batch * (h->cfg.N + 1);
-    hipLaunchKernelGGL(ref_window_kernel, dim3((rows + REF_ROWS - 1) / REF_ROWS), dim3(REF_ROWS), 0, s, cf, coeff, cum, seg, fpt,
-                       d_t, d_xr, d_ur);
+    hipLaunchKernelGGL(ref_window_kernel, dim3((rows + REF_ROWS - 1) / REF_ROWS), dim3(REF_ROWS), 0, s, ref_cfg(h, toff), tv.coeff, tv.tcum, tv.tseg,
+                       tv.fpt, d_t, d_xr, d_ur);
     NDP_HIP(h, hipGetLastError());
     return 0;
 }
 
 int ndp_ref_window_device(ndp_handle *h, const void *d_t, void *d_xr, void *d_ur, void *stream)
 {
-    if (!h || !d_t || !d_xr || !d_ur) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
-    int rc = launch_ref_window(h, (const double *)d_t, 0.0, (double *)d_xr, (double *)d_ur, s);
-    return rc ? rc : note_stream(h, s);
+    Entry g(h, d_t && d_xr && d_ur, stream);
+    if (g.rc) return g.rc;
+    return g.noted(launch_ref_window(h, (const double *)d_t, 0.0, (double *)d_xr, (double *)d_ur, g.s));
 }
 
 int ndp_ref_window(ndp_handle *h, const double *t, double *xr, double *ur)
 {
-    if (!h || !t || !xr || !ur) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, t && xr && ur);
+    if (g.rc) return g.rc;
     NDP_HIP(h, hipMemcpyAsync(h->sThr, t, (size_t)h->cfg.batch * 8, hipMemcpyHostToDevice, h->stream));
     int rc = launch_ref_window(h, h->sThr, 0.0, h->sxr, h->sur, h->stream);
     if (rc) return rc;
     NDP_HIP(h, hipMemcpyAsync(xr, h->sxr, nxs(h) * 8, hipMemcpyDeviceToHost, h->stream));
     NDP_HIP(h, hipMemcpyAsync(ur, h->sur, nus(h) * 8, hipMemcpyDeviceToHost, h->stream));
-    NDP_HIP(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return g.synced(0);
 }
 
 // ---- f1, the reference's sliding list (ref_list_* kernels; layout: RingGeom)
@@ -3678,20 +3665,14 @@ static int list_alloc(ndp_handle *h)
     return 0;
 }
 
-static RefCfg ref_cfg(const ndp_handle *h, double toff)
-{
-    return RefCfg{h->cfg.batch, h->cfg.N, h->traj_seg, h->cfg.dt, h->cfg.mass, h->cfg.gravity, toff};
-}
-
 // points at (d_t ? d_t[b] : 0) + toff + i * ts_nmpc, i = 0 .. npts-1, become list entries j0 + i (dup0: point 0 also entry j0 - 1)
 static int launch_list_fill(ndp_handle *h, const double *d_t, double toff, int npts, unsigned long long j0, int dup0, hipStream_t s)
 {
     if (!h->dTraj) { h->err = "ndp_ref_list: ndp_ref_set_trajectory was never called"; return -11; }
-    const size_t B = h->cfg.batch, S = (size_t)h->traj_seg;
-    const double *coeff = h->dTraj, *cum = coeff + B * S * 28, *seg = cum + B * (S + 1), *fpt = seg + B * S;
+    const TrajView tv = traj_view(h);
     const int n = h->cfg.batch * npts;
     const int bs = npts == 1 ? 64 : 256;        // one point per vehicle (the per-tick advance): small blocks spread over the CUs
-    hipLaunchKernelGGL(ref_list_fill_kernel, dim3((n + bs - 1) / bs), dim3(bs), 0, s, ref_cfg(h, toff), coeff, cum, seg, fpt, d_t,
+    hipLaunchKernelGGL(ref_list_fill_kernel, dim3((n + bs - 1) / bs), dim3(bs), 0, s, ref_cfg(h, toff), tv.coeff, tv.tcum, tv.tseg, tv.fpt, d_t,
                        h->cfg.ts_nmpc, npts, j0, ring_geom(h), dup0, h->dRingX, h->dRingU);
     NDP_HIP(h, hipGetLastError());
     return 0;
@@ -3699,25 +3680,20 @@ static int launch_list_fill(ndp_handle *h, const double *d_t, double toff, int n
 
 int ndp_ref_list_reset(ndp_handle *h)
 {
-    if (!h) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, true);
+    if (g.rc) return g.rc;
     int rc = list_alloc(h);
     if (rc) return rc;
     if ((rc = wait_all(h))) return rc;
     h->list_n = 0;
     // entries 1 .. ring-1 = the points at i * ts_nmpc, i = 0 .. ring-2; the first one duplicated as entry 0 (:62-76)
-    rc = launch_list_fill(h, nullptr, 0.0, list_ring(h) - 1, 1, 1, h->stream);
-    if (rc) return rc;
-    NDP_HIP(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return g.synced(launch_list_fill(h, nullptr, 0.0, list_ring(h) - 1, 1, 1, h->stream));
 }
 
 int ndp_ref_list_fix_pt(ndp_handle *h, const double *x_odom, int quirk_b1)
 {
-    if (!h || !x_odom) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, x_odom);
+    if (g.rc) return g.rc;
     int rc = list_alloc(h);
     if (rc) return rc;
     if ((rc = wait_all(h))) return rc;
@@ -3728,8 +3704,7 @@ int ndp_ref_list_fix_pt(ndp_handle *h, const double *x_odom, int quirk_b1)
     hipLaunchKernelGGL(ref_list_fix_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->sThr,
                        quirk_b1 ? h->cfg.mass * h->cfg.gravity : h->cfg.gravity, h->cfg.batch, rg, h->dRingX, h->dRingU);
     NDP_HIP(h, hipGetLastError());
-    NDP_HIP(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return g.synced(0);
 }
 
 // pop the oldest entry, append the point at trajectory time t + T_horizon (get_nmpc_pts, :79-93)
@@ -3744,12 +3719,9 @@ static int list_advance(ndp_handle *h, const double *d_t, hipStream_t s)
 
 int ndp_ref_list_advance_device(ndp_handle *h, const void *d_t, void *stream)
 {
-    if (!h || !d_t) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
-    int rc = list_advance(h, (const double *)d_t, s);
-    return rc ? rc : note_stream(h, s);
+    Entry g(h, d_t, stream);
+    if (g.rc) return g.rc;
+    return g.noted(list_advance(h, (const double *)d_t, g.s));
 }
 
 static int launch_list_window(ndp_handle *h, double *d_xr, double *d_ur, hipStream_t s)
@@ -3764,20 +3736,16 @@ static int launch_list_window(ndp_handle *h, double *d_xr, double *d_ur, hipStre
 
 int ndp_ref_list_window_device(ndp_handle *h, void *d_xr, void *d_ur, void *stream)
 {
-    if (!h || !d_xr || !d_ur) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
-    int rc = launch_list_window(h, (double *)d_xr, (double *)d_ur, s);
-    return rc ? rc : note_stream(h, s);
+    Entry g(h, d_xr && d_ur, stream);
+    if (g.rc) return g.rc;
+    return g.noted(launch_list_window(h, (double *)d_xr, (double *)d_ur, g.s));
 }
 
 // t == NULL: only read the current window (get_nmpc_ref_from_long_list); else advance first (get_nmpc_pts)
 int ndp_ref_list_window(ndp_handle *h, const double *t, double *xr, double *ur)
 {
-    if (!h || !xr || !ur) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, xr && ur);
+    if (g.rc) return g.rc;
     int rc = 0;
     if (t) {
         NDP_HIP(h, hipMemcpyAsync(h->sThr, t, (size_t)h->cfg.batch * 8, hipMemcpyHostToDevice, h->stream));
@@ -3786,8 +3754,7 @@ int ndp_ref_list_window(ndp_handle *h, const double *t, double *xr, double *ur)
     if ((rc = launch_list_window(h, h->sxr, h->sur, h->stream))) return rc;
     NDP_HIP(h, hipMemcpyAsync(xr, h->sxr, nxs(h) * 8, hipMemcpyDeviceToHost, h->stream));
     NDP_HIP(h, hipMemcpyAsync(ur, h->sur, nus(h) * 8, hipMemcpyDeviceToHost, h->stream));
-    NDP_HIP(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return g.synced(0);
 }
 
 // ---- the node's control tick, end to end on the device (nmpc_node.py:211-231; kernels: rti_kernel<..., TICK>, or tick_pre_kernel + rti_kernel)
@@ -3802,10 +3769,8 @@ static int ensure_tick(ndp_handle *h)
 
 int ndp_tick_config(ndp_handle *h, const int32_t *other_index, int gate_on_odometry)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_config");
-    if (!h) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, true, nullptr, "ndp_tick_config");
+    if (g.rc) return g.rc;
     int rc = wait_all(h);
     if (rc) return rc;
     if ((rc = ensure_tick(h))) return rc;
@@ -3839,10 +3804,8 @@ int ndp_tick_config(ndp_handle *h, const int32_t *other_index, int gate_on_odome
 // Same arithmetic as the one-launch tick with the neighbour in the same handle (bit-equal: tests/test_tick.py).
 int ndp_tick_config_remote(ndp_handle *h, const void *d_windows, int stride, int64_t rows, const int32_t *other_index, int gate_on_odometry)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_config_remote");
-    if (!h || !d_windows || !other_index) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, d_windows && other_index, nullptr, "ndp_tick_config_remote");
+    if (g.rc) return g.rc;
     int rc = wait_all(h);
     if (rc) return rc;
     if ((rc = ensure_tick(h))) return rc;
@@ -3864,20 +3827,60 @@ int ndp_tick_config_remote(ndp_handle *h, const void *d_windows, int stride, int
 // nmpc_ctl.reset(*ref_pub.get_nmpc_ref_from_long_list()) (nmpc_node.py:92,151-152): the iterate := the list's current window
 int ndp_tick_reset(ndp_handle *h)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_reset");
-    if (!h) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, true, nullptr, "ndp_tick_reset");
+    if (g.rc) return g.rc;
     if (h->slots_busy) { h->err = "ndp_tick_reset: ticks are still in flight (ndp_tick_end them first)"; return -14; }
     int rc = wait_all(h);
     if (rc) return rc;
     if ((rc = launch_list_window(h, h->dX, h->dU, h->stream))) return rc;
     NDP_HIP(h, hipMemsetAsync(h->dAct, 0, act_bytes(h), h->stream));      // reset(): the QPs start from an empty active set
-    NDP_HIP(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return g.synced(0);
 }
 
 enum { TICK_ESTIMATE = NDP_TICK_ESTIMATE, TICK_WANT_U0 = NDP_TICK_WANT_U0, TICK_T_UNIFORM = NDP_TICK_T_UNIFORM };
+
+// tick_pre_kernel's arguments.  adv: the list is advanced, its new entry the point at t[b] (device-accessible), or t_all for every vehicle
+// when t is null, + T_horizon.  est: the estimator runs on vz[B] (null: column 5 of x_odom[B][10]) and throttle[B] (null: the thrust
+// this handle commanded last tick).  pv: the advanced window's position / velocity columns also go there (ndp_xchg_tick_begin).
+static TickPre tick_pre(const ndp_handle *h, bool adv, const double *t, double t_all, bool est, const double *x_odom, const double *vz,
+                        const double *throttle, double *pv = nullptr)
+{
+    TickPre a{};
+    a.cf = ref_cfg(h, h->cfg.N * h->cfg.dt);
+    if (adv) {
+        const TrajView tv = traj_view(h);
+        a.coeff = tv.coeff; a.tcum = tv.tcum; a.tseg = tv.tseg; a.fpt = tv.fpt; a.seg_hint = tv.hint;
+    }
+    a.t = t; a.t_all = t_all; a.advance = adv ? 1 : 0;
+    a.rg = ring_geom(h);
+    a.j_new = h->list_n + (unsigned long long)a.rg.ring();
+    a.rx = h->dRingX; a.ru = h->dRingU;
+    a.thr = thr_cfg(h); a.st = h->dThr;
+    a.vz = vz ? vz : x_odom + 5; a.vz_pitch = vz ? 1 : NX;
+    a.throttle = throttle ? throttle : h->dTickThrust;
+    a.est = est ? 1 : 0;
+    if (pv) { a.pv = pv; a.pv_slot = a.rg.slot(h->list_n + 1); }
+    return a;
+}
+
+// the same work inside the one-launch tick (TickArgs), which reads the trajectory's segment cache the last such tick wrote
+static TickArgs tick_args(const ndp_handle *h, const TickPre &a)
+{
+    TickArgs ta{};
+    if (a.advance) {
+        const TrajView tv = traj_view(h);
+        ta.coeff = a.coeff; ta.tcum = a.tcum; ta.tseg = a.tseg; ta.fpt = a.fpt; ta.n_seg = a.cf.n_seg;
+        ta.segc = tv.segc[h->segc_par]; ta.segc_wr = tv.segc[h->segc_par ^ 1];
+    }
+    ta.t = a.t; ta.t_all = a.t_all; ta.advance = a.advance;
+    ta.toff = a.cf.toff; ta.mass = a.cf.mass; ta.g = a.cf.g;
+    ta.j_new = a.j_new; ta.new_slot = a.rg.slot(a.j_new);
+    ta.rg = a.rg; ta.rx = a.rx; ta.ru = a.ru;
+    ta.thr = a.thr; ta.st = a.st;
+    ta.vz = a.vz; ta.vz_pitch = a.vz_pitch; ta.throttle = a.throttle;
+    ta.est = a.est;
+    return ta;
+}
 
 // One tick's launches on `s`.  Every pointer is device-accessible (HBM or page-locked host memory): x_odom[B][10]; t[B] or null (the
 // list is not advanced: hover at a fixed point, or a vehicle between two trajectories); vz[B] or null (column 5 of x_odom);
@@ -3904,45 +3907,16 @@ static int tick_enqueue(ndp_handle *h, hipStream_t s, const double *x_odom, bool
                             (!h->dTickIndex || can_fuse(h));
     // the list position and the cache's copies move on only when the tick's launches have been accepted (below)
     const unsigned long long n_after = h->list_n + (adv ? 1ull : 0ull);
-    TickArgs ta{};
-    if (one_launch && (adv || est)) {
-        if (adv) {
-            const size_t Bs = (size_t)B, S = (size_t)h->traj_seg;
-            ta.coeff = h->dTraj; ta.tcum = ta.coeff + Bs * S * 28; ta.tseg = ta.tcum + Bs * (S + 1); ta.fpt = ta.tseg + Bs * S;
-            {   // the segment cache's two copies (tick_cache_store): [B][SEGC_PER] behind final_pt, the other behind the segment hints
-                double *c0 = const_cast<double *>(ta.fpt + Bs * 3), *c1 = c0 + Bs * SEGC_PER + (Bs * 4 + 7) / 8;
-                ta.segc = h->segc_par ? c1 : c0;
-                ta.segc_wr = h->segc_par ? c0 : c1;
-            }
-            ta.n_seg = h->traj_seg;
+    TickArgs ta;
+    if (adv || est) {
+        const TickPre a = tick_pre(h, adv, t, t_all, est, x_odom, vz, throttle);
+        if (one_launch) {
+            ta = tick_args(h, a);
+            so.tick = &ta;
+        } else {
+            hipLaunchKernelGGL(tick_pre_kernel, dim3((B + 63) / 64), dim3(64), 0, s, a);
+            NDP_HIP(h, hipGetLastError());
         }
-        ta.t = t; ta.t_all = t_all; ta.advance = adv ? 1 : 0;
-        ta.toff = h->cfg.N * h->cfg.dt; ta.mass = h->cfg.mass; ta.g = h->cfg.gravity;
-        ta.j_new = h->list_n + (unsigned long long)rg.ring();
-        ta.new_slot = rg.slot(ta.j_new);
-        ta.rg = rg; ta.rx = h->dRingX; ta.ru = h->dRingU;
-        ta.thr = thr_cfg(h); ta.st = h->dThr;
-        ta.vz = vz ? vz : x_odom + 5; ta.vz_pitch = vz ? 1 : NX;
-        ta.throttle = throttle ? throttle : h->dTickThrust;
-        ta.est = est ? 1 : 0;
-        so.tick = &ta;
-    } else if (adv || est) {
-        TickPre a{};
-        a.cf = ref_cfg(h, h->cfg.N * h->cfg.dt);
-        if (adv) {
-            const size_t Bs = (size_t)B, S = (size_t)h->traj_seg;
-            a.coeff = h->dTraj; a.tcum = a.coeff + Bs * S * 28; a.tseg = a.tcum + Bs * (S + 1); a.fpt = a.tseg + Bs * S;
-            a.seg_hint = reinterpret_cast<int *>(const_cast<double *>(a.fpt + Bs * 3 + Bs * SEGC_PER));
-        }
-        a.t = t; a.t_all = t_all; a.advance = adv ? 1 : 0;
-        a.j_new = h->list_n + (unsigned long long)rg.ring();
-        a.rg = rg; a.rx = h->dRingX; a.ru = h->dRingU;
-        a.thr = thr_cfg(h); a.st = h->dThr;
-        a.vz = vz ? vz : x_odom + 5; a.vz_pitch = vz ? 1 : NX;
-        a.throttle = throttle ? throttle : h->dTickThrust;
-        a.est = est ? 1 : 0;
-        hipLaunchKernelGGL(tick_pre_kernel, dim3((B + 63) / 64), dim3(64), 0, s, a);
-        NDP_HIP(h, hipGetLastError());
     }
     const size_t slot = rg.slot(n_after);
     Neigh nb;
@@ -3963,54 +3937,34 @@ static int tick_enqueue(ndp_handle *h, hipStream_t s, const double *x_odom, bool
 
 int ndp_tick_advance_device(ndp_handle *h, const void *d_x_odom, const void *d_t, const void *d_vz, const void *d_throttle, int flags, void *stream)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_advance_device");
-    if (!h || !d_x_odom) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, d_x_odom, stream, "ndp_tick_advance_device");
+    if (g.rc) return g.rc;
     int rc = ensure_tick(h);
     if (rc) return rc;
     if (!h->dRingX) { h->err = "ndp_tick_advance: no reference list (ndp_ref_list_fix_pt, or ndp_ref_set_trajectory + ndp_ref_list_reset, first)"; return -11; }
     const bool adv = d_t != nullptr, est = (flags & TICK_ESTIMATE) != 0, uni = adv && (flags & TICK_T_UNIFORM);
     if (adv && !h->dTraj) { h->err = "ndp_tick_advance: a trajectory time was given but ndp_ref_set_trajectory was never called"; return -11; }
     if (adv || est) {
-        const int B = h->cfg.batch;
-        const RingGeom rg = ring_geom(h);
-        TickPre a{};
-        a.cf = ref_cfg(h, h->cfg.N * h->cfg.dt);
-        if (adv) {
-            const size_t Bs = (size_t)B, S = (size_t)h->traj_seg;
-            a.coeff = h->dTraj; a.tcum = a.coeff + Bs * S * 28; a.tseg = a.tcum + Bs * (S + 1); a.fpt = a.tseg + Bs * S;
-            a.seg_hint = reinterpret_cast<int *>(const_cast<double *>(a.fpt + Bs * 3 + Bs * SEGC_PER));
-        }
-        a.t = uni ? nullptr : (const double *)d_t; a.t_all = uni ? *(const double *)d_t : 0.0; a.advance = adv ? 1 : 0;
-        a.j_new = h->list_n + (unsigned long long)rg.ring();
-        a.rg = rg; a.rx = h->dRingX; a.ru = h->dRingU;
-        a.thr = thr_cfg(h); a.st = h->dThr;
-        a.vz = d_vz ? (const double *)d_vz : (const double *)d_x_odom + 5; a.vz_pitch = d_vz ? 1 : NX;
-        a.throttle = d_throttle ? (const double *)d_throttle : h->dTickThrust;
-        a.est = est ? 1 : 0;
-        hipLaunchKernelGGL(tick_pre_kernel, dim3((B + 63) / 64), dim3(64), 0, s, a);
+        const TickPre a = tick_pre(h, adv, uni ? nullptr : (const double *)d_t, uni ? *(const double *)d_t : 0.0, est, (const double *)d_x_odom,
+                                   (const double *)d_vz, (const double *)d_throttle);
+        hipLaunchKernelGGL(tick_pre_kernel, dim3((h->cfg.batch + 63) / 64), dim3(64), 0, g.s, a);
         NDP_HIP(h, hipGetLastError());
         if (adv) ++h->list_n;
     }
-    return note_stream(h, s);
+    return g.noted(0);
 }
 
 int ndp_tick_window_pv_device(ndp_handle *h, void *d_pv, void *stream)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_window_pv_device");
-    if (!h || !d_pv) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, d_pv, stream, "ndp_tick_window_pv_device");
+    if (g.rc) return g.rc;
     if (!h->dRingX) { h->err = "ndp_tick_window_pv: no reference list"; return -11; }
     const RingGeom rg = ring_geom(h);
     const size_t B = h->cfg.batch, n = B * (size_t)(h->cfg.N + 1) * 3;
-    hipLaunchKernelGGL(pack_pv_list_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->dRingX + rg.slot(h->list_n) * 10, rg.px(),
+    hipLaunchKernelGGL(pack_pv_list_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.s, h->dRingX + rg.slot(h->list_n) * 10, rg.px(),
                        h->cfg.N + 1, (double *)d_pv, B);
     NDP_HIP(h, hipGetLastError());
-    return note_stream(h, s);
+    return g.noted(0);
 }
 
 // Stage 2 and the exchange in one call, on the tick's own stream: this tick's window columns packed out of the list into the
@@ -4018,12 +3972,10 @@ int ndp_tick_window_pv_device(ndp_handle *h, void *d_pv, void *stream)
 // front of ndp_tick_step_device by stream order alone (no event operation, no second stream: the tick's chain is serial anyway).
 int ndp_xchg_tick_windows(ndp_xchg *x, ndp_handle *h, void *d_gathered, void *stream)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_xchg_tick_windows");
-    if (!x || !h || !d_gathered) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
+    Entry g(h, x && d_gathered, stream, "ndp_xchg_tick_windows");
+    if (g.rc) return g.rc;
     if (x->device != h->cfg.device) { h->err = "ndp_xchg_tick_windows: the exchange and the handle live on different devices"; return -1; }
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = g.s;
     if (!h->dRingX) { h->err = "ndp_xchg_tick_windows: no reference list"; return -11; }
     const RingGeom rg = ring_geom(h);
     const size_t B = h->cfg.batch, rows = B * (size_t)(h->cfg.N + 1), n = rows * 3;
@@ -4037,7 +3989,7 @@ int ndp_xchg_tick_windows(ndp_xchg *x, ndp_handle *h, void *d_gathered, void *st
     NDP_HIP(h, hipGetLastError());
     const int r = g_rccl.allgather(x->send, d_gathered, rows * 6, /* ncclFloat64 */ 8, x->comm, s);
     if (r != 0) { x->err = g_rccl.errstr ? g_rccl.errstr(r) : "ncclAllGather failed"; h->err = "ndp_xchg_tick_windows: " + x->err; return -22; }
-    return note_stream(h, s);
+    return g.noted(0);
 }
 
 // stage 3 on `s` (h->mu held): the control step of the window at list position `pos`, neighbour rows out of `windows`
@@ -4058,13 +4010,9 @@ static int tick_step_enqueue(ndp_handle *h, hipStream_t s, const double *x_odom,
 
 int ndp_tick_step_device(ndp_handle *h, const void *d_x_odom, void *d_cmd, void *d_u0, void *stream)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_step_device");
-    if (!h || !d_x_odom || !d_cmd) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
-    int rc = tick_step_enqueue(h, s, (const double *)d_x_odom, (double *)d_cmd, (double *)d_u0, h->tick_remote, h->list_n);
-    return rc ? rc : note_stream(h, s);
+    Entry g(h, d_x_odom && d_cmd, stream, "ndp_tick_step_device");
+    if (g.rc) return g.rc;
+    return g.noted(tick_step_enqueue(h, g.s, (const double *)d_x_odom, (double *)d_cmd, (double *)d_u0, h->tick_remote, h->list_n));
 }
 
 // ---- the remote tick with the exchange ONE CONTROL PERIOD AHEAD.  A vehicle's window is a function of time alone (the list advance
@@ -4125,11 +4073,9 @@ int ndp_xchg_tick_async(ndp_xchg *x, int on)
 
 int ndp_xchg_tick_begin(ndp_xchg *x, ndp_handle *h, const void *d_t, int flags, void *d_gathered)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_xchg_tick_begin");
-    if (!x || !h || !d_gathered) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
+    Entry g(h, x && d_gathered, nullptr, "ndp_xchg_tick_begin");
+    if (g.rc) return g.rc;
     if (x->device != h->cfg.device) { h->err = "ndp_xchg_tick_begin: the exchange and the handle live on different devices"; return -1; }
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
     int rc = ensure_tick(h);
     if (rc) return rc;
     if (!h->dRingX) { h->err = "ndp_xchg_tick_begin: no reference list"; return -11; }
@@ -4172,17 +4118,9 @@ int ndp_xchg_tick_begin(ndp_xchg *x, ndp_handle *h, const void *d_t, int flags, 
     }
     if (d_t) {
         const bool uni = (flags & TICK_T_UNIFORM) != 0;
-        TickPre &a = j.a;
-        a.cf = ref_cfg(h, h->cfg.N * h->cfg.dt);
-        const size_t Bs = B, S = (size_t)h->traj_seg;
-        a.coeff = h->dTraj; a.tcum = a.coeff + Bs * S * 28; a.tseg = a.tcum + Bs * (S + 1); a.fpt = a.tseg + Bs * S;
-        a.seg_hint = reinterpret_cast<int *>(const_cast<double *>(a.fpt + Bs * 3 + Bs * SEGC_PER));
-        a.t = uni ? nullptr : (const double *)d_t; a.t_all = uni ? *(const double *)d_t : 0.0; a.advance = 1;
-        a.j_new = h->list_n + (unsigned long long)rg.ring();
-        a.rg = rg; a.rx = h->dRingX; a.ru = h->dRingU;
-        a.thr = thr_cfg(h); a.st = h->dThr;
-        a.vz = h->dTickThrust; a.vz_pitch = 1; a.throttle = h->dTickThrust; a.est = 0;      // (no estimator here: it belongs to the step's side)
-        a.pv = x->send; a.pv_slot = rg.slot(h->list_n + 1);                                 // ... and the advanced window's columns in the same launch
+        // (no estimator here: it belongs to the step's side) ... and the advanced window's columns in the same launch
+        j.a = tick_pre(h, true, uni ? nullptr : (const double *)d_t, uni ? *(const double *)d_t : 0.0, false, nullptr, h->dTickThrust,
+                       nullptr, x->send);
         j.adv = true;
         ++h->list_n;
     } else {
@@ -4205,11 +4143,9 @@ int ndp_xchg_tick_begin(ndp_xchg *x, ndp_handle *h, const void *d_t, int flags, 
 int ndp_xchg_tick_step(ndp_xchg *x, ndp_handle *h, const void *d_x_odom, const void *d_vz, const void *d_throttle, int flags,
                        void *d_cmd, void *d_u0, const void *d_gathered, void *stream)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_xchg_tick_step");
-    if (!x || !h || !d_x_odom || !d_cmd || !d_gathered) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, x && d_x_odom && d_cmd && d_gathered, stream, "ndp_xchg_tick_step");
+    if (g.rc) return g.rc;
+    hipStream_t s = g.s;
     if (x->ahead < 1) { h->err = "ndp_xchg_tick_step: no gather was begun for this tick (ndp_xchg_tick_begin first)"; return -14; }
     int rc = ensure_tick(h);
     if (rc) return rc;
@@ -4218,14 +4154,7 @@ int ndp_xchg_tick_step(ndp_xchg *x, ndp_handle *h, const void *d_x_odom, const v
     const int p = (int)(k % 3u);
     if (x->buf[p] != d_gathered || x->job_n[p] != k) { h->err = "ndp_xchg_tick_step: this tick's gather was begun into another buffer"; return -14; }
     if (flags & TICK_ESTIMATE) {
-        TickPre a{};
-        a.cf = ref_cfg(h, h->cfg.N * h->cfg.dt);
-        a.advance = 0;
-        a.rg = ring_geom(h); a.rx = h->dRingX; a.ru = h->dRingU;
-        a.thr = thr_cfg(h); a.st = h->dThr;
-        a.vz = d_vz ? (const double *)d_vz : (const double *)d_x_odom + 5; a.vz_pitch = d_vz ? 1 : NX;
-        a.throttle = d_throttle ? (const double *)d_throttle : h->dTickThrust;
-        a.est = 1;
+        const TickPre a = tick_pre(h, false, nullptr, 0.0, true, (const double *)d_x_odom, (const double *)d_vz, (const double *)d_throttle);
         hipLaunchKernelGGL(tick_pre_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, a);
         NDP_HIP(h, hipGetLastError());
     }
@@ -4243,21 +4172,17 @@ int ndp_xchg_tick_step(ndp_xchg *x, ndp_handle *h, const void *d_x_odom, const v
     x->steps = k;
     --x->ahead;
     if (slot->seq) { h->track_pending = true; return 0; }     // (the getters wait for the step's own completion event: no second one)
-    return note_stream(h, s);
+    return g.noted(0);
 }
 
 int ndp_tick_device(ndp_handle *h, const void *d_x_odom, const void *d_t, const void *d_vz, const void *d_throttle, int flags,
                     void *d_cmd, void *d_u0, void *stream)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_device");
-    if (!h || !d_x_odom || !d_cmd) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, d_x_odom && d_cmd, stream, "ndp_tick_device");
+    if (g.rc) return g.rc;
     const bool uni = d_t && (flags & TICK_T_UNIFORM);       // (then d_t is HOST memory: one double, read here)
-    int rc = tick_enqueue(h, s, (const double *)d_x_odom, d_t != nullptr, uni ? nullptr : (const double *)d_t, uni ? *(const double *)d_t : 0.0,
-                          (const double *)d_vz, (const double *)d_throttle, flags, (double *)d_cmd, (double *)d_u0, StepOut());
-    return rc ? rc : note_stream(h, s);
+    return g.noted(tick_enqueue(h, g.s, (const double *)d_x_odom, d_t != nullptr, uni ? nullptr : (const double *)d_t, uni ? *(const double *)d_t : 0.0,
+                                (const double *)d_vz, (const double *)d_throttle, flags, (double *)d_cmd, (double *)d_u0, StepOut()));
 }
 
 // host arrays: the inputs of a tick are packed into a slot's page-locked input mirror -- x_odom | t | vz | throttle, 80 + 24 bytes per
@@ -4266,7 +4191,6 @@ int ndp_tick_device(ndp_handle *h, const void *d_x_odom, const void *d_t, const 
 static int tick_begin_locked(ndp_handle *h, const double *x_odom, const double *t, const double *vz, const double *throttle, int flags)
 {
     const size_t B = h->cfg.batch;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
     int rc = ensure_slots(h);
     if (rc) return rc;
     if (h->slots_busy == 2) { h->err = "ndp_tick_begin: two ticks are already in flight (call ndp_tick_end first)"; return -14; }
@@ -4305,7 +4229,6 @@ static int tick_end_locked(ndp_handle *h, double *cmd, double *u0, int32_t *stat
     if (h->slots_busy == 0 || !h->tslot[h->slot_tail].busy) { h->err = "ndp_tick_end: no tick in flight (ndp_tick_begin first)"; return -14; }
     ndp_handle::HostSlot &sl = h->slot[h->slot_tail];
     if (u0 && !h->tslot[h->slot_tail].want_u0) { h->err = "ndp_tick_end: u0 was not requested at ndp_tick_begin (flags bit 1)"; return -15; }
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
     const auto tw0 = std::chrono::steady_clock::now();
     hipError_t e = hipErrorNotReady;
     for (int spin = 0; spin < 4000 && e == hipErrorNotReady; ++spin) e = hipEventQuery(sl.evOut);
@@ -4331,26 +4254,21 @@ static int tick_end_locked(ndp_handle *h, double *cmd, double *u0, int32_t *stat
 
 int ndp_tick_begin(ndp_handle *h, const double *x_odom, const double *t, const double *vz, const double *throttle, int flags)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_begin");
-    if (!h || !x_odom) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    return tick_begin_locked(h, x_odom, t, vz, throttle, flags);
+    Entry g(h, x_odom, nullptr, "ndp_tick_begin");
+    return g.rc ? g.rc : tick_begin_locked(h, x_odom, t, vz, throttle, flags);
 }
 
 int ndp_tick_end(ndp_handle *h, double *cmd, double *u0, int32_t *status_out, int32_t *ipm_iters_out)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_tick_end");
-    if (!h || !cmd) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    return tick_end_locked(h, cmd, u0, status_out, ipm_iters_out);
+    Entry g(h, cmd, nullptr, "ndp_tick_end");
+    return g.rc ? g.rc : tick_end_locked(h, cmd, u0, status_out, ipm_iters_out);
 }
 
 int ndp_tick(ndp_handle *h, const double *x_odom, const double *t, const double *vz, const double *throttle, int flags,
              double *cmd, double *u0, int32_t *status_out, int32_t *ipm_iters_out)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_tick");
-    if (!h || !x_odom || !cmd) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
+    Entry g(h, x_odom && cmd, nullptr, "ndp_tick");      // (begin and end under the one lock)
+    if (g.rc) return g.rc;
     if (h->slots_busy) { h->err = "ndp_tick: steps / ticks begun earlier are still in flight (end them first)"; return -14; }
     int rc = tick_begin_locked(h, x_odom, t, vz, throttle, flags | (u0 ? TICK_WANT_U0 : 0));
     if (rc) return rc;
@@ -4368,38 +4286,31 @@ static int launch_plant(ndp_handle *h, double *d_x, const double *d_u, const dou
 
 int ndp_plant_step_device(ndp_handle *h, void *d_x, const void *d_u, const void *d_f, double dt, int substeps, void *stream)
 {
-    if (!h || !d_x || !d_u || substeps < 1) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
-    int rc = launch_plant(h, (double *)d_x, (const double *)d_u, (const double *)d_f, dt, substeps, s);
-    return rc ? rc : note_stream(h, s);
+    Entry g(h, d_x && d_u && substeps >= 1, stream);
+    if (g.rc) return g.rc;
+    return g.noted(launch_plant(h, (double *)d_x, (const double *)d_u, (const double *)d_f, dt, substeps, g.s));
 }
 
 int ndp_plant_step(ndp_handle *h, double *x, const double *u, const double *f, double dt, int substeps)
 {
-    if (!h || !x || !u || substeps < 1) return -1;
+    Entry g(h, x && u && substeps >= 1);
+    if (g.rc) return g.rc;
     const size_t B = h->cfg.batch;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
     NDP_HIP(h, hipMemcpyAsync(h->sx0, x, B * 80, hipMemcpyHostToDevice, h->stream));
     NDP_HIP(h, hipMemcpyAsync(h->su0, u, B * 32, hipMemcpyHostToDevice, h->stream));
     if (f) NDP_HIP(h, hipMemcpyAsync(h->sThr, f, B * 24, hipMemcpyHostToDevice, h->stream));
     int rc = launch_plant(h, h->sx0, h->su0, f ? h->sThr : nullptr, dt, substeps, h->stream);
     if (rc) return rc;
     NDP_HIP(h, hipMemcpyAsync(x, h->sx0, B * 80, hipMemcpyDeviceToHost, h->stream));
-    NDP_HIP(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return g.synced(0);
 }
 
 // ---- f4: closed-loop rollout, everything enqueued back to back on one stream, nothing returns to the host in between
 int ndp_rollout_device(ndp_handle *h, int ticks, double t0, double dt_tick, int substeps, void *d_x, void *d_log, void *stream)
 {
-    if (h && h->sens_level) return sens_refuse(h, "ndp_rollout_device");
-    if (!h || ticks < 1 || substeps < 1 || !d_x) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, ticks >= 1 && substeps >= 1 && d_x, stream, "ndp_rollout_device");
+    if (g.rc) return g.rc;
+    hipStream_t s = g.s;
     if (h->cfg.use_fd) { h->err = "ndp_rollout_device: the rollout drives the NMPC model (use_fd = 0)"; return -8; }
     const size_t B = h->cfg.batch;
     double *x = (double *)d_x, *log = (double *)d_log;
@@ -4413,7 +4324,7 @@ int ndp_rollout_device(ndp_handle *h, int ticks, double t0, double dt_tick, int 
         if ((rc = launch_plant(h, x, h->su0, nullptr, dt_tick, substeps, s))) return rc;
         if (log) NDP_HIP(h, hipMemcpyAsync(log + (size_t)k * B * NX, x, B * NX * 8, hipMemcpyDeviceToDevice, s));
     }
-    return note_stream(h, s);
+    return g.noted(0);
 }
 
 // test/profiling hook: every instance writes its phase stamps (shader clock) to [B][NDP_NSTAMP] doubles
@@ -4471,11 +4382,8 @@ int ndp_sens_enable(ndp_handle *h, int level)
     if ((rc = get(h->dSensU0, n0))) return rc;
     if (level == 2 && ((rc = get(h->dSensU, nu)) || (rc = get(h->dSensX, nx)))) return rc;
     const int lds_bytes = (int)((size_t)h->lds_per_wave * sizeof(double) * h->waves);
-    const void *fns[] = {(const void *)RTI_SENS_K(4, false, 20, 0), (const void *)RTI_SENS_K(4, true, 20, 0),
-                         (const void *)RTI_SENS_K(4, false, 20, 1), (const void *)RTI_SENS_K(4, true, 20, 1), (const void *)RTI_SENS_K(4, false, 20, 2),
-                         (const void *)RTI_SENS_K(4, false, 0, 0), (const void *)RTI_SENS_K(4, true, 0, 0),
-                         (const void *)RTI_SENS_K(2, false, 0, 0), (const void *)RTI_SENS_K(2, true, 0, 0)};
-    for (const void *fn : fns) NDP_HIP(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    for (const RtiKern &k : k_rti)
+        if (k.sens) NDP_HIP(h, hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
     NDP_HIP(h, hipStreamSynchronize(h->stream));
     h->sens_level = level;
     return 0;
@@ -4506,9 +4414,8 @@ int ndp_refine_active(ndp_handle *h) { return h ? (int)(h->cfg.ipm_refine > 0 &&
 
 int ndp_synchronize(ndp_handle *h)
 {
-    if (!h) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    Entry g(h, true);
+    if (g.rc) return g.rc;
     return wait_all(h);
 }
 
