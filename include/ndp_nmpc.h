@@ -299,6 +299,25 @@ void *ndp_device_sens_u0(ndp_handle *h);
 void *ndp_device_sens_u(ndp_handle *h);
 void *ndp_device_sens_x(ndp_handle *h);
 
+/* Parameter sensitivities: the derivative of the same QP with respect to its data xr [N+1][10], ur [N][4] and the force f [N+1][3], with the
+ * linearisation point, x0 and the final active set held fixed -- the same three cases as above (fixed set: exact, the rows of pinned
+ * inputs exactly 0; interior point: its last Newton system; nonzero status: NaN).  Row i = d u0[i]:
+ *   du0/dxr [B][4][N+1][10], du0/dur [B][4][N][4], du0/df [B][4][N+1][3] (float64; the force itself is read as float32).
+ * Stage 0's reference rows are 0 (x0 is fixed) and so is f_N (it reaches no dynamics).  The force enters the dynamics additively, so
+ * du0/df is written in every configuration: with cfg.use_fd = 0 it is the derivative with respect to an additive force at f = 0.
+ * Computed by the adjoint of the last Riccati sweep (RtiWave::psens_out) in the same launch as the x0 sensitivities.  Served by the
+ * fused step (any N <= 27) and by every N = 20 form; an unfused step at another horizon returns -2 (no kernel: see DESIGN.md).
+ * ndp_sens_params_enable(h, 1): needs ndp_sens_enable level >= 1 (else -2), so every refusal of a sensitivity handle covers them; 0 frees
+ * the buffers, and so does ndp_sens_enable(h, 0).  ndp_sens_params_enabled: 1 / 0.
+ * ndp_get_sens_params: waits for the handle's work and copies; any pointer may be NULL; -2 when off.
+ * ndp_device_sens_xr / _ur / _f: the device buffers (NULL when off). */
+int ndp_sens_params_enable(ndp_handle *h, int on);
+int ndp_sens_params_enabled(ndp_handle *h);
+int ndp_get_sens_params(ndp_handle *h, double *du0_dxr, double *du0_dur, double *du0_df);
+void *ndp_device_sens_xr(ndp_handle *h);
+void *ndp_device_sens_ur(ndp_handle *h);
+void *ndp_device_sens_f(ndp_handle *h);
+
 /* Per-kernel timing with HIP events recorded on the stream each kernel is launched on:
  * on = n > 0 brackets every n-th launch of each kernel (n = 1: every launch), on = 0 stops and clears.
  * ndp_timing_read: name is "rti" or "mlp"; total over the bracketed launches.  Returns <0 if nothing was timed. */

@@ -54,6 +54,7 @@ EXPORTS = [
     "ndp_step_ex_f64", "ndp_refine_active", "ndp_get_active_set", "ndp_set_active_set", "ndp_debug_host_info", "ndp_tick_config", "ndp_tick_reset", "ndp_tick_begin", "ndp_tick_end", "ndp_tick", "ndp_tick_device",
     "ndp_tick_config_remote", "ndp_tick_advance_device", "ndp_tick_window_pv_device", "ndp_tick_step_device", "ndp_xchg_tick_windows", "ndp_xchg_tick_begin", "ndp_xchg_tick_step", "ndp_xchg_tick_async",
     "ndp_sens_enable", "ndp_sens_level", "ndp_get_sens", "ndp_device_sens_u0", "ndp_device_sens_u", "ndp_device_sens_x",
+    "ndp_sens_params_enable", "ndp_sens_params_enabled", "ndp_get_sens_params", "ndp_device_sens_xr", "ndp_device_sens_ur", "ndp_device_sens_f",
 ]
 
 _lib = None
@@ -127,7 +128,10 @@ def load():
     lib.ndp_sens_enable.argtypes = [vp, C.c_int]
     lib.ndp_sens_level.argtypes = [vp]
     lib.ndp_get_sens.argtypes = [vp] * 4
-    for name in ("ndp_device_sens_u0", "ndp_device_sens_u", "ndp_device_sens_x"):
+    lib.ndp_sens_params_enable.argtypes = [vp, C.c_int]
+    lib.ndp_sens_params_enabled.argtypes = [vp]
+    lib.ndp_get_sens_params.argtypes = [vp] * 4
+    for name in ("ndp_device_sens_u0", "ndp_device_sens_u", "ndp_device_sens_x", "ndp_device_sens_xr", "ndp_device_sens_ur", "ndp_device_sens_f"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = vp
     lib.ndp_set_active_set.argtypes = [vp] * 2

@@ -464,6 +464,41 @@ class BatchedNMPC:
             out.append(torch.as_tensor(_DevMem(ptr, shape), device=dev) if ptr else None)
         return tuple(out)
 
+    def enable_param_sensitivity(self, on=True):
+        """Every later step also writes the derivative of its QP with respect to xr, ur and the force f (ndp_sens_params_enable;
+        include/ndp_nmpc.h): du0/dxr [B,4,N+1,10], du0/dur [B,4,N,4], du0/df [B,4,N+1,3].  Needs enable_sensitivity(1 or 2) first;
+        enable_sensitivity(0) switches them off too.  At N != 20 the step must be the fused one (neighbour windows given)."""
+        self._check(self._lib.ndp_sens_params_enable(self._h, int(bool(on))), "ndp_sens_params_enable")
+
+    @property
+    def param_sensitivity_enabled(self):
+        return bool(self._lib.ndp_sens_params_enabled(self._h) == 1)
+
+    def param_sensitivity(self):
+        """(du0_dxr [B,4,N+1,10], du0_dur [B,4,N,4], du0_df [B,4,N+1,3]) of the last step, numpy float64.  Row i = d u0[i]; the rows of
+        pinned inputs are 0, stage 0's reference rows and f_N are 0; an instance with a nonzero status is NaN throughout."""
+        if not self.param_sensitivity_enabled:
+            raise NdpError("parameter sensitivities are not enabled (enable_param_sensitivity)")
+        dxr = np.empty((self.B, 4, self.N + 1, 10))
+        dur = np.empty((self.B, 4, self.N, 4))
+        df = np.empty((self.B, 4, self.N + 1, 3))
+        self._check(self._lib.ndp_get_sens_params(self._h, _lib.ptr(dxr), _lib.ptr(dur), _lib.ptr(df)), "ndp_get_sens_params")
+        return dxr, dur, df
+
+    def device_param_sensitivity(self):
+        """The device buffers as CUDA tensor views (no copy): (du0_dxr [B,4,N+1,10], du0_dur [B,4,N,4], du0_df [B,4,N+1,3]), float64.
+        Valid once the step's stream has reached them; the next step overwrites them."""
+        import torch
+        from .dist import _DevMem
+        if not self.param_sensitivity_enabled:
+            raise NdpError("parameter sensitivities are not enabled (enable_param_sensitivity)")
+        dev = torch.device("cuda", self.cfg.device)
+        out = []
+        for fn, shape in ((self._lib.ndp_device_sens_xr, (self.B, 4, self.N + 1, 10)), (self._lib.ndp_device_sens_ur, (self.B, 4, self.N, 4)),
+                          (self._lib.ndp_device_sens_f, (self.B, 4, self.N + 1, 3))):
+            out.append(torch.as_tensor(_DevMem(fn(self._h), shape), device=dev))
+        return tuple(out)
+
     # ------------------------------------------------------------------ HBM-resident API (torch CUDA tensors)
     @staticmethod
     def _dptr(t, dtype, shape):

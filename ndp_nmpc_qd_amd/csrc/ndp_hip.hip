@@ -264,6 +264,10 @@ struct SensArgs {
     double *du0 = nullptr, *dU = nullptr, *dX = nullptr;
     int level = 0;
 };
+// rti_psens_kernel's further outputs (ndp_sens_params_enable): [B][4][N+1][10], [B][4][N][4], [B][4][N+1][3]
+struct PSensArgs {
+    double *dxr = nullptr, *dur = nullptr, *df = nullptr;
+};
 
 // Arguments a kernel needs LATE (the tick's estimator constants, the list's geometry for the new entry's store, the trajectory arrays
 // of the rare slow path), fetched where they are used.  Read as ordinary members of `ka` the compiler requests every argument at the
@@ -311,8 +315,9 @@ template <class T> using gptr = __attribute__((address_space(1))) T *;
 template <int NSLOT, int WAVES, bool FUSED, int NC = 0, int PREC = 0, int NRC = (NC ? 1 : 0), int QMODE = 0, bool TICK = false>
 __global__ __launch_bounds__(64 * WAVES) NDP_RTI_ATTR void rti_kernel(KernArgs ka)
 {
-    constexpr bool SENS = false;
+    constexpr bool SENS = false, PSENS = false;
     const SensArgs sa{};
+    const PSensArgs pa{};
     extern __shared__ __attribute__((aligned(16))) double smem[];
     __shared__ unsigned wg_done;     // prefetched-force launches: the workgroup's waves that hold their force values (see LateArgs)
 #include "rti_kernel_body.inc"
@@ -324,7 +329,20 @@ template <int WAVES, bool FUSED, int NC, int QMODE>
 __global__ __launch_bounds__(64 * WAVES) void rti_sens_kernel(KernArgs ka, SensArgs sa)
 {
     constexpr int NSLOT = 3, PREC = 0, NRC = NC ? 1 : 0;
-    constexpr bool TICK = false, SENS = true;
+    constexpr bool TICK = false, SENS = true, PSENS = false;
+    const PSensArgs pa{};
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    __shared__ unsigned wg_done;
+#include "rti_kernel_body.inc"
+}
+
+// ... and also with its parameter sensitivities (ndp_sens_params_enable): du0/dxr, du0/dur, du0/df of the same QP, behind the x0 ones
+// (level >= 1), for the same shapes but the unfused run-time horizon (k_rti: that instantiation came out with a scratch frame).
+template <int WAVES, bool FUSED, int NC, int QMODE>
+__global__ __launch_bounds__(64 * WAVES) void rti_psens_kernel(KernArgs ka, SensArgs sa, PSensArgs pa)
+{
+    constexpr int NSLOT = 3, PREC = 0, NRC = NC ? 1 : 0;
+    constexpr bool TICK = false, SENS = true, PSENS = true;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     __shared__ unsigned wg_done;
 #include "rti_kernel_body.inc"
@@ -1777,6 +1795,9 @@ struct RtiK { static constexpr auto fn = rti_kernel<3, (WAVES == 2 && NC == 20 ?
 template <int WAVES, bool FUSED, int NC, int QMODE>
 struct RtiSensK { static constexpr auto fn = rti_sens_kernel<4, (FUSED && NC == 20 && QMODE == 0), 20, NDP_DEV_QMODE>; };
 #define RTI_SENS_K(...) (RtiSensK<__VA_ARGS__>::fn)
+template <int WAVES, bool FUSED, int NC, int QMODE>
+struct RtiPSensK { static constexpr auto fn = rti_psens_kernel<4, (FUSED && NC == 20 && QMODE == 0), 20, NDP_DEV_QMODE>; };
+#define RTI_PSENS_K(...) (RtiPSensK<__VA_ARGS__>::fn)
 #elif defined(NDP_DEV_COND_ONLY)
 // compile / register studies of the condensed study kernels: every instantiation collapses onto rti_kernel<5, 1, false, 0, 5 or 6>
 template <int NSLOT, int WAVES, bool FUSED, int NC = 0, int PREC = 0, int NRC = (NC ? 1 : 0), int QMODE = 0, bool TICK = false>
@@ -1785,6 +1806,9 @@ struct RtiK { static constexpr auto fn = rti_kernel<5, 1, false, 0, (PREC == 6 ?
 template <int WAVES, bool FUSED, int NC, int QMODE>       // (and the sensitivity kernels onto one)
 struct RtiSensK { static constexpr auto fn = rti_sens_kernel<4, false, 20, 0>; };
 #define RTI_SENS_K(...) (RtiSensK<__VA_ARGS__>::fn)
+template <int WAVES, bool FUSED, int NC, int QMODE>
+struct RtiPSensK { static constexpr auto fn = rti_psens_kernel<4, false, 20, 0>; };
+#define RTI_PSENS_K(...) (RtiPSensK<__VA_ARGS__>::fn)
 #elif defined(NDP_DEV_N40_ONLY)
 // register studies of config 5's shape (scripts/dev_regs.sh): every instantiation collapses onto rti_kernel<5, 2, false, 40, 0, 2, NDP_DEV_QMODE>
 #ifndef NDP_DEV_QMODE
@@ -1796,10 +1820,15 @@ struct RtiK { static constexpr auto fn = rti_kernel<5, 2, false, 40, 0, 2, NDP_D
 template <int WAVES, bool FUSED, int NC, int QMODE>       // (and the sensitivity kernels onto one)
 struct RtiSensK { static constexpr auto fn = rti_sens_kernel<4, false, 20, 0>; };
 #define RTI_SENS_K(...) (RtiSensK<__VA_ARGS__>::fn)
+template <int WAVES, bool FUSED, int NC, int QMODE>
+struct RtiPSensK { static constexpr auto fn = rti_psens_kernel<4, false, 20, 0>; };
+#define RTI_PSENS_K(...) (RtiPSensK<__VA_ARGS__>::fn)
 #else
 #define RTI_K(...) (rti_kernel<__VA_ARGS__>)
-// RTI_SENS_K(WAVES, FUSED, NC, QMODE): the rti_sens_kernel instantiation to reference (collapsed like RTI_K in development builds)
+// RTI_SENS_K / RTI_PSENS_K(WAVES, FUSED, NC, QMODE): the rti_sens_kernel / rti_psens_kernel instantiation to reference (collapsed like
+// RTI_K in development builds)
 #define RTI_SENS_K(...) (rti_sens_kernel<__VA_ARGS__>)
+#define RTI_PSENS_K(...) (rti_psens_kernel<__VA_ARGS__>)
 #endif
 
 // ---- host pack threads.  A host-array step first moves the caller's (pageable) arrays into a page-locked mirror the kernel can
@@ -1922,6 +1951,8 @@ struct ndp_handle {
     // ndp_sens_enable: initial-state sensitivities of every step's QP (rti_sens_kernel): level 0 off, 1 du0/dx0, 2 also dU/dx0 and dX/dx0
     int sens_level = 0;
     double *dSensU0 = nullptr, *dSensU = nullptr, *dSensX = nullptr;   // [B][4][10], [B][N][4][10], [B][N+1][10][10] (the last two: level 2)
+    // ndp_sens_params_enable: du0/dxr [B][4][N+1][10], du0/dur [B][4][N][4], du0/df [B][4][N+1][3] (rti_psens_kernel); null: off
+    double *dPSensXr = nullptr, *dPSensUr = nullptr, *dPSensF = nullptr;
     double *dThr = nullptr;    // hover-throttle estimator state, SoA [8][B]
     double *dStamps = nullptr; // [B][NDP_NSTAMP] whole-batch phase stamps (ndp_debug_stamps)
     double *dTraj = nullptr;   // f1: the trajectories and the tick's caches (layout: TrajView)
@@ -2076,7 +2107,7 @@ static bool queue_shape(const ndp_handle *h)
 struct RtiKern {
     const void *fn;
     int waves;                 // instances per workgroup: the launch geometry
-    bool sens;                 // rti_sens_kernel (KernArgs, SensArgs), else rti_kernel (KernArgs)
+    bool sens;                 // rti_sens_kernel (KernArgs, SensArgs) or rti_psens_kernel (KernArgs, SensArgs, PSensArgs), else rti_kernel (KernArgs)
 };
 enum RtiId {
     K3_4, K3_2, K3_1, K5_4, K5_2, K5_1, K3F_4, K3F_2, K3F_1,         // any horizon: 3 / 5 slots, fused downwash; 4, 2, 1 instances per group
@@ -2086,6 +2117,7 @@ enum RtiId {
     KPREC1, KPREC2, KPREC3, KPREC4, KPREC5, KPREC6,                   // precision studies, any horizon, one wave per group
     K40_F32, K40_BF16, K40, K40_PROD, K40_CONS,                       // BASELINE config 5's shape (N = 40, two RTI iterations)
     S20F_PROD, S20_PROD, S20_CONS, S20F, S20, SF_4, S_4, SF_2, S_2,   // sensitivities (three slots)
+    P20F_PROD, P20_PROD, P20_CONS, P20F, P20, PF_4, PF_2,              // ... with parameter sensitivities (no unfused run-time horizon)
     RTI_KERNELS
 };
 static const RtiKern k_rti[] = {
@@ -2108,6 +2140,10 @@ static const RtiKern k_rti[] = {
     {(const void *)RTI_SENS_K(4, true, 20, 0), 4, true}, {(const void *)RTI_SENS_K(4, false, 20, 0), 4, true},
     {(const void *)RTI_SENS_K(4, true, 0, 0), 4, true}, {(const void *)RTI_SENS_K(4, false, 0, 0), 4, true},
     {(const void *)RTI_SENS_K(2, true, 0, 0), 2, true}, {(const void *)RTI_SENS_K(2, false, 0, 0), 2, true},
+    {(const void *)RTI_PSENS_K(4, true, 20, 1), 4, true}, {(const void *)RTI_PSENS_K(4, false, 20, 1), 4, true},
+    {(const void *)RTI_PSENS_K(4, false, 20, 2), 4, true},
+    {(const void *)RTI_PSENS_K(4, true, 20, 0), 4, true}, {(const void *)RTI_PSENS_K(4, false, 20, 0), 4, true},
+    {(const void *)RTI_PSENS_K(4, true, 0, 0), 4, true}, {(const void *)RTI_PSENS_K(2, true, 0, 0), 2, true},
 };
 static_assert(sizeof(k_rti) / sizeof(k_rti[0]) == RTI_KERNELS, "one row per RtiId");
 
@@ -2497,7 +2533,7 @@ int ndp_destroy(ndp_handle *h)
     h->pool.reset();
     void *ptrs[] = {h->dForceAB[0], h->dForceAB[1], h->dProto, h->dRingX, h->dTraj, h->dTables, h->dStamps, h->dRelay, h->dThr, h->sThr, h->dKC, h->dForce, h->dFrag,
                     h->dIn, h->dOut, h->sdbg, h->dQctr, h->dQids, h->dTickIndex, h->dTickThrust, h->dAct,
-                    h->dSensU0, h->dSensU, h->dSensX};
+                    h->dSensU0, h->dSensU, h->dSensX, h->dPSensXr, h->dPSensUr, h->dPSensF};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &sl : h->slot) {
@@ -2840,10 +2876,22 @@ static RtiId rti_pick(const ndp_handle *h, bool fused, bool tick, bool prefetche
     }
     if (h->sens_level > 0) {
         // (ndp_sens_enable admits three-slot shapes at qp_precision 0, one RTI iteration, 2 or 4 instances per workgroup; work list: N = 20)
-        if (phase) return phase == 2 ? S20_CONS : fused ? S20F_PROD : S20_PROD;
-        if (N == 20 && W == 4) return fused ? S20F : S20;
-        if (W == 4) return fused ? SF_4 : S_4;
-        return fused ? SF_2 : S_2;
+        RtiId id;
+        if (phase) id = phase == 2 ? S20_CONS : fused ? S20F_PROD : S20_PROD;
+        else if (N == 20 && W == 4) id = fused ? S20F : S20;
+        else if (W == 4) id = fused ? SF_4 : S_4;
+        else id = fused ? SF_2 : S_2;
+        if (!h->dPSensXr) return id;
+        // ndp_sens_params_enable (launch_rti has refused the unfused run-time horizon: S_4, S_2)
+        switch (id) {
+        case S20F_PROD: return P20F_PROD;
+        case S20_PROD: return P20_PROD;
+        case S20_CONS: return P20_CONS;
+        case S20F: return P20F;
+        case S20: return P20;
+        case SF_4: return PF_4;
+        default: return PF_2;
+        }
     }
     if (phase == 2) return N == 20 ? K20_CONS : K40_CONS;
     if (phase == 1) {
@@ -2869,7 +2917,8 @@ static void launch_kern(const ndp_handle *h, RtiId id, hipStream_t s, KernArgs &
     const RtiKern &k = k_rti[id];
     const dim3 grid((h->cfg.batch + k.waves - 1) / k.waves), block(64 * k.waves);
     const size_t shm = (size_t)h->lds_per_wave * sizeof(double) * k.waves;
-    void *args[] = {&ka, &sa};          // (rti_kernel takes the first only)
+    PSensArgs pa{h->dPSensXr, h->dPSensUr, h->dPSensF};
+    void *args[] = {&ka, &sa, &pa};     // (rti_kernel takes the first only, rti_sens_kernel the first two)
     if (start || stop) (void)hipExtLaunchKernel(k.fn, grid, block, args, shm, s, start, stop, 0);
     else (void)hipLaunchKernel(k.fn, grid, block, args, shm, s);
 }
@@ -2958,6 +3007,13 @@ static bool can_fuse(const ndp_handle *h)
 static int enqueue_step(ndp_handle *h, const double *d_x0, const double *d_xr, const double *d_ur, const float *d_f,
                         const Neigh &nb, double *d_u0, double *d_dbg, hipStream_t s, const StepOut *so = nullptr)
 {
+    // The unfused step at a run-time horizon has no parameter-sensitivity kernel (rti_psens_kernel): that instantiation of the shared body
+    // sits at the register limit and would carry a scratch-memory frame.  The fused step (any N <= 27) and the N = 20 kernels serve them.
+    if (h->dPSensXr && !(nb.other && can_fuse(h)) && !(h->cfg.N == 20 && h->waves == 4)) {
+        h->err = "ndp_step: parameter sensitivities at N != 20 (or 2 instances per workgroup) need the fused step (neighbour windows "
+                 "given): the unfused kernel of a run-time horizon has none";
+        return -2;
+    }
     if ((d_f || nb.other) && !h->cfg.use_fd) { h->err = "ndp_step: a disturbance force needs use_fd = 1 (NDP model)"; return -8; }
     if (nb.other) {
         if (d_f) { h->err = "ndp_step: pass either f or other, not both"; return -7; }
@@ -4371,7 +4427,7 @@ int ndp_sens_enable(ndp_handle *h, int level)
     const size_t n0 = B * (size_t)sens_u0_pitch(), nu = B * (size_t)sens_u_pitch((int)N), nx = B * (size_t)sens_x_pitch((int)N);
     auto drop = [](double *&p) { if (p) (void)hipFree(p); p = nullptr; };
     if (level < 2) { drop(h->dSensU); drop(h->dSensX); }
-    if (level == 0) { drop(h->dSensU0); h->sens_level = 0; return 0; }
+    if (level == 0) { drop(h->dSensU0); drop(h->dPSensXr); drop(h->dPSensUr); drop(h->dPSensF); h->sens_level = 0; return 0; }
     // NaN until a step has written them
     auto get = [&](double *&p, size_t n) -> int {
         if (p) return 0;
@@ -4410,6 +4466,60 @@ int ndp_get_sens(ndp_handle *h, double *du0_dx0, double *dU_dx0, double *dX_dx0)
 void *ndp_device_sens_u0(ndp_handle *h) { return h ? h->dSensU0 : nullptr; }
 void *ndp_device_sens_u(ndp_handle *h) { return h ? h->dSensU : nullptr; }
 void *ndp_device_sens_x(ndp_handle *h) { return h ? h->dSensX : nullptr; }
+
+// ---- parameter sensitivities (rti_psens_kernel, RtiWave::psens_out)
+int ndp_sens_params_enable(ndp_handle *h, int on)
+{
+    if (!h) return -1;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (on && h->sens_level < 1) {
+        h->err = "ndp_sens_params_enable: parameter sensitivities need initial-state sensitivities on (ndp_sens_enable(h, 1 or 2) first)";
+        return -2;
+    }
+    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    int rc = wait_all(h);                 // (steps in flight may still write the buffers)
+    if (rc) return rc;
+    double **bufs[3] = {&h->dPSensXr, &h->dPSensUr, &h->dPSensF};
+    if (!on) {
+        for (double **p : bufs) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        return 0;
+    }
+    const size_t B = h->cfg.batch;
+    const int N = h->cfg.N;
+    const size_t n[3] = {B * (size_t)psens_xr_pitch(N), B * (size_t)psens_ur_pitch(N), B * (size_t)psens_f_pitch(N)};
+    for (int i = 0; i < 3; ++i) {         // NaN until a step has written them
+        if (*bufs[i]) continue;
+        NDP_HIP(h, hipMalloc((void **)bufs[i], n[i] * 8));
+        NDP_HIP(h, hipMemsetAsync(*bufs[i], 0xff, n[i] * 8, h->stream));
+    }
+    NDP_HIP(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int ndp_sens_params_enabled(ndp_handle *h) { return h ? (int)(h->dPSensXr != nullptr) : -1; }
+
+int ndp_get_sens_params(ndp_handle *h, double *du0_dxr, double *du0_dur, double *du0_df)
+{
+    if (!h) return -1;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->dPSensXr) { h->err = "ndp_get_sens_params: parameter sensitivities are not enabled (ndp_sens_params_enable)"; return -2; }
+    NDP_HIP(h, hipSetDevice(h->cfg.device));
+    int rc = wait_all(h);
+    if (rc) return rc;
+    const size_t B = h->cfg.batch;
+    const int N = h->cfg.N;
+    if (du0_dxr) NDP_HIP(h, hipMemcpy(du0_dxr, h->dPSensXr, B * psens_xr_pitch(N) * 8, hipMemcpyDeviceToHost));
+    if (du0_dur) NDP_HIP(h, hipMemcpy(du0_dur, h->dPSensUr, B * psens_ur_pitch(N) * 8, hipMemcpyDeviceToHost));
+    if (du0_df) NDP_HIP(h, hipMemcpy(du0_df, h->dPSensF, B * psens_f_pitch(N) * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+void *ndp_device_sens_xr(ndp_handle *h) { return h ? h->dPSensXr : nullptr; }
+void *ndp_device_sens_ur(ndp_handle *h) { return h ? h->dPSensUr : nullptr; }
+void *ndp_device_sens_f(ndp_handle *h) { return h ? h->dPSensF : nullptr; }
 int ndp_refine_active(ndp_handle *h) { return h ? (int)(h->cfg.ipm_refine > 0 && slots_for(h->cfg.N) <= 3 && h->cfg.qp_precision == 0) : -1; }
 
 int ndp_synchronize(ndp_handle *h)

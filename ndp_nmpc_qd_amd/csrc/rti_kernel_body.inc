@@ -1,8 +1,9 @@
-// rti_kernel_body.inc -- the statements of the control-step kernels rti_kernel and rti_sens_kernel (ndp_hip.hip), included INSIDE
+// rti_kernel_body.inc -- the statements of the control-step kernels rti_kernel, rti_sens_kernel and rti_psens_kernel (ndp_hip.hip), included INSIDE
 // their function bodies.  A device function both kernels call, however much inlined, reorders the kernels' code a little; the text
 // itself, compiled in each kernel's own body, gives rti_kernel exactly the code it had before rti_sens_kernel existed.
-// In scope where it is included: the template parameters NSLOT, WAVES, FUSED, NC, PREC, NRC, QMODE, TICK, the constant SENS, the kernel
-// argument `ka`, the sensitivity arguments `sa` (SensArgs; used only when SENS), the dynamic LDS `smem` and the word `wg_done`.
+// In scope where it is included: the template parameters NSLOT, WAVES, FUSED, NC, PREC, NRC, QMODE, TICK, the constants SENS and PSENS,
+// the kernel argument `ka`, the sensitivity arguments `sa` (SensArgs; used only when SENS) and `pa` (PSensArgs; used only when PSENS), the
+// dynamic LDS `smem` and the word `wg_done`.
     static_assert(!(FUSED && QMODE == 2), "the consumer reads the force the producer left in global memory");
     static_assert(!TICK || (QMODE <= 1 && NC > 0 && PREC == 0), "the one-launch tick exists for the compile-time horizon's in-place and producer forms");
 #ifndef NDP_NO_KERNARG_WARM
@@ -229,7 +230,13 @@
     if (TICK && advance && active) tick_cache_store(ka.ta, te, inst, (int)(threadIdx.x & 63u), seg_refill, seg_fill, seg_cfill);   // (requested in the prologue: long there)
     if (TICK && ka.ta.est && active) io.kthr = tick_estimator(ka.ta, inst, B, (int)(threadIdx.x & 63u));
     bool deferred;
-    if constexpr (SENS) {
+    if constexpr (PSENS) {
+        // ... and of its parameter outputs (rti_psens_kernel)
+        const SensIo so{sa.du0 + (size_t)inst * sens_u0_pitch(), sa.dU ? sa.dU + (size_t)inst * sens_u_pitch(N) : nullptr,
+                        sa.dX ? sa.dX + (size_t)inst * sens_x_pitch(N) : nullptr, sa.level};
+        const PSensIo po{pa.dxr + (size_t)inst * psens_xr_pitch(N), pa.dur + (size_t)inst * psens_ur_pitch(N), pa.df + (size_t)inst * psens_f_pitch(N)};
+        deferred = Prog::template run<QMODE == 1, QMODE == 0 || QMODE == 3, true, true>(P, io, lds, inb, x0v, &so, &po);
+    } else if constexpr (SENS) {
         // the instance's views of the sensitivity outputs (QMODE 2: the listed instance this wave solves)
         const SensIo so{sa.du0 + (size_t)inst * sens_u0_pitch(), sa.dU ? sa.dU + (size_t)inst * sens_u_pitch(N) : nullptr,
                         sa.dX ? sa.dX + (size_t)inst * sens_x_pitch(N) : nullptr, sa.level};

@@ -162,6 +162,14 @@ struct SensIo {
 NDP_HD int sens_u0_pitch() { return NU * NX; }
 NDP_HD int sens_u_pitch(int N) { return N * NU * NX; }
 NDP_HD int sens_x_pitch(int N) { return (N + 1) * NX * NX; }
+// Parameter sensitivities of the step's QP (RtiWave::psens_out), one instance's views: dxr [4][N+1][10] = du_0/dxr, dur [4][N][4] =
+// du_0/dur, df [4][N+1][3] = du_0/df.  Row i: the derivative of u_0[i].
+struct PSensIo {
+    double *dxr, *dur, *df;
+};
+NDP_HD int psens_xr_pitch(int N) { return NU * (N + 1) * NX; }
+NDP_HD int psens_ur_pitch(int N) { return NU * N * NU; }
+NDP_HD int psens_f_pitch(int N) { return NU * (N + 1) * 3; }
 // *RtiIo::iters = interior-point iterations of the step (low half) + Riccati sweeps its QP_AUTO solves took before them (high half);
 // COND_ACCEPTED in the sweep count (config 5's study): a condensed solve's result was kept
 enum { ITERS_SWEEP_SHIFT = 16, ITERS_IPM_MASK = 0xffff, COND_ACCEPTED = 0x1000 };
@@ -1959,8 +1967,10 @@ struct RtiWave {
     // IPM_RARE (the in-place kernels): the interior-point loop is the exception -- see NDP_RARELY.  (The work list's consumer runs
     // nothing else.)
     // SENS (rti_sens_kernel): after the step, the sensitivities of its last QP (sens_out) into *sens.  One RTI iteration only.
-    template <bool DEFER, bool IPM_RARE = false, bool SENS = false>
-    static NDP_D bool run(const RtiParams &P, const RtiIo &io, lp lds, InBuf &inb, vd x0v, const SensIo *sens = nullptr)
+    // PSENS (rti_psens_kernel): behind them, the parameter sensitivities (psens_out) into *psens.
+    template <bool DEFER, bool IPM_RARE = false, bool SENS = false, bool PSENS = false>
+    static NDP_D bool run(const RtiParams &P, const RtiIo &io, lp lds, InBuf &inb, vd x0v, const SensIo *sens = nullptr,
+                          const PSensIo *psens = nullptr)
     {
         const int N = horizon(P);
         const LdsMap m = make_map(N);
@@ -1995,6 +2005,7 @@ struct RtiWave {
         // kernels request every iteration's inputs at the top of the iteration into a buffer that dies at the commit; the
         // caller's early request (issue_first) is simply not used and disappears.
         constexpr bool LOCAL_IN = NR >= 2;
+        [[maybe_unused]] int zlast = m.ZX;     // PSENS: where the last QP's step lies (ZX|ZU, or CX|CU after the interior-point loop)
         for (int it = 0; it < n_rti; ++it) {
             InBuf lbuf;
             if constexpr (LOCAL_IN) {
@@ -2107,6 +2118,7 @@ struct RtiWave {
                 }
             }
             const int zsrc = done ? m.ZX : m.CX;       // ZX|ZU and CX|CU are laid out alike
+            if constexpr (PSENS) zlast = zsrc;
             if (IPM_RARE ? NDP_RARELY(!done) : !done) {
                 if (DEFER) return true;
                 if (as_on) {                           // the interior-point loop's answer carries no set: the next step starts cold
@@ -2175,6 +2187,9 @@ struct RtiWave {
         if constexpr (SENS) {
             if (sens && sens->level > 0) sens_out(P, m, T, lds, A, status != 0, *sens);
         }
+        if constexpr (PSENS) {
+            if (psens) psens_out(P, m, lds, io, A, zlast, status != 0, *psens);
+        }
         if (io.f_late) W::late_publish(late_prev, io.late_gsize, io.late_done_word);
         return false;
     }
@@ -2232,6 +2247,173 @@ struct RtiWave {
                 W::gst(so.dX, W::imin(r, vi(NX - 1)) * int(NX) + j + (k + 1) * int(NX * NX), bad ? nan : W::to_d(xn.r[c]), col && (r < NX));
             }
         }
+    }
+
+    // ---------------------------------------------------------------- parameter sensitivities
+    // The step's last QP differentiated with respect to its data xr, ur and f, with its linearisation point, x_0 and final set held
+    // fixed (interior point: its last Newton system).  The adjoint: (w^i, lam^i), the solution of that KKT system for the right-hand side
+    // e_{u_0,i} (homogeneous dynamics, dx_0 = 0, pinned inputs held at 0), gives
+    //     du_0[i]/dtheta = -sum_k w_k^i' (dg_k/dtheta + dH_k/dtheta z*_k) - sum_k lam_{k+1}^i' db_k/dtheta,
+    // with z* the QP's solution.  w^i is the closed-loop response of the last sweep's gains K~_k to the stage-0 input Lam_0^-1 e_i; lam^i
+    // its costates, lam_N = Q_N w_N, lam_k = Q_k w_k + A_k' lam_{k+1} (the effective cost blocks: barrier terms included).  The sweep
+    // keeps no Lam_0, so it is rebuilt from the same recursion: the responses X^j to u_0 = e_j (pass 1) have Lam_0 e_j = R_0 e_j + B_0' lam_1^j,
+    // and w^i = sum_j X^j Lam_0^-1[j][i] (a pinned stage-0 input: its row and column of Lam_0^-1 are 0).
+    // What depends on theta (build_cost, linearize): g_k[0..5] = s Qd (xbar - xr_k), g_k[u] = dt Rd (ubar - ur_k); the attitude block
+    // Q_k = s E(qr)' W E(qr) with gradient Q_k qbar, qr = xr_k[6..9], so that dg + dH z* = dQ_k/dqr q+ (q+ = qbar + dq*: the new attitude);
+    // b_k[0..2] = ... + h^2/2 f_k / m, b_k[3..5] = ... + h f_k / m (A_k, B_k do not see f).  s = dt, 1 at stage N.  Stage 0's cost does not
+    // move u_0 (x_0 is fixed) and f_N reaches no dynamics: those entries are 0.
+    // VALU, lane (r, c) = lane 4r + c < 40 holds row r, column c of a 10 x 4 block.  LDS after the commit: the responses [N+1][10][4] over
+    // UI .. ZD (46N + 30 >= 40 (N + 1) doubles for N >= 2, all dead), xr's attitude and the new one in rows 0..3 / 6..9 of XI, the final set in
+    // AS (the three-slot kernels keep it in registers), the costates and the 4x4 blocks in the constants area.  A nonzero status: NaN.
+    static NDP_D void psens_out(const RtiParams &P, const LdsMap &m, lp lds, const RtiIo &io, const ActSet &A, int zsrc, bool bad,
+                                const PSensIo &po)
+    {
+        static_assert(!A_LDS, "the final set is parked in the AS area, which the five-slot kernels use");
+        const int N = horizon(P);
+        const int nxr = (N + 1) * NX, nur = N * NU, nf = (N + 1) * 3;
+        vi lane = W::lane_here();
+        if (bad) {
+            const vd nan = vd(__builtin_nan(""));
+            NDP_KEEP_LOOP
+            for (int t = 0; t * 64 < NU * nxr; ++t) {
+                vi e = lane + 64 * t;
+                W::gst(po.dxr, e, nan, e < NU * nxr);
+                W::gst(po.dur, e, nan, e < NU * nur);
+                W::gst(po.df, e, nan, e < NU * nf);
+            }
+            return;
+        }
+        const int XT = m.UI, LM = m.KC, LI = m.KC + 40;        // responses (stage k: XT + 40 k); costates [10][4]; a 4x4 block
+        const vi r = W::imin(lane >> 2, vi(NX - 1)), c = lane & 3, iu = (lane >> 2) & 3;
+        const vb blk = lane < 4 * int(NX), sq = lane < 16;
+        // (the weights, before the constants area becomes staging)
+        const vd qd = W::ld(lds, r + (m.KC + int(KC_QD))), rd = W::ld(lds, iu + (m.KC + int(KC_RD)));
+        for (int t = 0; t < RUA; ++t) {                        // the final set, 0 / 1 per input bound
+            vi e = a_elem(P, lane, t);
+            W::st(lds, e + m.AS, W::sel(a_get(A, m, lds, t, e) == 0, vd(0.0), vd(1.0)));
+        }
+        NDP_KEEP_LOOP
+        for (int t = 0; t * 64 < 4 * (N + 1); ++t) {           // XI rows 0..3 <- qr_k, rows 6..9 <- q+_k
+            vi e = W::imin(lane + 64 * t, 4 * (N + 1) - 1), xo = (e >> 2) * int(NX) + 6 + (e & 3);
+            vd qr = W::gldu(io.xr, xo);
+            vd qp = W::ld(lds, xo + m.XI) + W::ld(lds, xo + zsrc);
+            W::st(lds, xo - 6 + m.XI, qr);
+            W::st(lds, xo + m.XI, qp);
+        }
+        vi offA[NX], offB[NU];
+        for (int j = 0; j < NX; ++j) offA[j] = m_entry(m, r, vi(j));
+        for (int i = 0; i < NU; ++i) offB[i] = m_entry(m, r, vi(12 + i));
+        W::stp(lds, lane + XT, vd(0.0), blk);                  // x_0 = 0
+        W::sync();
+        // ---- pass 1: the responses X^j to u_0 = e_j
+        NDP_KEEP_LOOP
+        for (int k = 0; k < N; ++k) {
+            const int xk = XT + 40 * k;
+            vd u = vd(0.0);                                    // lanes (i, c) < 16: u_k[i][c] = K~_k x_k, pinned rows 0; stage 0: e_c
+            for (int j = 0; j < NX; ++j) u = u + W::ld(lds, iu + (j * 4 + m.KT + mb(k))) * W::ld(lds, c + (j * 4 + xk));
+            if (k == 0) u = W::sel(iu == c, vd(1.0), vd(0.0));
+            u = W::sel(W::ld(lds, iu + (m.AS + 4 * k)) == 0.0, u, vd(0.0));
+            W::stp(lds, lane + LI, u, sq);
+            W::sync();
+            vd x = vd(0.0);                                    // lanes (r, c) < 40: x_{k+1} = A_k x_k + B_k u_k
+            for (int j = 0; j < NX; ++j) x = x + W::ld(lds, offA[j] + mb(k)) * W::ld(lds, c + (j * 4 + xk));
+            for (int i = 0; i < NU; ++i) x = x + W::ld(lds, offB[i] + mb(k)) * W::ld(lds, c + (i * 4 + LI));
+            W::stp(lds, lane + (xk + 40), x, blk);
+            W::sync();
+        }
+        // costate of stage k (1 <= k <= N) of the responses at XT: Q_k x_k + A_k' lam_{k+1}, lam_{k+1} at LM (stage N: none).  (The
+        // entries' offsets are formed here: arrays of them captured by this closure went to scratch memory where it was not inlined.)
+        auto costate = [&](int k) {
+            vd l = vd(0.0);
+            for (int j = 0; j < NX; ++j) l = l + W::ld(lds, c_entry(m, r, vi(j)) + cb(k)) * W::ld(lds, c + (j * 4 + XT + 40 * k));
+            if (k < N)
+                for (int j = 0; j < NX; ++j) l = l + W::ld(lds, m_entry(m, vi(j), r) + mb(k)) * W::ld(lds, c + (j * 4 + LM));
+            W::sync();
+            W::stp(lds, lane + LM, l, blk);
+            W::sync();
+        };
+        NDP_KEEP_LOOP
+        for (int k = N; k >= 1; --k) costate(k);
+        {   // Lam_0 = R_0 + B_0' lam_1 (a pinned row or column: the identity's), symmetrised; every lane inverts it (Gauss-Jordan, SPD: no
+            // pivoting) and keeps entry (i, c) of Lam_0^-1, pinned rows and columns 0
+            const vb pr = !(W::ld(lds, iu + m.AS) == 0.0), pc = !(W::ld(lds, c + m.AS) == 0.0);
+            const vd one = W::sel(iu == c, vd(1.0), vd(0.0));
+            vd lam = W::ld(lds, iu + (m.CB + int(CB_DEU))) * one;
+            for (int j = 0; j < NX; ++j) lam = lam + W::ld(lds, m_entry(m, vi(j), iu + 12)) * W::ld(lds, c + (j * 4 + LM));
+            W::stp(lds, lane + LI, W::sel(pr || pc, one, lam), sq);
+            W::sync();
+            vd a[4][4], y[4];
+            for (int p = 0; p < 4; ++p) {
+                y[p] = W::sel(c == p, vd(1.0), vd(0.0));
+                for (int q = 0; q < 4; ++q) a[p][q] = (W::ld(lds, vi(LI + 4 * p + q)) + W::ld(lds, vi(LI + 4 * q + p))) * 0.5;
+            }
+            for (int p = 0; p < 4; ++p) {
+                const vd rp = W::rcp(a[p][p]);
+                for (int q = 0; q < 4; ++q) a[p][q] = a[p][q] * rp;
+                y[p] = y[p] * rp;
+                for (int o = 0; o < 4; ++o) {
+                    if (o == p) continue;
+                    const vd f = a[o][p];
+                    for (int q = 0; q < 4; ++q) a[o][q] = a[o][q] - f * a[p][q];
+                    y[o] = y[o] - f * y[p];
+                }
+            }
+            const vd li = W::sel(iu == 0, y[0], W::sel(iu == 1, y[1], W::sel(iu == 2, y[2], y[3])));
+            W::sync();
+            W::stp(lds, lane + LI, W::sel(pr || pc, vd(0.0), li), sq);
+            W::sync();
+        }
+        NDP_KEEP_LOOP
+        for (int k = 1; k <= N; ++k) {                         // X^j -> w^i in place (DS operations of a wave are in order)
+            const int xk = XT + 40 * k;
+            vd w = vd(0.0);
+            for (int j = 0; j < NU; ++j) w = w + W::ld(lds, r * 4 + (j + xk)) * W::ld(lds, c + (j * 4 + LI));
+            W::stp(lds, lane + xk, w, blk);
+        }
+        W::stp(lds, lane + LM, vd(0.0), blk);                  // lam_{N+1} = 0
+        W::sync();
+        // ---- pass 2, stage N down to 0: the outputs of stage k, then lam_k
+        const vi fi = W::imin(W::div3(lane), vi(NU - 1)), fc = W::imin(lane - 3 * fi, vi(2));
+        const double h = P.dt;
+        NDP_KEEP_LOOP
+        for (int k = N; k >= 0; --k) {
+            const int xk = XT + 40 * k;
+            const double s = k < N ? h : 1.0;
+            {   // f_k, lanes (i, c) < 12 with i = lane / 3: -(h^2/2 lam_{k+1}[c][i] + h lam_{k+1}[3 + c][i]) / m
+                vd v = (W::ld(lds, fi + (fc * 4 + LM)) * (0.5 * h * h) + W::ld(lds, fi + (fc * 4 + 12 + LM)) * h) * -P.inv_mass;
+                W::gst(po.df, fi * nf + fc + 3 * k, v, lane < 3 * int(NU));
+            }
+            {   // xr_k, lanes (r, i) < 40: rows 0..5 s Qd_r w_k[r][i]; rows 6..9 -s d/dqr_m (w' E' W E v) with v = q+_k, E = E(qr_k)
+                vd wq[4], v[4], q[4], em[4];
+                for (int a = 0; a < 4; ++a) {
+                    wq[a] = W::ld(lds, c + ((6 + a) * 4 + xk));
+                    v[a] = W::ld(lds, vi(m.XI + k * int(NX) + 6 + a));
+                    q[a] = W::ld(lds, vi(m.XI + k * int(NX) + a));
+                    em[a] = W::sel(r == 6 + a, vd(1.0), vd(0.0));
+                }
+                vd ew[3], ev[3], mw[3], mv[3];
+                emul(q, wq, ew); emul(q, v, ev); emul(em, wq, mw); emul(em, v, mv);
+                vd att = vd(0.0);
+                for (int a = 0; a < 3; ++a) att = att + (mw[a] * ev[a] + ew[a] * mv[a]) * P.Qd[7 + a];
+                const vd xv = W::sel(r < 6, W::ld(lds, lane + xk) * qd * s, att * -s);
+                W::gst(po.dxr, c * nxr + r + k * int(NX), xv, blk);
+            }
+            if (k < N) {   // ur_k, lanes (i', i) < 16: dt Rd_i' u_k[i'][i], u_k = K~_k w_k (pinned rows 0); stage 0: Lam_0^-1
+                vd u = vd(0.0);
+                for (int j = 0; j < NX; ++j) u = u + W::ld(lds, iu + (j * 4 + m.KT + mb(k))) * W::ld(lds, c + (j * 4 + xk));
+                u = W::sel(W::ld(lds, iu + (m.AS + 4 * k)) == 0.0, u, vd(0.0));
+                if (k == 0) u = W::ld(lds, lane + LI);
+                W::gst(po.dur, c * nur + iu + k * int(NU), u * rd * h, sq);
+            }
+            if (k >= 1) costate(k);
+        }
+    }
+    // E(q) w (build_cost's E of the attitude residual, linear in q)
+    static NDP_D void emul(const vd q[4], const vd w[4], vd o[3])
+    {
+        o[0] = -q[1] * w[0] + q[0] * w[1] - q[3] * w[2] + q[2] * w[3];
+        o[1] = -q[2] * w[0] + q[3] * w[1] + q[0] * w[2] - q[1] * w[3];
+        o[2] = -q[3] * w[0] - q[2] * w[1] + q[1] * w[2] + q[0] * w[3];
     }
 };
 
