@@ -1,0 +1,179 @@
+// host.hpp -- the private host interface of the library's translation units: the handle, the entry-point frame and the host functions
+// one unit calls in another.
+//   ndp_hip.hip   the kernels but the exchange's, the handle's runtime, the steps, the rows (f1 - f4), the tick, the sensitivities
+//   exchange.hip  peer-mapped windows (ndp_peer_*), the RCCL exchange (ndp_xchg_*) and the remote tick one control period ahead
+// The functions declared below are NDP_HIDDEN: the library exports the C-ABI of include/ndp_nmpc.h and nothing more.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "wave_gfx950.hpp"   // defines the device qualifiers, must precede rti_wave.hpp
+#include "cfg_params.hpp"
+#include "kern_args.hpp"
+
+#define NDP_HIDDEN __attribute__((visibility("hidden")))
+
+using namespace ndp;
+
+struct ndp_handle {
+    ndp_cfg cfg;
+    RtiParams P;
+    int lds_per_wave = 0;      // doubles
+    int waves = 4;             // instances per workgroup
+    int n_simd = 1024;         // SIMDs of the device (4 per CU)
+    bool use_queue = false;    // interior-point solves through the work list: producer + consumer launch per step (QueueArgs)
+    // cfg.work_queue = 0 at (N, n_rti) = (20, 1), batch >= 2 instances per SIMD: the list is switched by what the steps do (queue_policy)
+    bool queue_auto = false;
+    unsigned long long *hIpm = nullptr;      // page-locked [2]: the device's monotonic counts (interior-point instances, steps executed),
+                                             // copied behind every QP_WINDOW-th launch
+    unsigned long long ipm_seen = 0, steps_seen = 0;   // the snapshot the last decision was taken on
+    unsigned queue_launches = 0;             // launches since the last copy was enqueued
+    hipStream_t stream = nullptr;
+    // persistent device state
+    double *dX = nullptr, *dU = nullptr;
+    float *dForce = nullptr, *dFrag = nullptr;
+    double *dKC = nullptr;     // constants block of the LDS image (fill_kc)
+    int *dTables = nullptr;    // per-lane index tables of the Riccati sweep (fill_tables)
+    signed char *dAct = nullptr;   // [B][act_pitch(N)] QP_AUTO's active sets, kept between control steps (RtiIo::act); emptied by reset / set_iterate
+    // ndp_sens_enable: initial-state sensitivities of every step's QP (rti_sens_kernel): level 0 off, 1 du0/dx0, 2 also dU/dx0 and dX/dx0
+    int sens_level = 0;
+    double *dSensU0 = nullptr, *dSensU = nullptr, *dSensX = nullptr;   // [B][4][10], [B][N][4][10], [B][N+1][10][10] (the last two: level 2)
+    // ndp_sens_params_enable: du0/dxr [B][4][N+1][10], du0/dur [B][4][N][4], du0/df [B][4][N+1][3] (rti_psens_kernel); null: off
+    double *dPSensXr = nullptr, *dPSensUr = nullptr, *dPSensF = nullptr;
+    double *dThr = nullptr;    // hover-throttle estimator state, SoA [8][B]
+    double *dStamps = nullptr; // [B][NDP_NSTAMP] whole-batch phase stamps (ndp_debug_stamps)
+    double *dTraj = nullptr;   // f1: the trajectories and the tick's caches (layout: TrajView)
+    int traj_seg = 0;
+    double *dRingX = nullptr, *dRingU = nullptr;   // f1: the reference's sliding list of reference points, phase-major (RingGeom), one allocation (first use)
+    unsigned long long list_n = 0;                 // absolute index of the list's oldest entry = control ticks since the list was built
+    int segc_par = 0;                              // which copy of the one-launch tick's segment cache the NEXT tick reads (tick_cache_store)
+    int list_step = 5;
+    // ndp_tick: the node's control tick on the device (rti_kernel<..., TICK>; other shapes: tick_pre_kernel + the control step)
+    int *dTickIndex = nullptr;       // [B] neighbour instance of every vehicle (< 0: none), or null: no vehicle has one
+    double *dTickThrust = nullptr;   // [B] the thrust command of the previous tick (what hover_throttle_callback reads off body_rate_cmd)
+    bool tick_gate = true;           // gate the downwash on |neighbour window node 0 xy - ego odometry xy| < r_horiz (ndp_nmpc_leader_node.py:65-74)
+    const double *tick_remote = nullptr;   // ndp_tick_config_remote: the neighbours' windows are rows of the CALLER's buffer (an exchange's gathered /
+    int tick_remote_stride = 6;            // peer-mapped windows, [rows][N+1][stride]) instead of this handle's own list
+    struct TickSlot { bool busy = false, want_u0 = false; } tslot[2];
+    double *dRelay = nullptr;  // follower relay: [B][4] = filtered offset xyz + initialised flag
+    double *sThr = nullptr;    // staging of the f1-f4 host entry points: 11 B doubles
+    // downwash one tick ahead on a second stream (LateArgs): force slots, protocol words, the stream, its fork / join events
+    float *dForceAB[2] = {nullptr, nullptr};
+    unsigned long long *dProto = nullptr;
+    hipStream_t aux = nullptr;
+    hipEvent_t evFork = nullptr, evJoin = nullptr;
+    unsigned prefetch_timeout_us = 100000, pf_groups_rti = 1, pf_ntiles = 1;
+    unsigned *dQctr = nullptr; // work list: entry count | B instance ids
+    int *dQids = nullptr;
+    bool have_mlp = false;
+    // Host-pointer entry points.  ONE block holds every input of a step (x0 | xr | ur | f | other | ego_xy, each 256-byte
+    // aligned) and one its outputs (u0 | status | iters | X | U).  Two slots of page-locked host mirrors of both (HostSlot,
+    // allocated at the first host step): the caller's arrays are packed into a slot's input mirror by the handle's pack threads,
+    // the kernel reads that mirror over PCIe and writes u0 / status / iterations (and, when asked, a copy of the new iterate)
+    // into the slot's output mirror itself -- one launch and one wait per step, no DMA operation, at every batch size (measured,
+    // batch 1024: 106 us per step with two steps in flight against 121 us with one H2D copy per step and 147-157 us with the
+    // block copied in chunks as it is packed: every asynchronous copy operation costs ~30 us of latency on this platform).
+    // With two slots the packing of step i+1 runs while step i's kernel does (ndp_step_begin / ndp_step_end).
+    // The persistent iterate dX | dU always lives in HBM.  dIn / dOut: device-side staging of the f1-f4 host entry points
+    // (views sx0 ..) and the small outputs of device-pointer steps.
+    unsigned char *dIn = nullptr, *dOut = nullptr;
+    size_t off_x0 = 0, off_xr = 0, off_ur = 0, off_f = 0, off_other = 0, off_ego = 0, in_bytes = 0;
+    size_t off_u0 = 0, off_st = 0, off_it = 0, out_bytes = 0, out_all = 0;
+    double *sx0 = nullptr, *sxr = nullptr, *sur = nullptr, *sother = nullptr, *sego = nullptr, *su0 = nullptr, *sdbg = nullptr;
+    float *sf = nullptr;
+    int *dStatus = nullptr, *dIters = nullptr;
+    const int *lastStatus = nullptr, *lastIters = nullptr;   // where the last step wrote them (dStatus / dIters or a slot's output mirror)
+    struct HostSlot {
+        unsigned char *hIn = nullptr, *hOut = nullptr;
+        hipEvent_t evOut = nullptr;                          // the step that uses the slot has completed
+        bool busy = false, want_iter = false;
+        double *dump = nullptr;
+    } slot[2];
+    bool slots_ready = false;
+    // ndp_track_steps: the completion of every control step marks an event WITHOUT a packet of its own (the dispatch packet's
+    // completion signal, hipExtLaunchKernel) -- what another stream orders itself behind (ndp_xchg_begin's after_event)
+    bool track_steps = false;
+    bool last_step_tracked = false;   // does stepDone[step_seq & 3] belong to the control step launched LAST?
+    bool track_pending = false;       // a tracked step on a caller's stream has not been waited for (wait_all)
+    hipEvent_t stepDone[4] = {nullptr, nullptr, nullptr, nullptr};
+    unsigned step_seq = 0;
+    double host_us[4] = {0, 0, 0, 0};   // last host step: packing | enqueue | wait for the results | copy-out  (ndp_debug_host_timing)
+    int host_cores = 0, pack_threads = 0;   // what ensure_slots found and started (ndp_debug_host_info)
+    int slot_head = 0, slot_tail = 0, slots_busy = 0;   // begin fills slot_head, end drains slot_tail
+    std::unique_ptr<struct PackPool> pool;
+    // the last foreign stream a *_device call enqueued on: the getters wait for it (hipEvent)
+    hipEvent_t evLast = nullptr;
+    bool ev_pending = false;
+    // timing
+    int timing = 0;            // 0 off, n > 0: bracket every n-th launch of each kernel with HIP events
+    int64_t launch_no[2] = {0, 0};
+    bool timing_open = false;
+    struct Ev { hipEvent_t a, b; int kind; };
+    std::vector<Ev> events;
+    std::mutex mu;
+    std::string err;
+};
+
+#define NDP_HIP(h, call)                                                                   \
+    do {                                                                                   \
+        hipError_t e_ = (call);                                                            \
+        if (e_ != hipSuccess) {                                                            \
+            (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                  \
+            return -(int)e_ - 1000;                                                        \
+        }                                                                                  \
+    } while (0)
+
+static inline RingGeom ring_geom(const ndp_handle *h) { return RingGeom{h->list_step, h->cfg.N + 1}; }
+
+enum { TICK_ESTIMATE = NDP_TICK_ESTIMATE, TICK_WANT_U0 = NDP_TICK_WANT_U0, TICK_T_UNIFORM = NDP_TICK_T_UNIFORM };
+
+// ---- host functions one unit calls in another (no locking, no sync: the caller holds h->mu).  C linkage like the entry points they
+// sit beside; hidden, so not exported.
+extern "C" {
+// ndp_hip.hip
+NDP_HIDDEN int sens_refuse(ndp_handle *h, const char *what);
+NDP_HIDDEN int note_stream(ndp_handle *h, hipStream_t s);
+NDP_HIDDEN int set_device(ndp_handle *h);
+NDP_HIDDEN int ensure_tick(ndp_handle *h);
+NDP_HIDDEN void launch_tick_pre(const TickPre &a, hipStream_t s);
+NDP_HIDDEN int tick_step_enqueue(ndp_handle *h, hipStream_t s, const double *x_odom, double *cmd, double *u0, const double *windows,
+                                 unsigned long long pos);
+// exchange.hip
+NDP_HIDDEN int peer_mapped(const void *p);
+NDP_HIDDEN void launch_pack_pv_list(const double *base, size_t pitch, int np1, double *pv, size_t B, hipStream_t s);
+}  // extern "C"
+// ndp_hip.hip (C++ linkage: it returns a TickPre)
+NDP_HIDDEN TickPre tick_pre(const ndp_handle *h, bool adv, const double *t, double t_all, bool est, const double *x_odom, const double *vz,
+                            const double *throttle, double *pv = nullptr);
+
+// The frame of a handle's entry point: h->mu is held for the whole call.  In this order: -1 for a null handle or missing arguments
+// (args false), -2 while sensitivities are on if the entry point does not compute them (refuse: its name), then the device is
+// selected and the stream resolved (null: the handle's own).  rc != 0: the call returns it.
+struct Entry {
+    ndp_handle *h;
+    std::unique_lock<std::mutex> lk;
+    hipStream_t s = nullptr;
+    int rc = -1;
+    Entry(ndp_handle *h_, bool args, void *stream = nullptr, const char *refuse = nullptr) : h(h_)
+    {
+        if (!h) return;
+        lk = std::unique_lock<std::mutex>(h->mu);
+        s = stream ? (hipStream_t)stream : h->stream;
+        if (refuse && h->sens_level) rc = sens_refuse(h, refuse);
+        else if (args) rc = set_device(h);
+    }
+    // the end of a form that enqueues on a caller's stream: the getters wait for that stream too
+    int noted(int r) { return r ? r : note_stream(h, s); }
+    // the end of a host-array form, behind its copies out: everything on the handle's stream has completed
+    int synced(int r)
+    {
+        if (r) return r;
+        NDP_HIP(h, hipStreamSynchronize(h->stream));
+        return 0;
+    }
+};
+

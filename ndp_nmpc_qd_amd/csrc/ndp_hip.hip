@@ -9,7 +9,7 @@
 //                 layers are chained through v_mfma_f32_32x32x2_f32 accumulators (no LDS round trip).
 //   mlp_stream_kernel + prefetch_gate_kernel / prefetch_done_kernel : the downwash of the NEXT tick on a second stream, LDS-free
 //                 (weights out of L2), ordered against the control step by per-tile epochs (LateArgs / PF_* words).
-//   peer_publish_kernel + peer_epoch_kernel : the per-tick neighbour exchange through peer-mapped windows (peer_epoch.hpp).
+//   (peer_publish_kernel / peer_epoch_kernel and the RCCL exchange's pack kernels live in exchange.hip; host.hpp: which unit owns what)
 //   ref_window_kernel, ref_list_*_kernel, throttle / actuator / plant kernels : the rows either side of the step (f1, f3, f4).
 // The iterate (X, U) of a handle lives in HBM and stays there between steps; host-array steps (ndp_step / ndp_step_begin)
 // read their inputs from, and mirror their outputs to, page-locked host slots over PCIe (zero-copy) -- see step_begin_locked.
@@ -17,7 +17,6 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
-#include <dlfcn.h>
 #include <sched.h>
 #include <stdio.h>
 
@@ -37,8 +36,7 @@
 #include "wave_gfx950.hpp"   // defines the device qualifiers, must precede rti_wave.hpp
 #include "cfg_params.hpp"
 #include "cond_qp.hpp"
-#define NDP_PEER_FN __host__ __device__ inline
-#include "peer_epoch.hpp"
+#include "host.hpp"
 
 namespace ndp {
 
@@ -200,17 +198,6 @@ struct LateArgs {
     unsigned groups_rti, ntiles;
 };
 __device__ __host__ inline unsigned pf_group_size(unsigned n, unsigned groups, unsigned g) { return n / groups + (g < n % groups ? 1u : 0u); }
-
-struct ThrCfg { double a1, a2, hm, g, R, Q0, Q1, mass; };
-
-// layout of the reference list in HBM (see the f1 list kernels below)
-struct RingGeom {
-    int step, np1;                 // list entries per node spacing; N + 1
-    __host__ __device__ int ring() const { return step * (np1 - 1) + 1; }
-    __host__ __device__ size_t px() const { return (size_t)step * 2 * np1 * 10; }     // doubles per vehicle, x ring
-    __host__ __device__ size_t pu() const { return (size_t)step * 2 * np1 * 4; }
-    __host__ __device__ size_t slot(unsigned long long j) const { return (size_t)(j % step) * 2 * np1 + (size_t)((j / step) % np1); }
-};
 
 // ndp_tick in ONE launch (rti_kernel<..., TICK = true>): what tick_pre_kernel does -- the reference list's newest entry, which is node
 // N of this tick's window, and the hover-throttle estimator's update -- done by the control step's own wave in front of its work, so
@@ -1060,7 +1047,6 @@ __global__ __launch_bounds__(256) void plant_kernel(double *__restrict__ x, cons
 // what NMPCRefPublisher.get_nmpc_pts returns (pt_pub/pt_publisher.py:79-103, base_pt_publisher.py:81-133,
 // diff_flatness :188-248, traj_full_pt_2_x_u :115-146).  One thread per (vehicle, node): reads its segment's 28
 // coefficients (224 contiguous bytes, shared by the neighbouring nodes of the vehicle), writes 80 + 32 contiguous bytes.
-struct RefCfg { int B, N, n_seg; double dt, mass, g, toff; };   // toff: added to every vehicle's node-0 time (rollouts)
 
 // Value and first ND - 1 derivatives of sum_i c[i] s^i at s by repeated synthetic division (the Taylor shift): pass k divides the
 // previous pass's quotient by (x - s) once more and leaves p^(k)(s) / k! -- NC_ - 1 - k fused multiply-adds, 22 for the four values of
@@ -1428,27 +1414,6 @@ __global__ __launch_bounds__(256) void ref_list_window_kernel(const double *__re
 //                    store is nmpc_u_2_att_tgt (:273-283): [wx, wy, wz, c mass / k_throttle] where the host reads it (RtiIo::cmd),
 //                    the thrust kept on the device for the next estimator update.  (A third launch for that -- tick_post_kernel,
 //                    the first form -- cost 4.6 us per tick in the trace for 32 bytes per vehicle.)
-struct TickPre {
-    RefCfg cf;
-    const double *coeff, *tcum, *tseg, *fpt;
-    int *seg_hint;                     // [B] the segment each vehicle's last point lay in (ref_point)
-    const double *t;                   // [B] trajectory time of the tick, or null: t_all for every vehicle
-    double t_all;
-    int advance;                       // 0: the list is not advanced
-    unsigned long long j_new;          // absolute index of the entry the new point becomes
-    RingGeom rg;
-    double *rx, *ru;
-    ThrCfg thr;
-    double *st;                        // estimator state, SoA [8][B]
-    const double *vz;                  // vz of vehicle b at vz[b * vz_pitch]: a [B] array (pitch 1) or column 5 of the odometry rows (pitch 10)
-    size_t vz_pitch;
-    const double *throttle;            // [B]: the thrust command sent last tick (caller's array, or the one the control step kept)
-    int est;                           // run the estimator this tick
-    // ndp_xchg_tick_begin: the advanced window's position / velocity columns -> pv[b][N+1][6] in the same launch (one launch less on a
-    // path that is bound by the host's launches); the window starts at list slot pv_slot, its node N is the point made here
-    double *pv = nullptr;
-    size_t pv_slot = 0;
-};
 
 __global__ __launch_bounds__(64) void tick_pre_kernel(TickPre a)
 {
@@ -1676,111 +1641,10 @@ __device__ __forceinline__ double tick_estimator(const TickArgs &ta, int inst, i
     return uniform_lane(k, 0);
 }
 
-// ------------------------------------------------------------------------------------------ peer windows: per-tick publish
-// peer_epoch.hpp's protocol on the device.  TWO launches per control tick and rank, in front of the control-step launch:
-//  peer_publish_kernel (<= 256 blocks)
-//   thread 0 of block 0   : reader role -- acknowledge tick t-1 in the neighbour's header (its slot may be overwritten now)
-//   thread 0 of each block: owner role  -- wait until the own slot t & 1 is free (the reader's acknowledgement of tick t-2)
-//   all threads           : copy this tick's windows (src, the reference generator's output) into the own slot, plain stores;
-//                           the end of the launch is what makes them visible system-wide
-//  peer_epoch_kernel (one wave)
-//   epoch[t & 1] := t (release, system scope), then -- reader role -- wait for the neighbour's epoch of tick t.  When this launch
-//   has completed, the control-step kernel launched next on the same stream may read the neighbour's slot t & 1 (kernel
-//   boundary = system-scope acquire).
-// (One launch that counts its finished blocks with an atomic and lets the last one publish was the first form: agent-scope atomics
-// on one address serialise at 30-60 ns each -- 8.7 us for 1.7 MB of windows against 4.7 us this way, 15-114 us against 7-9 us
-// for 20 MB depending on the block count; scripts/ubench/publish_copy.hip.)
-struct PeerDevMem {
-    typedef unsigned long long u64;
-    static __device__ __forceinline__ u64 load(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM); }
-    static __device__ __forceinline__ u64 peek(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-    static __device__ __forceinline__ void store(u64 *p, u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
-    static __device__ __forceinline__ u64 now_us() { return __builtin_amdgcn_s_memrealtime() / 100; }   // 100 MHz constant clock
-};
-
-struct PeerPubArgs {
-    const double *src;              // [n] doubles: this rank's windows of the tick
-    unsigned long long *own;        // this rank's buffer (header + two slots)
-    unsigned long long *nb;         // the neighbour rank's buffer, mapped (== own with one rank)
-    size_t n;
-    int slot;                       // the slot parity the host baked into the control-step launch that follows
-    unsigned timeout_us;
-};
-
-// No LDS and no barrier: the launch may have to run BESIDE a control step whose workgroups hold the CU's whole LDS (the one-tick-ahead
-// form), where a workgroup that asks for any would wait for a control-step workgroup to leave.  Every wave reads the tick and waits for the
-// slot by itself (the same two words).
-__global__ __launch_bounds__(256) void peer_publish_kernel(PeerPubArgs a)
-{
-    typedef PeerProto<PeerDevMem> PP;
-    typedef unsigned long long u64;
-    u64 t = 0;
-    if ((threadIdx.x & 63u) == 0) {
-        t = PP::next_tick(a.own);                    // (the epochs only change in peer_epoch_kernel, behind this launch)
-        if (blockIdx.x == 0 && threadIdx.x == 0) PP::ack_previous(a.nb, t);
-        const bool freed = PP::wait_slot_free(a.own, t, a.timeout_us);
-        if (blockIdx.x == 0 && threadIdx.x == 0 && !freed) a.own[PEER_W_STAT + PEER_STAT_ACK_TIMEOUT] += 1;
-    }
-    const unsigned par = (unsigned)__builtin_amdgcn_readfirstlane((int)(t & 1));
-    double2 *dst = reinterpret_cast<double2 *>(reinterpret_cast<unsigned char *>(a.own) + peer_slot_offset(a.n, (int)par));
-    const double2 *src = reinterpret_cast<const double2 *>(a.src);
-    const size_t n2 = a.n / 2;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (size_t)gridDim.x * blockDim.x) dst[i] = src[i];
-    if ((a.n & 1) && blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<double *>(dst)[a.n - 1] = a.src[a.n - 1];
-}
-
-__global__ void peer_epoch_kernel(PeerPubArgs a)
-{
-    typedef PeerProto<PeerDevMem> PP;
-    typedef unsigned long long u64;
-    if (threadIdx.x != 0) return;
-    const u64 t = PP::next_tick(a.own);
-    PP::set_epoch(a.own, t);
-    a.own[PEER_W_STAT + PEER_STAT_TICKS] = t;
-    if ((int)(t & 1) != a.slot) a.own[PEER_W_STAT + PEER_STAT_DESYNC] += 1;
-    if (!PP::wait_epoch(a.nb, t, a.timeout_us)) a.own[PEER_W_STAT + PEER_STAT_EPOCH_TIMEOUT] += 1;
-}
-
-// ------------------------------------------------------------------------------------------ RCCL exchange: the pack
-// rows x [10] reference windows -> rows x [6]: the position / velocity columns, all that travels (downwash_nn.py:22).  One 16-byte
-// piece per thread: piece p of row r = columns 2p, 2p + 1.
-__global__ __launch_bounds__(256) void pack_pv_kernel(const double *__restrict__ xr, double *__restrict__ pv, size_t rows)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows * 3) return;
-    const size_t r = i / 3, p = i - r * 3;
-    reinterpret_cast<double2 *>(pv)[i] = *reinterpret_cast<const double2 *>(xr + r * NX + 2 * p);
-}
-
-// the same for windows that lie in the reference list (ndp_tick): window row k of vehicle b = list row base + b * pitch + k * 10
-__global__ __launch_bounds__(256) void pack_pv_list_kernel(const double *__restrict__ base, size_t pitch, int np1, double *__restrict__ pv, size_t B)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B * (size_t)np1 * 3) return;
-    const size_t r = i / 3, p = i - r * 3, b = r / (size_t)np1, k = r - b * (size_t)np1;
-    reinterpret_cast<double2 *>(pv)[i] = *reinterpret_cast<const double2 *>(base + b * pitch + k * NX + 2 * p);
-}
-
 }  // namespace ndp
 
 // ------------------------------------------------------------------------------------------ C-ABI
 using namespace ndp;
-
-// Address ranges this process mapped from other processes / GPUs (ndp_peer_open): neighbour windows inside one are read with
-// system-scope loads (MlpArgs::other_sys).  A handful of entries, looked up once per launch.
-struct PeerRange { uintptr_t lo, hi; };
-static std::mutex g_peer_mu;
-static std::vector<PeerRange> g_peer_ranges;
-static int peer_mapped(const void *p)
-{
-    if (!p) return 0;
-    const uintptr_t a = (uintptr_t)p;
-    std::lock_guard<std::mutex> lk(g_peer_mu);
-    for (const PeerRange &r : g_peer_ranges)
-        if (a >= r.lo && a < r.hi) return 1;
-    return 0;
-}
-
 
 // RTI_K(...): the rti_kernel instantiation to reference.  -DNDP_DEV_HEADLINE_ONLY (kernel development builds only, never
 // the shipped library) collapses every instantiation but the reference configuration's two onto rti_kernel<3, 4, false, 20>, so
@@ -1928,115 +1792,7 @@ struct PackPool {
     }
 };
 
-struct ndp_handle {
-    ndp_cfg cfg;
-    RtiParams P;
-    int lds_per_wave = 0;      // doubles
-    int waves = 4;             // instances per workgroup
-    int n_simd = 1024;         // SIMDs of the device (4 per CU)
-    bool use_queue = false;    // interior-point solves through the work list: producer + consumer launch per step (QueueArgs)
-    // cfg.work_queue = 0 at (N, n_rti) = (20, 1), batch >= 2 instances per SIMD: the list is switched by what the steps do (queue_policy)
-    bool queue_auto = false;
-    unsigned long long *hIpm = nullptr;      // page-locked [2]: the device's monotonic counts (interior-point instances, steps executed),
-                                             // copied behind every QP_WINDOW-th launch
-    unsigned long long ipm_seen = 0, steps_seen = 0;   // the snapshot the last decision was taken on
-    unsigned queue_launches = 0;             // launches since the last copy was enqueued
-    hipStream_t stream = nullptr;
-    // persistent device state
-    double *dX = nullptr, *dU = nullptr;
-    float *dForce = nullptr, *dFrag = nullptr;
-    double *dKC = nullptr;     // constants block of the LDS image (fill_kc)
-    int *dTables = nullptr;    // per-lane index tables of the Riccati sweep (fill_tables)
-    signed char *dAct = nullptr;   // [B][act_pitch(N)] QP_AUTO's active sets, kept between control steps (RtiIo::act); emptied by reset / set_iterate
-    // ndp_sens_enable: initial-state sensitivities of every step's QP (rti_sens_kernel): level 0 off, 1 du0/dx0, 2 also dU/dx0 and dX/dx0
-    int sens_level = 0;
-    double *dSensU0 = nullptr, *dSensU = nullptr, *dSensX = nullptr;   // [B][4][10], [B][N][4][10], [B][N+1][10][10] (the last two: level 2)
-    // ndp_sens_params_enable: du0/dxr [B][4][N+1][10], du0/dur [B][4][N][4], du0/df [B][4][N+1][3] (rti_psens_kernel); null: off
-    double *dPSensXr = nullptr, *dPSensUr = nullptr, *dPSensF = nullptr;
-    double *dThr = nullptr;    // hover-throttle estimator state, SoA [8][B]
-    double *dStamps = nullptr; // [B][NDP_NSTAMP] whole-batch phase stamps (ndp_debug_stamps)
-    double *dTraj = nullptr;   // f1: the trajectories and the tick's caches (layout: TrajView)
-    int traj_seg = 0;
-    double *dRingX = nullptr, *dRingU = nullptr;   // f1: the reference's sliding list of reference points, phase-major (RingGeom), one allocation (first use)
-    unsigned long long list_n = 0;                 // absolute index of the list's oldest entry = control ticks since the list was built
-    int segc_par = 0;                              // which copy of the one-launch tick's segment cache the NEXT tick reads (tick_cache_store)
-    int list_step = 5;
-    // ndp_tick: the node's control tick on the device (rti_kernel<..., TICK>; other shapes: tick_pre_kernel + the control step)
-    int *dTickIndex = nullptr;       // [B] neighbour instance of every vehicle (< 0: none), or null: no vehicle has one
-    double *dTickThrust = nullptr;   // [B] the thrust command of the previous tick (what hover_throttle_callback reads off body_rate_cmd)
-    bool tick_gate = true;           // gate the downwash on |neighbour window node 0 xy - ego odometry xy| < r_horiz (ndp_nmpc_leader_node.py:65-74)
-    const double *tick_remote = nullptr;   // ndp_tick_config_remote: the neighbours' windows are rows of the CALLER's buffer (an exchange's gathered /
-    int tick_remote_stride = 6;            // peer-mapped windows, [rows][N+1][stride]) instead of this handle's own list
-    struct TickSlot { bool busy = false, want_u0 = false; } tslot[2];
-    double *dRelay = nullptr;  // follower relay: [B][4] = filtered offset xyz + initialised flag
-    double *sThr = nullptr;    // staging of the f1-f4 host entry points: 11 B doubles
-    // downwash one tick ahead on a second stream (LateArgs): force slots, protocol words, the stream, its fork / join events
-    float *dForceAB[2] = {nullptr, nullptr};
-    unsigned long long *dProto = nullptr;
-    hipStream_t aux = nullptr;
-    hipEvent_t evFork = nullptr, evJoin = nullptr;
-    unsigned prefetch_timeout_us = 100000, pf_groups_rti = 1, pf_ntiles = 1;
-    unsigned *dQctr = nullptr; // work list: entry count | B instance ids
-    int *dQids = nullptr;
-    bool have_mlp = false;
-    // Host-pointer entry points.  ONE block holds every input of a step (x0 | xr | ur | f | other | ego_xy, each 256-byte
-    // aligned) and one its outputs (u0 | status | iters | X | U).  Two slots of page-locked host mirrors of both (HostSlot,
-    // allocated at the first host step): the caller's arrays are packed into a slot's input mirror by the handle's pack threads,
-    // the kernel reads that mirror over PCIe and writes u0 / status / iterations (and, when asked, a copy of the new iterate)
-    // into the slot's output mirror itself -- one launch and one wait per step, no DMA operation, at every batch size (measured,
-    // batch 1024: 106 us per step with two steps in flight against 121 us with one H2D copy per step and 147-157 us with the
-    // block copied in chunks as it is packed: every asynchronous copy operation costs ~30 us of latency on this platform).
-    // With two slots the packing of step i+1 runs while step i's kernel does (ndp_step_begin / ndp_step_end).
-    // The persistent iterate dX | dU always lives in HBM.  dIn / dOut: device-side staging of the f1-f4 host entry points
-    // (views sx0 ..) and the small outputs of device-pointer steps.
-    unsigned char *dIn = nullptr, *dOut = nullptr;
-    size_t off_x0 = 0, off_xr = 0, off_ur = 0, off_f = 0, off_other = 0, off_ego = 0, in_bytes = 0;
-    size_t off_u0 = 0, off_st = 0, off_it = 0, out_bytes = 0, out_all = 0;
-    double *sx0 = nullptr, *sxr = nullptr, *sur = nullptr, *sother = nullptr, *sego = nullptr, *su0 = nullptr, *sdbg = nullptr;
-    float *sf = nullptr;
-    int *dStatus = nullptr, *dIters = nullptr;
-    const int *lastStatus = nullptr, *lastIters = nullptr;   // where the last step wrote them (dStatus / dIters or a slot's output mirror)
-    struct HostSlot {
-        unsigned char *hIn = nullptr, *hOut = nullptr;
-        hipEvent_t evOut = nullptr;                          // the step that uses the slot has completed
-        bool busy = false, want_iter = false;
-        double *dump = nullptr;
-    } slot[2];
-    bool slots_ready = false;
-    // ndp_track_steps: the completion of every control step marks an event WITHOUT a packet of its own (the dispatch packet's
-    // completion signal, hipExtLaunchKernel) -- what another stream orders itself behind (ndp_xchg_begin's after_event)
-    bool track_steps = false;
-    bool last_step_tracked = false;   // does stepDone[step_seq & 3] belong to the control step launched LAST?
-    bool track_pending = false;       // a tracked step on a caller's stream has not been waited for (wait_all)
-    hipEvent_t stepDone[4] = {nullptr, nullptr, nullptr, nullptr};
-    unsigned step_seq = 0;
-    double host_us[4] = {0, 0, 0, 0};   // last host step: packing | enqueue | wait for the results | copy-out  (ndp_debug_host_timing)
-    int host_cores = 0, pack_threads = 0;   // what ensure_slots found and started (ndp_debug_host_info)
-    int slot_head = 0, slot_tail = 0, slots_busy = 0;   // begin fills slot_head, end drains slot_tail
-    std::unique_ptr<struct PackPool> pool;
-    // the last foreign stream a *_device call enqueued on: the getters wait for it (hipEvent)
-    hipEvent_t evLast = nullptr;
-    bool ev_pending = false;
-    // timing
-    int timing = 0;            // 0 off, n > 0: bracket every n-th launch of each kernel with HIP events
-    int64_t launch_no[2] = {0, 0};
-    bool timing_open = false;
-    struct Ev { hipEvent_t a, b; int kind; };
-    std::vector<Ev> events;
-    std::mutex mu;
-    std::string err;
-};
-
 static thread_local std::string g_create_err;
-
-#define NDP_HIP(h, call)                                                                   \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                  \
-            return -(int)e_ - 1000;                                                        \
-        }                                                                                  \
-    } while (0)
 
 static size_t nxs(const ndp_handle *h) { return (size_t)h->cfg.batch * (h->cfg.N + 1) * NX; }
 static size_t nus(const ndp_handle *h) { return (size_t)h->cfg.batch * h->cfg.N * NU; }
@@ -2087,7 +1843,7 @@ static void copy_ipm_iters(int32_t *dst, const int32_t *src, size_t n)
 }
 
 // entry points that do not run the control step through rti_sens_kernel: refused on a handle with sensitivities on
-static int sens_refuse(ndp_handle *h, const char *what)
+int sens_refuse(ndp_handle *h, const char *what)
 {
     h->err = std::string(what) + ": not available while initial-state sensitivities are enabled (ndp_sens_enable(h, 0) first): "
              "only the in-place and work-list step forms compute them";
@@ -2198,325 +1954,6 @@ int ndp_debug_mfma_probe_f32(const float *a, const float *b, const float *c, flo
     const hipError_t e = hipMemcpy(d, dd, 320 * 4, hipMemcpyDeviceToHost);
     (void)hipFree(da); (void)hipFree(db); (void)hipFree(dc); (void)hipFree(dd);
     return e == hipSuccess ? 0 : -2;
-}
-
-// ------------------------------------------------------------------------------------------ peer windows (multi-GPU)
-// The reference's neighbour exchange is publish / subscribe of the 21x10 float64 reference window (PredXU: nmpc_node.py:116-133
-// publishes, ndp_nmpc_leader_node.py:40,60-76 subscribes).  One process per GPU: the publisher keeps its windows in a buffer
-// whose IPC handle it hands to the subscriber's process once; the subscriber maps it and its control-step kernel reads the
-// neighbour's window straight out of the publisher's HBM over xGMI (peer access) -- no per-step collective, no extra launch.
-int ndp_peer_alloc(int device, size_t bytes, void **ptr, unsigned char *handle64)
-{
-    if (!ptr || !handle64 || bytes == 0) return -1;
-    static_assert(sizeof(hipIpcMemHandle_t) == 64, "ndp_peer_*: the handle is passed as 64 bytes");
-    if (hipSetDevice(device) != hipSuccess) return -2;
-    // Fine-grained device memory: coherent between agents while kernels run (the epoch / acknowledgement words are polled by
-    // running kernels of two GPUs, the slots are written here and read there one launch later).  Ordinary (coarse-grained)
-    // memory if the runtime refuses, or when NDP_PEER_COARSE=1 asks for it; the protocol's accesses are system-scope either way.
-    void *p = nullptr;
-    const char *coarse = getenv("NDP_PEER_COARSE");
-    if ((coarse && coarse[0] == '1') || hipExtMallocWithFlags(&p, bytes, hipDeviceMallocFinegrained) != hipSuccess || !p) {
-        (void)hipGetLastError();
-        p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) return -3;
-    }
-    if (hipMemset(p, 0, bytes) != hipSuccess) { (void)hipFree(p); return -3; }      // epochs, acknowledgements, counters start at 0
-    if (hipDeviceSynchronize() != hipSuccess) { (void)hipFree(p); return -3; }
-    hipIpcMemHandle_t hd;
-    if (hipIpcGetMemHandle(&hd, p) != hipSuccess) { (void)hipFree(p); return -4; }
-    memcpy(handle64, &hd, 64);
-    *ptr = p;
-    return 0;
-}
-
-int ndp_peer_open(int device, const unsigned char *handle64, void **ptr)
-{
-    if (!ptr || !handle64) return -1;
-    if (hipSetDevice(device) != hipSuccess) return -2;
-    hipIpcMemHandle_t hd;
-    memcpy(&hd, handle64, 64);
-    void *p = nullptr;
-    if (hipIpcOpenMemHandle(&p, hd, hipIpcMemLazyEnablePeerAccess) != hipSuccess) { (void)hipGetLastError(); return -3; }
-    {   // remember the mapped range: windows inside it are read with system-scope loads (see peer_mapped)
-        void *base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, p) != hipSuccess || !base || size == 0) {
-            (void)hipGetLastError();
-            base = p; size = (size_t)1 << 40;       // extent unknown: err on the side of system-scope loads
-        }
-        std::lock_guard<std::mutex> lk(g_peer_mu);
-        g_peer_ranges.push_back({(uintptr_t)base, (uintptr_t)base + size});
-    }
-    *ptr = p;
-    return 0;
-}
-
-int ndp_peer_close(int device, void *ptr)
-{
-    if (!ptr) return -1;
-    if (hipSetDevice(device) != hipSuccess) return -2;
-    {
-        std::lock_guard<std::mutex> lk(g_peer_mu);
-        for (size_t i = 0; i < g_peer_ranges.size(); ++i)
-            if ((uintptr_t)ptr >= g_peer_ranges[i].lo && (uintptr_t)ptr < g_peer_ranges[i].hi) { g_peer_ranges.erase(g_peer_ranges.begin() + i); break; }
-    }
-    return hipIpcCloseMemHandle(ptr) == hipSuccess ? 0 : -3;
-}
-
-int ndp_peer_free(int device, void *ptr)
-{
-    if (!ptr) return -1;
-    if (hipSetDevice(device) != hipSuccess) return -2;
-    return hipFree(ptr) == hipSuccess ? 0 : -3;
-}
-
-
-// ---- per-tick publish / subscribe through such buffers (peer_epoch.hpp)
-int ndp_peer_layout(size_t n_doubles, size_t *buffer_bytes, size_t *slot0_offset, size_t *slot_stride)
-{
-    if (buffer_bytes) *buffer_bytes = peer_buffer_bytes(n_doubles);
-    if (slot0_offset) *slot0_offset = peer_slot_offset(n_doubles, 0);
-    if (slot_stride) *slot_stride = peer_slot_bytes(n_doubles);
-    return 0;
-}
-
-int ndp_peer_publish_device(int device, const void *d_src, size_t n_doubles, void *own_buf, void *nb_buf, int slot,
-                            unsigned timeout_us, void *stream)
-{
-    if (!d_src || !own_buf || !nb_buf || n_doubles == 0 || (slot & ~1)) return -1;
-    if (hipSetDevice(device) != hipSuccess) return -2;
-    PeerPubArgs a{(const double *)d_src, (unsigned long long *)own_buf, (unsigned long long *)nb_buf, n_doubles, slot, timeout_us};
-    size_t blocks = (n_doubles / 2 + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 256) blocks = 256;        // all resident at once: every block's first thread may wait on the reader
-    hipLaunchKernelGGL(peer_publish_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    hipLaunchKernelGGL(peer_epoch_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-int ndp_track_steps(ndp_handle *h, int on)
-{
-    if (!h) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    NDP_HIP(h, hipSetDevice(h->cfg.device));
-    if (on && !h->stepDone[0])
-        for (auto &e : h->stepDone) NDP_HIP(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    h->track_steps = on != 0;
-    return 0;
-}
-
-int ndp_last_step_event(ndp_handle *h, void **event)
-{
-    if (!h || !event) return -1;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!h->track_steps || h->step_seq == 0) { h->err = "ndp_last_step_event: no tracked step yet (ndp_track_steps first)"; return -14; }
-    if (!h->last_step_tracked) {
-        h->err = "ndp_last_step_event: the control step launched last carried no completion event (launched while tracking was off, or "
-                 "through a path that does not mark one): ordering a gather behind an OLDER step's event could overwrite a buffer the "
-                 "last step still reads";
-        return -14;
-    }
-    *event = (void *)h->stepDone[h->step_seq & 3];
-    return 0;
-}
-
-// ---- The north star's collective issued by the library itself: one RCCL all-gather per control tick of the ranks' position /
-// velocity windows, on a HIP stream of its own beside the control-step kernel (ordered by events, no host wait).  RCCL is bound at
-// run time (dlopen of the library the process already holds -- torch's -- or the system's): the C-ABI library carries no link-time
-// dependency on it and every other entry point works without it.
-namespace {
-typedef struct { char internal[128]; } rccl_uid;
-typedef int (*fn_uid)(rccl_uid *);
-typedef int (*fn_init)(void **, int, rccl_uid, int);
-typedef int (*fn_ag)(const void *, void *, size_t, int, void *, hipStream_t);
-typedef int (*fn_destroy)(void *);
-typedef const char *(*fn_errstr)(int);
-struct RcclApi {
-    void *lib = nullptr;
-    fn_uid uid = nullptr; fn_init init = nullptr; fn_ag allgather = nullptr; fn_destroy destroy = nullptr; fn_errstr errstr = nullptr;
-};
-std::mutex g_rccl_mu;
-RcclApi g_rccl;
-int rccl_bind(const char *path)
-{
-    std::lock_guard<std::mutex> lk(g_rccl_mu);
-    if (g_rccl.lib) return 0;
-    void *l = nullptr;
-    if (path && path[0]) l = dlopen(path, RTLD_NOW | RTLD_LOCAL);
-    if (!l) l = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL);
-    if (!l) l = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL);
-    if (!l) return -20;
-    RcclApi a;
-    a.lib = l;
-    a.uid = (fn_uid)dlsym(l, "ncclGetUniqueId"); a.init = (fn_init)dlsym(l, "ncclCommInitRank");
-    a.allgather = (fn_ag)dlsym(l, "ncclAllGather"); a.destroy = (fn_destroy)dlsym(l, "ncclCommDestroy");
-    a.errstr = (fn_errstr)dlsym(l, "ncclGetErrorString");
-    if (!a.uid || !a.init || !a.allgather || !a.destroy) { dlclose(l); return -21; }
-    g_rccl = a;
-    return 0;
-}
-}  // namespace
-
-struct ndp_xchg {
-    int device = 0, rank = 0, world = 1;
-    void *comm = nullptr;
-    hipStream_t cs = nullptr;                 // the exchange's own stream (another priority level: its own hardware queue)
-    hipEvent_t evReady = nullptr, evDone = nullptr;
-    double *send = nullptr;                   // packed windows of this rank
-    size_t send_doubles = 0;
-    // the remote tick with the exchange ahead of the control steps (ndp_xchg_tick_begin / _step): begins are numbered 1, 2, ...; begin n
-    // lives in slot n % 3 (at most two are ahead of the steps, and step k consumes begin k) and fills whichever gather buffer the
-    // caller names -- two buffers (begin i+1 behind step i) or three (begin i+2 behind step i: the gather then never waits for a step)
-    hipEvent_t evGather[3] = {nullptr, nullptr, nullptr};     // slot's gather is complete
-    unsigned long long win_n[3] = {0, 0, 0};         // the list position its windows belong to
-    const void *buf[3] = {nullptr, nullptr, nullptr};   // the gather buffer it fills
-    struct Reader { const void *ptr = nullptr; unsigned seq = 0; hipStream_t stream = nullptr; unsigned age = 0; };
-    Reader readers[4];                               // per gather buffer: the control step that read it last (seq: its tracked number, 0 = untracked)
-    unsigned steps = 0;                              // control steps taken (step k consumes begin k)
-    int ahead = 0;                                   // gathers begun and not yet stepped on (0 .. 2)
-    // ndp_xchg_tick_async: the exchange stream's launches of a begin (wait, advance + columns, ncclAllGather, event record: ~15 us of
-    // host time) are made by a thread of the exchange's own; the caller's begin only describes them (~2 us).  One host thread's
-    // launches are what bounds the remote tick one period ahead; with two the device does.
-    struct Job {
-        bool adv = false;
-        TickPre a{};                                  // adv: the advance (+ columns) launch
-        const double *pack_base = nullptr;            // !adv: the columns of the window that is there
-        size_t pack_pitch = 0, B = 0, rows = 0;
-        int np1 = 0, p = 0;
-        void *gathered = nullptr;
-        hipEvent_t wait_ev = nullptr;
-    };
-    Job job[3];                                      // begin n's launches: job[n % 3]
-    unsigned job_n[3] = {0, 0, 0};                   // ... and n itself
-    std::atomic<unsigned> posted{0}, done{0};
-    std::atomic<int> async_rc{0};
-    std::atomic<bool> stop{false};
-    std::thread worker;
-    bool async = false;
-    std::string err;
-};
-
-int ndp_xchg_destroy(ndp_xchg *x);
-
-int ndp_xchg_unique_id(const char *rccl_path, unsigned char *id128)
-{
-    if (!id128) return -1;
-    int rc = rccl_bind(rccl_path);
-    if (rc) return rc;
-    rccl_uid u;
-    if (g_rccl.uid(&u) != 0) return -22;
-    memcpy(id128, u.internal, 128);
-    return 0;
-}
-
-int ndp_xchg_create(int device, int rank, int world, const unsigned char *id128, const char *rccl_path, ndp_xchg **out)
-{
-    if (!id128 || !out || world < 1 || rank < 0 || rank >= world) return -1;
-    *out = nullptr;
-    int rc = rccl_bind(rccl_path);
-    if (rc) return rc;
-    if (hipSetDevice(device) != hipSuccess) return -2;
-    std::unique_ptr<ndp_xchg> x(new (std::nothrow) ndp_xchg);
-    if (!x) return -4;
-    x->device = device; x->rank = rank; x->world = world;
-    rccl_uid u;
-    memcpy(u.internal, id128, 128);
-    if (g_rccl.init(&x->comm, world, u, rank) != 0) return -22;      // collective: every rank calls it
-    int lo = 0, hi = 0;
-    if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess || hipStreamCreateWithPriority(&x->cs, hipStreamNonBlocking, hi) != hipSuccess ||
-        hipEventCreateWithFlags(&x->evReady, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x->evDone, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x->evGather[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x->evGather[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x->evGather[2], hipEventDisableTiming) != hipSuccess) {
-        (void)ndp_xchg_destroy(x.release());      // (releases whatever exists: communicator, stream, events)
-        return -3;
-    }
-    *out = x.release();
-    return 0;
-}
-
-// rows = B_local * (N + 1) windows rows of d_xr ([rows][10] doubles) -> d_gathered ([world * rows][6]); everything `after_stream`
-// holds so far comes first (null: the windows are in place, no ordering needed), nothing waits on the host
-int ndp_xchg_begin(ndp_xchg *x, const void *d_xr, size_t rows, void *d_gathered, void *after_stream, void *after_event)
-{
-    if (!x || !d_xr || !d_gathered || rows == 0) return -1;
-    if (hipSetDevice(x->device) != hipSuccess) return -2;
-    if (x->send_doubles < rows * 6) {
-        if (x->send) { (void)hipStreamSynchronize(x->cs); (void)hipFree(x->send); x->send = nullptr; }
-        if (hipMalloc((void **)&x->send, rows * 6 * sizeof(double)) != hipSuccess) return -3;
-        x->send_doubles = rows * 6;
-    }
-    // (every event operation is a packet the queue's command processor retires in order: ~3 us each on the stream that also
-    // carries the control steps -- callers whose windows are in place already pass no stream)
-    if (after_stream && (hipEventRecord(x->evReady, (hipStream_t)after_stream) != hipSuccess || hipStreamWaitEvent(x->cs, x->evReady, 0) != hipSuccess))
-        return -3;
-    if (after_event && hipStreamWaitEvent(x->cs, (hipEvent_t)after_event, 0) != hipSuccess) return -3;
-    const size_t pieces = rows * 3;
-    hipLaunchKernelGGL(pack_pv_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, x->cs, (const double *)d_xr, x->send, rows);
-    if (hipGetLastError() != hipSuccess) return -3;
-    const int r = g_rccl.allgather(x->send, d_gathered, rows * 6, /* ncclFloat64 */ 8, x->comm, x->cs);
-    if (r != 0) { x->err = g_rccl.errstr ? g_rccl.errstr(r) : "ncclAllGather failed"; return -22; }
-    return hipEventRecord(x->evDone, x->cs) == hipSuccess ? 0 : -3;
-}
-
-// `stream` waits (on the device) for the gather started last
-int ndp_xchg_end(ndp_xchg *x, void *stream)
-{
-    if (!x) return -1;
-    return hipStreamWaitEvent((hipStream_t)stream, x->evDone, 0) == hipSuccess ? 0 : -3;
-}
-
-// One call per control tick of the pipelined form: `stream` waits for the gather begun last (this tick's windows), then the NEXT tick's
-// gather is begun behind the last reader of its buffer -- the completion event of the control step launched last for h when the steps
-// are tracked (ndp_track_steps), else everything `stream` holds so far.
-int ndp_xchg_tick(ndp_xchg *x, ndp_handle *h, void *stream, const void *d_xr_next, size_t rows, void *d_gathered_next)
-{
-    void *ev = nullptr;
-    if (h) {
-        std::lock_guard<std::mutex> lk(h->mu);
-        if (h->sens_level) return sens_refuse(h, "ndp_xchg_tick");
-        if (h->track_steps && h->step_seq && h->last_step_tracked) ev = (void *)h->stepDone[h->step_seq & 3];
-    }
-    int rc = ndp_xchg_end(x, stream);
-    if (rc) return rc;
-    return ndp_xchg_begin(x, d_xr_next, rows, d_gathered_next, ev ? nullptr : stream, ev);
-}
-
-const char *ndp_xchg_last_error(const ndp_xchg *x) { return x ? x->err.c_str() : "null exchange"; }
-
-static void xchg_worker_stop(ndp_xchg *x)
-{
-    if (x->worker.joinable()) {
-        x->stop.store(true, std::memory_order_release);
-        x->worker.join();
-        x->stop.store(false, std::memory_order_release);
-    }
-    x->async = false;
-}
-
-int ndp_xchg_destroy(ndp_xchg *x)
-{
-    if (!x) return -1;
-    xchg_worker_stop(x);
-    (void)hipSetDevice(x->device);
-    if (x->cs) (void)hipStreamSynchronize(x->cs);
-    if (x->comm) (void)g_rccl.destroy(x->comm);
-    if (x->send) (void)hipFree(x->send);
-    if (x->evReady) (void)hipEventDestroy(x->evReady);
-    if (x->evDone) (void)hipEventDestroy(x->evDone);
-    for (hipEvent_t e : x->evGather) if (e) (void)hipEventDestroy(e);
-    if (x->cs) (void)hipStreamDestroy(x->cs);
-    delete x;
-    return 0;
-}
-
-int ndp_peer_stats(int device, const void *own_buf, unsigned long long *out4)
-{
-    if (!own_buf || !out4) return -1;
-    if (hipSetDevice(device) != hipSuccess) return -2;
-    if (hipDeviceSynchronize() != hipSuccess) return -3;
-    return hipMemcpy(out4, (const unsigned long long *)own_buf + PEER_W_STAT, PEER_STAT_N * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
 }
 
 int ndp_destroy(ndp_handle *h)
@@ -2746,7 +2183,7 @@ static int end_timing(ndp_handle *h, hipStream_t s)
 // A *_device call enqueued on a caller's stream: remember it so that the getters (ndp_get_status, ndp_get_iterate, ...)
 // wait for that work and not only for the library's own stream.  Streams being captured into a graph are skipped (an
 // event recorded there belongs to the graph and cannot be waited on from the host).
-static int note_stream(ndp_handle *h, hipStream_t s)
+int note_stream(ndp_handle *h, hipStream_t s)
 {
     if (s == h->stream) return 0;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -2769,38 +2206,11 @@ static int wait_all(ndp_handle *h)
     return 0;
 }
 
-static int set_device(ndp_handle *h)
+int set_device(ndp_handle *h)
 {
     NDP_HIP(h, hipSetDevice(h->cfg.device));
     return 0;
 }
-
-// The frame of a handle's entry point: h->mu is held for the whole call.  In this order: -1 for a null handle or missing arguments
-// (args false), -2 while sensitivities are on if the entry point does not compute them (refuse: its name), then the device is
-// selected and the stream resolved (null: the handle's own).  rc != 0: the call returns it.
-struct Entry {
-    ndp_handle *h;
-    std::unique_lock<std::mutex> lk;
-    hipStream_t s = nullptr;
-    int rc = -1;
-    Entry(ndp_handle *h_, bool args, void *stream = nullptr, const char *refuse = nullptr) : h(h_)
-    {
-        if (!h) return;
-        lk = std::unique_lock<std::mutex>(h->mu);
-        s = stream ? (hipStream_t)stream : h->stream;
-        if (refuse && h->sens_level) rc = sens_refuse(h, refuse);
-        else if (args) rc = set_device(h);
-    }
-    // the end of a form that enqueues on a caller's stream: the getters wait for that stream too
-    int noted(int r) { return r ? r : note_stream(h, s); }
-    // the end of a host-array form, behind its copies out: everything on the handle's stream has completed
-    int synced(int r)
-    {
-        if (r) return r;
-        NDP_HIP(h, hipStreamSynchronize(h->stream));
-        return 0;
-    }
-};
 
 struct Neigh {                 // neighbour windows of a step (device pointers)
     const double *other = nullptr;
@@ -3709,7 +3119,6 @@ int ndp_ref_window(ndp_handle *h, const double *t, double *xr, double *ur)
 }
 
 // ---- f1, the reference's sliding list (ref_list_* kernels; layout: RingGeom)
-static RingGeom ring_geom(const ndp_handle *h) { return RingGeom{h->list_step, h->cfg.N + 1}; }
 static int list_ring(const ndp_handle *h) { return ring_geom(h).ring(); }
 
 static int list_alloc(ndp_handle *h)
@@ -3814,7 +3223,7 @@ int ndp_ref_list_window(ndp_handle *h, const double *t, double *xr, double *ur)
 }
 
 // ---- the node's control tick, end to end on the device (nmpc_node.py:211-231; kernels: rti_kernel<..., TICK>, or tick_pre_kernel + rti_kernel)
-static int ensure_tick(ndp_handle *h)
+int ensure_tick(ndp_handle *h)
 {
     if (h->dTickThrust) return 0;
     NDP_HIP(h, hipMalloc((void **)&h->dTickThrust, (size_t)h->cfg.batch * 8));
@@ -3893,13 +3302,12 @@ int ndp_tick_reset(ndp_handle *h)
     return g.synced(0);
 }
 
-enum { TICK_ESTIMATE = NDP_TICK_ESTIMATE, TICK_WANT_U0 = NDP_TICK_WANT_U0, TICK_T_UNIFORM = NDP_TICK_T_UNIFORM };
-
 // tick_pre_kernel's arguments.  adv: the list is advanced, its new entry the point at t[b] (device-accessible), or t_all for every vehicle
 // when t is null, + T_horizon.  est: the estimator runs on vz[B] (null: column 5 of x_odom[B][10]) and throttle[B] (null: the thrust
 // this handle commanded last tick).  pv: the advanced window's position / velocity columns also go there (ndp_xchg_tick_begin).
-static TickPre tick_pre(const ndp_handle *h, bool adv, const double *t, double t_all, bool est, const double *x_odom, const double *vz,
-                        const double *throttle, double *pv = nullptr)
+}  // extern "C"      (tick_pre: C++ linkage, it returns a TickPre)
+TickPre tick_pre(const ndp_handle *h, bool adv, const double *t, double t_all, bool est, const double *x_odom, const double *vz,
+                 const double *throttle, double *pv)
 {
     TickPre a{};
     a.cf = ref_cfg(h, h->cfg.N * h->cfg.dt);
@@ -3917,6 +3325,13 @@ static TickPre tick_pre(const ndp_handle *h, bool adv, const double *t, double t
     a.est = est ? 1 : 0;
     if (pv) { a.pv = pv; a.pv_slot = a.rg.slot(h->list_n + 1); }
     return a;
+}
+extern "C" {
+
+// tick_pre_kernel, one thread per vehicle
+void launch_tick_pre(const TickPre &a, hipStream_t s)
+{
+    hipLaunchKernelGGL(tick_pre_kernel, dim3((a.cf.B + 63) / 64), dim3(64), 0, s, a);
 }
 
 // the same work inside the one-launch tick (TickArgs), which reads the trajectory's segment cache the last such tick wrote
@@ -3970,7 +3385,7 @@ static int tick_enqueue(ndp_handle *h, hipStream_t s, const double *x_odom, bool
             ta = tick_args(h, a);
             so.tick = &ta;
         } else {
-            hipLaunchKernelGGL(tick_pre_kernel, dim3((B + 63) / 64), dim3(64), 0, s, a);
+            launch_tick_pre(a, s);
             NDP_HIP(h, hipGetLastError());
         }
     }
@@ -4003,7 +3418,7 @@ int ndp_tick_advance_device(ndp_handle *h, const void *d_x_odom, const void *d_t
     if (adv || est) {
         const TickPre a = tick_pre(h, adv, uni ? nullptr : (const double *)d_t, uni ? *(const double *)d_t : 0.0, est, (const double *)d_x_odom,
                                    (const double *)d_vz, (const double *)d_throttle);
-        hipLaunchKernelGGL(tick_pre_kernel, dim3((h->cfg.batch + 63) / 64), dim3(64), 0, g.s, a);
+        launch_tick_pre(a, g.s);
         NDP_HIP(h, hipGetLastError());
         if (adv) ++h->list_n;
     }
@@ -4016,40 +3431,13 @@ int ndp_tick_window_pv_device(ndp_handle *h, void *d_pv, void *stream)
     if (g.rc) return g.rc;
     if (!h->dRingX) { h->err = "ndp_tick_window_pv: no reference list"; return -11; }
     const RingGeom rg = ring_geom(h);
-    const size_t B = h->cfg.batch, n = B * (size_t)(h->cfg.N + 1) * 3;
-    hipLaunchKernelGGL(pack_pv_list_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.s, h->dRingX + rg.slot(h->list_n) * 10, rg.px(),
-                       h->cfg.N + 1, (double *)d_pv, B);
+    launch_pack_pv_list(h->dRingX + rg.slot(h->list_n) * 10, rg.px(), h->cfg.N + 1, (double *)d_pv, h->cfg.batch, g.s);
     NDP_HIP(h, hipGetLastError());
-    return g.noted(0);
-}
-
-// Stage 2 and the exchange in one call, on the tick's own stream: this tick's window columns packed out of the list into the
-// exchange's send buffer, then ncclAllGather into d_gathered ([world * B][N+1][6]) -- both on `stream`, behind the list advance and in
-// front of ndp_tick_step_device by stream order alone (no event operation, no second stream: the tick's chain is serial anyway).
-int ndp_xchg_tick_windows(ndp_xchg *x, ndp_handle *h, void *d_gathered, void *stream)
-{
-    Entry g(h, x && d_gathered, stream, "ndp_xchg_tick_windows");
-    if (g.rc) return g.rc;
-    if (x->device != h->cfg.device) { h->err = "ndp_xchg_tick_windows: the exchange and the handle live on different devices"; return -1; }
-    hipStream_t s = g.s;
-    if (!h->dRingX) { h->err = "ndp_xchg_tick_windows: no reference list"; return -11; }
-    const RingGeom rg = ring_geom(h);
-    const size_t B = h->cfg.batch, rows = B * (size_t)(h->cfg.N + 1), n = rows * 3;
-    if (x->send_doubles < rows * 6) {
-        if (x->send) { (void)hipStreamSynchronize(x->cs); (void)hipStreamSynchronize(s); (void)hipFree(x->send); x->send = nullptr; }
-        NDP_HIP(h, hipMalloc((void **)&x->send, rows * 6 * sizeof(double)));
-        x->send_doubles = rows * 6;
-    }
-    hipLaunchKernelGGL(pack_pv_list_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->dRingX + rg.slot(h->list_n) * 10, rg.px(),
-                       h->cfg.N + 1, x->send, B);
-    NDP_HIP(h, hipGetLastError());
-    const int r = g_rccl.allgather(x->send, d_gathered, rows * 6, /* ncclFloat64 */ 8, x->comm, s);
-    if (r != 0) { x->err = g_rccl.errstr ? g_rccl.errstr(r) : "ncclAllGather failed"; h->err = "ndp_xchg_tick_windows: " + x->err; return -22; }
     return g.noted(0);
 }
 
 // stage 3 on `s` (h->mu held): the control step of the window at list position `pos`, neighbour rows out of `windows`
-static int tick_step_enqueue(ndp_handle *h, hipStream_t s, const double *x_odom, double *cmd, double *u0, const double *windows, unsigned long long pos)
+int tick_step_enqueue(ndp_handle *h, hipStream_t s, const double *x_odom, double *cmd, double *u0, const double *windows, unsigned long long pos)
 {
     if (!h->tick_remote) { h->err = "ndp_tick_step: ndp_tick_config_remote first (neighbours in the same handle: ndp_tick_device)"; return -17; }
     if (!h->dRingX) { h->err = "ndp_tick_step: no reference list"; return -11; }
@@ -4069,166 +3457,6 @@ int ndp_tick_step_device(ndp_handle *h, const void *d_x_odom, void *d_cmd, void 
     Entry g(h, d_x_odom && d_cmd, stream, "ndp_tick_step_device");
     if (g.rc) return g.rc;
     return g.noted(tick_step_enqueue(h, g.s, (const double *)d_x_odom, (double *)d_cmd, (double *)d_u0, h->tick_remote, h->list_n));
-}
-
-// ---- the remote tick with the exchange ONE CONTROL PERIOD AHEAD.  A vehicle's window is a function of time alone (the list advance
-// reads the trajectory, not the odometry): the list advance of tick i+1, its window columns and their all-gather run on the exchange's
-// own stream BESIDE the control step of tick i, into the other one of two gather buffers.  Per control period
-//     ndp_xchg_tick_step(tick i: estimator, wait for gather i on the device, control step)   then   ndp_xchg_tick_begin(tick i+1)
-// (one begin in front of the first step).  What orders what:
-//   gather i+1 writes the buffer step i-1 read      -> the exchange stream waits for that step's completion event (ndp_track_steps: it
-//                                                      rides on the step's dispatch packet; untracked: for everything its stream holds)
-//   advance i+1 writes list entries                  -> of another phase row than window i's (RingGeom: entries per node spacing >= 2,
-//                                                      refused otherwise), so it may run beside step i
-//   step i reads window i and gather buffer i        -> its stream waits for its begin's event, recorded behind advance i, pack, gather
-//   the estimator reads the thrust step i-1 commanded -> same stream as the steps, in front of step i
-// the exchange stream's launches of one begin; returns 0 or the error code (the caller's thread or the exchange's own)
-static int xchg_job_run(ndp_xchg *x, const ndp_xchg::Job &j)
-{
-    if (j.wait_ev && hipStreamWaitEvent(x->cs, j.wait_ev, 0) != hipSuccess) return -3;
-    if (j.adv) hipLaunchKernelGGL(tick_pre_kernel, dim3((unsigned)((j.B + 63) / 64)), dim3(64), 0, x->cs, j.a);
-    else {
-        const size_t n = j.rows * 3;
-        hipLaunchKernelGGL(pack_pv_list_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, x->cs, j.pack_base, j.pack_pitch, j.np1, x->send, j.B);
-    }
-    if (hipGetLastError() != hipSuccess) return -3;
-    const int r = g_rccl.allgather(x->send, j.gathered, j.rows * 6, /* ncclFloat64 */ 8, x->comm, x->cs);
-    if (r != 0) { x->err = g_rccl.errstr ? g_rccl.errstr(r) : "ncclAllGather failed"; return -22; }
-    return hipEventRecord(x->evGather[j.p], x->cs) == hipSuccess ? 0 : -3;
-}
-
-static void xchg_worker(ndp_xchg *x)
-{
-    (void)hipSetDevice(x->device);
-    int idle = 0;
-    for (;;) {
-        const unsigned want = x->done.load(std::memory_order_relaxed) + 1;
-        if ((int)(x->posted.load(std::memory_order_acquire) - want) >= 0) {
-            const int rc = xchg_job_run(x, x->job[want % 3]);
-            if (rc) x->async_rc.store(rc, std::memory_order_relaxed);
-            x->done.store(want, std::memory_order_release);
-            idle = 0;
-        } else if (x->stop.load(std::memory_order_acquire)) break;
-        else if (++idle < 200000) __builtin_ia32_pause();                     // (~ a millisecond of spinning behind the last job, then naps)
-        else std::this_thread::sleep_for(std::chrono::microseconds(50));
-    }
-}
-
-// on: begins are described by the caller and LAUNCHED by a thread of the exchange's own (see ndp_xchg::Job); off: launched by the caller
-int ndp_xchg_tick_async(ndp_xchg *x, int on)
-{
-    if (!x) return -1;
-    if (x->ahead != 0) { x->err = "ndp_xchg_tick_async: gathers are ahead of the control steps (step on them first)"; return -14; }
-    if (on && !x->worker.joinable()) {
-        x->stop.store(false);
-        try { x->worker = std::thread(xchg_worker, x); } catch (...) { x->err = "ndp_xchg_tick_async: no thread"; return -4; }
-        x->async = true;
-    } else if (!on) xchg_worker_stop(x);
-    return 0;
-}
-
-int ndp_xchg_tick_begin(ndp_xchg *x, ndp_handle *h, const void *d_t, int flags, void *d_gathered)
-{
-    Entry g(h, x && d_gathered, nullptr, "ndp_xchg_tick_begin");
-    if (g.rc) return g.rc;
-    if (x->device != h->cfg.device) { h->err = "ndp_xchg_tick_begin: the exchange and the handle live on different devices"; return -1; }
-    int rc = ensure_tick(h);
-    if (rc) return rc;
-    if (!h->dRingX) { h->err = "ndp_xchg_tick_begin: no reference list"; return -11; }
-    if (d_t && !h->dTraj) { h->err = "ndp_xchg_tick_begin: a trajectory time was given but ndp_ref_set_trajectory was never called"; return -11; }
-    if (x->ahead >= 2) { h->err = "ndp_xchg_tick_begin: two gathers are already ahead of the control steps (ndp_xchg_tick_step first)"; return -14; }
-    if ((rc = x->async_rc.load(std::memory_order_relaxed))) { h->err = "ndp_xchg_tick_begin: an earlier begin failed on the exchange's thread: " + x->err; return rc; }
-    const RingGeom rg = ring_geom(h);
-    if (d_t && rg.step < 2) { h->err = "ndp_xchg_tick_begin: the list's entries are one node spacing apart -- the advance would overwrite the window a control step may be reading (use the serial form: ndp_tick_advance_device, ndp_xchg_tick_windows, ndp_tick_step_device)"; return -17; }
-    // a second begin ahead writes list entry n + step N + 2 while the step on window n (entries n, n + step, ..., n + step N) may still
-    // run: with step 2 that entry lands in the same residue class as the window, i.e. on one of its nodes (RingGeom::slot)
-    if (d_t && x->ahead == 1 && rg.step < 3) { h->err = "ndp_xchg_tick_begin: the list's entries are two per node spacing -- a second begin ahead would overwrite the window the step before it may be reading (one begin ahead only: the two-buffer form)"; return -17; }
-    const size_t B = h->cfg.batch, rows = B * (size_t)(h->cfg.N + 1);
-    if (x->send_doubles < rows * 6) {
-        while (x->done.load(std::memory_order_acquire) != x->posted.load(std::memory_order_relaxed)) __builtin_ia32_pause();
-        if (x->send) { (void)hipStreamSynchronize(x->cs); (void)hipFree(x->send); x->send = nullptr; }
-        NDP_HIP(h, hipMalloc((void **)&x->send, rows * 6 * sizeof(double)));
-        x->send_doubles = rows * 6;
-    }
-    const unsigned n_job = x->posted.load(std::memory_order_relaxed) + 1;
-    const int p = (int)(n_job % 3u);
-    ndp_xchg::Job &j = x->job[p];                  // (free: at most two are ahead, and a step waits for its begin's launches)
-    j = ndp_xchg::Job{};
-    j.p = p; j.B = B; j.rows = rows; j.np1 = h->cfg.N + 1; j.gathered = d_gathered;
-    // the gather overwrites a buffer: behind the control step that read it last
-    const ndp_xchg::Reader *rd = nullptr;
-    for (const ndp_xchg::Reader &r : x->readers) if (r.ptr == d_gathered) rd = &r;
-    for (int q = 0; q < 3; ++q)                    // (a begin that is still ahead of its step names the same buffer: the caller cycles too few)
-        if (x->buf[q] == d_gathered && (int)(x->job_n[q] - x->steps) > 0) { h->err = "ndp_xchg_tick_begin: this gather buffer holds a tick that has not been stepped on yet"; return -14; }
-    if (rd) {
-        const bool precise = h->track_steps && rd->seq && h->step_seq - rd->seq < 4u;
-        if (precise) {
-            j.wait_ev = h->stepDone[rd->seq & 3];
-        } else {
-            NDP_HIP(h, hipEventRecord(x->evReady, rd->stream));
-            j.wait_ev = x->evReady;
-        }
-    } else if (n_job == 1) {            // the first gather: behind whatever made the list (ndp_ref_list_reset / ndp_tick_reset on the handle's stream)
-        NDP_HIP(h, hipEventRecord(x->evReady, h->stream));
-        j.wait_ev = x->evReady;
-    }
-    if (d_t) {
-        const bool uni = (flags & TICK_T_UNIFORM) != 0;
-        // (no estimator here: it belongs to the step's side) ... and the advanced window's columns in the same launch
-        j.a = tick_pre(h, true, uni ? nullptr : (const double *)d_t, uni ? *(const double *)d_t : 0.0, false, nullptr, h->dTickThrust,
-                       nullptr, x->send);
-        j.adv = true;
-        ++h->list_n;
-    } else {
-        j.pack_base = h->dRingX + rg.slot(h->list_n) * 10; j.pack_pitch = rg.px();
-    }
-    x->job_n[p] = n_job;
-    x->buf[p] = d_gathered;
-    if (x->async) x->posted.store(n_job, std::memory_order_release);          // the exchange's thread takes it from here
-    else {
-        rc = xchg_job_run(x, j);
-        x->posted.store(n_job, std::memory_order_relaxed);
-        x->done.store(n_job, std::memory_order_relaxed);
-        if (rc) { h->err = "ndp_xchg_tick_begin: " + (rc == -22 ? x->err : std::string("a HIP call on the exchange's stream failed")); return rc; }
-    }
-    x->win_n[p] = h->list_n;
-    ++x->ahead;
-    return 0;
-}
-
-int ndp_xchg_tick_step(ndp_xchg *x, ndp_handle *h, const void *d_x_odom, const void *d_vz, const void *d_throttle, int flags,
-                       void *d_cmd, void *d_u0, const void *d_gathered, void *stream)
-{
-    Entry g(h, x && d_x_odom && d_cmd && d_gathered, stream, "ndp_xchg_tick_step");
-    if (g.rc) return g.rc;
-    hipStream_t s = g.s;
-    if (x->ahead < 1) { h->err = "ndp_xchg_tick_step: no gather was begun for this tick (ndp_xchg_tick_begin first)"; return -14; }
-    int rc = ensure_tick(h);
-    if (rc) return rc;
-    const size_t B = h->cfg.batch;
-    const unsigned k = x->steps + 1;               // this step consumes begin k
-    const int p = (int)(k % 3u);
-    if (x->buf[p] != d_gathered || x->job_n[p] != k) { h->err = "ndp_xchg_tick_step: this tick's gather was begun into another buffer"; return -14; }
-    if (flags & TICK_ESTIMATE) {
-        const TickPre a = tick_pre(h, false, nullptr, 0.0, true, (const double *)d_x_odom, (const double *)d_vz, (const double *)d_throttle);
-        hipLaunchKernelGGL(tick_pre_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, a);
-        NDP_HIP(h, hipGetLastError());
-    }
-    // (asynchronous begins: the event must have been RECORDED by the exchange's thread before this stream is told to wait for it)
-    while ((int)(x->done.load(std::memory_order_acquire) - k) < 0) __builtin_ia32_pause();
-    if ((rc = x->async_rc.load(std::memory_order_relaxed))) { h->err = "ndp_xchg_tick_step: this tick's begin failed on the exchange's thread: " + x->err; return rc; }
-    NDP_HIP(h, hipStreamWaitEvent(s, x->evGather[p], 0));
-    rc = tick_step_enqueue(h, s, (const double *)d_x_odom, (double *)d_cmd, (double *)d_u0, (const double *)d_gathered, x->win_n[p]);
-    if (rc) return rc;
-    ndp_xchg::Reader *slot = nullptr;              // this buffer's entry, else the one not touched for longest
-    for (ndp_xchg::Reader &r : x->readers) if (r.ptr == d_gathered) slot = &r;
-    if (!slot) { slot = &x->readers[0]; for (ndp_xchg::Reader &r : x->readers) if (r.age < slot->age) slot = &r; }
-    slot->ptr = d_gathered; slot->stream = s; slot->age = k;
-    slot->seq = (h->track_steps && h->last_step_tracked) ? h->step_seq : 0u;
-    x->steps = k;
-    --x->ahead;
-    if (slot->seq) { h->track_pending = true; return 0; }     // (the getters wait for the step's own completion event: no second one)
-    return g.noted(0);
 }
 
 int ndp_tick_device(ndp_handle *h, const void *d_x_odom, const void *d_t, const void *d_vz, const void *d_throttle, int flags,

@@ -1,4 +1,5 @@
-"""Looks INTO the built libndp_nmpc_hip.so: the gfx950 code object it carries, the kernels' resource metadata and their ISA.
+"""Looks INTO the built libndp_nmpc_hip.so: the gfx950 code objects it carries (one per translation unit), the kernels' resource
+metadata and their ISA.
 
 Used by tests/test_isa_properties.py (no GPU needed) and scripts/isa_audit.py: properties of the shipped binary that no run-time
 test can see -- scratch (spill) bytes per lane of every rti_kernel instantiation, and that the epoch word of the downwash-ahead
@@ -14,60 +15,84 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 
-def device_code_object(so_path, arch="gfx950"):
-    """The bytes of the `arch` code object inside the clang offload bundle of a HIP shared library."""
+def device_code_objects(so_path, arch="gfx950"):
+    """The bytes of every `arch` code object inside a HIP shared library: one clang offload bundle per translation unit."""
     data = open(so_path, "rb").read()
+    out = []
     i = data.find(MAGIC)
-    if i < 0:
-        raise RuntimeError(f"{so_path}: no clang offload bundle")
-    n = struct.unpack_from("<Q", data, i + len(MAGIC))[0]
-    off = i + len(MAGIC) + 8
-    for _ in range(n):
-        o, sz, tl = struct.unpack_from("<QQQ", data, off)
-        off += 24
-        triple = data[off:off + tl].decode()
-        off += tl
-        if arch in triple and sz:
-            return data[i + o:i + o + sz]
-    raise RuntimeError(f"{so_path}: no {arch} code object in the bundle")
+    while i >= 0:
+        n = struct.unpack_from("<Q", data, i + len(MAGIC))[0]
+        off = i + len(MAGIC) + 8
+        for _ in range(n):
+            o, sz, tl = struct.unpack_from("<QQQ", data, off)
+            off += 24
+            triple = data[off:off + tl].decode()
+            off += tl
+            if arch in triple and sz:
+                out.append(data[i + o:i + o + sz])
+        i = data.find(MAGIC, off)
+    if not out:
+        raise RuntimeError(f"{so_path}: no {arch} code object in a clang offload bundle")
+    return out
 
 
 class CodeObject:
+    """The library's device code: every gfx950 code object in it, seen as one (kernel names are unique across them)."""
+
     def __init__(self, so_path, arch="gfx950"):
         self._td = tempfile.TemporaryDirectory()
-        self.path = os.path.join(self._td.name, "dev.co")
-        with open(self.path, "wb") as fh:
-            fh.write(device_code_object(so_path, arch))
+        self.paths = []
+        for k, blob in enumerate(device_code_objects(so_path, arch)):
+            self.paths.append(os.path.join(self._td.name, f"dev{k}.co"))
+            with open(self.paths[-1], "wb") as fh:
+                fh.write(blob)
         self._meta = None
+        self._home = None
+
+    def _notes(self, path):
+        txt = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", path], check=True, capture_output=True, text=True).stdout
+        meta = {}
+        for blk in re.split(r"\n\s+- \.agpr_count:", txt)[1:]:
+            blk = ".agpr_count:" + blk
+
+            def g(k, b=blk):
+                m = re.search(r"\." + k + r":\s+(\S+)", b)
+                return m.group(1) if m else None
+            name = g("name")
+            if name is None:
+                continue
+            meta[name] = dict(vgpr=int(g("vgpr_count")), agpr=int(g("agpr_count")), sgpr=int(g("sgpr_count")),
+                              spill=int(g("vgpr_spill_count")), sgpr_spill=int(g("sgpr_spill_count")),
+                              scratch=int(g("private_segment_fixed_size")), lds=int(g("group_segment_fixed_size")))
+        return meta
 
     def kernels(self):
-        """{mangled name: {vgpr, agpr, sgpr, spill, scratch, lds}} from the code object's metadata note."""
+        """{mangled name: {vgpr, agpr, sgpr, spill, scratch, lds}} from the code objects' metadata notes, merged.  Raises if a kernel
+        name appears in two code objects."""
         if self._meta is None:
-            txt = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", self.path], check=True, capture_output=True, text=True).stdout
-            meta = {}
-            for blk in re.split(r"\n\s+- \.agpr_count:", txt)[1:]:
-                blk = ".agpr_count:" + blk
-
-                def g(k, b=blk):
-                    m = re.search(r"\." + k + r":\s+(\S+)", b)
-                    return m.group(1) if m else None
-                name = g("name")
-                if name is None:
-                    continue
-                meta[name] = dict(vgpr=int(g("vgpr_count")), agpr=int(g("agpr_count")), sgpr=int(g("sgpr_count")),
-                                  spill=int(g("vgpr_spill_count")), sgpr_spill=int(g("sgpr_spill_count")),
-                                  scratch=int(g("private_segment_fixed_size")), lds=int(g("group_segment_fixed_size")))
-            self._meta = meta
+            meta, home = {}, {}
+            for path in self.paths:
+                for name, m in self._notes(path).items():
+                    if name in home:
+                        raise RuntimeError(f"kernel {name} is defined in two code objects ({home[name]}, {path})")
+                    meta[name], home[name] = m, path
+            self._meta, self._home = meta, home
         return self._meta
 
+    def code_object_of(self, symbol):
+        """Path of the extracted code object that holds kernel `symbol`."""
+        self.kernels()
+        return self._home[symbol]
+
     def disassemble(self, symbol):
-        """Instruction lines (mnemonic + operands, comments stripped) of one kernel."""
-        txt = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", f"--disassemble-symbols={symbol}", self.path],
+        """Instruction lines (mnemonic + operands, comments stripped) of one kernel, read from the code object that holds it."""
+        path = self.code_object_of(symbol)
+        txt = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", f"--disassemble-symbols={symbol}", path],
                              check=True, capture_output=True, text=True).stdout
         out = []
         for ln in txt.split("\n"):
             s = ln.split("//")[0].strip()
-            if not s or s.endswith(":") or s.startswith(("Disassembly", self.path, "/")) or "file format" in s:
+            if not s or s.endswith(":") or s.startswith(("Disassembly", path, "/")) or "file format" in s:
                 continue
             out.append(s)
         return out

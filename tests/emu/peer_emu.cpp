@@ -1,5 +1,5 @@
 // peer_emu.cpp -- csrc/peer_epoch.hpp between CPU processes (tests only; never linked into the product).
-// The per-tick publish step of ndp_hip.hip's peer_publish_kernel + peer_epoch_kernel, run by one thread per process over POSIX shared memory:
+// The per-tick publish step of exchange.hip's peer_publish_kernel + peer_epoch_kernel, run by one thread per process over POSIX shared memory:
 // the SAME protocol text (PeerProto) on a CPU memory backend, so that world-size-2 gloo tests can check writer -> reader
 // ordering, slot reuse and the bounded waits without a GPU.
 #include <string.h>

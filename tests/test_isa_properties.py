@@ -99,3 +99,15 @@ def test_lds_budget_of_the_reference_configuration():
     lib = _lib.load()
     assert 4 * 8 * lib.ndp_debug_lds_doubles(20) <= 160 * 1024
     assert 2 * 8 * lib.ndp_debug_lds_doubles(40) <= 160 * 1024
+
+
+def test_every_kernel_lies_in_exactly_one_code_object(co):
+    """The library is built from several translation units (ndp_hip.hip, exchange.hip), each with a code object of its own: kernels()
+    reads all of them (and raises on a kernel defined in two), and every unit's kernels are found."""
+    k = co.kernels()
+    assert len(co.paths) > 1
+    homes = {co.code_object_of(n) for n in k}
+    assert homes == set(co.paths), "a code object without kernels"
+    for part in ("mlp_stream_kernel", "tick_pre_kernel", "peer_publish_kernel", "plant_kernel", "rti_psens_kernel"):
+        assert any(part in n for n in k), part
+    assert sum("rti_kernel" in n for n in k) >= 20

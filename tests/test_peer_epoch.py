@@ -1,6 +1,6 @@
 """The per-tick neighbour exchange's ordering protocol (csrc/peer_epoch.hpp) between two CPU processes.
 
-The product runs PeerProto inside peer_publish_kernel (ndp_hip.hip) on buffers mapped across GPUs; tests/emu/peer_emu.cpp runs
+The product runs PeerProto inside peer_publish_kernel (exchange.hip) on buffers mapped across GPUs; tests/emu/peer_emu.cpp runs
 the SAME protocol text on a CPU memory backend over POSIX shared memory, so that gloo ranks can check -- without a GPU --
 what the reference gets from its ROS topic (nmpc_node.py:116-133,229-230 -> ndp_nmpc_leader_node.py:40,60-76): the reader of
 tick t sees exactly the windows the neighbour published for tick t, slots are not overwritten while they are being read, and
