@@ -18,7 +18,11 @@ second stream beside the control step of tick t (reported beside it in `downwash
 `--config 4` is BASELINE configs[3]: 4096 three-vehicle formations (12 288 instances) split over the GPUs (strong scaling).
 `--dump-outputs DIR`: what the headline form's last timed step computed, as DIR/<name>.npy (float64, at most 64 MB), so that two
 builds can be compared output for output on the same seeded inputs.
-Prints ONE JSON line on rank 0.  Exit code 1 (and "value": null) if the parity spot check fails or instances did not converge.
+A plain run times the headline form alone: set-up, warm-up, the --steps timed steps, the dump, the line.  `--full` adds everything
+else the line can carry: the other forms above, the parity spot checks against the CPU oracle, `repeat`, the roofline's figures that
+take launches of their own (kernel_us_dispatch, the stamped clock), `configs`, the interior-point / mixed / constrained / host / tick /
+rows legs, `cpu_baseline`, `config1` and `tick_remote`.
+Prints ONE JSON line on rank 0.  Exit code 1 (and "value": null) if instances did not converge or (--full) the parity spot check fails.
 """
 import argparse
 import csv
@@ -734,6 +738,11 @@ def main():
                     help="ndp_cfg.as_iter_max of the timed engine (default: the library's, 8); 0 = QP_AUTO as rounds 1-5 had it: early exit or interior point")
     ap.add_argument("--perturb", default="nominal", choices=["nominal", "mixed"],
                     help="mixed: 0.5 m / 1 m/s / 0.15 initial errors, ~20 %% of the instances need the interior-point loop")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the other downwash / exchange forms, the parity checks against the CPU "
+                         "oracle, the repeated passes, the per-dispatch kernel events and the clock stamps of the roofline, the configs "
+                         "block, the interior-point / mixed / constrained / host / tick / rows legs, the CPU baseline, config 1 and "
+                         "(N > 1) tick_remote.  Without it a run sets up, warms up, times the --steps steps, dumps and prints the line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-repeats", action="store_true", help="skip the extra timed passes over the same steps behind the timed region (`repeat`)")
     ap.add_argument("--no-tick-remote", action="store_true", help="N > 1: skip the `tick_remote` leg (ndp_tick with neighbours on the next rank)")
@@ -893,7 +902,7 @@ def main():
         # all-gather per step); the N = 1 headline above replays a hipGraph with no exchange at all.  The same steps are therefore
         # ALSO run here in exactly the N > 1 form -- a one-rank communicator, the pack + ncclAllGather on the library's stream per
         # step, host-launched and captured -- and reported as `scaling_baseline`: efficiency = value(N) / (N * scaling_baseline).
-        if not args.only_timed and not same_dev and args.perturb == "nominal":       # (the exchange forms gather the ranks' OWN reference windows: make_formation_shard's workload)
+        if args.full and not args.only_timed and not same_dev and args.perturb == "nominal":       # (the exchange forms gather the ranks' OWN reference windows: make_formation_shard's workload)
             baseline_modes = ((list(rccl_modes) if args.exchange in ("both", "rccl") else []) + (["peer"] if args.exchange in ("both", "peer") else [])
                               + (["peer_ahead"] if args.exchange == "peer_ahead" else []))
             modes = modes + baseline_modes
@@ -905,6 +914,9 @@ def main():
         modes = {"both": rccl_modes + ["peer"], "rccl": list(rccl_modes), "peer": ["peer"], "peer_ahead": ["peer_ahead"]}[args.exchange]
     if not (N + 1 <= 32 and args.qp_mode == 0 and not eng.work_queue):
         modes = [m for m in modes if m != "peer_ahead"]       # (the downwash-ahead launch holds one instance's rows in one 32-row tile)
+    if not args.full:
+        # the headline form alone; the rccl form's two launch modes are one form (`value` is the faster of the two, see finish)
+        modes = [m for m in modes if m in ("rccl", "rccl_graph")] if modes[0] in ("rccl", "rccl_graph") else modes[:1]
     peer, peer_err = None, None
     if any(m in PEER_FORMS for m in modes):
         stage["at"] = "PeerWindows: peer-mapped window buffers (IPC handles)"
@@ -1242,7 +1254,7 @@ def main():
         # REPEATS more times, each pass timed on its own (synchronise, clock, replay, synchronise): min / median / max say how much of
         # `value` is the box's mood.  One rank, graph launches only; not part of `value`.
         repeat_ms = []
-        if graphs and world == 1 and not tail and not args.no_repeats:
+        if graphs and world == 1 and not tail and args.full and not args.no_repeats:
             for _ in range(REPEATS):
                 torch.cuda.synchronize()
                 tr = time.perf_counter()
@@ -1251,7 +1263,7 @@ def main():
                         replay(gt)
                 torch.cuda.synchronize()
                 repeat_ms.append((time.perf_counter() - tr) * 1e3)
-        if graphs:                # start / stop events carried by EVERY dispatch packet of 64 host-launched steps, outside the timed region (kernel_us_dispatch_events)
+        if graphs and args.full:  # start / stop events carried by EVERY dispatch packet of 64 host-launched steps, outside the timed region (kernel_us_dispatch_events)
             eng.timing_enable(1)
             for i in range(64):
                 step(i, first=i == 0, last=i == 63)
@@ -1343,7 +1355,9 @@ def main():
             total = B * world * args.steps
             value = total / elapsed
             f_qp, f_mlp = algorithmic_flops_per_solve(N, sweeps, downwash)
-            pair_s = rti_ms * 1e-3 / max(rti_n, 1)       # HIP start / stop events carried by the launches' own dispatch packets (hipExtLaunchKernel)
+            # HIP start / stop events carried by the launches' own dispatch packets (hipExtLaunchKernel); None when no launch carried them
+            # (captured steps without --full: the 64 host-launched steps that carry them are a run of their own)
+            pair_s = rti_ms * 1e-3 / rti_n if rti_n else None
             mlp_s = mlp_ms * 1e-3 / max(mlp_n, 1) if mlp_n else 0.0
             # One launch per step on the launch stream (N = 1, no exchange): the kernel's average duration is the HIP-event time over
             # the timed region's launches / steps -- back to back in a replayed graph, so it includes the ~0.1 us between two nodes
@@ -1352,15 +1366,16 @@ def main():
             rti_s = head["region_ms"] * 1e-3 / args.steps if one_launch else pair_s
             prefetch_form = headline == "prefetch"
             fused = downwash and mlp_n == 0 and not prefetch_form   # gate + MLP run inside rti_kernel (one launch per step)
-            ach_tf = f_qp * B / rti_s / 1e12
+            ach_tf = f_qp * B / rti_s / 1e12 if rti_s else None
             abytes = algorithmic_bytes_per_solve(N, downwash)
             is_default = (not cfg4 and (fused or prefetch_form) and B == 1024 and N == 20 and args.qp_mode == 0 and args.perturb == "nominal" and world == 1)
             prof = committed_profile(is_default)
             # the committed profile annotates this run only if it describes it: its kernel duration must agree with the duration
             # measured live (HIP events) -- otherwise every figure derived from it is withheld and the mismatch is reported
             profile_mismatch = None
-            if prof["kernel_us"] is not None and not profile_agrees(prof["kernel_us"], rti_s * 1e6):
-                profile_mismatch = {"tag": prof["tag"], "kernel_us_rocprof": prof["kernel_us"], "kernel_us_live": rti_s * 1e6,
+            kernel_us = rti_s * 1e6 if rti_s else None
+            if prof["kernel_us"] is not None and not profile_agrees(prof["kernel_us"], kernel_us):
+                profile_mismatch = {"tag": prof["tag"], "kernel_us_rocprof": prof["kernel_us"], "kernel_us_live": kernel_us,
                                     "tolerance": PROFILE_TOLERANCE}
                 prof = {"kernel_us": None, "traffic": None, "wave_cycles_per_simd": None, "tag": prof["tag"]}
             # matrix-pipe occupancy estimate: a v_mfma_f64_16x16x4 / v_mfma_f32_32x32x2 holds the SIMD's pipe 64 cycles, the four-block
@@ -1376,7 +1391,7 @@ def main():
             clock_hz, clock_src = None, None
             if prof["wave_cycles_per_simd"] and prof["kernel_us"]:
                 clock_hz, clock_src = prof["wave_cycles_per_simd"] / (prof["kernel_us"] * 1e-6), f"profiles/{prof['tag']} PMC SQ_WAVE_CYCLES / kernel trace duration"
-            if clock_hz is None and not args.only_timed and not partial:
+            if clock_hz is None and args.full and not args.only_timed and not partial:
                 eng.debug_stamps(True)
                 eng.timing_enable(1)
                 step(0)
@@ -1404,15 +1419,15 @@ def main():
                            "neighbour_exchange": headline, **({"instance_order": args.instance_order} if cfg4 else {}),
                            "parallelism": f"instances sharded x{world}"},
                 "roofline": {"kernel": "rti_kernel", "bound": "mfma", "achieved": ach_tf, "peak": F64_MFMA_PEAK_TFLOPS,
-                             "unit": "TFLOP/s", "frac": ach_tf / F64_MFMA_PEAK_TFLOPS, "traffic": prof["traffic"],
+                             "unit": "TFLOP/s", "frac": ach_tf / F64_MFMA_PEAK_TFLOPS if ach_tf else None, "traffic": prof["traffic"],
                              "algorithmic_bytes": abytes * B, "profile_tag": prof["tag"],
                              **({"profile_mismatch": profile_mismatch} if profile_mismatch else {}),
-                             "kernel_us": rti_s * 1e6, "kernel_us_rocprof": prof["kernel_us"], "kernel_us_dispatch": pair_s * 1e6,
+                             "kernel_us": kernel_us, "kernel_us_rocprof": prof["kernel_us"], "kernel_us_dispatch": pair_s * 1e6 if pair_s else None,
                              "frac_rocprof": (f_qp * B / (prof["kernel_us"] * 1e-6) / 1e12 / F64_MFMA_PEAK_TFLOPS) if prof["kernel_us"] else None,
                              "flops_per_solve_f64": f_qp, "sweeps_per_solve": sweeps, "frac_interior_point": frac_ipm,
                              "clock_ghz": clock_hz / 1e9 if clock_hz else None,
-                             "mfma_pipe_busy_est": pipe_cycles / (rti_s * clock_hz) if clock_hz else None,
-                             "hbm_frac": abytes * B / (rti_s + mlp_s) / 1e9 / HBM_PEAK_GBS,
+                             "mfma_pipe_busy_est": pipe_cycles / (rti_s * clock_hz) if clock_hz and rti_s else None,
+                             "hbm_frac": abytes * B / (rti_s + mlp_s) / 1e9 / HBM_PEAK_GBS if rti_s else None,
                              **({"mlp_kernel_us": mlp_s * 1e6} if mlp_n else {})},
                 "parity_max_rel_vs_oracle": parity, "instances_not_converged": bad,
                 # SURVEY 8d words the metric over ndp_step calls INCLUDING the H2D of the inputs and the D2H of u0; `value` is the
@@ -1478,7 +1493,7 @@ def main():
                 if xchg_err and "rccl" in out["exchange"]:
                     out["exchange"]["rccl"]["library_collective_unavailable"] = xchg_err
                 out["exchange"]["headline"] = headline
-            extras = world == 1 and not args.only_timed and not cfg4 and args.perturb == "nominal" and args.qp_mode == 0 and not partial
+            extras = args.full and world == 1 and not args.only_timed and not cfg4 and args.perturb == "nominal" and args.qp_mode == 0 and not partial
             if extras and B == 1024 and N == 20 and not args.no_configs:
                 try:
                     from oracle import oracle as O_
@@ -1605,7 +1620,7 @@ def main():
                 except Exception as e:
                     out["rows"] = {"error": f"{type(e).__name__}: {e}"[:200]}
                 torch.cuda.set_stream(stream)
-            if not args.no_cpu_baseline and not args.only_timed and world == 1 and not cfg4 and not partial:
+            if args.full and not args.no_cpu_baseline and not args.only_timed and world == 1 and not cfg4 and not partial:
                 from oracle import oracle as O
                 nthr = min(O.num_threads(), effective_cores())
                 blob = np.fromfile(os.path.join(ROOT, "ndp_nmpc_qd_amd", "weights", "downwash_sn4.bin"), dtype="<f4")
@@ -1740,7 +1755,7 @@ def main():
             os._exit(code)
 
     def run_checked(m):
-        r = run_mode(m, check_parity=not args.only_timed)
+        r = run_mode(m, check_parity=args.full and not args.only_timed)
         if check_now and r.get("parity_fn") is not None:
             r["parity"] = r.pop("parity_fn")()
         return r
@@ -1764,7 +1779,7 @@ def main():
             if wd_state["done"]:                   # the timer fired while this leg was being torn down: it prints and exits
                 time.sleep(3600)
     # ---- N > 1: the node's control tick (ndp_tick) with every neighbour on the next rank -- a secondary leg like the forms above
-    if world > 1 and need_exchange and not cfg4 and N == 20 and args.qp_mode == 0 and not args.only_timed and not args.no_tick_remote:
+    if world > 1 and need_exchange and not cfg4 and N == 20 and args.qp_mode == 0 and args.full and not args.only_timed and not args.no_tick_remote:
         stage["at"] = "tick_remote (ndp_tick with neighbours on the next rank)"
         timer = threading.Timer(args.leg_timeout_s, watchdog, args=("tick_remote",))
         timer.daemon = True

@@ -2,7 +2,7 @@
 # Round-5 GPU sessions, one stage per gpurun call:  gpurun --timeout 1800 -- 'bash scripts/gpu_r05.sh <stage> [args]'
 #   tick     : tests of the tick and the list it reads + scripts/tick_rate.py + the headline's --only-timed run (regression check)
 #   tests    : the whole -m gpu suite
-#   bench    : the driver-shaped line (bench.py --steps 20 --warmup 5) + a 300-step run
+#   bench    : the driver-shaped line (bench.py --full --steps 20 --warmup 5) + a 300-step run
 #   profile  : scripts/profile_round.sh r05 (kernel trace + PMC passes of the headline), scripts/profile_rows.sh r05, HBM ceilings, tick stamps
 #   side     : 50 Hz cadence, host latency, stress parity
 # then: bash scripts/collect_profiles.sh r05  (gpurun_out/ -> profiles/)
@@ -24,7 +24,7 @@ tests)
   timeout 1700 python -m pytest tests -m gpu -q --timeout 600 "$@" 2>&1 | tail -40 > $O/tests.txt; tail -15 $O/tests.txt
   ;;
 bench)
-  timeout 600 python3 bench.py --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; tail -c 1500 $O/bench_driver.err; wc -c $O/bench_driver.json; hl < $O/bench_driver.json
+  timeout 600 python3 bench.py --full --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; tail -c 1500 $O/bench_driver.err; wc -c $O/bench_driver.json; hl < $O/bench_driver.json
   timeout 300 python3 bench.py --only-timed --steps 300 --warmup 30 --downwash-form fused 2>> $O/bench_driver.err | tee $O/bench300.json | hl
   ;;
 profile)

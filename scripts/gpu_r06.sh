@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-6 GPU sessions, one stage per gpurun call:  gpurun --timeout 1800 -- 'bash scripts/gpu_r06.sh <stage>'
 #   tests    : the whole -m gpu suite
-#   bench    : the driver-shaped line (bench.py --steps 20 --warmup 5) + a 300-step run + the mixed / constrained / interior-point --only-timed runs
+#   bench    : the driver-shaped line (bench.py --full --steps 20 --warmup 5) + a 300-step run + the mixed / constrained / interior-point --only-timed runs
 #   profile  : kernel trace + PMC passes of the headline (scripts/profile_round.sh r06), of the MIXED workload (r06mixed) and of
 #              config 5's condensed study kernels (kernel trace + SQ counters: matrix-pipe busy)
 #   side     : tick rate, config 5 table (scripts/config5_condensed.py), rows profile
@@ -16,7 +16,7 @@ tests)
   timeout 1700 python -m pytest tests -m gpu -q --timeout 600 "$@" 2>&1 | tail -40 > $O/tests.txt; tail -8 $O/tests.txt
   ;;
 bench)
-  timeout 900 python3 bench.py --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; tail -c 300 $O/bench_driver.err; wc -c $O/bench_driver.json; hl < $O/bench_driver.json
+  timeout 900 python3 bench.py --full --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; tail -c 300 $O/bench_driver.err; wc -c $O/bench_driver.json; hl < $O/bench_driver.json
   timeout 300 python3 bench.py --only-timed --steps 300 --warmup 30 --downwash-form fused 2>> $O/bench_driver.err | tee $O/bench300.json | hl
   timeout 300 python3 bench.py --only-timed --steps 200 --warmup 20 --perturb mixed 2>> $O/bench_driver.err | tee $O/bench_mixed.json | hl
   timeout 300 python3 bench.py --only-timed --steps 200 --warmup 20 --perturb mixed --as-iter-max 0 2>> $O/bench_driver.err | tee $O/bench_mixed_as_off.json | hl

@@ -10,6 +10,6 @@ for blk in ('forms','downwash_forms','scaling_baseline','exchange'):
     for k,v in (d.get(blk) or {}).items():
         if isinstance(v, dict): print('    %s %s %s' % (blk, k, {kk: vv for kk, vv in v.items() if kk in ('value','us','ok','counters','ticks','ack_timeouts','epoch_timeouts','slot_mismatches','force_timeouts','slot_timeouts')}))
 "; }
-timeout 900 python3 bench.py --steps 20000 --warmup 50 2> $O/default.err | sm soak_default | tee $O/soak.txt
-timeout 600 python3 bench.py --config 4 --formations 512 --steps 20000 --warmup 50 2> $O/c4.err | sm soak_c4 | tee -a $O/soak.txt
+timeout 900 python3 bench.py --full --steps 20000 --warmup 50 2> $O/default.err | sm soak_default | tee $O/soak.txt
+timeout 600 python3 bench.py --full --config 4 --formations 512 --steps 20000 --warmup 50 2> $O/c4.err | sm soak_c4 | tee -a $O/soak.txt
 timeout 900 python3 scripts/tick_soak.py 2> $O/tick.err | grep -v amdgpu | tee -a $O/soak.txt

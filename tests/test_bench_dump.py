@@ -77,3 +77,22 @@ def test_dump_is_the_same_whatever_the_clock_warm_up(tmp_path):
     assert np.all(np.isfinite(a["u0"])) and not a["status"].any()
     for n in NAMES:
         assert np.array_equal(a[n], b[n]), n
+
+
+@pytest.mark.gpu
+def test_a_plain_run_is_the_headline_alone():
+    """Without --full the line is the headline form's: its figures and nothing that takes a run of its own (other forms, the
+    oracle's parity check, repeated passes, the configs block and the other legs, the CPU baseline)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 20 and line["warmup"] == 5 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "solves/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["config"]["neighbour_exchange"] == "fused" and line["instances_not_converged"] == 0
+    assert line["parity_max_rel_vs_oracle"] is None and line["roofline"]["kernel_us"] > 0
+    assert set(line["forms"]) == {"fused"}
+    for block in ("configs", "ipm_always", "mixed", "constrained", "host", "tick", "rows", "cpu_baseline", "config1", "repeat",
+                  "scaling_baseline"):
+        assert block not in line, block
