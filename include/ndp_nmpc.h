@@ -586,6 +586,11 @@ int ndp_debug_host_timing(ndp_handle *h, double *out4);
 /* ... and what the host path runs on: out3 = {hardware threads of the machine, cores this process may really use (affinity mask and
  * cgroup CPU quota), pack threads the handle started (-1: no host-array step yet)}. */
 int ndp_debug_host_info(ndp_handle *h, int32_t *out3);
+/* Test hook: which control-step kernels this handle has launched.  mask (or NULL) receives the rows of the library's kernel table
+ * (enum RtiId in csrc/ndp_hip.hip) launched since the last call, as bit RtiId, and reading clears it; a step captured into a graph
+ * counts once, at capture.  out3 (or NULL) = {rows of the table, instances per workgroup, 1 if the downwash network can run inside
+ * the control step's launch (else a separate launch first)}. */
+int ndp_debug_rti_launched(ndp_handle *h, uint64_t *mask, int32_t *out3);
 int ndp_step_debug(ndp_handle *h, const double *x0, const double *xr, const double *ur, const float *f,
                    const double *other, const double *ego_xy, double *u0, double *lds_dump);
 

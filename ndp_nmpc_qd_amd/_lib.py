@@ -55,6 +55,7 @@ EXPORTS = [
     "ndp_tick_config_remote", "ndp_tick_advance_device", "ndp_tick_window_pv_device", "ndp_tick_step_device", "ndp_xchg_tick_windows", "ndp_xchg_tick_begin", "ndp_xchg_tick_step", "ndp_xchg_tick_async",
     "ndp_sens_enable", "ndp_sens_level", "ndp_get_sens", "ndp_device_sens_u0", "ndp_device_sens_u", "ndp_device_sens_x",
     "ndp_sens_params_enable", "ndp_sens_params_enabled", "ndp_get_sens_params", "ndp_device_sens_xr", "ndp_device_sens_ur", "ndp_device_sens_f",
+    "ndp_debug_rti_launched",
 ]
 
 _lib = None
@@ -136,6 +137,7 @@ def load():
         getattr(lib, name).restype = vp
     lib.ndp_set_active_set.argtypes = [vp] * 2
     lib.ndp_debug_host_info.argtypes = [vp, vp]
+    lib.ndp_debug_rti_launched.argtypes = [vp, C.POINTER(C.c_uint64), vp]
     lib.ndp_ref_list_reset.argtypes = [vp]
     lib.ndp_ref_list_fix_pt.argtypes = [vp, vp, C.c_int]
     lib.ndp_ref_list_window.argtypes = [vp] * 4
@@ -200,6 +202,20 @@ def lds_layout(N):
     out = (C.c_int * 8)()
     load().ndp_debug_lds_layout(int(N), out)
     return dict(zip(("XI", "MB", "CB", "MB_STRIDE", "CB_STRIDE", "total", "stamps"), list(out)[:7]))
+
+
+def rti_kernel_names(src=os.path.join(_HERE, "csrc", "ndp_hip.hip")):
+    """The rows of the library's control-step kernel table in RtiId order (enum RtiId in csrc/ndp_hip.hip; bit i of
+    ndp_debug_rti_launched's mask is row i)."""
+    import re
+    with open(src) as fh:
+        m = re.search(r"enum RtiId \{(.*?)\};", fh.read(), re.S)
+    if m is None:
+        raise RuntimeError(f"{src}: no enum RtiId")
+    names = re.findall(r"\b([A-Z][A-Z0-9_]*)\b", re.sub(r"//[^\n]*", "", m.group(1)))
+    if names[-1] != "RTI_KERNELS":
+        raise RuntimeError(f"{src}: enum RtiId does not end with RTI_KERNELS")
+    return names[:-1]
 
 
 def default_cfg(**kw):

@@ -647,6 +647,17 @@ class BatchedNMPC:
     def synchronize(self):
         self._check(self._lib.ndp_synchronize(self._h), "ndp_synchronize")
 
+    def debug_rti_launched(self):
+        """(names, waves, fusable): the rows of the control-step kernel table (csrc/ndp_hip.hip: enum RtiId) this handle launched since
+        the last call (ndp_debug_rti_launched; reading clears them), its instances per workgroup, and whether the downwash network can
+        run inside the control step's launch."""
+        mask, out = C.c_uint64(0), np.zeros(3, dtype=np.int32)
+        self._check(self._lib.ndp_debug_rti_launched(self._h, C.byref(mask), _lib.ptr(out)), "ndp_debug_rti_launched")
+        names = _lib.rti_kernel_names()
+        if len(names) != out[0]:
+            raise NdpError(f"the library has {out[0]} control-step kernels, enum RtiId names {len(names)}")
+        return {n for i, n in enumerate(names) if mask.value >> i & 1}, int(out[1]), bool(out[2])
+
     def debug_stamps(self, enable=True, read=False):
         """Whole-batch phase stamps (profiling hook): returns [B,24] of the last step when read=True."""
         out = np.zeros((self.B, 24)) if read else None

@@ -6,6 +6,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+#include <cstdint>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -25,6 +27,8 @@ struct ndp_handle {
     int lds_per_wave = 0;      // doubles
     int waves = 4;             // instances per workgroup
     int n_simd = 1024;         // SIMDs of the device (4 per CU)
+    // bit RtiId of every control-step kernel launched since ndp_debug_rti_launched last read it (launch_kern; relaxed: a test hook)
+    mutable std::atomic<uint64_t> rti_launched{0};
     bool use_queue = false;    // interior-point solves through the work list: producer + consumer launch per step (QueueArgs)
     // cfg.work_queue = 0 at (N, n_rti) = (20, 1), batch >= 2 instances per SIMD: the list is switched by what the steps do (queue_policy)
     bool queue_auto = false;

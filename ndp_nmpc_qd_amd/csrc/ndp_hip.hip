@@ -1902,6 +1902,7 @@ static const RtiKern k_rti[] = {
     {(const void *)RTI_PSENS_K(4, true, 0, 0), 4, true}, {(const void *)RTI_PSENS_K(2, true, 0, 0), 2, true},
 };
 static_assert(sizeof(k_rti) / sizeof(k_rti[0]) == RTI_KERNELS, "one row per RtiId");
+static_assert(RTI_KERNELS <= 64, "ndp_debug_rti_launched reports the rows as bits of one 64-bit mask");
 
 extern "C" {
 
@@ -2325,6 +2326,7 @@ static void launch_kern(const ndp_handle *h, RtiId id, hipStream_t s, KernArgs &
                         hipEvent_t stop = nullptr)
 {
     const RtiKern &k = k_rti[id];
+    h->rti_launched.fetch_or(1ull << id, std::memory_order_relaxed);
     const dim3 grid((h->cfg.batch + k.waves - 1) / k.waves), block(64 * k.waves);
     const size_t shm = (size_t)h->lds_per_wave * sizeof(double) * k.waves;
     PSensArgs pa{h->dPSensXr, h->dPSensUr, h->dPSensF};
@@ -2730,6 +2732,18 @@ int ndp_debug_host_info(ndp_handle *h, int32_t *out3)
     out3[0] = (int32_t)std::thread::hardware_concurrency();
     out3[1] = h->slots_ready ? h->host_cores : usable_cores();
     out3[2] = h->slots_ready ? h->pack_threads : -1;
+    return 0;
+}
+
+int ndp_debug_rti_launched(ndp_handle *h, uint64_t *mask, int32_t *out3)
+{
+    if (!h) return -1;
+    if (mask) *mask = h->rti_launched.exchange(0, std::memory_order_relaxed);
+    if (out3) {
+        out3[0] = RTI_KERNELS;
+        out3[1] = h->waves;
+        out3[2] = can_fuse(h) ? 1 : 0;
+    }
     return 0;
 }
 
