@@ -42,7 +42,7 @@ extern "C" {
 /* Version of this interface: bumped whenever an exported signature or the layout of ndp_cfg changes.  A binding built against
  * another header must refuse to run: ndp_abi_version() is what the loaded library was built with, ndp_cfg_size() its
  * sizeof(ndp_cfg) (ndp_create / ndp_default_cfg read and write that many bytes of the caller's struct). */
-#define NDP_ABI_VERSION 7
+#define NDP_ABI_VERSION 8
 int ndp_abi_version(void);
 size_t ndp_cfg_size(void);
 
@@ -317,6 +317,27 @@ int ndp_get_sens_params(ndp_handle *h, double *du0_dxr, double *du0_dur, double 
 void *ndp_device_sens_xr(ndp_handle *h);
 void *ndp_device_sens_ur(ndp_handle *h);
 void *ndp_device_sens_f(ndp_handle *h);
+
+/* Adjoint of the control step (reverse mode, a vector-Jacobian product): the derivative of one recorded step's QP -- with the same
+ * meaning as the sensitivities above (fixed final set: exact, pinned inputs' rows exactly 0; interior point: its last Newton system;
+ * nonzero status: NaN in every output of the instance) -- contracted with upstream gradients of its outputs u0 [B][4], X [B][N+1][10] and
+ * U [B][N][4] (the new iterate; gu0 adds to U_0), written as dL/dx0 [B][10], dL/dxr [B][N+1][10], dL/dur [B][N][4], dL/df [B][N+1][3] (fp64;
+ * stage 0's xr row and f_N are exactly 0; dL/df as du0/df: in every configuration).  Needs no sensitivities on, whatever ndp_sens_level.
+ * The tape: what determines one step, copied by the caller device-to-device on its stream BEFORE the step --
+ *   X_lin [B][N+1][10], U_lin [B][N][4] (ndp_device_iterate_x / _u) and act_lin [B][4N] int8 (ndp_device_active_set; NULL = empty sets),
+ * plus the step's own x0, xr, ur and the fp32 force it used (the caller's f, or ndp_device_force after a step with neighbour windows;
+ * NULL = no force).  The tape is caller-owned: any recorded step can be differentiated later, in any order.  At N = 20: 2.7 KB per instance.
+ * ndp_step_vjp_device enqueues on `stream`: the step is recomputed from the tape (the same program, into a workspace of the handle -- the
+ * engine's iterate, kept sets, sensitivity buffers and the tape are never written; two calls on one tape give bit-identical results),
+ * then one adjoint sweep of its last QP.  Upstream pointers: NULL = 0, not all NULL; output pointers: NULL = not written.
+ * d_u0_check [B][4] fp64 / d_status_check [B] int32 (optional): the recompute's u0 and status, equal to the recorded step's.
+ * Served for qp_precision 0, n_rti = 1, N <= 27 (N = 20 and the run-time-horizon kernel); anything else returns -2 with a reason in
+ * ndp_last_error and launches nothing. */
+void *ndp_device_active_set(ndp_handle *h);
+int ndp_step_vjp_device(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
+                        const void *d_X_lin, const void *d_U_lin, const void *d_act_lin,
+                        const void *d_gu0, const void *d_gX, const void *d_gU,
+                        void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_u0_check, void *d_status_check, void *stream);
 
 /* Per-kernel timing with HIP events recorded on the stream each kernel is launched on:
  * on = n > 0 brackets every n-th launch of each kernel (n = 1: every launch), on = 0 stops and clears.

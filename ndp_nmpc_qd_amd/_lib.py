@@ -16,7 +16,7 @@ WEIGHTS_PATH = os.path.join(_HERE, "weights", "downwash_sn4.bin")
 NX, NU = 10, 4
 MLP_NPARAM = 17859
 QP_AUTO, QP_IPM_ALWAYS = 0, 1
-ABI_VERSION = 7          # include/ndp_nmpc.h: NDP_ABI_VERSION (checked against the loaded library in load())
+ABI_VERSION = 8          # include/ndp_nmpc.h: NDP_ABI_VERSION (checked against the loaded library in load())
 TICK_ESTIMATE, TICK_WANT_U0, TICK_T_UNIFORM = 1, 2, 4
 
 
@@ -55,7 +55,7 @@ EXPORTS = [
     "ndp_tick_config_remote", "ndp_tick_advance_device", "ndp_tick_window_pv_device", "ndp_tick_step_device", "ndp_xchg_tick_windows", "ndp_xchg_tick_begin", "ndp_xchg_tick_step", "ndp_xchg_tick_async",
     "ndp_sens_enable", "ndp_sens_level", "ndp_get_sens", "ndp_device_sens_u0", "ndp_device_sens_u", "ndp_device_sens_x",
     "ndp_sens_params_enable", "ndp_sens_params_enabled", "ndp_get_sens_params", "ndp_device_sens_xr", "ndp_device_sens_ur", "ndp_device_sens_f",
-    "ndp_debug_rti_launched",
+    "ndp_debug_rti_launched", "ndp_device_active_set", "ndp_step_vjp_device",
 ]
 
 _lib = None
@@ -136,6 +136,9 @@ def load():
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = vp
     lib.ndp_set_active_set.argtypes = [vp] * 2
+    lib.ndp_device_active_set.argtypes = [vp]
+    lib.ndp_device_active_set.restype = vp
+    lib.ndp_step_vjp_device.argtypes = [vp] * 18
     lib.ndp_debug_host_info.argtypes = [vp, vp]
     lib.ndp_debug_rti_launched.argtypes = [vp, C.POINTER(C.c_uint64), vp]
     lib.ndp_ref_list_reset.argtypes = [vp]

@@ -499,6 +499,60 @@ class BatchedNMPC:
             out.append(torch.as_tensor(_DevMem(fn(self._h), shape), device=dev))
         return tuple(out)
 
+    # ------------------------------------------------------------------ adjoint of the control step (reverse mode)
+    def record_tape(self, stream=None):
+        """(X_lin [B,N+1,10] float64, U_lin [B,N,4] float64, act_lin [B,N,4] int8): device clones of the iterate and kept active sets the
+        NEXT step on `stream` (a torch CUDA stream; default: the current one) starts from -- what step_vjp_device needs, beside that
+        step's own x0, xr, ur and force, to differentiate it later (ndp_step_vjp_device).  The clones are ordered on `stream`: record the
+        tape on the stream the step will run on, before it.  torch's default stream cannot be named through the C-ABI (a NULL stream is
+        the engine's own), so there the engine's work is waited for first and the clones after."""
+        import torch
+        from .dist import _DevMem
+        dev = torch.device("cuda", self.cfg.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        default = s.cuda_stream == 0
+        if default:
+            self.synchronize()
+        views = ((self._lib.ndp_device_iterate_x, (self.B, self.N + 1, 10), "<f8"), (self._lib.ndp_device_iterate_u, (self.B, self.N, 4), "<f8"),
+                 (self._lib.ndp_device_active_set, (self.B, self.N, 4), "|i1"))
+        with torch.cuda.stream(s):
+            tape = tuple(torch.as_tensor(_DevMem(fn(self._h), shape, ts), device=dev).clone() for fn, shape, ts in views)
+        if default:
+            s.synchronize()
+        return tape
+
+    def step_vjp_device(self, x0, xr, ur, tape, gu0=None, gX=None, gU=None, f=None, gx0=None, gxr=None, gur=None, gf=None,
+                        u0_check=None, status_check=None, stream=None):
+        """Enqueues the adjoint of one recorded step on `stream` (ndp_step_vjp_device; include/ndp_nmpc.h): the step is recomputed from
+        `tape` (record_tape) and its x0, xr, ur and fp32 force f (the caller's, or device_force() after a step with neighbour windows;
+        None = no force), and the upstream gradients gu0 [B,4], gX [B,N+1,10], gU [B,N,4] (None = 0, not all None) are contracted with
+        the derivative of its QP into gx0 [B,10], gxr [B,N+1,10], gur [B,N,4], gf [B,N+1,3] (float64 CUDA tensors the caller allocates;
+        None = not written).  u0_check [B,4] float64 / status_check [B] int32: the recompute's u0 and status.  Sensitivities need not be
+        on; nothing of the engine's state is written.  stream None or torch's default stream: the call goes on the engine's own stream
+        (the C-ABI's NULL) behind a wait for torch's; read the outputs after engine.synchronize()."""
+        import torch
+        B, N = self.B, self.N
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        d = self._dptr
+        X, U, A = tape
+        self._check(self._lib.ndp_step_vjp_device(
+            self._h, d(x0, torch.float64, (B, 10)), d(xr, torch.float64, (B, N + 1, 10)), d(ur, torch.float64, (B, N, 4)),
+            d(f, torch.float32, (B, N + 1, 3)), d(X, torch.float64, (B, N + 1, 10)), d(U, torch.float64, (B, N, 4)),
+            d(A, torch.int8, (B, N, 4)), d(gu0, torch.float64, (B, 4)), d(gX, torch.float64, (B, N + 1, 10)),
+            d(gU, torch.float64, (B, N, 4)), d(gx0, torch.float64, (B, 10)), d(gxr, torch.float64, (B, N + 1, 10)),
+            d(gur, torch.float64, (B, N, 4)), d(gf, torch.float64, (B, N + 1, 3)), d(u0_check, torch.float64, (B, 4)),
+            d(status_check, torch.int32, (B,)), self._stream(stream)), "ndp_step_vjp_device")
+
+    def device_iterate(self):
+        """The engine's iterate as CUDA tensor views (no copy): (X [B,N+1,10], U [B,N,4]) float64 (ndp_device_iterate_x / _u); valid once
+        the step's stream has reached them; the next step overwrites them."""
+        import torch
+        from .dist import _DevMem
+        dev = torch.device("cuda", self.cfg.device)
+        return (torch.as_tensor(_DevMem(self._lib.ndp_device_iterate_x(self._h), (self.B, self.N + 1, 10)), device=dev),
+                torch.as_tensor(_DevMem(self._lib.ndp_device_iterate_u(self._h), (self.B, self.N, 4)), device=dev))
+
     # ------------------------------------------------------------------ HBM-resident API (torch CUDA tensors)
     @staticmethod
     def _dptr(t, dtype, shape):

@@ -48,6 +48,10 @@ struct ndp_handle {
     double *dSensU0 = nullptr, *dSensU = nullptr, *dSensX = nullptr;   // [B][4][10], [B][N][4][10], [B][N+1][10][10] (the last two: level 2)
     // ndp_sens_params_enable: du0/dxr [B][4][N+1][10], du0/dur [B][4][N][4], du0/df [B][4][N+1][3] (rti_psens_kernel); null: off
     double *dPSensXr = nullptr, *dPSensUr = nullptr, *dPSensF = nullptr;
+    // ndp_step_vjp_device's workspace (first call): the tape's iterate X | U, then u0 [B][4]; status | iterations [B] each; kept sets
+    double *dVjp = nullptr;
+    int *dVjpSt = nullptr;
+    signed char *dVjpAct = nullptr;
     double *dThr = nullptr;    // hover-throttle estimator state, SoA [8][B]
     double *dStamps = nullptr; // [B][NDP_NSTAMP] whole-batch phase stamps (ndp_debug_stamps)
     double *dTraj = nullptr;   // f1: the trajectories and the tick's caches (layout: TrajView)

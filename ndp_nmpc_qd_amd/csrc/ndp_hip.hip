@@ -335,6 +335,39 @@ __global__ __launch_bounds__(64 * WAVES) void rti_psens_kernel(KernArgs ka, Sens
 #include "rti_kernel_body.inc"
 }
 
+// The adjoint of the control step (ndp_step_vjp_device, RtiWave::vjp_out): the step's own program, recomputed from a caller's tape, then
+// the adjoint of its last QP contracted with the caller's upstream gradients.  The tape (the iterate and kept set before the step) has been
+// copied into the handle's VJP workspace by the host, so the recompute advances that copy: the kernel writes nothing but the workspace and
+// its outputs.  Three slots (N <= 27), qp_precision 0, one RTI iteration, in place; the force read from global memory (fp32, or none).
+// Instances per workgroup: blockDim.x / 64 (the handle's).  Not a row of k_rti: its own launcher (ndp_step_vjp_device).
+struct VjpArgs {
+    const double *gu0, *gX, *gU;
+    double *gx0, *gxr, *gur, *gf;
+};
+template <int NC>
+__global__ __launch_bounds__(256) void rti_vjp_kernel(KernArgs ka, VjpArgs va)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const RtiParams &P = ka.P;
+    const int waves = (int)(blockDim.x >> 6), wave = (int)(threadIdx.x >> 6);
+    const int inst = __builtin_amdgcn_readfirstlane((int)blockIdx.x * waves + wave);
+    if (inst >= ka.B) return;
+    const int N = NC ? NC : P.N;
+    RtiIo io;
+    bind_instance(io, ka.bp, inst, N);
+    const int lpw = NC ? ((lds_doubles(NC) + 1) & ~1) : ka.lds_per_wave;
+    WaveGfx950::lds_ptr lds = (WaveGfx950::lds_ptr)(smem + (size_t)wave * lpw);
+    using Prog = RtiWave<WaveGfx950, 3, NC, true, NC ? 1 : 0>;
+    const size_t i = (size_t)inst, nx = (size_t)(N + 1) * NX, nu = (size_t)N * NU, nf = (size_t)(N + 1) * 3;
+    const VjpIo vo{va.gu0 ? va.gu0 + i * NU : nullptr, va.gX ? va.gX + i * nx : nullptr, va.gU ? va.gU + i * nu : nullptr,
+                   va.gx0 ? va.gx0 + i * NX : nullptr, va.gxr ? va.gxr + i * nx : nullptr, va.gur ? va.gur + i * nu : nullptr,
+                   va.gf ? va.gf + i * nf : nullptr};
+    typename Prog::InBuf inb;
+    double x0v;
+    Prog::issue_first(P, io, inb, x0v);
+    Prog::template run<false, true, false, false, true>(P, io, lds, inb, x0v, nullptr, nullptr, &vo);
+}
+
 // test hook: one v_mfma_f64_16x16x4_f64 / v_mfma_f64_4x4x4_4b_f64 with caller-chosen per-lane operands (pins the register maps)
 __global__ void mfma_probe_kernel(const double *a, const double *b, const double *c, double *d)
 {
@@ -1971,7 +2004,7 @@ int ndp_destroy(ndp_handle *h)
     h->pool.reset();
     void *ptrs[] = {h->dForceAB[0], h->dForceAB[1], h->dProto, h->dRingX, h->dTraj, h->dTables, h->dStamps, h->dRelay, h->dThr, h->sThr, h->dKC, h->dForce, h->dFrag,
                     h->dIn, h->dOut, h->sdbg, h->dQctr, h->dQids, h->dTickIndex, h->dTickThrust, h->dAct,
-                    h->dSensU0, h->dSensU, h->dSensX, h->dPSensXr, h->dPSensUr, h->dPSensF};
+                    h->dSensU0, h->dSensU, h->dSensX, h->dPSensXr, h->dPSensUr, h->dPSensF, h->dVjp, h->dVjpSt, h->dVjpAct};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &sl : h->slot) {
@@ -2139,6 +2172,9 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
     for (const RtiKern &k : k_rti)      // (the sensitivity kernels: ndp_sens_enable)
         if (!k.sens && (e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) != hipSuccess)
             return fail("hipFuncSetAttribute", e);
+    for (const void *fn : {(const void *)rti_vjp_kernel<20>, (const void *)rti_vjp_kernel<0>})     // (the adjoint: ndp_step_vjp_device)
+        if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) != hipSuccess)
+            return fail("hipFuncSetAttribute(rti_vjp_kernel)", e);
     hipLaunchKernelGGL(throttle_reset_kernel, dim3((cfg->batch + 255) / 256), dim3(256), 0, h->stream, h->dThr, 50.0, cfg->batch);
     if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("hipStreamSynchronize", e);
     *out = h;
@@ -3762,6 +3798,53 @@ int ndp_get_sens_params(ndp_handle *h, double *du0_dxr, double *du0_dur, double 
 void *ndp_device_sens_xr(ndp_handle *h) { return h ? h->dPSensXr : nullptr; }
 void *ndp_device_sens_ur(ndp_handle *h) { return h ? h->dPSensUr : nullptr; }
 void *ndp_device_sens_f(ndp_handle *h) { return h ? h->dPSensF : nullptr; }
+
+// ---- adjoint of the control step (rti_vjp_kernel, RtiWave::vjp_out)
+void *ndp_device_active_set(ndp_handle *h) { return h ? h->dAct : nullptr; }
+
+int ndp_step_vjp_device(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
+                        const void *d_X_lin, const void *d_U_lin, const void *d_act_lin,
+                        const void *d_gu0, const void *d_gX, const void *d_gU,
+                        void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_u0_check, void *d_status_check, void *stream)
+{
+    Entry g(h, true, stream);
+    if (g.rc) return g.rc;
+    const ndp_cfg &c = h->cfg;
+    const char *why = nullptr;
+    if (c.n_rti != 1) why = "ndp_step_vjp_device: the adjoint needs n_rti = 1 (the derivative of the step's one QP)";
+    else if (c.qp_precision != 0) why = "ndp_step_vjp_device: the adjoint needs qp_precision 0 (the fp64 product path)";
+    else if (slots_for(c.N) > 3) why = "ndp_step_vjp_device: the adjoint is served for N <= 27 only (the five-slot kernels of N >= 28 have none)";
+    else if (!d_x0 || !d_xr || !d_ur || !d_X_lin || !d_U_lin) why = "ndp_step_vjp_device: x0, xr, ur and the tape's iterate (X_lin, U_lin) are required";
+    else if (!d_gu0 && !d_gX && !d_gU) why = "ndp_step_vjp_device: no upstream gradient (gu0, gX and gU all NULL)";
+    else if (d_f && !c.use_fd) why = "ndp_step_vjp_device: a disturbance force needs use_fd = 1 (NDP model)";
+    if (why) { h->err = why; return -2; }
+    const size_t B = c.batch;
+    if (!h->dVjp) {
+        NDP_HIP(h, hipMalloc((void **)&h->dVjp, (nxs(h) + nus(h) + B * NU) * 8));
+        NDP_HIP(h, hipMalloc((void **)&h->dVjpSt, B * 2 * 4));
+        NDP_HIP(h, hipMalloc((void **)&h->dVjpAct, act_bytes(h)));
+    }
+    double *X = h->dVjp, *U = X + nxs(h), *u0 = U + nus(h);
+    int *st = h->dVjpSt, *it = st + B;
+    hipStream_t s = g.s;
+    // the tape is copied, never written: the recompute advances the copy (two calls on one tape give the same result)
+    NDP_HIP(h, hipMemcpyAsync(X, d_X_lin, nxs(h) * 8, hipMemcpyDeviceToDevice, s));
+    NDP_HIP(h, hipMemcpyAsync(U, d_U_lin, nus(h) * 8, hipMemcpyDeviceToDevice, s));
+    if (d_act_lin) NDP_HIP(h, hipMemcpyAsync(h->dVjpAct, d_act_lin, act_bytes(h), hipMemcpyDeviceToDevice, s));
+    else NDP_HIP(h, hipMemsetAsync(h->dVjpAct, 0, act_bytes(h), s));
+    BatchPtrs bp{h->dKC, h->dTables, (const double *)d_x0, (const double *)d_xr, (const double *)d_ur, (const float *)d_f, X, U,
+                 d_u0_check ? (double *)d_u0_check : u0, d_status_check ? (int *)d_status_check : st, it, nullptr, nullptr, nullptr, nullptr,
+                 (size_t)(c.N + 1) * NX, (size_t)c.N * NU, (size_t)NX, nullptr, nullptr, nullptr, c.mass, 0, h->dVjpAct};
+    KernArgs ka{h->P, bp, (int)B, h->lds_per_wave, MlpArgs{}, QueueArgs{}, LateArgs{}, TickArgs{}};
+    VjpArgs va{(const double *)d_gu0, (const double *)d_gX, (const double *)d_gU, (double *)d_gx0, (double *)d_gxr, (double *)d_gur,
+               (double *)d_gf};
+    const int W = h->waves;
+    const void *fn = c.N == 20 ? (const void *)rti_vjp_kernel<20> : (const void *)rti_vjp_kernel<0>;
+    void *args[] = {&ka, &va};
+    NDP_HIP(h, hipLaunchKernel(fn, dim3((unsigned)((B + W - 1) / W)), dim3(64 * W), args, (size_t)h->lds_per_wave * sizeof(double) * W, s));
+    NDP_HIP(h, hipGetLastError());
+    return g.noted(0);
+}
 int ndp_refine_active(ndp_handle *h) { return h ? (int)(h->cfg.ipm_refine > 0 && slots_for(h->cfg.N) <= 3 && h->cfg.qp_precision == 0) : -1; }
 
 int ndp_synchronize(ndp_handle *h)

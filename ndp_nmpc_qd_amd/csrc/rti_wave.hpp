@@ -170,6 +170,12 @@ struct PSensIo {
 NDP_HD int psens_xr_pitch(int N) { return NU * (N + 1) * NX; }
 NDP_HD int psens_ur_pitch(int N) { return NU * N * NU; }
 NDP_HD int psens_f_pitch(int N) { return NU * (N + 1) * 3; }
+// Adjoint (vector-Jacobian product) of the step's QP (RtiWave::vjp_out), one instance's views.  Upstream: gu0 [4], gX [N+1][10], gU [N][4]
+// (null = 0); outputs: gx0 [10], gxr [N+1][10], gur [N][4], gf [N+1][3] (null = not written).
+struct VjpIo {
+    const double *gu0, *gX, *gU;
+    double *gx0, *gxr, *gur, *gf;
+};
 // *RtiIo::iters = interior-point iterations of the step (low half) + Riccati sweeps its QP_AUTO solves took before them (high half);
 // COND_ACCEPTED in the sweep count (config 5's study): a condensed solve's result was kept
 enum { ITERS_SWEEP_SHIFT = 16, ITERS_IPM_MASK = 0xffff, COND_ACCEPTED = 0x1000 };
@@ -1968,9 +1974,10 @@ struct RtiWave {
     // nothing else.)
     // SENS (rti_sens_kernel): after the step, the sensitivities of its last QP (sens_out) into *sens.  One RTI iteration only.
     // PSENS (rti_psens_kernel): behind them, the parameter sensitivities (psens_out) into *psens.
-    template <bool DEFER, bool IPM_RARE = false, bool SENS = false, bool PSENS = false>
+    // VJP (rti_vjp_kernel): after the step, the adjoint of its last QP contracted with an upstream gradient (vjp_out) into *vjp.
+    template <bool DEFER, bool IPM_RARE = false, bool SENS = false, bool PSENS = false, bool VJP = false>
     static NDP_D bool run(const RtiParams &P, const RtiIo &io, lp lds, InBuf &inb, vd x0v, const SensIo *sens = nullptr,
-                          const PSensIo *psens = nullptr)
+                          const PSensIo *psens = nullptr, const VjpIo *vjp = nullptr)
     {
         const int N = horizon(P);
         const LdsMap m = make_map(N);
@@ -2118,7 +2125,7 @@ struct RtiWave {
                 }
             }
             const int zsrc = done ? m.ZX : m.CX;       // ZX|ZU and CX|CU are laid out alike
-            if constexpr (PSENS) zlast = zsrc;
+            if constexpr (PSENS || VJP) zlast = zsrc;
             if (IPM_RARE ? NDP_RARELY(!done) : !done) {
                 if (DEFER) return true;
                 if (as_on) {                           // the interior-point loop's answer carries no set: the next step starts cold
@@ -2189,6 +2196,9 @@ struct RtiWave {
         }
         if constexpr (PSENS) {
             if (psens) psens_out(P, m, lds, io, A, zlast, status != 0, *psens);
+        }
+        if constexpr (VJP) {
+            if (vjp) vjp_out(P, m, T, lds, io, A, zlast, status != 0, *vjp);
         }
         if (io.f_late) W::late_publish(late_prev, io.late_gsize, io.late_done_word);
         return false;
@@ -2407,6 +2417,126 @@ struct RtiWave {
             }
             if (k >= 1) costate(k);
         }
+    }
+    // ---------------------------------------------------------------- adjoint (vector-Jacobian product)
+    // The step's last QP as psens_out differentiates it (linearisation point, x_0 and final set held fixed; interior point: its last Newton
+    // system), contracted with an upstream gradient gz = (gX, gU) of the new iterate (gu0 adds to gU_0; X_0 = x_0 exactly).  With the set
+    // fixed the QP's solution solves K [z; nu] = [-g; e], so dL/dtheta = [v; mu]' (d[-g; e]/dtheta - dK/dtheta [z; nu]) with the adjoint
+    //     K [v; mu] = [gz; 0]:
+    // v is the same QP with the linear term -gz, no defects, dx_0 = 0 and the pinned inputs held at 0 -- ONE more riccati_sweep over the same
+    // stage and cost blocks (barrier terms and pin weights included) with the gradients and defects replaced; a pinned row gets no
+    // gradient, its pin weight holds it within |B' p| / as_gamma of 0.  The costates are one backward pass over the effective blocks,
+    //     mu_N = gX_N - Q_N v_N,   mu_k = gX_k - Q_k v_k + A_k' mu_{k+1}   (mu_0 = dL/dx_0).
+    // The data derivatives are psens_out's: dL/dxr_k[0..5] = s Qd v_k, dL/dqr_k = -s d/dqr (v_q' E(qr)' W E(qr) q+_k), dL/dur_k = dt Rd v_u,k
+    // (pinned: 0), dL/df_k = (h^2/2 mu_{k+1}[0..2] + h mu_{k+1}[3..5]) / m -- stage 0's reference and f_N are exactly 0.
+    // LDS after the commit: qr and q+ in rows 0..3 / 6..9 of XI (as psens_out), the final set in AS, gX in CX, v in ZX|ZU, mu_{k+1} in ZD (the
+    // sweep's shadow, dead behind it).  A nonzero status (or a failed adjoint factorisation): NaN in every output.
+    static NDP_D void vjp_out(const RtiParams &P, const LdsMap &m, const Tables &T, lp lds, const RtiIo &io, const ActSet &A, int zsrc,
+                              bool bad, const VjpIo &vo)
+    {
+        static_assert(!A_LDS, "the final set is parked in the AS area, which the five-slot kernels use");
+        const int N = horizon(P);
+        const int nxr = (N + 1) * NX, nur = N * NU, nf = (N + 1) * 3;
+        vi lane = W::lane_here();
+        auto nan_out = [&]() {
+            const vd nan = vd(__builtin_nan(""));
+            NDP_KEEP_LOOP
+            for (int t = 0; t * 64 < nxr; ++t) {
+                vi e = lane + 64 * t;
+                if (vo.gxr) W::gst(vo.gxr, e, nan, e < nxr);
+                if (vo.gur) W::gst(vo.gur, e, nan, e < nur);
+                if (vo.gf) W::gst(vo.gf, e, nan, e < nf);
+            }
+            if (vo.gx0) W::gst(vo.gx0, lane, nan, lane < int(NX));
+        };
+        if (bad) { nan_out(); return; }
+        for (int t = 0; t < RUA; ++t) {                        // the final set, 0 / 1 per input bound
+            vi e = a_elem(P, lane, t);
+            W::st(lds, e + m.AS, W::sel(a_get(A, m, lds, t, e) == 0, vd(0.0), vd(1.0)));
+        }
+        NDP_KEEP_LOOP
+        for (int t = 0; t * 64 < 4 * (N + 1); ++t) {           // XI rows 0..3 <- qr_k, rows 6..9 <- q+_k (before the sweep overwrites ZX)
+            vi e = W::imin(lane + 64 * t, 4 * (N + 1) - 1), xo = (e >> 2) * int(NX) + 6 + (e & 3);
+            vd qr = W::gldu(io.xr, xo);
+            vd qp = W::ld(lds, xo + m.XI) + W::ld(lds, xo + zsrc);
+            W::st(lds, xo - 6 + m.XI, qr);
+            W::st(lds, xo + m.XI, qp);
+        }
+        W::sync();
+        // the adjoint's data: state gradients -gX_k, input gradients -gU_k (pinned: 0), no defects, dx_0 = 0
+        NDP_KEEP_LOOP
+        for (int t = 0; t * 64 < nxr; ++t) {
+            vi e = W::imin(lane + 64 * t, nxr - 1);
+            vi k = (e * 6554) >> 16, row = e - k * 10;         // e / 10, e < 16 384
+            vd gx = vo.gX ? W::gldu(vo.gX, e) : vd(0.0);
+            W::st(lds, k * int(CB_STRIDE) + row + (m.CB + int(CB_QE)), -gx);
+            W::st(lds, e + m.CX, gx);
+            W::stp(lds, W::imin(k, vi(N - 1)) * int(MB_STRIDE) + row + (m.MB + int(MB_B)), vd(0.0), k < N);
+        }
+        NDP_KEEP_LOOP
+        for (int t = 0; t * 64 < nur; ++t) {
+            vi e = W::imin(lane + 64 * t, nur - 1);
+            vd gu = vo.gU ? W::gldu(vo.gU, e) : vd(0.0);
+            if (vo.gu0) gu = gu + W::sel(e < int(NU), W::gldu(vo.gu0, W::imin(e, vi(NU - 1))), vd(0.0));
+            const vb pin = !(W::ld(lds, e + m.AS) == 0.0);
+            W::st(lds, (e >> 2) * int(CB_STRIDE) + (e & 3) + (m.CB + int(CB_RE)), W::sel(pin, vd(0.0), vd(0.0) - gu));
+        }
+        W::stp(lds, lane + m.ZX, vd(0.0), lane < int(NX));
+        W::sync();
+        // the interior point's last Newton system may carry barrier terms of 1e10: the sweep it takes then (lam_factor_ldl; its solves
+        // gather through 64 doubles of ZD, N >= 4)
+        bool ok;
+        if (zsrc != m.ZX && 14 * N + 10 >= 64) ok = riccati_sweep<false, true>(P, m, T, lds);
+        else ok = riccati_sweep(P, m, T, lds);
+        if (NDP_RARELY(!ok)) { nan_out(); return; }
+        const int LM = m.ZD;
+        const vi r = W::imin(lane, vi(NX - 1));
+        const vb row = lane < int(NX);
+        const double h = P.dt;
+        W::stp(lds, lane + LM, vd(0.0), row);                  // mu_{N+1} = 0
+        W::sync();
+        NDP_KEEP_LOOP
+        for (int k = N; k >= 0; --k) {
+            const int xk = m.ZX + k * int(NX);
+            const double s = k < N ? h : 1.0;
+            if (vo.gf) {   // f_k, lanes c < 3 (f_N: mu_{N+1} = 0)
+                const vi c = W::imin(lane, vi(2));
+                vd v = (W::ld(lds, c + LM) * (0.5 * h * h) + W::ld(lds, c + (LM + 3)) * h) * P.inv_mass;
+                W::gst(vo.gf, c + 3 * k, v, lane < 3);
+            }
+            if (vo.gxr) {   // xr_k, lanes r < 10: rows 0..5 s Qd_r v_k[r]; rows 6..9 -s d/dqr_r (v_q' E' W E q+) with E = E(qr_k)
+                vd wq[4], v[4], q[4], em[4];
+                for (int a = 0; a < 4; ++a) {
+                    wq[a] = W::ld(lds, vi(xk + 6 + a));
+                    v[a] = W::ld(lds, vi(m.XI + k * int(NX) + 6 + a));
+                    q[a] = W::ld(lds, vi(m.XI + k * int(NX) + a));
+                    em[a] = W::sel(r == 6 + a, vd(1.0), vd(0.0));
+                }
+                vd ew[3], ev[3], mw[3], mv[3];
+                emul(q, wq, ew); emul(q, v, ev); emul(em, wq, mw); emul(em, v, mv);
+                vd att = vd(0.0);
+                for (int a = 0; a < 3; ++a) att = att + (mw[a] * ev[a] + ew[a] * mv[a]) * P.Qd[7 + a];
+                const vd qd = W::ld(lds, r + (m.KC + int(KC_QD)));
+                const vd xv = W::sel(r < 6, W::ld(lds, r + xk) * qd * s, att * -s);
+                W::gst(vo.gxr, r + k * int(NX), xv, row);
+            }
+            if (k < N && vo.gur) {   // ur_k, lanes i < 4: dt Rd_i v_u,k[i], pinned 0
+                const vi i = W::imin(lane, vi(NU - 1));
+                vd u = W::ld(lds, i + (m.ZU + k * int(NU)));
+                u = W::sel(W::ld(lds, i + (m.AS + k * int(NU))) == 0.0, u, vd(0.0));
+                W::gst(vo.gur, i + k * int(NU), u * W::ld(lds, i + (m.KC + int(KC_RD))) * h, lane < int(NU));
+            }
+            {   // mu_k = gX_k - Q_k v_k + A_k' mu_{k+1}, lanes r < 10
+                vd l = W::ld(lds, r + (m.CX + k * int(NX)));
+                for (int j = 0; j < NX; ++j) l = l - W::ld(lds, c_entry(m, r, vi(j)) + cb(k)) * W::ld(lds, vi(xk + j));
+                if (k < N)
+                    for (int j = 0; j < NX; ++j) l = l + W::ld(lds, m_entry(m, vi(j), r) + mb(k)) * W::ld(lds, vi(LM + j));
+                W::sync();
+                W::stp(lds, r + LM, l, row);
+                W::sync();
+            }
+        }
+        if (vo.gx0) W::gst(vo.gx0, r, W::ld(lds, r + LM), row);
     }
     // E(q) w (build_cost's E of the attitude residual, linear in q)
     static NDP_D void emul(const vd q[4], const vd w[4], vd o[3])
