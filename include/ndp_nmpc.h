@@ -339,6 +339,33 @@ int ndp_step_vjp_device(ndp_handle *h, const void *d_x0, const void *d_xr, const
                         const void *d_gu0, const void *d_gX, const void *d_gU,
                         void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_u0_check, void *d_status_check, void *stream);
 
+/* Adjoint of DownwashNN.update + the r_horiz gate (downwash_nn.py:21-29, ndp_nmpc_leader_node.py:60-76) as ndp_step_device_ex
+ * evaluates them: the vector-Jacobian product of the 6-128-64-128-3 network (nn_net.py:7-18) with d_gf [B][N+1][3] fp64
+ * (ndp_step_vjp_device's d_gf as it lies; rounded to fp32).  d_other / other_stride (6 or 10) / d_other_index (int32 [B], < 0 = no
+ * neighbour, NULL = row i) / d_ego_ref [B][N+1][10] / d_ego_xy ([B][2], NULL = gate open) as the step that produced the force took them.
+ * The forward is recomputed with the step's own arithmetic, so the ReLU masks are those of the force the step used; the capped ReLU's
+ * upper branch has derivative 0 like the lower one.  Outputs, each NULL = not computed, not both NULL:
+ *   d_gz [B][N+1][6] fp64 : dL/d((other - ego_ref)[:, 0:6]) per row, 0 on closed / neighbour-less instances (the gate is
+ *                            piecewise constant: its own derivative is 0 and is not represented)
+ *   d_gw [NDP_MLP_NPARAM] fp32, blob order of ndp_set_mlp_weights, OVERWRITTEN (the caller accumulates).
+ * A row whose d_gf is not finite (an instance whose step failed) contributes 0 to d_gw and gets NaN in its own d_gz row.
+ * Products are exact fp32; the weight gradient is summed per workgroup and then in a fixed order (no atomics): two calls with the same
+ * inputs are bit-identical.  Nothing of the engine's state is written.  The partial sums live in one workspace of the handle (allocated
+ * by ndp_create, so the call may be captured into a graph): calls on one handle must be ordered against each other -- the same stream, or
+ * streams ordered by events; two in flight at once would share the workspace.  -6: weights never set; -2 with a reason in ndp_last_error:
+ * other_stride not 6 or 10, d_gf NULL, no output asked for. */
+int ndp_downwash_vjp_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index,
+                            const void *d_ego_ref, const void *d_ego_xy, const void *d_gf,
+                            void *d_gz, void *d_gw, void *stream);
+/* ndp_set_mlp_weights from device memory (d_blob: NDP_MLP_NPARAM fp32, the same order), enqueued on `stream`, no host synchronisation:
+ * a training loop's update.  The device builds the same bytes as the host form. */
+int ndp_set_mlp_weights_device(ndp_handle *h, const void *d_blob, void *stream);
+/* Test hook: host copies of the network's two device images, taken after a device synchronisation.
+ *   frag_out  18432 32-bit words: the forward's fragment blob (fp32 values, then fp16 pairs -- compare it as words, not as floats)
+ *   fragt_out 16384 floats: layers 2 and 3 transposed, the backward's records
+ * Either may be NULL (skipped).  Returns -1 for a NULL handle. */
+int ndp_debug_mlp_fragments(ndp_handle *h, void *frag_out, float *fragt_out);
+
 /* Per-kernel timing with HIP events recorded on the stream each kernel is launched on:
  * on = n > 0 brackets every n-th launch of each kernel (n = 1: every launch), on = 0 stops and clears.
  * ndp_timing_read: name is "rti" or "mlp"; total over the bracketed launches.  Returns <0 if nothing was timed. */

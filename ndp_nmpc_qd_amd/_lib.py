@@ -56,6 +56,7 @@ EXPORTS = [
     "ndp_sens_enable", "ndp_sens_level", "ndp_get_sens", "ndp_device_sens_u0", "ndp_device_sens_u", "ndp_device_sens_x",
     "ndp_sens_params_enable", "ndp_sens_params_enabled", "ndp_get_sens_params", "ndp_device_sens_xr", "ndp_device_sens_ur", "ndp_device_sens_f",
     "ndp_debug_rti_launched", "ndp_device_active_set", "ndp_step_vjp_device",
+    "ndp_downwash_vjp_device", "ndp_set_mlp_weights_device", "ndp_debug_mlp_fragments",
 ]
 
 _lib = None
@@ -139,6 +140,9 @@ def load():
     lib.ndp_device_active_set.argtypes = [vp]
     lib.ndp_device_active_set.restype = vp
     lib.ndp_step_vjp_device.argtypes = [vp] * 18
+    lib.ndp_downwash_vjp_device.argtypes = [vp, vp, C.c_int] + [vp] * 7
+    lib.ndp_set_mlp_weights_device.argtypes = [vp] * 3
+    lib.ndp_debug_mlp_fragments.argtypes = [vp] * 3
     lib.ndp_debug_host_info.argtypes = [vp, vp]
     lib.ndp_debug_rti_launched.argtypes = [vp, C.POINTER(C.c_uint64), vp]
     lib.ndp_ref_list_reset.argtypes = [vp]

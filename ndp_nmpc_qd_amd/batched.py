@@ -62,6 +62,7 @@ class BatchedNMPC:
     def set_mlp_weights(self, blob):
         blob = np.ascontiguousarray(blob, dtype=np.float32)
         self._check(self._lib.ndp_set_mlp_weights(self._h, _lib.ptr(blob), blob.size), "ndp_set_mlp_weights")
+        self._mlp_installed = None          # (torch_layer: whatever tensor was installed through set_mlp_weights_device no longer is)
 
     # ------------------------------------------------------------------ reference-shaped API (host arrays)
     def reset(self, xr, ur):
@@ -543,6 +544,56 @@ class BatchedNMPC:
             d(gU, torch.float64, (B, N, 4)), d(gx0, torch.float64, (B, 10)), d(gxr, torch.float64, (B, N + 1, 10)),
             d(gur, torch.float64, (B, N, 4)), d(gf, torch.float64, (B, N + 1, 3)), d(u0_check, torch.float64, (B, 4)),
             d(status_check, torch.int32, (B,)), self._stream(stream)), "ndp_step_vjp_device")
+
+    # ------------------------------------------------------------------ backward pass of the downwash network
+    def _other_ptr(self, other, other_index):
+        """(pointer, doubles per node) of neighbour windows [rows, N+1, 6 or 10] (rows = B without other_index)."""
+        import torch
+        if hasattr(other, "dev_ptr"):
+            return C.c_void_p(int(other.dev_ptr)), int(other.shape[2])
+        if not (isinstance(other, torch.Tensor) and other.is_cuda and other.is_contiguous() and other.dtype == torch.float64
+                and other.dim() == 3 and other.shape[1] == self.N + 1 and other.shape[2] in (6, 10)
+                and (other_index is not None or other.shape[0] == self.B)):
+            raise ValueError("other: expected a contiguous CUDA float64 [rows, N+1, 6 or 10] tensor")
+        return C.c_void_p(other.data_ptr()), int(other.shape[2])
+
+    def downwash_vjp_device(self, other, ego_ref, gf, ego_xy=None, other_index=None, gz=None, gw=None, stream=None):
+        """Enqueues the backward pass of the downwash network and its gate on `stream` (ndp_downwash_vjp_device; include/ndp_nmpc.h):
+        other / other_index / ego_ref (= the step's xr) / ego_xy as the step that produced the force took them, gf [B,N+1,3] float64 the
+        gradient of that force (step_vjp_device's gf as it lies).  Outputs (CUDA tensors the caller allocates, None = not computed, not
+        both None): gz [B,N+1,6] float64 = dL/d(other - ego_ref)[..., 0:6], exactly 0 on closed and neighbour-less instances; gw [17859]
+        float32 in blob order, overwritten.  A row whose gf is not finite (an instance whose step failed) adds nothing to gw and has NaN
+        in its own gz row.  This is the exact derivative of the fp32 network the step ran, with the gate held fixed.  Two calls with the
+        same inputs give bit-identical results; the engine's state is not written.  stream None or torch's default stream: the call goes
+        on the engine's own stream behind a wait for torch's (read the outputs after engine.synchronize())."""
+        import torch
+        B, N = self.B, self.N
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        optr, stride = self._other_ptr(other, other_index)
+        d = self._dptr
+        self._check(self._lib.ndp_downwash_vjp_device(
+            self._h, optr, stride, d(other_index, torch.int32, (B,)), d(ego_ref, torch.float64, (B, N + 1, 10)),
+            d(ego_xy, torch.float64, (B, 2)), d(gf, torch.float64, (B, N + 1, 3)), d(gz, torch.float64, (B, N + 1, 6)),
+            d(gw, torch.float32, (_lib.MLP_NPARAM,)), self._stream(stream)), "ndp_downwash_vjp_device")
+
+    def set_mlp_weights_device(self, blob, stream=None):
+        """set_mlp_weights from a float32 CUDA tensor of 17859 values in blob order, enqueued on `stream` with no host synchronisation
+        (ndp_set_mlp_weights_device): steps enqueued behind it on that stream use the new weights."""
+        import torch
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        self._check(self._lib.ndp_set_mlp_weights_device(self._h, self._dptr(blob, torch.float32, (_lib.MLP_NPARAM,)), self._stream(stream)),
+                    "ndp_set_mlp_weights_device")
+        self._mlp_installed = None          # (torch_layer._install_weights notes what IT installed, behind this call)
+
+    def debug_mlp_fragments(self):
+        """(frag, frag_t): host copies of the network's two device images as uint32 / float32 arrays (ndp_debug_mlp_fragments)."""
+        from . import mlp_frag
+        fr = np.zeros(mlp_frag.FR_TOTAL, dtype=np.uint32)
+        frt = np.zeros(mlp_frag.FRT_TOTAL, dtype=np.float32)
+        self._check(self._lib.ndp_debug_mlp_fragments(self._h, _lib.ptr(fr), _lib.ptr(frt)), "ndp_debug_mlp_fragments")
+        return fr, frt
 
     def device_iterate(self):
         """The engine's iterate as CUDA tensor views (no copy): (X [B,N+1,10], U [B,N,4]) float64 (ndp_device_iterate_x / _u); valid once

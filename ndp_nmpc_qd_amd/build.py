@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libndp_nmpc_hip.so")
 # the translation units (csrc/host.hpp: which one owns what); ndp_hip.hip first, it is by far the longest compile
-UNITS = ["ndp_hip.hip", "exchange.hip"]
+UNITS = ["ndp_hip.hip", "exchange.hip", "mlp_vjp.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))) + [os.path.join("..", "..", "include", "ndp_nmpc.h")]   # every header a unit can include
 # -amdgpu-mfma-vgpr-form: MFMA results go straight to VGPRs.  With the default AGPR form every accumulator that is
 # live across a basic block or feeds VALU/LDS is copied through v_accvgpr_read/write behind full-latency s_nops,

@@ -1,6 +1,7 @@
 // host.hpp -- the private host interface of the library's translation units: the handle, the entry-point frame and the host functions
 // one unit calls in another.
 //   ndp_hip.hip   the kernels but the exchange's, the handle's runtime, the steps, the rows (f1 - f4), the tick, the sensitivities
+//   mlp_vjp.hip   the downwash network's backward pass (ndp_downwash_vjp_device) and its weights set from device memory
 //   exchange.hip  peer-mapped windows (ndp_peer_*), the RCCL exchange (ndp_xchg_*) and the remote tick one control period ahead
 // The functions declared below are NDP_HIDDEN: the library exports the C-ABI of include/ndp_nmpc.h and nothing more.
 #pragma once
@@ -52,6 +53,9 @@ struct ndp_handle {
     double *dVjp = nullptr;
     int *dVjpSt = nullptr;
     signed char *dVjpAct = nullptr;
+    // mlp_vjp.hip: layers 2 and 3 transposed, one fp32 record per matrix instruction of the backward pass (FRT_TOTAL floats, written with
+    // dFrag by both ndp_set_mlp_weights forms); ndp_downwash_vjp_device's per-workgroup partial weight gradients [mlp_vjp_groups][NDP_MLP_NPARAM]
+    float *dFragT = nullptr, *dGwPart = nullptr;
     double *dThr = nullptr;    // hover-throttle estimator state, SoA [8][B]
     double *dStamps = nullptr; // [B][NDP_NSTAMP] whole-batch phase stamps (ndp_debug_stamps)
     double *dTraj = nullptr;   // f1: the trajectories and the tick's caches (layout: TrajView)
@@ -137,6 +141,16 @@ struct ndp_handle {
 
 static inline RingGeom ring_geom(const ndp_handle *h) { return RingGeom{h->list_step, h->cfg.N + 1}; }
 
+enum { FRT_TOTAL = 2 * 128 * 64 };   // floats of dFragT: 128 records of 64 lanes per layer (mlp_vjp.hip: fragt_source)
+// workgroups of mlp_vjp_kernel = rows of dGwPart: one per 128 rows (four 32-row tiles), at most 256 (then a grid-stride loop) -- a function
+// of the batch shape only
+enum { VJ_MAX_GROUPS = 256 };
+static inline int mlp_vjp_groups(const ndp_handle *h)
+{
+    const int ntiles = (h->cfg.batch * (h->cfg.N + 1) + 31) / 32, ngroups = (ntiles + 3) / 4;
+    return ngroups < VJ_MAX_GROUPS ? ngroups : VJ_MAX_GROUPS;
+}
+
 enum { TICK_ESTIMATE = NDP_TICK_ESTIMATE, TICK_WANT_U0 = NDP_TICK_WANT_U0, TICK_T_UNIFORM = NDP_TICK_T_UNIFORM };
 
 // ---- host functions one unit calls in another (no locking, no sync: the caller holds h->mu).  C linkage like the entry points they
@@ -150,6 +164,9 @@ NDP_HIDDEN int ensure_tick(ndp_handle *h);
 NDP_HIDDEN void launch_tick_pre(const TickPre &a, hipStream_t s);
 NDP_HIDDEN int tick_step_enqueue(ndp_handle *h, hipStream_t s, const double *x_odom, double *cmd, double *u0, const double *windows,
                                  unsigned long long pos);
+// mlp_vjp.hip
+NDP_HIDDEN void make_fragments_t(const float *blob, float *frt);
+NDP_HIDDEN hipError_t mlp_vjp_prepare(void);
 // exchange.hip
 NDP_HIDDEN int peer_mapped(const void *p);
 NDP_HIDDEN void launch_pack_pv_list(const double *base, size_t pitch, int np1, double *pv, size_t B, hipStream_t s);

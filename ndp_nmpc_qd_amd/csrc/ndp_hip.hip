@@ -37,22 +37,9 @@
 #include "cfg_params.hpp"
 #include "cond_qp.hpp"
 #include "host.hpp"
+#include "mlp_common.hpp"
 
 namespace ndp {
-
-// Individually rounded multiply / add.  hipcc contracts a*b+c into an FMA by default, and HIP's __dmul_rn/__dadd_rn
-// are plain operators that get re-fused; the reference evaluates the gate, the Kalman filter and the alpha filter
-// in Python/numpy doubles without fusion, so these few expressions are built from non-contractable operations.
-__device__ __forceinline__ double nc_mul(double a, double b)
-{
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ double nc_add(double a, double b)
-{
-#pragma clang fp contract(off)
-    return a + b;
-}
 
 // ------------------------------------------------------------------------------------------ RTI kernel
 struct BatchPtrs {
@@ -91,26 +78,6 @@ struct MlpArgs {            // fused downwash (null frag = not fused)
     size_t other_pitch;     // doubles from one row of `other` to the next: (N+1) other_stride when dense; RingGeom::px for windows in the list
     size_t ego_pitch;       // doubles from one instance's ego xy to the next: 2 ([B][2]), or 10 when the gate reads the odometry rows x0[B][10]
 };
-
-// Neighbour windows that live in ANOTHER agent's memory (peer windows over xGMI) are read with system-scope loads: such lines are
-// not kept coherent in this GPU's L2s, and what a kernel boundary invalidates depends on the fence scope the runtime put on the
-// dispatch packet (agent scope between back-to-back launches of one queue).  A system-scope load always fetches from the owner's
-// memory -- two 8-byte loads per lane and launch instead of one 16-byte load, nothing else changes.  Local windows: plain loads.
-typedef double ndp_d2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double ld_other(const double *p, int sys)
-{
-    return sys ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : *p;
-}
-__device__ __forceinline__ ndp_d2 ld_other2(const double *p, int sys)
-{
-    if (sys) {
-        ndp_d2 r;
-        r[0] = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        r[1] = __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        return r;
-    }
-    return *(const ndp_d2 *)p;
-}
 
 // Work list of instances whose QP needs the interior-point loop (batches with more instances than SIMDs).  An
 // interior-point solve costs ~18 Riccati sweeps against 1 for the early exit, so with several instances per SIMD one such
@@ -426,8 +393,6 @@ __global__ void queue_reset_kernel(unsigned *count, unsigned long long *ipm_tota
 // register r, which is exactly the B-operand shape of the next layer's 32x32x2 step when that step
 // contracts the feature pair {f0(r), f0(r)+4}.  The weights are pre-permuted on the host into that
 // "fragment order" (one 64-float record per MFMA), so A operands are coalesced 256-byte loads.
-typedef float f16_t __attribute__((ext_vector_type(16)));
-
 // Fragment blob (built on the host by make_fragments, parked in LDS during the MLP phase), in float units:
 //   FR_L1  12 x 64 f32     layer-1 A operands for v_mfma_f32_32x32x2_f32 (K = 6 inputs)
 //   FR_B1/B2/B3, FR_W4 ([128 features][4]: w0 w1 w2 0), FR_B4
@@ -439,8 +404,8 @@ enum { FR_L1 = 0, FR_B1 = FR_L1 + 12 * 64, FR_B2 = FR_B1 + 128, FR_B3 = FR_B2 + 
        // (a multiple of 8 pieces: every wave of a 1- / 2- / 4- / 8-wave workgroup moves the SAME number of them -- see stage_fragments)
        FR_CHUNKS = (FR_USED + 2047) / 2048 * 8, FR_TOTAL = FR_CHUNKS * 256 };
 static_assert(FR_HF % 4 == 0 && FR_W4 % 4 == 0, "16-byte alignment of the LDS image");
-
-__device__ __forceinline__ int f0(int r) { return (r & 3) + 8 * (r >> 2); }
+static_assert(FR_L1 == frag::L1 && FR_B1 == frag::B1 && FR_B2 == frag::B2 && FR_B3 == frag::B3 && FR_W4 == frag::W4 && FR_B4 == frag::B4 &&
+              FR_HF == frag::HF && FR_REC == frag::REC && FR_TOTAL == frag::TOTAL, "mlp_common.hpp: frag:: restates this enum for mlp_vjp.hip");
 
 // The four layers for one 32-row tile held by one wave.  zb[s] = input feature 2s + (lane>>5) of row lane&31;
 // returns the three outputs of row lane&31 in o[] (both half-waves hold the full sums).
@@ -467,45 +432,6 @@ __device__ __forceinline__ void stage_fragments(const float *__restrict__ fr, ld
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(fr + c * 256 + lane * 4),
                                              (__attribute__((address_space(3))) void *)(dst + c * 256), 16, 0, 0);
     }
-}
-
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-struct Split2 { h16x8 hi, lo; };
-#define NDP_LO_SCALE 2048.0f            // 2^11: the low parts are carried scaled so that they stay fp16-normal
-#define NDP_LO_INV (1.0f / 2048.0f)
-#define NDP_H16_CAP 65000.0f            // activations are capped below the fp16 overflow threshold (see split2)
-
-// x = hi + lo / 2^11 with two fp16 terms (11 + 11 significand bits; fp32 has 24): hi = fp16(x), the residual
-// x - hi is exact in fp32 and lo = fp16(residual * 2^11).  Relative error of the pair 2^-22.
-__device__ __forceinline__ void split2(const f16_t &v, int s, Split2 &o)
-{
-    typedef float f2_t __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {            // two registers at a time: packed f32 subtract / multiply, packed conversions
-        const f2_t x = {v[8 * s + j], v[8 * s + j + 1]};
-        const h2_t hh = __builtin_convertvector(x, h2_t);
-        const f2_t r = (x - __builtin_convertvector(hh, f2_t)) * NDP_LO_SCALE;
-        const h2_t ll = __builtin_convertvector(r, h2_t);
-        o.hi[j] = hh[0]; o.hi[j + 1] = hh[1];
-        o.lo[j] = ll[0]; o.lo[j + 1] = ll[1];
-    }
-}
-
-// ReLU of a hidden layer that feeds an fp16 split, capped at NDP_H16_CAP: one v_med3_f32, the price of a plain
-// v_max_f32.  The cap only acts on inputs ~1000x outside the training envelope, where the reference returns a finite
-// meaningless force; uncapped, the fp16 conversion would overflow to inf and turn that into NaN.
-__device__ __forceinline__ float relu_cap(float x) { return __builtin_amdgcn_fmed3f(x, 0.0f, NDP_H16_CAP); }
-
-// one (output tile, 16-deep k-step): W x = W_hi x_hi + (W_hi x_lo + W_lo x_hi) / 2^11; the dropped W_lo x_lo term is
-// below 2^-22 of the result.  Three v_mfma_f32_32x32x16_f16 (products exact in the fp32 accumulators), the cross terms
-// in their own accumulator.  16x the f32 MFMA rate per instruction, so the three still run 5x faster than the exact
-// f32 form; measured error on the reference fixture 3.7e-6 (bar 1e-5).
-__device__ __forceinline__ void mm3(const Split2 &w, const Split2 &x, f16_t &acc_hi, f16_t &acc_lo)
-{
-    acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(w.lo, x.hi, acc_lo, 0, 0, 0);
-    acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(w.hi, x.lo, acc_lo, 0, 0, 0);
-    acc_hi = __builtin_amdgcn_mfma_f32_32x32x16_f16(w.hi, x.hi, acc_hi, 0, 0, 0);
 }
 
 __device__ __forceinline__ void load_w(lds_cf32 fr, int rec, int lane, Split2 &w)
@@ -604,15 +530,6 @@ __device__ __forceinline__ void mlp_tile(lds_cf32 fr, const float zb[3], int lan
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[c] = o[c] + __shfl_xor(o[c], 32, 64) + fr[FR_B4 + c];
-}
-
-// gate of ndp_nmpc_leader_node.py:65-68: other.x[0] xy against ego ODOMETRY xy, strict '<'.  Individually rounded
-// mul/add (nc_mul / nc_add): the reference evaluates this in Python doubles and must agree at the rim.
-__device__ __forceinline__ bool gate_open(const double *other_inst, const double *ego_xy_inst, double r2)
-{
-    const double dx = other_inst[0] - ego_xy_inst[0];
-    const double dy = other_inst[1] - ego_xy_inst[1];
-    return nc_add(nc_mul(dx, dx), nc_mul(dy, dy)) < r2;
 }
 
 // Standalone form (DownwashNN.update for arbitrary row counts): one 32-row tile per wave, no tile loop --
@@ -2004,7 +1921,7 @@ int ndp_destroy(ndp_handle *h)
     h->pool.reset();
     void *ptrs[] = {h->dForceAB[0], h->dForceAB[1], h->dProto, h->dRingX, h->dTraj, h->dTables, h->dStamps, h->dRelay, h->dThr, h->sThr, h->dKC, h->dForce, h->dFrag,
                     h->dIn, h->dOut, h->sdbg, h->dQctr, h->dQids, h->dTickIndex, h->dTickThrust, h->dAct,
-                    h->dSensU0, h->dSensU, h->dSensX, h->dPSensXr, h->dPSensUr, h->dPSensF, h->dVjp, h->dVjpSt, h->dVjpAct};
+                    h->dSensU0, h->dSensU, h->dSensX, h->dPSensXr, h->dPSensUr, h->dPSensF, h->dVjp, h->dVjpSt, h->dVjpAct, h->dFragT, h->dGwPart};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &sl : h->slot) {
@@ -2114,7 +2031,7 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
     const size_t B = cfg->batch;
 #define ALLOC(p, n)                                                                      \
     if ((e = hipMalloc((void **)&(p), (n))) != hipSuccess) return fail("hipMalloc " #p, e)
-    ALLOC(h->dForce, nfs(h) * 4); ALLOC(h->dFrag, FR_TOTAL * 4); ALLOC(h->dKC, KC_HOST * 8);
+    ALLOC(h->dForce, nfs(h) * 4); ALLOC(h->dFrag, FR_TOTAL * 4); ALLOC(h->dFragT, FRT_TOTAL * 4); ALLOC(h->dGwPart, (size_t)mlp_vjp_groups(h) * NDP_MLP_NPARAM * 4); ALLOC(h->dKC, KC_HOST * 8);
     ALLOC(h->dThr, B * 8 * 8); ALLOC(h->sThr, B * 11 * 8);
     ALLOC(h->dRelay, B * 4 * 8);
     ALLOC(h->dQctr, 256); ALLOC(h->dQids, B * 4);
@@ -2169,6 +2086,7 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
     if ((e = hipFuncSetAttribute((const void *)mlp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)(FR_TOTAL * sizeof(float)))) != hipSuccess)
         return fail("hipFuncSetAttribute(mlp_kernel)", e);
+    if ((e = mlp_vjp_prepare()) != hipSuccess) return fail("hipFuncSetAttribute(mlp_vjp_kernel)", e);
     for (const RtiKern &k : k_rti)      // (the sensitivity kernels: ndp_sens_enable)
         if (!k.sens && (e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) != hipSuccess)
             return fail("hipFuncSetAttribute", e);
@@ -2189,7 +2107,10 @@ int ndp_set_mlp_weights(ndp_handle *h, const float *blob, size_t n)
     NDP_HIP(h, hipSetDevice(h->cfg.device));
     std::vector<float> fr;
     make_fragments(blob, fr);
+    std::vector<float> frt(FRT_TOTAL);
+    make_fragments_t(blob, frt.data());          // the backward pass's records (mlp_vjp.hip)
     NDP_HIP(h, hipMemcpyAsync(h->dFrag, fr.data(), FR_TOTAL * 4, hipMemcpyHostToDevice, h->stream));
+    NDP_HIP(h, hipMemcpyAsync(h->dFragT, frt.data(), FRT_TOTAL * 4, hipMemcpyHostToDevice, h->stream));
     NDP_HIP(h, hipStreamSynchronize(h->stream));
     h->have_mlp = true;
     return 0;

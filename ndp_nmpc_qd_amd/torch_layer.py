@@ -17,6 +17,9 @@ control_step_trajectory (ControlStepTrajectoryFunction) returns the whole new it
 and differentiates all three by the adjoint (reverse mode): the forward step records a small tape (the iterate and kept sets it started
 from, BatchedNMPC.record_tape) and runs unchanged; the backward recomputes the step from the tape and solves one adjoint system of its QP
 with the upstream gradients (BatchedNMPC.step_vjp_device).  Same derivative as above; no sensitivities need to be on.
+
+downwash / control_step_ndp / NDPControlStep (at the end of this file) continue that adjoint through the downwash network: gradients of the
+neighbour windows and of the network's weights (BatchedNMPC.downwash_vjp_device).  The entry points above keep refusing other / ego_xy.
 """
 import torch
 
@@ -155,3 +158,208 @@ class ControlStep(torch.nn.Module):
         if self.backward == "adjoint":
             return control_step_trajectory(self.engine, x0, xr, ur, f=f, other=other, ego_xy=ego_xy)[0]
         return control_step(self.engine, x0, xr, ur, f=f, other=other, ego_xy=ego_xy)
+
+
+# ---------------------------------------------------------------------------------------------- the downwash network, differentiated
+# What is differentiated: the fp32 network the step ran (its own ReLU masks) with respect to its input rows (other - ego_ref)[..., 0:6] and its
+# 17 859 weights (BatchedNMPC.downwash_vjp_device).  What is held fixed: the r_horiz gate (piecewise constant: ego_xy may not require grad)
+# and, in control_step_ndp, everything the step's adjoint holds fixed -- linearisation point and active set.
+
+def _cuda_stream(t):
+    """(stream, is torch's default stream) for a tensor's device; (None, False) for CPU tensors (stub engines in the tests)."""
+    if not t.is_cuda:
+        return None, False
+    s = torch.cuda.current_stream(t.device)
+    return s, s.cuda_stream == 0
+
+
+def _install_weights(engine, weights, stream):
+    """Installs `weights` (float32 CUDA tensor / nn.Parameter of 17 859 in blob order) as the engine's network unless they are the ones
+    installed last (same storage, same version counter).  Returns the key that identifies what is installed.  The engine keeps a
+    reference to the installed tensor, so its storage cannot be freed and handed to another tensor that would then pass for it; any other
+    way of setting the engine's weights (set_mlp_weights, set_mlp_weights_device) forgets the key."""
+    if weights is None:
+        return None
+    key = (weights.data_ptr(), weights._version)
+    if getattr(engine, "_mlp_installed", None) != key:
+        engine.set_mlp_weights_device(weights.detach(), stream=stream)
+        engine._mlp_installed, engine._mlp_installed_tensor = key, weights
+    return key
+
+
+def _check_installed(engine, key, who):
+    if key is not None and getattr(engine, "_mlp_installed", None) != key:
+        raise RuntimeError(f"{who}: the engine's network weights were replaced between this forward and its backward (the backward "
+                           "recomputes the forward from the installed weights): run the backward before the next forward with other weights")
+
+
+def _scatter_gz(gz, other, other_index):
+    """dL/d other from g_z [B,N+1,6]: columns 0..5, the rest 0; with other_index, instances that share a neighbour row add up."""
+    g = torch.zeros_like(other)
+    if other_index is None:
+        g[:, :, :6] = gz
+    else:
+        has = other_index >= 0
+        g[:, :, :6].index_add_(0, other_index[has].long(), gz[has])
+    return g
+
+
+def _minus_gz(gz, like):
+    g = torch.zeros_like(like)
+    g[:, :, :6] = -gz
+    return g
+
+
+class DownwashFunction(torch.autograd.Function):
+    """forward(other, engine, ego_ref, ego_xy, weights, other_index) -> f [B,N+1,3] float32, the gated downwash force (mlp_kernel);
+    backward: BatchedNMPC.downwash_vjp_device for the gradients of other, ego_ref and weights."""
+
+    @staticmethod
+    def forward(ctx, other, engine, ego_ref, ego_xy=None, weights=None, other_index=None):
+        if isinstance(ego_xy, torch.Tensor) and ego_xy.requires_grad:
+            raise ValueError("DownwashFunction: ego_xy requires grad, but the r_horiz gate is piecewise constant and is not differentiated "
+                             "(detach it)")
+        od, ed = other.detach().contiguous(), ego_ref.detach().contiguous()
+        stream, default = _cuda_stream(od)
+        if default:
+            stream.synchronize()
+        ctx.key = _install_weights(engine, weights, stream)
+        B, np1 = ed.shape[0], ed.shape[1]
+        dense = od
+        if other_index is not None or od.shape[2] != 10:      # the stand-alone forward takes dense [B,N+1,10] windows: gather (plumbing)
+            rows = od if other_index is None else od[other_index.clamp(min=0).long()]
+            dense = torch.zeros((B, np1, 10), dtype=od.dtype, device=od.device)
+            dense[:, :, :od.shape[2]] = rows
+        f = torch.empty((B, np1, 3), dtype=torch.float32, device=od.device)
+        engine.downwash_device(dense, ed, f, ego_xy=ego_xy, stream=stream)
+        if default:
+            engine.synchronize()
+        if other_index is not None:
+            f[other_index < 0] = 0.0                          # no neighbour: no force
+        ctx.engine = engine
+        ctx.have_w = weights is not None
+        ctx.save_for_backward(od, ed, *(t for t in (ego_xy, other_index, weights) if t is not None))
+        ctx.opt = (ego_xy is not None, other_index is not None)
+        return f
+
+    @staticmethod
+    def backward(ctx, g_f):
+        od, ed, *rest = ctx.saved_tensors
+        ego_xy = rest.pop(0) if ctx.opt[0] else None
+        other_index = rest.pop(0) if ctx.opt[1] else None
+        eng = ctx.engine
+        _check_installed(eng, ctx.key, "DownwashFunction")
+        need = ctx.needs_input_grad
+        gf = g_f.to(torch.float64).contiguous()
+        B, np1 = ed.shape[0], ed.shape[1]
+        gz = torch.empty((B, np1, 6), dtype=torch.float64, device=od.device) if need[0] or need[2] else None
+        gw = torch.empty(17859, dtype=torch.float32, device=od.device) if ctx.have_w and need[4] else None
+        if gz is None and gw is None:
+            return (None,) * 6
+        stream, default = _cuda_stream(od)
+        eng.downwash_vjp_device(od, ed, gf, ego_xy=ego_xy, other_index=other_index, gz=gz, gw=gw, stream=stream)
+        if default:
+            eng.synchronize()
+        return (_scatter_gz(gz, od, other_index) if need[0] else None, None, _minus_gz(gz, ed) if need[2] else None, None, gw, None)
+
+
+def downwash(engine, other, ego_ref, ego_xy=None, weights=None, other_index=None):
+    """f [B,N+1,3] float32 = the engine's gated downwash network on (other - ego_ref)[..., 0:6], differentiable in `other` (columns 0..5;
+    columns 6..9 get 0; with other_index [B] int32 the instances that share a neighbour row add up), `ego_ref` (the negative of the same
+    on columns 0..5) and `weights` (a float32 CUDA tensor / nn.Parameter of 17 859 in blob order; when given, the forward first installs
+    it in the engine unless it is what was installed last).  The gate is held fixed: ego_xy requiring grad raises.  A row whose upstream
+    gradient is not finite adds nothing to the weights' gradient and has NaN in its own input gradient."""
+    return DownwashFunction.apply(other, engine, ego_ref, ego_xy, weights, other_index)
+
+
+class ControlStepNDPFunction(torch.autograd.Function):
+    """forward(x0, engine, xr, ur, other, ego_xy, weights, other_index) -> (u0, X, U) float64: the fused control step (one launch);
+    backward: the step's adjoint (step_vjp_device) for x0, xr, ur and the force's gradient gf, then the network's backward pass on that gf
+    (downwash_vjp_device) for other, weights and xr's share (- g_z on columns 0..5)."""
+
+    @staticmethod
+    def forward(ctx, x0, engine, xr, ur, other, ego_xy=None, weights=None, other_index=None):
+        if isinstance(ego_xy, torch.Tensor) and ego_xy.requires_grad:
+            raise ValueError("ControlStepNDPFunction: ego_xy requires grad, but the r_horiz gate is piecewise constant and is not "
+                             "differentiated (detach it)")
+        det = lambda t: t.detach().contiguous()  # noqa: E731
+        x0, xr, ur, od = det(x0), det(xr), det(ur), det(other)
+        stream, default = _cuda_stream(x0)
+        if default:
+            stream.synchronize()
+        ctx.key = _install_weights(engine, weights, stream)
+        tape = engine.record_tape(stream)
+        u0 = torch.empty((x0.shape[0], 4), dtype=x0.dtype, device=x0.device)
+        engine.update_device(x0, xr, ur, u0, other=od, ego_xy=ego_xy, stream=stream, other_index=other_index)
+        if default:
+            engine.synchronize()
+        X, U = (t.clone() for t in engine.device_iterate())
+        force = engine.device_force().clone()
+        ctx.engine = engine
+        ctx.have_w = weights is not None
+        ctx.opt = (ego_xy is not None, other_index is not None)
+        ctx.save_for_backward(x0, xr, ur, od, force, *tape, *(t for t in (ego_xy, other_index, weights) if t is not None))
+        return u0, X, U
+
+    @staticmethod
+    def backward(ctx, g_u0, g_X, g_U):
+        x0, xr, ur, od, force, t0, t1, t2, *rest = ctx.saved_tensors
+        ego_xy = rest.pop(0) if ctx.opt[0] else None
+        other_index = rest.pop(0) if ctx.opt[1] else None
+        eng = ctx.engine
+        if g_u0 is None and g_X is None and g_U is None:
+            return (None,) * 8
+        _check_installed(eng, ctx.key, "ControlStepNDPFunction")
+        c = lambda g: None if g is None else g.to(torch.float64).contiguous()  # noqa: E731
+        z = lambda *s: torch.empty(*s, dtype=torch.float64, device=x0.device)  # noqa: E731
+        B, N = x0.shape[0], xr.shape[1] - 1
+        need = ctx.needs_input_grad
+        net_w = ctx.have_w and need[6]
+        net = need[2] or need[4] or net_w                    # anything behind the force
+        gx0 = z(B, 10) if need[0] else None
+        gxr = z(B, N + 1, 10) if need[2] else None
+        gur = z(B, N, 4) if need[3] else None
+        gf = z(B, N + 1, 3) if net else None
+        stream, default = _cuda_stream(x0)
+        eng.step_vjp_device(x0, xr, ur, (t0, t1, t2), gu0=c(g_u0), gX=c(g_X), gU=c(g_U), f=force, gx0=gx0, gxr=gxr, gur=gur, gf=gf,
+                            stream=stream)
+        g_other = gw = None
+        if net:
+            if default:
+                eng.synchronize()
+            gz = z(B, N + 1, 6) if need[2] or need[4] else None
+            gw = torch.empty(17859, dtype=torch.float32, device=x0.device) if net_w else None
+            eng.downwash_vjp_device(od, xr, gf, ego_xy=ego_xy, other_index=other_index, gz=gz, gw=gw, stream=stream)
+        if default:
+            eng.synchronize()
+        if net and need[2]:
+            gxr[:, :, :6] -= gz
+        if net and need[4]:
+            g_other = _scatter_gz(gz, od, other_index)
+        return (gx0, None, gxr, gur, g_other, None, gw, None)
+
+
+def control_step_ndp(engine, x0, xr, ur, other, ego_xy=None, weights=None, other_index=None):
+    """(u0, X, U) = the engine's control step with the fused downwash network, differentiable with respect to x0, xr, ur, the neighbour
+    windows `other` and the network's `weights` (see downwash): the step's adjoint, then the network's backward pass on the force's
+    gradient.  Held fixed: the step's linearisation point and active set, and the gate (ego_xy requiring grad raises).  Instances whose
+    step failed (nonzero status) have NaN gradients of their own inputs and contribute nothing to the weights' gradient."""
+    return ControlStepNDPFunction.apply(x0, engine, xr, ur, other, ego_xy, weights, other_index)
+
+
+class NDPControlStep(torch.nn.Module):
+    """control_step_ndp with the network's weights as this module's nn.Parameter `weights` (float32 [17859], blob order), initialised
+    from the shipped blob on the engine's device.  forward(x0, xr, ur, other, ego_xy=None, other_index=None) -> (u0, X, U)."""
+
+    def __init__(self, engine, weights=None):
+        super().__init__()
+        from . import _lib
+        self.engine = engine
+        w = torch.as_tensor(_lib.load_weights() if weights is None else weights, dtype=torch.float32).clone()
+        dev = getattr(getattr(engine, "cfg", None), "device", None)
+        if dev is not None and torch.cuda.is_available():
+            w = w.to(torch.device("cuda", int(dev)))
+        self.weights = torch.nn.Parameter(w)
+
+    def forward(self, x0, xr, ur, other, ego_xy=None, other_index=None):
+        return control_step_ndp(self.engine, x0, xr, ur, other, ego_xy=ego_xy, weights=self.weights, other_index=other_index)
