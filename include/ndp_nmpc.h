@@ -42,7 +42,7 @@ extern "C" {
 /* Version of this interface: bumped whenever an exported signature or the layout of ndp_cfg changes.  A binding built against
  * another header must refuse to run: ndp_abi_version() is what the loaded library was built with, ndp_cfg_size() its
  * sizeof(ndp_cfg) (ndp_create / ndp_default_cfg read and write that many bytes of the caller's struct). */
-#define NDP_ABI_VERSION 8
+#define NDP_ABI_VERSION 9
 int ndp_abi_version(void);
 size_t ndp_cfg_size(void);
 
@@ -338,6 +338,37 @@ int ndp_step_vjp_device(ndp_handle *h, const void *d_x0, const void *d_xr, const
                         const void *d_X_lin, const void *d_U_lin, const void *d_act_lin,
                         const void *d_gu0, const void *d_gX, const void *d_gU,
                         void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_u0_check, void *d_status_check, void *stream);
+
+/* The same adjoint with the gradient in the controller's own numbers beside it: the cost weights Qd [10], Rd [4]
+ * (nmpc_body_rate_ctl.py:48-49) and the mass (fhnp_params.py:9).  ndp_step_vjp_device's arguments, meaning, tape, workspace and refusals
+ * (its four outputs come out bit-equal), plus d_gmodel [B][16] fp64, required: per instance, columns 0..9 dL/dQd, 10..13 dL/dRd, 14 dL/dmass,
+ * 15 written as 0.  One row per instance on purpose: the caller sums (or weights) over the batch, there is no atomic and no second launch,
+ * and two calls are bit-identical.  Fixed final set: exact; the cost is linear in the weights, so with v the adjoint, x+ / u+ the new
+ * iterate and s = dt (stage N: 1)
+ *   dL/dQd[r] = -sum_k s v_k[r] (x+_k[r] - xr_k[r]) for r < 6, dL/dQd[6] = 0 exactly (its residual is the constant 0),
+ *   dL/dQd[7+a] = -sum_k s (E(qr_k) v_q,k)[a] (E(qr_k) q+_k)[a],  dL/dRd[i] = -dt sum_{k<N} v_u,k[i] (u+_k[i] - ur_k[i]) (pinned inputs: 0),
+ *   dL/dmass = -(1/m) sum_k dL/df_k . f_k with the fp32 force the step read (the force enters the model as f / m only); exactly 0 without one.
+ * Interior point: its last Newton system; a nonzero status or a failed adjoint factorisation: NaN in all 16.  Served as
+ * ndp_step_vjp_device is (qp_precision 0, n_rti = 1, N <= 27: kernels of its own for N = 20 and the run-time horizon); -2 with a reason otherwise. */
+int ndp_step_vjp_model_device(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
+                              const void *d_X_lin, const void *d_U_lin, const void *d_act_lin,
+                              const void *d_gu0, const void *d_gX, const void *d_gU,
+                              void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_gmodel, void *d_u0_check, void *d_status_check,
+                              void *stream);
+
+/* Changes the model of a live handle: Qd [10] replaces ndp_cfg.Qd (nmpc_body_rate_ctl.py:48), Rd [4] ndp_cfg.Rd (nmpc_body_rate_ctl.py:49),
+ * mass ndp_cfg.mass (fhnp_params.py:9).  Qd / Rd NULL = keep; mass <= 0 or NaN = keep.  Refused with -2 and a reason in ndp_last_error,
+ * changing nothing: a non-finite entry, a negative Qd, a non-positive Rd, an infinite mass, and -- with as_iter_max > 0 -- an Rd that breaks
+ * ndp_create's rule as_gamma >= NDP_AS_GAMMA_FLOOR * max_i(dt * Rd[i]).
+ * The call waits for the handle's work in flight, then updates the configuration, the kernel parameters and the device's constants table
+ * together.  The iterate, kept active sets, tapes, network weights, estimator state and sensitivity buffers stay as they are: a training
+ * loop keeps its warm start.  A step after the call is bit-equal to the same step on a handle created with these values and given the same
+ * iterate and kept sets.  The mass also reaches ndp_plant_step, the actuator command, the thrust estimator and the reference windows'
+ * flatness map from the next call on.
+ * The kernel parameters travel by value in the kernel arguments: launches enqueued after the call see the new model; anything the caller
+ * captured earlier into a graph of their own keeps the old arguments and must be captured again.  A tape recorded before the call can
+ * still be differentiated, but the adjoint recomputes the step with the handle's CURRENT model: restore the model the step ran with first. */
+int ndp_set_model(ndp_handle *h, const double *Qd, const double *Rd, double mass);
 
 /* Adjoint of DownwashNN.update + the r_horiz gate (downwash_nn.py:21-29, ndp_nmpc_leader_node.py:60-76) as ndp_step_device_ex
  * evaluates them: the vector-Jacobian product of the 6-128-64-128-3 network (nn_net.py:7-18) with d_gf [B][N+1][3] fp64

@@ -16,7 +16,7 @@ WEIGHTS_PATH = os.path.join(_HERE, "weights", "downwash_sn4.bin")
 NX, NU = 10, 4
 MLP_NPARAM = 17859
 QP_AUTO, QP_IPM_ALWAYS = 0, 1
-ABI_VERSION = 8          # include/ndp_nmpc.h: NDP_ABI_VERSION (checked against the loaded library in load())
+ABI_VERSION = 9          # include/ndp_nmpc.h: NDP_ABI_VERSION (checked against the loaded library in load())
 TICK_ESTIMATE, TICK_WANT_U0, TICK_T_UNIFORM = 1, 2, 4
 
 
@@ -57,6 +57,7 @@ EXPORTS = [
     "ndp_sens_params_enable", "ndp_sens_params_enabled", "ndp_get_sens_params", "ndp_device_sens_xr", "ndp_device_sens_ur", "ndp_device_sens_f",
     "ndp_debug_rti_launched", "ndp_device_active_set", "ndp_step_vjp_device",
     "ndp_downwash_vjp_device", "ndp_set_mlp_weights_device", "ndp_debug_mlp_fragments",
+    "ndp_step_vjp_model_device", "ndp_set_model",
 ]
 
 _lib = None
@@ -140,6 +141,8 @@ def load():
     lib.ndp_device_active_set.argtypes = [vp]
     lib.ndp_device_active_set.restype = vp
     lib.ndp_step_vjp_device.argtypes = [vp] * 18
+    lib.ndp_step_vjp_model_device.argtypes = [vp] * 19
+    lib.ndp_set_model.argtypes = [vp, vp, vp, C.c_double]
     lib.ndp_downwash_vjp_device.argtypes = [vp, vp, C.c_int] + [vp] * 7
     lib.ndp_set_mlp_weights_device.argtypes = [vp] * 3
     lib.ndp_debug_mlp_fragments.argtypes = [vp] * 3

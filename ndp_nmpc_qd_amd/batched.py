@@ -394,6 +394,24 @@ class BatchedNMPC:
         U = _lib.f64(U, (self.B, self.N, 4))
         self._check(self._lib.ndp_set_iterate(self._h, _lib.ptr(X), _lib.ptr(U)), "ndp_set_iterate")
 
+    def set_model(self, Qd=None, Rd=None, mass=None):
+        """Changes the cost weights Qd [10], Rd [4] and / or the mass of the live engine (ndp_set_model; include/ndp_nmpc.h); None = keep.
+        Waits for the engine's work in flight.  The iterate, kept sets, network weights and estimator state stay: the next step is
+        warm-started as before, and bit-equal to a fresh engine's with these values and that state.  A refused value (negative Qd,
+        non-positive Rd or mass, an Rd above what as_gamma holds) raises NdpError and changes nothing.  self.cfg follows."""
+        q = None if Qd is None else _lib.f64(Qd, (10,))
+        r = None if Rd is None else _lib.f64(Rd, (4,))
+        m = 0.0 if mass is None else float(mass)
+        if mass is not None and not m > 0.0:
+            raise NdpError(f"set_model: the mass must be positive (got {m})")
+        self._check(self._lib.ndp_set_model(self._h, _lib.ptr(q), _lib.ptr(r), m), "ndp_set_model")
+        if q is not None:
+            self.cfg.Qd[:] = [float(v) for v in q]
+        if r is not None:
+            self.cfg.Rd[:] = [float(v) for v in r]
+        if mass is not None:
+            self.cfg.mass = m
+
     def status(self):
         st = np.zeros(self.B, dtype=np.int32)
         it = np.zeros(self.B, dtype=np.int32)
@@ -523,20 +541,31 @@ class BatchedNMPC:
         return tape
 
     def step_vjp_device(self, x0, xr, ur, tape, gu0=None, gX=None, gU=None, f=None, gx0=None, gxr=None, gur=None, gf=None,
-                        u0_check=None, status_check=None, stream=None):
+                        u0_check=None, status_check=None, stream=None, gmodel=None):
         """Enqueues the adjoint of one recorded step on `stream` (ndp_step_vjp_device; include/ndp_nmpc.h): the step is recomputed from
         `tape` (record_tape) and its x0, xr, ur and fp32 force f (the caller's, or device_force() after a step with neighbour windows;
         None = no force), and the upstream gradients gu0 [B,4], gX [B,N+1,10], gU [B,N,4] (None = 0, not all None) are contracted with
         the derivative of its QP into gx0 [B,10], gxr [B,N+1,10], gur [B,N,4], gf [B,N+1,3] (float64 CUDA tensors the caller allocates;
         None = not written).  u0_check [B,4] float64 / status_check [B] int32: the recompute's u0 and status.  Sensitivities need not be
         on; nothing of the engine's state is written.  stream None or torch's default stream: the call goes on the engine's own stream
-        (the C-ABI's NULL) behind a wait for torch's; read the outputs after engine.synchronize()."""
+        (the C-ABI's NULL) behind a wait for torch's; read the outputs after engine.synchronize().
+        gmodel [B,16] float64 (given: the call is ndp_step_vjp_model_device, the same outputs bit for bit plus gmodel): per instance
+        dL/dQd [0:10], dL/dRd [10:14], dL/dmass [14], 0 [15]; NaN in all 16 where the step failed.  Sum over the batch yourself."""
         import torch
         B, N = self.B, self.N
         if stream is None or getattr(stream, "cuda_stream", stream) == 0:
             torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
         d = self._dptr
         X, U, A = tape
+        if gmodel is not None:
+            self._check(self._lib.ndp_step_vjp_model_device(
+                self._h, d(x0, torch.float64, (B, 10)), d(xr, torch.float64, (B, N + 1, 10)), d(ur, torch.float64, (B, N, 4)),
+                d(f, torch.float32, (B, N + 1, 3)), d(X, torch.float64, (B, N + 1, 10)), d(U, torch.float64, (B, N, 4)),
+                d(A, torch.int8, (B, N, 4)), d(gu0, torch.float64, (B, 4)), d(gX, torch.float64, (B, N + 1, 10)),
+                d(gU, torch.float64, (B, N, 4)), d(gx0, torch.float64, (B, 10)), d(gxr, torch.float64, (B, N + 1, 10)),
+                d(gur, torch.float64, (B, N, 4)), d(gf, torch.float64, (B, N + 1, 3)), d(gmodel, torch.float64, (B, 16)),
+                d(u0_check, torch.float64, (B, 4)), d(status_check, torch.int32, (B,)), self._stream(stream)), "ndp_step_vjp_model_device")
+            return
         self._check(self._lib.ndp_step_vjp_device(
             self._h, d(x0, torch.float64, (B, 10)), d(xr, torch.float64, (B, N + 1, 10)), d(ur, torch.float64, (B, N, 4)),
             d(f, torch.float32, (B, N + 1, 3)), d(X, torch.float64, (B, N + 1, 10)), d(U, torch.float64, (B, N, 4)),

@@ -335,6 +335,33 @@ __global__ __launch_bounds__(256) void rti_vjp_kernel(KernArgs ka, VjpArgs va)
     Prog::template run<false, true, false, false, true>(P, io, lds, inb, x0v, nullptr, nullptr, &vo);
 }
 
+// The same adjoint with the gradient in the cost weights and the mass beside it (ndp_step_vjp_model_device, RtiWave::vjp_out<true>):
+// gmodel [B][16] = dL/dQd [10] | dL/dRd [4] | dL/dmass | 0, one row per instance (the caller sums over the batch: no atomic, two calls are
+// bit-identical).  Kernels of their own, so that rti_vjp_kernel stays the code it was.
+template <int NC>
+__global__ __launch_bounds__(256) void rti_wvjp_kernel(KernArgs ka, VjpArgs va, double *gmodel)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const RtiParams &P = ka.P;
+    const int waves = (int)(blockDim.x >> 6), wave = (int)(threadIdx.x >> 6);
+    const int inst = __builtin_amdgcn_readfirstlane((int)blockIdx.x * waves + wave);
+    if (inst >= ka.B) return;
+    const int N = NC ? NC : P.N;
+    RtiIo io;
+    bind_instance(io, ka.bp, inst, N);
+    const int lpw = NC ? ((lds_doubles(NC) + 1) & ~1) : ka.lds_per_wave;
+    WaveGfx950::lds_ptr lds = (WaveGfx950::lds_ptr)(smem + (size_t)wave * lpw);
+    using Prog = RtiWave<WaveGfx950, 3, NC, true, NC ? 1 : 0>;
+    const size_t i = (size_t)inst, nx = (size_t)(N + 1) * NX, nu = (size_t)N * NU, nf = (size_t)(N + 1) * 3;
+    const VjpIo vo{va.gu0 ? va.gu0 + i * NU : nullptr, va.gX ? va.gX + i * nx : nullptr, va.gU ? va.gU + i * nu : nullptr,
+                   va.gx0 ? va.gx0 + i * NX : nullptr, va.gxr ? va.gxr + i * nx : nullptr, va.gur ? va.gur + i * nu : nullptr,
+                   va.gf ? va.gf + i * nf : nullptr};
+    typename Prog::InBuf inb;
+    double x0v;
+    Prog::issue_first(P, io, inb, x0v);
+    Prog::template run<false, true, false, false, true, true>(P, io, lds, inb, x0v, nullptr, nullptr, &vo, gmodel + i * 16);
+}
+
 // test hook: one v_mfma_f64_16x16x4_f64 / v_mfma_f64_4x4x4_4b_f64 with caller-chosen per-lane operands (pins the register maps)
 __global__ void mfma_probe_kernel(const double *a, const double *b, const double *c, double *d)
 {
@@ -1938,6 +1965,16 @@ int ndp_destroy(ndp_handle *h)
     return 0;
 }
 
+// a pin is the weight as_gamma on its input: far below the input weights it holds nothing, yet as_check still writes the input onto
+// its bound -- a wrong step with status 0 (NDP_AS_GAMMA_FLOOR in the header).  ndp_create's rule, and ndp_set_model's for a new Rd.
+static bool as_gamma_holds(const ndp_cfg &c, const double *Rd)
+{
+    if (c.as_iter_max <= 0) return true;
+    double rd = 0.0;
+    for (int i = 0; i < 4; ++i) rd = std::max(rd, std::fabs(c.dt * Rd[i]));
+    return std::isfinite(c.as_gamma) && c.as_gamma >= NDP_AS_GAMMA_FLOOR * rd;
+}
+
 int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
 {
     if (!cfg || !out) { g_create_err = "ndp_create: null argument"; return -1; }
@@ -1951,16 +1988,10 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
         g_create_err = "ndp_create: the condensed study (qp_precision 5 / 6) tiles the 4N x 4N Hessian by 16: N must be a multiple of 4, at most 40";
         return -2;
     }
-    if (cfg->as_iter_max > 0) {
-        // a pin is the weight as_gamma on its input: far below the input weights it holds nothing, yet as_check still writes the input onto
-        // its bound -- a wrong step with status 0 (NDP_AS_GAMMA_FLOOR in the header)
-        double rd = 0.0;
-        for (int i = 0; i < 4; ++i) rd = std::max(rd, std::fabs(cfg->dt * cfg->Rd[i]));
-        if (!std::isfinite(cfg->as_gamma) || !(cfg->as_gamma >= NDP_AS_GAMMA_FLOOR * rd)) {
-            g_create_err = "ndp_create: as_gamma must be finite and at least 1e8 * max(dt * Rd) when as_iter_max > 0 (a weaker pin does not hold "
-                           "its input on the bound)";
-            return -2;
-        }
+    if (!as_gamma_holds(*cfg, cfg->Rd)) {
+        g_create_err = "ndp_create: as_gamma must be finite and at least 1e8 * max(dt * Rd) when as_iter_max > 0 (a weaker pin does not hold "
+                       "its input on the bound)";
+        return -2;
     }
     if (cfg->ipm_refine > 0 && (slots_for(cfg->N) > 3 || cfg->qp_precision != 0)) {
         // (rounds 4-5 accepted the setting and ignored it -- a getter nobody called said so)
@@ -2090,6 +2121,9 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
     for (const RtiKern &k : k_rti)      // (the sensitivity kernels: ndp_sens_enable)
         if (!k.sens && (e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) != hipSuccess)
             return fail("hipFuncSetAttribute", e);
+    for (const void *fn : {(const void *)rti_wvjp_kernel<20>, (const void *)rti_wvjp_kernel<0>})   // (ndp_step_vjp_model_device)
+        if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess)
+            return fail("hipFuncSetAttribute(rti_wvjp_kernel)", e);
     for (const void *fn : {(const void *)rti_vjp_kernel<20>, (const void *)rti_vjp_kernel<0>})     // (the adjoint: ndp_step_vjp_device)
         if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) != hipSuccess)
             return fail("hipFuncSetAttribute(rti_vjp_kernel)", e);
@@ -3723,22 +3757,25 @@ void *ndp_device_sens_f(ndp_handle *h) { return h ? h->dPSensF : nullptr; }
 // ---- adjoint of the control step (rti_vjp_kernel, RtiWave::vjp_out)
 void *ndp_device_active_set(ndp_handle *h) { return h ? h->dAct : nullptr; }
 
-int ndp_step_vjp_device(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
-                        const void *d_X_lin, const void *d_U_lin, const void *d_act_lin,
-                        const void *d_gu0, const void *d_gX, const void *d_gU,
-                        void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_u0_check, void *d_status_check, void *stream)
+// model: the entry is ndp_step_vjp_model_device (rti_wvjp_kernel; d_gmodel required), else ndp_step_vjp_device (rti_vjp_kernel)
+static int step_vjp(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
+                    const void *d_X_lin, const void *d_U_lin, const void *d_act_lin,
+                    const void *d_gu0, const void *d_gX, const void *d_gU,
+                    void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_u0_check, void *d_status_check, void *stream,
+                    bool model, void *d_gmodel)
 {
     Entry g(h, true, stream);
     if (g.rc) return g.rc;
     const ndp_cfg &c = h->cfg;
-    const char *why = nullptr;
-    if (c.n_rti != 1) why = "ndp_step_vjp_device: the adjoint needs n_rti = 1 (the derivative of the step's one QP)";
-    else if (c.qp_precision != 0) why = "ndp_step_vjp_device: the adjoint needs qp_precision 0 (the fp64 product path)";
-    else if (slots_for(c.N) > 3) why = "ndp_step_vjp_device: the adjoint is served for N <= 27 only (the five-slot kernels of N >= 28 have none)";
-    else if (!d_x0 || !d_xr || !d_ur || !d_X_lin || !d_U_lin) why = "ndp_step_vjp_device: x0, xr, ur and the tape's iterate (X_lin, U_lin) are required";
-    else if (!d_gu0 && !d_gX && !d_gU) why = "ndp_step_vjp_device: no upstream gradient (gu0, gX and gU all NULL)";
-    else if (d_f && !c.use_fd) why = "ndp_step_vjp_device: a disturbance force needs use_fd = 1 (NDP model)";
-    if (why) { h->err = why; return -2; }
+    const char *why = nullptr;                      // (the message behind the entry's name)
+    if (c.n_rti != 1) why = "the adjoint needs n_rti = 1 (the derivative of the step's one QP)";
+    else if (c.qp_precision != 0) why = "the adjoint needs qp_precision 0 (the fp64 product path)";
+    else if (slots_for(c.N) > 3) why = "the adjoint is served for N <= 27 only (the five-slot kernels of N >= 28 have none)";
+    else if (!d_x0 || !d_xr || !d_ur || !d_X_lin || !d_U_lin) why = "x0, xr, ur and the tape's iterate (X_lin, U_lin) are required";
+    else if (!d_gu0 && !d_gX && !d_gU) why = "no upstream gradient (gu0, gX and gU all NULL)";
+    else if (d_f && !c.use_fd) why = "a disturbance force needs use_fd = 1 (NDP model)";
+    else if (model && !d_gmodel) why = "gmodel is required (without it: ndp_step_vjp_device)";
+    if (why) { h->err = std::string(model ? "ndp_step_vjp_model_device: " : "ndp_step_vjp_device: ") + why; return -2; }
     const size_t B = c.batch;
     if (!h->dVjp) {
         NDP_HIP(h, hipMalloc((void **)&h->dVjp, (nxs(h) + nus(h) + B * NU) * 8));
@@ -3760,11 +3797,69 @@ int ndp_step_vjp_device(ndp_handle *h, const void *d_x0, const void *d_xr, const
     VjpArgs va{(const double *)d_gu0, (const double *)d_gX, (const double *)d_gU, (double *)d_gx0, (double *)d_gxr, (double *)d_gur,
                (double *)d_gf};
     const int W = h->waves;
-    const void *fn = c.N == 20 ? (const void *)rti_vjp_kernel<20> : (const void *)rti_vjp_kernel<0>;
-    void *args[] = {&ka, &va};
+    const void *fn = model ? (c.N == 20 ? (const void *)rti_wvjp_kernel<20> : (const void *)rti_wvjp_kernel<0>)
+                           : (c.N == 20 ? (const void *)rti_vjp_kernel<20> : (const void *)rti_vjp_kernel<0>);
+    double *gm = (double *)d_gmodel;
+    void *args[] = {&ka, &va, &gm};                 // (rti_vjp_kernel takes the first two)
     NDP_HIP(h, hipLaunchKernel(fn, dim3((unsigned)((B + W - 1) / W)), dim3(64 * W), args, (size_t)h->lds_per_wave * sizeof(double) * W, s));
     NDP_HIP(h, hipGetLastError());
     return g.noted(0);
+}
+
+int ndp_step_vjp_device(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
+                        const void *d_X_lin, const void *d_U_lin, const void *d_act_lin,
+                        const void *d_gu0, const void *d_gX, const void *d_gU,
+                        void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_u0_check, void *d_status_check, void *stream)
+{
+    return step_vjp(h, d_x0, d_xr, d_ur, d_f, d_X_lin, d_U_lin, d_act_lin, d_gu0, d_gX, d_gU, d_gx0, d_gxr, d_gur, d_gf, d_u0_check,
+                    d_status_check, stream, false, nullptr);
+}
+
+int ndp_step_vjp_model_device(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
+                              const void *d_X_lin, const void *d_U_lin, const void *d_act_lin,
+                              const void *d_gu0, const void *d_gX, const void *d_gU,
+                              void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_gmodel, void *d_u0_check, void *d_status_check,
+                              void *stream)
+{
+    return step_vjp(h, d_x0, d_xr, d_ur, d_f, d_X_lin, d_U_lin, d_act_lin, d_gu0, d_gX, d_gU, d_gx0, d_gxr, d_gur, d_gf, d_u0_check,
+                    d_status_check, stream, true, d_gmodel);
+}
+
+// ---- the model of a live handle: cost weights and mass
+int ndp_set_model(ndp_handle *h, const double *Qd, const double *Rd, double mass)
+{
+    if (!h) return -1;
+    std::lock_guard<std::mutex> lk(h->mu);
+    ndp_cfg c = h->cfg;
+    const char *why = nullptr;
+    if (Qd)
+        for (int i = 0; i < 10; ++i) {
+            if (!std::isfinite(Qd[i]) || Qd[i] < 0.0) why = "ndp_set_model: every Qd must be finite and >= 0";
+            c.Qd[i] = Qd[i];
+        }
+    if (Rd)
+        for (int i = 0; i < 4; ++i) {
+            if (!std::isfinite(Rd[i]) || !(Rd[i] > 0.0)) why = "ndp_set_model: every Rd must be finite and > 0";
+            c.Rd[i] = Rd[i];
+        }
+    if (std::isinf(mass)) why = "ndp_set_model: the mass must be finite (<= 0 or NaN: keep)";
+    else if (mass > 0.0) c.mass = mass;
+    if (!why && !as_gamma_holds(c, c.Rd))
+        why = "ndp_set_model: as_gamma must be at least 1e8 * max(dt * Rd) when as_iter_max > 0 (ndp_create's rule: a weaker pin does not hold "
+              "its input on the bound)";
+    if (why) { h->err = why; return -2; }
+    NDP_HIP(h, hipSetDevice(c.device));
+    int rc = wait_all(h);                  // launches in flight read dKC; the copy below must not overtake them
+    if (rc) return rc;
+    // cfg, P (kernel arguments: the attitude weights, 1 / mass) and the constants table (KC_QD, KC_RD in LDS) change together; every
+    // other reader of the mass (plant, actuator command, thrust estimator, reference flatness, BatchPtrs) takes it from cfg per call
+    const RtiParams P = to_params(c);
+    double kc[KC_HOST];
+    fill_kc(P, kc);
+    NDP_HIP(h, hipMemcpy(h->dKC, kc, sizeof(kc), hipMemcpyHostToDevice));
+    h->cfg = c;
+    h->P = P;
+    return 0;
 }
 int ndp_refine_active(ndp_handle *h) { return h ? (int)(h->cfg.ipm_refine > 0 && slots_for(h->cfg.N) <= 3 && h->cfg.qp_precision == 0) : -1; }
 

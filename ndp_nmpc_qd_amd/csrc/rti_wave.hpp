@@ -1975,9 +1975,10 @@ struct RtiWave {
     // SENS (rti_sens_kernel): after the step, the sensitivities of its last QP (sens_out) into *sens.  One RTI iteration only.
     // PSENS (rti_psens_kernel): behind them, the parameter sensitivities (psens_out) into *psens.
     // VJP (rti_vjp_kernel): after the step, the adjoint of its last QP contracted with an upstream gradient (vjp_out) into *vjp.
-    template <bool DEFER, bool IPM_RARE = false, bool SENS = false, bool PSENS = false, bool VJP = false>
+    // WVJP (rti_wvjp_kernel, with VJP): the same pass also gives the gradient in the cost weights and the mass into gmodel [16].
+    template <bool DEFER, bool IPM_RARE = false, bool SENS = false, bool PSENS = false, bool VJP = false, bool WVJP = false>
     static NDP_D bool run(const RtiParams &P, const RtiIo &io, lp lds, InBuf &inb, vd x0v, const SensIo *sens = nullptr,
-                          const PSensIo *psens = nullptr, const VjpIo *vjp = nullptr)
+                          const PSensIo *psens = nullptr, const VjpIo *vjp = nullptr, double *gmodel = nullptr)
     {
         const int N = horizon(P);
         const LdsMap m = make_map(N);
@@ -2198,7 +2199,8 @@ struct RtiWave {
             if (psens) psens_out(P, m, lds, io, A, zlast, status != 0, *psens);
         }
         if constexpr (VJP) {
-            if (vjp) vjp_out(P, m, T, lds, io, A, zlast, status != 0, *vjp);
+            if constexpr (WVJP) { if (vjp) vjp_out<true>(P, m, T, lds, io, A, zlast, status != 0, *vjp, gmodel); }
+            else if (vjp) vjp_out(P, m, T, lds, io, A, zlast, status != 0, *vjp);
         }
         if (io.f_late) W::late_publish(late_prev, io.late_gsize, io.late_done_word);
         return false;
@@ -2431,8 +2433,18 @@ struct RtiWave {
     // (pinned: 0), dL/df_k = (h^2/2 mu_{k+1}[0..2] + h mu_{k+1}[3..5]) / m -- stage 0's reference and f_N are exactly 0.
     // LDS after the commit: qr and q+ in rows 0..3 / 6..9 of XI (as psens_out), the final set in AS, gX in CX, v in ZX|ZU, mu_{k+1} in ZD (the
     // sweep's shadow, dead behind it).  A nonzero status (or a failed adjoint factorisation): NaN in every output.
+    // WM (rti_wvjp_kernel): the same adjoint v contracted with the QP's derivative in the cost weights and the mass, into gm [16] = dL/dQd
+    // [10] | dL/dRd [4] | dL/dmass | 0.  The cost enters the QP as g = s W (xbar - xr), H = s W (s = dt, at stage N: 1), linear in W, so with
+    // the residual of the NEW iterate rho = x+ - xr (attitude: E(qr) q+; inputs: u+ - ur)
+    //     dL/dQd_r = -sum_k s v_k[r] rho_k[r],  dL/dQd_{7+a} = -sum_k s (E(qr_k) v_q,k)[a] (E(qr_k) q+_k)[a],  dL/dQd_6 = 0 (residual 0),
+    //     dL/dRd_i = -dt sum_{k<N} v_u,k[i] rho_u,k[i] (pinned: 0),  dL/dmass = -(1/m) sum_{k<N} dL/df_k . f_k (the force enters as f / m only;
+    //     the fp32 force the step read; none: exactly 0).
+    // rho of the position / velocity rows and the inputs is formed before XI and ZX are overwritten, rides in registers across the sweep
+    // and is parked in its dead data entries (qe, re of the cost blocks; the force in the defects b); the sums run in the costate
+    // loop, lane r < 10 on Qd_r, lanes 10..13 on Rd, lane 14 on the mass: no cross-lane reduction, no atomic.
+    template <bool WM = false>
     static NDP_D void vjp_out(const RtiParams &P, const LdsMap &m, const Tables &T, lp lds, const RtiIo &io, const ActSet &A, int zsrc,
-                              bool bad, const VjpIo &vo)
+                              bool bad, const VjpIo &vo, [[maybe_unused]] double *gm = nullptr)
     {
         static_assert(!A_LDS, "the final set is parked in the AS area, which the five-slot kernels use");
         const int N = horizon(P);
@@ -2448,8 +2460,23 @@ struct RtiWave {
                 if (vo.gf) W::gst(vo.gf, e, nan, e < nf);
             }
             if (vo.gx0) W::gst(vo.gx0, lane, nan, lane < int(NX));
+            if constexpr (WM) W::gst(gm, lane, nan, lane < 16);
         };
         if (bad) { nan_out(); return; }
+        constexpr int WX = NC ? ((NC + 1) * int(NX) + 63) / 64 : RX, WU = NC ? (NC * int(NU) + 63) / 64 : RU;
+        [[maybe_unused]] vd wdx[WX], wdu[WU], wf[RF];
+        [[maybe_unused]] const bool have_f = P.use_fd && io.f;
+        if constexpr (WM) {                                    // rho = x+ - xr, u+ - ur and the step's force, while XI|UI and the step still stand
+            for (int t = 0; t < WX; ++t) {
+                vi e = W::imin(lane + 64 * t, nxr - 1);
+                wdx[t] = W::ld(lds, e + m.XI) + W::ld(lds, e + zsrc) - W::gldu(io.xr, e);
+            }
+            for (int t = 0; t < WU; ++t) {
+                vi e = W::imin(lane + 64 * t, nur - 1);
+                wdu[t] = W::ld(lds, e + m.UI) + W::ld(lds, e + (zsrc + nxr)) - W::gldu(io.ur, e);
+            }
+            for (int t = 0; t < RF; ++t) wf[t] = have_f ? W::gldfu(io.f, W::imin(lane + 64 * t, nf - 1)) : vd(0.0);
+        }
         for (int t = 0; t < RUA; ++t) {                        // the final set, 0 / 1 per input bound
             vi e = a_elem(P, lane, t);
             W::st(lds, e + m.AS, W::sel(a_get(A, m, lds, t, e) == 0, vd(0.0), vd(1.0)));
@@ -2489,10 +2516,27 @@ struct RtiWave {
         if (zsrc != m.ZX && 14 * N + 10 >= 64) ok = riccati_sweep<false, true>(P, m, T, lds);
         else ok = riccati_sweep(P, m, T, lds);
         if (NDP_RARELY(!ok)) { nan_out(); return; }
+        if constexpr (WM) {                                    // park them where the sweep's data lay (qe, re, b: dead behind it)
+            for (int t = 0; t < WX; ++t) {
+                vi e = W::imin(lane + 64 * t, nxr - 1);
+                vi k = (e * 6554) >> 16, rw = e - k * 10;
+                W::st(lds, k * int(CB_STRIDE) + rw + (m.CB + int(CB_QE)), wdx[t]);
+            }
+            for (int t = 0; t < WU; ++t) {
+                vi e = W::imin(lane + 64 * t, nur - 1);
+                W::st(lds, (e >> 2) * int(CB_STRIDE) + (e & 3) + (m.CB + int(CB_RE)), wdu[t]);
+            }
+            for (int t = 0; t < RF; ++t) {
+                vi e = W::imin(lane + 64 * t, nf - 1);
+                vi k = W::div3(e), cc = e - 3 * k;
+                W::stp(lds, W::imin(k, vi(N - 1)) * int(MB_STRIDE) + cc + (m.MB + int(MB_B)), wf[t], k < N);
+            }
+        }
         const int LM = m.ZD;
         const vi r = W::imin(lane, vi(NX - 1));
         const vb row = lane < int(NX);
         const double h = P.dt;
+        [[maybe_unused]] vd gacc = vd(0.0);                    // WM: this lane's entry of gm
         W::stp(lds, lane + LM, vd(0.0), row);                  // mu_{N+1} = 0
         W::sync();
         NDP_KEEP_LOOP
@@ -2526,6 +2570,34 @@ struct RtiWave {
                 u = W::sel(W::ld(lds, i + (m.AS + k * int(NU))) == 0.0, u, vd(0.0));
                 W::gst(vo.gur, i + k * int(NU), u * W::ld(lds, i + (m.KC + int(KC_RD))) * h, lane < int(NU));
             }
+            if constexpr (WM) {   // lane r < 10: Qd_r; lanes 10..13: Rd; lane 14: the mass (mu_{k+1} still in LM)
+                vd wq[4], v[4], q[4];
+                for (int a = 0; a < 4; ++a) {
+                    wq[a] = W::ld(lds, vi(xk + 6 + a));
+                    v[a] = W::ld(lds, vi(m.XI + k * int(NX) + 6 + a));
+                    q[a] = W::ld(lds, vi(m.XI + k * int(NX) + a));
+                }
+                vd ew[3], ev[3];
+                emul(q, wq, ew); emul(q, v, ev);
+                const vd att = W::sel(r == 7, ew[0] * ev[0], W::sel(r == 8, ew[1] * ev[1], ew[2] * ev[2]));
+                const vd pv = W::ld(lds, r + xk) * W::ld(lds, r + (m.CB + cb(k) + int(CB_QE)));
+                vd term = W::sel(r < 6, pv, W::sel(r == 6, vd(0.0), att)) * s;
+                if (k < N) {
+                    const vi i = W::imin(W::sel(row, vi(0), lane - int(NX)), vi(NU - 1));
+                    vd u = W::ld(lds, i + (m.ZU + k * int(NU)));
+                    u = W::sel(W::ld(lds, i + (m.AS + k * int(NU))) == 0.0, u, vd(0.0));
+                    const vd tu = u * W::ld(lds, i + (m.CB + cb(k) + int(CB_RE))) * h;
+                    vd tm = vd(0.0);
+                    if (have_f)
+                        for (int c3 = 0; c3 < 3; ++c3)
+                            tm = tm + (W::ld(lds, vi(LM + c3)) * (0.5 * h * h) + W::ld(lds, vi(LM + 3 + c3)) * h) * (P.inv_mass * P.inv_mass) *
+                                          W::ld(lds, vi(m.MB + mb(k) + int(MB_B) + c3));
+                    term = W::sel(row, term, W::sel(lane < int(NX + NU), tu, tm));
+                } else {
+                    term = W::sel(row, term, vd(0.0));
+                }
+                gacc = gacc - term;
+            }
             {   // mu_k = gX_k - Q_k v_k + A_k' mu_{k+1}, lanes r < 10
                 vd l = W::ld(lds, r + (m.CX + k * int(NX)));
                 for (int j = 0; j < NX; ++j) l = l - W::ld(lds, c_entry(m, r, vi(j)) + cb(k)) * W::ld(lds, vi(xk + j));
@@ -2537,6 +2609,7 @@ struct RtiWave {
             }
         }
         if (vo.gx0) W::gst(vo.gx0, r, W::ld(lds, r + LM), row);
+        if constexpr (WM) W::gst(gm, lane, W::sel(lane < 15, gacc, vd(0.0)), lane < 16);
     }
     // E(q) w (build_cost's E of the attitude residual, linear in q)
     static NDP_D void emul(const vd q[4], const vd w[4], vd o[3])

@@ -20,6 +20,9 @@ with the upstream gradients (BatchedNMPC.step_vjp_device).  Same derivative as a
 
 downwash / control_step_ndp / NDPControlStep (at the end of this file) continue that adjoint through the downwash network: gradients of the
 neighbour windows and of the network's weights (BatchedNMPC.downwash_vjp_device).  The entry points above keep refusing other / ego_xy.
+
+control_step_tunable / TunableControlStep (behind them) differentiate the controller's own numbers -- the cost weights Qd, Rd and the mass --
+by the same adjoint (BatchedNMPC.set_model, step_vjp_device with gmodel).
 """
 import torch
 
@@ -363,3 +366,114 @@ class NDPControlStep(torch.nn.Module):
 
     def forward(self, x0, xr, ur, other, ego_xy=None, other_index=None):
         return control_step_ndp(self.engine, x0, xr, ur, other, ego_xy=ego_xy, weights=self.weights, other_index=other_index)
+
+
+# ---------------------------------------------------------------------------------------------- the controller's own numbers, differentiated
+# What is differentiated: the step's QP with respect to the cost weights Qd [10], Rd [4] and the mass (BatchedNMPC.step_vjp_device with
+# gmodel: ndp_step_vjp_model_device), beside x0, xr, ur and f as control_step_trajectory gives them.  Held fixed: linearisation point, x0 and
+# active set, as in every derivative here.  The network's backward (control_step_ndp) is not combined with this one: a caller who wants both
+# runs the force through `downwash` and passes it as f.
+
+def _model_values(Qd, Rd, mass):
+    """(Qd, Rd, mass) as host tuples of Python floats (None = not given).  Tensors on a device are copied to the host: that synchronises."""
+    h = lambda t, n: None if t is None else tuple(float(v) for v in torch.as_tensor(t).detach().to("cpu", torch.float64).reshape(n))  # noqa: E731
+    m = h(mass, 1)
+    return h(Qd, 10), h(Rd, 4), None if m is None else m[0]
+
+
+def _engine_model(engine):
+    return tuple(engine.cfg.Qd), tuple(engine.cfg.Rd), float(engine.cfg.mass)
+
+
+def _install_model(engine, Qd, Rd, mass):
+    """Installs the values through engine.set_model unless they are what the engine holds; returns the model the step then runs with."""
+    q, r, m = _model_values(Qd, Rd, mass)
+    eq, er, em = _engine_model(engine)
+    new = (q if q is not None and q != eq else None, r if r is not None and r != er else None, m if m is not None and m != em else None)
+    if any(v is not None for v in new):
+        engine.set_model(Qd=new[0], Rd=new[1], mass=new[2])
+    return _engine_model(engine)
+
+
+class TunableControlStepFunction(torch.autograd.Function):
+    """forward(x0, engine, xr, ur, Qd, Rd, mass, f) -> (u0, X, U) float64; backward: one call of the adjoint with the model gradient
+    (BatchedNMPC.step_vjp_device, gmodel=) for the gradients of x0, xr, ur, f, Qd, Rd and mass."""
+
+    @staticmethod
+    def forward(ctx, x0, engine, xr, ur, Qd, Rd, mass=None, f=None):
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t  # noqa: E731
+        x0, xr, ur, fd = det(x0), det(xr), det(ur), det(f)
+        ctx.model = _install_model(engine, Qd, Rd, mass)
+        stream, default = _cuda_stream(x0)
+        tape = engine.record_tape(stream)
+        u0 = torch.empty((x0.shape[0], 4), dtype=x0.dtype, device=x0.device)
+        engine.update_device(x0, xr, ur, u0, f=fd, stream=stream)
+        if default:
+            engine.synchronize()
+        X, U = (t.clone() for t in engine.device_iterate())
+        ctx.engine = engine
+        ctx.f_dtype = f.dtype if isinstance(f, torch.Tensor) else None
+        ctx.like = tuple(None if not isinstance(t, torch.Tensor) else (t.shape, t.dtype, t.device) for t in (Qd, Rd, mass))
+        ctx.save_for_backward(x0, xr, ur, *tape, *(() if fd is None else (fd,)))
+        return u0, X, U
+
+    @staticmethod
+    def backward(ctx, g_u0, g_X, g_U):
+        x0, xr, ur, t0, t1, t2, *rest = ctx.saved_tensors
+        force = rest[0] if rest else None
+        eng = ctx.engine
+        if g_u0 is None and g_X is None and g_U is None:
+            return (None,) * 8
+        if _engine_model(eng) != ctx.model:
+            raise RuntimeError("TunableControlStepFunction: the engine's model (Qd, Rd, mass) was changed between this forward and its "
+                               "backward (the backward recomputes the step from the engine's model): run the backward before the next "
+                               "forward with other values, or set the model back first")
+        c = lambda g: None if g is None else g.to(torch.float64).contiguous()  # noqa: E731
+        z = lambda *s: torch.empty(*s, dtype=torch.float64, device=x0.device)  # noqa: E731
+        B, N = x0.shape[0], xr.shape[1] - 1
+        need = ctx.needs_input_grad
+        gx0 = z(B, 10) if need[0] else None
+        gxr = z(B, N + 1, 10) if need[2] else None
+        gur = z(B, N, 4) if need[3] else None
+        gf = z(B, N + 1, 3) if need[7] and ctx.f_dtype is not None else None
+        gm = z(B, 16)
+        stream, default = _cuda_stream(x0)
+        eng.step_vjp_device(x0, xr, ur, (t0, t1, t2), gu0=c(g_u0), gX=c(g_X), gU=c(g_U), f=force, gx0=gx0, gxr=gxr, gur=gur, gf=gf,
+                            gmodel=gm, stream=stream)
+        if default:
+            eng.synchronize()
+        # a failed step (NaN in its row) contributes nothing: control_step_ndp's convention for the network's weights
+        tot = torch.where(torch.isfinite(gm).all(dim=1, keepdim=True), gm, torch.zeros_like(gm)).sum(dim=0)
+        out = []
+        for like, need_i, part in zip(ctx.like, need[4:7], (tot[0:10], tot[10:14], tot[14:15])):
+            out.append(None if like is None or not need_i else part.reshape(like[0]).to(device=like[2], dtype=like[1]))
+        return (gx0, None, gxr, gur, out[0], out[1], out[2], None if gf is None else gf.to(ctx.f_dtype))
+
+
+def control_step_tunable(engine, x0, xr, ur, Qd, Rd, mass=None, f=None):
+    """(u0, X, U) = the engine's control step with the cost weights Qd [10], Rd [4] and (optionally) the mass given as float64 tensors on
+    any device, differentiable with respect to them and to x0, xr, ur and f (the latter as control_step_trajectory).
+    Forward: the values are installed in the engine (BatchedNMPC.set_model) unless they are what it holds -- compared by value on the
+    host, so 15 doubles move to the host on every call, which SYNCHRONISES when they live on the device -- then the tape is recorded
+    and the step runs; the iterate and kept sets (the warm start) survive a change of the model.
+    Backward: one adjoint launch; the gradients of Qd, Rd and mass are the sum over the instances of the per-instance rows, a failed step
+    (nonzero status) contributing nothing.  If the engine's model was changed between a forward and its backward, the backward raises.
+    The library refuses a negative Qd, a non-positive Rd or mass (NdpError): keeping parameters positive is the caller's business (project
+    them after the optimiser's step, or optimise their logarithms) -- nothing is clamped here.
+    The downwash network is not part of this entry point (no other / ego_xy): see control_step_ndp for its gradients."""
+    return TunableControlStepFunction.apply(x0, engine, xr, ur, Qd, Rd, mass, f)
+
+
+class TunableControlStep(torch.nn.Module):
+    """control_step_tunable with Qd [10] and Rd [4] (and, with learn_mass=True, mass) as this module's float64 nn.Parameters, initialised
+    from the engine's cfg.  forward(x0, xr, ur, f=None) -> (u0, X, U).  Parameters are not clamped: see control_step_tunable."""
+
+    def __init__(self, engine, learn_mass=False):
+        super().__init__()
+        self.engine = engine
+        self.Qd = torch.nn.Parameter(torch.tensor(list(engine.cfg.Qd), dtype=torch.float64))
+        self.Rd = torch.nn.Parameter(torch.tensor(list(engine.cfg.Rd), dtype=torch.float64))
+        self.mass = torch.nn.Parameter(torch.tensor(float(engine.cfg.mass), dtype=torch.float64)) if learn_mass else None
+
+    def forward(self, x0, xr, ur, f=None):
+        return control_step_tunable(self.engine, x0, xr, ur, self.Qd, self.Rd, mass=self.mass, f=f)

@@ -1,0 +1,380 @@
+"""The control step's model on the device (run with -m gpu): ndp_set_model against a fresh handle, rti_wvjp_kernel's gradient in Qd, Rd and the
+mass against the dense fixed-set reference (tests/model_grad_ref.py) and against device finite differences THROUGH ndp_set_model,
+isolation and repeatability, and the torch layer (control_step_tunable, TunableControlStep).  CPU side: tests/test_model_grad.py."""
+import numpy as np
+import pytest
+
+from ndp_nmpc_qd_amd import synth
+from tests.model_grad_ref import model_grad_ref
+from tests.psens_ref import scale
+
+pytestmark = pytest.mark.gpu
+
+MIXED = dict(pos_sigma=0.5, vel_sigma=1.0, quat_sigma=0.15)        # bench.py's `mixed` workload
+
+
+@pytest.fixture(scope="module")
+def ndp():
+    import ndp_nmpc_qd_amd
+    return ndp_nmpc_qd_amd
+
+
+def _dev():
+    import torch
+    return torch.device("cuda", 0)
+
+
+def _t(a, dtype=None):
+    import torch
+    return torch.tensor(np.ascontiguousarray(a), device=_dev(), dtype=dtype)
+
+
+def _vjp(eng, x0, xr, ur, tape, f=None, gu0=None, gX=None, gU=None, model=True):
+    """step_vjp_device on torch tensors; returns numpy (gx0, gxr, gur, gf, u0_check, status_check[, gmodel])."""
+    import torch
+    B, N = eng.B, eng.N
+    z = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device=_dev())  # noqa: E731
+    out = (z(B, 10), z(B, N + 1, 10), z(B, N, 4), z(B, N + 1, 3), z(B, 4))
+    st = torch.full((B,), -1, dtype=torch.int32, device=_dev())
+    gm = z(B, 16) if model else None
+    eng.step_vjp_device(x0, xr, ur, tape, gu0=gu0, gX=gX, gU=gU, f=f, gx0=out[0], gxr=out[1], gur=out[2], gf=out[3], u0_check=out[4],
+                        status_check=st, gmodel=gm)
+    torch.cuda.synchronize()
+    return tuple(t.cpu().numpy() for t in out) + (st.cpu().numpy(),) + ((gm.cpu().numpy(),) if model else ())
+
+
+def _recorded_step(ndp, b, f=None, **kw):
+    """A fresh engine, one warm-up step (a kept set to start from), then the recorded step."""
+    import torch
+    B, N = b["x0"].shape[0], b["xr"].shape[1] - 1
+    eng = ndp.BatchedNMPC(B, N=N, disturbance=f is not None, **kw)
+    eng.reset(b["xr"], b["ur"])
+    t = {k: _t(b[k]) for k in ("x0", "xr", "ur")}
+    ft = _t(f, torch.float32) if f is not None else None
+    u0 = torch.empty(B, 4, dtype=torch.float64, device=_dev())
+    eng.update_device(t["x0"], t["xr"], t["ur"], u0, f=ft)
+    tape = eng.record_tape()
+    eng.update_device(t["x0"], t["xr"], t["ur"], u0, f=ft)
+    eng.synchronize()
+    st, it = eng.status()
+    _, act = eng.active_set()
+    return dict(eng=eng, t=t, tape=tape, force=ft, st=st, it=it, act=act)
+
+
+def _model(eng):
+    return np.array(list(eng.cfg.Qd)), np.array(list(eng.cfg.Rd)), float(eng.cfg.mass)
+
+
+def _full_step(eng, b, f):
+    u, X, U, st, it = eng.update(b["x0"], b["xr"], b["ur"], f=f, raise_on_status=False, full=True)
+    sw, act = eng.active_set()
+    return u, X, U, st, it, sw, act
+
+
+def test_set_model_is_a_fresh_handle_with_those_values(ndp):
+    """B = 1024 mixed with a force, three ticks; then set_model(Qd', Rd', m') on the live engine against an engine CREATED with those values
+    and given the same iterate and kept sets: u0, X, U, status, iteration word and kept set of the next two steps bit-equal.  Every
+    refusal leaves the next step bit-equal to what it would have been, and the iterate is the same memory with the same contents."""
+    B, N = 1024, 20
+    b = synth.make_batch(B, seed=synth.SEED0 + 90, **MIXED)
+    f = np.random.default_rng(20).normal(0.0, 0.3, (B, N + 1, 3)).astype(np.float32)
+    eng = ndp.BatchedNMPC(B, disturbance=True, load_mlp=False)
+    eng.reset(b["xr"], b["ur"])
+    for _ in range(3):
+        _full_step(eng, b, f)
+    Qd0, Rd0, m0 = _model(eng)
+    rng = np.random.default_rng(21)
+    Qd1, Rd1, m1 = Qd0 * rng.uniform(0.5, 2.0, 10), Rd0 * rng.uniform(0.5, 2.0, 4), m0 * 1.1
+    ptr0 = [v.data_ptr() for v in eng.device_iterate()]
+    X0, U0 = eng.get_iterate()
+    _, A0 = eng.active_set()
+    # refusals: nothing changes
+    for kw, what in ((dict(Qd=np.where(np.arange(10) == 2, -1.0, Qd1)), "Qd"), (dict(Rd=np.where(np.arange(4) == 1, 0.0, Rd1)), "Rd"),
+                     (dict(Qd=np.where(np.arange(10) == 0, np.nan, Qd1)), "Qd"), (dict(Rd=Rd1 * 1e6), "as_gamma"),
+                     (dict(Qd=Qd1, mass=float("inf")), "mass")):
+        with pytest.raises(ndp.NdpError, match=r"\(-2\).*" + what):
+            eng.set_model(**kw)
+        q, r, m = _model(eng)
+        assert np.array_equal(q, Qd0) and np.array_equal(r, Rd0) and m == m0
+    ref0 = ndp.BatchedNMPC(B, disturbance=True, load_mlp=False)
+    ref0.reset(b["xr"], b["ur"])
+    ref0.set_iterate(X0, U0)
+    ref0.set_active_set(A0)
+    a, c = _full_step(eng, b, f), _full_step(ref0, b, f)
+    ref0.close()
+    for x, y in zip(a, c):
+        assert np.array_equal(x, y, equal_nan=True)
+    # the change itself
+    X1, U1 = eng.get_iterate()
+    _, A1 = eng.active_set()
+    eng.set_model(Qd=Qd1, Rd=Rd1, mass=m1)
+    q, r, m = _model(eng)
+    assert np.array_equal(q, Qd1) and np.array_equal(r, Rd1) and m == m1
+    assert [v.data_ptr() for v in eng.device_iterate()] == ptr0
+    X1b, U1b = eng.get_iterate()
+    assert np.array_equal(X1, X1b) and np.array_equal(U1, U1b) and np.array_equal(A1, eng.active_set()[1])
+    ref = ndp.BatchedNMPC(B, disturbance=True, load_mlp=False, Qd=list(Qd1), Rd=list(Rd1), mass=m1)
+    ref.reset(b["xr"], b["ur"])
+    ref.set_iterate(X1, U1)
+    ref.set_active_set(A1)
+    for _ in range(2):
+        a, c = _full_step(eng, b, f), _full_step(ref, b, f)
+        for x, y in zip(a, c):
+            assert np.array_equal(x, y, equal_nan=True)
+    assert (a[3] == 0).sum() >= 900
+    # ... and it is a different controller from the old one
+    old = ndp.BatchedNMPC(B, disturbance=True, load_mlp=False)
+    old.reset(b["xr"], b["ur"])
+    old.set_iterate(X1, U1)
+    old.set_active_set(A1)
+    eng.set_iterate(X1, U1)
+    eng.set_active_set(A1)
+    assert not np.array_equal(_full_step(eng, b, f)[0], _full_step(old, b, f)[0])
+    # keep-forms: None / None / None changes nothing
+    eng.set_model()
+    assert np.array_equal(_model(eng)[0], Qd1) and _model(eng)[2] == m1
+    for e in (eng, ref, old):
+        e.close()
+
+
+@pytest.mark.parametrize("N", [20, 13])
+def test_device_model_gradient_matches_the_dense_reference(ndp, oracle, N):
+    """B = 64 mixed with a force, random (gu0, gX, gU): 12 seeded status-0 set finishes within 1e-9 of max(1, |g|max) of model_grad_ref at
+    the pre-step iterate and the step's final set (N = 13: the run-time-horizon kernel); gmodel[6] and [15] exactly 0; the four existing
+    outputs, the recompute's u0 and status bit-equal to ndp_step_vjp_device's; a failed step: NaN in all 16."""
+    B = 64
+    b = synth.make_batch(B, N=N, seed=synth.SEED0 + 91, **MIXED)
+    b["x0"][7, 3] = np.nan
+    f = np.random.default_rng(22).normal(0.0, 0.3, (B, N + 1, 3)).astype(np.float32)
+    r = _recorded_step(ndp, b, f=f)
+    rng = np.random.default_rng(23)
+    gu0, gX, gU = rng.normal(size=(B, 4)), rng.normal(size=(B, N + 1, 10)), rng.normal(size=(B, N, 4))
+    args = (r["eng"], r["t"]["x0"], r["t"]["xr"], r["t"]["ur"], r["tape"])
+    out = _vjp(*args, f=r["force"], gu0=_t(gu0), gX=_t(gX), gU=_t(gU))
+    plain = _vjp(*args, f=r["force"], gu0=_t(gu0), gX=_t(gX), gU=_t(gU), model=False)
+    Xl, Ul, _ = (v.cpu().numpy() for v in r["tape"])
+    r["eng"].close()
+    for x, y in zip(out[:6], plain):
+        assert np.array_equal(x, y, equal_nan=True)
+    gm = out[6]
+    assert r["st"][7] != 0 and np.isnan(gm[r["st"] != 0]).all()
+    ok = r["st"] == 0
+    assert np.isfinite(gm[ok]).all() and not gm[ok][:, 6].any() and not gm[ok][:, 15].any()
+    idx = np.flatnonzero(ok & ((r["it"] & 0xffff) == 0))
+    assert idx.size >= 40
+    cfg = oracle.default_cfg(N=N, use_fd=True)
+    worst = 0.0
+    for i in np.random.default_rng(24).choice(idx, 12, replace=False):
+        ref, gm2 = model_grad_ref(oracle, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f[i].astype(np.float64), Xl[i], Ul[i], r["act"][i],
+                                  gu0[i], gX[i], gU[i])
+        s = scale(ref)
+        assert abs(ref[14] - gm2) <= 1e-9 * s
+        worst = max(worst, np.max(np.abs(gm[i] - ref)) / s)
+        assert np.max(np.abs(gm[i] - ref)) <= 1e-9 * s, (i, np.max(np.abs(gm[i] - ref)) / s)
+    print(f"N={N}: worst distance from the dense reference {worst:.3e}")
+
+
+def test_device_finite_differences_through_set_model(ndp):
+    """L = gu0.u0 + gX.X + gU.U of the step on ONE engine: central differences in Qd[j] (a few j from each group), Rd[i] and the mass, each
+    probe installed with set_model and run from the same iterate and kept set, against the summed-up gmodel column on the instances whose
+    set and iteration word do not change, within 1e-6: setter and gradient mean the same thing."""
+    B, N = 256, 20
+    b = synth.make_batch(B, seed=synth.SEED0 + 92, **MIXED)
+    f = np.random.default_rng(25).normal(0.0, 0.4, (B, N + 1, 3)).astype(np.float32)
+    r = _recorded_step(ndp, b, f=f)
+    eng = r["eng"]
+    rng = np.random.default_rng(26)
+    gu0, gX, gU = rng.normal(size=(B, 4)), rng.normal(size=(B, N + 1, 10)), rng.normal(size=(B, N, 4))
+    gm = _vjp(eng, r["t"]["x0"], r["t"]["xr"], r["t"]["ur"], r["tape"], f=r["force"], gu0=_t(gu0), gX=_t(gX), gU=_t(gU))[6]
+    X0, U0, A0 = (v.cpu().numpy() for v in r["tape"])
+    Qd0, Rd0, m0 = _model(eng)
+    stable = (r["st"] == 0) & ((r["it"] & 0xffff) == 0)
+    fds = []
+    for col in (0, 2, 4, 5, 7, 9, 10, 13, 14):
+        base = Qd0[col] if col < 10 else Rd0[col - 10] if col < 14 else m0
+        h = 1e-5 * base
+        L = []
+        for sgn in (1.0, -1.0):
+            q, rd = Qd0.copy(), Rd0.copy()
+            if col < 10:
+                q[col] += sgn * h
+            elif col < 14:
+                rd[col - 10] += sgn * h
+            eng.set_model(Qd=q, Rd=rd, mass=m0 + sgn * h if col == 14 else m0)
+            eng.set_iterate(X0, U0)
+            eng.set_active_set(A0)
+            u, X, U, st, it = eng.update(b["x0"], b["xr"], b["ur"], f=f, raise_on_status=False, full=True)
+            _, A = eng.active_set()
+            stable &= (st == 0) & ((it & 0xffff) == 0) & (A == r["act"]).all(axis=(1, 2))
+            L.append((u * gu0).sum(axis=1) + (X * gX).sum(axis=(1, 2)) + (U * gU).sum(axis=(1, 2)))
+        fds.append((col, (L[0] - L[1]) / (2 * h)))
+    eng.close()
+    assert stable.sum() >= 150
+    for col, fd in fds:
+        got = gm[:, col]
+        err = np.abs(fd - got)[stable] / np.maximum(1.0, np.abs(got[stable]))
+        print(f"column {col}: worst finite-difference distance {err.max():.3e}, |g|max {np.abs(got[stable]).max():.3e}")
+        assert err.max() <= 1e-6, (col, err.max())
+        assert np.abs(got[stable]).max() > 1e-6            # (a gradient that is there to be compared)
+
+
+def test_state_and_tape_untouched_and_repeatable(ndp):
+    """The call leaves the engine's iterate, kept sets and sensitivity buffers bit-unchanged, and the tape too; two calls on one tape give
+    bit-identical outputs, gmodel included."""
+    B = 256
+    b = synth.make_batch(B, seed=synth.SEED0 + 93, **MIXED)
+    f = np.random.default_rng(27).normal(0.0, 0.3, (B, 21, 3)).astype(np.float32)
+    r = _recorded_step(ndp, b, f=f)
+    eng = r["eng"]
+    eng.enable_sensitivity(1)
+    eng.enable_param_sensitivity()
+    import torch
+    u0 = torch.empty(B, 4, dtype=torch.float64, device=_dev())
+    tape = eng.record_tape()
+    eng.update_device(r["t"]["x0"], r["t"]["xr"], r["t"]["ur"], u0, f=r["force"])
+    eng.synchronize()
+    state = lambda: [v.cpu().numpy().copy() for v in eng.device_iterate()] + [eng.active_set()[1], *eng.sensitivity()[:1],  # noqa: E731
+                                                                             *eng.param_sensitivity()]
+    before = state()
+    tape0 = [v.cpu().numpy().copy() for v in tape]
+    gu0 = _t(np.random.default_rng(28).normal(size=(B, 4)))
+    gX = _t(np.random.default_rng(29).normal(size=(B, 21, 10)))
+    a = _vjp(eng, r["t"]["x0"], r["t"]["xr"], r["t"]["ur"], tape, f=r["force"], gu0=gu0, gX=gX)
+    c = _vjp(eng, r["t"]["x0"], r["t"]["xr"], r["t"]["ur"], tape, f=r["force"], gu0=gu0, gX=gX)
+    after = state()
+    eng.close()
+    for x, y in zip(before, after):
+        assert np.array_equal(x, y, equal_nan=True)
+    for x, y in zip(tape0, tape):
+        assert np.array_equal(x, y.cpu().numpy())
+    for x, y in zip(a, c):
+        assert np.array_equal(x, y, equal_nan=True)
+
+
+def test_refusals_name_their_reason_and_launch_nothing(ndp):
+    import torch
+    for kw, N, what in ((dict(n_rti=2), 20, "n_rti = 1"), (dict(qp_precision=1), 20, "qp_precision 0"), ({}, 40, "N <= 27")):
+        B = 64
+        b = synth.make_batch(B, N=N, seed=synth.SEED0 + 85, **MIXED)
+        eng = ndp.BatchedNMPC(B, N=N, **kw)
+        eng.reset(b["xr"], b["ur"])
+        tape = eng.record_tape()
+        t = {k: _t(b[k]) for k in ("x0", "xr", "ur")}
+        gm = torch.full((B, 16), -7.0, dtype=torch.float64, device=_dev())
+        with pytest.raises(ndp.NdpError, match=r"ndp_step_vjp_model_device.*\(-2\).*" + what):
+            eng.step_vjp_device(t["x0"], t["xr"], t["ur"], tape, gu0=torch.ones(B, 4, dtype=torch.float64, device=_dev()), gmodel=gm)
+        torch.cuda.synchronize()
+        assert (gm == -7.0).all()
+        eng.close()
+
+
+def test_torch_tunable_layer_matches_the_direct_calls(ndp):
+    """control_step_tunable's gradients of x0, xr, ur, f equal control_step_trajectory's and those of Qd, Rd, mass the sum of the direct
+    call's finite gmodel rows (bit for bit: the same kernel on the same tape); a model changed between forward and backward raises."""
+    import torch
+    from ndp_nmpc_qd_amd.torch_layer import TunableControlStep, control_step_trajectory, control_step_tunable
+    B, N = 256, 20
+    b = synth.make_batch(B, seed=synth.SEED0 + 94, **MIXED)
+    b["x0"][3, 4] = np.nan
+    f = np.random.default_rng(30).normal(0.0, 0.4, (B, N + 1, 3)).astype(np.float32)
+    rng = np.random.default_rng(31)
+    g = [_t(rng.normal(size=s)) for s in ((B, 4), (B, N + 1, 10), (B, N, 4))]
+    side = torch.cuda.Stream(device=_dev())
+    side.wait_stream(torch.cuda.current_stream(_dev()))
+    res = []
+    for tunable in (True, False):
+        eng = ndp.BatchedNMPC(B, disturbance=True, load_mlp=False)
+        eng.reset(b["xr"], b["ur"])
+        x0, xr, ur = (_t(b[k]).requires_grad_(True) for k in ("x0", "xr", "ur"))
+        ft = _t(f, torch.float32).requires_grad_(True)
+        with torch.cuda.stream(side):
+            if tunable:
+                mod = TunableControlStep(eng, learn_mass=True)
+                assert mod.Qd.dtype == torch.float64 and mod.Qd.shape == (10,) and mod.Rd.shape == (4,)
+                tape = eng.record_tape(side)
+                out = mod(x0, xr, ur, f=ft)
+                gr = torch.autograd.grad(out, (x0, xr, ur, ft, mod.Qd, mod.Rd, mod.mass), g)
+                gm = torch.full((B, 16), -7.0, dtype=torch.float64, device=_dev())
+                eng.step_vjp_device(x0.detach(), xr.detach(), ur.detach(), tape, gu0=g[0], gX=g[1], gU=g[2], f=ft.detach(), gmodel=gm,
+                                    stream=side)
+            else:
+                out = control_step_trajectory(eng, x0, xr, ur, f=ft)
+                gr = torch.autograd.grad(out, (x0, xr, ur, ft), g)
+        side.synchronize()
+        res.append([v.detach().cpu().numpy() for v in gr])
+        if tunable:
+            gm = gm.cpu().numpy()
+            st, _ = eng.status()
+            # a second forward with another model, then the first graph's backward: refused
+            out2 = control_step_tunable(eng, x0, xr, ur, mod.Qd, mod.Rd, mass=mod.mass, f=ft)
+            with torch.no_grad():
+                mod.Qd[0] *= 1.5
+            control_step_tunable(eng, x0, xr, ur, mod.Qd, mod.Rd, mass=mod.mass, f=ft)
+            with pytest.raises(RuntimeError, match="model .* was changed"):
+                torch.autograd.grad(out2, (mod.Rd,), g)
+        eng.close()
+    for a, c in zip(res[0][:4], res[1]):
+        assert np.array_equal(a, c, equal_nan=True)
+    assert st[3] != 0 and np.isnan(gm[3]).all()
+    fin = np.isfinite(gm).all(axis=1)
+    assert fin.sum() >= 200 and np.array_equal(fin, st == 0)
+    tot = _t(np.where(fin[:, None], gm, 0.0)).sum(dim=0).cpu().numpy()
+    for got, want in ((res[0][4], tot[:10]), (res[0][5], tot[10:14]), (res[0][6], tot[14])):    # (the same sum, up to its order)
+        assert np.allclose(got, want, rtol=1e-12, atol=0.0)
+    assert np.isfinite(tot).all() and np.abs(tot[:6]).min() > 0
+
+
+def test_training_the_cost_weights_by_gradient_descent_with_a_line_search(ndp):
+    """Targets u0* from an engine with Qd*; start from a perturbed Qd; five steps of gradient descent on |u0 - u0*|^2 with a backtracking
+    line search (halving from t0 = |Qd| / |g|, at most 30 halvings): every step is accepted within the cap and lowers the loss.  No learning
+    rate or final loss is asserted: a wrong sign or scale of the gradient fails the search.  The iterate is restored before every evaluation,
+    and set_model keeps it (the same memory, the same contents)."""
+    import torch
+    from ndp_nmpc_qd_amd.torch_layer import control_step_tunable
+    B = 256
+    b = synth.make_batch(B, seed=synth.SEED0 + 95, **MIXED)
+    eng = ndp.BatchedNMPC(B)
+    eng.reset(b["xr"], b["ur"])
+    X0, U0 = eng.get_iterate()
+    x0, xr, ur = (_t(b[k]) for k in ("x0", "xr", "ur"))
+    Qs, Rd, _ = _model(eng)
+    Rd_t = torch.tensor(Rd, dtype=torch.float64)
+
+    def evaluate(q):
+        eng.set_iterate(X0, U0)
+        u0 = control_step_tunable(eng, x0, xr, ur, q, Rd_t)[0]
+        ok = torch.isfinite(u0).all(dim=1)
+        return u0, ok
+
+    with torch.no_grad():
+        u_star, ok_star = evaluate(torch.tensor(Qs, dtype=torch.float64))
+    scale_q = np.where(np.arange(10) == 6, 1.0, np.random.default_rng(32).uniform(0.4, 2.5, 10))
+    q = torch.tensor(Qs * scale_q, dtype=torch.float64, requires_grad=True)
+
+    def loss_of(qv):
+        u0, ok = evaluate(qv)
+        return ((u0 - u_star)[ok & ok_star] ** 2).sum()
+
+    ptr = [v.data_ptr() for v in eng.device_iterate()]
+    losses = []
+    for step in range(5):
+        loss = loss_of(q)
+        (gq,) = torch.autograd.grad(loss, (q,))
+        assert torch.isfinite(gq).all() and gq.abs().max() > 0
+        t = float(q.detach().norm() / gq.norm())
+        for halvings in range(31):
+            cand = (q.detach() - t * gq)
+            if (cand >= 0).all():
+                with torch.no_grad():
+                    new = float(loss_of(cand))
+                if new < float(loss.detach()):
+                    break
+            t *= 0.5
+        else:
+            raise AssertionError(f"step {step}: no decrease within 30 halvings (loss {float(loss):.6e})")
+        losses.append((float(loss), new, halvings))
+        q = cand.clone().requires_grad_(True)
+    assert [v.data_ptr() for v in eng.device_iterate()] == ptr
+    eng.close()
+    print("cost-weight training (loss before, after, halvings):", [("%.4e" % a, "%.4e" % c, h) for a, c, h in losses])
+    assert all(c < a for a, c, _ in losses) and losses[0][0] > 0
