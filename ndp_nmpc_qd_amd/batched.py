@@ -468,20 +468,22 @@ class BatchedNMPC:
         self._check(self._lib.ndp_get_sens(self._h, _lib.ptr(du0), _lib.ptr(dU), _lib.ptr(dX)), "ndp_get_sens")
         return du0, dU, dX
 
+    def _device_views(self, *views):
+        """CUDA tensor views (no copy) of the handle's buffers: views = (C getter, shape[, typestr; float64 without]); None for a buffer
+        that is not there."""
+        import torch
+        from .dist import _DevMem
+        dev = torch.device("cuda", self.cfg.device)
+        ptrs = [(fn(self._h), rest) for fn, *rest in views]
+        return tuple(torch.as_tensor(_DevMem(ptr, *rest), device=dev) if ptr else None for ptr, rest in ptrs)
+
     def device_sensitivity(self):
         """The device buffers as CUDA tensor views (no copy): (du0_dx0 [B,4,10], dU_dx0 [B,N,4,10] or None, dX_dx0 [B,N+1,10,10] or
         None), float64.  Valid once the step's stream has reached them; the next step overwrites them."""
-        import torch
-        from .dist import _DevMem
         if self.sensitivity_level < 1:
             raise NdpError("sensitivities are not enabled (enable_sensitivity)")
-        dev = torch.device("cuda", self.cfg.device)
-        out = []
-        for fn, shape in ((self._lib.ndp_device_sens_u0, (self.B, 4, 10)), (self._lib.ndp_device_sens_u, (self.B, self.N, 4, 10)),
-                          (self._lib.ndp_device_sens_x, (self.B, self.N + 1, 10, 10))):
-            ptr = fn(self._h)
-            out.append(torch.as_tensor(_DevMem(ptr, shape), device=dev) if ptr else None)
-        return tuple(out)
+        return self._device_views((self._lib.ndp_device_sens_u0, (self.B, 4, 10)), (self._lib.ndp_device_sens_u, (self.B, self.N, 4, 10)),
+                                  (self._lib.ndp_device_sens_x, (self.B, self.N + 1, 10, 10)))
 
     def enable_param_sensitivity(self, on=True):
         """Every later step also writes the derivative of its QP with respect to xr, ur and the force f (ndp_sens_params_enable;
@@ -507,16 +509,10 @@ class BatchedNMPC:
     def device_param_sensitivity(self):
         """The device buffers as CUDA tensor views (no copy): (du0_dxr [B,4,N+1,10], du0_dur [B,4,N,4], du0_df [B,4,N+1,3]), float64.
         Valid once the step's stream has reached them; the next step overwrites them."""
-        import torch
-        from .dist import _DevMem
         if not self.param_sensitivity_enabled:
             raise NdpError("parameter sensitivities are not enabled (enable_param_sensitivity)")
-        dev = torch.device("cuda", self.cfg.device)
-        out = []
-        for fn, shape in ((self._lib.ndp_device_sens_xr, (self.B, 4, self.N + 1, 10)), (self._lib.ndp_device_sens_ur, (self.B, 4, self.N, 4)),
-                          (self._lib.ndp_device_sens_f, (self.B, 4, self.N + 1, 3))):
-            out.append(torch.as_tensor(_DevMem(fn(self._h), shape), device=dev))
-        return tuple(out)
+        return self._device_views((self._lib.ndp_device_sens_xr, (self.B, 4, self.N + 1, 10)), (self._lib.ndp_device_sens_ur, (self.B, 4, self.N, 4)),
+                                  (self._lib.ndp_device_sens_f, (self.B, 4, self.N + 1, 3)))
 
     # ------------------------------------------------------------------ adjoint of the control step (reverse mode)
     def record_tape(self, stream=None):
@@ -526,16 +522,14 @@ class BatchedNMPC:
         tape on the stream the step will run on, before it.  torch's default stream cannot be named through the C-ABI (a NULL stream is
         the engine's own), so there the engine's work is waited for first and the clones after."""
         import torch
-        from .dist import _DevMem
-        dev = torch.device("cuda", self.cfg.device)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        s = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.cfg.device))
         default = s.cuda_stream == 0
         if default:
             self.synchronize()
-        views = ((self._lib.ndp_device_iterate_x, (self.B, self.N + 1, 10), "<f8"), (self._lib.ndp_device_iterate_u, (self.B, self.N, 4), "<f8"),
-                 (self._lib.ndp_device_active_set, (self.B, self.N, 4), "|i1"))
         with torch.cuda.stream(s):
-            tape = tuple(torch.as_tensor(_DevMem(fn(self._h), shape, ts), device=dev).clone() for fn, shape, ts in views)
+            tape = tuple(v.clone() for v in self._device_views(
+                (self._lib.ndp_device_iterate_x, (self.B, self.N + 1, 10)), (self._lib.ndp_device_iterate_u, (self.B, self.N, 4)),
+                (self._lib.ndp_device_active_set, (self.B, self.N, 4), "|i1")))
         if default:
             s.synchronize()
         return tape
@@ -557,22 +551,17 @@ class BatchedNMPC:
             torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
         d = self._dptr
         X, U, A = tape
-        if gmodel is not None:
-            self._check(self._lib.ndp_step_vjp_model_device(
-                self._h, d(x0, torch.float64, (B, 10)), d(xr, torch.float64, (B, N + 1, 10)), d(ur, torch.float64, (B, N, 4)),
+        args = [d(x0, torch.float64, (B, 10)), d(xr, torch.float64, (B, N + 1, 10)), d(ur, torch.float64, (B, N, 4)),
                 d(f, torch.float32, (B, N + 1, 3)), d(X, torch.float64, (B, N + 1, 10)), d(U, torch.float64, (B, N, 4)),
                 d(A, torch.int8, (B, N, 4)), d(gu0, torch.float64, (B, 4)), d(gX, torch.float64, (B, N + 1, 10)),
                 d(gU, torch.float64, (B, N, 4)), d(gx0, torch.float64, (B, 10)), d(gxr, torch.float64, (B, N + 1, 10)),
-                d(gur, torch.float64, (B, N, 4)), d(gf, torch.float64, (B, N + 1, 3)), d(gmodel, torch.float64, (B, 16)),
-                d(u0_check, torch.float64, (B, 4)), d(status_check, torch.int32, (B,)), self._stream(stream)), "ndp_step_vjp_model_device")
-            return
-        self._check(self._lib.ndp_step_vjp_device(
-            self._h, d(x0, torch.float64, (B, 10)), d(xr, torch.float64, (B, N + 1, 10)), d(ur, torch.float64, (B, N, 4)),
-            d(f, torch.float32, (B, N + 1, 3)), d(X, torch.float64, (B, N + 1, 10)), d(U, torch.float64, (B, N, 4)),
-            d(A, torch.int8, (B, N, 4)), d(gu0, torch.float64, (B, 4)), d(gX, torch.float64, (B, N + 1, 10)),
-            d(gU, torch.float64, (B, N, 4)), d(gx0, torch.float64, (B, 10)), d(gxr, torch.float64, (B, N + 1, 10)),
-            d(gur, torch.float64, (B, N, 4)), d(gf, torch.float64, (B, N + 1, 3)), d(u0_check, torch.float64, (B, 4)),
-            d(status_check, torch.int32, (B,)), self._stream(stream)), "ndp_step_vjp_device")
+                d(gur, torch.float64, (B, N, 4)), d(gf, torch.float64, (B, N + 1, 3)), d(u0_check, torch.float64, (B, 4)),
+                d(status_check, torch.int32, (B,)), self._stream(stream)]
+        name = "ndp_step_vjp_device"
+        if gmodel is not None:
+            args.insert(14, d(gmodel, torch.float64, (B, 16)))         # (behind gf)
+            name = "ndp_step_vjp_model_device"
+        self._check(getattr(self._lib, name)(self._h, *args), name)
 
     # ------------------------------------------------------------------ backward pass of the downwash network
     def _other_ptr(self, other, other_index):

@@ -3641,6 +3641,21 @@ void *ndp_device_iterate_u(ndp_handle *h) { return h ? h->dU : nullptr; }
 void *ndp_device_force(ndp_handle *h) { return h ? h->dForce : nullptr; }
 int ndp_work_queue_enabled(ndp_handle *h) { return h ? (int)h->use_queue : -1; }
 
+// ---- the sensitivity buffers: created on enabling, NaN until a step has written them
+static int nan_buffer(ndp_handle *h, double *&p, size_t n)
+{
+    if (p) return 0;
+    NDP_HIP(h, hipMalloc((void **)&p, n * 8));
+    NDP_HIP(h, hipMemsetAsync(p, 0xff, n * 8, h->stream));
+    return 0;
+}
+static void drop_buffer(double *&p) { if (p) (void)hipFree(p); p = nullptr; }
+static int copy_out(ndp_handle *h, double *dst, const double *src, size_t n)
+{
+    if (dst) NDP_HIP(h, hipMemcpy(dst, src, n * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // ---- initial-state sensitivities (rti_sens_kernel, RtiWave::sens_out)
 int ndp_sens_enable(ndp_handle *h, int level)
 {
@@ -3658,18 +3673,10 @@ int ndp_sens_enable(ndp_handle *h, int level)
     if (rc) return rc;
     const size_t B = h->cfg.batch, N = h->cfg.N;
     const size_t n0 = B * (size_t)sens_u0_pitch(), nu = B * (size_t)sens_u_pitch((int)N), nx = B * (size_t)sens_x_pitch((int)N);
-    auto drop = [](double *&p) { if (p) (void)hipFree(p); p = nullptr; };
-    if (level < 2) { drop(h->dSensU); drop(h->dSensX); }
-    if (level == 0) { drop(h->dSensU0); drop(h->dPSensXr); drop(h->dPSensUr); drop(h->dPSensF); h->sens_level = 0; return 0; }
-    // NaN until a step has written them
-    auto get = [&](double *&p, size_t n) -> int {
-        if (p) return 0;
-        NDP_HIP(h, hipMalloc((void **)&p, n * 8));
-        NDP_HIP(h, hipMemsetAsync(p, 0xff, n * 8, h->stream));
-        return 0;
-    };
-    if ((rc = get(h->dSensU0, n0))) return rc;
-    if (level == 2 && ((rc = get(h->dSensU, nu)) || (rc = get(h->dSensX, nx)))) return rc;
+    if (level < 2) { drop_buffer(h->dSensU); drop_buffer(h->dSensX); }
+    if (level == 0) { for (double **p : {&h->dSensU0, &h->dPSensXr, &h->dPSensUr, &h->dPSensF}) drop_buffer(*p); h->sens_level = 0; return 0; }
+    if ((rc = nan_buffer(h, h->dSensU0, n0))) return rc;
+    if (level == 2 && ((rc = nan_buffer(h, h->dSensU, nu)) || (rc = nan_buffer(h, h->dSensX, nx)))) return rc;
     const int lds_bytes = (int)((size_t)h->lds_per_wave * sizeof(double) * h->waves);
     for (const RtiKern &k : k_rti)
         if (k.sens) NDP_HIP(h, hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
@@ -3690,10 +3697,9 @@ int ndp_get_sens(ndp_handle *h, double *du0_dx0, double *dU_dx0, double *dX_dx0)
     int rc = wait_all(h);
     if (rc) return rc;
     const size_t B = h->cfg.batch;
-    if (du0_dx0) NDP_HIP(h, hipMemcpy(du0_dx0, h->dSensU0, B * sens_u0_pitch() * 8, hipMemcpyDeviceToHost));
-    if (dU_dx0) NDP_HIP(h, hipMemcpy(dU_dx0, h->dSensU, B * sens_u_pitch(h->cfg.N) * 8, hipMemcpyDeviceToHost));
-    if (dX_dx0) NDP_HIP(h, hipMemcpy(dX_dx0, h->dSensX, B * sens_x_pitch(h->cfg.N) * 8, hipMemcpyDeviceToHost));
-    return 0;
+    if ((rc = copy_out(h, du0_dx0, h->dSensU0, B * sens_u0_pitch()))) return rc;
+    if ((rc = copy_out(h, dU_dx0, h->dSensU, B * sens_u_pitch(h->cfg.N)))) return rc;
+    return copy_out(h, dX_dx0, h->dSensX, B * sens_x_pitch(h->cfg.N));
 }
 
 void *ndp_device_sens_u0(ndp_handle *h) { return h ? h->dSensU0 : nullptr; }
@@ -3712,22 +3718,15 @@ int ndp_sens_params_enable(ndp_handle *h, int on)
     NDP_HIP(h, hipSetDevice(h->cfg.device));
     int rc = wait_all(h);                 // (steps in flight may still write the buffers)
     if (rc) return rc;
-    double **bufs[3] = {&h->dPSensXr, &h->dPSensUr, &h->dPSensF};
     if (!on) {
-        for (double **p : bufs) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
+        for (double **p : {&h->dPSensXr, &h->dPSensUr, &h->dPSensF}) drop_buffer(*p);
         return 0;
     }
     const size_t B = h->cfg.batch;
     const int N = h->cfg.N;
-    const size_t n[3] = {B * (size_t)psens_xr_pitch(N), B * (size_t)psens_ur_pitch(N), B * (size_t)psens_f_pitch(N)};
-    for (int i = 0; i < 3; ++i) {         // NaN until a step has written them
-        if (*bufs[i]) continue;
-        NDP_HIP(h, hipMalloc((void **)bufs[i], n[i] * 8));
-        NDP_HIP(h, hipMemsetAsync(*bufs[i], 0xff, n[i] * 8, h->stream));
-    }
+    if ((rc = nan_buffer(h, h->dPSensXr, B * (size_t)psens_xr_pitch(N))) || (rc = nan_buffer(h, h->dPSensUr, B * (size_t)psens_ur_pitch(N))) ||
+        (rc = nan_buffer(h, h->dPSensF, B * (size_t)psens_f_pitch(N))))
+        return rc;
     NDP_HIP(h, hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -3744,10 +3743,9 @@ int ndp_get_sens_params(ndp_handle *h, double *du0_dxr, double *du0_dur, double 
     if (rc) return rc;
     const size_t B = h->cfg.batch;
     const int N = h->cfg.N;
-    if (du0_dxr) NDP_HIP(h, hipMemcpy(du0_dxr, h->dPSensXr, B * psens_xr_pitch(N) * 8, hipMemcpyDeviceToHost));
-    if (du0_dur) NDP_HIP(h, hipMemcpy(du0_dur, h->dPSensUr, B * psens_ur_pitch(N) * 8, hipMemcpyDeviceToHost));
-    if (du0_df) NDP_HIP(h, hipMemcpy(du0_df, h->dPSensF, B * psens_f_pitch(N) * 8, hipMemcpyDeviceToHost));
-    return 0;
+    if ((rc = copy_out(h, du0_dxr, h->dPSensXr, B * psens_xr_pitch(N)))) return rc;
+    if ((rc = copy_out(h, du0_dur, h->dPSensUr, B * psens_ur_pitch(N)))) return rc;
+    return copy_out(h, du0_df, h->dPSensF, B * psens_f_pitch(N));
 }
 
 void *ndp_device_sens_xr(ndp_handle *h) { return h ? h->dPSensXr : nullptr; }

@@ -27,6 +27,37 @@ by the same adjoint (BatchedNMPC.set_model, step_vjp_device with gmodel).
 import torch
 
 
+def _cuda_stream(t):
+    """(stream, is torch's default stream) for a tensor's device; (None, False) for CPU tensors (stub engines in the tests)."""
+    if not t.is_cuda:
+        return None, False
+    s = torch.cuda.current_stream(t.device)
+    return s, s.cuda_stream == 0
+
+
+def _taped_step(engine, stream, default, x0, xr, ur, **kw):
+    """The forward of the adjoint Functions: the tape of the step about to run, the step (update_device with kw) on `stream`, and clones of
+    the new iterate ordered behind it (the next step overwrites it).  Returns (tape, u0, X, U)."""
+    tape = engine.record_tape(stream)
+    u0 = torch.empty((x0.shape[0], 4), dtype=x0.dtype, device=x0.device)
+    engine.update_device(x0, xr, ur, u0, stream=stream, **kw)
+    if default:                            # torch's default stream: the step went on the engine's own (the C-ABI's NULL)
+        engine.synchronize()
+    X, U = (t.clone() for t in engine.device_iterate())
+    return tape, u0, X, U
+
+
+def _taped_step_vjp(engine, x0, xr, ur, tape, force, upstream, need, stream, **kw):
+    """The backward of the adjoint Functions: step_vjp_device (with kw) for the float64 casts of upstream = (g_u0, g_X, g_U) into newly
+    allocated outputs.  need: which of (gx0, gxr, gur, gf) to compute; returns those four, None where not needed.  No synchronisation."""
+    B, N = x0.shape[0], xr.shape[1] - 1
+    gu0, gX, gU = (None if g is None else g.to(torch.float64).contiguous() for g in upstream)
+    gx0, gxr, gur, gf = (torch.empty(*s, dtype=torch.float64, device=x0.device) if n else None
+                         for n, s in zip(need, ((B, 10), (B, N + 1, 10), (B, N, 4), (B, N + 1, 3))))
+    engine.step_vjp_device(x0, xr, ur, tape, gu0=gu0, gX=gX, gU=gU, f=force, gx0=gx0, gxr=gxr, gur=gur, gf=gf, stream=stream, **kw)
+    return gx0, gxr, gur, gf
+
+
 class ControlStepFunction(torch.autograd.Function):
     """forward(x0, engine, xr, ur, f, other, ego_xy) -> u0 [B,4] float64; backward: grad_x0 = K0' grad_u0 and, when the engine has parameter
     sensitivities on, the gradients of xr, ur and f (batched contractions on x0's device).  x0, xr, ur (and f / other / ego_xy when given)
@@ -45,10 +76,9 @@ class ControlStepFunction(torch.autograd.Function):
         x0 = x0.detach().contiguous()
         det = lambda t: t.detach() if isinstance(t, torch.Tensor) else t  # noqa: E731
         u0 = torch.empty((x0.shape[0], 4), dtype=x0.dtype, device=x0.device)
-        stream = torch.cuda.current_stream(x0.device) if x0.is_cuda else None
         # torch's default stream cannot be named through the C-ABI (a NULL stream is the engine's own): there the step runs on the
         # engine's stream, so the inputs are waited for in front of it and the step behind it
-        default = stream is not None and stream.cuda_stream == 0
+        stream, default = _cuda_stream(x0)
         if default:
             stream.synchronize()
         engine.update_device(x0, det(xr), det(ur), u0, f=det(f), other=other, ego_xy=ego_xy, stream=stream)
@@ -96,13 +126,7 @@ class ControlStepTrajectoryFunction(torch.autograd.Function):
                                  "(detach it, or leave it out of the graph)")
         det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t  # noqa: E731
         x0, xr, ur, fd = det(x0), det(xr), det(ur), det(f)
-        stream = torch.cuda.current_stream(x0.device)
-        tape = engine.record_tape(stream)
-        u0 = torch.empty((x0.shape[0], 4), dtype=x0.dtype, device=x0.device)
-        engine.update_device(x0, xr, ur, u0, f=fd, other=other, ego_xy=ego_xy, stream=stream)
-        if stream.cuda_stream == 0:        # torch's default stream: the step went on the engine's own (the C-ABI's NULL)
-            engine.synchronize()
-        X, U = (t.clone() for t in engine.device_iterate())      # (ordered behind the step: the next step overwrites them)
+        tape, u0, X, U = _taped_step(engine, *_cuda_stream(x0), x0, xr, ur, f=fd, other=other, ego_xy=ego_xy)
         force = engine.device_force().clone() if other is not None else fd
         ctx.engine = engine
         ctx.f_dtype = f.dtype if isinstance(f, torch.Tensor) else None
@@ -113,20 +137,13 @@ class ControlStepTrajectoryFunction(torch.autograd.Function):
     def backward(ctx, g_u0, g_X, g_U):
         x0, xr, ur, force, *tape = ctx.saved_tensors
         eng = ctx.engine
-        c = lambda g: None if g is None else g.to(torch.float64).contiguous()  # noqa: E731
-        g_u0, g_X, g_U = c(g_u0), c(g_X), c(g_U)
         if g_u0 is None and g_X is None and g_U is None:
             return (None,) * 7
-        z = lambda *s: torch.empty(*s, dtype=torch.float64, device=x0.device)  # noqa: E731
-        B, N = x0.shape[0], xr.shape[1] - 1
         need = ctx.needs_input_grad
-        gx0 = z(B, 10) if need[0] else None
-        gxr = z(B, N + 1, 10) if need[2] else None
-        gur = z(B, N, 4) if need[3] else None
-        gf = z(B, N + 1, 3) if need[4] and ctx.f_dtype is not None else None
-        stream = torch.cuda.current_stream(x0.device)
-        eng.step_vjp_device(x0, xr, ur, tape, gu0=g_u0, gX=g_X, gU=g_U, f=force, gx0=gx0, gxr=gxr, gur=gur, gf=gf, stream=stream)
-        if stream.cuda_stream == 0:
+        stream, default = _cuda_stream(x0)
+        gx0, gxr, gur, gf = _taped_step_vjp(eng, x0, xr, ur, tape, force, (g_u0, g_X, g_U),
+                                            (need[0], need[2], need[3], need[4] and ctx.f_dtype is not None), stream)
+        if default:
             eng.synchronize()
         return (gx0, None, gxr, gur, None if gf is None else gf.to(ctx.f_dtype), None, None)
 
@@ -167,14 +184,6 @@ class ControlStep(torch.nn.Module):
 # What is differentiated: the fp32 network the step ran (its own ReLU masks) with respect to its input rows (other - ego_ref)[..., 0:6] and its
 # 17 859 weights (BatchedNMPC.downwash_vjp_device).  What is held fixed: the r_horiz gate (piecewise constant: ego_xy may not require grad)
 # and, in control_step_ndp, everything the step's adjoint holds fixed -- linearisation point and active set.
-
-def _cuda_stream(t):
-    """(stream, is torch's default stream) for a tensor's device; (None, False) for CPU tensors (stub engines in the tests)."""
-    if not t.is_cuda:
-        return None, False
-    s = torch.cuda.current_stream(t.device)
-    return s, s.cuda_stream == 0
-
 
 def _install_weights(engine, weights, stream):
     """Installs `weights` (float32 CUDA tensor / nn.Parameter of 17 859 in blob order) as the engine's network unless they are the ones
@@ -291,12 +300,7 @@ class ControlStepNDPFunction(torch.autograd.Function):
         if default:
             stream.synchronize()
         ctx.key = _install_weights(engine, weights, stream)
-        tape = engine.record_tape(stream)
-        u0 = torch.empty((x0.shape[0], 4), dtype=x0.dtype, device=x0.device)
-        engine.update_device(x0, xr, ur, u0, other=od, ego_xy=ego_xy, stream=stream, other_index=other_index)
-        if default:
-            engine.synchronize()
-        X, U = (t.clone() for t in engine.device_iterate())
+        tape, u0, X, U = _taped_step(engine, stream, default, x0, xr, ur, other=od, ego_xy=ego_xy, other_index=other_index)
         force = engine.device_force().clone()
         ctx.engine = engine
         ctx.have_w = weights is not None
@@ -313,24 +317,17 @@ class ControlStepNDPFunction(torch.autograd.Function):
         if g_u0 is None and g_X is None and g_U is None:
             return (None,) * 8
         _check_installed(eng, ctx.key, "ControlStepNDPFunction")
-        c = lambda g: None if g is None else g.to(torch.float64).contiguous()  # noqa: E731
-        z = lambda *s: torch.empty(*s, dtype=torch.float64, device=x0.device)  # noqa: E731
         B, N = x0.shape[0], xr.shape[1] - 1
         need = ctx.needs_input_grad
         net_w = ctx.have_w and need[6]
         net = need[2] or need[4] or net_w                    # anything behind the force
-        gx0 = z(B, 10) if need[0] else None
-        gxr = z(B, N + 1, 10) if need[2] else None
-        gur = z(B, N, 4) if need[3] else None
-        gf = z(B, N + 1, 3) if net else None
         stream, default = _cuda_stream(x0)
-        eng.step_vjp_device(x0, xr, ur, (t0, t1, t2), gu0=c(g_u0), gX=c(g_X), gU=c(g_U), f=force, gx0=gx0, gxr=gxr, gur=gur, gf=gf,
-                            stream=stream)
+        gx0, gxr, gur, gf = _taped_step_vjp(eng, x0, xr, ur, (t0, t1, t2), force, (g_u0, g_X, g_U), (need[0], need[2], need[3], net), stream)
         g_other = gw = None
         if net:
             if default:
                 eng.synchronize()
-            gz = z(B, N + 1, 6) if need[2] or need[4] else None
+            gz = torch.empty((B, N + 1, 6), dtype=torch.float64, device=x0.device) if need[2] or need[4] else None
             gw = torch.empty(17859, dtype=torch.float32, device=x0.device) if net_w else None
             eng.downwash_vjp_device(od, xr, gf, ego_xy=ego_xy, other_index=other_index, gz=gz, gw=gw, stream=stream)
         if default:
@@ -404,13 +401,7 @@ class TunableControlStepFunction(torch.autograd.Function):
         det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t  # noqa: E731
         x0, xr, ur, fd = det(x0), det(xr), det(ur), det(f)
         ctx.model = _install_model(engine, Qd, Rd, mass)
-        stream, default = _cuda_stream(x0)
-        tape = engine.record_tape(stream)
-        u0 = torch.empty((x0.shape[0], 4), dtype=x0.dtype, device=x0.device)
-        engine.update_device(x0, xr, ur, u0, f=fd, stream=stream)
-        if default:
-            engine.synchronize()
-        X, U = (t.clone() for t in engine.device_iterate())
+        tape, u0, X, U = _taped_step(engine, *_cuda_stream(x0), x0, xr, ur, f=fd)
         ctx.engine = engine
         ctx.f_dtype = f.dtype if isinstance(f, torch.Tensor) else None
         ctx.like = tuple(None if not isinstance(t, torch.Tensor) else (t.shape, t.dtype, t.device) for t in (Qd, Rd, mass))
@@ -428,18 +419,11 @@ class TunableControlStepFunction(torch.autograd.Function):
             raise RuntimeError("TunableControlStepFunction: the engine's model (Qd, Rd, mass) was changed between this forward and its "
                                "backward (the backward recomputes the step from the engine's model): run the backward before the next "
                                "forward with other values, or set the model back first")
-        c = lambda g: None if g is None else g.to(torch.float64).contiguous()  # noqa: E731
-        z = lambda *s: torch.empty(*s, dtype=torch.float64, device=x0.device)  # noqa: E731
-        B, N = x0.shape[0], xr.shape[1] - 1
         need = ctx.needs_input_grad
-        gx0 = z(B, 10) if need[0] else None
-        gxr = z(B, N + 1, 10) if need[2] else None
-        gur = z(B, N, 4) if need[3] else None
-        gf = z(B, N + 1, 3) if need[7] and ctx.f_dtype is not None else None
-        gm = z(B, 16)
+        gm = torch.empty(x0.shape[0], 16, dtype=torch.float64, device=x0.device)
         stream, default = _cuda_stream(x0)
-        eng.step_vjp_device(x0, xr, ur, (t0, t1, t2), gu0=c(g_u0), gX=c(g_X), gU=c(g_U), f=force, gx0=gx0, gxr=gxr, gur=gur, gf=gf,
-                            gmodel=gm, stream=stream)
+        gx0, gxr, gur, gf = _taped_step_vjp(eng, x0, xr, ur, (t0, t1, t2), force, (g_u0, g_X, g_U),
+                                            (need[0], need[2], need[3], need[7] and ctx.f_dtype is not None), stream, gmodel=gm)
         if default:
             eng.synchronize()
         # a failed step (NaN in its row) contributes nothing: control_step_ndp's convention for the network's weights

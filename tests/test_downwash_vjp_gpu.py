@@ -11,28 +11,12 @@ import pytest
 
 from ndp_nmpc_qd_amd import _lib, mlp_frag, synth
 from tests import mlp_vjp_ref as R
+from tests.deriv_gpu import MIXED, _dev, _t, ndp  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 B, N = 1024, 20
 BAR = 1e-5
-MIXED = dict(pos_sigma=0.5, vel_sigma=1.0, quat_sigma=0.15)
-
-
-@pytest.fixture(scope="module")
-def ndp():
-    import ndp_nmpc_qd_amd
-    return ndp_nmpc_qd_amd
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _t(a, dtype=None):
-    import torch
-    return torch.tensor(np.ascontiguousarray(a), device=_dev(), dtype=dtype)
 
 
 def _case(form, seed, B=B):

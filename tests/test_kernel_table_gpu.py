@@ -6,7 +6,7 @@ names -- ndp_debug_rti_launched says which rows a handle really launched, and th
 they computed with a reference:
   * the oracle's plain-C twin of the active-set iterations (status, sweeps, kept sets identical, X and U within 1e-8);
   * the QP's KKT certificate (tests/kkt_certificate.py): 1e-9 for active-set answers, 3e5 tol for interior-point ones;
-  * the dense fixed-set references of the sensitivities (tests/sens_ref.py, tests/psens_ref.py), 1e-9;
+  * the dense fixed-set references of the sensitivities (tests/fixed_set_ref.py), 1e-9;
   * the oracle's interior-point loop where a row runs that algorithm, or a form the twin does not restate.
 CASES maps every launched row to the case that launches it; UNREACHABLE lists the rows no configuration reaches, with the reason
 tests/test_kernel_table.py checks on the CPU."""
@@ -268,8 +268,7 @@ def test_ragged_batches_write_nothing_past_the_batch(ndp, oracle, N, downwash, r
 def _sens_case(ndp, oracle, b, level, params, fused, **eng_kw):
     """One step of a fresh handle with sensitivities on; every checked instance (40 seeded status-0 active-set instances and 8 with
     pinned inputs) against the dense fixed-set references.  Returns the handle's launched rows."""
-    from tests.psens_ref import psens_ref, scale as pscale
-    from tests.sens_ref import scale, sens_ref
+    from tests.fixed_set_ref import psens_ref, scale, sens_ref
     B, N = b["x0"].shape[0], b["xr"].shape[1] - 1
     eng = ndp.BatchedNMPC(B, N=N, disturbance=fused, **eng_kw)
     eng.reset(b["xr"], b["ur"])
@@ -302,7 +301,7 @@ def _sens_case(ndp, oracle, b, level, params, fused, **eng_kw):
             w = max(w, np.max(np.abs(dU[i] - rU)) / s, np.max(np.abs(dX[i] - rX)) / max(1.0, np.max(np.abs(rX))))
         if params:
             ref = psens_ref(oracle, cfg, b["x0"][i], b["xr"][i], b["ur"][i], fi, Xp[i], Up[i], act[i])
-            sp = max(pscale(r) for r in ref)
+            sp = max(scale(r) for r in ref)
             w = max(w, *(np.max(np.abs(g[i] - r)) / sp for g, r in zip(ps, ref)))
     assert w <= SENS_BAR, w
     return rows

@@ -1,70 +1,19 @@
 """The control step's gradient in its cost weights and the mass (RtiWave::vjp_out<true>, rti_wvjp_kernel) without a GPU: the device's code
-on the host wave emulator (tests/wvjp_emu.cpp) against the dense fixed-set KKT reference (tests/model_grad_ref.py), the scale identity, the
+on the host wave emulator (tests/step_deriv_emu.cpp) against the dense fixed-set KKT reference (tests/fixed_set_ref.py), the scale identity, the
 interior-point finishes beside the existing adjoint's, a failed step, the kernels' ISA and the header / ABI.  The device side:
 tests/test_model_grad_gpu.py."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from ndp_nmpc_qd_amd import synth
-from tests.model_grad_ref import model_grad_ref
-from tests.psens_ref import NU, NX, _system, fixed_of, scale
-from tests.vjp_ref import upstream
+from tests.fixed_set_ref import NU, NX, model_grad_ref, scale, vjp_ref
+from tests.step_deriv_emu import MIXED, _tape, _vjp, step_emu  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-MIXED = dict(pos_sigma=0.5, vel_sigma=1.0, quat_sigma=0.15)
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _lib(tmp_path_factory, name):
-    so = str(tmp_path_factory.mktemp(name) / f"lib{name}.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-shared", "-o", so, os.path.join(HERE, f"{name}.cpp")])
-    return C.CDLL(so)
-
-
-@pytest.fixture(scope="module")
-def wvjp_emu(tmp_path_factory):
-    lib = _lib(tmp_path_factory, "wvjp_emu")
-    lib.wvjp_emu_step.argtypes = [C.c_void_p] * 19
-    return lib
-
-
-@pytest.fixture(scope="module")
-def vjp_emu(tmp_path_factory):
-    lib = _lib(tmp_path_factory, "vjp_emu")
-    lib.vjp_emu_step.argtypes = [C.c_void_p] * 18
-    return lib
-
-
-def _run(lib, cfg, x0, xr, ur, f, X, U, act, gu0=None, gX=None, gU=None, model=True):
-    """One emulated step from the tape (copied) with its adjoint; returns (u0, X, U, st, it, act, gx0, gxr, gur, gf[, gmodel])."""
-    N = cfg.N
-    X, U, act = X.copy(), U.copy(), act.copy()
-    u0 = np.zeros(4)
-    st, it = C.c_int(-1), C.c_int(-1)
-    gx0, gxr, gur, gf = np.full(10, -7.0), np.full((N + 1, 10), -7.0), np.full((N, 4), -7.0), np.full((N + 1, 3), -7.0)
-    gm = np.full(16, -7.0)
-    f32 = None if f is None else np.ascontiguousarray(f, dtype=np.float32)
-    c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
-    gu0, gX, gU = c(gu0), c(gX), c(gU)
-    args = [C.byref(cfg), _p(x0), _p(xr), _p(ur), _p(f32), _p(X), _p(U), _p(u0), C.byref(st), C.byref(it), _p(act),
-            _p(gu0), _p(gX), _p(gU), _p(gx0), _p(gxr), _p(gur), _p(gf)]
-    rc = lib.wvjp_emu_step(*args, _p(gm)) if model else lib.vjp_emu_step(*args)
-    assert rc == 0
-    return (u0, X, U, st.value, it.value, act, gx0, gxr, gur, gf) + ((gm,) if model else ())
-
-
-def _tape(b, i, rng, N):
-    return (b["xr"][i] + 0.01 * rng.normal(size=b["xr"][i].shape), b["ur"][i] + 0.01 * rng.normal(size=b["ur"][i].shape),
-            np.zeros(4 * N, dtype=np.int8))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _same(a, b):
@@ -73,11 +22,11 @@ def _same(a, b):
 
 @pytest.mark.parametrize("N,B,use_fd,as_iter_max", [(2, 4, False, None), (13, 4, True, None), (20, 6, False, None), (27, 3, True, None),
                                                     (20, 3, False, 0)])
-def test_emulated_model_gradient_matches_the_dense_fixed_set_reference(oracle, wvjp_emu, vjp_emu, N, B, use_fd, as_iter_max):
+def test_emulated_model_gradient_matches_the_dense_fixed_set_reference(oracle, step_emu, N, B, use_fd, as_iter_max):
     """The shapes of test_emulated_vjp_matches_the_dense_fixed_set_reference, random (gu0, gX, gU): on every active-set / early-exit finish
     all 15 numbers within 1e-10 of max(1, |g|max) of model_grad_ref at the step's final set; gmodel[6] and gmodel[15] exactly 0, gmodel[14]
     exactly 0 without a force; the reference's two step sizes in 1 / m agree to 1e-9; the scale identity sum Qd gQd + sum Rd gRd = 0 within
-    1e-10 of max(1, max |Qd g|); the other outputs bit-equal to vjp_emu's."""
+    1e-10 of max(1, max |Qd g|); the other outputs bit-equal to vjp_emu_step's."""
     from tests.emu import emu
     b = synth.make_batch(B, N=N, seed=synth.SEED0 + 60 + N, **MIXED)
     cfg = emu.default_cfg(N=N, use_fd=use_fd, as_iter_max=as_iter_max)
@@ -90,8 +39,8 @@ def test_emulated_model_gradient_matches_the_dense_fixed_set_reference(oracle, w
         X, U, act = _tape(b, i, rng, N)
         f = rng.normal(0.0, 0.3, (N + 1, 3)).astype(np.float32) if use_fd else None
         gu0, gX, gU = rng.normal(size=4), rng.normal(size=(N + 1, 10)), rng.normal(size=(N, 4))
-        a = _run(wvjp_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act, gu0, gX, gU)
-        p = _run(vjp_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act, gu0, gX, gU, model=False)
+        a = _vjp(step_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act, gu0, gX, gU, model=True)
+        p = _vjp(step_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act, gu0, gX, gU)
         assert _same(a[:10], p)
         st, it, actn, gm = a[3], a[4], a[5], a[10]
         assert st == 0
@@ -117,25 +66,8 @@ def test_emulated_model_gradient_matches_the_dense_fixed_set_reference(oracle, w
         assert pinned >= 1
 
 
-def _gxr_ref(oracle, cfg, x0, xr, ur, f, X, U, pins, gu0, gX, gU, h=0.125):
-    """vjp_ref's dL/dxr with a caller's pins (inputs and velocities)."""
-    N = cfg.N
-    ff = None if (f is None or not cfg.use_fd) else np.asarray(f, dtype=np.float64)
-    sysf = lambda a: _system(oracle.linearize(cfg, x0, a, ur, ff, X, U), pins)  # noqa: E731
-    K, rhs0, nz = sysf(xr)
-    sol = np.linalg.solve(K, rhs0)
-    adj = np.linalg.solve(K.T, np.concatenate([upstream(N, gu0, gX, gU), np.zeros(K.shape[0] - nz)]))
-    g = np.zeros(xr.size)
-    for j in range(xr.size):
-        d = np.zeros(xr.size)
-        d[j] = h
-        (Ka, ra, _), (Kb, rb, _) = sysf(xr + d.reshape(xr.shape)), sysf(xr - d.reshape(xr.shape))
-        g[j] = adj @ (((ra - rb) - (Ka - Kb) @ sol) / (2 * h))
-    return g.reshape(xr.shape)
-
-
 @pytest.mark.parametrize("N,use_fd", [(20, False), (13, True)])
-def test_interior_point_finishes_are_as_close_to_the_pinned_reference_as_the_existing_adjoint(oracle, wvjp_emu, N, use_fd):
+def test_interior_point_finishes_are_as_close_to_the_pinned_reference_as_the_existing_adjoint(oracle, step_emu, N, use_fd):
     """qp_mode 1 with the velocity box shrunk to +-3 (test_gu0_only_is_the_parameter_sensitivities_contracted's instances): the interior
     point's last Newton system is barrier-smoothed, so no distance from the dense reference is fixed.  Measured instead: the reference pins
     the bounds that are active at the solution (within 1e-6), and gmodel's distance from it (of max(1, |g|max)) is at most 10 x the
@@ -156,7 +88,7 @@ def test_interior_point_finishes_are_as_close_to_the_pinned_reference_as_the_exi
         X, U, act = _tape(b, i, rng, N)
         f = rng.normal(0.0, 0.3, (N + 1, 3)).astype(np.float32) if use_fd else None
         gu0, gX, gU = rng.normal(size=4), rng.normal(size=(N + 1, 10)), rng.normal(size=(N, 4))
-        a = _run(wvjp_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act, gu0, gX, gU)
+        a = _vjp(step_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act, gu0, gX, gU, model=True)
         if a[3] != 0 or not (a[4] & 0xffff):
             continue
         n_ipm += 1
@@ -174,7 +106,7 @@ def test_interior_point_finishes_are_as_close_to_the_pinned_reference_as_the_exi
                 if abs(Xn[k, 3 + j] - ubv[j]) < 1e-6 or abs(Xn[k, 3 + j] - lbv[j]) < 1e-6:
                     pins.append((k * NX + 3 + j, float(qp["uv"][k, j] if abs(Xn[k, 3 + j] - ubv[j]) < 1e-6 else qp["lv"][k, j])))
         ref, _ = model_grad_ref(oracle, ocfg, b["x0"][i], b["xr"][i], b["ur"][i], f64, X, U, None, gu0, gX, gU, pin_v=pins)
-        gxr = _gxr_ref(oracle, ocfg, b["x0"][i], b["xr"][i], b["ur"][i], f64, X, U, pins, gu0, gX, gU)
+        gxr = vjp_ref(oracle, ocfg, b["x0"][i], b["xr"][i], b["ur"][i], f64, X, U, None, gu0, gX, gU, pin_v=pins)[1]
         dm = np.max(np.abs(a[10] - ref)) / scale(ref)
         dx = np.max(np.abs(a[7] - gxr)) / scale(gxr)
         print(f"N={N} i={i} pins={len(pins)} gmodel distance {dm:.3e}  gxr distance {dx:.3e}")
@@ -184,14 +116,14 @@ def test_interior_point_finishes_are_as_close_to_the_pinned_reference_as_the_exi
     assert worst_m <= 10.0 * worst_x, (worst_m, worst_x)
 
 
-def test_emulated_failed_step_gives_nan_in_all_16(wvjp_emu):
+def test_emulated_failed_step_gives_nan_in_all_16(step_emu):
     from tests.emu import emu
     N = 20
     b = synth.make_batch(1, seed=synth.SEED0 + 40, **MIXED)
     cfg = emu.default_cfg()
     x0 = b["x0"][0].copy()
     x0[3] = np.nan
-    out = _run(wvjp_emu, cfg, x0, b["xr"][0], b["ur"][0], None, b["xr"][0], b["ur"][0], np.zeros(4 * N, dtype=np.int8), gu0=np.ones(4))
+    out = _vjp(step_emu, cfg, x0, b["xr"][0], b["ur"][0], None, b["xr"][0], b["ur"][0], np.zeros(4 * N, dtype=np.int8), gu0=np.ones(4), model=True)
     assert out[3] != 0 and all(np.isnan(g).all() for g in out[6:])
     assert out[10].shape == (16,)
 

@@ -1,65 +1,14 @@
 """The control step's model on the device (run with -m gpu): ndp_set_model against a fresh handle, rti_wvjp_kernel's gradient in Qd, Rd and the
-mass against the dense fixed-set reference (tests/model_grad_ref.py) and against device finite differences THROUGH ndp_set_model,
+mass against the dense fixed-set reference (tests/fixed_set_ref.py) and against device finite differences THROUGH ndp_set_model,
 isolation and repeatability, and the torch layer (control_step_tunable, TunableControlStep).  CPU side: tests/test_model_grad.py."""
 import numpy as np
 import pytest
 
 from ndp_nmpc_qd_amd import synth
-from tests.model_grad_ref import model_grad_ref
-from tests.psens_ref import scale
+from tests.deriv_gpu import MIXED, _dev, _recorded_step, _t, _vjp, ndp  # noqa: F401
+from tests.fixed_set_ref import model_grad_ref, scale
 
 pytestmark = pytest.mark.gpu
-
-MIXED = dict(pos_sigma=0.5, vel_sigma=1.0, quat_sigma=0.15)        # bench.py's `mixed` workload
-
-
-@pytest.fixture(scope="module")
-def ndp():
-    import ndp_nmpc_qd_amd
-    return ndp_nmpc_qd_amd
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _t(a, dtype=None):
-    import torch
-    return torch.tensor(np.ascontiguousarray(a), device=_dev(), dtype=dtype)
-
-
-def _vjp(eng, x0, xr, ur, tape, f=None, gu0=None, gX=None, gU=None, model=True):
-    """step_vjp_device on torch tensors; returns numpy (gx0, gxr, gur, gf, u0_check, status_check[, gmodel])."""
-    import torch
-    B, N = eng.B, eng.N
-    z = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device=_dev())  # noqa: E731
-    out = (z(B, 10), z(B, N + 1, 10), z(B, N, 4), z(B, N + 1, 3), z(B, 4))
-    st = torch.full((B,), -1, dtype=torch.int32, device=_dev())
-    gm = z(B, 16) if model else None
-    eng.step_vjp_device(x0, xr, ur, tape, gu0=gu0, gX=gX, gU=gU, f=f, gx0=out[0], gxr=out[1], gur=out[2], gf=out[3], u0_check=out[4],
-                        status_check=st, gmodel=gm)
-    torch.cuda.synchronize()
-    return tuple(t.cpu().numpy() for t in out) + (st.cpu().numpy(),) + ((gm.cpu().numpy(),) if model else ())
-
-
-def _recorded_step(ndp, b, f=None, **kw):
-    """A fresh engine, one warm-up step (a kept set to start from), then the recorded step."""
-    import torch
-    B, N = b["x0"].shape[0], b["xr"].shape[1] - 1
-    eng = ndp.BatchedNMPC(B, N=N, disturbance=f is not None, **kw)
-    eng.reset(b["xr"], b["ur"])
-    t = {k: _t(b[k]) for k in ("x0", "xr", "ur")}
-    ft = _t(f, torch.float32) if f is not None else None
-    u0 = torch.empty(B, 4, dtype=torch.float64, device=_dev())
-    eng.update_device(t["x0"], t["xr"], t["ur"], u0, f=ft)
-    tape = eng.record_tape()
-    eng.update_device(t["x0"], t["xr"], t["ur"], u0, f=ft)
-    eng.synchronize()
-    st, it = eng.status()
-    _, act = eng.active_set()
-    return dict(eng=eng, t=t, tape=tape, force=ft, st=st, it=it, act=act)
-
 
 def _model(eng):
     return np.array(list(eng.cfg.Qd)), np.array(list(eng.cfg.Rd)), float(eng.cfg.mass)
@@ -150,8 +99,8 @@ def test_device_model_gradient_matches_the_dense_reference(ndp, oracle, N):
     rng = np.random.default_rng(23)
     gu0, gX, gU = rng.normal(size=(B, 4)), rng.normal(size=(B, N + 1, 10)), rng.normal(size=(B, N, 4))
     args = (r["eng"], r["t"]["x0"], r["t"]["xr"], r["t"]["ur"], r["tape"])
-    out = _vjp(*args, f=r["force"], gu0=_t(gu0), gX=_t(gX), gU=_t(gU))
-    plain = _vjp(*args, f=r["force"], gu0=_t(gu0), gX=_t(gX), gU=_t(gU), model=False)
+    out = _vjp(*args, f=r["force"], gu0=_t(gu0), gX=_t(gX), gU=_t(gU), model=True)
+    plain = _vjp(*args, f=r["force"], gu0=_t(gu0), gX=_t(gX), gU=_t(gU))
     Xl, Ul, _ = (v.cpu().numpy() for v in r["tape"])
     r["eng"].close()
     for x, y in zip(out[:6], plain):
@@ -185,7 +134,7 @@ def test_device_finite_differences_through_set_model(ndp):
     eng = r["eng"]
     rng = np.random.default_rng(26)
     gu0, gX, gU = rng.normal(size=(B, 4)), rng.normal(size=(B, N + 1, 10)), rng.normal(size=(B, N, 4))
-    gm = _vjp(eng, r["t"]["x0"], r["t"]["xr"], r["t"]["ur"], r["tape"], f=r["force"], gu0=_t(gu0), gX=_t(gX), gU=_t(gU))[6]
+    gm = _vjp(eng, r["t"]["x0"], r["t"]["xr"], r["t"]["ur"], r["tape"], f=r["force"], gu0=_t(gu0), gX=_t(gX), gU=_t(gU), model=True)[6]
     X0, U0, A0 = (v.cpu().numpy() for v in r["tape"])
     Qd0, Rd0, m0 = _model(eng)
     stable = (r["st"] == 0) & ((r["it"] & 0xffff) == 0)
@@ -239,8 +188,8 @@ def test_state_and_tape_untouched_and_repeatable(ndp):
     tape0 = [v.cpu().numpy().copy() for v in tape]
     gu0 = _t(np.random.default_rng(28).normal(size=(B, 4)))
     gX = _t(np.random.default_rng(29).normal(size=(B, 21, 10)))
-    a = _vjp(eng, r["t"]["x0"], r["t"]["xr"], r["t"]["ur"], tape, f=r["force"], gu0=gu0, gX=gX)
-    c = _vjp(eng, r["t"]["x0"], r["t"]["xr"], r["t"]["ur"], tape, f=r["force"], gu0=gu0, gX=gX)
+    a = _vjp(eng, r["t"]["x0"], r["t"]["xr"], r["t"]["ur"], tape, f=r["force"], gu0=gu0, gX=gX, model=True)
+    c = _vjp(eng, r["t"]["x0"], r["t"]["xr"], r["t"]["ur"], tape, f=r["force"], gu0=gu0, gX=gX, model=True)
     after = state()
     eng.close()
     for x, y in zip(before, after):

@@ -1,19 +1,13 @@
-"""Parameter sensitivities (du0/dxr, du0/dur, du0/df) without a GPU: the numpy reference (tests/psens_ref.py) against central differences
+"""Parameter sensitivities (du0/dxr, du0/dur, du0/df) without a GPU: the numpy reference (tests/fixed_set_ref.py) against central differences
 of the whole linearise-and-KKT-solve, the device's code (RtiWave::psens_out) on the host wave emulator against that reference, the
 translation identity that ties them to du0/dx0, and the torch layer's backward.  The device side: tests/test_param_sensitivity_gpu.py."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from ndp_nmpc_qd_amd import synth
 from tests import ref_numpy as R
-from tests.psens_ref import fixed_of, psens_ref, scale
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-MIXED = dict(pos_sigma=0.5, vel_sigma=1.0, quat_sigma=0.15)
+from tests.fixed_set_ref import fixed_of, psens_ref, scale
+from tests.step_deriv_emu import MIXED, _psens, step_emu  # noqa: F401
 
 
 def test_psens_ref_matches_central_differences_of_linearise_and_solve(oracle):
@@ -59,34 +53,8 @@ def test_psens_ref_matches_central_differences_of_linearise_and_solve(oracle):
 
 
 # ---------------------------------------------------------------- the device program on the host wave emulator
-@pytest.fixture(scope="module")
-def psens_emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("psens_emu") / "libpsens_emu.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-shared", "-o", so, os.path.join(HERE, "psens_emu.cpp")])
-    lib = C.CDLL(so)
-    lib.psens_emu_step.argtypes = [C.c_void_p] + [C.c_void_p] * 14
-    return lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _emu_step(lib, cfg, x0, xr, ur, f, X, U, act):
-    N = cfg.N
-    u0 = np.zeros(4)
-    st, it = C.c_int(-1), C.c_int(-1)
-    du0 = np.full((4, 10), -7.0)
-    dxr, dur, df = np.full((4, N + 1, 10), -7.0), np.full((4, N, 4), -7.0), np.full((4, N + 1, 3), -7.0)
-    f32 = None if f is None else np.ascontiguousarray(f, dtype=np.float32)
-    rc = lib.psens_emu_step(C.byref(cfg), _p(x0), _p(xr), _p(ur), _p(f32), _p(X), _p(U), _p(u0), C.byref(st), C.byref(it), _p(act),
-                            _p(du0), _p(dxr), _p(dur), _p(df))
-    assert rc == 0
-    return u0, st.value, du0, dxr, dur, df
-
-
 @pytest.mark.parametrize("N,B,use_fd", [(20, 8, False), (13, 4, False), (20, 3, True)])
-def test_emulated_param_sensitivities_match_the_fixed_set_reference(oracle, psens_emu, N, B, use_fd):
+def test_emulated_param_sensitivities_match_the_fixed_set_reference(oracle, step_emu, N, B, use_fd):
     """RtiWave::psens_out on the host emulator (N = 20: the compile-time horizon; 13: the run-time form), mixed workload with inputs on
     their bounds: du0/dxr, du0/dur, du0/df against psens_ref of the QP at the pre-step iterate with the step's final set, to 1e-10 of
     max(1, |J|max); stage 0's reference rows and f_N exactly 0; pinned stage-0 rows exactly 0; and the translation identity
@@ -101,7 +69,7 @@ def test_emulated_param_sensitivities_match_the_fixed_set_reference(oracle, psen
         X, U = b["xr"][i].copy(), b["ur"][i].copy()
         f = rng.normal(0.0, 0.3, (N + 1, 3)).astype(np.float32) if use_fd else None
         act = np.zeros(4 * N, dtype=np.int8)
-        u0, st, du0, dxr, dur, df = _emu_step(psens_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act)
+        u0, _, _, st, _, act, du0, dxr, dur, df = _psens(step_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act)
         assert st == 0
         A = act.reshape(N, 4)
         pinned += int(A.any())
@@ -115,14 +83,14 @@ def test_emulated_param_sensitivities_match_the_fixed_set_reference(oracle, psen
     assert pinned >= 1
 
 
-def test_emulated_nan_state_gives_nan_param_sensitivities(psens_emu):
+def test_emulated_nan_state_gives_nan_param_sensitivities(step_emu):
     from tests.emu import emu
     b = synth.make_batch(1, seed=synth.SEED0 + 40, **MIXED)
     cfg = emu.default_cfg()
     x0 = b["x0"][0].copy()
     x0[3] = np.nan
     X, U = b["xr"][0].copy(), b["ur"][0].copy()
-    _, st, du0, dxr, dur, df = _emu_step(psens_emu, cfg, x0, b["xr"][0], b["ur"][0], None, X, U, np.zeros(80, dtype=np.int8))
+    _, _, _, st, _, _, du0, dxr, dur, df = _psens(step_emu, cfg, x0, b["xr"][0], b["ur"][0], None, X, U, np.zeros(80, dtype=np.int8))
     assert st != 0 and np.isnan(du0).all() and np.isnan(dxr).all() and np.isnan(dur).all() and np.isnan(df).all()
 
 

@@ -1,22 +1,16 @@
 """Parameter sensitivities on the device (run with -m gpu): rti_psens_kernel's du0/dxr, du0/dur, du0/df against the fixed-set reference
-(tests/psens_ref.py), against device finite differences, the torch layer's gradients, the translation identity, and the step's other
+(tests/fixed_set_ref.py), against device finite differences, the torch layer's gradients, the translation identity, and the step's other
 outputs against a handle with them off.  CPU side: tests/test_param_sensitivity.py."""
 import numpy as np
 import pytest
 
 from ndp_nmpc_qd_amd import synth
-from tests.psens_ref import psens_ref, scale
+from tests.deriv_gpu import MIXED, ndp  # noqa: F401
+from tests.fixed_set_ref import psens_ref, scale
 
 pytestmark = pytest.mark.gpu
 
-MIXED = dict(pos_sigma=0.5, vel_sigma=1.0, quat_sigma=0.15)        # bench.py's `mixed` workload
 BAR = 1e-9
-
-
-@pytest.fixture(scope="module")
-def ndp():
-    import ndp_nmpc_qd_amd
-    return ndp_nmpc_qd_amd
 
 
 def _step(ndp, b, level, params, fused=False, f=None, **kw):

@@ -1,19 +1,13 @@
-"""Initial-state sensitivities without a GPU: the numpy reference (tests/sens_ref.py) against central differences of the dense KKT
+"""Initial-state sensitivities without a GPU: the numpy reference (tests/fixed_set_ref.py) against central differences of the dense KKT
 solve, the device's sensitivity code (RtiWave::sens_out) on the host wave emulator against that reference, the torch layer's backward
 and the acados facade's error paths.  The device side: tests/test_sensitivity_gpu.py."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from ndp_nmpc_qd_amd import synth
 from tests import ref_numpy as R
-from tests.sens_ref import scale, sens_ref
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-MIXED = dict(pos_sigma=0.5, vel_sigma=1.0, quat_sigma=0.15)
+from tests.fixed_set_ref import scale, sens_ref
+from tests.step_deriv_emu import MIXED, _emu_step, step_emu  # noqa: F401
 
 
 def _qps(oracle, N, B, seed, f=False):
@@ -47,34 +41,8 @@ def test_sens_ref_matches_central_differences_of_the_kkt_solve(oracle):
 
 
 # ---------------------------------------------------------------- the sensitivity sweep on the host wave emulator
-@pytest.fixture(scope="module")
-def sens_emu(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("sens_emu") / "libsens_emu.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-shared", "-o", so, os.path.join(HERE, "sens_emu.cpp")])
-    lib = C.CDLL(so)
-    lib.sens_emu_step.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 13
-    return lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _emu_step(lib, cfg, level, x0, xr, ur, X, U, act):
-    N = cfg.N
-    u0 = np.zeros(4)
-    st, it = C.c_int(-1), C.c_int(-1)
-    du0 = np.full((4, 10), -7.0)
-    dU = np.full((N, 4, 10), -7.0)
-    dX = np.full((N + 1, 10, 10), -7.0)
-    rc = lib.sens_emu_step(C.byref(cfg), level, _p(x0), _p(xr), _p(ur), None, _p(X), _p(U), _p(u0), C.byref(st), C.byref(it),
-                           _p(act), _p(du0), _p(dU), _p(dX))
-    assert rc == 0
-    return u0, st.value, it.value & 0xffff, du0, dU, dX
-
-
 @pytest.mark.parametrize("N,B", [(20, 8), (13, 4)])
-def test_emulated_sensitivity_sweep_matches_the_fixed_set_reference(oracle, sens_emu, N, B):
+def test_emulated_sensitivity_sweep_matches_the_fixed_set_reference(oracle, step_emu, N, B):
     """The device's wave program with sensitivities (level 2) on the host emulator, mixed workload (inputs on their bounds): du0, dU
     and dX against sens_ref of the QP at the pre-step iterate with the step's final set, to 1e-10 of max(1, |K|max); pinned rows exactly
     0; dX_0 = I; level 1 writes the same du0 and nothing else."""
@@ -85,8 +53,8 @@ def test_emulated_sensitivity_sweep_matches_the_fixed_set_reference(oracle, sens
     for i in range(B):
         X, U = b["xr"][i].copy(), b["ur"][i].copy()
         act = np.zeros(4 * N, dtype=np.int8)
-        u0, st, it, du0, dU, dX = _emu_step(sens_emu, cfg, 2, b["x0"][i], b["xr"][i], b["ur"][i], X, U, act)
-        assert st == 0 and it == 0
+        u0, _, _, st, it, act, du0, dU, dX = _emu_step(step_emu, cfg, 2, b["x0"][i], b["xr"][i], b["ur"][i], X, U, act)
+        assert st == 0 and it & 0xffff == 0
         A = act.reshape(N, 4)
         pinned += int(A.any())
         r0, rU, rX = sens_ref(qps[i], A)
@@ -98,19 +66,19 @@ def test_emulated_sensitivity_sweep_matches_the_fixed_set_reference(oracle, sens
         # level 1: the same du0, the level-2 outputs untouched
         X1, U1 = b["xr"][i].copy(), b["ur"][i].copy()
         a1 = np.zeros(4 * N, dtype=np.int8)
-        u01, _, _, d1, dU1, dX1 = _emu_step(sens_emu, cfg, 1, b["x0"][i], b["xr"][i], b["ur"][i], X1, U1, a1)
+        u01, _, _, _, _, _, d1, dU1, dX1 = _emu_step(step_emu, cfg, 1, b["x0"][i], b["xr"][i], b["ur"][i], X1, U1, a1)
         assert np.array_equal(d1, du0) and np.array_equal(u01, u0) and (dU1 == -7.0).all() and (dX1 == -7.0).all()
     assert pinned >= 1
 
 
-def test_emulated_nan_state_gives_nan_sensitivities(sens_emu):
+def test_emulated_nan_state_gives_nan_sensitivities(step_emu):
     from tests.emu import emu
     b = synth.make_batch(1, seed=synth.SEED0 + 40, **MIXED)
     cfg = emu.default_cfg()
     x0 = b["x0"][0].copy()
     x0[3] = np.nan
     X, U = b["xr"][0].copy(), b["ur"][0].copy()
-    _, st, _, du0, dU, dX = _emu_step(sens_emu, cfg, 2, x0, b["xr"][0], b["ur"][0], X, U, np.zeros(80, dtype=np.int8))
+    _, _, _, st, _, _, du0, dU, dX = _emu_step(step_emu, cfg, 2, x0, b["xr"][0], b["ur"][0], X, U, np.zeros(80, dtype=np.int8))
     assert st != 0 and np.isnan(du0).all() and np.isnan(dU).all() and np.isnan(dX).all()
 
 

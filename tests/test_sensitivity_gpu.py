@@ -1,22 +1,16 @@
-"""Initial-state sensitivities on the device (run with -m gpu): rti_sens_kernel against the fixed-set reference (tests/sens_ref.py: the
+"""Initial-state sensitivities on the device (run with -m gpu): rti_sens_kernel against the fixed-set reference (tests/fixed_set_ref.py: the
 oracle's QP at the pre-step iterate, dense KKT), against device finite differences, and the step's other outputs against a handle with
 sensitivities off.  CPU side: tests/test_sensitivity.py."""
 import numpy as np
 import pytest
 
 from ndp_nmpc_qd_amd import synth
-from tests.sens_ref import scale, sens_ref
+from tests.deriv_gpu import MIXED, ndp  # noqa: F401
+from tests.fixed_set_ref import scale, sens_ref
 
 pytestmark = pytest.mark.gpu
 
-MIXED = dict(pos_sigma=0.5, vel_sigma=1.0, quat_sigma=0.15)        # bench.py's `mixed` workload (test_kkt_certificate_gpu.py)
 BAR = 1e-9
-
-
-@pytest.fixture(scope="module")
-def ndp():
-    import ndp_nmpc_qd_amd
-    return ndp_nmpc_qd_amd
 
 
 def _step(ndp, b, level, fused=False, **kw):

@@ -1,86 +1,18 @@
 """The adjoint of the control step (RtiWave::vjp_out) without a GPU: the device's code on the host wave emulator against the dense fixed-set
-KKT reference (tests/vjp_ref.py) for random upstream gradients on (u0, X, U), against the parameter sensitivities (psens_emu) for an
+KKT reference (tests/fixed_set_ref.py) for random upstream gradients on (u0, X, U), against the parameter sensitivities (the emulator's psens_emu_step) for an
 upstream on u0 alone -- interior-point finishes included --, the recompute against the step, and the kernels' ISA.  The device side:
 tests/test_step_vjp_gpu.py."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from ndp_nmpc_qd_amd import synth
-from tests.psens_ref import scale
-from tests.vjp_ref import vjp_ref
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-MIXED = dict(pos_sigma=0.5, vel_sigma=1.0, quat_sigma=0.15)
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _lib(tmp_path_factory, name):
-    so = str(tmp_path_factory.mktemp(name) / f"lib{name}.so")
-    subprocess.check_call(["g++", "-O2", "-fPIC", "-std=c++17", "-shared", "-o", so, os.path.join(HERE, f"{name}.cpp")])
-    return C.CDLL(so)
-
-
-@pytest.fixture(scope="module")
-def vjp_emu(tmp_path_factory):
-    lib = _lib(tmp_path_factory, "vjp_emu")
-    lib.vjp_emu_step.argtypes = [C.c_void_p] * 18
-    return lib
-
-
-@pytest.fixture(scope="module")
-def psens_emu(tmp_path_factory):
-    lib = _lib(tmp_path_factory, "psens_emu")
-    lib.psens_emu_step.argtypes = [C.c_void_p] * 15
-    return lib
-
-
-def _vjp(lib, cfg, x0, xr, ur, f, X, U, act, gu0=None, gX=None, gU=None):
-    """One emulated step from the tape (X, U, act: copied, not touched) with its adjoint; returns (u0, X, U, st, it, act, gx0, gxr, gur, gf)."""
-    N = cfg.N
-    X, U, act = X.copy(), U.copy(), act.copy()
-    u0 = np.zeros(4)
-    st, it = C.c_int(-1), C.c_int(-1)
-    gx0, gxr, gur, gf = np.full(10, -7.0), np.full((N + 1, 10), -7.0), np.full((N, 4), -7.0), np.full((N + 1, 3), -7.0)
-    f32 = None if f is None else np.ascontiguousarray(f, dtype=np.float32)
-    c = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
-    gu0, gX, gU = c(gu0), c(gX), c(gU)
-    rc = lib.vjp_emu_step(C.byref(cfg), _p(x0), _p(xr), _p(ur), _p(f32), _p(X), _p(U), _p(u0), C.byref(st), C.byref(it), _p(act),
-                          _p(gu0), _p(gX), _p(gU), _p(gx0), _p(gxr), _p(gur), _p(gf))
-    assert rc == 0
-    return u0, X, U, st.value, it.value, act, gx0, gxr, gur, gf
-
-
-def _psens(lib, cfg, x0, xr, ur, f, X, U, act):
-    """The same step on psens_emu (its tape copied); returns (u0, X, U, st, it, act, du0, dxr, dur, df)."""
-    N = cfg.N
-    X, U, act = X.copy(), U.copy(), act.copy()
-    u0 = np.zeros(4)
-    st, it = C.c_int(-1), C.c_int(-1)
-    du0 = np.full((4, 10), -7.0)
-    dxr, dur, df = np.full((4, N + 1, 10), -7.0), np.full((4, N, 4), -7.0), np.full((4, N + 1, 3), -7.0)
-    f32 = None if f is None else np.ascontiguousarray(f, dtype=np.float32)
-    rc = lib.psens_emu_step(C.byref(cfg), _p(x0), _p(xr), _p(ur), _p(f32), _p(X), _p(U), _p(u0), C.byref(st), C.byref(it), _p(act),
-                            _p(du0), _p(dxr), _p(dur), _p(df))
-    assert rc == 0
-    return u0, X, U, st.value, it.value, act, du0, dxr, dur, df
-
-
-def _tape(b, i, rng, N):
-    """A pre-step iterate near the reference (so the linearisation point is not the reference itself) and an empty kept set."""
-    return (b["xr"][i] + 0.01 * rng.normal(size=b["xr"][i].shape), b["ur"][i] + 0.01 * rng.normal(size=b["ur"][i].shape),
-            np.zeros(4 * N, dtype=np.int8))
+from tests.fixed_set_ref import scale, vjp_ref
+from tests.step_deriv_emu import MIXED, _psens, _tape, _vjp, step_emu  # noqa: F401
 
 
 @pytest.mark.parametrize("N,B,use_fd,as_iter_max", [(2, 4, False, None), (13, 4, True, None), (20, 6, False, None), (27, 3, True, None),
                                                     (20, 3, False, 0)])
-def test_emulated_vjp_matches_the_dense_fixed_set_reference(oracle, vjp_emu, N, B, use_fd, as_iter_max):
+def test_emulated_vjp_matches_the_dense_fixed_set_reference(oracle, step_emu, N, B, use_fd, as_iter_max):
     """Random (gu0, gX, gU) on mixed instances (inputs on their bounds among them; as_iter_max = 0: the early exit of rounds 1-5 or the
     interior point): every active-set / early-exit finish within 1e-10 of max(1, |g|max) of vjp_ref at the step's final set; stage 0's
     reference row and f_N exactly 0, pinned inputs' rows exactly 0."""
@@ -94,7 +26,7 @@ def test_emulated_vjp_matches_the_dense_fixed_set_reference(oracle, vjp_emu, N, 
         X, U, act = _tape(b, i, rng, N)
         f = rng.normal(0.0, 0.3, (N + 1, 3)).astype(np.float32) if use_fd else None
         gu0, gX, gU = rng.normal(size=4), rng.normal(size=(N + 1, 10)), rng.normal(size=(N, 4))
-        u0, Xn, Un, st, it, actn, gx0, gxr, gur, gf = _vjp(vjp_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act, gu0, gX, gU)
+        u0, Xn, Un, st, it, actn, gx0, gxr, gur, gf = _vjp(step_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act, gu0, gX, gU)
         assert st == 0
         if it & 0xffff:                                  # interior point: its last Newton system (test_gu0_only_...)
             continue
@@ -112,12 +44,12 @@ def test_emulated_vjp_matches_the_dense_fixed_set_reference(oracle, vjp_emu, N, 
 
 
 @pytest.mark.parametrize("N,use_fd,ipm", [(20, False, False), (13, True, False), (20, False, True), (13, True, True)])
-def test_gu0_only_is_the_parameter_sensitivities_contracted(vjp_emu, psens_emu, N, use_fd, ipm):
-    """An upstream on u0 alone: gx0 = K0' gu0, gxr / gur / gf = gu0 contracted with psens_emu's du0/dxr, du0/dur, du0/df, within 1e-12 of
+def test_gu0_only_is_the_parameter_sensitivities_contracted(step_emu, N, use_fd, ipm):
+    """An upstream on u0 alone: gx0 = K0' gu0, gxr / gur / gf = gu0 contracted with psens_emu_step's du0/dxr, du0/dur, du0/df, within 1e-12 of
     max(1, |g|max) for free and pinned finishes; interior-point ones (ipm: qp_mode 1, the velocity box shrunk to +-3) within 1e-6: both
     solve the last Newton system, whose barrier terms on an active velocity bound reach 1e10 -- they agree to ~1e-13 on most instances and
     to ~1e-7 on the stiffest.  The recompute IS the step: u0, X, U, status, iteration word and
-    kept set bit-equal to psens_emu's."""
+    kept set bit-equal to psens_emu_step's."""
     from tests.emu import emu
     B = 6
     b = synth.make_batch(B, N=N, seed=synth.SEED0 + 70 + N, **MIXED)
@@ -131,8 +63,8 @@ def test_gu0_only_is_the_parameter_sensitivities_contracted(vjp_emu, psens_emu, 
         X, U, act = _tape(b, i, rng, N)
         f = rng.normal(0.0, 0.3, (N + 1, 3)).astype(np.float32) if use_fd else None
         gu0 = rng.normal(size=4)
-        a = _vjp(vjp_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act, gu0=gu0)
-        p = _psens(psens_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act)
+        a = _vjp(step_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act, gu0=gu0)
+        p = _psens(step_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act)
         for x, y in zip(a[:6], p[:6]):
             assert np.array_equal(x, y)
         if a[3] != 0:
@@ -149,14 +81,14 @@ def test_gu0_only_is_the_parameter_sensitivities_contracted(vjp_emu, psens_emu, 
         assert n_ipm >= 3
 
 
-def test_emulated_nan_state_gives_nan_gradients(vjp_emu):
+def test_emulated_nan_state_gives_nan_gradients(step_emu):
     from tests.emu import emu
     N = 20
     b = synth.make_batch(1, seed=synth.SEED0 + 40, **MIXED)
     cfg = emu.default_cfg()
     x0 = b["x0"][0].copy()
     x0[3] = np.nan
-    out = _vjp(vjp_emu, cfg, x0, b["xr"][0], b["ur"][0], None, b["xr"][0], b["ur"][0], np.zeros(4 * N, dtype=np.int8), gu0=np.ones(4))
+    out = _vjp(step_emu, cfg, x0, b["xr"][0], b["ur"][0], None, b["xr"][0], b["ur"][0], np.zeros(4 * N, dtype=np.int8), gu0=np.ones(4))
     assert out[3] != 0 and all(np.isnan(g).all() for g in out[6:])
 
 

@@ -1,77 +1,15 @@
 """The adjoint of the control step on the device (run with -m gpu): rti_vjp_kernel for an upstream on u0 alone against today's Jacobians,
-for full-trajectory upstreams against the dense fixed-set reference (tests/vjp_ref.py), against device finite differences, the recompute
+for full-trajectory upstreams against the dense fixed-set reference (tests/fixed_set_ref.py), against device finite differences, the recompute
 against the recorded step, isolation (engine state and tape untouched, repeatable), tapes kept over later steps, refusals, and the torch
 layer.  CPU side: tests/test_step_vjp.py."""
 import numpy as np
 import pytest
 
 from ndp_nmpc_qd_amd import synth
-from tests.psens_ref import scale
-from tests.vjp_ref import vjp_ref
+from tests.deriv_gpu import MIXED, _dev, _recorded_step, _t, _vjp, ndp  # noqa: F401
+from tests.fixed_set_ref import scale, vjp_ref
 
 pytestmark = pytest.mark.gpu
-
-MIXED = dict(pos_sigma=0.5, vel_sigma=1.0, quat_sigma=0.15)        # bench.py's `mixed` workload
-
-
-@pytest.fixture(scope="module")
-def ndp():
-    import ndp_nmpc_qd_amd
-    return ndp_nmpc_qd_amd
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _t(a, dtype=None):
-    import torch
-    return torch.tensor(np.ascontiguousarray(a), device=_dev(), dtype=dtype)
-
-
-def _vjp(eng, x0, xr, ur, tape, f=None, gu0=None, gX=None, gU=None):
-    """ndp_step_vjp_device on torch tensors; returns numpy (gx0, gxr, gur, gf, u0_check, status_check)."""
-    import torch
-    B, N = eng.B, eng.N
-    z = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device=_dev())  # noqa: E731
-    out = (z(B, 10), z(B, N + 1, 10), z(B, N, 4), z(B, N + 1, 3), z(B, 4))
-    st = torch.full((B,), -1, dtype=torch.int32, device=_dev())
-    eng.step_vjp_device(x0, xr, ur, tape, gu0=gu0, gX=gX, gU=gU, f=f, gx0=out[0], gxr=out[1], gur=out[2], gf=out[3], u0_check=out[4],
-                        status_check=st)
-    torch.cuda.synchronize()
-    return tuple(t.cpu().numpy() for t in out) + (st.cpu().numpy(),)
-
-
-def _recorded_step(ndp, b, fused=False, f=None, params=True, **kw):
-    """A fresh engine, one warm-up step (a kept set to start from), then the recorded step: tape, the step through update_device, and (params)
-    today's Jacobians.  Returns a dict of everything the tests compare."""
-    import torch
-    B, N = b["x0"].shape[0], b["xr"].shape[1] - 1
-    eng = ndp.BatchedNMPC(B, N=N, disturbance=fused or f is not None, **kw)
-    eng.reset(b["xr"], b["ur"])
-    t = {k: _t(b[k]) for k in ("x0", "xr", "ur")}
-    ft = _t(f, torch.float32) if f is not None else None
-    nb = dict(other=_t(b["other"]), ego_xy=_t(b["ego_xy"])) if fused else {}
-    u0 = torch.empty(B, 4, dtype=torch.float64, device=_dev())
-    eng.update_device(t["x0"], t["xr"], t["ur"], u0, f=ft, **nb)
-    if params:
-        eng.enable_sensitivity(1)
-        eng.enable_param_sensitivity()
-    tape = eng.record_tape()
-    eng.update_device(t["x0"], t["xr"], t["ur"], u0, f=ft, **nb)
-    eng.synchronize()                      # (the step went on the engine's own stream: torch's default one cannot be named)
-    force = eng.device_force().clone() if fused else ft
-    X, U = (v.clone() for v in eng.device_iterate())
-    torch.cuda.synchronize()
-    st, it = eng.status()
-    _, act = eng.active_set()
-    r = dict(eng=eng, t=t, tape=tape, force=force, u0=u0.cpu().numpy(), X=X.cpu().numpy(), U=U.cpu().numpy(), st=st, it=it, act=act)
-    if params:
-        r["K0"] = eng.sensitivity()[0]
-        r["J"] = eng.param_sensitivity()
-    return r
-
 
 @pytest.mark.parametrize("form", [dict(fused=True), dict(), dict(work_queue=1), dict(work_queue=2), dict(qp_mode=1, fused=True)])
 def test_gu0_only_matches_the_jacobians_and_the_recompute_is_the_step(ndp, form):
@@ -81,7 +19,7 @@ def test_gu0_only_matches_the_jacobians_and_the_recompute_is_the_step(ndp, form)
     form = dict(form)
     fused = form.pop("fused", False)
     b = synth.make_batch(1024, seed=synth.SEED0 + 80, downwash=fused, **MIXED)
-    r = _recorded_step(ndp, b, fused=fused, **form)
+    r = _recorded_step(ndp, b, fused=fused, params=True, **form)
     g = np.random.default_rng(1).normal(size=(1024, 4))
     gx0, gxr, gur, gf, u0c, stc = _vjp(r["eng"], r["t"]["x0"], r["t"]["xr"], r["t"]["ur"], r["tape"], f=r["force"], gu0=_t(g))
     r["eng"].close()
@@ -175,7 +113,7 @@ def test_state_and_tape_untouched_and_repeatable(ndp):
     B = 256
     b = synth.make_batch(B, seed=synth.SEED0 + 83, downwash=True, **MIXED)
     b["x0"][5, 3] = np.nan
-    r = _recorded_step(ndp, b, fused=True)
+    r = _recorded_step(ndp, b, fused=True, params=True)
     eng = r["eng"]
     before = [v.cpu().numpy().copy() for v in eng.device_iterate()] + [eng.active_set()[1], *eng.sensitivity()[:1], *eng.param_sensitivity()]
     tape0 = [v.cpu().numpy().copy() for v in r["tape"]]
