@@ -356,6 +356,25 @@ int ndp_step_vjp_model_device(ndp_handle *h, const void *d_x0, const void *d_xr,
                               void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_gmodel, void *d_u0_check, void *d_status_check,
                               void *stream);
 
+/* Forward mode of the control step (a Jacobian-vector product): the derivative of one recorded step's QP -- the same derivative as the
+ * adjoint's above (fixed final set: exact; interior point: its last Newton system) -- along n_tan directions of its data per call.  A
+ * direction is (tx0 [10], txr [N+1][10], tur [N][4], tf [N+1][3]); its result is the first-order change of the step's whole output,
+ * du0 [4], dX [N+1][10], dU [N][4] (du0 = dU_0; dX_0 = tx0).  All fp64 and instance-major, T = n_tan:
+ *   d_tx0 [B][T][10], d_txr [B][T][N+1][10], d_tur [B][T][N][4], d_tf [B][T][N+1][3]     (NULL = 0, not all four NULL)
+ *   d_du0 [B][T][4],  d_dX  [B][T][N+1][10], d_dU  [B][T][N][4]                         (NULL = not written, not all three NULL)
+ * The row of a pinned input in dU is exactly 0; stage 0's txr row and tf_N move nothing; a nonzero status or a failed factorisation of
+ * the tangent solve gives NaN in every output of the instance.  <g, JVP(t)> = <VJP(g), t> holds against ndp_step_vjp_device on one tape.
+ * Tape, workspace, ordering, repeatability, d_u0_check and d_status_check: exactly ndp_step_vjp_device's (the two share the workspace; calls
+ * on one handle are ordered).  The step is recomputed, then every direction costs one more Riccati sweep; T directions in one call give
+ * what T calls of one give, bit for bit.  -2 with a reason in ndp_last_error, nothing launched: the adjoint's refusals (n_rti != 1,
+ * qp_precision != 0, N >= 28, a missing x0 / xr / ur / X_lin / U_lin, d_f without use_fd), n_tan outside 1..NDP_JVP_MAX_TANGENTS, d_tf
+ * without use_fd. */
+#define NDP_JVP_MAX_TANGENTS 8
+int ndp_step_jvp_device(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
+                        const void *d_X_lin, const void *d_U_lin, const void *d_act_lin, int n_tan,
+                        const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf,
+                        void *d_du0, void *d_dX, void *d_dU, void *d_u0_check, void *d_status_check, void *stream);
+
 /* Changes the model of a live handle: Qd [10] replaces ndp_cfg.Qd (nmpc_body_rate_ctl.py:48), Rd [4] ndp_cfg.Rd (nmpc_body_rate_ctl.py:49),
  * mass ndp_cfg.mass (fhnp_params.py:9).  Qd / Rd NULL = keep; mass <= 0 or NaN = keep.  Refused with -2 and a reason in ndp_last_error,
  * changing nothing: a non-finite entry, a negative Qd, a non-positive Rd, an infinite mass, and -- with as_iter_max > 0 -- an Rd that breaks

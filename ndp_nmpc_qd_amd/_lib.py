@@ -57,7 +57,7 @@ EXPORTS = [
     "ndp_sens_params_enable", "ndp_sens_params_enabled", "ndp_get_sens_params", "ndp_device_sens_xr", "ndp_device_sens_ur", "ndp_device_sens_f",
     "ndp_debug_rti_launched", "ndp_device_active_set", "ndp_step_vjp_device",
     "ndp_downwash_vjp_device", "ndp_set_mlp_weights_device", "ndp_debug_mlp_fragments",
-    "ndp_step_vjp_model_device", "ndp_set_model",
+    "ndp_step_vjp_model_device", "ndp_set_model", "ndp_step_jvp_device",
 ]
 
 _lib = None
@@ -142,6 +142,7 @@ def load():
     lib.ndp_device_active_set.restype = vp
     lib.ndp_step_vjp_device.argtypes = [vp] * 18
     lib.ndp_step_vjp_model_device.argtypes = [vp] * 19
+    lib.ndp_step_jvp_device.argtypes = [vp] * 8 + [C.c_int] + [vp] * 10
     lib.ndp_set_model.argtypes = [vp, vp, vp, C.c_double]
     lib.ndp_downwash_vjp_device.argtypes = [vp, vp, C.c_int] + [vp] * 7
     lib.ndp_set_mlp_weights_device.argtypes = [vp] * 3

@@ -563,6 +563,34 @@ class BatchedNMPC:
             name = "ndp_step_vjp_model_device"
         self._check(getattr(self._lib, name)(self._h, *args), name)
 
+    def step_jvp_device(self, x0, xr, ur, tape, tx0=None, txr=None, tur=None, tf=None, f=None, du0=None, dX=None, dU=None,
+                        u0_check=None, status_check=None, stream=None):
+        """Enqueues the forward-mode derivative of one recorded step on `stream` (ndp_step_jvp_device; include/ndp_nmpc.h): the step is
+        recomputed from `tape`, x0, xr, ur and f as step_vjp_device does, and the first-order change of its output along T directions
+        (tx0 [B,T,10], txr [B,T,N+1,10], tur [B,T,N,4], tf [B,T,N+1,3]; float64 CUDA tensors, None = 0, not all None) is written into
+        du0 [B,T,4], dX [B,T,N+1,10], dU [B,T,N,4] (float64 CUDA tensors the caller allocates; None = not written, not all None).  T
+        (1..8) is read from the tangents' second dimension; tangents and outputs without that axis mean T = 1.  u0_check, status_check
+        and stream: as step_vjp_device's.  Nothing of the engine's state is written."""
+        import torch
+        B, N = self.B, self.N
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        tails = ((10,), (N + 1, 10), (N, 4), (N + 1, 3), (4,), (N + 1, 10), (N, 4))
+        given = [(t, s) for t, s in zip((tx0, txr, tur, tf, du0, dX, dU), tails) if t is not None]
+        Ts = {int(t.shape[1]) if t.dim() == len(s) + 2 else 1 for t, s in given}
+        if len(Ts) > 1:
+            raise ValueError(f"step_jvp_device: tangents and outputs disagree on the number of directions ({sorted(Ts)})")
+        T = Ts.pop() if Ts else 1
+        d = self._dptr
+        # (without the T axis: [B, ...] is [B, 1, ...] as it lies)
+        dt = lambda t, s: d(t, torch.float64, (B, T) + s if t is not None and t.dim() == len(s) + 2 else (B,) + s)  # noqa: E731
+        X, U, A = tape
+        args = [d(x0, torch.float64, (B, 10)), d(xr, torch.float64, (B, N + 1, 10)), d(ur, torch.float64, (B, N, 4)),
+                d(f, torch.float32, (B, N + 1, 3)), d(X, torch.float64, (B, N + 1, 10)), d(U, torch.float64, (B, N, 4)),
+                d(A, torch.int8, (B, N, 4)), T, *(dt(t, s) for t, s in zip((tx0, txr, tur, tf, du0, dX, dU), tails)),
+                d(u0_check, torch.float64, (B, 4)), d(status_check, torch.int32, (B,)), self._stream(stream)]
+        self._check(self._lib.ndp_step_jvp_device(self._h, *args), "ndp_step_jvp_device")
+
     # ------------------------------------------------------------------ backward pass of the downwash network
     def _other_ptr(self, other, other_index):
         """(pointer, doubles per node) of neighbour windows [rows, N+1, 6 or 10] (rows = B without other_index)."""

@@ -362,6 +362,38 @@ __global__ __launch_bounds__(256) void rti_wvjp_kernel(KernArgs ka, VjpArgs va, 
     Prog::template run<false, true, false, false, true, true>(P, io, lds, inb, x0v, nullptr, nullptr, &vo, gmodel + i * 16);
 }
 
+// The forward-mode derivative of the control step (ndp_step_jvp_device, RtiWave::jvp_out): the recompute of rti_vjp_kernel -- the same
+// workspace, the same tape rules -- then one Riccati sweep per direction over the blocks the step left, n_tan directions per call.  The
+// tangents and outputs are instance-major: instance i's T directions lie together.  Not a row of k_rti: ndp_step_jvp_device launches it.
+struct JvpArgs {
+    const double *tx0, *txr, *tur, *tf;
+    double *du0, *dX, *dU;
+    int T;
+};
+template <int NC>
+__global__ __launch_bounds__(256) void rti_jvp_kernel(KernArgs ka, JvpArgs ja)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const RtiParams &P = ka.P;
+    const int waves = (int)(blockDim.x >> 6), wave = (int)(threadIdx.x >> 6);
+    const int inst = __builtin_amdgcn_readfirstlane((int)blockIdx.x * waves + wave);
+    if (inst >= ka.B) return;
+    const int N = NC ? NC : P.N;
+    RtiIo io;
+    bind_instance(io, ka.bp, inst, N);
+    const int lpw = NC ? ((lds_doubles(NC) + 1) & ~1) : ka.lds_per_wave;
+    WaveGfx950::lds_ptr lds = (WaveGfx950::lds_ptr)(smem + (size_t)wave * lpw);
+    using Prog = RtiWave<WaveGfx950, 3, NC, true, NC ? 1 : 0>;
+    const size_t i = (size_t)inst * (size_t)ja.T, nx = (size_t)(N + 1) * NX, nu = (size_t)N * NU, nf = (size_t)(N + 1) * 3;
+    const JvpIo jo{ja.tx0 ? ja.tx0 + i * NX : nullptr, ja.txr ? ja.txr + i * nx : nullptr, ja.tur ? ja.tur + i * nu : nullptr,
+                   ja.tf ? ja.tf + i * nf : nullptr, ja.du0 ? ja.du0 + i * NU : nullptr, ja.dX ? ja.dX + i * nx : nullptr,
+                   ja.dU ? ja.dU + i * nu : nullptr, ja.T};
+    typename Prog::InBuf inb;
+    double x0v;
+    Prog::issue_first(P, io, inb, x0v);
+    Prog::template run<false, true, false, false, false, false, true>(P, io, lds, inb, x0v, nullptr, nullptr, nullptr, nullptr, &jo);
+}
+
 // test hook: one v_mfma_f64_16x16x4_f64 / v_mfma_f64_4x4x4_4b_f64 with caller-chosen per-lane operands (pins the register maps)
 __global__ void mfma_probe_kernel(const double *a, const double *b, const double *c, double *d)
 {
@@ -2124,6 +2156,9 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
     for (const void *fn : {(const void *)rti_wvjp_kernel<20>, (const void *)rti_wvjp_kernel<0>})   // (ndp_step_vjp_model_device)
         if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess)
             return fail("hipFuncSetAttribute(rti_wvjp_kernel)", e);
+    for (const void *fn : {(const void *)rti_jvp_kernel<20>, (const void *)rti_jvp_kernel<0>})     // (forward mode: ndp_step_jvp_device)
+        if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) != hipSuccess)
+            return fail("hipFuncSetAttribute(rti_jvp_kernel)", e);
     for (const void *fn : {(const void *)rti_vjp_kernel<20>, (const void *)rti_vjp_kernel<0>})     // (the adjoint: ndp_step_vjp_device)
         if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)) != hipSuccess)
             return fail("hipFuncSetAttribute(rti_vjp_kernel)", e);
@@ -3755,6 +3790,33 @@ void *ndp_device_sens_f(ndp_handle *h) { return h ? h->dPSensF : nullptr; }
 // ---- adjoint of the control step (rti_vjp_kernel, RtiWave::vjp_out)
 void *ndp_device_active_set(ndp_handle *h) { return h ? h->dAct : nullptr; }
 
+// What the derivative kernels that recompute a recorded step share (rti_vjp_kernel, rti_wvjp_kernel, rti_jvp_kernel): the handle's workspace
+// (first call), the tape copied into it on s -- never written: the recompute advances the copy, two calls on one tape give the same result --
+// and the step's kernel arguments on that copy.
+static int recompute_args(ndp_handle *h, hipStream_t s, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
+                          const void *d_X_lin, const void *d_U_lin, const void *d_act_lin, void *d_u0_check, void *d_status_check,
+                          KernArgs &ka)
+{
+    const ndp_cfg &c = h->cfg;
+    const size_t B = c.batch;
+    if (!h->dVjp) {
+        NDP_HIP(h, hipMalloc((void **)&h->dVjp, (nxs(h) + nus(h) + B * NU) * 8));
+        NDP_HIP(h, hipMalloc((void **)&h->dVjpSt, B * 2 * 4));
+        NDP_HIP(h, hipMalloc((void **)&h->dVjpAct, act_bytes(h)));
+    }
+    double *X = h->dVjp, *U = X + nxs(h), *u0 = U + nus(h);
+    int *st = h->dVjpSt, *it = st + B;
+    NDP_HIP(h, hipMemcpyAsync(X, d_X_lin, nxs(h) * 8, hipMemcpyDeviceToDevice, s));
+    NDP_HIP(h, hipMemcpyAsync(U, d_U_lin, nus(h) * 8, hipMemcpyDeviceToDevice, s));
+    if (d_act_lin) NDP_HIP(h, hipMemcpyAsync(h->dVjpAct, d_act_lin, act_bytes(h), hipMemcpyDeviceToDevice, s));
+    else NDP_HIP(h, hipMemsetAsync(h->dVjpAct, 0, act_bytes(h), s));
+    BatchPtrs bp{h->dKC, h->dTables, (const double *)d_x0, (const double *)d_xr, (const double *)d_ur, (const float *)d_f, X, U,
+                 d_u0_check ? (double *)d_u0_check : u0, d_status_check ? (int *)d_status_check : st, it, nullptr, nullptr, nullptr, nullptr,
+                 (size_t)(c.N + 1) * NX, (size_t)c.N * NU, (size_t)NX, nullptr, nullptr, nullptr, c.mass, 0, h->dVjpAct};
+    ka = KernArgs{h->P, bp, (int)B, h->lds_per_wave, MlpArgs{}, QueueArgs{}, LateArgs{}, TickArgs{}};
+    return 0;
+}
+
 // model: the entry is ndp_step_vjp_model_device (rti_wvjp_kernel; d_gmodel required), else ndp_step_vjp_device (rti_vjp_kernel)
 static int step_vjp(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
                     const void *d_X_lin, const void *d_U_lin, const void *d_act_lin,
@@ -3775,23 +3837,9 @@ static int step_vjp(ndp_handle *h, const void *d_x0, const void *d_xr, const voi
     else if (model && !d_gmodel) why = "gmodel is required (without it: ndp_step_vjp_device)";
     if (why) { h->err = std::string(model ? "ndp_step_vjp_model_device: " : "ndp_step_vjp_device: ") + why; return -2; }
     const size_t B = c.batch;
-    if (!h->dVjp) {
-        NDP_HIP(h, hipMalloc((void **)&h->dVjp, (nxs(h) + nus(h) + B * NU) * 8));
-        NDP_HIP(h, hipMalloc((void **)&h->dVjpSt, B * 2 * 4));
-        NDP_HIP(h, hipMalloc((void **)&h->dVjpAct, act_bytes(h)));
-    }
-    double *X = h->dVjp, *U = X + nxs(h), *u0 = U + nus(h);
-    int *st = h->dVjpSt, *it = st + B;
     hipStream_t s = g.s;
-    // the tape is copied, never written: the recompute advances the copy (two calls on one tape give the same result)
-    NDP_HIP(h, hipMemcpyAsync(X, d_X_lin, nxs(h) * 8, hipMemcpyDeviceToDevice, s));
-    NDP_HIP(h, hipMemcpyAsync(U, d_U_lin, nus(h) * 8, hipMemcpyDeviceToDevice, s));
-    if (d_act_lin) NDP_HIP(h, hipMemcpyAsync(h->dVjpAct, d_act_lin, act_bytes(h), hipMemcpyDeviceToDevice, s));
-    else NDP_HIP(h, hipMemsetAsync(h->dVjpAct, 0, act_bytes(h), s));
-    BatchPtrs bp{h->dKC, h->dTables, (const double *)d_x0, (const double *)d_xr, (const double *)d_ur, (const float *)d_f, X, U,
-                 d_u0_check ? (double *)d_u0_check : u0, d_status_check ? (int *)d_status_check : st, it, nullptr, nullptr, nullptr, nullptr,
-                 (size_t)(c.N + 1) * NX, (size_t)c.N * NU, (size_t)NX, nullptr, nullptr, nullptr, c.mass, 0, h->dVjpAct};
-    KernArgs ka{h->P, bp, (int)B, h->lds_per_wave, MlpArgs{}, QueueArgs{}, LateArgs{}, TickArgs{}};
+    KernArgs ka;
+    if (int rc = recompute_args(h, s, d_x0, d_xr, d_ur, d_f, d_X_lin, d_U_lin, d_act_lin, d_u0_check, d_status_check, ka)) return rc;
     VjpArgs va{(const double *)d_gu0, (const double *)d_gX, (const double *)d_gU, (double *)d_gx0, (double *)d_gxr, (double *)d_gur,
                (double *)d_gf};
     const int W = h->waves;
@@ -3821,6 +3869,40 @@ int ndp_step_vjp_model_device(ndp_handle *h, const void *d_x0, const void *d_xr,
 {
     return step_vjp(h, d_x0, d_xr, d_ur, d_f, d_X_lin, d_U_lin, d_act_lin, d_gu0, d_gX, d_gU, d_gx0, d_gxr, d_gur, d_gf, d_u0_check,
                     d_status_check, stream, true, d_gmodel);
+}
+
+// ---- forward mode of the control step (rti_jvp_kernel, RtiWave::jvp_out): the adjoint's recompute, workspace and tape rules
+int ndp_step_jvp_device(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
+                        const void *d_X_lin, const void *d_U_lin, const void *d_act_lin, int n_tan,
+                        const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf,
+                        void *d_du0, void *d_dX, void *d_dU, void *d_u0_check, void *d_status_check, void *stream)
+{
+    Entry g(h, true, stream);
+    if (g.rc) return g.rc;
+    const ndp_cfg &c = h->cfg;
+    const char *why = nullptr;
+    if (c.n_rti != 1) why = "the derivative needs n_rti = 1 (the derivative of the step's one QP)";
+    else if (c.qp_precision != 0) why = "the derivative needs qp_precision 0 (the fp64 product path)";
+    else if (slots_for(c.N) > 3) why = "the derivative is served for N <= 27 only (the five-slot kernels of N >= 28 have none)";
+    else if (!d_x0 || !d_xr || !d_ur || !d_X_lin || !d_U_lin) why = "x0, xr, ur and the tape's iterate (X_lin, U_lin) are required";
+    else if (n_tan < 1 || n_tan > NDP_JVP_MAX_TANGENTS) why = "n_tan must be 1..8 (directions per call)";
+    else if (!d_tx0 && !d_txr && !d_tur && !d_tf) why = "no tangent (tx0, txr, tur and tf all NULL)";
+    else if (!d_du0 && !d_dX && !d_dU) why = "no output asked for (du0, dX and dU all NULL)";
+    else if (d_f && !c.use_fd) why = "a disturbance force needs use_fd = 1 (NDP model)";
+    else if (d_tf && !c.use_fd) why = "a force tangent needs use_fd = 1 (NDP model)";
+    if (why) { h->err = std::string("ndp_step_jvp_device: ") + why; return -2; }
+    const size_t B = c.batch;
+    hipStream_t s = g.s;
+    KernArgs ka;
+    if (int rc = recompute_args(h, s, d_x0, d_xr, d_ur, d_f, d_X_lin, d_U_lin, d_act_lin, d_u0_check, d_status_check, ka)) return rc;
+    JvpArgs ja{(const double *)d_tx0, (const double *)d_txr, (const double *)d_tur, (const double *)d_tf, (double *)d_du0, (double *)d_dX,
+               (double *)d_dU, n_tan};
+    const int W = h->waves;
+    const void *fn = c.N == 20 ? (const void *)rti_jvp_kernel<20> : (const void *)rti_jvp_kernel<0>;
+    void *args[] = {&ka, &ja};
+    NDP_HIP(h, hipLaunchKernel(fn, dim3((unsigned)((B + W - 1) / W)), dim3(64 * W), args, (size_t)h->lds_per_wave * sizeof(double) * W, s));
+    NDP_HIP(h, hipGetLastError());
+    return g.noted(0);
 }
 
 // ---- the model of a live handle: cost weights and mass

@@ -176,6 +176,14 @@ struct VjpIo {
     const double *gu0, *gX, *gU;
     double *gx0, *gxr, *gur, *gf;
 };
+// Forward-mode derivative (Jacobian-vector product) of the step's QP (RtiWave::jvp_out), one instance's views, T directions per call.
+// Tangents: tx0 [T][10], txr [T][N+1][10], tur [T][N][4], tf [T][N+1][3] (null = 0); outputs: du0 [T][4], dX [T][N+1][10], dU [T][N][4]
+// (null = not written).
+struct JvpIo {
+    const double *tx0, *txr, *tur, *tf;
+    double *du0, *dX, *dU;
+    int T;
+};
 // *RtiIo::iters = interior-point iterations of the step (low half) + Riccati sweeps its QP_AUTO solves took before them (high half);
 // COND_ACCEPTED in the sweep count (config 5's study): a condensed solve's result was kept
 enum { ITERS_SWEEP_SHIFT = 16, ITERS_IPM_MASK = 0xffff, COND_ACCEPTED = 0x1000 };
@@ -1976,9 +1984,11 @@ struct RtiWave {
     // PSENS (rti_psens_kernel): behind them, the parameter sensitivities (psens_out) into *psens.
     // VJP (rti_vjp_kernel): after the step, the adjoint of its last QP contracted with an upstream gradient (vjp_out) into *vjp.
     // WVJP (rti_wvjp_kernel, with VJP): the same pass also gives the gradient in the cost weights and the mass into gmodel [16].
-    template <bool DEFER, bool IPM_RARE = false, bool SENS = false, bool PSENS = false, bool VJP = false, bool WVJP = false>
+    // JVP (rti_jvp_kernel): after the step, the directional derivatives of its last QP along the caller's tangents (jvp_out) into *jvp.
+    template <bool DEFER, bool IPM_RARE = false, bool SENS = false, bool PSENS = false, bool VJP = false, bool WVJP = false, bool JVP = false>
     static NDP_D bool run(const RtiParams &P, const RtiIo &io, lp lds, InBuf &inb, vd x0v, const SensIo *sens = nullptr,
-                          const PSensIo *psens = nullptr, const VjpIo *vjp = nullptr, double *gmodel = nullptr)
+                          const PSensIo *psens = nullptr, const VjpIo *vjp = nullptr, double *gmodel = nullptr,
+                          [[maybe_unused]] const JvpIo *jvp = nullptr)
     {
         const int N = horizon(P);
         const LdsMap m = make_map(N);
@@ -2126,7 +2136,7 @@ struct RtiWave {
                 }
             }
             const int zsrc = done ? m.ZX : m.CX;       // ZX|ZU and CX|CU are laid out alike
-            if constexpr (PSENS || VJP) zlast = zsrc;
+            if constexpr (PSENS || VJP || JVP) zlast = zsrc;
             if (IPM_RARE ? NDP_RARELY(!done) : !done) {
                 if (DEFER) return true;
                 if (as_on) {                           // the interior-point loop's answer carries no set: the next step starts cold
@@ -2201,6 +2211,9 @@ struct RtiWave {
         if constexpr (VJP) {
             if constexpr (WVJP) { if (vjp) vjp_out<true>(P, m, T, lds, io, A, zlast, status != 0, *vjp, gmodel); }
             else if (vjp) vjp_out(P, m, T, lds, io, A, zlast, status != 0, *vjp);
+        }
+        if constexpr (JVP) {
+            if (jvp) jvp_out(P, m, T, lds, io, A, zlast, status != 0, *jvp);
         }
         if (io.f_late) W::late_publish(late_prev, io.late_gsize, io.late_done_word);
         return false;
@@ -2477,6 +2490,7 @@ struct RtiWave {
             }
             for (int t = 0; t < RF; ++t) wf[t] = have_f ? W::gldfu(io.f, W::imin(lane + 64 * t, nf - 1)) : vd(0.0);
         }
+        // (this parking of the set and of qr, q+ is repeated as text in jvp_out -- a shared function changes the adjoint kernels: keep the two in step)
         for (int t = 0; t < RUA; ++t) {                        // the final set, 0 / 1 per input bound
             vi e = a_elem(P, lane, t);
             W::st(lds, e + m.AS, W::sel(a_get(A, m, lds, t, e) == 0, vd(0.0), vd(1.0)));
@@ -2610,6 +2624,116 @@ struct RtiWave {
         }
         if (vo.gx0) W::gst(vo.gx0, r, W::ld(lds, r + LM), row);
         if constexpr (WM) W::gst(gm, lane, W::sel(lane < 15, gacc, vd(0.0)), lane < 16);
+    }
+    // ---------------------------------------------------------------- forward mode (Jacobian-vector product)
+    // The step's last QP as vjp_out differentiates it (linearisation point and final set held fixed; interior point: its last Newton system),
+    // along a direction (tx0, txr, tur, tf) of its data.  x0, xr, ur and f do not enter A_k, B_k or the Hessian but for the attitude block, so
+    // the tangent z' = (dX, dU) of the solution solves the SAME QP with other data, every pin held at 0:
+    //     dx_0 = tx0;   defects b'_k = [h^2/2 tf_k / m; h tf_k / m; 0] (tf_N reaches no dynamics);
+    //     gradient rows 0..5: -s Qd txr_k (s = dt, at stage N: 1);  input rows: -dt Rd tur_k (pinned: 0);
+    //     attitude rows: (dQ_k/dqr . tqr) q+_k = s (E(tqr)' W E(qr) + E(qr)' W E(tqr)) q+_k, psens_out's and vjp_out's data derivative (E is
+    //     linear in qr; q+ = the new attitude).  Stage 0's rows move nothing (dx_0 is given).
+    // One riccati_sweep per direction over the stage and cost blocks the step left (barrier terms and pin weights included), with the
+    // gradients, the defects and dx_0 replaced; z' is the sweep's own forward solution: no costate pass.  A pinned row of dU is exactly 0
+    // (the sweep holds it within |B' p| / as_gamma of 0), as sens_out writes it.  The directions are rounds of one rolled loop: a round reads
+    // nothing an earlier one wrote but the data entries it replaces itself (the Hessian part of the sweep does not see them), so T
+    // directions in one call are T calls of one, bit for bit.
+    // LDS after the commit: qr and q+ in rows 0..3 / 6..9 of XI (as vjp_out), formed before the first tangent sweep overwrites ZX|ZU; the
+    // final set in AS.  A nonzero status or a failed factorisation: NaN in every output.
+    static NDP_D void jvp_out(const RtiParams &P, const LdsMap &m, const Tables &T, lp lds, const RtiIo &io, const ActSet &A, int zsrc,
+                              bool bad, const JvpIo &jo)
+    {
+        static_assert(!A_LDS, "the final set is parked in the AS area, which the five-slot kernels use");
+        const int N = horizon(P);
+        const int nxr = (N + 1) * NX, nur = N * NU, nf = (N + 1) * 3;
+        vi lane = W::lane_here();
+        auto nan_out = [&]() {
+            const vd nan = vd(__builtin_nan(""));
+            NDP_KEEP_LOOP
+            for (int d = 0; d < jo.T; ++d) {
+                NDP_KEEP_LOOP
+                for (int t = 0; t * 64 < nxr; ++t) {
+                    vi e = lane + 64 * t;
+                    if (jo.dX) W::gst(jo.dX, e + d * nxr, nan, e < nxr);
+                    if (jo.dU) W::gst(jo.dU, e + d * nur, nan, e < nur);
+                }
+                if (jo.du0) W::gst(jo.du0, lane + d * int(NU), nan, lane < int(NU));
+            }
+        };
+        if (bad) { nan_out(); return; }
+        // (vjp_out's parking of the set and of qr, q+, repeated as text -- a shared function changes the adjoint kernels: keep the two in step)
+        for (int t = 0; t < RUA; ++t) {                        // the final set, 0 / 1 per input bound
+            vi e = a_elem(P, lane, t);
+            W::st(lds, e + m.AS, W::sel(a_get(A, m, lds, t, e) == 0, vd(0.0), vd(1.0)));
+        }
+        NDP_KEEP_LOOP
+        for (int t = 0; t * 64 < 4 * (N + 1); ++t) {           // XI rows 0..3 <- qr_k, rows 6..9 <- q+_k (before a sweep overwrites ZX)
+            vi e = W::imin(lane + 64 * t, 4 * (N + 1) - 1), xo = (e >> 2) * int(NX) + 6 + (e & 3);
+            vd qr = W::gldu(io.xr, xo);
+            vd qp = W::ld(lds, xo + m.XI) + W::ld(lds, xo + zsrc);
+            W::st(lds, xo - 6 + m.XI, qr);
+            W::st(lds, xo + m.XI, qp);
+        }
+        W::sync();
+        const double h = P.dt;
+        NDP_KEEP_LOOP
+        for (int d = 0; d < jo.T; ++d) {
+            const vi ln = W::lane_here();                      // (an opaque lane id per round: nothing of a round's index arithmetic is held across the sweeps)
+            // this direction's data: state gradients and defects, one lane per (stage, row)
+            NDP_KEEP_LOOP
+            for (int t = 0; t * 64 < nxr; ++t) {
+                vi e = W::imin(ln + 64 * t, nxr - 1);
+                vi k = (e * 6554) >> 16, row = e - k * 10;     // e / 10, e < 16 384
+                vd tq[4] = {vd(0.0), vd(0.0), vd(0.0), vd(0.0)}, tr = vd(0.0);
+                if (jo.txr) {
+                    tr = W::gldu(jo.txr, e + d * nxr);
+                    for (int a = 0; a < 4; ++a) tq[a] = W::gldu(jo.txr, k * int(NX) + (6 + a + d * nxr));
+                }
+                vd q[4], v[4], em[4];
+                for (int a = 0; a < 4; ++a) {
+                    q[a] = W::ld(lds, k * int(NX) + (m.XI + a));
+                    v[a] = W::ld(lds, k * int(NX) + (m.XI + 6 + a));
+                    em[a] = W::sel(row == 6 + a, vd(1.0), vd(0.0));
+                }
+                vd ev[3], tv[3], ec[3], tc[3];                 // E(qr) q+, E(tqr) q+, column `row - 6` of E(qr) and of E(tqr)
+                emul(q, v, ev); emul(tq, v, tv); emul(q, em, ec); emul(tq, em, tc);
+                vd att = vd(0.0);
+                for (int a = 0; a < 3; ++a) att = att + (tc[a] * ev[a] + ec[a] * tv[a]) * P.Qd[7 + a];
+                const vd s = W::sel(k < N, vd(h), vd(1.0));
+                const vd qd = W::ld(lds, row + (m.KC + int(KC_QD)));
+                W::st(lds, k * int(CB_STRIDE) + row + (m.CB + int(CB_QE)), W::sel(row < 6, vd(0.0) - tr * qd * s, att * s));
+                const vi c3 = W::sel(row < 3, row, W::sel(row < 6, row - 3, vi(0))), kf = W::imin(k, vi(N - 1));
+                const vd tf = jo.tf ? W::gldu(jo.tf, kf * 3 + c3 + d * nf) * P.inv_mass : vd(0.0);
+                W::stp(lds, kf * int(MB_STRIDE) + row + (m.MB + int(MB_B)),
+                       W::sel(row < 3, tf * (0.5 * h * h), W::sel(row < 6, tf * h, vd(0.0))), k < N);
+            }
+            NDP_KEEP_LOOP
+            for (int t = 0; t * 64 < nur; ++t) {               // input gradients (pinned: 0)
+                vi e = W::imin(ln + 64 * t, nur - 1);
+                const vd tu = jo.tur ? W::gldu(jo.tur, e + d * nur) : vd(0.0);
+                const vb pin = !(W::ld(lds, e + m.AS) == 0.0);
+                const vd rd = W::ld(lds, (e & 3) + (m.KC + int(KC_RD)));
+                W::st(lds, (e >> 2) * int(CB_STRIDE) + (e & 3) + (m.CB + int(CB_RE)), W::sel(pin, vd(0.0), vd(0.0) - tu * rd * h));
+            }
+            {
+                const vi r = W::imin(ln, vi(NX - 1));
+                W::stp(lds, r + m.ZX, jo.tx0 ? W::gldu(jo.tx0, r + d * int(NX)) : vd(0.0), ln < int(NX));
+            }
+            W::sync();
+            // the interior point's last Newton system may carry barrier terms of 1e10: the sweep it takes then (as vjp_out)
+            bool ok;
+            if (zsrc != m.ZX && 14 * N + 10 >= 64) ok = riccati_sweep<false, true>(P, m, T, lds);
+            else ok = riccati_sweep(P, m, T, lds);
+            if (NDP_RARELY(!ok)) { nan_out(); return; }
+            NDP_KEEP_LOOP
+            for (int t = 0; t * 64 < nxr; ++t) {               // dX = z'_x (stage 0: tx0 as given), dU = z'_u, pinned rows 0; du0 = dU_0
+                vi e = W::imin(ln + 64 * t, nxr - 1), eu = W::imin(ln + 64 * t, nur - 1);
+                if (jo.dX) W::gst(jo.dX, e + d * nxr, W::ld(lds, e + m.ZX), ln + 64 * t < nxr);
+                const vd u = W::sel(W::ld(lds, eu + m.AS) == 0.0, W::ld(lds, eu + m.ZU), vd(0.0));
+                if (jo.dU) W::gst(jo.dU, eu + d * nur, u, ln + 64 * t < nur);
+                if (t == 0 && jo.du0) W::gst(jo.du0, eu + d * int(NU), u, ln < int(NU));
+            }
+        }
     }
     // E(q) w (build_cost's E of the attitude residual, linear in q)
     static NDP_D void emul(const vd q[4], const vd w[4], vd o[3])

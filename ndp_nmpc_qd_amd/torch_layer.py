@@ -21,6 +21,9 @@ with the upstream gradients (BatchedNMPC.step_vjp_device).  Same derivative as a
 downwash / control_step_ndp / NDPControlStep (at the end of this file) continue that adjoint through the downwash network: gradients of the
 neighbour windows and of the network's weights (BatchedNMPC.downwash_vjp_device).  The entry points above keep refusing other / ego_xy.
 
+control_step_jvp is the forward-mode counterpart (BatchedNMPC.step_jvp_device): the step, then the first-order change of (u0, X, U) along
+given directions of x0, xr, ur and f.  It returns plain tensors; there is no autograd hookup.
+
 control_step_tunable / TunableControlStep (behind them) differentiate the controller's own numbers -- the cost weights Qd, Rd and the mass --
 by the same adjoint (BatchedNMPC.set_model, step_vjp_device with gmodel).
 """
@@ -152,6 +155,29 @@ def control_step_trajectory(engine, x0, xr, ur, f=None, other=None, ego_xy=None)
     """(u0, X, U) = the engine's control step at x0 and its new iterate (the predicted trajectory), differentiable with respect to x0, xr,
     ur and f through the adjoint of the step (see ControlStepTrajectoryFunction); needs no sensitivities on."""
     return ControlStepTrajectoryFunction.apply(x0, engine, xr, ur, f, other, ego_xy)
+
+
+def control_step_jvp(engine, x0, xr, ur, tangents, f=None):
+    """(u0, X, U, du0, dX, dU): the engine's control step at x0 with its new iterate, and the first-order change of all three along the
+    directions tangents = (tx0, txr, tur, tf) (forward mode: BatchedNMPC.step_jvp_device; float64 CUDA tensors [B,T,...] or, for one
+    direction, [B,...]; None = 0).  The tape is recorded, the ordinary step runs, then the derivative on the same stream.  The outputs carry
+    the tangents' T axis: a tangent without it gives du0 [B,4], dX [B,N+1,10], dU [B,N,4].  No autograd hookup: nothing here is recorded in
+    a graph."""
+    det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t  # noqa: E731
+    x0, xr, ur, fd = det(x0), det(xr), det(ur), det(f)
+    tans = [None if t is None else det(t).to(torch.float64) for t in tangents]
+    given = [(t, n) for t, n in zip(tans, (2, 3, 3, 3)) if t is not None]
+    if not given:
+        raise ValueError("control_step_jvp: no tangent (tx0, txr, tur and tf all None)")
+    B, N = x0.shape[0], xr.shape[1] - 1
+    lead = (B,) + tuple({int(t.shape[1]) for t, n in given if t.dim() == n + 1})[:1]
+    stream, default = _cuda_stream(x0)
+    tape, u0, X, U = _taped_step(engine, stream, default, x0, xr, ur, f=fd)
+    du0, dX, dU = (torch.empty(lead + s, dtype=torch.float64, device=x0.device) for s in ((4,), (N + 1, 10), (N, 4)))
+    engine.step_jvp_device(x0, xr, ur, tape, *tans, f=fd, du0=du0, dX=dX, dU=dU, stream=stream)
+    if default:
+        engine.synchronize()
+    return u0, X, U, du0, dX, dU
 
 
 class ControlStep(torch.nn.Module):

@@ -8,6 +8,8 @@ one side stream, in one of these settings:
            does for a backward through every step
   model    as vjp, with BOTH adjoint launches behind every step on the same tape and upstream gradient -- ndp_step_vjp_device
            (rti_vjp_kernel) and ndp_step_vjp_model_device (rti_wvjp_kernel)
+  jvp1     the plain step with one tape recorded before it and one forward-mode launch behind it (rti_jvp_kernel) along ONE direction
+           (tx0, txr, tur and tf all given); jvp8: along eight directions in the one launch
 Run under rocprofv3 by scripts/deriv_cost.sh, which compares the kernels' durations."""
 import argparse
 import os
@@ -18,7 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--setting", choices=("off", "level1", "level2", "params", "vjp", "model"), default="off")
+    ap.add_argument("--setting", choices=("off", "level1", "level2", "params", "vjp", "model", "jvp1", "jvp8"), default="off")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--batch", type=int, default=1024)
     a = ap.parse_args()
@@ -41,15 +43,20 @@ def main():
     out = [torch.empty(*shape, dtype=torch.float64, device=dev) for shape in
            ((a.batch, 10), (a.batch, 21, 10), (a.batch, 20, 4), (a.batch, 21, 3), (a.batch, 16))]
     gmodels = {"vjp": (None,), "model": (None, out[4])}.get(a.setting, ())      # one adjoint launch behind the step for each
+    T = {"jvp1": 1, "jvp8": 8}.get(a.setting, 0)
+    tan = [torch.randn(a.batch, T, *shape, dtype=torch.float64, device=dev) for shape in ((10,), (21, 10), (20, 4), (21, 3))] if T else []
+    dout = [torch.empty(a.batch, T, *shape, dtype=torch.float64, device=dev) for shape in ((4,), (21, 10), (20, 4))] if T else []
     s.wait_stream(torch.cuda.current_stream(dev))
     with torch.cuda.stream(s):
         step = eng.bind_update_device(t["x0"], t["xr"], t["ur"], u0, other=t["other"], ego_xy=t["ego_xy"], stream=s)
         for _ in range(a.steps):
-            tape = eng.record_tape(s) if gmodels else None
+            tape = eng.record_tape(s) if gmodels or T else None
             step()
             for gm in gmodels:
                 eng.step_vjp_device(t["x0"], t["xr"], t["ur"], tape, gu0=g, f=eng.device_force(), gx0=out[0], gxr=out[1], gur=out[2],
                                     gf=out[3], gmodel=gm, stream=s)
+            if T:
+                eng.step_jvp_device(t["x0"], t["xr"], t["ur"], tape, *tan, f=eng.device_force(), du0=dout[0], dX=dout[1], dU=dout[2], stream=s)
     s.synchronize()
     eng.synchronize()
     st, it = eng.status()
