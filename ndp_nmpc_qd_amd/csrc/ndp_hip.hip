@@ -302,6 +302,22 @@ __global__ __launch_bounds__(64 * WAVES) void rti_psens_kernel(KernArgs ka, Sens
 #include "rti_kernel_body.inc"
 }
 
+// What the three kernels below share in front of their own Io: the wave's instance (a ragged last workgroup: its spare waves leave), its
+// views of the batch and its LDS, and the step's program.  Text, not a function (see rti_kernel_body.inc): a shared function changed all
+// six kernels' code, and so did issuing the step's first loads in front of the Io instead of behind it, so that call stays with each kernel.
+#define NDP_RECOMPUTE_PROLOGUE                                                                     \
+    extern __shared__ __attribute__((aligned(16))) double smem[];                                  \
+    const RtiParams &P = ka.P;                                                                     \
+    const int waves = (int)(blockDim.x >> 6), wave = (int)(threadIdx.x >> 6);                      \
+    const int inst = __builtin_amdgcn_readfirstlane((int)blockIdx.x * waves + wave);               \
+    if (inst >= ka.B) return;                                                                      \
+    const int N = NC ? NC : P.N;                                                                   \
+    RtiIo io;                                                                                      \
+    bind_instance(io, ka.bp, inst, N);                                                             \
+    const int lpw = NC ? ((lds_doubles(NC) + 1) & ~1) : ka.lds_per_wave;                           \
+    WaveGfx950::lds_ptr lds = (WaveGfx950::lds_ptr)(smem + (size_t)wave * lpw);                    \
+    using Prog = RtiWave<WaveGfx950, 3, NC, true, NC ? 1 : 0>;
+
 // The adjoint of the control step (ndp_step_vjp_device, RtiWave::vjp_out): the step's own program, recomputed from a caller's tape, then
 // the adjoint of its last QP contracted with the caller's upstream gradients.  The tape (the iterate and kept set before the step) has been
 // copied into the handle's VJP workspace by the host, so the recompute advances that copy: the kernel writes nothing but the workspace and
@@ -314,17 +330,7 @@ struct VjpArgs {
 template <int NC>
 __global__ __launch_bounds__(256) void rti_vjp_kernel(KernArgs ka, VjpArgs va)
 {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const RtiParams &P = ka.P;
-    const int waves = (int)(blockDim.x >> 6), wave = (int)(threadIdx.x >> 6);
-    const int inst = __builtin_amdgcn_readfirstlane((int)blockIdx.x * waves + wave);
-    if (inst >= ka.B) return;
-    const int N = NC ? NC : P.N;
-    RtiIo io;
-    bind_instance(io, ka.bp, inst, N);
-    const int lpw = NC ? ((lds_doubles(NC) + 1) & ~1) : ka.lds_per_wave;
-    WaveGfx950::lds_ptr lds = (WaveGfx950::lds_ptr)(smem + (size_t)wave * lpw);
-    using Prog = RtiWave<WaveGfx950, 3, NC, true, NC ? 1 : 0>;
+    NDP_RECOMPUTE_PROLOGUE
     const size_t i = (size_t)inst, nx = (size_t)(N + 1) * NX, nu = (size_t)N * NU, nf = (size_t)(N + 1) * 3;
     const VjpIo vo{va.gu0 ? va.gu0 + i * NU : nullptr, va.gX ? va.gX + i * nx : nullptr, va.gU ? va.gU + i * nu : nullptr,
                    va.gx0 ? va.gx0 + i * NX : nullptr, va.gxr ? va.gxr + i * nx : nullptr, va.gur ? va.gur + i * nu : nullptr,
@@ -341,17 +347,7 @@ __global__ __launch_bounds__(256) void rti_vjp_kernel(KernArgs ka, VjpArgs va)
 template <int NC>
 __global__ __launch_bounds__(256) void rti_wvjp_kernel(KernArgs ka, VjpArgs va, double *gmodel)
 {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const RtiParams &P = ka.P;
-    const int waves = (int)(blockDim.x >> 6), wave = (int)(threadIdx.x >> 6);
-    const int inst = __builtin_amdgcn_readfirstlane((int)blockIdx.x * waves + wave);
-    if (inst >= ka.B) return;
-    const int N = NC ? NC : P.N;
-    RtiIo io;
-    bind_instance(io, ka.bp, inst, N);
-    const int lpw = NC ? ((lds_doubles(NC) + 1) & ~1) : ka.lds_per_wave;
-    WaveGfx950::lds_ptr lds = (WaveGfx950::lds_ptr)(smem + (size_t)wave * lpw);
-    using Prog = RtiWave<WaveGfx950, 3, NC, true, NC ? 1 : 0>;
+    NDP_RECOMPUTE_PROLOGUE
     const size_t i = (size_t)inst, nx = (size_t)(N + 1) * NX, nu = (size_t)N * NU, nf = (size_t)(N + 1) * 3;
     const VjpIo vo{va.gu0 ? va.gu0 + i * NU : nullptr, va.gX ? va.gX + i * nx : nullptr, va.gU ? va.gU + i * nu : nullptr,
                    va.gx0 ? va.gx0 + i * NX : nullptr, va.gxr ? va.gxr + i * nx : nullptr, va.gur ? va.gur + i * nu : nullptr,
@@ -373,17 +369,7 @@ struct JvpArgs {
 template <int NC>
 __global__ __launch_bounds__(256) void rti_jvp_kernel(KernArgs ka, JvpArgs ja)
 {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const RtiParams &P = ka.P;
-    const int waves = (int)(blockDim.x >> 6), wave = (int)(threadIdx.x >> 6);
-    const int inst = __builtin_amdgcn_readfirstlane((int)blockIdx.x * waves + wave);
-    if (inst >= ka.B) return;
-    const int N = NC ? NC : P.N;
-    RtiIo io;
-    bind_instance(io, ka.bp, inst, N);
-    const int lpw = NC ? ((lds_doubles(NC) + 1) & ~1) : ka.lds_per_wave;
-    WaveGfx950::lds_ptr lds = (WaveGfx950::lds_ptr)(smem + (size_t)wave * lpw);
-    using Prog = RtiWave<WaveGfx950, 3, NC, true, NC ? 1 : 0>;
+    NDP_RECOMPUTE_PROLOGUE
     const size_t i = (size_t)inst * (size_t)ja.T, nx = (size_t)(N + 1) * NX, nu = (size_t)N * NU, nf = (size_t)(N + 1) * 3;
     const JvpIo jo{ja.tx0 ? ja.tx0 + i * NX : nullptr, ja.txr ? ja.txr + i * nx : nullptr, ja.tur ? ja.tur + i * nu : nullptr,
                    ja.tf ? ja.tf + i * nf : nullptr, ja.du0 ? ja.du0 + i * NU : nullptr, ja.dX ? ja.dX + i * nx : nullptr,
@@ -393,6 +379,8 @@ __global__ __launch_bounds__(256) void rti_jvp_kernel(KernArgs ka, JvpArgs ja)
     Prog::issue_first(P, io, inb, x0v);
     Prog::template run<false, true, false, false, false, false, true>(P, io, lds, inb, x0v, nullptr, nullptr, nullptr, nullptr, &jo);
 }
+
+#undef NDP_RECOMPUTE_PROLOGUE
 
 // test hook: one v_mfma_f64_16x16x4_f64 / v_mfma_f64_4x4x4_4b_f64 with caller-chosen per-lane operands (pins the register maps)
 __global__ void mfma_probe_kernel(const double *a, const double *b, const double *c, double *d)
@@ -3790,15 +3778,35 @@ void *ndp_device_sens_f(ndp_handle *h) { return h ? h->dPSensF : nullptr; }
 // ---- adjoint of the control step (rti_vjp_kernel, RtiWave::vjp_out)
 void *ndp_device_active_set(ndp_handle *h) { return h ? h->dAct : nullptr; }
 
-// What the derivative kernels that recompute a recorded step share (rti_vjp_kernel, rti_wvjp_kernel, rti_jvp_kernel): the handle's workspace
-// (first call), the tape copied into it on s -- never written: the recompute advances the copy, two calls on one tape give the same result --
-// and the step's kernel arguments on that copy.
-static int recompute_args(ndp_handle *h, hipStream_t s, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
-                          const void *d_X_lin, const void *d_U_lin, const void *d_act_lin, void *d_u0_check, void *d_status_check,
-                          KernArgs &ka)
+// What the derivative kernels that recompute a recorded step share (rti_vjp_kernel, rti_wvjp_kernel, rti_jvp_kernel).  Their entries take
+// the step's inputs and the tape it started from, never written (the recompute advances a copy: two calls on one tape give the same result),
+// and optionally return the recomputed u0 and status for the caller to check against the recorded ones.
+struct Tape {
+    const void *x0, *xr, *ur, *f, *X_lin, *U_lin, *act_lin;
+    void *u0_check, *status_check;
+};
+
+// The refusals all of those entries make, in their order: the configuration's and the required pointers', then `own` -- the entry's
+// refusals of its own arguments, or null -- then the force's.  Empty: none.  noun: what the entry's texts call the derivative.
+static std::string recompute_refusal(const ndp_cfg &c, const char *noun, const Tape &t, const char *own)
+{
+    const std::string the = std::string("the ") + noun;
+    if (c.n_rti != 1) return the + " needs n_rti = 1 (the derivative of the step's one QP)";
+    if (c.qp_precision != 0) return the + " needs qp_precision 0 (the fp64 product path)";
+    if (slots_for(c.N) > 3) return the + " is served for N <= 27 only (the five-slot kernels of N >= 28 have none)";
+    if (!t.x0 || !t.xr || !t.ur || !t.X_lin || !t.U_lin) return "x0, xr, ur and the tape's iterate (X_lin, U_lin) are required";
+    if (own) return own;
+    if (t.f && !c.use_fd) return "a disturbance force needs use_fd = 1 (NDP model)";
+    return "";
+}
+
+// The launch: the handle's workspace (first call), the tape copied into it on the entry's stream, the step's kernel arguments on that
+// copy, then the kernel for the horizon (fn20: the compile-time N = 20, else fn0) with a1, a2 behind them (a2: null if it takes two).
+static int recompute_launch(ndp_handle *h, Entry &g, const Tape &t, const void *fn20, const void *fn0, void *a1, void *a2)
 {
     const ndp_cfg &c = h->cfg;
     const size_t B = c.batch;
+    hipStream_t s = g.s;
     if (!h->dVjp) {
         NDP_HIP(h, hipMalloc((void **)&h->dVjp, (nxs(h) + nus(h) + B * NU) * 8));
         NDP_HIP(h, hipMalloc((void **)&h->dVjpSt, B * 2 * 4));
@@ -3806,50 +3814,36 @@ static int recompute_args(ndp_handle *h, hipStream_t s, const void *d_x0, const 
     }
     double *X = h->dVjp, *U = X + nxs(h), *u0 = U + nus(h);
     int *st = h->dVjpSt, *it = st + B;
-    NDP_HIP(h, hipMemcpyAsync(X, d_X_lin, nxs(h) * 8, hipMemcpyDeviceToDevice, s));
-    NDP_HIP(h, hipMemcpyAsync(U, d_U_lin, nus(h) * 8, hipMemcpyDeviceToDevice, s));
-    if (d_act_lin) NDP_HIP(h, hipMemcpyAsync(h->dVjpAct, d_act_lin, act_bytes(h), hipMemcpyDeviceToDevice, s));
+    NDP_HIP(h, hipMemcpyAsync(X, t.X_lin, nxs(h) * 8, hipMemcpyDeviceToDevice, s));
+    NDP_HIP(h, hipMemcpyAsync(U, t.U_lin, nus(h) * 8, hipMemcpyDeviceToDevice, s));
+    if (t.act_lin) NDP_HIP(h, hipMemcpyAsync(h->dVjpAct, t.act_lin, act_bytes(h), hipMemcpyDeviceToDevice, s));
     else NDP_HIP(h, hipMemsetAsync(h->dVjpAct, 0, act_bytes(h), s));
-    BatchPtrs bp{h->dKC, h->dTables, (const double *)d_x0, (const double *)d_xr, (const double *)d_ur, (const float *)d_f, X, U,
-                 d_u0_check ? (double *)d_u0_check : u0, d_status_check ? (int *)d_status_check : st, it, nullptr, nullptr, nullptr, nullptr,
+    BatchPtrs bp{h->dKC, h->dTables, (const double *)t.x0, (const double *)t.xr, (const double *)t.ur, (const float *)t.f, X, U,
+                 t.u0_check ? (double *)t.u0_check : u0, t.status_check ? (int *)t.status_check : st, it, nullptr, nullptr, nullptr, nullptr,
                  (size_t)(c.N + 1) * NX, (size_t)c.N * NU, (size_t)NX, nullptr, nullptr, nullptr, c.mass, 0, h->dVjpAct};
-    ka = KernArgs{h->P, bp, (int)B, h->lds_per_wave, MlpArgs{}, QueueArgs{}, LateArgs{}, TickArgs{}};
-    return 0;
-}
-
-// model: the entry is ndp_step_vjp_model_device (rti_wvjp_kernel; d_gmodel required), else ndp_step_vjp_device (rti_vjp_kernel)
-static int step_vjp(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
-                    const void *d_X_lin, const void *d_U_lin, const void *d_act_lin,
-                    const void *d_gu0, const void *d_gX, const void *d_gU,
-                    void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_u0_check, void *d_status_check, void *stream,
-                    bool model, void *d_gmodel)
-{
-    Entry g(h, true, stream);
-    if (g.rc) return g.rc;
-    const ndp_cfg &c = h->cfg;
-    const char *why = nullptr;                      // (the message behind the entry's name)
-    if (c.n_rti != 1) why = "the adjoint needs n_rti = 1 (the derivative of the step's one QP)";
-    else if (c.qp_precision != 0) why = "the adjoint needs qp_precision 0 (the fp64 product path)";
-    else if (slots_for(c.N) > 3) why = "the adjoint is served for N <= 27 only (the five-slot kernels of N >= 28 have none)";
-    else if (!d_x0 || !d_xr || !d_ur || !d_X_lin || !d_U_lin) why = "x0, xr, ur and the tape's iterate (X_lin, U_lin) are required";
-    else if (!d_gu0 && !d_gX && !d_gU) why = "no upstream gradient (gu0, gX and gU all NULL)";
-    else if (d_f && !c.use_fd) why = "a disturbance force needs use_fd = 1 (NDP model)";
-    else if (model && !d_gmodel) why = "gmodel is required (without it: ndp_step_vjp_device)";
-    if (why) { h->err = std::string(model ? "ndp_step_vjp_model_device: " : "ndp_step_vjp_device: ") + why; return -2; }
-    const size_t B = c.batch;
-    hipStream_t s = g.s;
-    KernArgs ka;
-    if (int rc = recompute_args(h, s, d_x0, d_xr, d_ur, d_f, d_X_lin, d_U_lin, d_act_lin, d_u0_check, d_status_check, ka)) return rc;
-    VjpArgs va{(const double *)d_gu0, (const double *)d_gX, (const double *)d_gU, (double *)d_gx0, (double *)d_gxr, (double *)d_gur,
-               (double *)d_gf};
+    KernArgs ka{h->P, bp, (int)B, h->lds_per_wave, MlpArgs{}, QueueArgs{}, LateArgs{}, TickArgs{}};
     const int W = h->waves;
-    const void *fn = model ? (c.N == 20 ? (const void *)rti_wvjp_kernel<20> : (const void *)rti_wvjp_kernel<0>)
-                           : (c.N == 20 ? (const void *)rti_vjp_kernel<20> : (const void *)rti_vjp_kernel<0>);
-    double *gm = (double *)d_gmodel;
-    void *args[] = {&ka, &va, &gm};                 // (rti_vjp_kernel takes the first two)
+    const void *fn = c.N == 20 ? fn20 : fn0;
+    void *args[] = {&ka, a1, a2};
     NDP_HIP(h, hipLaunchKernel(fn, dim3((unsigned)((B + W - 1) / W)), dim3(64 * W), args, (size_t)h->lds_per_wave * sizeof(double) * W, s));
     NDP_HIP(h, hipGetLastError());
     return g.noted(0);
+}
+
+// model: the entry is ndp_step_vjp_model_device (rti_wvjp_kernel; d_gmodel required), else ndp_step_vjp_device (rti_vjp_kernel)
+static int step_vjp(ndp_handle *h, const Tape &t, const void *d_gu0, const void *d_gX, const void *d_gU,
+                    void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *stream, bool model, void *d_gmodel)
+{
+    Entry g(h, true, stream);
+    if (g.rc) return g.rc;
+    std::string why = recompute_refusal(h->cfg, "adjoint", t, !d_gu0 && !d_gX && !d_gU ? "no upstream gradient (gu0, gX and gU all NULL)" : nullptr);
+    if (why.empty() && model && !d_gmodel) why = "gmodel is required (without it: ndp_step_vjp_device)";
+    if (!why.empty()) { h->err = std::string(model ? "ndp_step_vjp_model_device: " : "ndp_step_vjp_device: ") + why; return -2; }
+    VjpArgs va{(const double *)d_gu0, (const double *)d_gX, (const double *)d_gU, (double *)d_gx0, (double *)d_gxr, (double *)d_gur,
+               (double *)d_gf};
+    double *gm = (double *)d_gmodel;
+    if (model) return recompute_launch(h, g, t, (const void *)rti_wvjp_kernel<20>, (const void *)rti_wvjp_kernel<0>, &va, &gm);
+    return recompute_launch(h, g, t, (const void *)rti_vjp_kernel<20>, (const void *)rti_vjp_kernel<0>, &va, nullptr);
 }
 
 int ndp_step_vjp_device(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
@@ -3857,8 +3851,8 @@ int ndp_step_vjp_device(ndp_handle *h, const void *d_x0, const void *d_xr, const
                         const void *d_gu0, const void *d_gX, const void *d_gU,
                         void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_u0_check, void *d_status_check, void *stream)
 {
-    return step_vjp(h, d_x0, d_xr, d_ur, d_f, d_X_lin, d_U_lin, d_act_lin, d_gu0, d_gX, d_gU, d_gx0, d_gxr, d_gur, d_gf, d_u0_check,
-                    d_status_check, stream, false, nullptr);
+    return step_vjp(h, Tape{d_x0, d_xr, d_ur, d_f, d_X_lin, d_U_lin, d_act_lin, d_u0_check, d_status_check}, d_gu0, d_gX, d_gU, d_gx0, d_gxr,
+                    d_gur, d_gf, stream, false, nullptr);
 }
 
 int ndp_step_vjp_model_device(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
@@ -3867,8 +3861,8 @@ int ndp_step_vjp_model_device(ndp_handle *h, const void *d_x0, const void *d_xr,
                               void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_gmodel, void *d_u0_check, void *d_status_check,
                               void *stream)
 {
-    return step_vjp(h, d_x0, d_xr, d_ur, d_f, d_X_lin, d_U_lin, d_act_lin, d_gu0, d_gX, d_gU, d_gx0, d_gxr, d_gur, d_gf, d_u0_check,
-                    d_status_check, stream, true, d_gmodel);
+    return step_vjp(h, Tape{d_x0, d_xr, d_ur, d_f, d_X_lin, d_U_lin, d_act_lin, d_u0_check, d_status_check}, d_gu0, d_gX, d_gU, d_gx0, d_gxr,
+                    d_gur, d_gf, stream, true, d_gmodel);
 }
 
 // ---- forward mode of the control step (rti_jvp_kernel, RtiWave::jvp_out): the adjoint's recompute, workspace and tape rules
@@ -3879,30 +3873,17 @@ int ndp_step_jvp_device(ndp_handle *h, const void *d_x0, const void *d_xr, const
 {
     Entry g(h, true, stream);
     if (g.rc) return g.rc;
-    const ndp_cfg &c = h->cfg;
-    const char *why = nullptr;
-    if (c.n_rti != 1) why = "the derivative needs n_rti = 1 (the derivative of the step's one QP)";
-    else if (c.qp_precision != 0) why = "the derivative needs qp_precision 0 (the fp64 product path)";
-    else if (slots_for(c.N) > 3) why = "the derivative is served for N <= 27 only (the five-slot kernels of N >= 28 have none)";
-    else if (!d_x0 || !d_xr || !d_ur || !d_X_lin || !d_U_lin) why = "x0, xr, ur and the tape's iterate (X_lin, U_lin) are required";
-    else if (n_tan < 1 || n_tan > NDP_JVP_MAX_TANGENTS) why = "n_tan must be 1..8 (directions per call)";
-    else if (!d_tx0 && !d_txr && !d_tur && !d_tf) why = "no tangent (tx0, txr, tur and tf all NULL)";
-    else if (!d_du0 && !d_dX && !d_dU) why = "no output asked for (du0, dX and dU all NULL)";
-    else if (d_f && !c.use_fd) why = "a disturbance force needs use_fd = 1 (NDP model)";
-    else if (d_tf && !c.use_fd) why = "a force tangent needs use_fd = 1 (NDP model)";
-    if (why) { h->err = std::string("ndp_step_jvp_device: ") + why; return -2; }
-    const size_t B = c.batch;
-    hipStream_t s = g.s;
-    KernArgs ka;
-    if (int rc = recompute_args(h, s, d_x0, d_xr, d_ur, d_f, d_X_lin, d_U_lin, d_act_lin, d_u0_check, d_status_check, ka)) return rc;
+    const Tape t{d_x0, d_xr, d_ur, d_f, d_X_lin, d_U_lin, d_act_lin, d_u0_check, d_status_check};
+    const char *own = nullptr;
+    if (n_tan < 1 || n_tan > NDP_JVP_MAX_TANGENTS) own = "n_tan must be 1..8 (directions per call)";
+    else if (!d_tx0 && !d_txr && !d_tur && !d_tf) own = "no tangent (tx0, txr, tur and tf all NULL)";
+    else if (!d_du0 && !d_dX && !d_dU) own = "no output asked for (du0, dX and dU all NULL)";
+    std::string why = recompute_refusal(h->cfg, "derivative", t, own);
+    if (why.empty() && d_tf && !h->cfg.use_fd) why = "a force tangent needs use_fd = 1 (NDP model)";
+    if (!why.empty()) { h->err = "ndp_step_jvp_device: " + why; return -2; }
     JvpArgs ja{(const double *)d_tx0, (const double *)d_txr, (const double *)d_tur, (const double *)d_tf, (double *)d_du0, (double *)d_dX,
                (double *)d_dU, n_tan};
-    const int W = h->waves;
-    const void *fn = c.N == 20 ? (const void *)rti_jvp_kernel<20> : (const void *)rti_jvp_kernel<0>;
-    void *args[] = {&ka, &ja};
-    NDP_HIP(h, hipLaunchKernel(fn, dim3((unsigned)((B + W - 1) / W)), dim3(64 * W), args, (size_t)h->lds_per_wave * sizeof(double) * W, s));
-    NDP_HIP(h, hipGetLastError());
-    return g.noted(0);
+    return recompute_launch(h, g, t, (const void *)rti_jvp_kernel<20>, (const void *)rti_jvp_kernel<0>, &ja, nullptr);
 }
 
 // ---- the model of a live handle: cost weights and mass

@@ -230,17 +230,17 @@
     if (TICK && advance && active) tick_cache_store(ka.ta, te, inst, (int)(threadIdx.x & 63u), seg_refill, seg_fill, seg_cfill);   // (requested in the prologue: long there)
     if (TICK && ka.ta.est && active) io.kthr = tick_estimator(ka.ta, inst, B, (int)(threadIdx.x & 63u));
     bool deferred;
-    if constexpr (PSENS) {
-        // ... and of its parameter outputs (rti_psens_kernel)
-        const SensIo so{sa.du0 + (size_t)inst * sens_u0_pitch(), sa.dU ? sa.dU + (size_t)inst * sens_u_pitch(N) : nullptr,
-                        sa.dX ? sa.dX + (size_t)inst * sens_x_pitch(N) : nullptr, sa.level};
-        const PSensIo po{pa.dxr + (size_t)inst * psens_xr_pitch(N), pa.dur + (size_t)inst * psens_ur_pitch(N), pa.df + (size_t)inst * psens_f_pitch(N)};
-        deferred = Prog::template run<QMODE == 1, QMODE == 0 || QMODE == 3, true, true>(P, io, lds, inb, x0v, &so, &po);
-    } else if constexpr (SENS) {
+    if constexpr (SENS) {
         // the instance's views of the sensitivity outputs (QMODE 2: the listed instance this wave solves)
         const SensIo so{sa.du0 + (size_t)inst * sens_u0_pitch(), sa.dU ? sa.dU + (size_t)inst * sens_u_pitch(N) : nullptr,
                         sa.dX ? sa.dX + (size_t)inst * sens_x_pitch(N) : nullptr, sa.level};
-        deferred = Prog::template run<QMODE == 1, QMODE == 0 || QMODE == 3, true>(P, io, lds, inb, x0v, &so);
+        if constexpr (PSENS) {
+            // ... and of its parameter outputs (rti_psens_kernel)
+            const PSensIo po{pa.dxr + (size_t)inst * psens_xr_pitch(N), pa.dur + (size_t)inst * psens_ur_pitch(N), pa.df + (size_t)inst * psens_f_pitch(N)};
+            deferred = Prog::template run<QMODE == 1, QMODE == 0 || QMODE == 3, true, true>(P, io, lds, inb, x0v, &so, &po);
+        } else {
+            deferred = Prog::template run<QMODE == 1, QMODE == 0 || QMODE == 3, true>(P, io, lds, inb, x0v, &so);
+        }
     } else {
         deferred = Prog::template run<QMODE == 1, QMODE == 0 || QMODE == 3>(P, io, lds, inb, x0v);
     }

@@ -2313,6 +2313,8 @@ struct RtiWave {
         const vb blk = lane < 4 * int(NX), sq = lane < 16;
         // (the weights, before the constants area becomes staging)
         const vd qd = W::ld(lds, r + (m.KC + int(KC_QD))), rd = W::ld(lds, iu + (m.KC + int(KC_RD)));
+        // (this parking of the set and of qr, q+ stands as text here, in vjp_out and in jvp_out: keep the three in step.  One shared member
+        // called from the three changed all seven rti_psens_kernel instantiations and the six recompute kernels, registers unchanged)
         for (int t = 0; t < RUA; ++t) {                        // the final set, 0 / 1 per input bound
             vi e = a_elem(P, lane, t);
             W::st(lds, e + m.AS, W::sel(a_get(A, m, lds, t, e) == 0, vd(0.0), vd(1.0)));
@@ -2409,6 +2411,8 @@ struct RtiWave {
                 W::gst(po.df, fi * nf + fc + 3 * k, v, lane < 3 * int(NU));
             }
             {   // xr_k, lanes (r, i) < 40: rows 0..5 s Qd_r w_k[r][i]; rows 6..9 -s d/dqr_m (w' E' W E v) with v = q+_k, E = E(qr_k)
+                // (the attitude block, from v, q, em to att, stands as text here and in vjp_out: keep the two in step.  One shared member
+                // taking wq and r changed all seven rti_psens_kernel instantiations and the four adjoint kernels, registers unchanged)
                 vd wq[4], v[4], q[4], em[4];
                 for (int a = 0; a < 4; ++a) {
                     wq[a] = W::ld(lds, c + ((6 + a) * 4 + xk));
@@ -2490,7 +2494,7 @@ struct RtiWave {
             }
             for (int t = 0; t < RF; ++t) wf[t] = have_f ? W::gldfu(io.f, W::imin(lane + 64 * t, nf - 1)) : vd(0.0);
         }
-        // (this parking of the set and of qr, q+ is repeated as text in jvp_out -- a shared function changes the adjoint kernels: keep the two in step)
+        // (psens_out's parking of the set and of qr, q+, repeated as text here and in jvp_out: keep the three in step; why, there)
         for (int t = 0; t < RUA; ++t) {                        // the final set, 0 / 1 per input bound
             vi e = a_elem(P, lane, t);
             W::st(lds, e + m.AS, W::sel(a_get(A, m, lds, t, e) == 0, vd(0.0), vd(1.0)));
@@ -2525,7 +2529,8 @@ struct RtiWave {
         W::stp(lds, lane + m.ZX, vd(0.0), lane < int(NX));
         W::sync();
         // the interior point's last Newton system may carry barrier terms of 1e10: the sweep it takes then (lam_factor_ldl; its solves
-        // gather through 64 doubles of ZD, N >= 4)
+        // gather through 64 doubles of ZD, N >= 4).  (The choice stands as text here and in jvp_out: keep the two in step.  One shared member
+        // changed five of the six recompute kernels -- not rti_jvp_kernel<20> -- by 0 to 2 instructions, registers unchanged)
         bool ok;
         if (zsrc != m.ZX && 14 * N + 10 >= 64) ok = riccati_sweep<false, true>(P, m, T, lds);
         else ok = riccati_sweep(P, m, T, lds);
@@ -2563,6 +2568,7 @@ struct RtiWave {
                 W::gst(vo.gf, c + 3 * k, v, lane < 3);
             }
             if (vo.gxr) {   // xr_k, lanes r < 10: rows 0..5 s Qd_r v_k[r]; rows 6..9 -s d/dqr_r (v_q' E' W E q+) with E = E(qr_k)
+                // (psens_out's attitude block, repeated as text: keep the two in step; why, there)
                 vd wq[4], v[4], q[4], em[4];
                 for (int a = 0; a < 4; ++a) {
                     wq[a] = W::ld(lds, vi(xk + 6 + a));
@@ -2661,7 +2667,7 @@ struct RtiWave {
             }
         };
         if (bad) { nan_out(); return; }
-        // (vjp_out's parking of the set and of qr, q+, repeated as text -- a shared function changes the adjoint kernels: keep the two in step)
+        // (psens_out's parking of the set and of qr, q+, repeated as text here and in vjp_out: keep the three in step; why, there)
         for (int t = 0; t < RUA; ++t) {                        // the final set, 0 / 1 per input bound
             vi e = a_elem(P, lane, t);
             W::st(lds, e + m.AS, W::sel(a_get(A, m, lds, t, e) == 0, vd(0.0), vd(1.0)));
@@ -2720,7 +2726,8 @@ struct RtiWave {
                 W::stp(lds, r + m.ZX, jo.tx0 ? W::gldu(jo.tx0, r + d * int(NX)) : vd(0.0), ln < int(NX));
             }
             W::sync();
-            // the interior point's last Newton system may carry barrier terms of 1e10: the sweep it takes then (as vjp_out)
+            // the interior point's last Newton system may carry barrier terms of 1e10: the sweep it takes then (vjp_out's choice, repeated as
+            // text: keep the two in step; why, there)
             bool ok;
             if (zsrc != m.ZX && 14 * N + 10 >= 64) ok = riccati_sweep<false, true>(P, m, T, lds);
             else ok = riccati_sweep(P, m, T, lds);

@@ -1,6 +1,7 @@
 // step_deriv_emu.cpp -- the control step with each of its derivatives on the host wave emulator, one instance per call: the initial-state
 // sensitivities (RtiWave::run<..., SENS>, sens_out), the parameter sensitivities (<..., SENS, PSENS>, psens_out), the adjoint of its QP
-// (<..., VJP>, vjp_out) and the adjoint with the gradient in the cost weights and the mass (<..., VJP, WVJP>, vjp_out<true>).
+// (<..., VJP>, vjp_out), the adjoint with the gradient in the cost weights and the mass (<..., VJP, WVJP>, vjp_out<true>) and forward mode
+// (<..., JVP>, jvp_out; T directions per call).
 // TEST INFRASTRUCTURE ONLY: compiled by tests/step_deriv_emu.py into a temporary directory (tests/emu/ is left as it is).
 #include <vector>
 
@@ -36,21 +37,21 @@ bool setup(Setup &s, const ndp_cfg *cfg, const double *x0, const double *xr, con
     return true;
 }
 
-template <class Prog, bool SENS, bool PSENS, bool VJP, bool WVJP>
-void run_prog(Setup &s, const ndp::SensIo *so, const ndp::PSensIo *po, const ndp::VjpIo *vo, double *gmodel)
+template <class Prog, bool SENS, bool PSENS, bool VJP, bool WVJP, bool JVP>
+void run_prog(Setup &s, const ndp::SensIo *so, const ndp::PSensIo *po, const ndp::VjpIo *vo, double *gmodel, const ndp::JvpIo *jo)
 {
     typename Prog::InBuf inb;
     emu::vd x0v;
     Prog::issue_first(s.P, s.io, inb, x0v);
-    Prog::template run<false, false, SENS, PSENS, VJP, WVJP>(s.P, s.io, s.lds.data(), inb, x0v, so, po, vo, gmodel);
+    Prog::template run<false, false, SENS, PSENS, VJP, WVJP, JVP>(s.P, s.io, s.lds.data(), inb, x0v, so, po, vo, gmodel, jo);
 }
 
 // as the device runs them: N = 20 the compile-time horizon with host-built tables, other horizons the run-time form
-template <bool SENS, bool PSENS, bool VJP, bool WVJP>
-void run(Setup &s, const ndp::SensIo *so, const ndp::PSensIo *po, const ndp::VjpIo *vo, double *gmodel)
+template <bool SENS, bool PSENS, bool VJP, bool WVJP, bool JVP = false>
+void run(Setup &s, const ndp::SensIo *so, const ndp::PSensIo *po, const ndp::VjpIo *vo, double *gmodel, const ndp::JvpIo *jo = nullptr)
 {
-    if (s.P.N == 20) run_prog<ndp::RtiWave<emu::Wave, 3, 20, true, 1>, SENS, PSENS, VJP, WVJP>(s, so, po, vo, gmodel);
-    else run_prog<ndp::RtiWave<emu::Wave, 3, 0, true>, SENS, PSENS, VJP, WVJP>(s, so, po, vo, gmodel);
+    if (s.P.N == 20) run_prog<ndp::RtiWave<emu::Wave, 3, 20, true, 1>, SENS, PSENS, VJP, WVJP, JVP>(s, so, po, vo, gmodel, jo);
+    else run_prog<ndp::RtiWave<emu::Wave, 3, 0, true>, SENS, PSENS, VJP, WVJP, JVP>(s, so, po, vo, gmodel, jo);
 }
 
 }  // namespace
@@ -102,6 +103,19 @@ int wvjp_emu_step(const ndp_cfg *cfg, const double *x0, const double *xr, const 
     if (!gmodel || !setup(s, cfg, x0, xr, ur, f, X, U, u0, status, iters, act)) return -1;
     const ndp::VjpIo vo{gu0, gX, gU, gx0, gxr, gur, gf};
     run<false, false, true, true>(s, nullptr, nullptr, &vo, gmodel);
+    return 0;
+}
+
+// X, U, act: the tape, advanced in place as the step does; T directions tx0 [T][10], txr [T][N+1][10], tur [T][N][4], tf [T][N+1][3] (any
+// may be null); du0 [T][4], dX [T][N+1][10], dU [T][N][4] (any may be null)
+int jvp_emu_step(const ndp_cfg *cfg, int T, const double *x0, const double *xr, const double *ur, const float *f, double *X, double *U,
+                 double *u0, int *status, int *iters, signed char *act, const double *tx0, const double *txr, const double *tur,
+                 const double *tf, double *du0, double *dX, double *dU)
+{
+    Setup s;
+    if (T < 1 || !setup(s, cfg, x0, xr, ur, f, X, U, u0, status, iters, act)) return -1;
+    const ndp::JvpIo jo{tx0, txr, tur, tf, du0, dX, dU, T};
+    run<false, false, false, false, true>(s, nullptr, nullptr, nullptr, nullptr, &jo);
     return 0;
 }
 }

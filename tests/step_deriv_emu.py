@@ -25,6 +25,7 @@ def step_emu(tmp_path_factory):
         _lib.psens_emu_step.argtypes = [C.c_void_p] * 15
         _lib.vjp_emu_step.argtypes = [C.c_void_p] * 18
         _lib.wvjp_emu_step.argtypes = [C.c_void_p] * 19
+        _lib.jvp_emu_step.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 17
     return _lib
 
 
@@ -72,3 +73,13 @@ def _vjp(lib, cfg, x0, xr, ur, f, X, U, act, gu0=None, gX=None, gU=None, model=F
     if model:
         out += (np.full(16, -7.0),)
     return _step(lib.wvjp_emu_step if model else lib.vjp_emu_step, cfg, (), x0, xr, ur, f, X, U, act, up + out) + out
+
+
+def _jvp(lib, cfg, x0, xr, ur, f, X, U, act, tx0=None, txr=None, tur=None, tf=None):
+    """The tangents' T directions ([T, ...] each, None = 0): ... + (du0 [T,4], dX [T,N+1,10], dU [T,N,4])."""
+    N = cfg.N
+    tans = tuple(None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (tx0, txr, tur, tf))
+    T = next(a.shape[0] for a in tans if a is not None)
+    assert all(a is None or a.shape[0] == T for a in tans)
+    out = np.full((T, 4), -7.0), np.full((T, N + 1, 10), -7.0), np.full((T, N, 4), -7.0)
+    return _step(lib.jvp_emu_step, cfg, (T,), x0, xr, ur, f, X, U, act, tans + out) + out

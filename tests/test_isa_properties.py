@@ -52,9 +52,13 @@ def test_config5_kernels_have_no_scratch(co):
 
 def test_no_rti_kernel_instantiation_uses_scratch_memory(co):
     """All of them: run-time horizons (which spilled 320-376 B per lane through round 3), the fp32 / bf16 study kernels, every
-    compile-time shape."""
+    compile-time shape.  And the six kernels that recompute a recorded step for its adjoint, its model gradient and its forward mode."""
     k = {n: v for n, v in co.kernels().items() if "rti_kernel" in n}
     assert len(k) >= 20
+    for name in ("rti_vjp_kernel", "rti_wvjp_kernel", "rti_jvp_kernel"):       # each at <20> and <0>
+        recompute = {n: v for n, v in co.kernels().items() if name in n}
+        assert len(recompute) == 2, (name, sorted(recompute))
+        k.update(recompute)
     bad = {n: v for n, v in k.items() if v["scratch"] != 0}
     assert not bad, bad
 

@@ -1,14 +1,12 @@
 """The forward-mode derivative of the control step (RtiWave::jvp_out) without a GPU: the device's code on the host wave emulator against the
-dense fixed-set reference (tests/jvp_ref.py), against the adjoint on the same tape (duality), T directions against T calls, failed steps,
+dense fixed-set reference (tests/fixed_set_ref.py), against the adjoint on the same tape (duality), T directions against T calls, failed steps,
 pins, interior-point finishes, and the kernels' ISA.  The device side: tests/test_step_jvp_gpu.py."""
 import numpy as np
 import pytest
 
 from ndp_nmpc_qd_amd import synth
-from tests.fixed_set_ref import NU, NX, scale, vjp_ref
-from tests.jvp_ref import jvp_ref
-from tests.step_deriv_emu import MIXED, _tape, _vjp
-from tests.step_jvp_emu import _jvp, jvp_emu  # noqa: F401
+from tests.fixed_set_ref import NU, NX, jvp_ref, scale, vjp_ref
+from tests.step_deriv_emu import MIXED, _jvp, _tape, _vjp, step_emu  # noqa: F401
 
 
 def _tangents(rng, N, T, use_fd):
@@ -26,7 +24,7 @@ def _f64(f):
 
 @pytest.mark.parametrize("N,B,use_fd", [(2, 4, False), (2, 3, True), (13, 4, True), (13, 3, False), (20, 6, False), (20, 3, True),
                                         (27, 3, True), (27, 2, False)])
-def test_emulated_jvp_matches_the_dense_fixed_set_reference(oracle, jvp_emu, N, B, use_fd):
+def test_emulated_jvp_matches_the_dense_fixed_set_reference(oracle, step_emu, N, B, use_fd):
     """One random direction (tx0, txr, tur, tf) on the mixed workload (seed SEED0 + 40; inputs on their bounds among the instances): every
     set finish within 1e-10 of max(1, |z'|max) of jvp_ref at the step's final set; dX_0 = tx0 and du0 = dU_0 exactly, pinned rows of dU
     exactly 0; jvp_ref's two step sizes in the attitude reference agree to 1e-9."""
@@ -41,7 +39,7 @@ def test_emulated_jvp_matches_the_dense_fixed_set_reference(oracle, jvp_emu, N, 
         X, U, act = _tape(b, i, rng, N)
         f = _force(rng, N, use_fd)
         tan = _tangents(rng, N, 1, use_fd)
-        u0, Xn, Un, st, it, actn, du0, dX, dU = _jvp(jvp_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act, *tan)
+        u0, Xn, Un, st, it, actn, du0, dX, dU = _jvp(step_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act, *tan)
         assert st == 0
         if it & 0xffff:                                  # interior point: test_interior_point_finishes_...
             continue
@@ -59,7 +57,7 @@ def test_emulated_jvp_matches_the_dense_fixed_set_reference(oracle, jvp_emu, N, 
     assert checked >= 2
 
 
-def test_the_mixed_workload_holds_free_and_pinned_finishes(jvp_emu):
+def test_the_mixed_workload_holds_free_and_pinned_finishes(step_emu):
     """What the dense comparison above rests on, at N = 20: the first instances of the mixed workload finish free AND pinned."""
     from tests.emu import emu
     N, B = 20, 12
@@ -69,7 +67,7 @@ def test_the_mixed_workload_holds_free_and_pinned_finishes(jvp_emu):
     kinds = set()
     for i in range(B):
         X, U, act = _tape(b, i, rng, N)
-        out = _jvp(jvp_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], None, X, U, act, tx0=np.ones((1, 10)))
+        out = _jvp(step_emu, cfg, b["x0"][i], b["xr"][i], b["ur"][i], None, X, U, act, tx0=np.ones((1, 10)))
         if out[3] == 0 and not out[4] & 0xffff:
             kinds.add(bool(out[5].any()))
             assert not out[8][0][out[5].reshape(N, 4) != 0].any()
@@ -77,7 +75,7 @@ def test_the_mixed_workload_holds_free_and_pinned_finishes(jvp_emu):
 
 
 @pytest.mark.parametrize("N,use_fd,ipm", [(20, False, False), (13, True, False), (27, True, False), (20, False, True), (13, True, True)])
-def test_duality_with_the_adjoint_on_the_same_tape(jvp_emu, N, use_fd, ipm):
+def test_duality_with_the_adjoint_on_the_same_tape(step_emu, N, use_fd, ipm):
     """<gz, JVP(t)> = <VJP(gz), t> for random gz = (gu0, gX, gU) and t = (tx0, txr, tur, tf) against vjp_emu_step: both are solves with one K.
     Bar: 1e-11 of the larger side's magnitude (the largest |term| of either inner product, at least 1), for set finishes and for
     interior-point ones alike (ipm: qp_mode 1, the velocity box +-3): there too both solve ONE system, the last Newton system's, with the
@@ -100,8 +98,8 @@ def test_duality_with_the_adjoint_on_the_same_tape(jvp_emu, N, use_fd, ipm):
         tan = _tangents(rng, N, 1, use_fd)
         gu0, gX, gU = rng.normal(size=4), rng.normal(size=(N + 1, 10)), rng.normal(size=(N, 4))
         args = (cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act)
-        j = _jvp(jvp_emu, *args, *tan)
-        a = _vjp(jvp_emu, *args, gu0, gX, gU)
+        j = _jvp(step_emu, *args, *tan)
+        a = _vjp(step_emu, *args, gu0, gX, gU)
         for x, y in zip(j[:6], a[:6]):                   # the recompute is the same step
             assert np.array_equal(x, y)
         assert j[3] == 0
@@ -119,7 +117,7 @@ def test_duality_with_the_adjoint_on_the_same_tape(jvp_emu, N, use_fd, ipm):
 
 
 @pytest.mark.parametrize("N,use_fd", [(20, False), (13, True)])
-def test_three_directions_in_one_call_are_three_calls_bit_for_bit(jvp_emu, N, use_fd):
+def test_three_directions_in_one_call_are_three_calls_bit_for_bit(step_emu, N, use_fd):
     from tests.emu import emu
     B = 4
     b = synth.make_batch(B, N=N, seed=synth.SEED0 + 40, **MIXED)
@@ -130,15 +128,15 @@ def test_three_directions_in_one_call_are_three_calls_bit_for_bit(jvp_emu, N, us
         f = _force(rng, N, use_fd)
         tan = _tangents(rng, N, 3, use_fd)
         args = (cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act)
-        three = _jvp(jvp_emu, *args, *tan)
+        three = _jvp(step_emu, *args, *tan)
         assert three[3] == 0 and all(np.isfinite(v).all() for v in three[6:])
         for d in range(3):
-            one = _jvp(jvp_emu, *args, *(None if t is None else t[d:d + 1] for t in tan))
+            one = _jvp(step_emu, *args, *(None if t is None else t[d:d + 1] for t in tan))
             for x, y in zip(three[6:], one[6:]):
                 assert np.array_equal(x[d], y[0])
 
 
-def test_null_tangents_are_zero_and_null_outputs_are_left_alone(jvp_emu):
+def test_null_tangents_are_zero_and_null_outputs_are_left_alone(step_emu):
     """tx0 alone equals the full call with the other tangents 0, bit for bit; an output that is not asked for is not written."""
     from tests.emu import emu
     N = 13
@@ -148,25 +146,25 @@ def test_null_tangents_are_zero_and_null_outputs_are_left_alone(jvp_emu):
     X, U, act = _tape(b, 0, rng, N)
     tx0 = rng.normal(size=(2, 10))
     args = (cfg, b["x0"][0], b["xr"][0], b["ur"][0], _force(rng, N, True), X, U, act)
-    a = _jvp(jvp_emu, *args, tx0=tx0)
-    c = _jvp(jvp_emu, *args, tx0, np.zeros((2, N + 1, 10)), np.zeros((2, N, 4)), np.zeros((2, N + 1, 3)))
+    a = _jvp(step_emu, *args, tx0=tx0)
+    c = _jvp(step_emu, *args, tx0, np.zeros((2, N + 1, 10)), np.zeros((2, N, 4)), np.zeros((2, N + 1, 3)))
     for x, y in zip(a[6:], c[6:]):
         assert np.array_equal(x, y)
 
 
-def test_emulated_nan_state_gives_nan_tangents(jvp_emu):
+def test_emulated_nan_state_gives_nan_tangents(step_emu):
     from tests.emu import emu
     N = 20
     b = synth.make_batch(1, seed=synth.SEED0 + 40, **MIXED)
     cfg = emu.default_cfg()
     x0 = b["x0"][0].copy()
     x0[3] = np.nan
-    out = _jvp(jvp_emu, cfg, x0, b["xr"][0], b["ur"][0], None, b["xr"][0], b["ur"][0], np.zeros(4 * N, dtype=np.int8), tx0=np.ones((3, 10)))
+    out = _jvp(step_emu, cfg, x0, b["xr"][0], b["ur"][0], None, b["xr"][0], b["ur"][0], np.zeros(4 * N, dtype=np.int8), tx0=np.ones((3, 10)))
     assert out[3] != 0 and all(np.isnan(g).all() for g in out[6:])
 
 
 @pytest.mark.parametrize("N,use_fd", [(20, False), (13, True)])
-def test_interior_point_finishes_are_as_close_to_the_pinned_reference_as_the_adjoint(oracle, jvp_emu, N, use_fd):
+def test_interior_point_finishes_are_as_close_to_the_pinned_reference_as_the_adjoint(oracle, step_emu, N, use_fd):
     """qp_mode 1 with the velocity box shrunk to +-3 (the adjoint's interior-point instances, tests/test_step_vjp.py: seed SEED0 + 70 + N):
     the last Newton system is barrier-smoothed, so the reference pins the bounds that are active at the solution (within 1e-6), and the
     tangent's distance from jvp_ref (of max(1, |z'|max)) is held to 2 x the distance of the adjoint's outputs from vjp_ref on the same
@@ -191,11 +189,11 @@ def test_interior_point_finishes_are_as_close_to_the_pinned_reference_as_the_adj
         gu0, gX, gU = rng.normal(size=4), rng.normal(size=(N + 1, 10)), rng.normal(size=(N, 4))
         tan = _tangents(rng, N, 1, use_fd)
         args = (cfg, b["x0"][i], b["xr"][i], b["ur"][i], f, X, U, act)
-        j = _jvp(jvp_emu, *args, *tan)
+        j = _jvp(step_emu, *args, *tan)
         if j[3] != 0 or not (j[4] & 0xffff):
             continue
         n_ipm += 1
-        a = _vjp(jvp_emu, *args, gu0, gX, gU)
+        a = _vjp(step_emu, *args, gu0, gX, gU)
         Xn, Un = j[1].reshape(N + 1, NX), j[2].reshape(N, NU)
         qp = oracle.linearize(ocfg, b["x0"][i], b["xr"][i], b["ur"][i], _f64(f) if use_fd else None, X, U)
         lbu, ubu, lbv, ubv = (np.array(list(v)) for v in (cfg.lbu, cfg.ubu, cfg.lbv, cfg.ubv))

@@ -1,13 +1,12 @@
 """The forward-mode derivative of the control step on the device (run with -m gpu): rti_jvp_kernel against the dense fixed-set reference
-(tests/jvp_ref.py), ragged workgroups, duality against ndp_step_vjp_device, consistency with the level-2 and parameter sensitivities,
+(tests/fixed_set_ref.py), ragged workgroups, duality against ndp_step_vjp_device, consistency with the level-2 and parameter sensitivities,
 isolation (engine state and tape untouched, repeatable), refusals, and the torch layer.  CPU side: tests/test_step_jvp.py."""
 import numpy as np
 import pytest
 
 from ndp_nmpc_qd_amd import synth
 from tests.deriv_gpu import MIXED, _dev, _recorded_step, _t, _vjp, ndp  # noqa: F401
-from tests.fixed_set_ref import scale
-from tests.jvp_ref import jvp_apply, jvp_system
+from tests.fixed_set_ref import jvp_apply, jvp_system, scale
 
 pytestmark = pytest.mark.gpu
 
