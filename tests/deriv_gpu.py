@@ -1,5 +1,5 @@
 """What the device tests of the control step's derivatives share (tests/test_*_gpu.py): the package fixture, tensors on cuda:0, a recorded
-step with its tape, and step_vjp_device with -7.0-filled outputs."""
+step with its tape, step_vjp_device and step_jvp_device with -7.0-filled outputs, and random tangents."""
 import numpy as np
 import pytest
 
@@ -22,18 +22,45 @@ def _t(a, dtype=None):
     return torch.tensor(np.ascontiguousarray(a), device=_dev(), dtype=dtype)
 
 
-def _vjp(eng, x0, xr, ur, tape, f=None, gu0=None, gX=None, gU=None, model=False):
-    """step_vjp_device on torch tensors; returns numpy (gx0, gxr, gur, gf, u0_check, status_check[, gmodel])."""
+def _vjp(eng, x0, xr, ur, tape, f=None, gu0=None, gX=None, gU=None, model=False, guard=0):
+    """step_vjp_device on torch tensors; returns numpy (gx0, gxr, gur, gf, u0_check, status_check[, gmodel]).  guard: the outputs are the
+    first B rows of buffers with that many rows more, returned whole (the rows behind B keep their -7.0 / -1)."""
     import torch
     B, N = eng.B, eng.N
+    R = B + guard
     z = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device=_dev())  # noqa: E731
-    out = (z(B, 10), z(B, N + 1, 10), z(B, N, 4), z(B, N + 1, 3), z(B, 4))
-    st = torch.full((B,), -1, dtype=torch.int32, device=_dev())
-    gm = z(B, 16) if model else None
-    eng.step_vjp_device(x0, xr, ur, tape, gu0=gu0, gX=gX, gU=gU, f=f, gx0=out[0], gxr=out[1], gur=out[2], gf=out[3], u0_check=out[4],
-                        status_check=st, gmodel=gm)
+    out = (z(R, 10), z(R, N + 1, 10), z(R, N, 4), z(R, N + 1, 3), z(R, 4))
+    st = torch.full((R,), -1, dtype=torch.int32, device=_dev())
+    gm = z(R, 16) if model else None
+    eng.step_vjp_device(x0, xr, ur, tape, gu0=gu0, gX=gX, gU=gU, f=f, gx0=out[0][:B], gxr=out[1][:B], gur=out[2][:B], gf=out[3][:B],
+                        u0_check=out[4][:B], status_check=st[:B], gmodel=gm[:B] if model else None)
     torch.cuda.synchronize()
     return tuple(t.cpu().numpy() for t in out) + (st.cpu().numpy(),) + ((gm.cpu().numpy(),) if model else ())
+
+
+def _jvp(eng, x0, xr, ur, tape, T, f=None, tx0=None, txr=None, tur=None, tf=None, guard=0):
+    """step_jvp_device on torch tensors with -7.0-filled outputs; returns numpy (du0 [B,T,4], dX, dU, u0_check, status_check).  guard: as
+    _vjp's."""
+    import torch
+    B, N = eng.B, eng.N
+    R = B + guard
+    z = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device=_dev())  # noqa: E731
+    out = (z(R, T, 4), z(R, T, N + 1, 10), z(R, T, N, 4), z(R, 4))
+    st = torch.full((R,), -1, dtype=torch.int32, device=_dev())
+    eng.step_jvp_device(x0, xr, ur, tape, tx0=tx0, txr=txr, tur=tur, tf=tf, f=f, du0=out[0][:B], dX=out[1][:B], dU=out[2][:B],
+                        u0_check=out[3][:B], status_check=st[:B])
+    torch.cuda.synchronize()
+    return tuple(t.cpu().numpy() for t in out) + (st.cpu().numpy(),)
+
+
+def _tangents(seed, B, N, T, force=True):
+    rng = np.random.default_rng(seed)
+    return (rng.normal(size=(B, T, 10)), rng.normal(size=(B, T, N + 1, 10)), rng.normal(size=(B, T, N, 4)),
+            rng.normal(size=(B, T, N + 1, 3)) if force else None)
+
+
+def _tt(tan):
+    return dict(zip(("tx0", "txr", "tur", "tf"), (None if t is None else _t(t) for t in tan)))
 
 
 def _recorded_step(ndp, b, fused=False, f=None, params=False, **kw):

@@ -7,8 +7,11 @@ system of tests/ref_numpy.kkt_solve; z = (dx_0..dx_N, du_0..du_{N-1}), the new i
     d[z; nu]/dtheta = K^-1 (de'/dtheta - dK/dtheta [z; nu]),   e' = [-g; e],
 and for a loss L with gradient gz on z the adjoint [v; mu] solves K' [v; mu] = [gz; 0] and
     dL/dtheta = [v; mu]' (de'/dtheta - dK/dtheta [z; nu]).
-The bracket is `fd_column`: central differences of oracle.linearize, exact to rounding at any step where the data are at most quadratic in
-the parameter.  That holds for xr, ur and f (the attitude weight E(qr)' W E(qr) is quadratic; every term of dK is dH: the dynamics do not
+The bracket is a central difference of oracle.linearize, exact to rounding at any step where the data are at most quadratic in the
+parameter: `fd_column` on two dense systems for the sixteen model entries (model_grad_ref), and for the many entries of xr, ur and f
+(vjp_ref, psens_ref, jvp_ref: _param_columns) `fd_times`, the same difference on two block products K [z; nu] that never form K
+(`system_times`; tests/test_deriv_edges.py holds it to the dense product).  jvp_apply keeps the half-step attitude columns it forms in
+the dict jvp_system returned, so the directions of one system share them.  Exactness holds for xr, ur and f (the attitude weight E(qr)' W E(qr) is quadratic; every term of dK is dH: the dynamics do not
 see them -- included all the same) and for Qd and Rd (linear).  The force is differenced with the disturbance on (use_fd): it enters the
 defects additively, so the derivative is the same at any force, and at f = 0 without it.  In the mass the system is not polynomial (the
 force enters as f / m), but it is affine in u = 1 / m: the mass is differenced in u (cfg.mass = 1 / (u +- du)), exact to rounding as well
@@ -97,6 +100,32 @@ def fd_column(sa, sb, sol, step):
     return ((ra - rb) - (Ka - Kb) @ sol) / (2 * step)
 
 
+def system_times(qp, fixed, sol):
+    """(K sol, rhs) of system(qp, fixed) without forming K: the stage blocks applied one by one.  What the data columns difference (two
+    of these per parameter entry; tests/test_deriv_edges.py holds it to system()'s dense product)."""
+    A, B, b, Q, q, Rd, r, dx0 = (np.asarray(qp[k], dtype=np.float64) for k in ("A", "B", "b", "Q", "q", "Rd", "r", "dx0"))
+    N = A.shape[0]
+    nzx = (N + 1) * NX
+    nz = nzx + N * NU
+    dx, du, nu, npin = sol[:nzx].reshape(N + 1, NX), sol[nzx:nz].reshape(N, NU), sol[nz:nz + nzx].reshape(N + 1, NX), sol[nz + nzx:]
+    tx = np.einsum("kij,kj->ki", Q, dx) + nu                         # H z + E' nu, state rows
+    tx[:N] -= np.einsum("kji,kj->ki", A, nu[1:])
+    top = np.concatenate([tx.ravel(), (Rd * du - np.einsum("kji,kj->ki", B, nu[1:])).ravel()])
+    bx = dx.copy()                                                   # E z
+    bx[1:] -= np.einsum("kij,kj->ki", A, dx[:-1]) + np.einsum("kij,kj->ki", B, du)
+    z = sol[:nz]
+    for i, (v, _) in enumerate(fixed):
+        top[v] += npin[i]
+    out = np.concatenate([top, bx.ravel(), np.array([z[v] for v, _ in fixed])])
+    rhs = np.concatenate([-q.ravel(), -r.ravel(), dx0, b.ravel(), np.array([val for _, val in fixed])])
+    return out, rhs
+
+
+def fd_times(pa, pb, step):
+    """fd_column from two system_times results."""
+    return ((pa[1] - pb[1]) - (pa[0] - pb[0])) / (2 * step)
+
+
 def _adjoint(K, nz, N, gu0, gX, gU):
     return np.linalg.solve(K.T, np.concatenate([upstream(N, gu0, gX, gU), np.zeros(K.shape[0] - nz)]))
 
@@ -118,15 +147,20 @@ def _param_columns(oracle, cfg, x0, xr, ur, f, X, U, act, extra, h):
 
     K, rhs0, nz, fixed = sysf(cfg, xr, ur, f)
     sol = np.linalg.solve(K, rhs0)
+
+    def times(c, a, b_, ff):
+        qp = oracle.linearize(c, x0, a, b_, ff if c.use_fd else None, X, U)
+        return system_times(qp, fixed_of(qp, A) + extra, sol)
+
     cols = []
     for which, base in (("xr", xr), ("ur", ur), ("f", f)):
         cols.append([])
         for j in range(base.size):
             d = np.zeros(base.size)
             d[j] = h
-            sa, sb = (sysf(cfg, pa, ur, f) if which == "xr" else sysf(cfg, xr, pa, f) if which == "ur" else sysf(cfd, xr, ur, pa)
+            sa, sb = (times(cfg, pa, ur, f) if which == "xr" else times(cfg, xr, pa, f) if which == "ur" else times(cfd, xr, ur, pa)
                       for pa in (base + d.reshape(base.shape), base - d.reshape(base.shape)))
-            cols[-1].append(fd_column(sa, sb, sol, h))
+            cols[-1].append(fd_times(sa, sb, h))
     return K, nz, sol, fixed, cols, xr, ur, f
 
 
@@ -150,32 +184,40 @@ def sens_ref(qp, act=None):
     return dU[0].copy(), dU, dX
 
 
-def psens_ref(oracle, cfg, x0, xr, ur, f, X, U, act=None, h=0.125):
-    """Returns (dxr [4,N+1,10], dur [4,N,4], df [4,N+1,3]): row i = d u0[i] / d(parameter) of the QP oracle.linearize builds at the
-    iterate (X, U), the pinned inputs of act (int8 [N,4] or None) held at their bounds."""
-    N = cfg.N
-    K, nz, _, fixed, cols, _, _, _ = _param_columns(oracle, cfg, x0, xr, ur, f, X, U, act, [], h)
+def psens_apply(c):
+    """psens_ref from jvp_system's dict (one set of data columns serves every derivative of one linearisation)."""
+    N, K, nz, cols, fixed = c["N"], c["K"], c["nz"], c["cols"], c["fixed"]
     dz = np.linalg.solve(K, np.stack(cols[0] + cols[1] + cols[2], axis=1))[:nz]
     du0 = dz[(N + 1) * NX:(N + 1) * NX + NU]            # [4, n_params]
     n1, n2 = (N + 1) * NX, N * NU
     for v, _ in fixed:                                  # exactly 0, as the device writes them
-        if v < (N + 1) * NX + NU:
+        if (N + 1) * NX <= v < (N + 1) * NX + NU:
             du0[v - (N + 1) * NX] = 0.0
     return (du0[:, :n1].reshape(NU, N + 1, NX).copy(), du0[:, n1:n1 + n2].reshape(NU, N, NU).copy(),
             du0[:, n1 + n2:].reshape(NU, N + 1, 3).copy())
+
+
+def psens_ref(oracle, cfg, x0, xr, ur, f, X, U, act=None, h=0.125):
+    """Returns (dxr [4,N+1,10], dur [4,N,4], df [4,N+1,3]): row i = d u0[i] / d(parameter) of the QP oracle.linearize builds at the
+    iterate (X, U), the pinned inputs of act (int8 [N,4] or None) held at their bounds."""
+    return psens_apply(jvp_system(oracle, cfg, x0, xr, ur, f, X, U, act, h))
+
+
+def vjp_apply(c, gu0=None, gX=None, gU=None):
+    """vjp_ref from jvp_system's dict."""
+    N, K, nz, cols = c["N"], c["K"], c["nz"], c["cols"]
+    adj = _adjoint(K, nz, N, gu0, gX, gU)
+    gxr, gur, gf = (np.array([adj @ col for col in cs]).reshape(base.shape) for cs, base in zip(cols, (c["xr"], c["ur"], c["f"])))
+    if c["act"] is not None:                            # exactly 0, as the device writes them
+        gur[c["act"] != 0] = 0.0
+    return adj[nz:nz + NX].copy(), gxr, gur, gf
 
 
 def vjp_ref(oracle, cfg, x0, xr, ur, f, X, U, act=None, gu0=None, gX=None, gU=None, h=0.125, pin_v=None):
     """Returns (gx0 [10], gxr [N+1,10], gur [N,4], gf [N+1,3]) of L = gz' z* for the QP at the iterate (X, U) with the pinned inputs of act
     (int8 [N,4] or None) held at their bounds.  pin_v: optional list of (variable index, value) pins added to act's (the interior-point
     comparison pins the active velocity bounds too)."""
-    N = cfg.N
-    K, nz, _, _, cols, xr, ur, f = _param_columns(oracle, cfg, x0, xr, ur, f, X, U, act, list(pin_v or []), h)
-    adj = _adjoint(K, nz, N, gu0, gX, gU)
-    gxr, gur, gf = (np.array([adj @ c for c in cs]).reshape(base.shape) for cs, base in zip(cols, (xr, ur, f)))
-    if act is not None:                                 # exactly 0, as the device writes them
-        gur[np.asarray(act).reshape(N, NU) != 0] = 0.0
-    return adj[nz:nz + NX].copy(), gxr, gur, gf
+    return vjp_apply(jvp_system(oracle, cfg, x0, xr, ur, f, X, U, act, h, pin_v), gu0, gX, gU)
 
 
 def _perturbed(cfg, j, d):
@@ -228,9 +270,9 @@ def jvp_system(oracle, cfg, x0, xr, ur, f, X, U, act=None, h=0.125, pin_v=None):
 
     def sysf(a):
         qp = oracle.linearize(cfg, x0, a, ur64, f64 if cfg.use_fd else None, X, U)
-        return system(qp, fixed_of(qp, A) + extra)
+        return system_times(qp, fixed_of(qp, A) + extra, sol)
 
-    return dict(N=cfg.N, K=K, nz=nz, sol=sol, fixed=fixed, cols=cols, xr=xr64, sysf=sysf, h=h)
+    return dict(N=cfg.N, K=K, nz=nz, sol=sol, fixed=fixed, cols=cols, xr=xr64, ur=ur64, f=f64, act=A, sysf=sysf, h=h)
 
 
 def jvp_apply(c, tx0=None, txr=None, tur=None, tf=None):
@@ -255,10 +297,12 @@ def jvp_apply(c, tx0=None, txr=None, tur=None, tf=None):
     if txr is not None:
         c2 = list(cols[0])
         for j in (j for j in range(nzx) if j % NX >= 6 and tans[0][j] != 0.0):
-            d = np.zeros(nzx)
-            d[j] = 0.5 * h
-            d = d.reshape(c["xr"].shape)
-            c2[j] = fd_column(c["sysf"](c["xr"] + d), c["sysf"](c["xr"] - d), c["sol"], 0.5 * h)
+            if j not in c.setdefault("half", {}):                       # (kept: the directions of one system share them)
+                d = np.zeros(nzx)
+                d[j] = 0.5 * h
+                d = d.reshape(c["xr"].shape)
+                c["half"][j] = fd_times(c["sysf"](c["xr"] + d), c["sysf"](c["xr"] - d), 0.5 * h)
+            c2[j] = c["half"][j]
         dz2 = solve([c2, cols[1], cols[2]])
     dX, dU = dz[:nzx].reshape(N + 1, NX), dz[nzx:].reshape(N, NU)
     return dU[0].copy(), dX, dU, dz2

@@ -51,11 +51,11 @@ def _step(entry, cfg, lead, x0, xr, ur, f, X, U, act, tail):
     return u0, X, U, st.value, it.value, act
 
 
-def _emu_step(lib, cfg, level, x0, xr, ur, X, U, act):
-    """Initial-state sensitivities at `level`: ... + (du0, dU, dX)."""
+def _emu_step(lib, cfg, level, x0, xr, ur, X, U, act, f=None):
+    """Initial-state sensitivities at `level` (f: the step's fp32 force, with use_fd): ... + (du0, dU, dX)."""
     N = cfg.N
     out = np.full((4, 10), -7.0), np.full((N, 4, 10), -7.0), np.full((N + 1, 10, 10), -7.0)
-    return _step(lib.sens_emu_step, cfg, (level,), x0, xr, ur, None, X, U, act, out) + out
+    return _step(lib.sens_emu_step, cfg, (level,), x0, xr, ur, f, X, U, act, out) + out
 
 
 def _psens(lib, cfg, x0, xr, ur, f, X, U, act):

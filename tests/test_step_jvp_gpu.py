@@ -5,33 +5,10 @@ import numpy as np
 import pytest
 
 from ndp_nmpc_qd_amd import synth
-from tests.deriv_gpu import MIXED, _dev, _recorded_step, _t, _vjp, ndp  # noqa: F401
+from tests.deriv_gpu import MIXED, _dev, _jvp, _recorded_step, _t, _tangents, _tt, _vjp, ndp  # noqa: F401
 from tests.fixed_set_ref import jvp_apply, jvp_system, scale
 
 pytestmark = pytest.mark.gpu
-
-
-def _jvp(eng, x0, xr, ur, tape, T, f=None, tx0=None, txr=None, tur=None, tf=None):
-    """step_jvp_device on torch tensors with -7.0-filled outputs; returns numpy (du0 [B,T,4], dX, dU, u0_check, status_check)."""
-    import torch
-    B, N = eng.B, eng.N
-    z = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device=_dev())  # noqa: E731
-    out = (z(B, T, 4), z(B, T, N + 1, 10), z(B, T, N, 4), z(B, 4))
-    st = torch.full((B,), -1, dtype=torch.int32, device=_dev())
-    eng.step_jvp_device(x0, xr, ur, tape, tx0=tx0, txr=txr, tur=tur, tf=tf, f=f, du0=out[0], dX=out[1], dU=out[2], u0_check=out[3],
-                        status_check=st)
-    torch.cuda.synchronize()
-    return tuple(t.cpu().numpy() for t in out) + (st.cpu().numpy(),)
-
-
-def _tangents(seed, B, N, T, force=True):
-    rng = np.random.default_rng(seed)
-    return (rng.normal(size=(B, T, 10)), rng.normal(size=(B, T, N + 1, 10)), rng.normal(size=(B, T, N, 4)),
-            rng.normal(size=(B, T, N + 1, 3)) if force else None)
-
-
-def _tt(tan):
-    return dict(zip(("tx0", "txr", "tur", "tf"), (None if t is None else _t(t) for t in tan)))
 
 
 @pytest.fixture(scope="module")
