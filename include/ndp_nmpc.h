@@ -479,7 +479,7 @@ int ndp_ref_window_device(ndp_handle *h, const void *d_t, void *d_xr, void *d_ur
  *   *_device            : the two halves separately, on device buffers.  The list position is host state baked into each
  *                         launch's arguments: these calls must NOT be captured into a hipGraph (a replay would reuse the
  *                         position of the captured tick); ndp_ref_window_device has no such state and is capturable.
- * Device layout: phase-major, every entry stored twice, so that every window is contiguous (csrc/ndp_hip.hip: RingGeom) -- the
+ * Device layout: phase-major, every entry stored twice, so that every window is contiguous (csrc/kern_args.hpp: RingGeom) -- the
  * stand-alone window call is a dense copy and ndp_tick's control step reads its windows in place. */
 int ndp_ref_list_reset(ndp_handle *h);
 int ndp_ref_list_fix_pt(ndp_handle *h, const double *x_odom, int quirk_b1);
@@ -685,7 +685,7 @@ int ndp_debug_host_timing(ndp_handle *h, double *out4);
  * cgroup CPU quota), pack threads the handle started (-1: no host-array step yet)}. */
 int ndp_debug_host_info(ndp_handle *h, int32_t *out3);
 /* Test hook: which control-step kernels this handle has launched.  mask (or NULL) receives the rows of the library's kernel table
- * (enum RtiId in csrc/ndp_hip.hip) launched since the last call, as bit RtiId, and reading clears it; a step captured into a graph
+ * (enum RtiId in csrc/rti_table.hpp) launched since the last call, as bit RtiId, and reading clears it; a step captured into a graph
  * counts once, at capture.  out3 (or NULL) = {rows of the table, instances per workgroup, 1 if the downwash network can run inside
  * the control step's launch (else a separate launch first)}. */
 int ndp_debug_rti_launched(ndp_handle *h, uint64_t *mask, int32_t *out3);

@@ -215,8 +215,8 @@ def lds_layout(N):
     return dict(zip(("XI", "MB", "CB", "MB_STRIDE", "CB_STRIDE", "total", "stamps"), list(out)[:7]))
 
 
-def rti_kernel_names(src=os.path.join(_HERE, "csrc", "ndp_hip.hip")):
-    """The rows of the library's control-step kernel table in RtiId order (enum RtiId in csrc/ndp_hip.hip; bit i of
+def rti_kernel_names(src=os.path.join(_HERE, "csrc", "rti_table.hpp")):
+    """The rows of the library's control-step kernel table in RtiId order (enum RtiId in csrc/rti_table.hpp; bit i of
     ndp_debug_rti_launched's mask is row i)."""
     import re
     with open(src) as fh:

@@ -799,7 +799,7 @@ class BatchedNMPC:
         self._check(self._lib.ndp_synchronize(self._h), "ndp_synchronize")
 
     def debug_rti_launched(self):
-        """(names, waves, fusable): the rows of the control-step kernel table (csrc/ndp_hip.hip: enum RtiId) this handle launched since
+        """(names, waves, fusable): the rows of the control-step kernel table (csrc/rti_table.hpp: enum RtiId) this handle launched since
         the last call (ndp_debug_rti_launched; reading clears them), its instances per workgroup, and whether the downwash network can
         run inside the control step's launch."""
         mask, out = C.c_uint64(0), np.zeros(3, dtype=np.int32)

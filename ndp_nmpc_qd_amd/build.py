@@ -10,8 +10,9 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libndp_nmpc_hip.so")
-# the translation units (csrc/host.hpp: which one owns what); ndp_hip.hip first, it is by far the longest compile
-UNITS = ["ndp_hip.hip", "exchange.hip", "mlp_vjp.hip"]
+# the translation units (csrc/host.hpp: which one owns what); rti_kernels.hip first, it is by far the longest compile
+UNITS = ["rti_kernels.hip", "ndp_hip.hip", "downwash.hip", "rows.hip", "tick.hip", "exchange.hip", "mlp_vjp.hip"]
+HOST_ONLY = {"tick.hip"}      # units without a kernel: compiled for the host only, so that no empty code object goes into the library
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))) + [os.path.join("..", "..", "include", "ndp_nmpc.h")]   # every header a unit can include
 # -amdgpu-mfma-vgpr-form: MFMA results go straight to VGPRs.  With the default AGPR form every accumulator that is
 # live across a basic block or feeds VALU/LDS is copied through v_accvgpr_read/write behind full-latency s_nops,
@@ -42,7 +43,7 @@ def build(force=False, verbose=False, out=LIB, extra=()):
 
     def compile_unit(job):
         u, o = job
-        cmd = ["hipcc"] + flags + ["-c", "-o", o, os.path.join(CSRC, u)]
+        cmd = ["hipcc"] + flags + (["--cuda-host-only"] if u in HOST_ONLY else []) + ["-c", "-o", o, os.path.join(CSRC, u)]
         if verbose:
             print(" ".join(cmd), flush=True)
         return subprocess.run(cmd, cwd=CSRC).returncode

@@ -1,8 +1,18 @@
 // host.hpp -- the private host interface of the library's translation units: the handle, the entry-point frame and the host functions
 // one unit calls in another.
-//   ndp_hip.hip   the kernels but the exchange's, the handle's runtime, the steps, the rows (f1 - f4), the tick, the sensitivities
-//   mlp_vjp.hip   the downwash network's backward pass (ndp_downwash_vjp_device) and its weights set from device memory
-//   exchange.hip  peer-mapped windows (ndp_peer_*), the RCCL exchange (ndp_xchg_*) and the remote tick one control period ahead
+//   rti_kernels.hip  the control-step kernels (rti_*_kernel), their table k_rti (rows: rti_table.hpp) and its launcher; first in build.UNITS,
+//                    by far the longest compile -- no other unit names one of its kernels.  Also mfma_probe*_kernel, mlp_kernel and
+//                    tick_pre_kernel with their launchers: they share inlined device functions with the control-step kernels, and apart
+//                    from them the compiler specialises those functions (different code for them and for the one-launch ticks)
+//   ndp_hip.hip      the handle's runtime: pack threads, create / destroy, every step form (enqueue_step, launch_rti, rti_pick), the
+//                    host-array step, timing, the sensitivities, the adjoint / forward-mode entry points, ndp_set_model, the debug hooks
+//   downwash.hip     the downwash network's forward entry points, mlp_stream_kernel + the prefetch protocol, ndp_set_mlp_weights
+//   rows.hip         the rows f1 - f4: reference window and list, follower relay, throttle estimator, actuator command, plant, rollout
+//   tick.hip         the control tick's host side (ndp_tick*); no kernel: compiled for the host only
+//   mlp_vjp.hip      the downwash network's backward pass (ndp_downwash_vjp_device) and its weights set from device memory
+//   exchange.hip     peer-mapped windows (ndp_peer_*), the RCCL exchange (ndp_xchg_*) and the remote tick one control period ahead
+// A kernel sits with the host code that launches it; device code that two units' kernels inline is a header (mlp_tile.hpp, ref_point.hpp,
+// tick_wave.hpp), and so are the argument blocks the host fills (kern_args.hpp).
 // The functions declared below are NDP_HIDDEN: the library exports the C-ABI of include/ndp_nmpc.h and nothing more.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -17,6 +27,7 @@
 #include "wave_gfx950.hpp"   // defines the device qualifiers, must precede rti_wave.hpp
 #include "cfg_params.hpp"
 #include "kern_args.hpp"
+#include "rti_table.hpp"
 
 #define NDP_HIDDEN __attribute__((visibility("hidden")))
 
@@ -153,15 +164,95 @@ static inline int mlp_vjp_groups(const ndp_handle *h)
 
 enum { TICK_ESTIMATE = NDP_TICK_ESTIMATE, TICK_WANT_U0 = NDP_TICK_WANT_U0, TICK_T_UNIFORM = NDP_TICK_T_UNIFORM };
 
+// ---- file-local helpers several units need
+static inline size_t nxs(const ndp_handle *h) { return (size_t)h->cfg.batch * (h->cfg.N + 1) * NX; }
+static inline size_t nus(const ndp_handle *h) { return (size_t)h->cfg.batch * h->cfg.N * NU; }
+static inline size_t nfs(const ndp_handle *h) { return (size_t)h->cfg.batch * (h->cfg.N + 1) * 3; }
+static inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+static inline size_t act_bytes(const ndp_handle *h) { return (size_t)h->cfg.batch * (size_t)act_pitch(h->cfg.N); }
+// The trajectory block dTraj (ndp_ref_set_trajectory), one allocation of `doubles`, in this order: coefficients [B][S][28] (x, y, z: 8
+// each, yaw: 4) | time_cum [B][S+1] | time_seg [B][S] | final_pt [B][3] | the one-launch tick's segment cache [B][SEGC_PER] (empty =
+// NaNs: tick_early) | the segment hints int[B] (ref_point) | the cache's second copy [B][SEGC_PER] (tick_cache_store).  base = null:
+// the size only.
+struct TrajView {
+    double *coeff, *tcum, *tseg, *fpt, *segc[2];
+    int *hint;
+    size_t doubles;
+};
+static inline TrajView traj_view(double *base, size_t B, size_t S)
+{
+    TrajView v;
+    size_t o = 0;
+    auto part = [&](size_t n) { double *p = base ? base + o : nullptr; o += n; return p; };
+    v.coeff = part(B * S * 28); v.tcum = part(B * (S + 1)); v.tseg = part(B * S); v.fpt = part(B * 3);
+    v.segc[0] = part(B * SEGC_PER); v.hint = reinterpret_cast<int *>(part((B * 4 + 7) / 8)); v.segc[1] = part(B * SEGC_PER);
+    v.doubles = o;
+    return v;
+}
+static inline TrajView traj_view(const ndp_handle *h) { return traj_view(h->dTraj, (size_t)h->cfg.batch, (size_t)h->traj_seg); }
+// the step's iteration words (RtiIo::iters) -> the caller's interior-point iteration counts
+static inline void copy_ipm_iters(int32_t *dst, const int32_t *src, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) dst[i] = src[i] & ITERS_IPM_MASK;
+}
+
+struct Neigh {                 // neighbour windows of a step (device pointers)
+    const double *other = nullptr;
+    int stride = NX;           // doubles per node: 10 or 6
+    const int *index = nullptr;
+    const double *ego_xy = nullptr;
+    size_t pitch = 0;          // doubles between rows of `other`; 0 = dense, (N+1) stride
+    size_t ego_pitch = 0;      // doubles between instances of ego_xy; 0 = dense, 2
+};
+
+struct StepOut {               // where a step's status / iteration counts go and whether the new iterate is mirrored (device-accessible
+    int *status = nullptr;     // pointers; null = the handle's HBM block / no mirror): the host-array step of small batches points
+    int *iters = nullptr;      // them into a page-locked host block
+    double *Xm = nullptr, *Um = nullptr;
+    hipEvent_t done = nullptr; // marked by the step's last launch through its own dispatch packet (no event packet behind it), or null
+    size_t xr_pitch = 0, ur_pitch = 0;   // doubles between the instances' reference windows; 0 = dense arrays (see BatchPtrs)
+    double *cmd = nullptr;               // ndp_tick: the actuator command written by the control step itself (BatchPtrs::cmd) ...
+    const double *kthr = nullptr;        // ... from k_throttle[B]
+    double *thrust_keep = nullptr;
+    bool f_f64 = false;                  // d_f holds doubles (ndp_step_ex_f64)
+    const TickArgs *tick = nullptr;      // the launch is a whole control tick (rti_kernel<..., TICK>): list advance + estimator inside
+};
+
+enum RecomputeId { RC_WVJP, RC_JVP, RC_VJP };   // the derivative kernels that recompute a recorded step (rti_kernels.hip: recompute_kernel)
+
 // ---- host functions one unit calls in another (no locking, no sync: the caller holds h->mu).  C linkage like the entry points they
 // sit beside; hidden, so not exported.
 extern "C" {
+// rti_kernels.hip.  launch_kern: one launch of row `id`, the caller checks hipGetLastError; rti_set_lds: the dynamic LDS of the table's
+// plain rows and the recompute kernels (sens false) or of its sensitivity rows
+NDP_HIDDEN bool queue_shape(const ndp_handle *h);
+NDP_HIDDEN void launch_kern(const ndp_handle *h, RtiId id, hipStream_t s, KernArgs &ka, SensArgs &sa, hipEvent_t start = nullptr,
+                            hipEvent_t stop = nullptr);
+NDP_HIDDEN const void *recompute_kernel(RecomputeId id, bool n20);
+NDP_HIDDEN hipError_t rti_set_lds(bool sens, int lds_bytes, const char **what);
+NDP_HIDDEN hipError_t mlp_prepare(void);
+NDP_HIDDEN int launch_mlp(ndp_handle *h, const Neigh &nb, const double *d_ego, float *d_f, hipStream_t s, size_t ego_pitch = 0);
+NDP_HIDDEN void launch_tick_pre(const TickPre &a, hipStream_t s);
 // ndp_hip.hip
 NDP_HIDDEN int sens_refuse(ndp_handle *h, const char *what);
 NDP_HIDDEN int note_stream(ndp_handle *h, hipStream_t s);
 NDP_HIDDEN int set_device(ndp_handle *h);
+NDP_HIDDEN int wait_all(ndp_handle *h);
+NDP_HIDDEN int begin_timing(ndp_handle *h, hipStream_t s, int kind, bool defer = false);
+NDP_HIDDEN int end_timing(ndp_handle *h, hipStream_t s);
+NDP_HIDDEN bool can_fuse(const ndp_handle *h);
+NDP_HIDDEN int launch_rti(ndp_handle *h, const double *d_x0, const double *d_xr, const double *d_ur, const float *d_f, double *d_u0,
+                          double *d_dbg, hipStream_t s, const Neigh *nb = nullptr, const StepOut *so = nullptr, bool prefetched = false);
+NDP_HIDDEN int enqueue_step(ndp_handle *h, const double *d_x0, const double *d_xr, const double *d_ur, const float *d_f, const Neigh &nb,
+                            double *d_u0, double *d_dbg, hipStream_t s, const StepOut *so = nullptr);
+NDP_HIDDEN int ensure_slots(ndp_handle *h);
+// rows.hip
+NDP_HIDDEN ThrCfg thr_cfg(const ndp_handle *h);
+NDP_HIDDEN RefCfg ref_cfg(const ndp_handle *h, double toff);
+NDP_HIDDEN void launch_throttle_reset(const ndp_handle *h);
+NDP_HIDDEN int launch_list_window(ndp_handle *h, double *d_xr, double *d_ur, hipStream_t s);
+// tick.hip
 NDP_HIDDEN int ensure_tick(ndp_handle *h);
-NDP_HIDDEN void launch_tick_pre(const TickPre &a, hipStream_t s);
 NDP_HIDDEN int tick_step_enqueue(ndp_handle *h, hipStream_t s, const double *x_odom, double *cmd, double *u0, const double *windows,
                                  unsigned long long pos);
 // mlp_vjp.hip
@@ -171,7 +262,7 @@ NDP_HIDDEN hipError_t mlp_vjp_prepare(void);
 NDP_HIDDEN int peer_mapped(const void *p);
 NDP_HIDDEN void launch_pack_pv_list(const double *base, size_t pitch, int np1, double *pv, size_t B, hipStream_t s);
 }  // extern "C"
-// ndp_hip.hip (C++ linkage: it returns a TickPre)
+// tick.hip (C++ linkage: it returns a TickPre)
 NDP_HIDDEN TickPre tick_pre(const ndp_handle *h, bool adv, const double *t, double t_all, bool est, const double *x_odom, const double *vz,
                             const double *throttle, double *pv = nullptr);
 

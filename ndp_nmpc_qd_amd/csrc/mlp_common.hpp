@@ -1,4 +1,4 @@
-// mlp_common.hpp -- what the downwash network's kernels share across translation units (ndp_hip.hip: mlp_tile, mlp_kernel, the fused
+// mlp_common.hpp -- what the downwash network's kernels share across translation units (mlp_tile.hpp: mlp_tile; downwash.hip: mlp_kernel; rti_kernels.hip: the fused
 // control step; mlp_vjp.hip: the network's backward pass): the fragment blob's offsets, the fp16 pair split, the capped ReLU, the gate and
 // the neighbour-window loads.  Device code only; every function is inlined into its caller.
 #pragma once
@@ -42,7 +42,7 @@ __device__ __forceinline__ ndp_d2 ld_other2(const double *p, int sys)
 
 typedef float f16_t __attribute__((ext_vector_type(16)));
 
-// The fragment blob's offsets in float units (ndp_hip.hip: enum FR_*, which defines the layout and asserts that these agree with it).
+// The fragment blob's offsets in float units (mlp_tile.hpp: enum FR_*, which defines the layout and asserts that these agree with it).
 namespace frag {
 constexpr int L1 = 0, B1 = L1 + 12 * 64, B2 = B1 + 128, B3 = B2 + 64, W4 = B3 + 128, B4 = W4 + 4 * 128, HF = B4 + 4, REC = 512,
               USED = HF + 32 * REC, TOTAL = (USED + 2047) / 2048 * 8 * 256;

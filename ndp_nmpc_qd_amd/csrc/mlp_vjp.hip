@@ -51,7 +51,7 @@ __host__ __device__ inline int fragt_source(int i)
     return l3 ? PW3 + out * 64 + in : PW2 + out * 128 + in;
 }
 
-// the 32-bit word i of dFrag (make_fragments in ndp_hip.hip is the definition; this is the same map read per word)
+// the 32-bit word i of dFrag (make_fragments in downwash.hip is the definition; this is the same map read per word)
 __device__ inline unsigned frag_word(const float *__restrict__ blob, int i)
 {
     using namespace frag;
@@ -139,7 +139,7 @@ __device__ __forceinline__ f16_t vjp_layer1(const float *fr, const float zb[3], 
     return acc;
 }
 
-// mlp_tile's forward (ndp_hip.hip) with the weights read from global memory, keeping the activations: the same matrix instructions in the
+// mlp_tile's forward (mlp_tile.hpp) with the weights read from global memory, keeping the activations: the same matrix instructions in the
 // same order on the same operands, so the activations -- and with them the ReLU masks -- are those of the force the step used.  a1 is
 // not kept (64 registers for the whole backward pass): vjp_layer1 computes it again where the second layer's gradient needs it.
 __device__ __forceinline__ void vjp_forward(const float *fr, const float zb[3], int lane, f16_t a2[2], f16_t a3[4])

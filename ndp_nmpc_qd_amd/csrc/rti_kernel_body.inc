@@ -1,4 +1,4 @@
-// rti_kernel_body.inc -- the statements of the control-step kernels rti_kernel, rti_sens_kernel and rti_psens_kernel (ndp_hip.hip), included INSIDE
+// rti_kernel_body.inc -- the statements of the control-step kernels rti_kernel, rti_sens_kernel and rti_psens_kernel (rti_kernels.hip), included INSIDE
 // their function bodies.  A device function both kernels call, however much inlined, reorders the kernels' code a little; the text
 // itself, compiled in each kernel's own body, gives rti_kernel exactly the code it had before rti_sens_kernel existed.
 // In scope where it is included: the template parameters NSLOT, WAVES, FUSED, NC, PREC, NRC, QMODE, TICK, the constants SENS and PSENS,

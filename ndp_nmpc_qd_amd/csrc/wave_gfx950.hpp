@@ -82,7 +82,7 @@ struct WaveGfx950 {
     // The step's parameter block for code that runs RARELY: the same bytes through a pointer into the kernel's argument segment that has
     // passed an empty asm, so that the fetches stay where they are written (constant-address-space scalar loads, scalar-cache hits)
     // instead of being hoisted to wherever the compiler first sees a path to them.  The block is the FIRST member of the kernel's one
-    // argument (ndp_hip.hip: KernArgs::P, asserted there).  (Taking the parameter's address instead would make the compiler copy the
+    // argument (kern_args.hpp: KernArgs::P, asserted there).  (Taking the parameter's address instead would make the compiler copy the
     // whole argument to scratch memory.)
     template <class T>
     static NDP_D const __attribute__((address_space(4))) T *late_params(const T &)

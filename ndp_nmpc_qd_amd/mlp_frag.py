@@ -5,7 +5,7 @@ import numpy as np
 SHAPES = (("W1", (128, 6)), ("b1", (128,)), ("W2", (64, 128)), ("b2", (64,)), ("W3", (128, 64)), ("b3", (128,)), ("W4", (3, 128)),
           ("b4", (3,)))
 NPARAM = 17859
-FR_TOTAL = 18432          # floats of the forward's fragment blob (csrc/ndp_hip.hip: FR_TOTAL)
+FR_TOTAL = 18432          # floats of the forward's fragment blob (csrc/mlp_tile.hpp: FR_TOTAL)
 FRT_TOTAL = 2 * 128 * 64  # floats of the transposed image (csrc/host.hpp: FRT_TOTAL)
 
 

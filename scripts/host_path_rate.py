@@ -1,7 +1,7 @@
 """Host-array step rate (SURVEY 8d's wording of the metric: H2D of the inputs and D2H of u0 inside the time), pageable numpy in /
 numpy out, batch 1024 (or argv[1]), N = 20, downwash on.  One tick at a time (ndp_step) and two ticks in flight
 (ndp_step_begin / ndp_step_end).  Environment: NDP_PACK_THREADS (pack threads beside the caller), NDP_HOST_PATH (measurement
-switch of csrc/ndp_hip.hip: zero | dma | dma1).  Also a plain multi-threaded memcpy of the same bytes for reference.
+switch of csrc/ndp_hip.hip, the host-array step: zero | dma | dma1).  Also a plain multi-threaded memcpy of the same bytes for reference.
 Run on the GPU box: python scripts/host_path_rate.py [B]"""
 import os
 import sys

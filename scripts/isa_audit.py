@@ -4,7 +4,7 @@ the instruction mix of the backward / forward sweep (the block with the most mat
 
     python scripts/isa_audit.py [extra hipcc flags]  > profiles/rNN_isa_audit.txt
 
-Compiles csrc/ndp_hip.hip to device assembly (--cuda-device-only -S) in a temporary directory (nothing is written into the tree; no
+Compiles csrc/rti_kernels.hip to device assembly (--cuda-device-only -S) in a temporary directory (nothing is written into the tree; no
 GPU needed).  (-save-temps, used before, round-trips the module through bitcode, which this compiler's reader rejects for the
 current source: "Invalid cast".)
 """
@@ -32,7 +32,7 @@ def main():
     extra = sys.argv[1:]
     with tempfile.TemporaryDirectory() as td:
         cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fPIC",
-               "--cuda-device-only", "-S", "-I" + CSRC, "-o", os.path.join(td, "x.s"), os.path.join(CSRC, "ndp_hip.hip")] + extra
+               "--cuda-device-only", "-S", "-I" + CSRC, "-o", os.path.join(td, "x.s"), os.path.join(CSRC, "rti_kernels.hip")] + extra
         subprocess.run(cmd, cwd=td, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         text = open(os.path.join(td, "x.s")).read()
     print("hipcc " + " ".join(cmd[1:8] + extra))

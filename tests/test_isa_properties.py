@@ -106,12 +106,21 @@ def test_lds_budget_of_the_reference_configuration():
 
 
 def test_every_kernel_lies_in_exactly_one_code_object(co):
-    """The library is built from several translation units (ndp_hip.hip, exchange.hip), each with a code object of its own: kernels()
+    """The library is built from several translation units (build.UNITS), each with a code object of its own: kernels()
     reads all of them (and raises on a kernel defined in two), and every unit's kernels are found."""
     k = co.kernels()
     assert len(co.paths) > 1
     homes = {co.code_object_of(n) for n in k}
     assert homes == set(co.paths), "a code object without kernels"
-    for part in ("mlp_stream_kernel", "tick_pre_kernel", "peer_publish_kernel", "plant_kernel", "rti_psens_kernel"):
+    assert len(co.paths) == len(build.UNITS) - len(build.HOST_ONLY)
+    for part in ("mlp_stream_kernel", "tick_pre_kernel", "peer_publish_kernel", "plant_kernel", "rti_psens_kernel", "mlp_kernel",
+                 "ref_window_kernel", "mfma_probe_kernel", "mlp_vjp_kernel"):
         assert any(part in n for n in k), part
     assert sum("rti_kernel" in n for n in k) >= 20
+
+
+def test_units_are_the_hip_files_of_csrc():
+    """Every *.hip in csrc/ is built (listed in build.UNITS) and every listed unit exists: an orphaned or forgotten unit fails here."""
+    assert len(set(build.UNITS)) == len(build.UNITS)
+    assert set(build.UNITS) == {f for f in os.listdir(build.CSRC) if f.endswith(".hip")}
+    assert build.HOST_ONLY <= set(build.UNITS)

@@ -1,4 +1,4 @@
-"""The control-step kernel table on the CPU: every row of enum RtiId / k_rti (csrc/ndp_hip.hip) has a device case in
+"""The control-step kernel table on the CPU: every row of enum RtiId (csrc/rti_table.hpp) / k_rti (csrc/rti_kernels.hip) has a device case in
 tests/test_kernel_table_gpu.py, or is listed there as unreachable for a reason this file checks by arithmetic; and the launch geometry
 that module expects per horizon follows from ndp_create's rules applied to the LDS image of the wave program's host build."""
 import os
@@ -9,18 +9,20 @@ import pytest
 from ndp_nmpc_qd_amd import _lib
 from tests import test_kernel_table_gpu as G
 
-SRC = os.path.join(os.path.dirname(_lib.__file__), "csrc", "ndp_hip.hip")
+CSRC = os.path.join(os.path.dirname(_lib.__file__), "csrc")
+SRC = os.path.join(CSRC, "rti_kernels.hip")          # the table k_rti
+FRAG_SRC = os.path.join(CSRC, "mlp_tile.hpp")        # the fragment blob's layout
 LDS_BYTES = 160 * 1024
 
 
-def _source():
-    with open(SRC) as fh:
+def _source(path=SRC):
+    with open(path) as fh:
         return re.sub(r"//[^\n]*", "", fh.read())
 
 
 def _fr_total():
     """FR_TOTAL (floats of the downwash network's fragment blob): the enum that defines it, evaluated with C's integer division."""
-    m = re.search(r"enum \{ (FR_L1 = .*?)\};", _source(), re.S)
+    m = re.search(r"enum \{ (FR_L1 = .*?)\};", _source(FRAG_SRC), re.S)
     vals = {}
     for item in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(","):
         name, expr = (t.strip() for t in item.split("="))
@@ -45,7 +47,7 @@ def _per_wave_bytes(emu, N):
 
 
 def _dbg_extra():
-    with open(os.path.join(os.path.dirname(SRC), "rti_wave.hpp")) as fh:
+    with open(os.path.join(CSRC, "rti_wave.hpp")) as fh:
         return int(re.search(r"enum \{ DBG_EXTRA = (\d+) \}", fh.read()).group(1))
 
 

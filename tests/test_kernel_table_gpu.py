@@ -1,4 +1,4 @@
-"""Every row of the control-step kernel table (enum RtiId / k_rti in csrc/ndp_hip.hip) on the device, at every horizon (run with -m gpu).
+"""Every row of the control-step kernel table (enum RtiId in csrc/rti_table.hpp / k_rti in csrc/rti_kernels.hip) on the device, at every horizon (run with -m gpu).
 
 Each row is an instantiation of its own (slots, instances per workgroup, fused or unfused downwash, compile-time or run-time horizon,
 work-list phase, tick form, precision), with its own register allocation and lane predicates.  Every case below launches the rows it

@@ -729,7 +729,7 @@ def test_remote_tick_with_the_exchange_one_period_ahead_equals_the_single_handle
 
 
 def _ring_slot(step, np1, j):
-    """ndp_hip.hip: RingGeom::slot -- where list entry j lives (entries of one residue j mod step share a row of np1 nodes)."""
+    """kern_args.hpp: RingGeom::slot -- where list entry j lives (entries of one residue j mod step share a row of np1 nodes)."""
     return (j % step) * 2 * np1 + (j // step) % np1
 
 
