@@ -38,6 +38,7 @@ extern "C" {
 #define NDP_NX 10
 #define NDP_NU 4
 #define NDP_MLP_NPARAM 17859 /* 6-128-64-128-3 with biases, nn_net.py:7-18 */
+#define NDP_MLP_W23_LIMIT 65504.0f /* |W2|, |W3| must stay below the largest finite fp16 (ndp_set_mlp_weights) */
 
 /* Version of this interface: bumped whenever an exported signature or the layout of ndp_cfg changes.  A binding built against
  * another header must refuse to run: ndp_abi_version() is what the loaded library was built with, ndp_cfg_size() its
@@ -145,7 +146,13 @@ int ndp_destroy(ndp_handle *h);
 const char *ndp_last_error(const ndp_handle *h); /* h may be NULL: last create error */
 
 /* Replaces nn_model.load_state_dict(torch.load(...)) (downwash_nn.py:14-16).
- * blob: W1[128][6] b1 W2[64][128] b2 W3[128][64] b3 W4[3][128] b4, fp32, n = NDP_MLP_NPARAM. */
+ * blob: W1[128][6] b1 W2[64][128] b2 W3[128][64] b3 W4[3][128] b4, fp32, n = NDP_MLP_NPARAM.
+ * Supported range: every parameter finite, |W2| and |W3| below NDP_MLP_W23_LIMIT.  Layers 2 and 3 run on fp16 pairs w = hi + lo / 2^11
+ * (hi = fp16(w), lo = fp16((w - hi) * 2^11), fp16 subnormals kept): 22 significand bits down to an absolute resolution of 2^-35, so
+ * weights may be scaled down by 2^-10 and more at the 1e-5 bar; a W2 / W3 entry of 65520 or more would become an fp16 infinity and every
+ * force NaN.  Layers 1 and 4 and the biases are fp32; hidden activations that feed a split are capped at 65000.
+ * Returns -2 with a reason in ndp_last_error, the weights installed before still in force, for n != NDP_MLP_NPARAM, a non-finite
+ * parameter, or a W2 / W3 entry outside the range. */
 int ndp_set_mlp_weights(ndp_handle *h, const float *blob, size_t n);
 
 /* Replaces NMPCBodyRateController.reset (nmpc_body_rate_ctl.py:86-91):
@@ -408,7 +415,9 @@ int ndp_downwash_vjp_device(ndp_handle *h, const void *d_other, int other_stride
                             const void *d_ego_ref, const void *d_ego_xy, const void *d_gf,
                             void *d_gz, void *d_gw, void *stream);
 /* ndp_set_mlp_weights from device memory (d_blob: NDP_MLP_NPARAM fp32, the same order), enqueued on `stream`, no host synchronisation:
- * a training loop's update.  The device builds the same bytes as the host form. */
+ * a training loop's update.  The device builds the same bytes as the host form.  This form does NOT check the values (that would take a
+ * synchronisation): the range stated at ndp_set_mlp_weights is the caller's to keep -- a non-finite parameter or |W2|, |W3| >= 65520
+ * (an fp16 infinity) gives NaN forces. */
 int ndp_set_mlp_weights_device(ndp_handle *h, const void *d_blob, void *stream);
 /* Test hook: host copies of the network's two device images, taken after a device synchronisation.
  *   frag_out  18432 32-bit words: the forward's fragment blob (fp32 values, then fp16 pairs -- compare it as words, not as floats)

@@ -6,7 +6,9 @@
 // (The fused form runs inside the control step: rti_kernels.hip.  The backward pass: mlp_vjp.hip.)
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "host.hpp"
@@ -256,6 +258,20 @@ int ndp_set_mlp_weights(ndp_handle *h, const float *blob, size_t n)
     if (!h || !blob) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     if (n != NDP_MLP_NPARAM) { h->err = "ndp_set_mlp_weights: expected 17859 floats"; return -2; }
+    // refused before anything is touched (the weights installed before stay in force): a non-finite parameter, and a W2 / W3 entry
+    // whose fp16 hi part would not be finite (layers 2 and 3 run on fp16 pairs: include/ndp_nmpc.h)
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(blob[i])) {
+            h->err = "ndp_set_mlp_weights: parameter " + std::to_string(i) + " is not finite";
+            return -2;
+        }
+    const size_t w2 = 128 * 6 + 128, w3 = w2 + 64 * 128 + 64;
+    for (size_t i = 0; i < 64 * 128; ++i)
+        if (std::fabs(blob[w2 + i]) >= NDP_MLP_W23_LIMIT || std::fabs(blob[w3 + i]) >= NDP_MLP_W23_LIMIT) {
+            h->err = "ndp_set_mlp_weights: |W2|, |W3| must be below 65504 (layers 2 and 3 run on fp16 pairs); entry " + std::to_string(i) +
+                     " of " + (std::fabs(blob[w2 + i]) >= NDP_MLP_W23_LIMIT ? "W2" : "W3") + " is not";
+            return -2;
+        }
     NDP_HIP(h, hipSetDevice(h->cfg.device));
     std::vector<float> fr;
     make_fragments(blob, fr);

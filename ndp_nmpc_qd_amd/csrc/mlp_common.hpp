@@ -52,12 +52,16 @@ __device__ __forceinline__ int f0(int r) { return (r & 3) + 8 * (r >> 2); }
 
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 struct Split2 { h16x8 hi, lo; };
-#define NDP_LO_SCALE 2048.0f            // 2^11: the low parts are carried scaled so that they stay fp16-normal
+// 2^11: the low parts are carried scaled by the reciprocal of fp16's relative spacing, |lo| = |x - hi| * 2^11 <= |x|.  That does NOT keep
+// them fp16-normal: lo is an fp16 subnormal whenever |x - hi| < 2^-25 -- always for |x| < 2^-14, where hi is subnormal too -- so the pair
+// relies on subnormal fp16 operands being honoured by the conversions and by v_mfma_f32_32x32x16_f16 (tests/test_downwash_weights_gpu.py
+// holds the tile to that with weights rescaled into this range).  The pair's absolute resolution is 2^-35 (fp16's 2^-24 / 2^11).
+#define NDP_LO_SCALE 2048.0f
 #define NDP_LO_INV (1.0f / 2048.0f)
 #define NDP_H16_CAP 65000.0f            // activations are capped below the fp16 overflow threshold (see split2)
 
 // x = hi + lo / 2^11 with two fp16 terms (11 + 11 significand bits; fp32 has 24): hi = fp16(x), the residual
-// x - hi is exact in fp32 and lo = fp16(residual * 2^11).  Relative error of the pair 2^-22.
+// x - hi is exact in fp32 and lo = fp16(residual * 2^11).  Error of the pair 2^-22 |x| + 2^-35.
 __device__ __forceinline__ void split2(const f16_t &v, int s, Split2 &o)
 {
     typedef float f2_t __attribute__((ext_vector_type(2)));

@@ -22,7 +22,7 @@ BAR = 1e-5
 def _case(form, seed, B=B):
     """Inputs of one form (B instances): other - xr drawn as the network's golden rows, gf ~ N(0, 1).  Returns a dict with numpy arrays: other (as
     handed to the device), xr, ego_xy or None, index or None, z [B,N+1,6] (the rows the network sees), live [B] (gate open and a
-    neighbour present), gf."""
+    neighbour present), gf.  Nothing here depends on the weights: tests/test_downwash_weights_gpu.py runs the same cases under other blobs."""
     rng = np.random.default_rng(seed)
     xr = rng.normal(0.0, 1.0, (B, N + 1, 10))
     gf = rng.normal(size=(B, N + 1, 3))
@@ -74,11 +74,12 @@ def _device_vjp(eng, c, gf, want_gw=True):
     return gz.cpu().numpy(), None if gw is None else gw.cpu().numpy()
 
 
-def _reference(c, gf):
-    """float64 reference on the live rows (dead rows: zero upstream).  Returns (g_z, g_w, margin) with [B,N+1,...] shapes."""
+def _reference(c, gf, blob=None):
+    """float64 reference of the network with the weights `blob` (None: the shipped ones) on the live rows (dead rows: zero upstream).
+    Returns (g_z, g_w, margin) with [B,N+1,...] shapes."""
     B = c["xr"].shape[0]
     g = gf * c["live"][:, None, None]
-    gz, gw, margin, _ = R.vjp64(_lib.load_weights(), c["z"].reshape(-1, 6), g.reshape(-1, 3))
+    gz, gw, margin, _ = R.vjp64(_lib.load_weights() if blob is None else blob, c["z"].reshape(-1, 6), g.reshape(-1, 3))
     return gz.reshape(B, N + 1, 6), gw, margin.reshape(B, N + 1)
 
 
