@@ -414,6 +414,25 @@ int ndp_set_model(ndp_handle *h, const double *Qd, const double *Rd, double mass
 int ndp_downwash_vjp_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index,
                             const void *d_ego_ref, const void *d_ego_xy, const void *d_gf,
                             void *d_gz, void *d_gw, void *stream);
+/* Forward mode of DownwashNN.update + the r_horiz gate: the Jacobian-vector product of the same network along n_tan directions per call,
+ * the mirror of ndp_downwash_vjp_device and the producer of ndp_step_jvp_device's d_tf.  d_other / other_stride / d_other_index /
+ * d_ego_ref / d_ego_xy as the step that produced the force took them; the forward is recomputed with the step's own arithmetic, so the
+ * ReLU masks are those of the force the step used (capped ReLU: derivative 0 on both flat branches).  A direction is
+ *   d_tz [B][T][N+1][6] fp64 : the direction of (other - ego_ref)[..., 0:6] per row (rounded to fp32 as d_gf is), NULL = 0
+ *   d_tw [T][NDP_MLP_NPARAM] fp32 : the direction of the weights, blob order of ndp_set_mlp_weights, NULL = 0 (and none of its work runs)
+ * with T = n_tan, not both NULL.  Outputs:
+ *   d_df [B][T][N+1][3] fp64, required: the first-order change of the force, exactly ndp_step_jvp_device's d_tf layout (hand it over as
+ *                             it lies); exactly 0 in every direction on closed / neighbour-less instances (the gate is held fixed)
+ *   d_f_check [B][N+1][3] fp32, optional: the recomputed force, bit-equal to ndp_downwash_device's on open rows, 0 elsewhere.
+ * The tangent is linear: nothing on its path is capped or converted to fp16, so any finite fp32 direction is served (no range limit on
+ * d_tz or d_tw).  Products are exact fp32; W2 and W3 are read from the forward's fp16 pair image (hi + lo / 2^11: the weight to 2^-22).
+ * T directions in one call give, bit for bit, what T calls with one direction each give; two calls are bit-identical.  No workspace of
+ * the handle is used and nothing of the engine's state is written, so calls need no ordering against each other.
+ * -1: NULL handle (or d_other / d_ego_ref missing); -6: weights never set; -2 with a reason in ndp_last_error, nothing launched:
+ * other_stride not 6 or 10, n_tan outside 1..NDP_JVP_MAX_TANGENTS, no tangent given, d_df NULL. */
+int ndp_downwash_jvp_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index,
+                            const void *d_ego_ref, const void *d_ego_xy, int n_tan,
+                            const void *d_tz, const void *d_tw, void *d_df, void *d_f_check, void *stream);
 /* ndp_set_mlp_weights from device memory (d_blob: NDP_MLP_NPARAM fp32, the same order), enqueued on `stream`, no host synchronisation:
  * a training loop's update.  The device builds the same bytes as the host form.  This form does NOT check the values (that would take a
  * synchronisation): the range stated at ndp_set_mlp_weights is the caller's to keep -- a non-finite parameter or |W2|, |W3| >= 65520

@@ -56,7 +56,7 @@ EXPORTS = [
     "ndp_sens_enable", "ndp_sens_level", "ndp_get_sens", "ndp_device_sens_u0", "ndp_device_sens_u", "ndp_device_sens_x",
     "ndp_sens_params_enable", "ndp_sens_params_enabled", "ndp_get_sens_params", "ndp_device_sens_xr", "ndp_device_sens_ur", "ndp_device_sens_f",
     "ndp_debug_rti_launched", "ndp_device_active_set", "ndp_step_vjp_device",
-    "ndp_downwash_vjp_device", "ndp_set_mlp_weights_device", "ndp_debug_mlp_fragments",
+    "ndp_downwash_vjp_device", "ndp_downwash_jvp_device", "ndp_set_mlp_weights_device", "ndp_debug_mlp_fragments",
     "ndp_step_vjp_model_device", "ndp_set_model", "ndp_step_jvp_device",
 ]
 
@@ -145,6 +145,7 @@ def load():
     lib.ndp_step_jvp_device.argtypes = [vp] * 8 + [C.c_int] + [vp] * 10
     lib.ndp_set_model.argtypes = [vp, vp, vp, C.c_double]
     lib.ndp_downwash_vjp_device.argtypes = [vp, vp, C.c_int] + [vp] * 7
+    lib.ndp_downwash_jvp_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 5
     lib.ndp_set_mlp_weights_device.argtypes = [vp] * 3
     lib.ndp_debug_mlp_fragments.argtypes = [vp] * 3
     lib.ndp_debug_host_info.argtypes = [vp, vp]

@@ -623,6 +623,45 @@ class BatchedNMPC:
             d(ego_xy, torch.float64, (B, 2)), d(gf, torch.float64, (B, N + 1, 3)), d(gz, torch.float64, (B, N + 1, 6)),
             d(gw, torch.float32, (_lib.MLP_NPARAM,)), self._stream(stream)), "ndp_downwash_vjp_device")
 
+    def downwash_jvp_device(self, other, ego_ref, tz=None, tw=None, ego_xy=None, other_index=None, n_tan=None, df=None, f_check=None,
+                            stream=None):
+        """Enqueues the forward mode of the downwash network and its gate on `stream` (ndp_downwash_jvp_device; include/ndp_nmpc.h):
+        other / other_index / ego_ref (= the step's xr) / ego_xy as the step that produced the force took them.  Directions (None = 0, not
+        both None): tz [B,T,N+1,6] float64, the direction of (other - ego_ref)[..., 0:6]; tw [T,17859] float32, the direction of the
+        weights in blob order.  Outputs (CUDA tensors the caller allocates): df [B,T,N+1,3] float64, required -- the first-order change
+        of the force in step_jvp_device's tf layout, exactly 0 on closed and neighbour-less instances; f_check [B,N+1,3] float32, optional
+        -- the recomputed force.  T (1..8) is n_tan when given, else read from the tensors; tensors without the T axis mean T = 1.  The
+        gate is held fixed.  T directions in one call equal T calls of one bit for bit; the engine's state is not written.  stream None or
+        torch's default stream: the call goes on the engine's own stream behind a wait for torch's (read the outputs after
+        engine.synchronize())."""
+        import torch
+        B, N = self.B, self.N
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        tails = ((N + 1, 6), (_lib.MLP_NPARAM,), (N + 1, 3))
+        lead = (1, 0, 1)                                                # dimensions in front of the T axis
+        if n_tan is None:
+            Ts = {int(t.shape[ld]) if t.dim() == ld + 1 + len(s) else 1 for t, s, ld in zip((tz, tw, df), tails, lead) if t is not None}
+            if len(Ts) > 1:
+                raise ValueError(f"downwash_jvp_device: tangents and output disagree on the number of directions ({sorted(Ts)})")
+            n_tan = Ts.pop() if Ts else 1
+        T = int(n_tan)
+        d = self._dptr
+
+        def dt(t, s, ld):                                               # (without the T axis: the tensor is T = 1 as it lies)
+            if t is None:
+                return None
+            head = (B,) if ld else ()
+            full = head + (T,) + s
+            if t.dim() != len(full) and T != 1:
+                raise ValueError(f"downwash_jvp_device: a tensor without the T axis with n_tan = {T}")
+            return d(t, torch.float32 if s is tails[1] else torch.float64, full if t.dim() == len(full) else head + s)
+        optr, stride = self._other_ptr(other, other_index)
+        self._check(self._lib.ndp_downwash_jvp_device(
+            self._h, optr, stride, d(other_index, torch.int32, (B,)), d(ego_ref, torch.float64, (B, N + 1, 10)),
+            d(ego_xy, torch.float64, (B, 2)), T, dt(tz, tails[0], 1), dt(tw, tails[1], 0), dt(df, tails[2], 1),
+            d(f_check, torch.float32, (B, N + 1, 3)), self._stream(stream)), "ndp_downwash_jvp_device")
+
     def set_mlp_weights_device(self, blob, stream=None):
         """set_mlp_weights from a float32 CUDA tensor of 17859 values in blob order, enqueued on `stream` with no host synchronisation
         (ndp_set_mlp_weights_device): steps enqueued behind it on that stream use the new weights."""

@@ -10,6 +10,7 @@
 //   rows.hip         the rows f1 - f4: reference window and list, follower relay, throttle estimator, actuator command, plant, rollout
 //   tick.hip         the control tick's host side (ndp_tick*); no kernel: compiled for the host only
 //   mlp_vjp.hip      the downwash network's backward pass (ndp_downwash_vjp_device) and its weights set from device memory
+//   mlp_jvp.hip      the downwash network's forward mode (ndp_downwash_jvp_device)
 //   exchange.hip     peer-mapped windows (ndp_peer_*), the RCCL exchange (ndp_xchg_*) and the remote tick one control period ahead
 // A kernel sits with the host code that launches it; device code that two units' kernels inline is a header (mlp_tile.hpp, ref_point.hpp,
 // tick_wave.hpp), and so are the argument blocks the host fills (kern_args.hpp).

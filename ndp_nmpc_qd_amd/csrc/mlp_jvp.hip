@@ -1,0 +1,358 @@
+// mlp_jvp.hip -- forward mode (a Jacobian-vector product) of the downwash network (nn_net.py:7-18, 6-128-64-128-3): the mirror of
+// mlp_vjp.hip's backward pass.
+//
+// Kernel
+//   mlp_jvp_kernel : per 32-row tile and wave, four waves per workgroup (the row -> (instance, node) mapping, gate and addressing of
+//                    mlp_vjp_kernel; one tile per wave, no loop over tiles, no LDS, no barrier): the forward recomputed with mlp_tile's
+//                    arithmetic, all three hidden activations kept in registers (their ReLU masks are the forward's own), then for each
+//                    of the call's T directions, one rolled loop,
+//                      da_l = m_l (W_l da_(l-1) + dW_l a_(l-1) + db_l),  da_0 = dz,  df = W_4 da_3 + dW_4 a_3 + db_4
+//                    Layers 1..3 run on v_mfma_f32_32x32x2_f32 (exact fp32 products), layer 4 on the VALU.  The A operands:
+//                      W_1         the forward's own records (frag::L1)
+//                      W_2, W_3    rebuilt per lane from the forward's fp16 pair records, hi + lo / 2^11 -- element j of record (ot, it, s)
+//                                  is the weight that multiplies register 8 s + j of the in-tile, so no data moves between lanes; the pair
+//                                  holds the weight to 2^-22 |w| + 2^-35 and honours fp16 subnormals as the forward does
+//                      dW_l, db_l  read straight from the caller's blob-ordered buffer (four registers of a lane are 16 contiguous bytes
+//                                  of one weight row); none of it runs when no weight direction is given
+//                    A tangent is linear: nothing on its path is capped, clamped or converted to fp16, so there is no range limit on
+//                    it beyond fp32's own.  Rows go from registers straight to global memory; no atomics, no workspace of the handle.
+#include <hip/hip_runtime.h>
+
+#include "../../include/ndp_nmpc.h"
+#include "host.hpp"
+#include "mlp_common.hpp"
+
+namespace ndp {
+
+// blob order of ndp_set_mlp_weights: W1[128][6] b1 W2[64][128] b2 W3[128][64] b3 W4[3][128] b4 (the same enum as mlp_vjp.hip's)
+enum { PW1 = 0, PB1 = PW1 + 128 * 6, PW2 = PB1 + 128, PB2 = PW2 + 64 * 128, PW3 = PB2 + 64, PB3 = PW3 + 128 * 64, PW4 = PB3 + 128,
+       PB4 = PW4 + 3 * 128, PTOTAL = PB4 + 3 };
+static_assert(PTOTAL == NDP_MLP_NPARAM, "blob layout");
+
+struct MlpJvpArgs {
+    const float *fr;
+    const double *other, *ego, *ego_xy;
+    const double *tz;       // [B][T][np1][6] or null
+    const float *tw;        // [T][NDP_MLP_NPARAM] or null
+    double *df;             // [B][T][np1][3]
+    float *fchk;            // [rows][3] or null
+    int rows, np1, ntan;
+    double r2;
+    int other_stride;
+    const int *other_index;
+    int other_sys;
+    size_t other_pitch, ego_pitch, ego_xy_pitch;
+};
+
+typedef float f4_t __attribute__((ext_vector_type(4)));
+
+// (as mlp_vjp.hip's VJP_FENCE: the weights come from global memory in fully unrolled loops; a compiler-only memory fence between groups
+// bounds what is requested ahead)
+#define JVP_FENCE() asm volatile("" ::: "memory")
+
+// four consecutive floats of a direction of the weights; a direction starts at a multiple of 17 859 floats, so only 4-byte alignment holds
+__device__ __forceinline__ f4_t ld4(const float *p)
+{
+    f4_t v;
+    __builtin_memcpy(&v, p, 16);
+    return v;
+}
+
+__device__ __forceinline__ void jvp_load_w(const float *fr, int rec, int lane, Split2 &w)      // copy of mlp_vjp.hip's load_w_vjp
+{
+    const h16x8 *p = reinterpret_cast<const h16x8 *>(fr + frag::HF) + rec * 128 + lane;
+    w.hi = p[0]; w.lo = p[64];
+}
+
+// one 32-feature tile of the first layer's activations (mlp_tile's layer 1; copy of mlp_vjp.hip's vjp_layer1)
+__device__ __forceinline__ f16_t jvp_layer1(const float *fr, const float zb[3], int lane, int ot)
+{
+    f16_t acc;
+    JVP_FENCE();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = fr[frag::B1 + ot * 32 + f0(r) + 4 * (lane >> 5)];
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fr[frag::L1 + (ot * 3 + s) * 64 + lane], zb[s], acc, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = relu_cap(acc[r]);
+    return acc;
+}
+
+// mlp_tile's forward (mlp_tile.hpp) with the weights read from global memory, keeping all three hidden activations, and its last layer:
+// the same matrix instructions in the same order on the same operands, the same chain of fused multiply-adds behind them, so o[] is
+// mlp_kernel's force bit for bit.  (Layers 1..3: copy of mlp_vjp.hip's vjp_forward, which does not keep a1 and has no layer 4.)
+__device__ __forceinline__ void jvp_forward(const float *fr, const float zb[3], int lane, f16_t a1[4], f16_t a2[2], f16_t a3[4], float o[3])
+{
+    const int h = lane >> 5;
+    Split2 x1[4][2], x2[2][2];
+#pragma unroll
+    for (int ot = 0; ot < 4; ++ot) {
+        a1[ot] = jvp_layer1(fr, zb, lane, ot);
+        split2(a1[ot], 0, x1[ot][0]);
+        split2(a1[ot], 1, x1[ot][1]);
+    }
+    f16_t acc, accl;
+#pragma unroll
+    for (int rec = 0; rec < 32; ++rec) {
+        const bool l2 = rec < 16;
+        const int q = l2 ? rec : rec - 16;
+        const int ot = l2 ? q / 8 : q / 4, it = l2 ? (q / 2) % 4 : (q / 2) % 2, s = q % 2;
+        const bool first = l2 ? (q % 8 == 0) : (q % 4 == 0), last = l2 ? (q % 8 == 7) : (q % 4 == 3);
+        Split2 wc;
+        JVP_FENCE();
+        jvp_load_w(fr, rec, lane, wc);
+        if (first) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                acc[r] = fr[(l2 ? frag::B2 : frag::B3) + ot * 32 + f0(r) + 4 * h];
+                accl[r] = 0.0f;
+            }
+        }
+        mm3(wc, l2 ? x1[it][s] : x2[it][s], acc, accl);
+        if (last) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float v = fmaf(accl[r], NDP_LO_INV, acc[r]);
+                acc[r] = l2 ? relu_cap(v) : fmaxf(v, 0.0f);
+            }
+            if (l2) { a2[ot] = acc; split2(acc, 0, x2[ot][0]); split2(acc, 1, x2[ot][1]); }
+            else a3[ot] = acc;
+        }
+    }
+    const f4_t *w4 = reinterpret_cast<const f4_t *>(fr + frag::W4);
+    o[0] = o[1] = o[2] = 0.0f;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+        JVP_FENCE();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const f4_t q = w4[it * 32 + f0(r) + 4 * h];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c] = fmaf(q[c], a3[it][r], o[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = o[c] + __shfl_xor(o[c], 32, 64) + fr[frag::B4 + c];
+}
+
+// derivative of relu_cap as mlp_vjp.hip's mask_cap defines it: 1 strictly inside (0, cap), 0 on both flat branches
+__device__ __forceinline__ float jvp_mask_cap(float a, float d) { return a > 0.0f && a < NDP_H16_CAP ? d : 0.0f; }
+
+// acc += W[out tile][in tiles 0..nit-1] d, W rebuilt from the pair records rec0 + 2 it + s (see the head of this file)
+__device__ __forceinline__ void jvp_dense(const float *fr, int rec0, int nit, const f16_t *d, int lane, f16_t &acc)
+{
+#pragma unroll
+    for (int it = 0; it < nit; ++it) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            Split2 w;
+            JVP_FENCE();
+            jvp_load_w(fr, rec0 + 2 * it + s, lane, w);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fmaf((float)w.lo[j], NDP_LO_INV, (float)w.hi[j]), d[it][8 * s + j], acc, 0, 0, 0);
+        }
+    }
+}
+
+// acc += dW[out tile][in tiles 0..nit-1] a; wrow = this lane's row of dW plus 4 (lane >> 5): registers 4 q .. 4 q + 3 of an in-tile are
+// its features 8 q + 4 (lane >> 5) + 0..3
+__device__ __forceinline__ void jvp_dweight(const float *wrow, int nit, const f16_t *a, f16_t &acc)
+{
+#pragma unroll
+    for (int it = 0; it < nit; ++it) {
+        JVP_FENCE();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f4_t v = ld4(wrow + it * 32 + 8 * q);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(v[i], a[it][4 * q + i], acc, 0, 0, 0);
+        }
+    }
+}
+
+// the accumulator a tile's tangent starts from: the bias direction of its 32 features, or 0
+__device__ __forceinline__ f16_t jvp_dbias(const float *tb, int h)
+{
+    f16_t acc;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        f4_t v = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (tb) v = ld4(tb + 8 * q + 4 * h);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[4 * q + i] = v[i];
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(256) void mlp_jvp_kernel(MlpJvpArgs A)
+{
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 31, h = lane >> 5;
+    const int ntiles = (A.rows + 31) / 32;
+    const int tile = (int)blockIdx.x * 4 + wave;
+    if (tile >= ntiles) return;
+    const int T = A.ntan;
+    const int row = tile * 32 + j;
+    const bool valid = row < A.rows;
+    const int rowc = valid ? row : A.rows - 1;
+    const int inst = rowc / A.np1, k = rowc - inst * A.np1;
+    const int orow = A.other_index ? A.other_index[inst] : inst;
+    const double *oth = A.other + (size_t)(orow < 0 ? 0 : orow) * A.other_pitch;
+    bool open = valid && orow >= 0;
+    if (A.ego_xy) {
+        const double oxy[2] = {ld_other(oth, A.other_sys), ld_other(oth + 1, A.other_sys)};
+        open = open && gate_open(oxy, A.ego_xy + (size_t)inst * A.ego_xy_pitch, A.r2);
+    }
+    const int tile_open = __builtin_amdgcn_readfirstlane((int)(__ballot(open) != 0ull));
+    const size_t trow = ((size_t)inst * T) * A.np1 + k;        // this row in direction 0; direction t: + t * np1
+    if (!tile_open) {                                          // no open row: exact zeros, nothing computed
+        if (valid && h == 0) {
+#pragma unroll 1
+            for (int t = 0; t < T; ++t) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) A.df[(trow + (size_t)t * A.np1) * 3 + c] = 0.0;
+            }
+            if (A.fchk) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) A.fchk[(size_t)row * 3 + c] = 0.0f;
+            }
+        }
+        return;
+    }
+
+    float zb[3], o[3];
+    f16_t a1[4], a2[2], a3[4];
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+        zb[s] = (float)(ld_other(oth + (size_t)k * A.other_stride + 2 * s + h, A.other_sys) -
+                        A.ego[(size_t)inst * A.ego_pitch + (size_t)k * NX + 2 * s + h]);
+    jvp_forward(A.fr, zb, lane, a1, a2, a3, o);
+    if (A.fchk && valid && h == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) A.fchk[(size_t)row * 3 + c] = open ? o[c] : 0.0f;
+    }
+
+#pragma unroll 1
+    for (int t = 0; t < T; ++t) {
+        // (the weight records are the same in every round: keep the compiler from hoisting their loads out of the loop into registers)
+        const float *fr = A.fr;
+        asm volatile("" : "+s"(fr));
+        // (likewise the activations: seen as loop constants, the 160 mask comparisons are hoisted in front of the loop as lane masks in
+        // scalar registers, more than there are)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(a1[i]), "+v"(a3[i]));
+        asm volatile("" : "+v"(a2[0]), "+v"(a2[1]));
+        const float *tw = A.tw ? A.tw + (size_t)t * PTOTAL : nullptr;
+        float tzb[3] = {0.0f, 0.0f, 0.0f};
+        if (A.tz) {
+#pragma unroll
+            for (int s = 0; s < 3; ++s) tzb[s] = (float)A.tz[(trow + (size_t)t * A.np1) * 6 + 2 * s + h];
+        }
+        // ---- layer 1: da1 = m1 (W1 dz + dW1 z + db1)
+        f16_t d1[4];
+#pragma unroll
+        for (int ot = 0; ot < 4; ++ot) {
+            f16_t acc = jvp_dbias(tw ? tw + PB1 + ot * 32 : nullptr, h);
+            JVP_FENCE();
+#pragma unroll
+            for (int s = 0; s < 3; ++s)
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fr[frag::L1 + (ot * 3 + s) * 64 + lane], tzb[s], acc, 0, 0, 0);
+            if (tw) {
+#pragma unroll
+                for (int s = 0; s < 3; ++s)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(tw[PW1 + (ot * 32 + j) * 6 + 2 * s + h], zb[s], acc, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) d1[ot][r] = jvp_mask_cap(a1[ot][r], acc[r]);
+        }
+        // ---- layer 2: da2 = m2 (W2 da1 + dW2 a1 + db2)
+        f16_t d2[2];
+#pragma unroll
+        for (int ot = 0; ot < 2; ++ot) {
+            f16_t acc = jvp_dbias(tw ? tw + PB2 + ot * 32 : nullptr, h);
+            jvp_dense(fr, ot * 8, 4, d1, lane, acc);
+            if (tw) jvp_dweight(tw + PW2 + (ot * 32 + j) * 128 + 4 * h, 4, a1, acc);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) d2[ot][r] = jvp_mask_cap(a2[ot][r], acc[r]);
+        }
+        // ---- layer 3: da3 = m3 (W3 da2 + dW3 a2 + db3), plain ReLU
+        f16_t d3[4];
+#pragma unroll
+        for (int ot = 0; ot < 4; ++ot) {
+            f16_t acc = jvp_dbias(tw ? tw + PB3 + ot * 32 : nullptr, h);
+            jvp_dense(fr, 16 + ot * 4, 2, d2, lane, acc);
+            if (tw) jvp_dweight(tw + PW3 + (ot * 32 + j) * 64 + 4 * h, 2, a2, acc);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) d3[ot][r] = a3[ot][r] > 0.0f ? acc[r] : 0.0f;
+        }
+        // ---- layer 4 on the VALU: df = W4 da3 + dW4 a3 + db4; each half-wave owns 64 of the 128 features of its row
+        float g[3] = {0.0f, 0.0f, 0.0f};
+        const f4_t *w4 = reinterpret_cast<const f4_t *>(fr + frag::W4);
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            JVP_FENCE();
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const f4_t q = w4[it * 32 + f0(r) + 4 * h];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) g[c] = fmaf(q[c], d3[it][r], g[c]);
+            }
+        }
+        if (tw) {
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                JVP_FENCE();
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const f4_t v = ld4(tw + PW4 + c * 128 + it * 32 + 8 * q + 4 * h);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) g[c] = fmaf(v[i], a3[it][4 * q + i], g[c]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            g[c] += __shfl_xor(g[c], 32, 64);
+            if (tw) g[c] += tw[PB4 + c];
+        }
+        if (valid && h == 0) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) A.df[(trow + (size_t)t * A.np1) * 3 + c] = open ? (double)g[c] : 0.0;
+        }
+    }
+}
+
+}  // namespace ndp
+
+using namespace ndp;
+
+extern "C" {
+
+int ndp_downwash_jvp_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index, const void *d_ego_ref,
+                            const void *d_ego_xy, int n_tan, const void *d_tz, const void *d_tw, void *d_df, void *d_f_check, void *stream)
+{
+    Entry g(h, d_other && d_ego_ref, stream);
+    if (g.rc) return g.rc;
+    const char *why = nullptr;
+    if (!h->have_mlp) { h->err = "ndp_downwash_jvp_device: ndp_set_mlp_weights was never called"; return -6; }
+    if (other_stride != 6 && other_stride != NX) why = "ndp_downwash_jvp_device: other_stride must be 6 or 10";
+    else if (n_tan < 1 || n_tan > NDP_JVP_MAX_TANGENTS) why = "ndp_downwash_jvp_device: n_tan must be 1..8 (directions per call)";
+    else if (!d_tz && !d_tw) why = "ndp_downwash_jvp_device: no tangent given (d_tz and d_tw both NULL)";
+    else if (!d_df) why = "ndp_downwash_jvp_device: d_df is required (the tangent of the force)";
+    if (why) { h->err = why; return -2; }
+    const int np1 = h->cfg.N + 1, rows = h->cfg.batch * np1;
+    const int ntiles = (rows + 31) / 32;
+    MlpJvpArgs a{h->dFrag, (const double *)d_other, (const double *)d_ego_ref, (const double *)d_ego_xy, (const double *)d_tz,
+                 (const float *)d_tw, (double *)d_df, (float *)d_f_check, rows, np1, n_tan, h->cfg.r_horiz * h->cfg.r_horiz, other_stride,
+                 (const int *)d_other_index, peer_mapped(d_other), (size_t)np1 * other_stride, (size_t)np1 * NX, (size_t)2};
+    hipLaunchKernelGGL(mlp_jvp_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, g.s, a);
+    NDP_HIP(h, hipGetLastError());
+    return g.noted(0);
+}
+
+}  // extern "C"

@@ -24,6 +24,9 @@ neighbour windows and of the network's weights (BatchedNMPC.downwash_vjp_device)
 control_step_jvp is the forward-mode counterpart (BatchedNMPC.step_jvp_device): the step, then the first-order change of (u0, X, U) along
 given directions of x0, xr, ur and f.  It returns plain tensors; there is no autograd hookup.
 
+downwash_jvp / control_step_ndp_jvp continue that forward mode through the downwash network (BatchedNMPC.downwash_jvp_device): the force's tangent
+is the network's, along directions of the neighbour windows, of xr and of the weights.  Plain tensors as well.
+
 control_step_tunable / TunableControlStep (behind them) differentiate the controller's own numbers -- the cost weights Qd, Rd and the mass --
 by the same adjoint (BatchedNMPC.set_model, step_vjp_device with gmodel).
 """
@@ -389,6 +392,106 @@ class NDPControlStep(torch.nn.Module):
 
     def forward(self, x0, xr, ur, other, ego_xy=None, other_index=None):
         return control_step_ndp(self.engine, x0, xr, ur, other, ego_xy=ego_xy, weights=self.weights, other_index=other_index)
+
+
+# ---------------------------------------------------------------------------------------------- the downwash network, forward mode
+# The mirror of the block above (BatchedNMPC.downwash_jvp_device): the first-order change of the force along directions of the neighbour
+# windows, of ego_ref and of the weights, and its composition with the step's forward mode.  Held fixed: what the backward holds fixed
+# (gate, linearisation point, active set); ego_xy has no tangent.  Plain tensors, no autograd hookup, like control_step_jvp.
+
+def _with_t_axis(tangents, dims, who):
+    """The tangents (None, or tensors whose T axis -- position 0 for the weights' direction (dims 1), 1 for the others -- may be missing)
+    as detached contiguous tensors that all have it.  Returns (list, T, whether any tangent came with the axis)."""
+    out, Ts, had = [], set(), False
+    for t, n in zip(tangents, dims):
+        if t is None:
+            out.append(None)
+            continue
+        t = t.detach()
+        if t.dim() == n:
+            t = t.unsqueeze(0 if n == 1 else 1)
+        elif t.dim() == n + 1:
+            had = True
+        else:
+            raise ValueError(f"{who}: a tangent has {t.dim()} dimensions, expected {n} or {n + 1}")
+        Ts.add(int(t.shape[0 if n == 1 else 1]))
+        out.append(t)
+    if not Ts:
+        raise ValueError(f"{who}: no tangent (all None)")
+    if len(Ts) > 1:
+        raise ValueError(f"{who}: the tangents disagree on the number of directions ({sorted(Ts)})")
+    return out, Ts.pop(), had
+
+
+def _network_tz(t_other, t_ego, other_index):
+    """tz [B,T,N+1,6] = t_other[other_index] - t_ego on columns 0..5 (either may be None; both None: None): the direction of the
+    network's input rows.  Plumbing, the mirror of _scatter_gz / _minus_gz."""
+    tz = None
+    if t_other is not None:
+        rows = t_other if other_index is None else t_other[other_index.clamp(min=0).long()]
+        tz = rows[..., :6].to(torch.float64)
+    if t_ego is not None:
+        e = t_ego[..., :6].to(torch.float64)
+        tz = -e if tz is None else tz - e
+    return None if tz is None else tz.contiguous()
+
+
+def downwash_jvp(engine, other, ego_ref, tangents, ego_xy=None, weights=None, other_index=None):
+    """(f, df): the engine's gated downwash force f [B,N+1,3] float32 on (other - ego_ref)[..., 0:6] and its first-order change df
+    [B,T,N+1,3] float64 along tangents = (t_other, t_ego_ref, t_weights) (forward mode: BatchedNMPC.downwash_jvp_device).  t_other is
+    shaped like `other` ([rows,T,N+1,6 or 10]; columns 6..9 move nothing; with other_index every instance reads its neighbour row's
+    direction), t_ego_ref like ego_ref ([B,T,N+1,10]), t_weights [T,17859] float32 in blob order; each may be None (= 0, not all three)
+    and each may come without the T axis -- then df is [B,N+1,3] if none has it.  `weights`, when given, are installed first as
+    `downwash` does.  The gate is held fixed: ego_xy has no tangent.  No autograd hookup."""
+    od, ed = other.detach().contiguous(), ego_ref.detach().contiguous()
+    (t_other, t_ego, t_w), T, had = _with_t_axis(tangents, (3, 3, 1), "downwash_jvp")
+    stream, default = _cuda_stream(od)
+    if default:
+        stream.synchronize()
+    _install_weights(engine, weights, stream)
+    B, np1 = ed.shape[0], ed.shape[1]
+    tz = _network_tz(t_other, t_ego, other_index)
+    tw = None if t_w is None else t_w.to(torch.float32).contiguous()
+    f = torch.empty((B, np1, 3), dtype=torch.float32, device=od.device)
+    df = torch.empty((B, T, np1, 3), dtype=torch.float64, device=od.device)
+    engine.downwash_jvp_device(od, ed, tz=tz, tw=tw, ego_xy=ego_xy, other_index=other_index, n_tan=T, df=df, f_check=f, stream=stream)
+    if default:
+        engine.synchronize()
+    return f, df if had else df[:, 0]
+
+
+def control_step_ndp_jvp(engine, x0, xr, ur, other, tangents, ego_xy=None, weights=None, other_index=None):
+    """(u0, X, U, du0, dX, dU): the engine's control step with the fused downwash network and its new iterate, and the first-order change
+    of all three along tangents = (tx0, txr, tur, t_other, t_weights) -- control_step_jvp with the force's tangent produced by the
+    network's forward mode instead of given.  On one stream: the taped fused step; the network's JVP with tz = t_other[other_index] -
+    txr[..., 0:6] (and t_weights), giving tf; BatchedNMPC.step_jvp_device with (tx0, txr, tur, tf) and the force the step wrote.
+    Shapes: tx0 [B,T,10], txr [B,T,N+1,10], tur [B,T,N,4], t_other like `other` with the T axis behind its first, t_weights [T,17859]
+    float32; None = 0 (not all five); each may come without the T axis, and the outputs carry it unless none does.  Held fixed: the
+    linearisation point, the active set and the gate (ego_xy has no tangent).  Instances whose step failed have NaN tangents.  No
+    autograd hookup."""
+    det = lambda t: t.detach().contiguous()  # noqa: E731
+    x0, xr, ur, od = det(x0), det(xr), det(ur), det(other)
+    (tx0, txr, tur, t_other, t_w), T, had = _with_t_axis(tangents, (2, 3, 3, 3, 1), "control_step_ndp_jvp")
+    tx0, txr, tur = (None if t is None else t.to(torch.float64).contiguous() for t in (tx0, txr, tur))
+    B, N = x0.shape[0], xr.shape[1] - 1
+    stream, default = _cuda_stream(x0)
+    if default:
+        stream.synchronize()
+    _install_weights(engine, weights, stream)
+    tape, u0, X, U = _taped_step(engine, stream, default, x0, xr, ur, other=od, ego_xy=ego_xy, other_index=other_index)
+    tz = _network_tz(t_other, txr, other_index)
+    tw = None if t_w is None else t_w.to(torch.float32).contiguous()
+    tf = None
+    if tz is not None or tw is not None:
+        tf = torch.empty((B, T, N + 1, 3), dtype=torch.float64, device=x0.device)
+        engine.downwash_jvp_device(od, xr, tz=tz, tw=tw, ego_xy=ego_xy, other_index=other_index, n_tan=T, df=tf, stream=stream)
+    du0, dX, dU = (torch.empty((B, T) + s, dtype=torch.float64, device=x0.device) for s in ((4,), (N + 1, 10), (N, 4)))
+    engine.step_jvp_device(x0, xr, ur, tape, tx0, txr, tur, tf, f=engine.device_force(), du0=du0, dX=dX, dU=dU, stream=stream)
+    if default:
+        engine.synchronize()
+    if not had:
+        du0, dX, dU = du0[:, 0], dX[:, 0], dU[:, 0]
+    return u0, X, U, du0, dX, dU
 
 
 # ---------------------------------------------------------------------------------------------- the controller's own numbers, differentiated
