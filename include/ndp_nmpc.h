@@ -585,6 +585,35 @@ int ndp_plant_step_device(ndp_handle *h, void *d_x, const void *d_u, const void 
  * enqueued back to back on the stream; nothing returns to the host in between, nothing is synchronised. */
 int ndp_rollout_device(ndp_handle *h, int ticks, double t0, double dt_tick, int substeps, void *d_x, void *d_log, void *stream);
 
+/* ---- f4, the formation form (plant = a1 dynamics + downwash model): the downwash force the neighbour's ACTUAL state
+ * puts on the ACTUAL vehicle, and the closed loop around it -- the experiment the downwash prediction is for (the reference has no
+ * simulator; the force model is its own network, dnwash_nn_est/downwash_nn.py:22-28, behind the gate of ndp_nmpc_leader_node.py:65-68).
+ * ndp_plant_force*: for vehicle v with o = other_index[v] the network at (x[o] - x[v])[0:6] (fp64 difference rounded to fp32, as
+ *   ndp_downwash forms (other - ego_ref)[0:6]); the gate is o >= 0 && (!gate || |x[o].xy - x[v].xy|^2 < r_horiz^2), strict.  f[B][3] is
+ *   fp64 (what ndp_plant_step reads) = scale * (double)net, bit-equal to ndp_downwash_device's value for the same six inputs, or exactly
+ *   0 (gate closed; no neighbour: o < 0, o >= B, other_index NULL -- then no weights are needed).  d_xy[B][2] (or NULL) receives
+ *   x[v][0:2]: the dense buffer ndp_step_device_ex takes as d_ego_xy.  One launch, one network row per vehicle; it reads x only. */
+int ndp_plant_force_device(ndp_handle *h, const void *d_x, const void *d_other_index, int gate, double scale, void *d_f, void *d_xy,
+                           void *stream);
+int ndp_plant_force(ndp_handle *h, const double *x, const int32_t *other_index, int gate, double scale, double *f);
+/* ndp_rollout_formation_device: ndp_rollout_device with the downwash acting on the plant.  Reset at the trajectory's window at t0, then
+ *   per tick k: reference window at t0 + k*dt_tick -> plant force (scale plant_scale: the model-mismatch knob) + ego xy from the plant
+ *   states -> control step -> plant step with that force.  The force is made from the states of one and the same tick, before any of them
+ *   moves, and is HELD over the tick's plant call: it is not re-evaluated inside the RK4 substeps.
+ *   The control step with NDP_FORM_COMPENSATE (needs use_fd = 1) is the fused step of ndp_step_device_ex: d_other = this tick's reference
+ *   windows of the whole batch, d_other_index as given, d_ego_xy = the plant's xy when NDP_FORM_GATE is set -- the reference's own rule,
+ *   the neighbour's window against the ego odometry.  Without it the step is the plain one (f = NULL) on a use_fd 0 or 1 handle: the
+ *   paper's baseline, blind in the same downwash.  d_other_index NULL: nobody has a neighbour -- ndp_rollout_device's states, bit for bit.
+ *   d_x[B][10] plant state in/out.  Each may be NULL: d_log[ticks][B][10] the state after every tick, d_log_u[ticks][B][4] u0,
+ *   d_log_f[ticks][B][3] the plant force, d_worst_status int32[B] the largest status of each vehicle's steps.  Everything is enqueued on one
+ *   stream; nothing returns to the host, nothing is synchronised.  -8 (nothing enqueued, the handle stays usable): NDP_FORM_COMPENSATE on
+ *   a use_fd = 0 handle, no weights installed (and d_other_index given), no trajectory set.  With sensitivities on: -2, as
+ *   ndp_rollout_device. */
+int ndp_rollout_formation_device(ndp_handle *h, int ticks, double t0, double dt_tick, int substeps, const void *d_other_index, int flags,
+                                 double plant_scale, void *d_x, void *d_log, void *d_log_u, void *d_log_f, void *d_worst_status, void *stream);
+#define NDP_FORM_GATE        1   /* r_horiz gate in the plant force and in the controller's prediction */
+#define NDP_FORM_COMPENSATE  2   /* the controller predicts the force (needs use_fd = 1); else it runs blind */
+
 /* ---- Peer windows: the neighbour exchange across GPUs as publish / subscribe over xGMI.
  * Replaces the PredXU topic between processes: the publisher is nmpc_node.py:116-133,229-230 (`nmpc_x_ref`, 21x10 float64, a NEW
  * message every control tick), the subscriber ndp_nmpc_leader_node.py:40,60-76 (consumes the latest one).  One process per GPU:

@@ -383,6 +383,45 @@ class BatchedNMPC:
             self._h, int(ticks), float(t0), float(dt), int(substeps), self._dptr(x, torch.float64, (self.B, 10)),
             self._dptr(log, torch.float64, (int(ticks), self.B, 10)), self._stream(stream)), "ndp_rollout_device")
 
+    # ---- f4, the formation form: the downwash acting on the plant
+    def plant_force(self, x, other_index, gate=True, scale=1.0):
+        """The downwash force on every vehicle from the plant states x[B,10] (ndp_plant_force; include/ndp_nmpc.h): vehicle v feels the
+        network at (x[other_index[v]] - x[v])[0:6] behind the r_horiz gate (gate=False: open everywhere); other_index int32[B], < 0 =
+        none, None = nobody has a neighbour.  Returns f[B,3] float64 = scale * net, exactly 0 where closed."""
+        x = _lib.f64(x, (self.B, 10))
+        oi = None if other_index is None else np.ascontiguousarray(other_index, dtype=np.int32).reshape(self.B)
+        f = np.empty((self.B, 3))
+        self._check(self._lib.ndp_plant_force(self._h, _lib.ptr(x), _lib.ptr(oi), 1 if gate else 0, float(scale), _lib.ptr(f)), "ndp_plant_force")
+        return f
+
+    def plant_force_device(self, x, other_index, f_out, xy_out=None, gate=True, scale=1.0, stream=None):
+        """plant_force on CUDA tensors, enqueued on `stream` with no synchronisation (ndp_plant_force_device): x[B,10] float64,
+        other_index int32[B] or None, f_out[B,3] float64; xy_out[B,2] float64 (optional) receives x[:, 0:2], the ego_xy of update_device."""
+        import torch
+        self._check(self._lib.ndp_plant_force_device(
+            self._h, self._dptr(x, torch.float64, (self.B, 10)), self._dptr(other_index, torch.int32, (self.B,)), 1 if gate else 0, float(scale),
+            self._dptr(f_out, torch.float64, (self.B, 3)), self._dptr(xy_out, torch.float64, (self.B, 2)), self._stream(stream)),
+            "ndp_plant_force_device")
+
+    def rollout_formation_device(self, ticks, x, other_index, log=None, log_u=None, log_f=None, worst_status=None, t0=0.0, dt=CP.ts_nmpc,
+                                 substeps=4, gate=True, compensate=None, plant_scale=1.0, stream=None):
+        """rollout_device with the downwash acting on the plant (ndp_rollout_formation_device; include/ndp_nmpc.h): per tick reference
+        window -> plant force (plant_force_device at scale plant_scale) -> control step -> plant step with that force, held over the tick.
+        compensate (default: the engine's `disturbance`): the controller predicts the force from its neighbour's reference window (the
+        fused step with other = the batch's reference windows, other_index, ego_xy = the plant's xy); False: it flies blind through the
+        same downwash.  x[B,10] is updated in place; other_index int32[B] CUDA tensor (< 0: none) or None; optional CUDA tensors
+        log[ticks,B,10] the states, log_u[ticks,B,4] u0, log_f[ticks,B,3] the plant force (float64), worst_status[B] int32 the largest
+        status of every vehicle's steps."""
+        import torch
+        K, B = int(ticks), self.B
+        comp = self.disturbance if compensate is None else bool(compensate)
+        flags = (_lib.FORM_GATE if gate else 0) | (_lib.FORM_COMPENSATE if comp else 0)
+        self._check(self._lib.ndp_rollout_formation_device(
+            self._h, K, float(t0), float(dt), int(substeps), self._dptr(other_index, torch.int32, (B,)), flags, float(plant_scale),
+            self._dptr(x, torch.float64, (B, 10)), self._dptr(log, torch.float64, (K, B, 10)), self._dptr(log_u, torch.float64, (K, B, 4)),
+            self._dptr(log_f, torch.float64, (K, B, 3)), self._dptr(worst_status, torch.int32, (B,)), self._stream(stream)),
+            "ndp_rollout_formation_device")
+
     def get_iterate(self):
         X = np.empty((self.B, self.N + 1, 10))
         U = np.empty((self.B, self.N, 4))

@@ -3,6 +3,7 @@
 //                 are in rti_kernels.hip (see there: it shares stage_fragments with the fused control step); its entry points are here.
 //   mlp_stream_kernel + prefetch_gate_kernel / prefetch_done_kernel : the downwash of the NEXT tick on a second stream, LDS-free
 //                 (weights out of L2), ordered against the control step by per-tile epochs (LateArgs / PF_* words).
+//   plant_force_kernel : f4, the downwash force on the plant from the vehicles' actual states, one row per vehicle (ndp_plant_force*).
 // (The fused form runs inside the control step: rti_kernels.hip.  The backward pass: mlp_vjp.hip.)
 #include <hip/hip_runtime.h>
 
@@ -149,6 +150,45 @@ void mlp_stream_kernel(const float *__restrict__ fr, const double *__restrict__ 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (lane == 0)
         __hip_atomic_store(proto + PF_EPOCH + (m & 1) * (unsigned)ntiles + tile, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- f4: the downwash force ON THE PLANT, one network row per vehicle (the closed-loop formation rollout's truth).  Vehicle v with
+// o = other_index[v]: the network at (x[o] - x[v])[0:6] (fp64 difference rounded to fp32, as mlp_kernel forms (other - ego_ref)[0:6]),
+// behind the r_horiz gate on |x[o].xy - x[v].xy| (gate_open: strict, the same individually rounded expression); f[v] = scale * (double)net
+// in fp64 (what plant_kernel reads), exactly 0 when the gate is closed or there is no neighbour (other_index null, o < 0 -- or o >= B,
+// which is never read); xy[v] = x[v][0:2], the dense ego-odometry buffer the fused control step takes.
+// The tile is the LDS-free stream form (mlp_tile_stream): a batch is a few tiles at most (B / 32), so parking the 72-KB fragment image in
+// LDS per workgroup would cost more than the tile itself; the weights come out of L2.  Its arithmetic is mlp_tile's, instruction for
+// instruction, so the force is bit-equal to ndp_downwash_device's for the same six inputs.  One wave = 32 vehicles; a workgroup has
+// blockDim.x / 64 waves (launch_plant_force: 1 to 4).  Control flow around the matrix instructions is wave-uniform: a wave leaves as a
+// whole (its tile is past the batch, or none of its rows is open); the lanes past B in the last tile recompute vehicle B - 1 and store
+// nothing.  It reads x only and writes f / xy only: every force is made from the states of one tick, so it is a launch of its own in
+// front of the in-place plant_kernel.
+__global__ __launch_bounds__(256)
+void plant_force_kernel(const float *__restrict__ fr, const double *__restrict__ x, const int *__restrict__ other_index,
+                        double *__restrict__ f, double *__restrict__ xy, int B, double r2, int gate, double scale)
+{
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6);
+    const int j = lane & 31, h = lane >> 5;
+    const int tile = (int)blockIdx.x * nw + wave;
+    if (tile * 32 >= B) return;
+    const int v = tile * 32 + j;
+    const bool valid = v < B;
+    const int vc = valid ? v : B - 1;
+    const int o = other_index ? other_index[vc] : -1;
+    const bool has = o >= 0 && o < B;
+    const double *xe = x + (size_t)vc * NX, *xo = x + (size_t)(has ? o : vc) * NX;
+    bool open = valid && has;
+    if (gate) open = open && gate_open(xo, xe, r2);
+    if (xy && valid && h == 1) { xy[(size_t)v * 2] = xe[0]; xy[(size_t)v * 2 + 1] = xe[1]; }
+    float zb[3], out[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int s = 0; s < 3; ++s) zb[s] = (float)(xo[2 * s + h] - xe[2 * s + h]);
+    if (__ballot(open) != 0ull) mlp_tile_stream(fr, zb, lane, out);      // (a 64-bit mask in scalar registers: the branch is the wave's)
+    if (valid && h == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) f[(size_t)v * 3 + c] = open ? scale * (double)out[c] : 0.0;
+    }
 }
 
 // One wave, in front of downwash launch m on the second stream: takes the number, waits until the control step that read force
@@ -406,6 +446,41 @@ int ndp_debug_downwash_stream_device(ndp_handle *h, const void *d_other, const v
                        h->cfg.r_horiz * h->cfg.r_horiz, NX, (const int *)nullptr, (unsigned long long *)nullptr, peer_mapped(d_other));
     NDP_HIP(h, hipGetLastError());
     return g.noted(0);
+}
+
+// ---- f4: the downwash force on the plant (plant_force_kernel).  No locking, no sync; d_index null: no network pass, no weights needed.
+int launch_plant_force(ndp_handle *h, const double *d_x, const int *d_index, int gate, double scale, double *d_f, double *d_xy, hipStream_t s)
+{
+    if (d_index && !h->have_mlp) { h->err = "downwash requested but ndp_set_mlp_weights was never called"; return -6; }
+    const int B = h->cfg.batch, ntiles = (B + 31) / 32;
+    const int nw = ntiles < 4 ? ntiles : 4;          // waves per workgroup: no idle wave in a batch of up to 96 vehicles
+    hipLaunchKernelGGL(plant_force_kernel, dim3((ntiles + nw - 1) / nw), dim3(64 * nw), 0, s, (const float *)h->dFrag, d_x, d_index, d_f, d_xy, B,
+                       h->cfg.r_horiz * h->cfg.r_horiz, gate ? 1 : 0, scale);
+    NDP_HIP(h, hipGetLastError());
+    return 0;
+}
+
+int ndp_plant_force_device(ndp_handle *h, const void *d_x, const void *d_other_index, int gate, double scale, void *d_f, void *d_xy,
+                           void *stream)
+{
+    Entry g(h, d_x && d_f, stream);
+    if (g.rc) return g.rc;
+    return g.noted(launch_plant_force(h, (const double *)d_x, (const int *)d_other_index, gate, scale, (double *)d_f, (double *)d_xy, g.s));
+}
+
+int ndp_plant_force(ndp_handle *h, const double *x, const int32_t *other_index, int gate, double scale, double *f)
+{
+    Entry g(h, x && f);
+    if (g.rc) return g.rc;
+    const size_t B = h->cfg.batch;
+    hipStream_t s = h->stream;
+    int *d_index = reinterpret_cast<int *>(h->sThr + 3 * B);          // sThr: f [B][3] | index int32[B]
+    NDP_HIP(h, hipMemcpyAsync(h->sx0, x, B * NX * 8, hipMemcpyHostToDevice, s));
+    if (other_index) NDP_HIP(h, hipMemcpyAsync(d_index, other_index, B * 4, hipMemcpyHostToDevice, s));
+    int rc = launch_plant_force(h, h->sx0, other_index ? d_index : nullptr, gate, scale, h->sThr, nullptr, s);
+    if (rc) return rc;
+    NDP_HIP(h, hipMemcpyAsync(f, h->sThr, B * 3 * 8, hipMemcpyDeviceToHost, s));
+    return g.synced(0);
 }
 
 int ndp_downwash(ndp_handle *h, const double *other, const double *ego_ref, const double *ego_xy, float *f_out)

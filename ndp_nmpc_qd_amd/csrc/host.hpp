@@ -6,8 +6,9 @@
 //                    from them the compiler specialises those functions (different code for them and for the one-launch ticks)
 //   ndp_hip.hip      the handle's runtime: pack threads, create / destroy, every step form (enqueue_step, launch_rti, rti_pick), the
 //                    host-array step, timing, the sensitivities, the adjoint / forward-mode entry points, ndp_set_model, the debug hooks
-//   downwash.hip     the downwash network's forward entry points, mlp_stream_kernel + the prefetch protocol, ndp_set_mlp_weights
-//   rows.hip         the rows f1 - f4: reference window and list, follower relay, throttle estimator, actuator command, plant, rollout
+//   downwash.hip     the downwash network's forward entry points, mlp_stream_kernel + the prefetch protocol, ndp_set_mlp_weights,
+//                    plant_force_kernel (f4: the downwash force on the plant)
+//   rows.hip         the rows f1 - f4: reference window and list, follower relay, throttle estimator, actuator command, plant, rollouts
 //   tick.hip         the control tick's host side (ndp_tick*); no kernel: compiled for the host only
 //   mlp_vjp.hip      the downwash network's backward pass (ndp_downwash_vjp_device) and its weights set from device memory
 //   mlp_jvp.hip      the downwash network's forward mode (ndp_downwash_jvp_device)
@@ -247,6 +248,9 @@ NDP_HIDDEN int launch_rti(ndp_handle *h, const double *d_x0, const double *d_xr,
 NDP_HIDDEN int enqueue_step(ndp_handle *h, const double *d_x0, const double *d_xr, const double *d_ur, const float *d_f, const Neigh &nb,
                             double *d_u0, double *d_dbg, hipStream_t s, const StepOut *so = nullptr);
 NDP_HIDDEN int ensure_slots(ndp_handle *h);
+// downwash.hip
+NDP_HIDDEN int launch_plant_force(ndp_handle *h, const double *d_x, const int *d_index, int gate, double scale, double *d_f, double *d_xy,
+                                  hipStream_t s);
 // rows.hip
 NDP_HIDDEN ThrCfg thr_cfg(const ndp_handle *h);
 NDP_HIDDEN RefCfg ref_cfg(const ndp_handle *h, double toff);

@@ -1,6 +1,6 @@
 // rows.hip -- the rows either side of the control step, kernels and entry points: f1 the reference window and the reference's sliding
 // list (ref_window_kernel, ref_list_*_kernel), f2 the follower relay, f3 the hover-throttle estimator and the actuator command, f4 the
-// plant and the closed-loop rollout.  (A reference point itself, the list store and the estimator's update: ref_point.hpp.)
+// plant and the closed-loop rollouts (the formation rollout's force on the plant: downwash.hip, plant_force_kernel).  (A reference point itself, the list store and the estimator's update: ref_point.hpp.)
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -170,6 +170,15 @@ __global__ __launch_bounds__(256) void plant_kernel(double *__restrict__ x, cons
     for (int i = 6; i < 10; ++i) xv[i] /= n;
 #pragma unroll
     for (int i = 0; i < 5; ++i) reinterpret_cast<double2 *>(x)[(size_t)v * 5 + i] = make_double2(xv[2 * i], xv[2 * i + 1]);
+}
+
+// the formation rollout's worst status per vehicle: the first tick writes it, the later ones keep the larger value
+__global__ __launch_bounds__(256) void status_max_kernel(const int *__restrict__ status, int *__restrict__ worst, int first, int B)
+{
+    const int v = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (v >= B) return;
+    const int st = status[v];
+    worst[v] = first || st > worst[v] ? st : worst[v];
 }
 
 #define REF_ROWS 64     // rows (vehicle, node) per workgroup = one wave: small batches spread over all CUs
@@ -679,6 +688,49 @@ int ndp_rollout_device(ndp_handle *h, int ticks, double t0, double dt_tick, int 
         if (k > 0 && (rc = launch_ref_window(h, nullptr, t0 + k * dt_tick, h->sxr, h->sur, s))) return rc;
         if ((rc = launch_rti(h, x, h->sxr, h->sur, nullptr, h->su0, nullptr, s))) return rc;
         if ((rc = launch_plant(h, x, h->su0, nullptr, dt_tick, substeps, s))) return rc;
+        if (log) NDP_HIP(h, hipMemcpyAsync(log + (size_t)k * B * NX, x, B * NX * 8, hipMemcpyDeviceToDevice, s));
+    }
+    return g.noted(0);
+}
+
+// ---- f4: closed-loop FORMATION rollout: the rollout above with the downwash acting on the plant.  Per tick: reference window -> the force the
+// neighbour's actual state puts on the actual vehicle, + the ego xy (plant_force_kernel, from the states BEFORE the tick's plant step) ->
+// control step (NDP_FORM_COMPENSATE: the fused step of ndp_step_device_ex against this tick's reference windows of the whole batch; else
+// the plain step, blind) -> plant step with that force, held over the tick.  u0 and the force are written straight into their log slots
+// when those are given.  Refused (-8) before anything is enqueued.
+int ndp_rollout_formation_device(ndp_handle *h, int ticks, double t0, double dt_tick, int substeps, const void *d_other_index, int flags,
+                                 double plant_scale, void *d_x, void *d_log, void *d_log_u, void *d_log_f, void *d_worst_status, void *stream)
+{
+    Entry g(h, ticks >= 1 && substeps >= 1 && d_x && !(flags & ~(NDP_FORM_GATE | NDP_FORM_COMPENSATE)), stream, "ndp_rollout_formation_device");
+    if (g.rc) return g.rc;
+    hipStream_t s = g.s;
+    const bool comp = (flags & NDP_FORM_COMPENSATE) != 0, gate = (flags & NDP_FORM_GATE) != 0;
+    const int *idx = (const int *)d_other_index;
+    if (comp && !h->cfg.use_fd) { h->err = "ndp_rollout_formation_device: NDP_FORM_COMPENSATE needs use_fd = 1 (NDP model)"; return -8; }
+    if (idx && !h->have_mlp) { h->err = "ndp_rollout_formation_device: ndp_set_mlp_weights was never called (the force on the plant is the network's)"; return -8; }
+    if (!h->dTraj) { h->err = "ndp_rollout_formation_device: ndp_ref_set_trajectory was never called"; return -8; }
+    const size_t B = h->cfg.batch;
+    double *x = (double *)d_x, *log = (double *)d_log, *log_u = (double *)d_log_u, *log_f = (double *)d_log_f;
+    double *xy = h->sThr + 3 * B;                                      // sThr: f [B][3] | xy [B][2]
+    Neigh nb;
+    nb.other = h->sxr; nb.index = idx; nb.ego_xy = gate ? xy : nullptr;
+    int rc = launch_ref_window(h, nullptr, t0, h->sxr, h->sur, s);     // reset(xr, ur) at the first tick's reference
+    if (rc) return rc;
+    NDP_HIP(h, hipMemcpyAsync(h->dX, h->sxr, nxs(h) * 8, hipMemcpyDefault, s));
+    NDP_HIP(h, hipMemcpyAsync(h->dU, h->sur, nus(h) * 8, hipMemcpyDefault, s));
+    NDP_HIP(h, hipMemsetAsync(h->dAct, 0, act_bytes(h), s));
+    for (int k = 0; k < ticks; ++k) {
+        double *f = log_f ? log_f + (size_t)k * B * 3 : h->sThr, *u = log_u ? log_u + (size_t)k * B * NU : h->su0;
+        if (k > 0 && (rc = launch_ref_window(h, nullptr, t0 + k * dt_tick, h->sxr, h->sur, s))) return rc;
+        if ((rc = launch_plant_force(h, x, idx, gate, plant_scale, f, xy, s))) return rc;
+        if (comp && idx) rc = enqueue_step(h, x, h->sxr, h->sur, nullptr, nb, u, nullptr, s);
+        else rc = launch_rti(h, x, h->sxr, h->sur, nullptr, u, nullptr, s);
+        if (rc) return rc;
+        if (d_worst_status) {
+            hipLaunchKernelGGL(status_max_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, h->lastStatus, (int *)d_worst_status, k == 0, (int)B);
+            NDP_HIP(h, hipGetLastError());
+        }
+        if ((rc = launch_plant(h, x, u, f, dt_tick, substeps, s))) return rc;
         if (log) NDP_HIP(h, hipMemcpyAsync(log + (size_t)k * B * NX, x, B * NX * 8, hipMemcpyDeviceToDevice, s));
     }
     return g.noted(0);

@@ -111,6 +111,8 @@ def main():
         return bench_ref_window(a, torch, ndp, dev)
     if a.row == "rollout":
         return bench_rollout(a, torch, ndp, dev)
+    if a.row == "rollout_formation":
+        return bench_rollout_formation(a, torch, ndp, dev)
     if a.row == "ref_list":
         return bench_ref_list(a, torch, ndp, dev)
     eng = ndp.BatchedNMPC(B, N=2, load_mlp=False)       # tiny horizon: only the estimator state matters here
@@ -263,6 +265,37 @@ def bench_rollout(a, torch, ndp, dev):
                       "metric": "vehicle ticks/s", "value": B * a.steps / el, "batch": B, "ticks": a.steps,
                       "us_per_tick": el / a.steps * 1e6, "simulated_seconds_per_vehicle": a.steps * 0.02,
                       "tracking_error_at_end_m": {"median": float(np.median(err)), "max": float(err.max())}}))
+
+
+def bench_rollout_formation(a, torch, ndp, dev):
+    """The rollout row with the downwash acting on the plant: B vehicles in stacked pairs (scripts/formation_rollout.py: the neighbour
+    0.5 m above), a.steps ticks in one ndp_rollout_formation_device call per controller -- NDP (the fused step predicts the force) and
+    NMPC (blind).  4 launches per tick: reference window, plant force, control step, plant step."""
+    import numpy as np
+    from formation_rollout import set_trajectory, stacked_pairs
+    B = a.batch - a.batch % 2
+    tr, idx = stacked_pairs(B // 2, 0.5, n_seg=int(np.ceil(((a.warmup + a.steps) * 0.02 + 2.5) / 0.5)))
+    idx_t = torch.from_numpy(idx).to(dev)
+    res = {}
+    for name, dist in (("ndp", True), ("nmpc", False)):
+        eng = ndp.BatchedNMPC(B, disturbance=dist, load_mlp=True)
+        set_trajectory(eng, tr)
+        x = torch.from_numpy(eng.ref_window(np.zeros(B))[0][:, 0].copy()).to(dev)
+        worst = torch.zeros(B, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        eng.rollout_formation_device(a.warmup, x, idx_t)
+        eng.synchronize()
+        t0 = time.perf_counter()
+        eng.rollout_formation_device(a.steps, x, idx_t, worst_status=worst, t0=a.warmup * 0.02)
+        eng.synchronize()
+        el = time.perf_counter() - t0
+        xr_end, _ = eng.ref_window(np.full(B, (a.warmup + a.steps) * 0.02))
+        ez = np.abs(x.cpu().numpy()[:, 2] - xr_end[:, 0, 2])
+        res[name] = {"value": B * a.steps / el, "us_per_tick": el / a.steps * 1e6, "worst_status": int(worst.max()),
+                     "z_error_at_end_m": {"lower_max": float(ez[0::2].max()), "upper_max": float(ez[1::2].max())}}
+    print(json.dumps({"row": "closed-loop formation rollout: reference window + plant force (downwash network, one row per vehicle) + "
+                             "control step (N=20, 1 RTI) + plant step per tick, stacked pairs dz = 0.5 m",
+                      "metric": "vehicle ticks/s", "batch": B, "ticks": a.steps, "controllers": res}))
 
 
 if __name__ == "__main__":
