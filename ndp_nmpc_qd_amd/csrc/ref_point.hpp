@@ -100,7 +100,11 @@ __device__ __forceinline__ double traj_chain(const double *__restrict__ ca, int 
 // in the one-launch tick, where a single wave runs the map with nothing to overlap it, ~4 000 cycles of a 7 300-cycle prologue; in the
 // list / window kernels the same chains are why "HBM-bound" kernels sat at 0.4 of the HBM roof.  These are seed + Newton forms
 // (v_rcp_f64 / v_rsq_f64: 2^-26 relative or better; two steps -> ~1e-16, not correctly rounded) and a Cody-Waite sincos with the
-// fdlibm kernel polynomials (|error| < 1 ulp for |x| < 1e5) -- deterministic, shared by every kernel that makes a reference point.
+// fdlibm kernel polynomials -- deterministic, shared by every kernel that makes a reference point.  sincos_n is not correctly rounded
+// and not "under 1 ulp": its ABSOLUTE error stays under 2^-52 = 2.2e-16 (one rounding of the reduced argument + the kernels' ulp; held
+// on the device for |x| <= 1e5 by the `yaw` family of tests/test_ref_point_gpu.py and on a port of this arithmetic for |x| <= 1e8 by
+// tests/test_ref_point.py, largest seen 1.9e-16); in ulps of the result that is up to ~2 on random arguments and more beside a zero.
+// The quadrant comes from (int)k: |x| must stay below 2^31 pi / 2 ~ 3.4e9.
 __device__ __forceinline__ double rcp_n(double a)
 {
     double r = __builtin_amdgcn_rcp(a);

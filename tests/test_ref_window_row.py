@@ -188,6 +188,7 @@ def test_gpu_reference_window_feeds_the_controller(oracle):
     xo, uo = oracle.ref_window(np.concatenate([tc.coeff_x.reshape(B, M, 8), tc.coeff_y.reshape(B, M, 8), tc.coeff_z.reshape(B, M, 8),
                                                tc.coeff_yaw.reshape(B, M, 4)], axis=2), tc.traj_time_cum, tseg, tc.final_pt, np.full(B, 1.0))
     np.testing.assert_allclose(xr.cpu().numpy(), xo, rtol=1e-10, atol=1e-10)
+    np.testing.assert_allclose(ur.cpu().numpy(), uo, rtol=1e-9, atol=1e-9)
     cfg = oracle.default_cfg()
     X, U = xo.copy(), uo.copy()
     u_or, st, _ = oracle.step_batch(cfg, x0.cpu().numpy(), xo, uo, None, X, U)
