@@ -614,6 +614,41 @@ int ndp_rollout_formation_device(ndp_handle *h, int ticks, double t0, double dt_
 #define NDP_FORM_GATE        1   /* r_horiz gate in the plant force and in the controller's prediction */
 #define NDP_FORM_COMPENSATE  2   /* the controller predicts the force (needs use_fd = 1); else it runs blind */
 
+/* ---- Downwash from SEVERAL neighbours.  Every entry point above gives a vehicle one neighbour, as the reference does: its leader subscribes
+ * to one neighbour's prediction (ndp_nmpc_leader_node.py:40), although its flagship is a formation of three (three_qd_ndp_nmpc.launch), where a
+ * vehicle can fly under two others at once.  The calls below take other_index as int32[B][K], K slots per vehicle, 1 <= K <= NDP_MAX_NEIGH,
+ * and SUPERPOSE the slots' forces.  Superposition is a modelling assumption: the network was trained on pairs (dnwash_nn_est/downwash_nn.py:
+ * 22-28 sees one relative state).  The gate (ndp_nmpc_leader_node.py:65-68) is per slot, the same strict expression; a slot with index < 0 is
+ * empty; the same index in two slots counts twice.  Slots are summed in slot order, the first open slot's value taken as it is, closed
+ * slots adding nothing -- so K = 1 reproduces the single-neighbour call bit for bit, and any K equals the sum, in slot order, of K
+ * single-neighbour results.  K outside 1..NDP_MAX_NEIGH: -2, nothing enqueued.  The derivative paths, the fused step and the tick stay
+ * single-neighbour (the derivative of a sum is K calls with the same upstream).
+ * ndp_downwash_multi*: the controller's prediction, f_out[B][N+1][3] fp32 = sum over k (fp32) of ndp_downwash_device's value for neighbour
+ *   other_index[i][k]: the network at (other - ego_ref)[0:6], slot k open iff index >= 0 and (ego_xy NULL or |other[o_k] node 0 xy -
+ *   ego_xy[i]|^2 < r_horiz^2).  Device form: d_other [rows][N+1][other_stride] and other_stride (10 or 6, else -13) as ndp_step_device_ex;
+ *   host form: other[B][N+1][10].  One launch; the weights are moved on chip once per workgroup and reused by the K slots.
+ * ndp_plant_force_multi*: the force on the plant, f[v] = sum over k (fp64, products and sums individually rounded) of scale * (double)net(x[o_k]
+ *   - x[v]) = the sum of K ndp_plant_force results; a slot with o < 0 or o >= B contributes exactly 0 and is never read; other_index NULL:
+ *   nobody has a neighbour (zeros, no weights needed).  d_xy as ndp_plant_force_device. */
+#define NDP_MAX_NEIGH 8
+int ndp_downwash_multi_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index, int K, const void *d_ego_ref,
+                              const void *d_ego_xy, void *d_f_out, void *stream);
+int ndp_downwash_multi(ndp_handle *h, const double *other, const int32_t *other_index, int K, const double *ego_ref, const double *ego_xy,
+                       float *f_out);
+int ndp_plant_force_multi_device(ndp_handle *h, const void *d_x, const void *d_other_index, int K, int gate, double scale, void *d_f,
+                                 void *d_xy, void *stream);
+int ndp_plant_force_multi(ndp_handle *h, const double *x, const int32_t *other_index, int K, int gate, double scale, double *f);
+/* ndp_rollout_formation_multi_device: ndp_rollout_formation_device with d_other_index int32[B][K].  Per tick k: reference window at t0 +
+ *   k*dt_tick -> the summed plant force (ndp_plant_force_multi_device at plant_scale, which also writes the ego xy) -> with NDP_FORM_COMPENSATE
+ *   the summed prediction (ndp_downwash_multi_device: d_other = d_ego_ref = this tick's reference windows of the whole batch, d_ego_xy = the
+ *   plant's xy when NDP_FORM_GATE is set) into the handle's force buffer and the control step with that force as d_f (ndp_step_device's
+ *   external-force step); without it the plain step -> plant step with the plant force.  Logs and -8 / -2 refusals as
+ *   ndp_rollout_formation_device, and -2 for K outside 1..NDP_MAX_NEIGH (checked even when d_other_index is NULL: pass 1); d_other_index
+ *   NULL: ndp_rollout_device's states.  One stream, nothing is synchronised. */
+int ndp_rollout_formation_multi_device(ndp_handle *h, int ticks, double t0, double dt_tick, int substeps, const void *d_other_index, int K,
+                                       int flags, double plant_scale, void *d_x, void *d_log, void *d_log_u, void *d_log_f,
+                                       void *d_worst_status, void *stream);
+
 /* ---- Peer windows: the neighbour exchange across GPUs as publish / subscribe over xGMI.
  * Replaces the PredXU topic between processes: the publisher is nmpc_node.py:116-133,229-230 (`nmpc_x_ref`, 21x10 float64, a NEW
  * message every control tick), the subscriber ndp_nmpc_leader_node.py:40,60-76 (consumes the latest one).  One process per GPU:

@@ -19,6 +19,7 @@ QP_AUTO, QP_IPM_ALWAYS = 0, 1
 ABI_VERSION = 9          # include/ndp_nmpc.h: NDP_ABI_VERSION (checked against the loaded library in load())
 TICK_ESTIMATE, TICK_WANT_U0, TICK_T_UNIFORM = 1, 2, 4
 FORM_GATE, FORM_COMPENSATE = 1, 2       # include/ndp_nmpc.h: NDP_FORM_*
+MAX_NEIGH = 8                           # include/ndp_nmpc.h: NDP_MAX_NEIGH (neighbours per vehicle of the *_multi entry points)
 
 
 class NdpCfg(C.Structure):
@@ -60,6 +61,8 @@ EXPORTS = [
     "ndp_downwash_vjp_device", "ndp_downwash_jvp_device", "ndp_set_mlp_weights_device", "ndp_debug_mlp_fragments",
     "ndp_step_vjp_model_device", "ndp_set_model", "ndp_step_jvp_device",
     "ndp_plant_force", "ndp_plant_force_device", "ndp_rollout_formation_device",
+    "ndp_downwash_multi", "ndp_downwash_multi_device", "ndp_plant_force_multi", "ndp_plant_force_multi_device",
+    "ndp_rollout_formation_multi_device",
 ]
 
 _lib = None
@@ -208,6 +211,11 @@ def load():
     lib.ndp_rollout_formation_device.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, vp, C.c_int, C.c_double] + [vp] * 6
     lib.ndp_plant_force.argtypes = [vp, vp, vp, C.c_int, C.c_double, vp]
     lib.ndp_plant_force_device.argtypes = [vp, vp, vp, C.c_int, C.c_double, vp, vp, vp]
+    lib.ndp_downwash_multi.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
+    lib.ndp_downwash_multi_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    lib.ndp_plant_force_multi.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, vp]
+    lib.ndp_plant_force_multi_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp]
+    lib.ndp_rollout_formation_multi_device.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, vp, C.c_int, C.c_int, C.c_double] + [vp] * 6
     lib.ndp_plant_step.argtypes = [vp, vp, vp, vp, C.c_double, C.c_int]
     lib.ndp_plant_step_device.argtypes = [vp, vp, vp, vp, C.c_double, C.c_int, vp]
     _lib = lib

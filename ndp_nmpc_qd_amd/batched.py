@@ -422,6 +422,84 @@ class BatchedNMPC:
             self._dptr(log_f, torch.float64, (K, B, 3)), self._dptr(worst_status, torch.int32, (B,)), self._stream(stream)),
             "ndp_rollout_formation_device")
 
+    # ---- f4 with K neighbours per vehicle: the forces of the slots superposed (a modelling assumption: the network was trained on pairs)
+    def _index_multi(self, other_index):
+        """other_index int32[B, K] as a contiguous array -> (array, K)."""
+        oi = np.ascontiguousarray(other_index, dtype=np.int32)
+        if oi.ndim != 2 or oi.shape[0] != self.B:
+            raise ValueError(f"other_index: expected int32 [{self.B}, K], got {tuple(oi.shape)}")
+        return oi, int(oi.shape[1])
+
+    def _dindex_multi(self, other_index):
+        """other_index int32[B, K] CUDA tensor -> (pointer, K)."""
+        import torch
+        if not (isinstance(other_index, torch.Tensor) and other_index.dim() == 2):
+            raise ValueError(f"other_index: expected a CUDA int32 [{self.B}, K] tensor")
+        K = int(other_index.shape[1])
+        return self._dptr(other_index, torch.int32, (self.B, K)), K
+
+    def downwash_multi(self, other, other_index, ego_ref, ego_xy=None):
+        """downwash with K neighbours per instance (ndp_downwash_multi; include/ndp_nmpc.h): other[B,N+1,10] the batch's windows,
+        other_index int32[B,K] the rows of `other` instance i hears (< 0: an empty slot).  Returns f[B,N+1,3] float32: the fp32 sum, in slot
+        order, of what downwash gives per slot, each slot behind its own gate (ego_xy[B,2]; None: open)."""
+        other = _lib.f64(other, (self.B, self.N + 1, 10))
+        ego_ref = _lib.f64(ego_ref, (self.B, self.N + 1, 10))
+        ego_xy = _lib.f64(ego_xy, (self.B, 2))
+        oi, K = self._index_multi(other_index)
+        f = np.empty((self.B, self.N + 1, 3), dtype=np.float32)
+        self._check(self._lib.ndp_downwash_multi(self._h, _lib.ptr(other), _lib.ptr(oi), K, _lib.ptr(ego_ref), _lib.ptr(ego_xy), _lib.ptr(f)),
+                    "ndp_downwash_multi")
+        return f
+
+    def downwash_multi_device(self, other, other_index, ego_ref, f_out, ego_xy=None, stream=None):
+        """downwash_multi on CUDA tensors, enqueued on `stream` with no synchronisation (ndp_downwash_multi_device): other [rows,N+1,6 or
+        10] float64 as update_device takes it with other_index, other_index int32[B,K], ego_ref[B,N+1,10], f_out[B,N+1,3] float32 (the
+        `f` of update_device), ego_xy[B,2] or None."""
+        import torch
+        B, N = self.B, self.N
+        optr, stride = self._other_ptr(other, other_index)
+        iptr, K = self._dindex_multi(other_index)
+        self._check(self._lib.ndp_downwash_multi_device(
+            self._h, optr, stride, iptr, K, self._dptr(ego_ref, torch.float64, (B, N + 1, 10)), self._dptr(ego_xy, torch.float64, (B, 2)),
+            self._dptr(f_out, torch.float32, (B, N + 1, 3)), self._stream(stream)), "ndp_downwash_multi_device")
+
+    def plant_force_multi(self, x, other_index, gate=True, scale=1.0):
+        """plant_force with K neighbours per vehicle (ndp_plant_force_multi): other_index int32[B,K] (< 0 or >= B: an empty slot).  Returns
+        f[B,3] float64: the fp64 sum, in slot order, of what plant_force gives per slot."""
+        x = _lib.f64(x, (self.B, 10))
+        oi, K = self._index_multi(other_index)
+        f = np.empty((self.B, 3))
+        self._check(self._lib.ndp_plant_force_multi(self._h, _lib.ptr(x), _lib.ptr(oi), K, 1 if gate else 0, float(scale), _lib.ptr(f)),
+                    "ndp_plant_force_multi")
+        return f
+
+    def plant_force_multi_device(self, x, other_index, f_out, xy_out=None, gate=True, scale=1.0, stream=None):
+        """plant_force_multi on CUDA tensors, enqueued on `stream` with no synchronisation (ndp_plant_force_multi_device): x[B,10] float64,
+        other_index int32[B,K], f_out[B,3] float64; xy_out[B,2] float64 (optional) receives x[:, 0:2]."""
+        import torch
+        iptr, K = self._dindex_multi(other_index)
+        self._check(self._lib.ndp_plant_force_multi_device(
+            self._h, self._dptr(x, torch.float64, (self.B, 10)), iptr, K, 1 if gate else 0, float(scale),
+            self._dptr(f_out, torch.float64, (self.B, 3)), self._dptr(xy_out, torch.float64, (self.B, 2)), self._stream(stream)),
+            "ndp_plant_force_multi_device")
+
+    def rollout_formation_multi_device(self, ticks, x, other_index, log=None, log_u=None, log_f=None, worst_status=None, t0=0.0,
+                                       dt=CP.ts_nmpc, substeps=4, gate=True, compensate=None, plant_scale=1.0, stream=None):
+        """rollout_formation_device with K neighbours per vehicle (ndp_rollout_formation_multi_device; include/ndp_nmpc.h): other_index
+        int32[B,K] CUDA tensor (< 0: an empty slot) or None.  The plant feels the sum of the slots' forces (plant_force_multi_device); with
+        compensate the controller is given the sum of the slots' predictions (downwash_multi_device on the batch's reference windows, then
+        the step with that f).  Everything else as rollout_formation_device."""
+        import torch
+        T, B = int(ticks), self.B
+        comp = self.disturbance if compensate is None else bool(compensate)
+        flags = (_lib.FORM_GATE if gate else 0) | (_lib.FORM_COMPENSATE if comp else 0)
+        iptr, K = (None, 1) if other_index is None else self._dindex_multi(other_index)
+        self._check(self._lib.ndp_rollout_formation_multi_device(
+            self._h, T, float(t0), float(dt), int(substeps), iptr, K, flags, float(plant_scale),
+            self._dptr(x, torch.float64, (B, 10)), self._dptr(log, torch.float64, (T, B, 10)), self._dptr(log_u, torch.float64, (T, B, 4)),
+            self._dptr(log_f, torch.float64, (T, B, 3)), self._dptr(worst_status, torch.int32, (B,)), self._stream(stream)),
+            "ndp_rollout_formation_multi_device")
+
     def get_iterate(self):
         X = np.empty((self.B, self.N + 1, 10))
         U = np.empty((self.B, self.N, 4))

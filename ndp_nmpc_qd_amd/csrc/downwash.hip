@@ -4,6 +4,8 @@
 //   mlp_stream_kernel + prefetch_gate_kernel / prefetch_done_kernel : the downwash of the NEXT tick on a second stream, LDS-free
 //                 (weights out of L2), ordered against the control step by per-tile epochs (LateArgs / PF_* words).
 //   plant_force_kernel : f4, the downwash force on the plant from the vehicles' actual states, one row per vehicle (ndp_plant_force*).
+//   mlp_multi_kernel / plant_force_multi_kernel : the prediction and the plant force with K neighbours per vehicle, forces summed
+//                 (ndp_downwash_multi*, ndp_plant_force_multi*).
 // (The fused form runs inside the control step: rti_kernels.hip.  The backward pass: mlp_vjp.hip.)
 #include <hip/hip_runtime.h>
 
@@ -188,6 +190,121 @@ void plant_force_kernel(const float *__restrict__ fr, const double *__restrict__
     if (valid && h == 0) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) f[(size_t)v * 3 + c] = open ? scale * (double)out[c] : 0.0;
+    }
+}
+
+// ---- K neighbours per vehicle, forces superposed (a modelling assumption: the network was trained on pairs).  other_index is int32[B][K],
+// 1 <= K <= NDP_MAX_NEIGH; a slot is one neighbour, gated on its own; slots are summed in slot order, the first open slot's value taken as
+// it is, closed slots adding nothing.  Both kernels run the slots as a ROLLED loop around the tile: every weight load is then loop-invariant,
+// and left alone the compiler hoists the weights out of the loop into registers (rti_kernels.hip: mlp_kernel; mlp_jvp.hip) -- the weights'
+// base is made opaque at the head of every round.  A slot none of whose 32 rows is open is skipped as a whole (wave-uniform ballot).
+struct MlpMultiArgs {
+    const float *fr;
+    const double *other, *ego, *ego_xy;     // other [rows][np1][other_stride], ego [B][np1][10], ego_xy [B][2] or null
+    const int *other_index;                 // [B][K]
+    float *fout;                            // [B][np1][3]
+    int rows, np1, K, other_stride, other_sys;
+    double r2;
+};
+
+// The controller's prediction: row (instance i, node n) = sum over the slots of what mlp_kernel gives for neighbour other_index[i][k], in
+// fp32.  mlp_kernel's mapping (one wave per 32-row tile, four per workgroup) and its tile, mlp_tile, on the fragment image parked in LDS
+// once per workgroup: the K slots reuse it, which is what one launch buys over K launches of mlp_kernel (K transfers) plus an add.
+__global__ __launch_bounds__(256) void mlp_multi_kernel(MlpMultiArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) float wsm[];
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    const int j = lane & 31, h = lane >> 5;
+    const int ntiles = (A.rows + 31) / 32;
+    const int tile = (int)blockIdx.x * 4 + wave;
+    stage_fragments(A.fr, (lds_f32)wsm, (int)threadIdx.x, 256);
+    __syncthreads();
+    if (tile >= ntiles) return;
+    const int row = tile * 32 + j;
+    const bool valid = row < A.rows;
+    const int rowc = valid ? row : A.rows - 1;
+    const int inst = rowc / A.np1, k = rowc - inst * A.np1;
+    double e[3];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) e[s] = A.ego[(size_t)rowc * NX + 2 * s + h];
+    float f[3] = {0.0f, 0.0f, 0.0f};
+    bool any = false;
+#pragma unroll 1
+    for (int q = 0; q < A.K; ++q) {
+        unsigned base = 0;
+        asm volatile("" : "+s"(base));       // (the image is the same in every round: see above)
+        lds_cf32 wl = (lds_cf32)wsm + base;
+        const int orow = A.other_index[(size_t)inst * A.K + q];
+        const double *oth = A.other + (size_t)(orow < 0 ? 0 : orow) * A.np1 * A.other_stride;
+        bool open = valid && orow >= 0;
+        if (A.ego_xy) {
+            const double oxy[2] = {ld_other(oth, A.other_sys), ld_other(oth + 1, A.other_sys)};
+            open = open && gate_open(oxy, A.ego_xy + (size_t)inst * 2, A.r2);
+        }
+        if (__ballot(open) == 0ull) continue;
+        float zb[3], o[3];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) zb[s] = (float)(ld_other(oth + (size_t)k * A.other_stride + 2 * s + h, A.other_sys) - e[s]);
+        mlp_tile(wl, zb, lane, o);
+        if (open) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) f[c] = any ? f[c] + o[c] : o[c];
+            any = true;
+        }
+    }
+    if (valid && h == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) A.fout[(size_t)row * 3 + c] = f[c];
+    }
+}
+
+// The force on the plant: plant_force_kernel with K slots per vehicle, f[v] = sum over the open slots of scale * (double)net(x[o_k] - x[v])
+// in fp64 (products and sums individually rounded: the sum of K ndp_plant_force results, bit for bit).  A slot with o < 0 or o >= B
+// contributes exactly 0 and is never read.  The same stream tile, launch shape and tail rule as plant_force_kernel.
+__global__ __launch_bounds__(256)
+void plant_force_multi_kernel(const float *__restrict__ fr, const double *__restrict__ x, const int *__restrict__ other_index, int K,
+                              double *__restrict__ f, double *__restrict__ xy, int B, double r2, int gate, double scale)
+{
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6);
+    const int j = lane & 31, h = lane >> 5;
+    const int tile = (int)blockIdx.x * nw + wave;
+    if (tile * 32 >= B) return;
+    const int v = tile * 32 + j;
+    const bool valid = v < B;
+    const int vc = valid ? v : B - 1;
+    const double *xe = x + (size_t)vc * NX;
+    if (xy && valid && h == 1) { xy[(size_t)v * 2] = xe[0]; xy[(size_t)v * 2 + 1] = xe[1]; }
+    double e[3], acc[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < 3; ++s) e[s] = xe[2 * s + h];
+    bool any = false;
+#pragma unroll 1
+    for (int q = 0; q < K; ++q) {
+        unsigned base = 0;
+        asm volatile("" : "+s"(base));       // (the weights are the same in every round: see above; an opaque OFFSET, so that fr stays a
+        g_cf32 frq = fr + base;              // global-memory pointer -- an opaque pointer is a generic one, and its loads flat loads)
+        const int o = other_index[(size_t)vc * K + q];
+        const bool has = o >= 0 && o < B;
+        const double *xo = x + (size_t)(has ? o : vc) * NX;
+        bool open = valid && has;
+        if (gate) open = open && gate_open(xo, xe, r2);
+        if (__ballot(open) == 0ull) continue;
+        float zb[3], out[3];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) zb[s] = (float)(xo[2 * s + h] - e[s]);
+        mlp_tile_stream(frq, zb, lane, out);
+        if (open) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const double p = nc_mul(scale, (double)out[c]);
+                acc[c] = any ? nc_add(acc[c], p) : p;
+            }
+            any = true;
+        }
+    }
+    if (valid && h == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) f[(size_t)v * 3 + c] = acc[c];
     }
 }
 
@@ -478,6 +595,110 @@ int ndp_plant_force(ndp_handle *h, const double *x, const int32_t *other_index, 
     NDP_HIP(h, hipMemcpyAsync(h->sx0, x, B * NX * 8, hipMemcpyHostToDevice, s));
     if (other_index) NDP_HIP(h, hipMemcpyAsync(d_index, other_index, B * 4, hipMemcpyHostToDevice, s));
     int rc = launch_plant_force(h, h->sx0, other_index ? d_index : nullptr, gate, scale, h->sThr, nullptr, s);
+    if (rc) return rc;
+    NDP_HIP(h, hipMemcpyAsync(f, h->sThr, B * 3 * 8, hipMemcpyDeviceToHost, s));
+    return g.synced(0);
+}
+
+// ---- K neighbours per vehicle (mlp_multi_kernel, plant_force_multi_kernel).  No locking, no sync.
+// allow mlp_multi_kernel's dynamic-LDS launch (ndp_create)
+hipError_t mlp_multi_prepare(void)
+{
+    return hipFuncSetAttribute((const void *)mlp_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FR_TOTAL * sizeof(float)));
+}
+
+// -2 (nothing enqueued) unless 1 <= K <= NDP_MAX_NEIGH
+int check_neigh(ndp_handle *h, const char *who, int K)
+{
+    if (K >= 1 && K <= NDP_MAX_NEIGH) return 0;
+    h->err = std::string(who) + ": K must be 1..8 (NDP_MAX_NEIGH neighbours per vehicle), got " + std::to_string(K);
+    return -2;
+}
+
+int launch_mlp_multi(ndp_handle *h, const double *d_other, int other_stride, const int *d_index, int K, const double *d_ego,
+                     const double *d_ego_xy, float *d_f, hipStream_t s)
+{
+    if (!h->have_mlp) { h->err = "downwash requested but ndp_set_mlp_weights was never called"; return -6; }
+    const int np1 = h->cfg.N + 1, rows = h->cfg.batch * np1;
+    const int ntiles = (rows + 31) / 32;
+    MlpMultiArgs a{h->dFrag, d_other, d_ego, d_ego_xy, d_index, d_f, rows, np1, K, other_stride, peer_mapped(d_other),
+                   h->cfg.r_horiz * h->cfg.r_horiz};
+    hipLaunchKernelGGL(mlp_multi_kernel, dim3((ntiles + 3) / 4), dim3(256), FR_TOTAL * sizeof(float), s, a);
+    NDP_HIP(h, hipGetLastError());
+    return 0;
+}
+
+int launch_plant_force_multi(ndp_handle *h, const double *d_x, const int *d_index, int K, int gate, double scale, double *d_f, double *d_xy,
+                             hipStream_t s)
+{
+    if (!d_index) return launch_plant_force(h, d_x, nullptr, gate, scale, d_f, d_xy, s);      // nobody has a neighbour: zeros, no weights needed
+    if (!h->have_mlp) { h->err = "downwash requested but ndp_set_mlp_weights was never called"; return -6; }
+    const int B = h->cfg.batch, ntiles = (B + 31) / 32;
+    const int nw = ntiles < 4 ? ntiles : 4;
+    hipLaunchKernelGGL(plant_force_multi_kernel, dim3((ntiles + nw - 1) / nw), dim3(64 * nw), 0, s, (const float *)h->dFrag, d_x, d_index, K, d_f,
+                       d_xy, B, h->cfg.r_horiz * h->cfg.r_horiz, gate ? 1 : 0, scale);
+    NDP_HIP(h, hipGetLastError());
+    return 0;
+}
+
+int ndp_downwash_multi_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index, int K, const void *d_ego_ref,
+                              const void *d_ego_xy, void *d_f_out, void *stream)
+{
+    Entry g(h, true, stream);
+    if (g.rc) return g.rc;
+    int rc = check_neigh(h, "ndp_downwash_multi_device", K);      // (in front of the arguments: an index array of K = 0 may well be NULL)
+    if (rc) return rc;
+    if (!(d_other && d_other_index && d_ego_ref && d_f_out)) return -1;
+    if (other_stride != 10 && other_stride != 6) { h->err = "ndp_downwash_multi_device: other_stride must be 10 or 6"; return -13; }
+    return g.noted(launch_mlp_multi(h, (const double *)d_other, other_stride, (const int *)d_other_index, K, (const double *)d_ego_ref,
+                                    (const double *)d_ego_xy, (float *)d_f_out, g.s));
+}
+
+int ndp_downwash_multi(ndp_handle *h, const double *other, const int32_t *other_index, int K, const double *ego_ref, const double *ego_xy,
+                       float *f_out)
+{
+    Entry g(h, true);
+    if (g.rc) return g.rc;
+    int rc = check_neigh(h, "ndp_downwash_multi", K);
+    if (rc) return rc;
+    if (!(other && other_index && ego_ref && f_out)) return -1;
+    const size_t B = h->cfg.batch;
+    hipStream_t s = h->stream;
+    int *d_index = reinterpret_cast<int *>(h->sThr);                  // sThr: index int32[B][K] (at most 4 B doubles)
+    NDP_HIP(h, hipMemcpyAsync(h->sother, other, nxs(h) * 8, hipMemcpyHostToDevice, s));
+    NDP_HIP(h, hipMemcpyAsync(h->sxr, ego_ref, nxs(h) * 8, hipMemcpyHostToDevice, s));
+    NDP_HIP(h, hipMemcpyAsync(d_index, other_index, B * K * 4, hipMemcpyHostToDevice, s));
+    if (ego_xy) NDP_HIP(h, hipMemcpyAsync(h->sego, ego_xy, B * 2 * 8, hipMemcpyHostToDevice, s));
+    rc = launch_mlp_multi(h, h->sother, NX, d_index, K, h->sxr, ego_xy ? h->sego : nullptr, h->dForce, s);
+    if (rc) return rc;
+    NDP_HIP(h, hipMemcpyAsync(f_out, h->dForce, nfs(h) * 4, hipMemcpyDeviceToHost, s));
+    return g.synced(0);
+}
+
+int ndp_plant_force_multi_device(ndp_handle *h, const void *d_x, const void *d_other_index, int K, int gate, double scale, void *d_f,
+                                 void *d_xy, void *stream)
+{
+    Entry g(h, true, stream);
+    if (g.rc) return g.rc;
+    int rc = check_neigh(h, "ndp_plant_force_multi_device", K);
+    if (rc) return rc;
+    if (!(d_x && d_f)) return -1;
+    return g.noted(launch_plant_force_multi(h, (const double *)d_x, (const int *)d_other_index, K, gate, scale, (double *)d_f, (double *)d_xy, g.s));
+}
+
+int ndp_plant_force_multi(ndp_handle *h, const double *x, const int32_t *other_index, int K, int gate, double scale, double *f)
+{
+    Entry g(h, true);
+    if (g.rc) return g.rc;
+    int rc = check_neigh(h, "ndp_plant_force_multi", K);
+    if (rc) return rc;
+    if (!(x && f)) return -1;
+    const size_t B = h->cfg.batch;
+    hipStream_t s = h->stream;
+    int *d_index = reinterpret_cast<int *>(h->sThr + 3 * B);          // sThr: f [B][3] | index int32[B][K] (at most 4 B doubles)
+    NDP_HIP(h, hipMemcpyAsync(h->sx0, x, B * NX * 8, hipMemcpyHostToDevice, s));
+    if (other_index) NDP_HIP(h, hipMemcpyAsync(d_index, other_index, B * K * 4, hipMemcpyHostToDevice, s));
+    rc = launch_plant_force_multi(h, h->sx0, other_index ? d_index : nullptr, K, gate, scale, h->sThr, nullptr, s);
     if (rc) return rc;
     NDP_HIP(h, hipMemcpyAsync(f, h->sThr, B * 3 * 8, hipMemcpyDeviceToHost, s));
     return g.synced(0);

@@ -7,7 +7,7 @@
 //   ndp_hip.hip      the handle's runtime: pack threads, create / destroy, every step form (enqueue_step, launch_rti, rti_pick), the
 //                    host-array step, timing, the sensitivities, the adjoint / forward-mode entry points, ndp_set_model, the debug hooks
 //   downwash.hip     the downwash network's forward entry points, mlp_stream_kernel + the prefetch protocol, ndp_set_mlp_weights,
-//                    plant_force_kernel (f4: the downwash force on the plant)
+//                    plant_force_kernel (f4: the downwash force on the plant), mlp_multi_kernel / plant_force_multi_kernel (K neighbours)
 //   rows.hip         the rows f1 - f4: reference window and list, follower relay, throttle estimator, actuator command, plant, rollouts
 //   tick.hip         the control tick's host side (ndp_tick*); no kernel: compiled for the host only
 //   mlp_vjp.hip      the downwash network's backward pass (ndp_downwash_vjp_device) and its weights set from device memory
@@ -251,6 +251,13 @@ NDP_HIDDEN int ensure_slots(ndp_handle *h);
 // downwash.hip
 NDP_HIDDEN int launch_plant_force(ndp_handle *h, const double *d_x, const int *d_index, int gate, double scale, double *d_f, double *d_xy,
                                   hipStream_t s);
+// ... and with K neighbours per vehicle, d_index int32[B][K] (check_neigh: -2 unless 1 <= K <= NDP_MAX_NEIGH; the launchers do not check)
+NDP_HIDDEN hipError_t mlp_multi_prepare(void);
+NDP_HIDDEN int check_neigh(ndp_handle *h, const char *who, int K);
+NDP_HIDDEN int launch_mlp_multi(ndp_handle *h, const double *d_other, int other_stride, const int *d_index, int K, const double *d_ego,
+                                const double *d_ego_xy, float *d_f, hipStream_t s);
+NDP_HIDDEN int launch_plant_force_multi(ndp_handle *h, const double *d_x, const int *d_index, int K, int gate, double scale, double *d_f,
+                                        double *d_xy, hipStream_t s);
 // rows.hip
 NDP_HIDDEN ThrCfg thr_cfg(const ndp_handle *h);
 NDP_HIDDEN RefCfg ref_cfg(const ndp_handle *h, double toff);

@@ -374,6 +374,7 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
     const int lds_bytes = (int)(per_wave_bytes * h->waves);
     if ((e = mlp_prepare()) != hipSuccess) return fail("hipFuncSetAttribute(mlp_kernel)", e);
     if ((e = mlp_vjp_prepare()) != hipSuccess) return fail("hipFuncSetAttribute(mlp_vjp_kernel)", e);
+    if ((e = mlp_multi_prepare()) != hipSuccess) return fail("hipFuncSetAttribute(mlp_multi_kernel)", e);
     const char *what = nullptr;
     if ((e = rti_set_lds(false, lds_bytes, &what)) != hipSuccess) return fail(what, e);      // (the sensitivity kernels: ndp_sens_enable)
     launch_throttle_reset(h);

@@ -736,4 +736,49 @@ int ndp_rollout_formation_device(ndp_handle *h, int ticks, double t0, double dt_
     return g.noted(0);
 }
 
+// ---- f4: the formation rollout with K neighbours per vehicle, forces superposed (other_index int32[B][K]).  Per tick: reference window ->
+// plant_force_multi_kernel (the summed force from the states BEFORE the tick's plant step, + the ego xy) -> NDP_FORM_COMPENSATE:
+// mlp_multi_kernel on this tick's reference windows of the whole batch into the handle's force buffer, then the control step with that force
+// as its external force (the step of ndp_step_device with d_f: no control-step kernel knows about K); else the plain step, blind -> plant
+// step with the plant force, held over the tick.  Refused (-8 / -2) before anything is enqueued.
+int ndp_rollout_formation_multi_device(ndp_handle *h, int ticks, double t0, double dt_tick, int substeps, const void *d_other_index, int K,
+                                       int flags, double plant_scale, void *d_x, void *d_log, void *d_log_u, void *d_log_f,
+                                       void *d_worst_status, void *stream)
+{
+    Entry g(h, ticks >= 1 && substeps >= 1 && d_x && !(flags & ~(NDP_FORM_GATE | NDP_FORM_COMPENSATE)), stream, "ndp_rollout_formation_multi_device");
+    if (g.rc) return g.rc;
+    hipStream_t s = g.s;
+    const bool comp = (flags & NDP_FORM_COMPENSATE) != 0, gate = (flags & NDP_FORM_GATE) != 0;
+    const int *idx = (const int *)d_other_index;
+    int rc = check_neigh(h, "ndp_rollout_formation_multi_device", K);      // (also without an index: an index array of K = 0 may well be NULL)
+    if (rc) return rc;
+    if (comp && !h->cfg.use_fd) { h->err = "ndp_rollout_formation_multi_device: NDP_FORM_COMPENSATE needs use_fd = 1 (NDP model)"; return -8; }
+    if (idx && !h->have_mlp) { h->err = "ndp_rollout_formation_multi_device: ndp_set_mlp_weights was never called (the force on the plant is the network's)"; return -8; }
+    if (!h->dTraj) { h->err = "ndp_rollout_formation_multi_device: ndp_ref_set_trajectory was never called"; return -8; }
+    const size_t B = h->cfg.batch;
+    double *x = (double *)d_x, *log = (double *)d_log, *log_u = (double *)d_log_u, *log_f = (double *)d_log_f;
+    double *xy = h->sThr + 3 * B;                                      // sThr: f [B][3] | xy [B][2]
+    if ((rc = launch_ref_window(h, nullptr, t0, h->sxr, h->sur, s))) return rc;     // reset(xr, ur) at the first tick's reference
+    NDP_HIP(h, hipMemcpyAsync(h->dX, h->sxr, nxs(h) * 8, hipMemcpyDefault, s));
+    NDP_HIP(h, hipMemcpyAsync(h->dU, h->sur, nus(h) * 8, hipMemcpyDefault, s));
+    NDP_HIP(h, hipMemsetAsync(h->dAct, 0, act_bytes(h), s));
+    for (int k = 0; k < ticks; ++k) {
+        double *f = log_f ? log_f + (size_t)k * B * 3 : h->sThr, *u = log_u ? log_u + (size_t)k * B * NU : h->su0;
+        if (k > 0 && (rc = launch_ref_window(h, nullptr, t0 + k * dt_tick, h->sxr, h->sur, s))) return rc;
+        if ((rc = launch_plant_force_multi(h, x, idx, K, gate, plant_scale, f, xy, s))) return rc;
+        if (comp && idx) {
+            if ((rc = launch_mlp_multi(h, h->sxr, NX, idx, K, h->sxr, gate ? xy : nullptr, h->dForce, s))) return rc;
+            rc = enqueue_step(h, x, h->sxr, h->sur, h->dForce, Neigh{}, u, nullptr, s);
+        } else rc = launch_rti(h, x, h->sxr, h->sur, nullptr, u, nullptr, s);
+        if (rc) return rc;
+        if (d_worst_status) {
+            hipLaunchKernelGGL(status_max_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, h->lastStatus, (int *)d_worst_status, k == 0, (int)B);
+            NDP_HIP(h, hipGetLastError());
+        }
+        if ((rc = launch_plant(h, x, u, f, dt_tick, substeps, s))) return rc;
+        if (log) NDP_HIP(h, hipMemcpyAsync(log + (size_t)k * B * NX, x, B * NX * 8, hipMemcpyDeviceToDevice, s));
+    }
+    return g.noted(0);
+}
+
 }  // extern "C"

@@ -115,6 +115,10 @@ def main():
         return bench_rollout_formation(a, torch, ndp, dev)
     if a.row == "ref_list":
         return bench_ref_list(a, torch, ndp, dev)
+    if a.row == "downwash_multi":
+        return bench_downwash_multi(a, torch, ndp, dev)
+    if a.row == "rollout_formation_multi":
+        return bench_rollout_formation_multi(a, torch, ndp, dev)
     eng = ndp.BatchedNMPC(B, N=2, load_mlp=False)       # tiny horizon: only the estimator state matters here
     vz = torch.randn(B, dtype=torch.float64, device=dev) * 0.1
     th = torch.rand(B, dtype=torch.float64, device=dev) * 0.8 + 0.15
@@ -295,6 +299,84 @@ def bench_rollout_formation(a, torch, ndp, dev):
                      "z_error_at_end_m": {"lower_max": float(ez[0::2].max()), "upper_max": float(ez[1::2].max())}}
     print(json.dumps({"row": "closed-loop formation rollout: reference window + plant force (downwash network, one row per vehicle) + "
                              "control step (N=20, 1 RTI) + plant step per tick, stacked pairs dz = 0.5 m",
+                      "metric": "vehicle ticks/s", "batch": B, "ticks": a.steps, "controllers": res}))
+
+
+def bench_downwash_multi(a, torch, ndp, dev):
+    """The controller's prediction from K neighbours (B = a.batch instances, N = 20), K = 2 and 3: ONE ndp_downwash_multi_device launch
+    (the weights parked in LDS once per workgroup, reused by the K slots) against what the single-neighbour library needs for the same
+    sum -- K launches of ndp_downwash_device on pre-gathered windows plus torch adds -- in the same run, alternating, by device events."""
+    import numpy as np
+    B, N = a.batch, 20
+    rng = np.random.default_rng(7)
+    eng = ndp.BatchedNMPC(B, N=N, load_mlp=True)
+    st = torch.cuda.Stream(device=dev)
+    torch.cuda.set_stream(st)
+    ego = np.zeros((B, N + 1, 10))
+    ego[:, :, 0:2] = rng.uniform(-0.4, 0.4, (B, 1, 2))
+    ego[:, :, 2] = 1.0
+    ego[:, :, 3:6] = rng.normal(0, 0.3, (B, N + 1, 3))
+    other = ego.copy()
+    other[:, :, 2] += rng.uniform(0.4, 0.9, (B, 1))
+    ego_t, other_t = torch.from_numpy(ego).to(dev), torch.from_numpy(other).to(dev)
+    xy_t = ego_t[:, 0, 0:2].contiguous()
+    out = {}
+    for K in (2, 3):
+        idx = np.stack([rng.permutation(B) for _ in range(K)], axis=1).astype(np.int32)
+        idx_t = torch.from_numpy(idx).to(dev)
+        gathered = [other_t[torch.from_numpy(idx[:, k].astype(np.int64)).to(dev)].contiguous() for k in range(K)]
+        f_multi = torch.empty(B, N + 1, 3, dtype=torch.float32, device=dev)
+        f_k = [torch.empty_like(f_multi) for _ in range(K)]
+        f_sum = torch.empty_like(f_multi)
+
+        def multi(i):
+            eng.downwash_multi_device(other_t, idx_t, ego_t, f_multi, ego_xy=xy_t, stream=st)
+
+        def single(i):
+            for k in range(K):
+                eng.downwash_device(gathered[k], ego_t, f_k[k], ego_xy=xy_t, stream=st)
+            torch.add(f_k[0], f_k[1], out=f_sum)
+            for k in range(2, K):
+                f_sum.add_(f_k[k])
+        tm, ts = [], []
+        for _ in range(3):                                # alternating: other people's work shares the machine
+            tm.append(_events(torch, multi, a.steps, a.warmup))
+            ts.append(_events(torch, single, a.steps, a.warmup))
+        assert torch.equal(f_multi, f_sum)
+        out[f"K{K}"] = {"one_launch_us": min(tm) * 1e6, "k_launches_plus_add_us": min(ts) * 1e6, "speedup": min(ts) / min(tm),
+                        "one_launch_us_runs": [t * 1e6 for t in tm], "k_launches_plus_add_us_runs": [t * 1e6 for t in ts]}
+    print(json.dumps({"row": "downwash prediction from K neighbours: one mlp_multi_kernel launch against K mlp_kernel launches + add",
+                      "metric": "us per call (device events, launches included)", "batch": B, "N": N, "results": out}))
+
+
+def bench_rollout_formation_multi(a, torch, ndp, dev):
+    """The formation rollout row with two neighbours per vehicle: B vehicles in stacked triples (scripts/formation_rollout.py --triples,
+    dz = 0.5 m), a.steps ticks in one ndp_rollout_formation_multi_device call per controller.  Compensating: 5 launches per tick
+    (reference window, plant force, prediction, control step, plant step); blind: 4."""
+    import numpy as np
+    from formation_rollout import set_trajectory, stacked_triples
+    B = a.batch - a.batch % 3
+    tr, idx = stacked_triples(B // 3, 0.5, n_seg=int(np.ceil(((a.warmup + a.steps) * 0.02 + 2.5) / 0.5)))
+    idx_t = torch.from_numpy(idx).to(dev)
+    res = {}
+    for name, dist in (("ndp_all_slots", True), ("nmpc_blind", False)):
+        eng = ndp.BatchedNMPC(B, disturbance=dist, load_mlp=True)
+        set_trajectory(eng, tr)
+        x = torch.from_numpy(eng.ref_window(np.zeros(B))[0][:, 0].copy()).to(dev)
+        worst = torch.zeros(B, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        eng.rollout_formation_multi_device(a.warmup, x, idx_t)
+        eng.synchronize()
+        t0 = time.perf_counter()
+        eng.rollout_formation_multi_device(a.steps, x, idx_t, worst_status=worst, t0=a.warmup * 0.02)
+        eng.synchronize()
+        el = time.perf_counter() - t0
+        xr_end, _ = eng.ref_window(np.full(B, (a.warmup + a.steps) * 0.02))
+        ez = np.abs(x.cpu().numpy()[:, 2] - xr_end[:, 0, 2])
+        res[name] = {"value": B * a.steps / el, "us_per_tick": el / a.steps * 1e6, "worst_status": int(worst.max()),
+                     "z_error_at_end_m": {"lowest_max": float(ez[0::3].max()), "top_max": float(ez[2::3].max())}}
+    print(json.dumps({"row": "closed-loop formation rollout, two neighbours per vehicle: reference window + summed plant force + "
+                             "[summed prediction +] control step (N=20, 1 RTI) + plant step per tick, stacked triples dz = 0.5 m",
                       "metric": "vehicle ticks/s", "batch": B, "ticks": a.steps, "controllers": res}))
 
 

@@ -1,0 +1,140 @@
+"""The formation experiment with SEVERAL neighbours per vehicle on the CPU, from the oracle's pieces (tests/formation_ref.py extended):
+ref_window -> the true force summed over the slots at the actual relative states -> step_batch (blind, or with the slots' predictions
+summed) -> plant_step.  tests/test_formation_multi.py holds it to the effect; tests/test_formation_multi_rollout_gpu.py holds the device
+rollout to it.
+
+The workload: `triples` triples stacked on one figure-eight each, dz apart (vehicle 3 t + m flies m * dz above vehicle 3 t), every vehicle
+hears the two others of its triple, slot 0 = the next one up, cyclically.  The lowest vehicle (3 t) flies under two others at once.
+Superposing the slots' forces is the modelling assumption of the device entry points (include/ndp_nmpc.h): the network was trained on pairs.
+
+Three modes: 'blind' (plain NMPC), 'slot0' (the controller predicts from slot 0 only: all a single-neighbour entry point can do), 'all'
+(the predictions of all slots summed).  The plant feels the sum over all slots in every mode."""
+import functools
+import os
+
+import numpy as np
+
+from ndp_nmpc_qd_amd import synth
+from ndp_nmpc_qd_amd.params import downwash_params as DP
+from ndp_nmpc_qd_amd.params import nmpc_params as CP
+from oracle import oracle as O
+from tests import formation_ref as F
+
+ROOT = F.ROOT
+TRIPLES, TICKS, SKIP, SEED = 2, F.TICKS, F.SKIP, 7
+MODES = ("blind", "slot0", "all")
+NET_BAR = 1e-5                           # the project's network bar: |device - oracle| <= NET_BAR * max(1, |f|) per network output
+PROBES = 3                               # sensitivity(): reruns of the loop with every network output perturbed inside that bar
+
+
+def workload(triples=TRIPLES, dz=0.5, seed=SEED):
+    """dict: the trajectory arrays (coeff_x .. final_pt), other_index int32[B, 2], B = 3 triples."""
+    B = 3 * triples
+    tr = synth.figure_eight_traj(B, seed=seed, n_seg=F.N_SEG, t_seg=F.T_SEG, omega_range=(0.5, 1.0))
+    for k in ("coeff_x", "coeff_y", "coeff_z", "coeff_yaw", "time_cum", "time_seg", "final_pt"):
+        for m in (1, 2):
+            tr[k][m::3] = tr[k][0::3]
+    for m in (1, 2):
+        tr["coeff_z"][m::3, 0::8] += m * dz
+        tr["final_pt"][m::3, 2] += m * dz
+    v = np.arange(B)
+    t, m = v // 3 * 3, v % 3
+    tr["other_index"] = np.stack([t + (m + 1) % 3, t + (m + 2) % 3], axis=1).astype(np.int32)
+    return tr
+
+
+def _noise(rng, f):
+    """f perturbed by uniform noise of +-NET_BAR * max(1, |f|) on its non-zero entries (a closed slot stays exactly 0); rng None: f."""
+    if rng is None:
+        return f
+    return np.where(f != 0, f + rng.uniform(-1.0, 1.0, f.shape) * NET_BAR * np.maximum(1.0, np.abs(f)), f).astype(f.dtype)
+
+
+def true_force_multi(blob, x, idx, gate=True, scale=1.0, rng=None):
+    """The force on the plant: the fp64 sum, in slot order, of formation_ref.true_force per slot (idx int32[B, K]; < 0: empty)."""
+    f = None
+    for k in range(idx.shape[1]):
+        fk = _noise(rng, F.true_force(blob, x, idx[:, k], gate, scale))
+        f = fk if f is None else f + fk
+    return f
+
+
+def oracle_prediction(blob, xr, idx1, ego_xy):
+    """One slot's prediction (idx1 int32[B]; < 0: empty): oracle.downwash_batch of the neighbour's reference window against the ego's,
+    behind the gate on (window node 0 xy, ego_xy); zeros for an empty slot.  float32 [B, N+1, 3]."""
+    has = idx1 >= 0
+    o = np.where(has, idx1, np.arange(len(idx1)))
+    fk = O.downwash_batch(blob, xr[o].copy(), xr, ego_xy, r_horiz=DP.r_horiz)
+    return np.where(has[:, None, None], fk, np.float32(0.0)).astype(np.float32)
+
+
+def prediction_multi(blob, xr, idx, ego_xy, rng=None):
+    """The controller's prediction: the fp32 sum, in slot order, of oracle_prediction per slot, each slot behind its own gate."""
+    f = None
+    for k in range(idx.shape[1]):
+        fk = _noise(rng, oracle_prediction(blob, xr, idx[:, k], ego_xy))
+        f = fk if f is None else (f + fk).astype(np.float32)
+    return f
+
+
+def pred_index(tr, mode):
+    """The slots the controller hears in `mode`: None (blind), slot 0, or all."""
+    return {"blind": None, "slot0": tr["other_index"][:, :1], "all": tr["other_index"]}[mode]
+
+
+def cpu_rollout(blob, tr, xr_all, ur_all, mode, ticks=TICKS, gate=True, scale=1.0, dt=CP.ts_nmpc, substeps=4, rng=None):
+    """-> (states [ticks, B, 10], u0 [ticks, B, 4], force [ticks, B, 3], status [ticks, B]) from x = xr[0][:, 0]."""
+    idx, pidx = tr["other_index"], pred_index(tr, mode)
+    cfg = O.default_cfg(use_fd=pidx is not None)
+    X, U = xr_all[0].copy(), ur_all[0].copy()
+    x = xr_all[0][:, 0].copy()
+    log, log_u, log_f, log_s = [], [], [], []
+    for k in range(ticks):
+        xr, ur = xr_all[k], ur_all[k]
+        f = true_force_multi(blob, x, idx, gate, scale, rng)
+        fp = None if pidx is None else prediction_multi(blob, xr, pidx, x[:, 0:2].copy() if gate else None, rng)
+        u0, st, _ = O.step_batch(cfg, x, xr, ur, fp, X, U)
+        x = O.plant_step(cfg, x.copy(), u0, f, dt, substeps)
+        log.append(x.copy()); log_u.append(u0); log_f.append(f); log_s.append(st)
+    return np.stack(log), np.stack(log_u), np.stack(log_f), np.stack(log_s)
+
+
+def max_slot_distance(states, idx):
+    """The largest horizontal distance between a vehicle and any of its slots' neighbours over a rollout's states."""
+    d = states[:, idx, 0:2] - states[:, :, None, 0:2]
+    return float(np.sqrt((d * d).sum(-1)).max())
+
+
+def _blob():
+    return np.fromfile(os.path.join(ROOT, "ndp_nmpc_qd_amd", "weights", "downwash_sn4.bin"), dtype="<f4")
+
+
+@functools.lru_cache(maxsize=None)
+def reference(dz):
+    """The acceptance workload at one dz, computed once per session: dict tr, xr, ur, and per mode the rollout.  (The oracle library must
+    have been built: the tests' `oracle` fixture does.)"""
+    blob = _blob()
+    tr = workload(TRIPLES, dz)
+    xr, ur = F.windows(tr, TICKS)
+    out = dict(tr=tr, xr=xr, ur=ur)
+    for mode in MODES:
+        out[mode] = cpu_rollout(blob, tr, xr, ur, mode)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def sensitivity(dz):
+    """The loop's own sensitivity to network error inside the project's bar: per mode, the worst position difference (m) between
+    reference(dz) and PROBES reruns with every per-slot network output -- plant force and prediction -- perturbed by uniform noise of
+    +-NET_BAR * max(1, |f|).  What a device whose network meets the bar may differ by; the device tests' position bar is a multiple of it."""
+    r = reference(dz)
+    blob = _blob()
+    out = {}
+    for mode in MODES:
+        worst = 0.0
+        for p in range(PROBES):
+            rng = np.random.default_rng([1000 + p, int(round(dz * 100)), MODES.index(mode)])
+            states = cpu_rollout(blob, r["tr"], r["xr"], r["ur"], mode, rng=rng)[0]
+            worst = max(worst, float(np.abs(states[:, :, 0:3] - r[mode][0][:, :, 0:3]).max()))
+        out[mode] = worst
+    return out
