@@ -621,8 +621,8 @@ int ndp_rollout_formation_device(ndp_handle *h, int ticks, double t0, double dt_
  * 22-28 sees one relative state).  The gate (ndp_nmpc_leader_node.py:65-68) is per slot, the same strict expression; a slot with index < 0 is
  * empty; the same index in two slots counts twice.  Slots are summed in slot order, the first open slot's value taken as it is, closed
  * slots adding nothing -- so K = 1 reproduces the single-neighbour call bit for bit, and any K equals the sum, in slot order, of K
- * single-neighbour results.  K outside 1..NDP_MAX_NEIGH: -2, nothing enqueued.  The derivative paths, the fused step and the tick stay
- * single-neighbour (the derivative of a sum is K calls with the same upstream).
+ * single-neighbour results.  K outside 1..NDP_MAX_NEIGH: -2, nothing enqueued.  The fused step, the prefetch form and the tick stay
+ * single-neighbour; the derivatives of the summed prediction are ndp_downwash_multi_vjp_device / ndp_downwash_multi_jvp_device below.
  * ndp_downwash_multi*: the controller's prediction, f_out[B][N+1][3] fp32 = sum over k (fp32) of ndp_downwash_device's value for neighbour
  *   other_index[i][k]: the network at (other - ego_ref)[0:6], slot k open iff index >= 0 and (ego_xy NULL or |other[o_k] node 0 xy -
  *   ego_xy[i]|^2 < r_horiz^2).  Device form: d_other [rows][N+1][other_stride] and other_stride (10 or 6, else -13) as ndp_step_device_ex;
@@ -648,6 +648,40 @@ int ndp_plant_force_multi(ndp_handle *h, const double *x, const int32_t *other_i
 int ndp_rollout_formation_multi_device(ndp_handle *h, int ticks, double t0, double dt_tick, int substeps, const void *d_other_index, int K,
                                        int flags, double plant_scale, void *d_x, void *d_log, void *d_log_u, void *d_log_f,
                                        void *d_worst_status, void *stream);
+/* Reverse mode of ndp_downwash_multi_device as that call evaluates the force: ndp_downwash_vjp_device with d_other_index int32[B][K]
+ * (required).  The per-slot rules are the forward's: each slot behind its own gate (the same strict expression), index < 0 = empty, the same
+ * index in two slots counts twice, other_stride 6 or 10, d_ego_xy NULL = open.  d_gf [B][N+1][3] fp64 is the gradient of the SUMMED force and
+ * is shared by the K slots of a row.  Every slot's forward is recomputed with the step's own arithmetic (its ReLU masks are the forward's).
+ * One launch over the B K (N+1) virtual rows (instance, slot, node): a 32-row tile with no open row -- a closed or empty slot's -- costs its
+ * gate only.  Outputs, each NULL = not computed, not both NULL:
+ *   d_gz [B][K][N+1][6] fp64 : per slot; d_gz[i][k] is bit-equal to what ndp_downwash_vjp_device writes for other_index[:, k] -- 0 on closed
+ *                               and empty slots, NaN on the open slots of a row whose d_gf is not finite
+ *   d_gw [NDP_MLP_NPARAM] fp32, OVERWRITTEN: the sum over all (row, slot), accumulated in registers across the launch, one partial-sum pass
+ *                               and one fixed-order reduction, no atomics: two calls are bit-identical.  A row whose d_gf is not finite adds
+ *                               nothing: the result is bit-equal to the call with that row's d_gf zeroed.  NOT promised bit-equal to the sum
+ *                               of K ndp_downwash_vjp_device results (the order of summation differs).
+ * At K = 1 both outputs are bit-equal to ndp_downwash_vjp_device's.  Nothing of the engine's state is written.  The partial sums use the
+ * SAME workspace as ndp_downwash_vjp_device (allocated by ndp_create, so the call may be captured into a graph; its size caps the
+ * workgroups, the rest is a grid-stride loop): calls of either kind on one handle must be ordered against each other -- the same stream, or
+ * streams ordered by events.  -1: NULL handle (or d_other / d_ego_ref missing); -6: weights never set; -2 with a reason in ndp_last_error,
+ * nothing launched: K outside 1..NDP_MAX_NEIGH, d_other_index NULL, other_stride not 6 or 10, d_gf NULL, no output asked for. */
+int ndp_downwash_multi_vjp_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index, int K,
+                                  const void *d_ego_ref, const void *d_ego_xy, const void *d_gf, void *d_gz, void *d_gw, void *stream);
+/* Forward mode of ndp_downwash_multi_device: ndp_downwash_jvp_device with d_other_index int32[B][K] (required), the mirror of the call
+ * above.  Directions, T = n_tan, not both NULL:
+ *   d_tz [B][T][K][N+1][6] fp64 : per slot, the direction of (other[o_k] - ego_ref)[..., 0:6], NULL = 0
+ *   d_tw [T][NDP_MLP_NPARAM] fp32 : the direction of the weights (shared by the slots), NULL = 0
+ * Outputs:
+ *   d_df [B][T][N+1][3] fp64, required: the fp64 sum IN SLOT ORDER of the slots' (double) tangents, the first open slot's value taken as it
+ *                             is, closed slots adding nothing: bit-equal to that sum of K ndp_downwash_jvp_device results (d_tz[:, :, k],
+ *                             the same d_tw); exactly 0 where no slot is open.  The lane that owns a row accumulates it in d_df itself.
+ *   d_f_check [B][N+1][3] fp32, optional: the recomputed summed force, bit-equal to ndp_downwash_multi_device's output.
+ * T directions in one call give what T calls give, bit for bit; K = 1 is bit-equal to ndp_downwash_jvp_device.  No atomics, no workspace,
+ * nothing of the engine's state written: calls need no ordering against each other.  Refusals as above, and -2 for n_tan outside
+ * 1..NDP_JVP_MAX_TANGENTS, no tangent given, d_df NULL. */
+int ndp_downwash_multi_jvp_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index, int K,
+                                  const void *d_ego_ref, const void *d_ego_xy, int n_tan, const void *d_tz, const void *d_tw, void *d_df,
+                                  void *d_f_check, void *stream);
 
 /* ---- Peer windows: the neighbour exchange across GPUs as publish / subscribe over xGMI.
  * Replaces the PredXU topic between processes: the publisher is nmpc_node.py:116-133,229-230 (`nmpc_x_ref`, 21x10 float64, a NEW

@@ -63,6 +63,7 @@ EXPORTS = [
     "ndp_plant_force", "ndp_plant_force_device", "ndp_rollout_formation_device",
     "ndp_downwash_multi", "ndp_downwash_multi_device", "ndp_plant_force_multi", "ndp_plant_force_multi_device",
     "ndp_rollout_formation_multi_device",
+    "ndp_downwash_multi_vjp_device", "ndp_downwash_multi_jvp_device",
 ]
 
 _lib = None
@@ -216,6 +217,8 @@ def load():
     lib.ndp_plant_force_multi.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, vp]
     lib.ndp_plant_force_multi_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp]
     lib.ndp_rollout_formation_multi_device.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, vp, C.c_int, C.c_int, C.c_double] + [vp] * 6
+    lib.ndp_downwash_multi_vjp_device.argtypes = [vp, vp, C.c_int, vp, C.c_int] + [vp] * 6
+    lib.ndp_downwash_multi_jvp_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int] + [vp] * 5
     lib.ndp_plant_step.argtypes = [vp, vp, vp, vp, C.c_double, C.c_int]
     lib.ndp_plant_step_device.argtypes = [vp, vp, vp, vp, C.c_double, C.c_int, vp]
     _lib = lib

@@ -779,6 +779,64 @@ class BatchedNMPC:
             d(ego_xy, torch.float64, (B, 2)), T, dt(tz, tails[0], 1), dt(tw, tails[1], 0), dt(df, tails[2], 1),
             d(f_check, torch.float32, (B, N + 1, 3)), self._stream(stream)), "ndp_downwash_jvp_device")
 
+    # ---- the same two with K neighbours per instance (the derivatives of downwash_multi_device)
+    def downwash_multi_vjp_device(self, other, other_index, ego_ref, gf, ego_xy=None, gz=None, gw=None, stream=None):
+        """Enqueues the backward pass of downwash_multi_device on `stream` (ndp_downwash_multi_vjp_device; include/ndp_nmpc.h): other
+        [rows,N+1,6 or 10] / other_index int32[B,K] / ego_ref / ego_xy as the forward took them, gf [B,N+1,3] float64 the gradient of the
+        SUMMED force (shared by the slots).  Outputs (None = not computed, not both None): gz [B,K,N+1,6] float64 per slot, bit-equal to
+        what downwash_vjp_device gives for other_index[:, k] (0 on closed and empty slots); gw [17859] float32, overwritten, the sum over
+        all rows and slots in one fixed order.  A row whose gf is not finite adds nothing to gw and has NaN in the gz rows of its open
+        slots.  Shares downwash_vjp_device's workspace: order the two against each other.  The engine's state is not written.  stream None
+        or torch's default stream: as downwash_vjp_device."""
+        import torch
+        B, N = self.B, self.N
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        optr, stride = self._other_ptr(other, other_index)
+        iptr, K = self._dindex_multi(other_index)
+        d = self._dptr
+        self._check(self._lib.ndp_downwash_multi_vjp_device(
+            self._h, optr, stride, iptr, K, d(ego_ref, torch.float64, (B, N + 1, 10)), d(ego_xy, torch.float64, (B, 2)),
+            d(gf, torch.float64, (B, N + 1, 3)), d(gz, torch.float64, (B, K, N + 1, 6)), d(gw, torch.float32, (_lib.MLP_NPARAM,)),
+            self._stream(stream)), "ndp_downwash_multi_vjp_device")
+
+    def downwash_multi_jvp_device(self, other, other_index, ego_ref, tz=None, tw=None, ego_xy=None, n_tan=None, df=None, f_check=None,
+                                  stream=None):
+        """Enqueues the forward mode of downwash_multi_device on `stream` (ndp_downwash_multi_jvp_device; include/ndp_nmpc.h).  Directions
+        (None = 0, not both None): tz [B,T,K,N+1,6] float64 per slot, tw [T,17859] float32.  Outputs: df [B,T,N+1,3] float64, required --
+        the float64 sum in slot order of what downwash_jvp_device gives per slot, exactly 0 where no slot is open; f_check [B,N+1,3]
+        float32, optional -- the summed force, bit-equal to downwash_multi_device's.  T (1..8) is n_tan when given, else read from the
+        tensors; tensors without the T axis mean T = 1.  No workspace; the engine's state is not written.  stream None or torch's default
+        stream: as downwash_jvp_device."""
+        import torch
+        B, N = self.B, self.N
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        optr, stride = self._other_ptr(other, other_index)
+        iptr, K = self._dindex_multi(other_index)
+        tails = ((K, N + 1, 6), (_lib.MLP_NPARAM,), (N + 1, 3))
+        lead = (1, 0, 1)                                                # dimensions in front of the T axis
+        if n_tan is None:
+            Ts = {int(t.shape[ld]) if t.dim() == ld + 1 + len(s) else 1 for t, s, ld in zip((tz, tw, df), tails, lead) if t is not None}
+            if len(Ts) > 1:
+                raise ValueError(f"downwash_multi_jvp_device: tangents and output disagree on the number of directions ({sorted(Ts)})")
+            n_tan = Ts.pop() if Ts else 1
+        T = int(n_tan)
+        d = self._dptr
+
+        def dt(t, s, ld):                                               # (without the T axis: the tensor is T = 1 as it lies)
+            if t is None:
+                return None
+            head = (B,) if ld else ()
+            full = head + (T,) + s
+            if t.dim() != len(full) and T != 1:
+                raise ValueError(f"downwash_multi_jvp_device: a tensor without the T axis with n_tan = {T}")
+            return d(t, torch.float32 if s is tails[1] else torch.float64, full if t.dim() == len(full) else head + s)
+        self._check(self._lib.ndp_downwash_multi_jvp_device(
+            self._h, optr, stride, iptr, K, d(ego_ref, torch.float64, (B, N + 1, 10)), d(ego_xy, torch.float64, (B, 2)), T,
+            dt(tz, tails[0], 1), dt(tw, tails[1], 0), dt(df, tails[2], 1), d(f_check, torch.float32, (B, N + 1, 3)),
+            self._stream(stream)), "ndp_downwash_multi_jvp_device")
+
     def set_mlp_weights_device(self, blob, stream=None):
         """set_mlp_weights from a float32 CUDA tensor of 17859 values in blob order, enqueued on `stream` with no host synchronisation
         (ndp_set_mlp_weights_device): steps enqueued behind it on that stream use the new weights."""

@@ -10,8 +10,9 @@
 //                    plant_force_kernel (f4: the downwash force on the plant), mlp_multi_kernel / plant_force_multi_kernel (K neighbours)
 //   rows.hip         the rows f1 - f4: reference window and list, follower relay, throttle estimator, actuator command, plant, rollouts
 //   tick.hip         the control tick's host side (ndp_tick*); no kernel: compiled for the host only
-//   mlp_vjp.hip      the downwash network's backward pass (ndp_downwash_vjp_device) and its weights set from device memory
-//   mlp_jvp.hip      the downwash network's forward mode (ndp_downwash_jvp_device)
+//   mlp_vjp.hip      the downwash network's backward pass (ndp_downwash_vjp_device, ndp_downwash_multi_vjp_device) and its weights set from
+//                    device memory
+//   mlp_jvp.hip      the downwash network's forward mode (ndp_downwash_jvp_device, ndp_downwash_multi_jvp_device)
 //   exchange.hip     peer-mapped windows (ndp_peer_*), the RCCL exchange (ndp_xchg_*) and the remote tick one control period ahead
 // A kernel sits with the host code that launches it; device code that two units' kernels inline is a header (mlp_tile.hpp, ref_point.hpp,
 // tick_wave.hpp), and so are the argument blocks the host fills (kern_args.hpp).
@@ -68,6 +69,7 @@ struct ndp_handle {
     signed char *dVjpAct = nullptr;
     // mlp_vjp.hip: layers 2 and 3 transposed, one fp32 record per matrix instruction of the backward pass (FRT_TOTAL floats, written with
     // dFrag by both ndp_set_mlp_weights forms); ndp_downwash_vjp_device's per-workgroup partial weight gradients [mlp_vjp_groups][NDP_MLP_NPARAM]
+    // (ndp_downwash_multi_vjp_device shares them: it never launches more workgroups than that)
     float *dFragT = nullptr, *dGwPart = nullptr;
     double *dThr = nullptr;    // hover-throttle estimator state, SoA [8][B]
     double *dStamps = nullptr; // [B][NDP_NSTAMP] whole-batch phase stamps (ndp_debug_stamps)

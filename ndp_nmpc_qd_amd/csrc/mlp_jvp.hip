@@ -16,6 +16,8 @@
 //                                  of one weight row); none of it runs when no weight direction is given
 //                    A tangent is linear: nothing on its path is capped, clamped or converted to fp16, so there is no range limit on
 //                    it beyond fp32's own.  Rows go from registers straight to global memory; no atomics, no workspace of the handle.
+//   mlp_jvp_multi_kernel : the same with K neighbour slots per instance, a rolled loop over the slots around the per-tile work, the T
+//                    directions inside it (mlp_jvp_direction.inc is the text both kernels run per direction); df summed in slot order.
 #include <hip/hip_runtime.h>
 
 #include "../../include/ndp_nmpc.h"
@@ -250,79 +252,96 @@ __global__ __launch_bounds__(256) void mlp_jvp_kernel(MlpJvpArgs A)
 #pragma unroll
             for (int s = 0; s < 3; ++s) tzb[s] = (float)A.tz[(trow + (size_t)t * A.np1) * 6 + 2 * s + h];
         }
-        // ---- layer 1: da1 = m1 (W1 dz + dW1 z + db1)
-        f16_t d1[4];
-#pragma unroll
-        for (int ot = 0; ot < 4; ++ot) {
-            f16_t acc = jvp_dbias(tw ? tw + PB1 + ot * 32 : nullptr, h);
-            JVP_FENCE();
-#pragma unroll
-            for (int s = 0; s < 3; ++s)
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fr[frag::L1 + (ot * 3 + s) * 64 + lane], tzb[s], acc, 0, 0, 0);
-            if (tw) {
-#pragma unroll
-                for (int s = 0; s < 3; ++s)
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(tw[PW1 + (ot * 32 + j) * 6 + 2 * s + h], zb[s], acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) d1[ot][r] = jvp_mask_cap(a1[ot][r], acc[r]);
-        }
-        // ---- layer 2: da2 = m2 (W2 da1 + dW2 a1 + db2)
-        f16_t d2[2];
-#pragma unroll
-        for (int ot = 0; ot < 2; ++ot) {
-            f16_t acc = jvp_dbias(tw ? tw + PB2 + ot * 32 : nullptr, h);
-            jvp_dense(fr, ot * 8, 4, d1, lane, acc);
-            if (tw) jvp_dweight(tw + PW2 + (ot * 32 + j) * 128 + 4 * h, 4, a1, acc);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) d2[ot][r] = jvp_mask_cap(a2[ot][r], acc[r]);
-        }
-        // ---- layer 3: da3 = m3 (W3 da2 + dW3 a2 + db3), plain ReLU
-        f16_t d3[4];
-#pragma unroll
-        for (int ot = 0; ot < 4; ++ot) {
-            f16_t acc = jvp_dbias(tw ? tw + PB3 + ot * 32 : nullptr, h);
-            jvp_dense(fr, 16 + ot * 4, 2, d2, lane, acc);
-            if (tw) jvp_dweight(tw + PW3 + (ot * 32 + j) * 64 + 4 * h, 2, a2, acc);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) d3[ot][r] = a3[ot][r] > 0.0f ? acc[r] : 0.0f;
-        }
-        // ---- layer 4 on the VALU: df = W4 da3 + dW4 a3 + db4; each half-wave owns 64 of the 128 features of its row
-        float g[3] = {0.0f, 0.0f, 0.0f};
-        const f4_t *w4 = reinterpret_cast<const f4_t *>(fr + frag::W4);
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            JVP_FENCE();
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const f4_t q = w4[it * 32 + f0(r) + 4 * h];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) g[c] = fmaf(q[c], d3[it][r], g[c]);
-            }
-        }
-        if (tw) {
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                JVP_FENCE();
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const f4_t v = ld4(tw + PW4 + c * 128 + it * 32 + 8 * q + 4 * h);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) g[c] = fmaf(v[i], a3[it][4 * q + i], g[c]);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            g[c] += __shfl_xor(g[c], 32, 64);
-            if (tw) g[c] += tw[PB4 + c];
-        }
+#include "mlp_jvp_direction.inc"
         if (valid && h == 0) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) A.df[(trow + (size_t)t * A.np1) * 3 + c] = open ? (double)g[c] : 0.0;
+        }
+    }
+}
+
+// K neighbour slots per instance (ndp_downwash_multi_jvp_device): other_index int32[B][K] (required), tz [B][T][K][np1][6].  The rows are
+// the real rows (instance, node), mlp_jvp_kernel's mapping; the slots run as a ROLLED loop around its per-tile work, as mlp_multi_kernel's
+// do around mlp_tile (downwash.hip), the T directions inside the slot loop.  Every weight load is invariant in both loops: the weights'
+// base is made opaque at the head of every round of either.  A slot none of whose 32 rows is open is skipped as a whole.
+//   f_check : the fp32 sum in slot order, the first open slot's value taken as it is -- mlp_multi_kernel's sum, bit for bit
+//   df      : the fp64 sum in slot order of the slots' (double) values, kept in the output itself: the lane that owns the row stores the
+//             first open slot's value and adds the later ones to what it stored (its own stores, its own loads: no other lane touches
+//             the row); a row with no open slot gets its zeros behind the loop.  No atomics, no workspace.
+__global__ __launch_bounds__(256) void mlp_jvp_multi_kernel(MlpJvpArgs A, int K)
+{
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 31, h = lane >> 5;
+    const int ntiles = (A.rows + 31) / 32;
+    const int tile = (int)blockIdx.x * 4 + wave;
+    if (tile >= ntiles) return;
+    const int T = A.ntan;
+    const int row = tile * 32 + j;
+    const bool valid = row < A.rows;
+    const int rowc = valid ? row : A.rows - 1;
+    const int inst = rowc / A.np1, k = rowc - inst * A.np1;
+    const size_t trow = ((size_t)inst * T) * A.np1 + k;        // this row of df in direction 0; direction t: + t * np1
+    double e[3];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) e[s] = A.ego[(size_t)inst * A.ego_pitch + (size_t)k * NX + 2 * s + h];
+    float f[3] = {0.0f, 0.0f, 0.0f};
+    bool any = false;
+#pragma unroll 1
+    for (int slot = 0; slot < K; ++slot) {
+        const float *frq = A.fr;
+        asm volatile("" : "+s"(frq));
+        const int orow = A.other_index[(size_t)inst * K + slot];
+        const double *oth = A.other + (size_t)(orow < 0 ? 0 : orow) * A.other_pitch;
+        bool open = valid && orow >= 0;
+        if (A.ego_xy) {
+            const double oxy[2] = {ld_other(oth, A.other_sys), ld_other(oth + 1, A.other_sys)};
+            open = open && gate_open(oxy, A.ego_xy + (size_t)inst * A.ego_xy_pitch, A.r2);
+        }
+        if (__ballot(open) == 0ull) continue;
+        float zb[3], o[3];
+        f16_t a1[4], a2[2], a3[4];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) zb[s] = (float)(ld_other(oth + (size_t)k * A.other_stride + 2 * s + h, A.other_sys) - e[s]);
+        jvp_forward(frq, zb, lane, a1, a2, a3, o);
+        if (open) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) f[c] = any ? f[c] + o[c] : o[c];
+        }
+#pragma unroll 1
+        for (int t = 0; t < T; ++t) {
+            // (as mlp_jvp_kernel's T loop: weights and activations made opaque per round)
+            const float *fr = A.fr;
+            asm volatile("" : "+s"(fr));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(a1[i]), "+v"(a3[i]));
+            asm volatile("" : "+v"(a2[0]), "+v"(a2[1]));
+            const float *tw = A.tw ? A.tw + (size_t)t * PTOTAL : nullptr;
+            float tzb[3] = {0.0f, 0.0f, 0.0f};
+            if (A.tz) {
+#pragma unroll
+                for (int s = 0; s < 3; ++s)
+                    tzb[s] = (float)A.tz[((((size_t)inst * T + t) * K + slot) * A.np1 + k) * 6 + 2 * s + h];
+            }
+#include "mlp_jvp_direction.inc"
+            if (open && h == 0) {
+                double *d = A.df + (trow + (size_t)t * A.np1) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) d[c] = any ? d[c] + (double)g[c] : (double)g[c];
+            }
+        }
+        any = any || open;
+    }
+    if (valid && h == 0) {
+        if (!any) {
+#pragma unroll 1
+            for (int t = 0; t < T; ++t) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) A.df[(trow + (size_t)t * A.np1) * 3 + c] = 0.0;
+            }
+        }
+        if (A.fchk) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) A.fchk[(size_t)row * 3 + c] = f[c];
         }
     }
 }
@@ -351,6 +370,31 @@ int ndp_downwash_jvp_device(ndp_handle *h, const void *d_other, int other_stride
                  (const float *)d_tw, (double *)d_df, (float *)d_f_check, rows, np1, n_tan, h->cfg.r_horiz * h->cfg.r_horiz, other_stride,
                  (const int *)d_other_index, peer_mapped(d_other), (size_t)np1 * other_stride, (size_t)np1 * NX, (size_t)2};
     hipLaunchKernelGGL(mlp_jvp_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, g.s, a);
+    NDP_HIP(h, hipGetLastError());
+    return g.noted(0);
+}
+
+int ndp_downwash_multi_jvp_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index, int K,
+                                  const void *d_ego_ref, const void *d_ego_xy, int n_tan, const void *d_tz, const void *d_tw, void *d_df,
+                                  void *d_f_check, void *stream)
+{
+    Entry g(h, d_other && d_ego_ref, stream);
+    if (g.rc) return g.rc;
+    const char *why = nullptr;
+    if (!h->have_mlp) { h->err = "ndp_downwash_multi_jvp_device: ndp_set_mlp_weights was never called"; return -6; }
+    if (K < 1 || K > NDP_MAX_NEIGH) why = "ndp_downwash_multi_jvp_device: K must be 1..8 (NDP_MAX_NEIGH neighbours per vehicle)";
+    else if (!d_other_index) why = "ndp_downwash_multi_jvp_device: d_other_index is required (int32 [B][K])";
+    else if (other_stride != 6 && other_stride != NX) why = "ndp_downwash_multi_jvp_device: other_stride must be 6 or 10";
+    else if (n_tan < 1 || n_tan > NDP_JVP_MAX_TANGENTS) why = "ndp_downwash_multi_jvp_device: n_tan must be 1..8 (directions per call)";
+    else if (!d_tz && !d_tw) why = "ndp_downwash_multi_jvp_device: no tangent given (d_tz and d_tw both NULL)";
+    else if (!d_df) why = "ndp_downwash_multi_jvp_device: d_df is required (the tangent of the summed force)";
+    if (why) { h->err = why; return -2; }
+    const int np1 = h->cfg.N + 1, rows = h->cfg.batch * np1;
+    const int ntiles = (rows + 31) / 32;
+    MlpJvpArgs a{h->dFrag, (const double *)d_other, (const double *)d_ego_ref, (const double *)d_ego_xy, (const double *)d_tz,
+                 (const float *)d_tw, (double *)d_df, (float *)d_f_check, rows, np1, n_tan, h->cfg.r_horiz * h->cfg.r_horiz, other_stride,
+                 (const int *)d_other_index, peer_mapped(d_other), (size_t)np1 * other_stride, (size_t)np1 * NX, (size_t)2};
+    hipLaunchKernelGGL(mlp_jvp_multi_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, g.s, a, K);
     NDP_HIP(h, hipGetLastError());
     return g.noted(0);
 }

@@ -11,6 +11,7 @@
 //                                          grid-stride loop; biases by a column sum out of the same LDS image.
 //                           All products are exact fp32 (the accuracy bar of the gradient decides, not speed).  Per-workgroup partial
 //                           gradients go to a workspace of the handle, no atomics.
+//   mlp_vjp_multi_kernel  : the same body (mlp_vjp_body.inc) over virtual rows, K neighbour slots per instance, one upstream row per instance.
 //   mlp_vjp_reduce_kernel : sums the partials in a fixed order into the caller's buffer (two calls are bit-identical).
 //   mlp_frag_kernel       : builds dFrag and dFragT from a blob in device memory (ndp_set_mlp_weights_device), bit for bit what
 //                           make_fragments / make_fragments_t build on the host.
@@ -229,218 +230,33 @@ __device__ __forceinline__ float bias_rows(lds_cf32 buf, const int open[4], int 
     return s;
 }
 
+// The body of both backward kernels is mlp_vjp_body.inc, included as text: a template or an inlined function around it changed the
+// registers the compiler gives mlp_vjp_kernel, and that kernel's code object is held fixed.  The body names the instance whose ego window,
+// ego xy and upstream row it reads through two macros.
+#define VJP_EGO inst
+#define VJP_FROW (size_t)row
 __global__ __launch_bounds__(256) void mlp_vjp_kernel(MlpVjpArgs A)
 {
-    extern __shared__ __attribute__((aligned(16))) float vsm[];
-    lds_f32 buf = (lds_f32)vsm;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = lane & 31, h = lane >> 5;
-    const int ntiles = (A.rows + 31) / 32, ngroups = (ntiles + 3) / 4;
-    const bool want_w = A.part != nullptr;
-    lds_f32 mine = buf + wave * VJ_WAVE;
-
-    // this wave's share of the weight gradient: dW4 tile (0, wave) | dW3 tiles (wave, 0..1) | dW2 tiles (wave >> 1, 2 (wave & 1) + 0..1) |
-    // dW1 tile (wave, 0) with b1 in its column 6; the bias sums of layers 2..4 per thread (bias_rows)
-    f16_t g4, g3[2], g2[2], g1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) g4[r] = g3[0][r] = g3[1][r] = g2[0][r] = g2[1][r] = g1[r] = 0.0f;
-    float gb4 = 0.0f, gb3 = 0.0f, gb2 = 0.0f;
-
-#pragma unroll 1
-    for (int grp = (int)blockIdx.x; grp < ngroups; grp += (int)gridDim.x) {
-        // (the weight records are the same in every round: keep the compiler from hoisting 17k loads out of the loop into registers)
-        const float *fr = A.fr, *frt = A.frt;
-        asm volatile("" : "+s"(fr), "+s"(frt));
-        const int tile = grp * 4 + wave;
-        const int row = tile * 32 + j;
-        const bool valid = row < A.rows;
-        const int rowc = valid ? row : A.rows - 1;
-        const int inst = rowc / A.np1, k = rowc - inst * A.np1;
-        const int orow = A.other_index ? A.other_index[inst] : inst;
-        const double *oth = A.other + (size_t)(orow < 0 ? 0 : orow) * A.other_pitch;
-        bool open = valid && orow >= 0;
-        if (A.ego_xy) {
-            const double oxy[2] = {ld_other(oth, A.other_sys), ld_other(oth + 1, A.other_sys)};
-            open = open && gate_open(oxy, A.ego_xy + (size_t)inst * A.ego_xy_pitch, A.r2);
-        }
-        const int tile_open = __builtin_amdgcn_readfirstlane((int)(__ballot(open) != 0ull));
-        float d4[3] = {0.0f, 0.0f, 0.0f};
-        bool finite = true;
-        f16_t a2[2], a3[4], dl[4];
-        float zb[3];
-        if (tile_open) {
-            if (open) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    d4[c] = (float)A.gf[(size_t)row * 3 + c];
-                    finite = finite && __builtin_isfinite(d4[c]);
-                }
-                // a row whose upstream gradient is not finite (a failed step's) adds nothing to the weights and gets NaN itself
-                if (!finite) d4[0] = d4[1] = d4[2] = 0.0f;
-            }
-#pragma unroll
-            for (int s = 0; s < 3; ++s)
-                zb[s] = (float)(ld_other(oth + (size_t)k * A.other_stride + 2 * s + h, A.other_sys) -
-                                A.ego[(size_t)inst * A.ego_pitch + (size_t)k * NX + 2 * s + h]);
-            vjp_forward(fr, zb, lane, a2, a3);
-        }
-
-        // ---- layer 4: dW4 = d4 (x) a3, db4
-        __syncthreads();                                   // (the previous round's reads of the image are over)
-        if (lane == 0) ((__attribute__((address_space(3))) int *)(buf + VJ_FLAGS))[wave] = tile_open;
-        if (tile_open && want_w) {
-            if (h == 0) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) mine[c * VJ_PITCH + j] = d4[c];
-            }
-#pragma unroll
-            for (int t = 0; t < 4; ++t) park(mine, a3[t], 1 + t, lane);
-        }
-        __syncthreads();
-        int opn[4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) opn[w] = __builtin_amdgcn_readfirstlane(((const __attribute__((address_space(3))) int *)(buf + VJ_FLAGS))[w]);
-        if (want_w) {
-            contract(buf, opn, 0, wave, 32, 3, 32, -1, lane, g4);
-            gb4 += bias_rows(buf, opn, 3, tid);
-        }
-        // d3 = (W4' d4) m3
-        if (tile_open) {
-            typedef float f4_t __attribute__((ext_vector_type(4)));
-            const f4_t *w4 = reinterpret_cast<const f4_t *>(fr + frag::W4);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                VJP_FENCE();
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const f4_t q = w4[t * 32 + f0(r) + 4 * h];
-                    const float v = fmaf(q[2], d4[2], fmaf(q[1], d4[1], q[0] * d4[0]));
-                    dl[t][r] = a3[t][r] > 0.0f ? v : 0.0f;
-                }
-            }
-        }
-        // ---- layer 3: dW3 = d3 (x) a2, db3
-        __syncthreads();
-        if (tile_open && want_w) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) park(mine, dl[t], t, lane);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) park(mine, a2[t], 4 + t, lane);
-        }
-        __syncthreads();
-        if (want_w) {
-            contract(buf, opn, wave, 0, 128, 32, 32, -1, lane, g3[0]);
-            contract(buf, opn, wave, 1, 128, 32, 32, -1, lane, g3[1]);
-            gb3 += bias_rows(buf, opn, 128, tid);
-        }
-        // d2 = (W3' d3) m2
-        f16_t d2[2];
-        if (tile_open) {
-#pragma unroll
-            for (int it = 0; it < 2; ++it) {
-                f16_t acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-#pragma unroll
-                for (int st = 0; st < 4; ++st) {
-                    VJP_FENCE();
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(frt[FRT_L3 + ((it * 4 + st) * 16 + r) * 64 + lane], dl[st][r], acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) d2[it][r] = mask_cap(a2[it][r], acc[r]);
-            }
-        }
-        // ---- layer 2: dW2 = d2 (x) a1, db2
-        __syncthreads();
-        if (tile_open) {                                   // (a1 also serves d1's mask below: parked whether or not dW is asked for)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) park(mine, d2[t], t, lane);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) park(mine, vjp_layer1(fr, zb, lane, t), 2 + t, lane);
-        }
-        __syncthreads();
-        if (want_w) {
-            contract(buf, opn, wave >> 1, 2 * (wave & 1), 64, 32, 32, -1, lane, g2[0]);
-            contract(buf, opn, wave >> 1, 2 * (wave & 1) + 1, 64, 32, 32, -1, lane, g2[1]);
-            gb2 += bias_rows(buf, opn, 64, tid);
-        }
-        // d1 = (W2' d2) m1
-        if (tile_open) {
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                f16_t acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-#pragma unroll
-                for (int st = 0; st < 2; ++st) {
-                    VJP_FENCE();
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(frt[FRT_L2 + ((it * 2 + st) * 16 + r) * 64 + lane], d2[st][r], acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) dl[it][r] = mask_cap(mine[((2 + it) * 32 + f0(r) + 4 * h) * VJ_PITCH + j], acc[r]);   // a1, this wave's own
-            }
-        }
-        // ---- layer 1: dW1 = d1 (x) z, db1 (the column of ones behind z's six features)
-        __syncthreads();
-        if (tile_open && want_w) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) park(mine, dl[t], t, lane);
-#pragma unroll
-            for (int s = 0; s < 3; ++s) mine[(128 + 2 * s + h) * VJ_PITCH + j] = zb[s];
-        }
-        __syncthreads();
-        if (want_w) contract(buf, opn, wave, 0, 128, 32, 6, 6, lane, g1);
-        // g_z = W1' d1
-        if (A.gz) {
-            float gz[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-            if (tile_open) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    VJP_FENCE();
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-#pragma unroll
-                        for (int i = 0; i < 6; ++i)
-                            gz[i] = fmaf(fr[frag::L1 + (t * 3 + (i >> 1)) * 64 + f0(r) + 4 * h + 32 * (i & 1)], dl[t][r], gz[i]);
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < 6; ++i) gz[i] += __shfl_xor(gz[i], 32, 64);
-            }
-            if (valid && h == 0) {
-#pragma unroll
-                for (int i = 0; i < 6; ++i)
-                    A.gz[(size_t)row * 6 + i] = !open ? 0.0 : finite ? (double)gz[i] : (double)__builtin_nanf("");
-            }
-        }
-    }
-    if (!want_w) return;
-
-    // ---- this workgroup's partial gradient, every entry written
-    float *P = A.part + (size_t)blockIdx.x * PTOTAL;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int m = f0(r) + 4 * h;
-        if (m < 3) P[PW4 + m * 128 + wave * 32 + j] = g4[r];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            P[PW3 + (wave * 32 + m) * 64 + t * 32 + j] = g3[t][r];
-            P[PW2 + ((wave >> 1) * 32 + m) * 128 + (2 * (wave & 1) + t) * 32 + j] = g2[t][r];
-        }
-        if (j < 6) P[PW1 + (wave * 32 + m) * 6 + j] = g1[r];
-        if (j == 6) P[PB1 + wave * 32 + m] = g1[r];
-    }
-    __syncthreads();
-    buf[tid] = gb4; buf[256 + tid] = gb3; buf[512 + tid] = gb2;
-    __syncthreads();
-    if (tid < 3) P[PB4 + tid] = buf[tid] + buf[128 + tid];
-    if (tid < 128) P[PB3 + tid] = buf[256 + tid] + buf[256 + 128 + tid];
-    if (tid < 64) P[PB2 + tid] = buf[512 + tid] + buf[512 + 128 + tid];
+#include "mlp_vjp_body.inc"
 }
+#undef VJP_EGO
+#undef VJP_FROW
+
+// K slots per instance (ndp_downwash_multi_vjp_device), other_index int32[B][K] (required): one launch instead of K launches, K reductions
+// and K - 1 adds.  The rows are VIRTUAL rows (i K + k) (N+1) + n, A.rows = B K (N+1) of them: the pair (instance i, slot k) plays the part of
+// the instance -- its neighbour row and gate come from other_index[i][k], which is entry i K + k of the flat array, the body's own
+// expression -- while the ego window, the ego xy and the upstream row are those of the real instance i (f is the sum of the slots, so its
+// gradient is shared by them).  g_z goes out as the virtual rows lie, [B][K][N+1][6]; the weight gradient accumulates over all (row, slot)
+// in the same registers.  A tile none of whose rows is open -- a closed or empty slot's -- costs its gate and nothing else.  Nothing else
+// differs, so at K = 1 this is mlp_vjp_kernel's arithmetic in mlp_vjp_kernel's order.
+#define VJP_EGO (inst / K)
+#define VJP_FROW ((size_t)(inst / K) * A.np1 + k)
+__global__ __launch_bounds__(256) void mlp_vjp_multi_kernel(MlpVjpArgs A, int K)
+{
+#include "mlp_vjp_body.inc"
+}
+#undef VJP_EGO
+#undef VJP_FROW
 
 __global__ __launch_bounds__(256) void mlp_vjp_reduce_kernel(const float *__restrict__ part, int groups, float *__restrict__ out)
 {
@@ -464,7 +280,9 @@ void make_fragments_t(const float *blob, float *frt)
 
 hipError_t mlp_vjp_prepare(void)
 {
-    return hipFuncSetAttribute((const void *)mlp_vjp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(VJ_LDS_FLOATS * sizeof(float)));
+    const hipError_t e = hipFuncSetAttribute((const void *)mlp_vjp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(VJ_LDS_FLOATS * sizeof(float)));
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute((const void *)mlp_vjp_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(VJ_LDS_FLOATS * sizeof(float)));
 }
 
 int ndp_downwash_vjp_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index, const void *d_ego_ref,
@@ -484,6 +302,35 @@ int ndp_downwash_vjp_device(ndp_handle *h, const void *d_other, int other_stride
                  (double *)d_gz, d_gw ? h->dGwPart : nullptr, rows, np1, h->cfg.r_horiz * h->cfg.r_horiz, other_stride,
                  (const int *)d_other_index, peer_mapped(d_other), (size_t)np1 * other_stride, (size_t)np1 * NX, (size_t)2};
     hipLaunchKernelGGL(mlp_vjp_kernel, dim3(G), dim3(256), VJ_LDS_FLOATS * sizeof(float), g.s, a);
+    NDP_HIP(h, hipGetLastError());
+    if (d_gw) {
+        hipLaunchKernelGGL(mlp_vjp_reduce_kernel, dim3((PTOTAL + 255) / 256), dim3(256), 0, g.s, (const float *)h->dGwPart, G, (float *)d_gw);
+        NDP_HIP(h, hipGetLastError());
+    }
+    return g.noted(0);
+}
+
+int ndp_downwash_multi_vjp_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index, int K,
+                                  const void *d_ego_ref, const void *d_ego_xy, const void *d_gf, void *d_gz, void *d_gw, void *stream)
+{
+    Entry g(h, d_other && d_ego_ref, stream);
+    if (g.rc) return g.rc;
+    const char *why = nullptr;
+    if (!h->have_mlp) { h->err = "ndp_downwash_multi_vjp_device: ndp_set_mlp_weights was never called"; return -6; }
+    if (K < 1 || K > NDP_MAX_NEIGH) why = "ndp_downwash_multi_vjp_device: K must be 1..8 (NDP_MAX_NEIGH neighbours per vehicle)";
+    else if (!d_other_index) why = "ndp_downwash_multi_vjp_device: d_other_index is required (int32 [B][K])";
+    else if (other_stride != 6 && other_stride != NX) why = "ndp_downwash_multi_vjp_device: other_stride must be 6 or 10";
+    else if (!d_gf) why = "ndp_downwash_multi_vjp_device: d_gf is required (the upstream gradient of the summed force)";
+    else if (!d_gz && !d_gw) why = "ndp_downwash_multi_vjp_device: no output asked for (d_gz and d_gw both NULL)";
+    if (why) { h->err = why; return -2; }
+    const int np1 = h->cfg.N + 1, rows = h->cfg.batch * K * np1;          // virtual rows
+    // the workspace is ndp_downwash_vjp_device's, [mlp_vjp_groups][NDP_MLP_NPARAM]: never more workgroups than it has rows (the grid-stride
+    // loop takes the rest); at K = 1 this is ndp_downwash_vjp_device's grid, hence its summation order
+    const int ngroups = ((rows + 31) / 32 + 3) / 4, cap = mlp_vjp_groups(h), G = ngroups < cap ? ngroups : cap;
+    MlpVjpArgs a{h->dFrag, h->dFragT, (const double *)d_other, (const double *)d_ego_ref, (const double *)d_ego_xy, (const double *)d_gf,
+                 (double *)d_gz, d_gw ? h->dGwPart : nullptr, rows, np1, h->cfg.r_horiz * h->cfg.r_horiz, other_stride,
+                 (const int *)d_other_index, peer_mapped(d_other), (size_t)np1 * other_stride, (size_t)np1 * NX, (size_t)2};
+    hipLaunchKernelGGL(mlp_vjp_multi_kernel, dim3(G), dim3(256), VJ_LDS_FLOATS * sizeof(float), g.s, a, K);
     NDP_HIP(h, hipGetLastError());
     if (d_gw) {
         hipLaunchKernelGGL(mlp_vjp_reduce_kernel, dim3((PTOTAL + 255) / 256), dim3(256), 0, g.s, (const float *)h->dGwPart, G, (float *)d_gw);

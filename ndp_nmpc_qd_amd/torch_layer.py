@@ -27,6 +27,11 @@ given directions of x0, xr, ur and f.  It returns plain tensors; there is no aut
 downwash_jvp / control_step_ndp_jvp continue that forward mode through the downwash network (BatchedNMPC.downwash_jvp_device): the force's tangent
 is the network's, along directions of the neighbour windows, of xr and of the weights.  Plain tensors as well.
 
+downwash_multi / control_step_ndp_multi / NDPControlStepMulti and downwash_multi_jvp / control_step_ndp_multi_jvp (behind their
+single-neighbour siblings) are the same four with K neighbours per instance, other_index [B,K]: the summed prediction
+(BatchedNMPC.downwash_multi_device) into the external-force step, differentiated by BatchedNMPC.downwash_multi_vjp_device /
+downwash_multi_jvp_device.
+
 control_step_tunable / TunableControlStep (behind them) differentiate the controller's own numbers -- the cost weights Qd, Rd and the mass --
 by the same adjoint (BatchedNMPC.set_model, step_vjp_device with gmodel).
 """
@@ -394,8 +399,151 @@ class NDPControlStep(torch.nn.Module):
         return control_step_ndp(self.engine, x0, xr, ur, other, ego_xy=ego_xy, weights=self.weights, other_index=other_index)
 
 
+# ---------------------------------------------------------------------------------------------- K neighbours per instance, differentiated
+# The K-slot siblings of the block above: the force is the sum over the slots other_index [B,K] (< 0: an empty slot) of the network on
+# (other[o_k] - ego_ref)[..., 0:6], each slot behind its own gate (BatchedNMPC.downwash_multi_device); its backward pass is one call
+# (BatchedNMPC.downwash_multi_vjp_device).  The same things are held fixed.  The fused step is single-neighbour, so control_step_ndp_multi
+# runs the summed prediction into a force tensor and then the external-force step: the route the multi-neighbour rollout takes.
+
+def _scatter_gz_multi(gz, other, other_index):
+    """dL/d other from g_z [B,K,N+1,6]: columns 0..5, the rest 0; instances and slots that share a neighbour row add up."""
+    g = torch.zeros_like(other)
+    has = other_index >= 0
+    g[:, :, :6].index_add_(0, other_index[has].long(), gz[has])
+    return g
+
+
+class DownwashMultiFunction(torch.autograd.Function):
+    """forward(other, engine, other_index, ego_ref, ego_xy, weights) -> f [B,N+1,3] float32, the summed gated downwash force
+    (mlp_multi_kernel); backward: BatchedNMPC.downwash_multi_vjp_device for the gradients of other, ego_ref and weights."""
+
+    @staticmethod
+    def forward(ctx, other, engine, other_index, ego_ref, ego_xy=None, weights=None):
+        if isinstance(ego_xy, torch.Tensor) and ego_xy.requires_grad:
+            raise ValueError("DownwashMultiFunction: ego_xy requires grad, but the r_horiz gate is piecewise constant and is not "
+                             "differentiated (detach it)")
+        od, ed = other.detach().contiguous(), ego_ref.detach().contiguous()
+        stream, default = _cuda_stream(od)
+        if default:
+            stream.synchronize()
+        ctx.key = _install_weights(engine, weights, stream)
+        f = torch.empty((ed.shape[0], ed.shape[1], 3), dtype=torch.float32, device=od.device)
+        engine.downwash_multi_device(od, other_index, ed, f, ego_xy=ego_xy, stream=stream)
+        if default:
+            engine.synchronize()
+        ctx.engine = engine
+        ctx.have_w = weights is not None
+        ctx.have_xy = ego_xy is not None
+        ctx.save_for_backward(od, ed, other_index, *(t for t in (ego_xy, weights) if t is not None))
+        return f
+
+    @staticmethod
+    def backward(ctx, g_f):
+        od, ed, other_index, *rest = ctx.saved_tensors
+        ego_xy = rest.pop(0) if ctx.have_xy else None
+        eng = ctx.engine
+        _check_installed(eng, ctx.key, "DownwashMultiFunction")
+        need = ctx.needs_input_grad
+        gf = g_f.to(torch.float64).contiguous()
+        B, np1, K = ed.shape[0], ed.shape[1], other_index.shape[1]
+        gz = torch.empty((B, K, np1, 6), dtype=torch.float64, device=od.device) if need[0] or need[3] else None
+        gw = torch.empty(17859, dtype=torch.float32, device=od.device) if ctx.have_w and need[5] else None
+        if gz is None and gw is None:
+            return (None,) * 6
+        stream, default = _cuda_stream(od)
+        eng.downwash_multi_vjp_device(od, other_index, ed, gf, ego_xy=ego_xy, gz=gz, gw=gw, stream=stream)
+        if default:
+            eng.synchronize()
+        return (_scatter_gz_multi(gz, od, other_index) if need[0] else None, None, None,
+                _minus_gz(gz.sum(dim=1), ed) if need[3] else None, None, gw)
+
+
+def downwash_multi(engine, other, other_index, ego_ref, ego_xy=None, weights=None):
+    """f [B,N+1,3] float32 = the engine's summed downwash force from K neighbours per instance: other [rows,N+1,6 or 10] float64,
+    other_index int32 [B,K] the rows of `other` instance i hears (< 0: an empty slot; the same row twice counts twice), each slot behind
+    its own gate.  Differentiable in `other` (columns 0..5; instances and slots that share a row add up), `ego_ref` (minus the sum over
+    the slots on columns 0..5) and `weights` (as `downwash`: installed first unless they are what was installed last).  The gate is held
+    fixed: ego_xy requiring grad raises.  A row whose upstream gradient is not finite adds nothing to the weights' gradient and has NaN
+    in the input gradients of its open slots."""
+    return DownwashMultiFunction.apply(other, engine, other_index, ego_ref, ego_xy, weights)
+
+
+class ControlStepNDPMultiFunction(torch.autograd.Function):
+    """forward(x0, engine, xr, ur, other, other_index, ego_xy, weights) -> (u0, X, U) float64: the summed prediction (downwash_multi_device
+    with ego_ref = xr) into a force tensor, then the external-force control step; backward: the step's adjoint (step_vjp_device) for x0,
+    xr, ur and the force's gradient gf, then downwash_multi_vjp_device on that gf for other, weights and xr's share (minus the sum over
+    the slots of g_z on columns 0..5)."""
+
+    @staticmethod
+    def forward(ctx, x0, engine, xr, ur, other, other_index, ego_xy=None, weights=None):
+        if isinstance(ego_xy, torch.Tensor) and ego_xy.requires_grad:
+            raise ValueError("ControlStepNDPMultiFunction: ego_xy requires grad, but the r_horiz gate is piecewise constant and is not "
+                             "differentiated (detach it)")
+        det = lambda t: t.detach().contiguous()  # noqa: E731
+        x0, xr, ur, od = det(x0), det(xr), det(ur), det(other)
+        stream, default = _cuda_stream(x0)
+        if default:
+            stream.synchronize()
+        ctx.key = _install_weights(engine, weights, stream)
+        force = torch.empty((xr.shape[0], xr.shape[1], 3), dtype=torch.float32, device=x0.device)
+        engine.downwash_multi_device(od, other_index, xr, force, ego_xy=ego_xy, stream=stream)
+        tape, u0, X, U = _taped_step(engine, stream, default, x0, xr, ur, f=force)
+        ctx.engine = engine
+        ctx.have_w = weights is not None
+        ctx.have_xy = ego_xy is not None
+        ctx.save_for_backward(x0, xr, ur, od, other_index, force, *tape, *(t for t in (ego_xy, weights) if t is not None))
+        return u0, X, U
+
+    @staticmethod
+    def backward(ctx, g_u0, g_X, g_U):
+        x0, xr, ur, od, other_index, force, t0, t1, t2, *rest = ctx.saved_tensors
+        ego_xy = rest.pop(0) if ctx.have_xy else None
+        eng = ctx.engine
+        if g_u0 is None and g_X is None and g_U is None:
+            return (None,) * 8
+        _check_installed(eng, ctx.key, "ControlStepNDPMultiFunction")
+        B, N, K = x0.shape[0], xr.shape[1] - 1, other_index.shape[1]
+        need = ctx.needs_input_grad
+        net_w = ctx.have_w and need[7]
+        net = need[2] or need[4] or net_w                    # anything behind the force
+        stream, default = _cuda_stream(x0)
+        gx0, gxr, gur, gf = _taped_step_vjp(eng, x0, xr, ur, (t0, t1, t2), force, (g_u0, g_X, g_U), (need[0], need[2], need[3], net), stream)
+        g_other = gw = None
+        if net:
+            if default:
+                eng.synchronize()
+            gz = torch.empty((B, K, N + 1, 6), dtype=torch.float64, device=x0.device) if need[2] or need[4] else None
+            gw = torch.empty(17859, dtype=torch.float32, device=x0.device) if net_w else None
+            eng.downwash_multi_vjp_device(od, other_index, xr, gf, ego_xy=ego_xy, gz=gz, gw=gw, stream=stream)
+        if default:
+            eng.synchronize()
+        if net and need[2]:
+            gxr[:, :, :6] -= gz.sum(dim=1)
+        if net and need[4]:
+            g_other = _scatter_gz_multi(gz, od, other_index)
+        return (gx0, None, gxr, gur, g_other, None, None, gw)
+
+
+def control_step_ndp_multi(engine, x0, xr, ur, other, other_index, ego_xy=None, weights=None):
+    """(u0, X, U) = the engine's control step compensating the summed downwash of K neighbours per instance (see downwash_multi for
+    other / other_index), differentiable with respect to x0, xr, ur, `other` and the network's `weights`: the step's adjoint, then the
+    K-slot backward pass of the network on the force's gradient.  The forward is two launches (the summed prediction, then the
+    external-force step): the fused step is single-neighbour.  Held fixed: the linearisation point, the active set and the gates (ego_xy
+    requiring grad raises).  Instances whose step failed (nonzero status) have NaN gradients of their own inputs and contribute nothing
+    to the weights' gradient."""
+    return ControlStepNDPMultiFunction.apply(x0, engine, xr, ur, other, other_index, ego_xy, weights)
+
+
+class NDPControlStepMulti(NDPControlStep):
+    """control_step_ndp_multi with the network's weights as this module's nn.Parameter `weights` (see NDPControlStep).
+    forward(x0, xr, ur, other, other_index, ego_xy=None) -> (u0, X, U)."""
+
+    def forward(self, x0, xr, ur, other, other_index, ego_xy=None):
+        return control_step_ndp_multi(self.engine, x0, xr, ur, other, other_index, ego_xy=ego_xy, weights=self.weights)
+
+
 # ---------------------------------------------------------------------------------------------- the downwash network, forward mode
-# The mirror of the block above (BatchedNMPC.downwash_jvp_device): the first-order change of the force along directions of the neighbour
+# The mirror of the single-neighbour block above (BatchedNMPC.downwash_jvp_device): the first-order change of the force along directions of the neighbour
 # windows, of ego_ref and of the weights, and its composition with the step's forward mode.  Held fixed: what the backward holds fixed
 # (gate, linearisation point, active set); ego_xy has no tangent.  Plain tensors, no autograd hookup, like control_step_jvp.
 
@@ -487,6 +635,74 @@ def control_step_ndp_jvp(engine, x0, xr, ur, other, tangents, ego_xy=None, weigh
         engine.downwash_jvp_device(od, xr, tz=tz, tw=tw, ego_xy=ego_xy, other_index=other_index, n_tan=T, df=tf, stream=stream)
     du0, dX, dU = (torch.empty((B, T) + s, dtype=torch.float64, device=x0.device) for s in ((4,), (N + 1, 10), (N, 4)))
     engine.step_jvp_device(x0, xr, ur, tape, tx0, txr, tur, tf, f=engine.device_force(), du0=du0, dX=dX, dU=dU, stream=stream)
+    if default:
+        engine.synchronize()
+    if not had:
+        du0, dX, dU = du0[:, 0], dX[:, 0], dU[:, 0]
+    return u0, X, U, du0, dX, dU
+
+
+def _network_tz_multi(t_other, t_ego, other_index):
+    """tz [B,T,K,N+1,6] = t_other[other_index[:, k]] - t_ego on columns 0..5 per slot (either may be None; both None: None).  Plumbing, the
+    mirror of _scatter_gz_multi; an empty slot's rows are never read by the device."""
+    tz = None
+    if t_other is not None:
+        rows = t_other[other_index.clamp(min=0).long()]                   # [B,K,T,N+1,cols]
+        tz = rows[..., :6].to(torch.float64).transpose(1, 2)
+    if t_ego is not None:
+        e = t_ego[..., :6].to(torch.float64).unsqueeze(2)                 # [B,T,1,N+1,6]
+        tz = (-e).expand(-1, -1, other_index.shape[1], -1, -1) if tz is None else tz - e
+    return None if tz is None else tz.contiguous()
+
+
+def downwash_multi_jvp(engine, other, other_index, ego_ref, tangents, ego_xy=None, weights=None):
+    """(f, df): the engine's summed downwash force f [B,N+1,3] float32 from K neighbours per instance (see downwash_multi) and its
+    first-order change df [B,T,N+1,3] float64 along tangents = (t_other, t_ego_ref, t_weights), shaped as downwash_jvp takes them (forward
+    mode: BatchedNMPC.downwash_multi_jvp_device; every slot reads its neighbour row's direction).  The gates are held fixed.  No autograd
+    hookup."""
+    od, ed = other.detach().contiguous(), ego_ref.detach().contiguous()
+    (t_other, t_ego, t_w), T, had = _with_t_axis(tangents, (3, 3, 1), "downwash_multi_jvp")
+    stream, default = _cuda_stream(od)
+    if default:
+        stream.synchronize()
+    _install_weights(engine, weights, stream)
+    B, np1 = ed.shape[0], ed.shape[1]
+    tz = _network_tz_multi(t_other, t_ego, other_index)
+    tw = None if t_w is None else t_w.to(torch.float32).contiguous()
+    f = torch.empty((B, np1, 3), dtype=torch.float32, device=od.device)
+    df = torch.empty((B, T, np1, 3), dtype=torch.float64, device=od.device)
+    engine.downwash_multi_jvp_device(od, other_index, ed, tz=tz, tw=tw, ego_xy=ego_xy, n_tan=T, df=df, f_check=f, stream=stream)
+    if default:
+        engine.synchronize()
+    return f, df if had else df[:, 0]
+
+
+def control_step_ndp_multi_jvp(engine, x0, xr, ur, other, other_index, tangents, ego_xy=None, weights=None):
+    """(u0, X, U, du0, dX, dU): control_step_ndp_multi's step and new iterate, and the first-order change of all three along tangents =
+    (tx0, txr, tur, t_other, t_weights), shaped as control_step_ndp_jvp takes them.  On one stream: the summed prediction, the taped
+    external-force step, the network's K-slot JVP with tz[:, :, k] = t_other[other_index[:, k]] - txr[..., 0:6] (and t_weights), giving
+    tf; BatchedNMPC.step_jvp_device with (tx0, txr, tur, tf) and the same force.  Held fixed: the linearisation point, the active set and
+    the gates.  Instances whose step failed have NaN tangents.  No autograd hookup."""
+    det = lambda t: t.detach().contiguous()  # noqa: E731
+    x0, xr, ur, od = det(x0), det(xr), det(ur), det(other)
+    (tx0, txr, tur, t_other, t_w), T, had = _with_t_axis(tangents, (2, 3, 3, 3, 1), "control_step_ndp_multi_jvp")
+    tx0, txr, tur = (None if t is None else t.to(torch.float64).contiguous() for t in (tx0, txr, tur))
+    B, N = x0.shape[0], xr.shape[1] - 1
+    stream, default = _cuda_stream(x0)
+    if default:
+        stream.synchronize()
+    _install_weights(engine, weights, stream)
+    force = torch.empty((B, N + 1, 3), dtype=torch.float32, device=x0.device)
+    engine.downwash_multi_device(od, other_index, xr, force, ego_xy=ego_xy, stream=stream)
+    tape, u0, X, U = _taped_step(engine, stream, default, x0, xr, ur, f=force)
+    tz = _network_tz_multi(t_other, txr, other_index)
+    tw = None if t_w is None else t_w.to(torch.float32).contiguous()
+    tf = None
+    if tz is not None or tw is not None:
+        tf = torch.empty((B, T, N + 1, 3), dtype=torch.float64, device=x0.device)
+        engine.downwash_multi_jvp_device(od, other_index, xr, tz=tz, tw=tw, ego_xy=ego_xy, n_tan=T, df=tf, stream=stream)
+    du0, dX, dU = (torch.empty((B, T) + s, dtype=torch.float64, device=x0.device) for s in ((4,), (N + 1, 10), (N, 4)))
+    engine.step_jvp_device(x0, xr, ur, tape, tx0, txr, tur, tf, f=force, du0=du0, dX=dX, dU=dU, stream=stream)
     if default:
         engine.synchronize()
     if not had:

@@ -117,9 +117,11 @@ def main():
         return bench_ref_list(a, torch, ndp, dev)
     if a.row == "downwash_multi":
         return bench_downwash_multi(a, torch, ndp, dev)
+    if a.row == "downwash_multi_vjp":
+        return bench_downwash_multi_vjp(a, torch, ndp, dev)
     if a.row == "rollout_formation_multi":
         return bench_rollout_formation_multi(a, torch, ndp, dev)
-    eng = ndp.BatchedNMPC(B, N=2, load_mlp=False)       # tiny horizon: only the estimator state matters here
+    eng =ndp.BatchedNMPC(B, N=2, load_mlp=False)       # tiny horizon: only the estimator state matters here
     vz = torch.randn(B, dtype=torch.float64, device=dev) * 0.1
     th = torch.rand(B, dtype=torch.float64, device=dev) * 0.8 + 0.15
     k = torch.empty(B, dtype=torch.float64, device=dev)
@@ -347,6 +349,95 @@ def bench_downwash_multi(a, torch, ndp, dev):
                         "one_launch_us_runs": [t * 1e6 for t in tm], "k_launches_plus_add_us_runs": [t * 1e6 for t in ts]}
     print(json.dumps({"row": "downwash prediction from K neighbours: one mlp_multi_kernel launch against K mlp_kernel launches + add",
                       "metric": "us per call (device events, launches included)", "batch": B, "N": N, "results": out}))
+
+
+def bench_downwash_multi_vjp(a, torch, ndp, dev):
+    """The derivatives of the K-neighbour prediction (B = a.batch instances, N = 20), K = 2 and 3, every gate open and about a third of the
+    slots open.  Reverse mode, gz and gw both asked for: ONE ndp_downwash_multi_vjp_device call against what it replaces on the same
+    inputs -- K ndp_downwash_vjp_device calls into K buffers plus the K - 1 adds of gw.  Forward mode, T = 1 and 4: one
+    ndp_downwash_multi_jvp_device call against K ndp_downwash_jvp_device calls plus the K - 1 adds of df.  Alternating passes in one
+    run, by device events; the figure of a pass is its mean over a.steps calls, the figure reported is the median of the passes."""
+    import numpy as np
+    B, N, P = a.batch, 20, 17859
+    rng = np.random.default_rng(7)
+    eng = ndp.BatchedNMPC(B, N=N, load_mlp=True)
+    st = torch.cuda.Stream(device=dev)
+    torch.cuda.set_stream(st)
+    T = lambda x, dt=None: torch.from_numpy(np.ascontiguousarray(x)).to(dev) if dt is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev, dt)  # noqa: E731
+    ego = rng.normal(0.0, 1.0, (B, N + 1, 10))
+    gf_t = T(rng.normal(size=(B, N + 1, 3)))
+    out = {}
+    for K in (2, 3):
+        z = np.empty((B, K, N + 1, 6))
+        z[..., :3], z[..., 3:] = rng.uniform(-1.5, 1.5, (B, K, N + 1, 3)), rng.uniform(-3.0, 3.0, (B, K, N + 1, 3))
+        for mix in ("all_open", "third_open"):
+            # every slot a row of `other` of its own; node 0's xy of slot (i, k) sits rad away from ego_xy[i]
+            want = np.ones((B, K), dtype=bool) if mix == "all_open" else rng.random((B, K)) < 1.0 / 3.0
+            rad = np.where(want, rng.uniform(0.0, 0.9, (B, K)), rng.uniform(1.1, 3.0, (B, K)))
+            ang = rng.uniform(0.0, 2.0 * np.pi, (B, K))
+            zz = z.copy()
+            zz[:, :, 0, 0], zz[:, :, 0, 1] = rad * np.cos(ang), rad * np.sin(ang)
+            other = rng.normal(0.0, 1.0, (B * K, N + 1, 10))
+            other[:, :, :6] = (ego[:, None, :, :6] + zz).reshape(B * K, N + 1, 6)
+            idx = np.arange(B * K, dtype=np.int32).reshape(B, K)
+            other_t, ego_t, xy_t, idx_t = T(other), T(ego), T(ego[:, 0, 0:2]), T(idx)
+            idx_k = [T(idx[:, k]) for k in range(K)]
+            gz_m = torch.empty(B, K, N + 1, 6, dtype=torch.float64, device=dev)
+            gw_m = torch.empty(P, dtype=torch.float32, device=dev)
+            gz_k = [torch.empty(B, N + 1, 6, dtype=torch.float64, device=dev) for _ in range(K)]
+            gw_k = [torch.empty(P, dtype=torch.float32, device=dev) for _ in range(K)]
+            gw_s = torch.empty(P, dtype=torch.float32, device=dev)
+
+            def vjp_multi(i):
+                eng.downwash_multi_vjp_device(other_t, idx_t, ego_t, gf_t, ego_xy=xy_t, gz=gz_m, gw=gw_m, stream=st)
+
+            def vjp_single(i):
+                for k in range(K):
+                    eng.downwash_vjp_device(other_t, ego_t, gf_t, ego_xy=xy_t, other_index=idx_k[k], gz=gz_k[k], gw=gw_k[k], stream=st)
+                torch.add(gw_k[0], gw_k[1], out=gw_s)
+                for k in range(2, K):
+                    gw_s.add_(gw_k[k])
+            res = {"slots_open": float(want.mean())}
+            tm, ts = [], []
+            for _ in range(5):                            # alternating: other people's work shares the machine
+                tm.append(_events(torch, vjp_multi, a.steps, a.warmup))
+                ts.append(_events(torch, vjp_single, a.steps, a.warmup))
+            assert all(torch.equal(gz_m[:, k], gz_k[k]) for k in range(K))
+            scale = float(gw_s.abs().max())
+            assert float((gw_m - gw_s).abs().max()) <= 1e-4 * max(1.0, scale)
+            res["vjp"] = {"one_call_us": float(np.median(tm)) * 1e6, "k_calls_plus_adds_us": float(np.median(ts)) * 1e6,
+                          "ratio_k_calls_over_one": float(np.median(ts) / np.median(tm)),
+                          "one_call_us_passes": [t * 1e6 for t in tm], "k_calls_plus_adds_us_passes": [t * 1e6 for t in ts]}
+            for nt in (1, 4):
+                tz_t = T(rng.normal(size=(B, nt, K, N + 1, 6)))
+                tz_k = [tz_t[:, :, k].contiguous() for k in range(K)]
+                tw_t = T(0.01 * rng.normal(size=(nt, P)), torch.float32)
+                df_m = torch.empty(B, nt, N + 1, 3, dtype=torch.float64, device=dev)
+                df_k = [torch.empty_like(df_m) for _ in range(K)]
+                df_s = torch.empty_like(df_m)
+
+                def jvp_multi(i):
+                    eng.downwash_multi_jvp_device(other_t, idx_t, ego_t, tz=tz_t, tw=tw_t, ego_xy=xy_t, n_tan=nt, df=df_m, stream=st)
+
+                def jvp_single(i):
+                    for k in range(K):
+                        eng.downwash_jvp_device(other_t, ego_t, tz=tz_k[k], tw=tw_t, ego_xy=xy_t, other_index=idx_k[k], n_tan=nt, df=df_k[k],
+                                                stream=st)
+                    torch.add(df_k[0], df_k[1], out=df_s)
+                    for k in range(2, K):
+                        df_s.add_(df_k[k])
+                tm, ts = [], []
+                for _ in range(5):
+                    tm.append(_events(torch, jvp_multi, a.steps, a.warmup))
+                    ts.append(_events(torch, jvp_single, a.steps, a.warmup))
+                assert torch.equal(df_m, df_s)
+                res[f"jvp_T{nt}"] = {"one_call_us": float(np.median(tm)) * 1e6, "k_calls_plus_adds_us": float(np.median(ts)) * 1e6,
+                                     "ratio_k_calls_over_one": float(np.median(ts) / np.median(tm)),
+                                     "one_call_us_passes": [t * 1e6 for t in tm], "k_calls_plus_adds_us_passes": [t * 1e6 for t in ts]}
+            out[f"K{K}_{mix}"] = res
+    print(json.dumps({"row": "derivatives of the downwash prediction from K neighbours: one mlp_vjp_multi_kernel / mlp_jvp_multi_kernel "
+                             "call against K single-neighbour calls + adds", "metric": "us per call (device events, launches included; "
+                             "median of 5 alternating passes)", "batch": B, "N": N, "results": out}))
 
 
 def bench_rollout_formation_multi(a, torch, ndp, dev):
