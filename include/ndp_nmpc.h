@@ -683,6 +683,45 @@ int ndp_downwash_multi_jvp_device(ndp_handle *h, const void *d_other, int other_
                                   const void *d_ego_ref, const void *d_ego_xy, int n_tan, const void *d_tz, const void *d_tw, void *d_df,
                                   void *d_f_check, void *stream);
 
+/* ---- Training the downwash network on the device (nn_train.py:129-157 with --SN): one full-batch Adam step followed by the spectral-norm
+ * cap on every weight matrix, in ONE launch of four workgroups (one per layer) behind the weight gradient of ndp_downwash_vjp_device /
+ * ndp_downwash_multi_vjp_device.  No host value changes between two steps (the step counter lives in device memory), so steps can be
+ * enqueued back to back or captured into a graph.
+ *
+ * ndp_mlp_spectral_norms_device: d_sigma[l] (fp64 [4]) = the largest singular value of the weight matrix of layer l + 1 of d_w (fp32
+ *   [NDP_MLP_NPARAM], blob order of ndp_set_mlp_weights; biases are not part of it).  Per layer: the Gram matrix on the smaller side (6x6,
+ *   64x64, 64x64, 3x3) in fp64 on the f64 matrix instruction (products of fp32 values are exact there), Householder tridiagonalisation in
+ *   LDS, then 8 rounds of 256-way multisection on Sturm counts from a Gershgorin bound: a direct method whose accuracy does not depend on
+ *   the gaps between singular values (relative error of the order of 64 x 2^-53), every loop with a compile-time trip count.  An all-zero
+ *   matrix gives exactly 0.  The handle's weights are not read or written.
+ * ndp_mlp_spectral_norms: the same for a host blob; synchronises.
+ * ndp_mlp_adam_sn_device: one optimiser step.  d_w, d_m, d_v fp32 [NDP_MLP_NPARAM] (parameters and Adam's two moments, updated in place),
+ *   d_g fp32 [NDP_MLP_NPARAM] (the gradient, exactly what the VJP calls write as d_gw), d_step int64 [1] (steps taken so far).  All-zero
+ *   d_m, d_v, d_step are a fresh optimiser.  With t = step + 1, torch.optim.Adam's defaults (no weight decay, no amsgrad):
+ *       m = beta1 m + (1 - beta1) g,  v = beta2 v + (1 - beta2) g^2,  p = p - lr / (1 - beta1^t) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *   in fp64 from the fp32 inputs, every operation rounded on its own (no fused multiply-add); m, v and p are each rounded to fp32 once, in
+ *   that order, and the p update reads the STORED m and v: a step is a pure function of the stored state.  fp32 subnormals are kept.  Then, per layer, sigma of the updated weight matrix as above and,
+ *   if sn_cap > 0 and sigma > sn_cap, every weight of the layer becomes fp32(w * (sn_cap / sigma)), factor and product in fp64 (the
+ *   reference's fp32 `param / s * SN` rounds twice: at most 1.5 ulp apart).  Biases are never scaled (nn_train.py:153).  sn_cap <= 0: no
+ *   layer is scaled.
+ *   Non-finite gradient: if any of the NDP_MLP_NPARAM values of d_g is NaN or infinite the call changes nothing -- d_w, d_m, d_v and
+ *   d_step stay bit for bit -- and d_info[0] = 1 (every workgroup scans the whole gradient and decides alike).
+ *   d_step is advanced by the kernel, once per step that was not skipped: every workgroup reads it at entry and the last one to finish
+ *   (an agent-scope ticket in a workspace of the handle, which that workgroup resets) writes step + 1.
+ *   d_sigma fp64 [4], NULL allowed: the norms AFTER the call -- of a layer that was scaled, the norm of the scaled (rounded) matrix,
+ *     computed again; after a skipped step, the norms of the unchanged weights.
+ *   d_info int32 [4], NULL allowed: [0] 1 if the step was skipped, else 0; [1] bitmask of the layers that were scaled (bit l = layer l + 1);
+ *     [2], [3] reserved, written as 0.
+ *   install != 0: behind the update, on the same stream, what ndp_set_mlp_weights_device(h, d_w, stream) does -- also after a skipped step.
+ *   The ticket lives in one workspace of the handle (allocated by ndp_create, so the call may be captured): calls on one handle must be
+ *   ordered against each other -- the same stream, or streams ordered by events.
+ *   -1: NULL handle or a NULL required pointer (d_w, d_g, d_m, d_v, d_step); -2 with a reason in ndp_last_error: lr not finite, a beta
+ *   outside [0, 1), eps <= 0 (or NaN), sn_cap NaN.  Nothing is launched on -1 or -2. */
+int ndp_mlp_spectral_norms_device(ndp_handle *h, const void *d_w, void *d_sigma, void *stream);
+int ndp_mlp_spectral_norms(ndp_handle *h, const float *blob, double *sigma4);
+int ndp_mlp_adam_sn_device(ndp_handle *h, void *d_w, const void *d_g, void *d_m, void *d_v, void *d_step, double lr, double beta1,
+                           double beta2, double eps, double sn_cap, void *d_sigma, void *d_info, int install, void *stream);
+
 /* ---- Peer windows: the neighbour exchange across GPUs as publish / subscribe over xGMI.
  * Replaces the PredXU topic between processes: the publisher is nmpc_node.py:116-133,229-230 (`nmpc_x_ref`, 21x10 float64, a NEW
  * message every control tick), the subscriber ndp_nmpc_leader_node.py:40,60-76 (consumes the latest one).  One process per GPU:

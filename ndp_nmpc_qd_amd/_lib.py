@@ -64,6 +64,7 @@ EXPORTS = [
     "ndp_downwash_multi", "ndp_downwash_multi_device", "ndp_plant_force_multi", "ndp_plant_force_multi_device",
     "ndp_rollout_formation_multi_device",
     "ndp_downwash_multi_vjp_device", "ndp_downwash_multi_jvp_device",
+    "ndp_mlp_spectral_norms_device", "ndp_mlp_spectral_norms", "ndp_mlp_adam_sn_device",
 ]
 
 _lib = None
@@ -219,6 +220,9 @@ def load():
     lib.ndp_rollout_formation_multi_device.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, vp, C.c_int, C.c_int, C.c_double] + [vp] * 6
     lib.ndp_downwash_multi_vjp_device.argtypes = [vp, vp, C.c_int, vp, C.c_int] + [vp] * 6
     lib.ndp_downwash_multi_jvp_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int] + [vp] * 5
+    lib.ndp_mlp_spectral_norms_device.argtypes = [vp] * 4
+    lib.ndp_mlp_spectral_norms.argtypes = [vp] * 3
+    lib.ndp_mlp_adam_sn_device.argtypes = [vp] * 6 + [C.c_double] * 5 + [vp, vp, C.c_int, vp]
     lib.ndp_plant_step.argtypes = [vp, vp, vp, vp, C.c_double, C.c_int]
     lib.ndp_plant_step_device.argtypes = [vp, vp, vp, vp, C.c_double, C.c_int, vp]
     _lib = lib

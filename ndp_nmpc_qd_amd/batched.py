@@ -855,6 +855,49 @@ class BatchedNMPC:
         self._check(self._lib.ndp_debug_mlp_fragments(self._h, _lib.ptr(fr), _lib.ptr(frt)), "ndp_debug_mlp_fragments")
         return fr, frt
 
+    # ---- training the downwash network on the device (csrc/mlp_train.hip)
+    def mlp_spectral_norms(self, blob):
+        """float64 [4]: the largest singular value of each layer's weight matrix of a host blob (17859 float32 in blob order;
+        ndp_mlp_spectral_norms).  Synchronises.  The engine's own weights are not read."""
+        blob = np.ascontiguousarray(blob, dtype=np.float32)
+        if blob.size != _lib.MLP_NPARAM:
+            raise ValueError(f"blob: expected {_lib.MLP_NPARAM} float32 values, got {blob.size}")
+        out = np.zeros(4, dtype=np.float64)
+        self._check(self._lib.ndp_mlp_spectral_norms(self._h, _lib.ptr(blob), _lib.ptr(out)), "ndp_mlp_spectral_norms")
+        return out
+
+    def mlp_spectral_norms_device(self, w, sigma, stream=None):
+        """Enqueues the four spectral norms of the float32 CUDA blob `w` [17859] into the float64 CUDA tensor `sigma` [4] on `stream`
+        (ndp_mlp_spectral_norms_device): a direct method in fp64, accurate to the order of 1e-14 whatever the gaps between singular values.
+        stream None or torch's default stream: as downwash_vjp_device."""
+        import torch
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        d = self._dptr
+        self._check(self._lib.ndp_mlp_spectral_norms_device(self._h, d(w, torch.float32, (_lib.MLP_NPARAM,)), d(sigma, torch.float64, (4,)),
+                                                            self._stream(stream)), "ndp_mlp_spectral_norms_device")
+
+    def mlp_adam_sn_device(self, w, g, m, v, step, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, sn=0.0, sigma=None, info=None, install=False,
+                           stream=None):
+        """Enqueues one optimiser step on `stream` (ndp_mlp_adam_sn_device; include/ndp_nmpc.h): torch.optim.Adam's update (defaults: no
+        weight decay, no amsgrad) of the float32 CUDA blob `w` [17859] with the gradient `g` (what downwash_vjp_device writes as gw) and
+        the moments `m`, `v` (float32 [17859], in place), then, with sn > 0, every weight matrix whose spectral norm exceeds sn scaled back
+        onto it (biases never).  `step` int64 CUDA [1] counts the steps taken and is advanced by the kernel, so calls can be enqueued back
+        to back or captured.  A non-finite gradient changes nothing and sets info[0].  sigma float64 [4] (the norms after the call) and
+        info int32 [4] (skipped flag, bitmask of scaled layers, 0, 0) are optional.  install: the engine's network becomes the updated `w`
+        behind the step (set_mlp_weights_device on the same stream).  Never synchronises the device.  stream None or torch's default
+        stream: as downwash_vjp_device."""
+        import torch
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        d, n = self._dptr, (_lib.MLP_NPARAM,)
+        self._check(self._lib.ndp_mlp_adam_sn_device(
+            self._h, d(w, torch.float32, n), d(g, torch.float32, n), d(m, torch.float32, n), d(v, torch.float32, n),
+            d(step, torch.int64, (1,)), float(lr), float(betas[0]), float(betas[1]), float(eps), float(sn), d(sigma, torch.float64, (4,)),
+            d(info, torch.int32, (4,)), int(bool(install)), self._stream(stream)), "ndp_mlp_adam_sn_device")
+        if install:
+            self._mlp_installed = None      # (torch_layer.DownwashAdamSN notes what IT installed, behind this call)
+
     def device_iterate(self):
         """The engine's iterate as CUDA tensor views (no copy): (X [B,N+1,10], U [B,N,4]) float64 (ndp_device_iterate_x / _u); valid once
         the step's stream has reached them; the next step overwrites them."""

@@ -13,6 +13,8 @@
 //   mlp_vjp.hip      the downwash network's backward pass (ndp_downwash_vjp_device, ndp_downwash_multi_vjp_device) and its weights set from
 //                    device memory
 //   mlp_jvp.hip      the downwash network's forward mode (ndp_downwash_jvp_device, ndp_downwash_multi_jvp_device)
+//   mlp_train.hip    the downwash network's optimiser step: Adam + spectral-norm cap in one launch (ndp_mlp_adam_sn_device), the layers'
+//                    spectral norms (ndp_mlp_spectral_norms*)
 //   exchange.hip     peer-mapped windows (ndp_peer_*), the RCCL exchange (ndp_xchg_*) and the remote tick one control period ahead
 // A kernel sits with the host code that launches it; device code that two units' kernels inline is a header (mlp_tile.hpp, ref_point.hpp,
 // tick_wave.hpp), and so are the argument blocks the host fills (kern_args.hpp).
@@ -71,6 +73,9 @@ struct ndp_handle {
     // dFrag by both ndp_set_mlp_weights forms); ndp_downwash_vjp_device's per-workgroup partial weight gradients [mlp_vjp_groups][NDP_MLP_NPARAM]
     // (ndp_downwash_multi_vjp_device shares them: it never launches more workgroups than that)
     float *dFragT = nullptr, *dGwPart = nullptr;
+    // mlp_train.hip: word 0 = the ticket of ndp_mlp_adam_sn_device's four workgroups (0 between launches), then 4 doubles and a blob's
+    // floats: the staging of the host form ndp_mlp_spectral_norms (TRAIN_WS_BYTES)
+    unsigned long long *dTrain = nullptr;
     double *dThr = nullptr;    // hover-throttle estimator state, SoA [8][B]
     double *dStamps = nullptr; // [B][NDP_NSTAMP] whole-batch phase stamps (ndp_debug_stamps)
     double *dTraj = nullptr;   // f1: the trajectories and the tick's caches (layout: TrajView)
@@ -165,6 +170,8 @@ static inline int mlp_vjp_groups(const ndp_handle *h)
     const int ntiles = (h->cfg.batch * (h->cfg.N + 1) + 31) / 32, ngroups = (ntiles + 3) / 4;
     return ngroups < VJ_MAX_GROUPS ? ngroups : VJ_MAX_GROUPS;
 }
+
+enum { TRAIN_WS_BYTES = 64 + 4 * 8 + 17859 * 4 };   // dTrain: ticket (64 bytes of its own) | sigma [4] fp64 | blob [NDP_MLP_NPARAM] fp32
 
 enum { TICK_ESTIMATE = NDP_TICK_ESTIMATE, TICK_WANT_U0 = NDP_TICK_WANT_U0, TICK_T_UNIFORM = NDP_TICK_T_UNIFORM };
 

@@ -206,7 +206,7 @@ int ndp_destroy(ndp_handle *h)
     h->pool.reset();
     void *ptrs[] = {h->dForceAB[0], h->dForceAB[1], h->dProto, h->dRingX, h->dTraj, h->dTables, h->dStamps, h->dRelay, h->dThr, h->sThr, h->dKC, h->dForce, h->dFrag,
                     h->dIn, h->dOut, h->sdbg, h->dQctr, h->dQids, h->dTickIndex, h->dTickThrust, h->dAct,
-                    h->dSensU0, h->dSensU, h->dSensX, h->dPSensXr, h->dPSensUr, h->dPSensF, h->dVjp, h->dVjpSt, h->dVjpAct, h->dFragT, h->dGwPart};
+                    h->dSensU0, h->dSensU, h->dSensX, h->dPSensXr, h->dPSensUr, h->dPSensF, h->dVjp, h->dVjpSt, h->dVjpAct, h->dFragT, h->dGwPart, h->dTrain};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &sl : h->slot) {
@@ -328,6 +328,8 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
     (void)hipMemsetAsync(h->dAct, 0, B * (size_t)act_pitch(cfg->N), h->stream);
     (void)hipMemsetAsync(h->dRelay, 0, B * 4 * 8, h->stream);
     (void)hipMemsetAsync(h->dQctr, 0, 256, h->stream);
+    ALLOC(h->dTrain, TRAIN_WS_BYTES);
+    (void)hipMemsetAsync(h->dTrain, 0, 64, h->stream);
     {
         double kc[KC_HOST];
         fill_kc(h->P, kc);

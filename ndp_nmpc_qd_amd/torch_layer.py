@@ -32,6 +32,9 @@ single-neighbour siblings) are the same four with K neighbours per instance, oth
 (BatchedNMPC.downwash_multi_device) into the external-force step, differentiated by BatchedNMPC.downwash_multi_vjp_device /
 downwash_multi_jvp_device.
 
+DownwashAdamSN (at the end of this file) is the optimiser those weight gradients were built for: the reference's full-batch Adam and
+spectral-norm cap as one launch per step (BatchedNMPC.mlp_adam_sn_device).
+
 control_step_tunable / TunableControlStep (behind them) differentiate the controller's own numbers -- the cost weights Qd, Rd and the mass --
 by the same adjoint (BatchedNMPC.set_model, step_vjp_device with gmodel).
 """
@@ -806,3 +809,85 @@ class TunableControlStep(torch.nn.Module):
 
     def forward(self, x0, xr, ur, f=None):
         return control_step_tunable(self.engine, x0, xr, ur, self.Qd, self.Rd, mass=self.mass, f=f)
+
+
+# ---------------------------------------------------------------------------------------------- training the downwash network
+# The reference's loop (nn_train.py:129-157 with --SN): full-batch Adam, then every weight matrix scaled back onto a spectral-norm cap.  On the
+# device both are ONE launch behind the weight gradient (BatchedNMPC.mlp_adam_sn_device): no singular value travels to the host.
+
+class DownwashAdamSN(torch.optim.Optimizer):
+    """torch.optim.Adam (its defaults: no weight decay, no amsgrad) followed by the spectral-norm cap `sn` on the four weight matrices
+    (sn = 0: no cap), for ONE parameter: the downwash network's 17 859 float32 values in blob order on the engine's device -- the tensor
+    handed to downwash(..., weights=w).  The reference's options: lr 1e-4, betas (0.9, 0.999), eps 1e-8 (nn_train.py:90,132).
+
+    The state lives in tensors on the parameter's device: m, v (float32 [17859]), step (int64 [1], advanced by the kernel), sigma (float64
+    [4]: the layers' norms after the last step) and info (int32 [4]: [0] the last step was skipped because its gradient was not finite,
+    [1] bitmask of the layers it scaled); state_dict() / load_state_dict() carry them with their dtypes.  step() enqueues one call on the
+    current stream and never synchronises; on torch's default stream, which the C interface cannot name, the call goes on the engine's
+    own stream between two waits, as every layer of this module does it.  install=True: the engine's network is the updated parameter
+    behind every step (also a skipped one), and the next downwash(weights=w) does not install it again.
+
+    The kernel writes through the parameter's pointer, which does not move its version counter: step() bumps it, so that a following
+    forward can tell the weights have changed."""
+
+    _DTYPES = {"m": torch.float32, "v": torch.float32, "step": torch.int64, "sigma": torch.float64, "info": torch.int32}
+
+    def __init__(self, params, engine, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, sn=0.0, install=True):
+        if isinstance(params, torch.Tensor):
+            params = [params]
+        if not (lr == lr and abs(lr) != float("inf")):
+            raise ValueError(f"DownwashAdamSN: lr = {lr} is not finite")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"DownwashAdamSN: betas = {betas} must lie in [0, 1)")
+        if not eps > 0.0:
+            raise ValueError(f"DownwashAdamSN: eps = {eps} must be positive")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, sn=float(sn), install=bool(install)))
+        ps = [p for g in self.param_groups for p in g["params"]]
+        if len(ps) != 1 or ps[0].numel() != 17859 or ps[0].dim() != 1 or ps[0].dtype != torch.float32 or not ps[0].is_contiguous():
+            raise ValueError("DownwashAdamSN: expected ONE contiguous float32 parameter of 17859 values (the network's blob)")
+        self.engine = engine
+
+    def _state_of(self, p):
+        st = self.state[p]
+        if not st:
+            st["m"], st["v"] = torch.zeros_like(p, memory_format=torch.preserve_format), torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["step"] = torch.zeros(1, dtype=torch.int64, device=p.device)
+            st["sigma"] = torch.zeros(4, dtype=torch.float64, device=p.device)
+            st["info"] = torch.zeros(4, dtype=torch.int32, device=p.device)
+        return st
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        group = self.param_groups[0]
+        p = group["params"][0]
+        if p.grad is None:
+            return loss
+        g = p.grad
+        if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape:
+            raise ValueError("DownwashAdamSN: the gradient must be a contiguous float32 tensor of the parameter's shape")
+        st = self._state_of(p)
+        eng = self.engine
+        stream, default = _cuda_stream(p)
+        eng.mlp_adam_sn_device(p.detach(), g, st["m"], st["v"], st["step"], lr=group["lr"], betas=group["betas"], eps=group["eps"],
+                               sn=group["sn"], sigma=st["sigma"], info=st["info"], install=group["install"], stream=stream)
+        if default:
+            eng.synchronize()
+        torch.autograd.graph.increment_version(p)
+        if group["install"]:                 # what _install_weights would note: the parameter as it now is IS the engine's network
+            eng._mlp_installed, eng._mlp_installed_tensor = (p.data_ptr(), p._version), p
+        return loss
+
+    def load_state_dict(self, state_dict):
+        """torch's loader casts floating-point state to the parameter's dtype (sigma is float64) and leaves `step` where it was saved: the
+        five tensors are taken from `state_dict` again, as copies on the parameter's device with their own dtypes."""
+        super().load_state_dict(state_dict)
+        ps = [p for g in self.param_groups for p in g["params"]]
+        ids = [i for g in state_dict["param_groups"] for i in g["params"]]
+        for p, i in zip(ps, ids):
+            src = state_dict["state"].get(i)
+            if src:
+                self.state[p] = {k: torch.as_tensor(src[k]).detach().to(device=p.device, dtype=dt, copy=True) for k, dt in self._DTYPES.items()}
