@@ -722,6 +722,38 @@ int ndp_mlp_spectral_norms(ndp_handle *h, const float *blob, double *sigma4);
 int ndp_mlp_adam_sn_device(ndp_handle *h, void *d_w, const void *d_g, void *d_m, void *d_v, void *d_step, double lr, double beta1,
                            double beta2, double eps, double sn_cap, void *d_sigma, void *d_info, int install, void *stream);
 
+/* ---- The network on sample rows, and its fit (nn_train.py:99-108,131,142-147: x_train [n,6], y_train [n,3] cast to float32, nn.MSELoss,
+ * loss.backward(); nn_test.py / plot_pred_one_line: the network on plain grid rows).  No window, no gate, no engine batch shape: the data
+ * set is whatever the caller holds in device memory.
+ *   d_z [R][6] fp32 : the network's input rows, the caller's (other - ego)[0:6] already in float32;  d_y [R][3] fp32 : the labels;
+ *   d_rw [R] fp32   : per-row weights, NULL = every weight 1;
+ *   d_index int32 [M] : output / batch row m uses data row index[m]; NULL = index[m] = m (then M <= R).  An index < 0 or >= R is an EMPTY
+ *     slot: never read, contributes nothing, its d_f row is exactly 0.  An index listed twice counts twice.  Fixed-size mini-batches pad
+ *     their tail with -1.
+ * The weights are the installed ones (ndp_set_mlp_weights / _device).
+ * ndp_mlp_rows_device: d_f [M][3] fp32 = the network's output, each row bit-equal to what ndp_downwash_device returns for the same six
+ *   fp32 inputs (a row with a non-finite input: NaN).
+ * ndp_mlp_fit_rows_device: with e = f - y in fp32 (one rounding per component),
+ *   d_loss fp64 [1] = scale * sum_m rw (e0^2 + e1^2 + e2^2): each square exact in fp64, products with rw and scale and all sums in fp64
+ *     (scale = 1 / (3 n) gives nn.MSELoss).  Each workgroup writes a partial sum to a workspace; a reduce in fixed order writes d_loss.
+ *   d_gw fp32 [NDP_MLP_NPARAM], blob order, OVERWRITTEN = d loss / d weights: the backward pass of ndp_downwash_vjp_device (the forward
+ *     recomputed once in the kernel, its own ReLU masks, the capped ReLU's derivative 0 on both flat branches, exact fp32 products) with
+ *     the upstream d4[c] = fp32(2 scale rw e[c]), the factor formed in fp64 and rounded once.  Per-workgroup partials, a fixed-order reduce,
+ *     no atomics: two calls give identical bits.  NULL: loss only, none of the backward pass runs.
+ *   d_f fp32 [M][3], NULL allowed: the prediction the loss was formed from.
+ *   d_info int32 [2], NULL allowed: rows used, rows skipped.  A row is skipped when its z, y, rw, prediction or residual is not finite: it
+ *     contributes nothing to the loss or to d_gw.  Every other non-empty row is used (a row with rw = 0 too).  Empty slots are neither.
+ *   groups: the number of workgroups (128 rows each per round, a grid-stride loop covers the rest); 0 = the library's choice,
+ *     min(ceil(M / 128), NDP_FIT_MAX_GROUPS); 1..NDP_FIT_MAX_GROUPS forces that count.  It changes results through summation order only.
+ * The partials live in a workspace of the handle of their own (allocated by ndp_create, so the calls may be captured): fit calls on one
+ * handle must be ordered against each other.  Nothing else of the handle is written.
+ * -1: NULL handle, d_z NULL, d_y NULL (fit); -6: weights never set; -2 with a reason in ndp_last_error and nothing launched: R < 1, M < 1,
+ * R or M >= 2^31, d_index NULL with M > R, groups outside 0..NDP_FIT_MAX_GROUPS, d_loss, d_gw and d_f all NULL (fit), d_f NULL (rows). */
+#define NDP_FIT_MAX_GROUPS 256
+int ndp_mlp_rows_device(ndp_handle *h, const void *d_z, const void *d_index, int64_t R, int64_t M, void *d_f, void *stream);
+int ndp_mlp_fit_rows_device(ndp_handle *h, const void *d_z, const void *d_y, const void *d_rw, const void *d_index, int64_t R, int64_t M,
+                            double scale, int groups, void *d_loss, void *d_gw, void *d_f, void *d_info, void *stream);
+
 /* ---- Peer windows: the neighbour exchange across GPUs as publish / subscribe over xGMI.
  * Replaces the PredXU topic between processes: the publisher is nmpc_node.py:116-133,229-230 (`nmpc_x_ref`, 21x10 float64, a NEW
  * message every control tick), the subscriber ndp_nmpc_leader_node.py:40,60-76 (consumes the latest one).  One process per GPU:

@@ -20,6 +20,7 @@ ABI_VERSION = 9          # include/ndp_nmpc.h: NDP_ABI_VERSION (checked against 
 TICK_ESTIMATE, TICK_WANT_U0, TICK_T_UNIFORM = 1, 2, 4
 FORM_GATE, FORM_COMPENSATE = 1, 2       # include/ndp_nmpc.h: NDP_FORM_*
 MAX_NEIGH = 8                           # include/ndp_nmpc.h: NDP_MAX_NEIGH (neighbours per vehicle of the *_multi entry points)
+FIT_MAX_GROUPS = 256                    # include/ndp_nmpc.h: NDP_FIT_MAX_GROUPS (workgroups of ndp_mlp_fit_rows_device)
 
 
 class NdpCfg(C.Structure):
@@ -65,6 +66,7 @@ EXPORTS = [
     "ndp_rollout_formation_multi_device",
     "ndp_downwash_multi_vjp_device", "ndp_downwash_multi_jvp_device",
     "ndp_mlp_spectral_norms_device", "ndp_mlp_spectral_norms", "ndp_mlp_adam_sn_device",
+    "ndp_mlp_rows_device", "ndp_mlp_fit_rows_device",
 ]
 
 _lib = None
@@ -223,6 +225,8 @@ def load():
     lib.ndp_mlp_spectral_norms_device.argtypes = [vp] * 4
     lib.ndp_mlp_spectral_norms.argtypes = [vp] * 3
     lib.ndp_mlp_adam_sn_device.argtypes = [vp] * 6 + [C.c_double] * 5 + [vp, vp, C.c_int, vp]
+    lib.ndp_mlp_rows_device.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp, vp]
+    lib.ndp_mlp_fit_rows_device.argtypes = [vp] * 5 + [C.c_int64, C.c_int64, C.c_double, C.c_int] + [vp] * 5
     lib.ndp_plant_step.argtypes = [vp, vp, vp, vp, C.c_double, C.c_int]
     lib.ndp_plant_step_device.argtypes = [vp, vp, vp, vp, C.c_double, C.c_int, vp]
     _lib = lib

@@ -898,6 +898,49 @@ class BatchedNMPC:
         if install:
             self._mlp_installed = None      # (torch_layer.DownwashAdamSN notes what IT installed, behind this call)
 
+    # ---- the network on sample rows (ndp_mlp_rows_device, ndp_mlp_fit_rows_device): no window, no gate, any number of rows
+    @staticmethod
+    def _rows_shape(z, index, f):
+        """(R, M) of a row call: z [R,6]; M from index [M], else from f [M,3], else R."""
+        R = int(z.shape[0]) if z is not None and z.dim() == 2 else 0
+        M = int(index.shape[0]) if index is not None else int(f.shape[0]) if f is not None else R
+        return R, M
+
+    def mlp_rows_device(self, z, f, index=None, stream=None):
+        """Enqueues the installed network on the float32 CUDA rows z [R,6] on `stream` (ndp_mlp_rows_device; include/ndp_nmpc.h):
+        f [M,3] float32, row m from data row index[m] (int32 CUDA [M]; None: row m, M <= R).  An index < 0 or >= R is an empty slot: never
+        read, its f row exactly 0.  Each row is bit-equal to downwash_device's for the same six float32 inputs.  The engine's state is
+        not written.  stream None or torch's default stream: as downwash_vjp_device."""
+        import torch
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        R, M = self._rows_shape(z, index, f)
+        d = self._dptr
+        self._check(self._lib.ndp_mlp_rows_device(self._h, d(z, torch.float32, (R, 6)), d(index, torch.int32, (M,)), R, M,
+                                                  d(f, torch.float32, (M, 3)), self._stream(stream)), "ndp_mlp_rows_device")
+
+    def mlp_fit_rows_device(self, z, y, scale, index=None, row_weight=None, groups=0, loss=None, gw=None, f=None, info=None, M=None,
+                            stream=None):
+        """Enqueues the fused loss and weight gradient of the installed network on sample rows on `stream` (ndp_mlp_fit_rows_device;
+        include/ndp_nmpc.h): z [R,6], y [R,3], row_weight [R] (None: 1) float32 CUDA; index int32 CUDA [M] as in mlp_rows_device (None:
+        the first M rows; M defaults to R).  Outputs (CUDA tensors the caller allocates, None = not computed, not all of loss, gw, f):
+        loss float64 [1] = scale * sum rw |f - y|^2 (scale = 1 / (3 n): nn.MSELoss); gw [17859] float32 in blob order, overwritten;
+        f [M,3] float32, the prediction; info int32 [2], rows used and rows skipped (non-finite z, y, rw or prediction).  groups: the
+        number of workgroups, 0 = the library's choice, 1.._lib.FIT_MAX_GROUPS forces it (summation order only).  Two calls give
+        identical bits.  Its workspace is its own; fit calls on one engine must be ordered against each other.  The engine's state is
+        not written.  stream None or torch's default stream: as downwash_vjp_device."""
+        import torch
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        R, Mi = self._rows_shape(z, index, f)
+        M = Mi if M is None else int(M)
+        d = self._dptr
+        self._check(self._lib.ndp_mlp_fit_rows_device(
+            self._h, d(z, torch.float32, (R, 6)), d(y, torch.float32, (R, 3)), d(row_weight, torch.float32, (R,)),
+            d(index, torch.int32, (M,)), R, M, float(scale), int(groups), d(loss, torch.float64, (1,)),
+            d(gw, torch.float32, (_lib.MLP_NPARAM,)), d(f, torch.float32, (M, 3)), d(info, torch.int32, (2,)), self._stream(stream)),
+            "ndp_mlp_fit_rows_device")
+
     def device_iterate(self):
         """The engine's iterate as CUDA tensor views (no copy): (X [B,N+1,10], U [B,N,4]) float64 (ndp_device_iterate_x / _u); valid once
         the step's stream has reached them; the next step overwrites them."""

@@ -12,12 +12,15 @@
 //   tick.hip         the control tick's host side (ndp_tick*); no kernel: compiled for the host only
 //   mlp_vjp.hip      the downwash network's backward pass (ndp_downwash_vjp_device, ndp_downwash_multi_vjp_device) and its weights set from
 //                    device memory
+//   mlp_fit.hip      the downwash network on sample rows: the forward (ndp_mlp_rows_device) and the fit's loss and weight gradient in one
+//                    pass (ndp_mlp_fit_rows_device); shares mlp_vjp.hip's device functions (mlp_vjp_dev.hpp) and the text of its rounds
+//                    (mlp_vjp_back.inc, mlp_vjp_part.inc)
 //   mlp_jvp.hip      the downwash network's forward mode (ndp_downwash_jvp_device, ndp_downwash_multi_jvp_device)
 //   mlp_train.hip    the downwash network's optimiser step: Adam + spectral-norm cap in one launch (ndp_mlp_adam_sn_device), the layers'
 //                    spectral norms (ndp_mlp_spectral_norms*)
 //   exchange.hip     peer-mapped windows (ndp_peer_*), the RCCL exchange (ndp_xchg_*) and the remote tick one control period ahead
 // A kernel sits with the host code that launches it; device code that two units' kernels inline is a header (mlp_tile.hpp, ref_point.hpp,
-// tick_wave.hpp), and so are the argument blocks the host fills (kern_args.hpp).
+// tick_wave.hpp, mlp_vjp_dev.hpp), and so are the argument blocks the host fills (kern_args.hpp).
 // The functions declared below are NDP_HIDDEN: the library exports the C-ABI of include/ndp_nmpc.h and nothing more.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -73,6 +76,9 @@ struct ndp_handle {
     // dFrag by both ndp_set_mlp_weights forms); ndp_downwash_vjp_device's per-workgroup partial weight gradients [mlp_vjp_groups][NDP_MLP_NPARAM]
     // (ndp_downwash_multi_vjp_device shares them: it never launches more workgroups than that)
     float *dFragT = nullptr, *dGwPart = nullptr;
+    // ndp_mlp_fit_rows_device's partials, a workspace of its own (its size does not follow the batch shape): gradients
+    // [NDP_FIT_MAX_GROUPS][NDP_MLP_NPARAM] fp32 | losses [NDP_FIT_MAX_GROUPS] fp64 | rows used, skipped [NDP_FIT_MAX_GROUPS][2] int32
+    float *dFitPart = nullptr;
     // mlp_train.hip: word 0 = the ticket of ndp_mlp_adam_sn_device's four workgroups (0 between launches), then 4 doubles and a blob's
     // floats: the staging of the host form ndp_mlp_spectral_norms (TRAIN_WS_BYTES)
     unsigned long long *dTrain = nullptr;
@@ -171,6 +177,7 @@ static inline int mlp_vjp_groups(const ndp_handle *h)
     return ngroups < VJ_MAX_GROUPS ? ngroups : VJ_MAX_GROUPS;
 }
 
+enum { FIT_WS_BYTES = NDP_FIT_MAX_GROUPS * (17859 * 4 + 8 + 2 * 4) };   // dFitPart
 enum { TRAIN_WS_BYTES = 64 + 4 * 8 + 17859 * 4 };   // dTrain: ticket (64 bytes of its own) | sigma [4] fp64 | blob [NDP_MLP_NPARAM] fp32
 
 enum { TICK_ESTIMATE = NDP_TICK_ESTIMATE, TICK_WANT_U0 = NDP_TICK_WANT_U0, TICK_T_UNIFORM = NDP_TICK_T_UNIFORM };
@@ -279,6 +286,8 @@ NDP_HIDDEN int tick_step_enqueue(ndp_handle *h, hipStream_t s, const double *x_o
 // mlp_vjp.hip
 NDP_HIDDEN void make_fragments_t(const float *blob, float *frt);
 NDP_HIDDEN hipError_t mlp_vjp_prepare(void);
+// mlp_fit.hip
+NDP_HIDDEN hipError_t mlp_fit_prepare(void);
 // exchange.hip
 NDP_HIDDEN int peer_mapped(const void *p);
 NDP_HIDDEN void launch_pack_pv_list(const double *base, size_t pitch, int np1, double *pv, size_t B, hipStream_t s);

@@ -206,7 +206,7 @@ int ndp_destroy(ndp_handle *h)
     h->pool.reset();
     void *ptrs[] = {h->dForceAB[0], h->dForceAB[1], h->dProto, h->dRingX, h->dTraj, h->dTables, h->dStamps, h->dRelay, h->dThr, h->sThr, h->dKC, h->dForce, h->dFrag,
                     h->dIn, h->dOut, h->sdbg, h->dQctr, h->dQids, h->dTickIndex, h->dTickThrust, h->dAct,
-                    h->dSensU0, h->dSensU, h->dSensX, h->dPSensXr, h->dPSensUr, h->dPSensF, h->dVjp, h->dVjpSt, h->dVjpAct, h->dFragT, h->dGwPart, h->dTrain};
+                    h->dSensU0, h->dSensU, h->dSensX, h->dPSensXr, h->dPSensUr, h->dPSensF, h->dVjp, h->dVjpSt, h->dVjpAct, h->dFragT, h->dGwPart, h->dFitPart, h->dTrain};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &sl : h->slot) {
@@ -330,6 +330,7 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
     (void)hipMemsetAsync(h->dQctr, 0, 256, h->stream);
     ALLOC(h->dTrain, TRAIN_WS_BYTES);
     (void)hipMemsetAsync(h->dTrain, 0, 64, h->stream);
+    ALLOC(h->dFitPart, FIT_WS_BYTES);      // (every entry a call reads is written by that call: no memset)
     {
         double kc[KC_HOST];
         fill_kc(h->P, kc);
@@ -376,6 +377,7 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
     const int lds_bytes = (int)(per_wave_bytes * h->waves);
     if ((e = mlp_prepare()) != hipSuccess) return fail("hipFuncSetAttribute(mlp_kernel)", e);
     if ((e = mlp_vjp_prepare()) != hipSuccess) return fail("hipFuncSetAttribute(mlp_vjp_kernel)", e);
+    if ((e = mlp_fit_prepare()) != hipSuccess) return fail("hipFuncSetAttribute(mlp_fit_rows_kernel)", e);
     if ((e = mlp_multi_prepare()) != hipSuccess) return fail("hipFuncSetAttribute(mlp_multi_kernel)", e);
     const char *what = nullptr;
     if ((e = rti_set_lds(false, lds_bytes, &what)) != hipSuccess) return fail(what, e);      // (the sensitivity kernels: ndp_sens_enable)

@@ -35,6 +35,10 @@ downwash_multi_jvp_device.
 DownwashAdamSN (at the end of this file) is the optimiser those weight gradients were built for: the reference's full-batch Adam and
 spectral-norm cap as one launch per step (BatchedNMPC.mlp_adam_sn_device).
 
+downwash_rows / downwash_fit_rows (behind it) are the network on plain sample rows [R,6] float32, the form the reference trains and
+evaluates on: the forward without autograd, and the weighted MSE whose forward is ONE fused call that also leaves the weight gradient
+(BatchedNMPC.mlp_rows_device / mlp_fit_rows_device); mini-batches are index lists into a resident data set.
+
 control_step_tunable / TunableControlStep (behind them) differentiate the controller's own numbers -- the cost weights Qd, Rd and the mass --
 by the same adjoint (BatchedNMPC.set_model, step_vjp_device with gmodel).
 """
@@ -891,3 +895,61 @@ class DownwashAdamSN(torch.optim.Optimizer):
             src = state_dict["state"].get(i)
             if src:
                 self.state[p] = {k: torch.as_tensor(src[k]).detach().to(device=p.device, dtype=dt, copy=True) for k, dt in self._DTYPES.items()}
+
+
+# ---------------------------------------------------------------------------------------------- the network on sample rows
+# The form the reference trains and evaluates on (nn_train.py:99-108,131,142-147; nn_test.py's force-field grids): flat rows x [n,6],
+# y [n,3] in float32, no prediction window, no gate, any n.  Any engine serves (its batch shape plays no part); mini-batches are index lists.
+
+def downwash_rows(engine, z, weights=None, index=None):
+    """f [M,3] float32 = the engine's network on the float32 CUDA rows z [R,6] (BatchedNMPC.mlp_rows_device): row m from data row
+    index[m] (int32 [M]; None: every row in order); an index < 0 or >= R gives a row of exact zeros.  `weights`, when given, is
+    installed first as downwash does it.  NO autograd: the result carries no graph, whatever requires grad -- this is for evaluation sets
+    and the reference's force-field grids; fit through downwash_fit_rows."""
+    zd = z.detach()
+    stream, default = _cuda_stream(zd)
+    if default:
+        stream.synchronize()
+    _install_weights(engine, weights, stream)
+    f = torch.empty((zd.shape[0] if index is None else index.shape[0], 3), dtype=torch.float32, device=zd.device)
+    engine.mlp_rows_device(zd, f, index=index, stream=stream)
+    if default:
+        engine.synchronize()
+    return f
+
+
+class DownwashFitRowsFunction(torch.autograd.Function):
+    """forward(weights, engine, z, y, index, row_weight, scale, groups, info) -> the float64 scalar loss, by the ONE fused call that
+    also leaves the weight gradient (BatchedNMPC.mlp_fit_rows_device), which is kept; backward: that gradient times the upstream."""
+
+    @staticmethod
+    def forward(ctx, weights, engine, z, y, index, row_weight, scale, groups, info):
+        stream, default = _cuda_stream(z)
+        if default:
+            stream.synchronize()
+        _install_weights(engine, weights, stream)
+        loss = torch.empty(1, dtype=torch.float64, device=z.device)
+        gw = torch.empty(17859, dtype=torch.float32, device=z.device) if ctx.needs_input_grad[0] else None
+        engine.mlp_fit_rows_device(z, y, scale, index=index, row_weight=row_weight, groups=groups, loss=loss, gw=gw, info=info, stream=stream)
+        if default:
+            engine.synchronize()
+        ctx.gw = gw
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        gw = ctx.gw
+        return (None if gw is None else gw * g_loss.to(gw.dtype),) + (None,) * 8
+
+
+def downwash_fit_rows(engine, z, y, weights, index=None, row_weight=None, scale=None, groups=0, info=None):
+    """The float64 scalar loss scale * sum_m rw |net(z[index[m]]) - y[index[m]]|^2 of the engine's network on sample rows, differentiable
+    in `weights` only (a float32 CUDA tensor / nn.Parameter of 17 859 in blob order, installed first as downwash does it): loss and weight
+    gradient come out of ONE fused call in the forward, the backward multiplies the kept gradient by its upstream.  z [R,6], y [R,3],
+    row_weight [R] (None: 1) float32 CUDA, none of them differentiated; index int32 [M] (None: every row) -- an index < 0 or >= R is an
+    empty slot, an index listed twice counts twice, fixed-size mini-batches pad with -1.  scale None: 1 / (3 M), nn.MSELoss over M rows
+    (with padded mini-batches pass 1 / (3 M_real)).  groups: BatchedNMPC.mlp_fit_rows_device's.  info: an int32 CUDA [2] tensor that
+    receives rows used / rows skipped (non-finite rows add nothing)."""
+    M = z.shape[0] if index is None else index.shape[0]
+    return DownwashFitRowsFunction.apply(weights, engine, z.detach(), y.detach(), index, None if row_weight is None else row_weight.detach(),
+                                         1.0 / (3.0 * M) if scale is None else float(scale), int(groups), info)
