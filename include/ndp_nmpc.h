@@ -585,6 +585,51 @@ int ndp_plant_step_device(ndp_handle *h, void *d_x, const void *d_u, const void 
  * enqueued back to back on the stream; nothing returns to the host in between, nothing is synchronised. */
 int ndp_rollout_device(ndp_handle *h, int ticks, double t0, double dt_tick, int substeps, void *d_x, void *d_log, void *stream);
 
+/* ---- f4, the plant over a GIVEN input sequence, with reverse and forward mode: B vehicles simulated over `ticks` ticks of inputs and
+ * forces in ONE launch (one lane per vehicle, the state in registers from the first tick to the last) instead of one ndp_plant_step_device
+ * launch and one copy into a log per tick.  What shooting methods and system identification from logged flights call, and the link of the
+ * closed loop the control step's and the downwash network's derivatives chain with.  Mass and gravity are the handle's (cfg).
+ * ndp_plant_rollout_device:
+ *   d_x0 [B][10] fp64                 the initial states
+ *   d_u  [ticks][B][4] fp64           the inputs, one per tick
+ *   d_f  [ticks][B][3] fp64 or NULL   the external forces, each HELD over its tick as ndp_plant_step_device holds it; NULL = none
+ *   d_xs [ticks][B][10] fp64          receives the state after every tick
+ *   Row k of d_xs is BIT-EQUAL to what k + 1 successive ndp_plant_step_device calls give with the same dt and substeps (RK4 with
+ *   `substeps` over dt, the quaternion renormalised once per tick), with d_f and with NULL.  d_x0 may be any tick's slot of d_xs (a lane
+ *   reads its own row first and writes its own rows only).  Nothing of the engine's state is written and nothing is allocated: the call can
+ *   be captured into a graph, and calls need no ordering against each other.
+ *   -1: NULL handle, d_x0, d_u or d_xs; -2 with a reason in ndp_last_error: ticks < 1, substeps outside 1..NDP_PLANT_MAX_SUBSTEPS.  A
+ *   refused call enqueues nothing (so for the two calls below). */
+#define NDP_PLANT_MAX_SUBSTEPS 16
+int ndp_plant_rollout_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_u, const void *d_f,
+                             void *d_xs, void *stream);
+/* Reverse mode of the call above.  For L = sum over k of <d_gxs[k], xs[k]> it writes, each NULL = not computed, not all three NULL:
+ *   d_gx0 [B][10] fp64         dL/dx0
+ *   d_gu  [ticks][B][4] fp64   dL/du
+ *   d_gf  [ticks][B][3] fp64   dL/df -- also with d_f NULL (the derivative at f = 0; bit-equal to the call with an all-zero d_f)
+ * Inputs: d_x0, d_u, d_f as the forward took them; d_xs [ticks][B][10] the forward's log, required -- tick k restarts from xs[k-1] (x0 at
+ * k = 0), the chain is never re-integrated from its start; d_gxs [ticks][B][10] fp64 the upstream gradient of every logged state,
+ * required (a terminal-only loss passes zeros elsewhere).  Outputs are OVERWRITTEN and must not alias an input.
+ * The derivative is that of the arithmetic performed: the RK4 stages with u and the force held over the tick, then q / |q| applied once per
+ * tick to the un-normalised end state -- so a d_gxs[k] parallel to the quaternion of xs[k] moves nothing.  That end state and the substeps'
+ * start states are recomputed from the tick's input state (O(substeps^2) substeps per tick, nothing stored).  One lane per vehicle, no
+ * atomics, no workspace: two calls are bit-identical, an output does not depend on which others are asked for, and calls need no ordering
+ * against each other.  -1: NULL handle, d_x0, d_u, d_xs or d_gxs; -2: as the forward call, or no output asked for. */
+int ndp_plant_rollout_vjp_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_u, const void *d_f,
+                                 const void *d_xs, const void *d_gxs, void *d_gx0, void *d_gu, void *d_gf, void *stream);
+/* Forward mode of ndp_plant_rollout_device, T = n_tan directions (1..NDP_JVP_MAX_TANGENTS) in one call.  Directions, each NULL = 0, not
+ * all three NULL:
+ *   d_tx0 [B][T][10] fp64, d_tu [ticks][B][T][4] fp64, d_tf [ticks][B][T][3] fp64
+ * Outputs:
+ *   d_dxs [ticks][B][T][10] fp64, required: the first-order change of every logged state
+ *   d_xs_check [ticks][B][10] fp64, optional: the recomputed primal, bit-equal to ndp_plant_rollout_device's log
+ * No log is needed: the primal is carried along.  One lane per (vehicle, direction): T directions in one call give what T calls give, bit
+ * for bit.  No atomics, no workspace, nothing of the engine's state written.  -1: NULL handle, d_x0 or d_u; -2: as the forward call,
+ * n_tan out of range, no tangent given, d_dxs NULL. */
+int ndp_plant_rollout_jvp_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_u, const void *d_f,
+                                 int n_tan, const void *d_tx0, const void *d_tu, const void *d_tf, void *d_dxs, void *d_xs_check,
+                                 void *stream);
+
 /* ---- f4, the formation form (plant = a1 dynamics + downwash model): the downwash force the neighbour's ACTUAL state
  * puts on the ACTUAL vehicle, and the closed loop around it -- the experiment the downwash prediction is for (the reference has no
  * simulator; the force model is its own network, dnwash_nn_est/downwash_nn.py:22-28, behind the gate of ndp_nmpc_leader_node.py:65-68).

@@ -19,6 +19,7 @@ QP_AUTO, QP_IPM_ALWAYS = 0, 1
 ABI_VERSION = 9          # include/ndp_nmpc.h: NDP_ABI_VERSION (checked against the loaded library in load())
 TICK_ESTIMATE, TICK_WANT_U0, TICK_T_UNIFORM = 1, 2, 4
 FORM_GATE, FORM_COMPENSATE = 1, 2       # include/ndp_nmpc.h: NDP_FORM_*
+PLANT_MAX_SUBSTEPS = 16                 # include/ndp_nmpc.h: NDP_PLANT_MAX_SUBSTEPS (ndp_plant_rollout*_device)
 MAX_NEIGH = 8                           # include/ndp_nmpc.h: NDP_MAX_NEIGH (neighbours per vehicle of the *_multi entry points)
 FIT_MAX_GROUPS = 256                    # include/ndp_nmpc.h: NDP_FIT_MAX_GROUPS (workgroups of ndp_mlp_fit_rows_device)
 
@@ -67,6 +68,7 @@ EXPORTS = [
     "ndp_downwash_multi_vjp_device", "ndp_downwash_multi_jvp_device",
     "ndp_mlp_spectral_norms_device", "ndp_mlp_spectral_norms", "ndp_mlp_adam_sn_device",
     "ndp_mlp_rows_device", "ndp_mlp_fit_rows_device",
+    "ndp_plant_rollout_device", "ndp_plant_rollout_vjp_device", "ndp_plant_rollout_jvp_device",
 ]
 
 _lib = None
@@ -229,6 +231,9 @@ def load():
     lib.ndp_mlp_fit_rows_device.argtypes = [vp] * 5 + [C.c_int64, C.c_int64, C.c_double, C.c_int] + [vp] * 5
     lib.ndp_plant_step.argtypes = [vp, vp, vp, vp, C.c_double, C.c_int]
     lib.ndp_plant_step_device.argtypes = [vp, vp, vp, vp, C.c_double, C.c_int, vp]
+    lib.ndp_plant_rollout_device.argtypes = [vp, C.c_int, C.c_double, C.c_int] + [vp] * 5
+    lib.ndp_plant_rollout_vjp_device.argtypes = [vp, C.c_int, C.c_double, C.c_int] + [vp] * 9
+    lib.ndp_plant_rollout_jvp_device.argtypes = [vp, C.c_int, C.c_double, C.c_int, vp, vp, vp, C.c_int] + [vp] * 6
     _lib = lib
     return lib
 

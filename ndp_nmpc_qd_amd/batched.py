@@ -383,6 +383,61 @@ class BatchedNMPC:
             self._h, int(ticks), float(t0), float(dt), int(substeps), self._dptr(x, torch.float64, (self.B, 10)),
             self._dptr(log, torch.float64, (int(ticks), self.B, 10)), self._stream(stream)), "ndp_rollout_device")
 
+    # ---- f4, the plant over a given input sequence, with reverse and forward mode
+    def plant_rollout_device(self, x0, u, xs, f=None, dt=CP.ts_nmpc, substeps=4, stream=None):
+        """The plant over an input sequence in one launch, enqueued on `stream` with no synchronisation (ndp_plant_rollout_device;
+        include/ndp_nmpc.h): x0[B,10], u[ticks,B,4], f[ticks,B,3] or None (each force held over its tick), all float64 CUDA tensors;
+        xs[ticks,B,10] receives the state after every tick, row k bit-equal to k + 1 ndp_plant_step_device calls.  x0 may be a slot of
+        xs.  ticks is read from u.  The engine's state is not written."""
+        import torch
+        B, K = self.B, self._plant_ticks(u, "plant_rollout_device")
+        d = self._dptr
+        self._check(self._lib.ndp_plant_rollout_device(
+            self._h, K, float(dt), int(substeps), d(x0, torch.float64, (B, 10)), d(u, torch.float64, (K, B, 4)),
+            d(f, torch.float64, (K, B, 3)), d(xs, torch.float64, (K, B, 10)), self._stream(stream)), "ndp_plant_rollout_device")
+
+    def plant_rollout_vjp_device(self, x0, u, xs, gxs, f=None, gx0=None, gu=None, gf=None, dt=CP.ts_nmpc, substeps=4, stream=None):
+        """Enqueues the backward pass of plant_rollout_device on `stream` (ndp_plant_rollout_vjp_device; include/ndp_nmpc.h): x0, u, f as
+        the forward took them, xs[ticks,B,10] its log, gxs[ticks,B,10] the gradient of every logged state.  Outputs (None = not computed,
+        not all None), overwritten, float64: gx0[B,10], gu[ticks,B,4], gf[ticks,B,3] (also with f None: the derivative at f = 0).  The
+        derivative of the arithmetic performed: force held over the tick, quaternion renormalised once per tick.  No workspace; two calls
+        are bit-identical."""
+        import torch
+        B, K = self.B, self._plant_ticks(u, "plant_rollout_vjp_device")
+        d = self._dptr
+        self._check(self._lib.ndp_plant_rollout_vjp_device(
+            self._h, K, float(dt), int(substeps), d(x0, torch.float64, (B, 10)), d(u, torch.float64, (K, B, 4)),
+            d(f, torch.float64, (K, B, 3)), d(xs, torch.float64, (K, B, 10)), d(gxs, torch.float64, (K, B, 10)),
+            d(gx0, torch.float64, (B, 10)), d(gu, torch.float64, (K, B, 4)), d(gf, torch.float64, (K, B, 3)), self._stream(stream)),
+            "ndp_plant_rollout_vjp_device")
+
+    def plant_rollout_jvp_device(self, x0, u, dxs, f=None, tx0=None, tu=None, tf=None, n_tan=None, xs_check=None, dt=CP.ts_nmpc, substeps=4,
+                                 stream=None):
+        """Enqueues the forward mode of plant_rollout_device on `stream` (ndp_plant_rollout_jvp_device; include/ndp_nmpc.h).  Directions
+        (None = 0, not all None), float64: tx0[B,T,10], tu[ticks,B,T,4], tf[ticks,B,T,3].  Outputs: dxs[ticks,B,T,10], required;
+        xs_check[ticks,B,10], optional -- the primal, bit-equal to plant_rollout_device's log.  T (1..8) is n_tan when given, else read
+        from dxs.  T directions in one call equal T calls bit for bit.  No workspace; the engine's state is not written."""
+        import torch
+        B, K = self.B, self._plant_ticks(u, "plant_rollout_jvp_device")
+        if n_tan is None:
+            if not (isinstance(dxs, torch.Tensor) and dxs.dim() == 4):
+                raise ValueError("plant_rollout_jvp_device: dxs must be a [ticks,B,T,10] tensor")
+            n_tan = dxs.shape[2]
+        T = int(n_tan)
+        d = self._dptr
+        self._check(self._lib.ndp_plant_rollout_jvp_device(
+            self._h, K, float(dt), int(substeps), d(x0, torch.float64, (B, 10)), d(u, torch.float64, (K, B, 4)),
+            d(f, torch.float64, (K, B, 3)), T, d(tx0, torch.float64, (B, T, 10)), d(tu, torch.float64, (K, B, T, 4)),
+            d(tf, torch.float64, (K, B, T, 3)), d(dxs, torch.float64, (K, B, T, 10)), d(xs_check, torch.float64, (K, B, 10)),
+            self._stream(stream)), "ndp_plant_rollout_jvp_device")
+
+    @staticmethod
+    def _plant_ticks(u, who):
+        import torch
+        if not (isinstance(u, torch.Tensor) and u.dim() == 3 and u.shape[0] >= 1):
+            raise ValueError(f"{who}: u must be a [ticks,B,4] tensor with ticks >= 1")
+        return int(u.shape[0])
+
     # ---- f4, the formation form: the downwash acting on the plant
     def plant_force(self, x, other_index, gate=True, scale=1.0):
         """The downwash force on every vehicle from the plant states x[B,10] (ndp_plant_force; include/ndp_nmpc.h): vehicle v feels the

@@ -18,9 +18,11 @@
 //   mlp_jvp.hip      the downwash network's forward mode (ndp_downwash_jvp_device, ndp_downwash_multi_jvp_device)
 //   mlp_train.hip    the downwash network's optimiser step: Adam + spectral-norm cap in one launch (ndp_mlp_adam_sn_device), the layers'
 //                    spectral norms (ndp_mlp_spectral_norms*)
+//   plant_deriv.hip  the plant over a given input sequence and its derivatives (ndp_plant_rollout_device, ndp_plant_rollout_vjp_device,
+//                    ndp_plant_rollout_jvp_device); a tick's arithmetic is plant_dyn.hpp's, shared with rows.hip's plant_kernel
 //   exchange.hip     peer-mapped windows (ndp_peer_*), the RCCL exchange (ndp_xchg_*) and the remote tick one control period ahead
 // A kernel sits with the host code that launches it; device code that two units' kernels inline is a header (mlp_tile.hpp, ref_point.hpp,
-// tick_wave.hpp, mlp_vjp_dev.hpp), and so are the argument blocks the host fills (kern_args.hpp).
+// tick_wave.hpp, mlp_vjp_dev.hpp, plant_dyn.hpp), and so are the argument blocks the host fills (kern_args.hpp).
 // The functions declared below are NDP_HIDDEN: the library exports the C-ABI of include/ndp_nmpc.h and nothing more.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -8,6 +8,7 @@
 
 #include "host.hpp"
 #include "mlp_common.hpp"
+#include "plant_dyn.hpp"
 #include "ref_point.hpp"
 
 namespace ndp {
@@ -119,57 +120,18 @@ __global__ __launch_bounds__(256) void relay_reference_kernel(const double *__re
 }
 
 // ------------------------------------------------------------------------------------------ f4 kernel
-// plant: the OCP's own dynamics (nmpc_body_rate_ctl.py:147-158 + f/mass), RK4 substeps, quaternion renormalised
-__device__ __forceinline__ void plant_f(const double *x, const double *u, const double *acc, double *d)
-{
-    const double qw = x[6], qx = x[7], qy = x[8], qz = x[9];
-    d[0] = x[3]; d[1] = x[4]; d[2] = x[5];
-    d[3] = 2.0 * (qx * qz + qw * qy) * u[3] + acc[0];
-    d[4] = 2.0 * (qy * qz - qw * qx) * u[3] + acc[1];
-    d[5] = (1.0 - 2.0 * qx * qx - 2.0 * qy * qy) * u[3] + acc[2];
-    d[6] = (-u[0] * qx - u[1] * qy - u[2] * qz) * 0.5;
-    d[7] = (u[0] * qw + u[2] * qy - u[1] * qz) * 0.5;
-    d[8] = (u[1] * qw - u[2] * qx + u[0] * qz) * 0.5;
-    d[9] = (u[2] * qw + u[1] * qx - u[0] * qy) * 0.5;
-}
-
+// plant: the OCP's own dynamics, RK4 substeps, quaternion renormalised -- the tick's arithmetic is plant_tick (plant_dyn.hpp), shared
+// with the rollout over an input sequence (plant_deriv.hip), whose log rows are these results bit for bit
 __global__ __launch_bounds__(256) void plant_kernel(double *__restrict__ x, const double *__restrict__ u, const double *__restrict__ f,
                                                     double h, int sub, double inv_mass, double g, int B)
 {
     const int v = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (v >= B) return;
-    double xv[10], uv[4], acc[3] = {0.0, 0.0, -g};
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const double2 t = reinterpret_cast<const double2 *>(x)[(size_t)v * 5 + i];
-        xv[2 * i] = t.x; xv[2 * i + 1] = t.y;
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const double2 t = reinterpret_cast<const double2 *>(u)[(size_t)v * 2 + i];
-        uv[2 * i] = t.x; uv[2 * i + 1] = t.y;
-    }
-    if (f) { acc[0] = f[v * 3] * inv_mass; acc[1] = f[v * 3 + 1] * inv_mass; acc[2] = f[v * 3 + 2] * inv_mass - g; }
-    for (int s = 0; s < sub; ++s) {
-        double k1[10], k2[10], k3[10], k4[10], xs[10];
-        plant_f(xv, uv, acc, k1);
-#pragma unroll
-        for (int i = 0; i < 10; ++i) xs[i] = xv[i] + 0.5 * h * k1[i];
-        plant_f(xs, uv, acc, k2);
-#pragma unroll
-        for (int i = 0; i < 10; ++i) xs[i] = xv[i] + 0.5 * h * k2[i];
-        plant_f(xs, uv, acc, k3);
-#pragma unroll
-        for (int i = 0; i < 10; ++i) xs[i] = xv[i] + h * k3[i];
-        plant_f(xs, uv, acc, k4);
-#pragma unroll
-        for (int i = 0; i < 10; ++i) xv[i] += h / 6.0 * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]);
-    }
-    const double n = sqrt(xv[6] * xv[6] + xv[7] * xv[7] + xv[8] * xv[8] + xv[9] * xv[9]);
-#pragma unroll
-    for (int i = 6; i < 10; ++i) xv[i] /= n;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) reinterpret_cast<double2 *>(x)[(size_t)v * 5 + i] = make_double2(xv[2 * i], xv[2 * i + 1]);
+    double xv[10], uv[4];
+    plant_ld_row<5>(x + (size_t)v * 10, xv);
+    plant_ld_row<2>(u + (size_t)v * 4, uv);
+    plant_tick(xv, uv, f, (size_t)v * 3, h, sub, inv_mass, g);
+    plant_st_row<5>(x + (size_t)v * 10, xv);
 }
 
 // the formation rollout's worst status per vehicle: the first tick writes it, the later ones keep the larger value

@@ -41,8 +41,15 @@ evaluates on: the forward without autograd, and the weighted MSE whose forward i
 
 control_step_tunable / TunableControlStep (behind them) differentiate the controller's own numbers -- the cost weights Qd, Rd and the mass --
 by the same adjoint (BatchedNMPC.set_model, step_vjp_device with gmodel).
+
+plant_rollout / plant_step / plant_rollout_jvp (at the end of this file) are the plant: the rigid body over a given sequence of inputs and
+forces in one launch, differentiable in the initial state, the inputs and the forces (BatchedNMPC.plant_rollout_device,
+plant_rollout_vjp_device, plant_rollout_jvp_device).  plant_step is its one-tick case, the piece that chains with the control_step*
+Functions: u0 -> plant_step -> the next tick's x0, with the values ndp_plant_step_device gives bit for bit.
 """
 import torch
+
+from .params import nmpc_params as CP
 
 
 def _cuda_stream(t):
@@ -953,3 +960,98 @@ def downwash_fit_rows(engine, z, y, weights, index=None, row_weight=None, scale=
     M = z.shape[0] if index is None else index.shape[0]
     return DownwashFitRowsFunction.apply(weights, engine, z.detach(), y.detach(), index, None if row_weight is None else row_weight.detach(),
                                          1.0 / (3.0 * M) if scale is None else float(scale), int(groups), info)
+
+
+# ---------------------------------------------------------------------------------------------- the plant over an input sequence
+# The rigid body the closed-loop rollouts integrate (ndp_plant_step_device), over GIVEN inputs and forces: one launch for the whole
+# sequence, and the derivative of exactly that arithmetic -- each force held over its tick, the quaternion renormalised once per tick.
+
+class PlantRolloutFunction(torch.autograd.Function):
+    """forward(x0, engine, u, f, dt, substeps) -> xs [ticks,B,10] float64, the state after every tick (BatchedNMPC.plant_rollout_device);
+    backward: ONE BatchedNMPC.plant_rollout_vjp_device call on the saved log for the gradients of x0, u and f."""
+
+    @staticmethod
+    def forward(ctx, x0, engine, u, f, dt, substeps):
+        x0d, ud = x0.detach().contiguous(), u.detach().contiguous()
+        fd = None if f is None else f.detach().contiguous()
+        stream, default = _cuda_stream(x0d)
+        if default:
+            stream.synchronize()
+        xs = torch.empty((ud.shape[0], ud.shape[1], 10), dtype=torch.float64, device=x0d.device)
+        engine.plant_rollout_device(x0d, ud, xs, f=fd, dt=dt, substeps=substeps, stream=stream)
+        if default:
+            engine.synchronize()
+        ctx.engine, ctx.dt, ctx.substeps, ctx.have_f = engine, dt, substeps, fd is not None
+        ctx.save_for_backward(x0d, ud, xs, *(() if fd is None else (fd,)))
+        return xs
+
+    @staticmethod
+    def backward(ctx, g_xs):
+        x0d, ud, xs, *rest = ctx.saved_tensors
+        fd = rest[0] if ctx.have_f else None
+        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.have_f and ctx.needs_input_grad[3])
+        if not any(need):
+            return (None,) * 6
+        K, B = ud.shape[0], ud.shape[1]
+        gx0, gu, gf = (torch.empty(s, dtype=torch.float64, device=x0d.device) if n else None
+                       for n, s in zip(need, ((B, 10), (K, B, 4), (K, B, 3))))
+        stream, default = _cuda_stream(x0d)
+        if default:
+            stream.synchronize()
+        ctx.engine.plant_rollout_vjp_device(x0d, ud, xs, g_xs.to(torch.float64).contiguous(), f=fd, gx0=gx0, gu=gu, gf=gf, dt=ctx.dt,
+                                            substeps=ctx.substeps, stream=stream)
+        if default:
+            ctx.engine.synchronize()
+        return gx0, None, gu, gf, None, None
+
+
+def plant_rollout(engine, x0, u, f=None, dt=CP.ts_nmpc, substeps=4):
+    """xs [ticks,B,10] float64 = the engine's plant from x0 [B,10] over the inputs u [ticks,B,4] and the external forces f [ticks,B,3]
+    (None: none), float64 CUDA tensors: per tick RK4 with `substeps` over dt with the input and the force held, then the quaternion
+    renormalised -- row k is what k + 1 ndp_plant_step_device calls give, bit for bit.  Differentiable in x0, u and f (reverse mode over
+    the saved log, one call).  Mass and gravity are the engine's and are not differentiated.  The engine's state is not touched: unlike
+    the control_step* Functions, two forward calls return the same values."""
+    return PlantRolloutFunction.apply(x0, engine, u, f, float(dt), int(substeps))
+
+
+def plant_step(engine, x, u, f=None, dt=CP.ts_nmpc, substeps=4):
+    """[B,10] float64 = one tick of the plant from x [B,10] with the input u [B,4] and the force f [B,3] (None: none): plant_rollout's
+    ticks = 1 case.  The piece that chains with control_step*: u0 = control_step(...); x = plant_step(engine, x, u0)."""
+    return plant_rollout(engine, x, u.unsqueeze(0), None if f is None else f.unsqueeze(0), dt, substeps)[0]
+
+
+def plant_rollout_jvp(engine, x0, u, tangents, f=None, dt=CP.ts_nmpc, substeps=4):
+    """(xs, dxs): plant_rollout's log xs [ticks,B,10] and its first-order change dxs [ticks,B,T,10] along tangents = (tx0, tu, tf) (forward
+    mode: BatchedNMPC.plant_rollout_jvp_device).  tx0 [B,T,10], tu [ticks,B,T,4], tf [ticks,B,T,3]; each may be None (= 0, not all three) and
+    each may come without the T axis -- then dxs is [ticks,B,10] if none has it.  tf may be given with f None (the direction away from no
+    force).  T <= 8.  No autograd hookup."""
+    x0d, ud = x0.detach().contiguous(), u.detach().contiguous()
+    fd = None if f is None else f.detach().contiguous()
+    ts, Ts, had = [], set(), False
+    for t, n in zip(tangents, (2, 3, 3)):                      # (dimensions without the T axis, which sits in front of the last)
+        if t is not None:
+            t = t.detach().to(torch.float64)
+            if t.dim() == n:
+                t = t.unsqueeze(-2)
+            elif t.dim() == n + 1:
+                had = True
+            else:
+                raise ValueError(f"plant_rollout_jvp: a tangent has {t.dim()} dimensions, expected {n} or {n + 1}")
+            Ts.add(int(t.shape[-2]))
+            t = t.contiguous()
+        ts.append(t)
+    if not Ts:
+        raise ValueError("plant_rollout_jvp: no tangent (all None)")
+    if len(Ts) > 1:
+        raise ValueError(f"plant_rollout_jvp: the tangents disagree on the number of directions ({sorted(Ts)})")
+    T, (K, B) = Ts.pop(), ud.shape[:2]
+    stream, default = _cuda_stream(x0d)
+    if default:
+        stream.synchronize()
+    xs = torch.empty((K, B, 10), dtype=torch.float64, device=x0d.device)
+    dxs = torch.empty((K, B, T, 10), dtype=torch.float64, device=x0d.device)
+    engine.plant_rollout_jvp_device(x0d, ud, dxs, f=fd, tx0=ts[0], tu=ts[1], tf=ts[2], n_tan=T, xs_check=xs, dt=dt, substeps=substeps,
+                                    stream=stream)
+    if default:
+        engine.synchronize()
+    return xs, dxs if had else dxs[:, :, 0]
