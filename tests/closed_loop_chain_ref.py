@@ -1,0 +1,260 @@
+"""The float64 reference of the closed loop chained tick by tick -- control step -> plant step -> the next tick's x0 -- in plain numpy,
+composed from the references the suite already trusts: tests/fixed_set_ref.py (the step's QP with a fixed set), tests/plant_deriv_ref.py
+(the plant, complex step) and tests/mlp_vjp_ref.py / tests/mlp_jvp_ref.py (the downwash network).  tests/test_closed_loop_chain.py holds it
+to central differences of the oracle's closed loop and to its own duality; tests/test_closed_loop_chain_gpu.py holds the torch layer's chain
+(ndp_nmpc_qd_amd/torch_layer.py: control_step_trajectory / control_step_ndp -> plant_step) to it.
+
+The chain, for k = 0 .. K-1 from x_0 and the engine's warm start:
+    (u0_k, X_k, U_k) = step_k(x_k, xr_k, ur_k, force_k)        x_{k+1} = plant(x_k, u0_k, fp_k)
+    L = sum_k <G_k, x_{k+1}> + <H_k, u0_k> + <A_k, X_k>
+ext form: force_k = f_k, a float32 leaf [B,N+1,3].  ndp form: force_k = the gated network (weights w) on (other_k[idx] - xr_k)[..., 0:6].
+
+A PARTIAL derivative, by the layer's contract: every tick's linearisation point (its pre-step iterate), final active set and gate are held
+fixed.  The input is therefore the RECORD of a nominal run (`nominal_cpu`, or the device's own in the GPU tests): per tick x_k, xr_k, ur_k,
+the force the step saw, fp_k, the pre-step iterate and kept set, the final set, u0_k and X_k.  `systems` builds every tick's step system and
+plant Jacobian once; `reverse` is one reverse sweep over them (the gradient of L in every leaf), `forward` the forward sweep (the tangents of
+every x_{k+1}, u0_k, X_k along T directions of the leaves).  Vehicles are independent except through other_k[idx] and w, so the sweeps run
+on a subset `which` of the vehicles (ndp form: all of them -- the weights' gradient sums over the batch)."""
+import numpy as np
+
+from ndp_nmpc_qd_amd.params import downwash_params as DP
+from ndp_nmpc_qd_amd.params import nmpc_params as CP
+from tests import fixed_set_ref as F
+from tests import mlp_jvp_ref as MJ
+from tests import mlp_vjp_ref as MV
+from tests import plant_deriv_ref as P
+
+DT, SUBSTEPS = CP.ts_nmpc, 4
+
+
+def twin_cfg(oracle, N):
+    """The oracle's twin of the device's default QP mode with the force on."""
+    cfg = oracle.default_cfg(N=N, use_fd=True)
+    cfg.qp_mode = 0
+    return cfg
+
+
+def gate_open(other_k, idx, x):
+    """[B] bool: a neighbour, and its window's node 0 strictly inside r_horiz of the ego state's xy (orc_downwash's rule)."""
+    d = other_k[np.clip(idx, 0, None)][:, 0, :2] - x[:, :2]
+    return (idx >= 0) & (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] < DP.r_horiz ** 2)
+
+
+def net_rows(other_k, xr_k, idx):
+    """z [B,N+1,6] float64: the rows the network sees, (other[idx] - xr)[..., 0:6]."""
+    return other_k[np.clip(idx, 0, None)][:, :, :6] - xr_k[:, :, :6]
+
+
+def margins(blob, other, xr, idx):
+    """[K,B,N+1]: every network row's float64 margin (mlp_vjp_ref.forward64) -- a function of the leaves alone, not of the state."""
+    out = []
+    for o, r in zip(other, xr):
+        z = net_rows(o, r, idx)
+        out.append(MV.vjp64(blob, z.reshape(-1, 6), np.zeros((z.shape[0] * z.shape[1], 3)))[2].reshape(z.shape[:2]))
+    return np.stack(out)
+
+
+def _force(oracle, blob, other_k, xr_k, idx, x, net64):
+    """The ndp form's force [B,N+1,3] as float64 values: the oracle's fp32 network (what the device runs), or -- net64, for finite
+    differences, which fp32 rounding would drown -- the float64 network this module differentiates.  Gate on x's xy."""
+    if not net64:
+        return oracle.downwash_batch(np.asarray(blob, dtype=np.float32), other_k[np.clip(idx, 0, None)].copy(), xr_k, x[:, :2].copy(),
+                                     r_horiz=DP.r_horiz).astype(np.float64) * (idx >= 0)[:, None, None]
+    import torch
+    z = net_rows(other_k, xr_k, idx)
+    f = MV.forward64(MV.params64(blob), torch.tensor(z.reshape(-1, 6)))[0].numpy().reshape(z.shape[:2] + (3,))
+    return f * gate_open(other_k, idx, x)[:, None, None]
+
+
+def nominal_cpu(oracle, x0, xr, ur, fp, f=None, other=None, idx=None, blob=None, net64=False, restart=None, dt=DT, substeps=SUBSTEPS):
+    """The chain on the oracle (step_batch_as in the device's QP mode, plant_step, downwash_batch): reset to (xr_0, ur_0), one warm-up step
+    on tick 0's inputs, then K ticks.  x0 [B,10], xr [K,B,N+1,10], ur [K,B,N,4], fp [K,B,3]; ext form: f [K,B,N+1,3]; ndp form: other
+    [K,rows,N+1,10], idx int32 [B], blob [17859] (any float dtype; net64: see _force).  restart: a record whose pre-step iterate and kept
+    set every tick starts from instead of what the tick before left (the rule of the finite-difference tests: the linearisation point does
+    not move with the perturbation).  Returns the record, a dict of arrays with the tick axis first."""
+    K, B, N = xr.shape[0], x0.shape[0], xr.shape[2] - 1
+    cfg = twin_cfg(oracle, N)
+    ndp = other is not None
+    force = (lambda k, x: _force(oracle, blob, other[k], xr[k], idx, x, net64)) if ndp else (lambda k, x: np.asarray(f[k], dtype=np.float64))
+    X, U, act = xr[0].copy(), ur[0].copy(), np.zeros((B, N, 4), dtype=np.int8)
+    if restart is None:
+        oracle.step_batch_as(cfg, x0, xr[0], ur[0], force(0, x0), X, U, act)
+    x = np.array(x0, dtype=np.float64)
+    keys = ("x", "force", "Xpre", "Upre", "act_pre", "act", "u0", "X", "st", "it", "open")
+    rec = {k: [] for k in keys}
+    for k in range(K):
+        if restart is not None:
+            X, U, act = restart["Xpre"][k].copy(), restart["Upre"][k].copy(), restart["act_pre"][k].copy()
+        fk = force(k, x)
+        rec["x"].append(x.copy()); rec["force"].append(fk); rec["Xpre"].append(X.copy()); rec["Upre"].append(U.copy())
+        rec["act_pre"].append(act.copy())
+        rec["open"].append(gate_open(other[k], idx, x) if ndp else np.ones(B, dtype=bool))
+        u0, st, it, _ = oracle.step_batch_as(cfg, x, xr[k], ur[k], fk, X, U, act)
+        x = oracle.plant_step(cfg, x.copy(), u0, np.ascontiguousarray(fp[k]), dt, substeps)
+        rec["act"].append(act.copy()); rec["u0"].append(u0); rec["X"].append(X.copy()); rec["st"].append(st); rec["it"].append(it)
+    rec["x"].append(x.copy())
+    rec = {k: np.stack(v) for k, v in rec.items()}
+    rec.update(xr=np.asarray(xr), ur=np.asarray(ur), fp=np.asarray(fp), other=None if other is None else np.asarray(other), idx=idx,
+               blob=blob)
+    return rec
+
+
+def set_finish(rec):
+    """[B] bool: every tick a status-0 set finish with no interior-point iteration."""
+    return ((rec["st"] == 0) & ((rec["it"] & 0xffff) == 0)).all(axis=0)
+
+
+def loss(rec, G, H, A):
+    """[B]: L per vehicle, G [K,B,10] on x_{k+1}, H [K,B,4] on u0_k, A [K,B,N+1,10] on X_k."""
+    return (G * rec["x"][1:]).sum(axis=(0, 2)) + (H * rec["u0"]).sum(axis=(0, 2)) + (A * rec["X"]).sum(axis=(0, 2, 3))
+
+
+def systems(oracle, rec, which, dt=DT, substeps=SUBSTEPS):
+    """The expensive part, once per record: per tick the plant's Jacobian [len(which), 10, 17] at (x_k, u0_k, fp_k) and per (tick,
+    vehicle) fixed_set_ref.jvp_system at the pre-step iterate with the final set.  What `reverse` and `forward` take."""
+    K, N = rec["xr"].shape[0], rec["xr"].shape[2] - 1
+    cfg = oracle.default_cfg(N=N, use_fd=True)
+    which = [int(v) for v in which]
+    J = [P.jacobian(rec["x"][k][which], rec["u0"][k][which][None], rec["fp"][k][which][None], dt, substeps, cfg.mass, cfg.g)
+         for k in range(K)]
+    S = [[F.jvp_system(oracle, cfg, rec["x"][k][v], rec["xr"][k][v], rec["ur"][k][v], rec["force"][k][v], rec["Xpre"][k][v],
+                       rec["Upre"][k][v], rec["act"][k][v]) for v in which] for k in range(K)]
+    return dict(which=which, J=J, S=S, K=K, N=N)
+
+
+def step_link(sys_, k, gu0, gX):
+    """The step link of tick k alone: (gx0 [n,10], gxr, gur, gf) for the upstreams gu0 [n,4], gX [n,N+1,10] of the vehicles in `which`."""
+    out = [F.vjp_apply(c, gu0[j], gX[j], None) for j, c in enumerate(sys_["S"][k])]
+    return tuple(np.stack([o[i] for o in out]) for i in range(4))
+
+
+def plant_link(sys_, k, gx):
+    """The plant link of tick k alone: (gx [n,10], gu [n,4], gfp [n,3]) for the upstream gx [n,10] of x_{k+1}."""
+    a, b, c = P.vjp(sys_["J"][k], gx[None])
+    return a, b[0], c[0]
+
+
+def reverse(sys_, rec, G, H, A, drop=None):
+    """One reverse sweep: the gradient of sum over `which` of L in every leaf.  G, H, A: full-batch arrays as `loss` takes them.  drop
+    [K,B,N+1] bool or None: network rows left out by the margin rule (their gf is zeroed before the network, as the device tests do it).
+    Returns a dict: x0 [n,10], xr [K,n,N+1,10], ur [K,n,N,4], fp [K,n,3], f [K,n,N+1,3] (ext: the leaf's; ndp: the step's gf as the
+    network's backward receives it, margin rule applied) and, ndp form, other [K,rows,N+1,10], w [17859] and gz [K,n,N+1,6]; rows in
+    the order of `which`."""
+    which, K, N = sys_["which"], sys_["K"], sys_["N"]
+    n = len(which)
+    ndp = rec["other"] is not None
+    out = dict(xr=np.zeros((K, n, N + 1, 10)), ur=np.zeros((K, n, N, 4)), fp=np.zeros((K, n, 3)), f=np.zeros((K, n, N + 1, 3)))
+    if ndp:
+        out.update(other=np.zeros_like(rec["other"], dtype=np.float64), w=np.zeros(MV.mlp_frag.NPARAM), gz=np.zeros((K, n, N + 1, 6)))
+    gx_next = np.zeros((n, 10))
+    for k in reversed(range(K)):
+        gx_p, gu_p, out["fp"][k] = plant_link(sys_, k, G[k][which] + gx_next)
+        gx0, out["xr"][k], out["ur"][k], gf = step_link(sys_, k, H[k][which] + gu_p, A[k][which])
+        gx_next = gx_p + gx0
+        if ndp:
+            gf = gf * rec["open"][k][which][:, None, None]
+            if drop is not None:
+                gf = np.where(drop[k][which][:, :, None], 0.0, gf)
+            z = net_rows(rec["other"][k], rec["xr"][k], rec["idx"])[which]
+            gz, gw, _, _ = MV.vjp64(rec["blob"], z.reshape(-1, 6), gf.reshape(-1, 3))
+            gz = gz.reshape(n, N + 1, 6)
+            out["gz"][k] = gz
+            out["xr"][k][:, :, :6] -= gz
+            np.add.at(out["other"][k][:, :, :6], rec["idx"][which], gz)
+            out["w"] += gw
+        out["f"][k] = gf
+    out["x0"] = gx_next
+    return out
+
+
+def forward(sys_, rec, t_x0, t_xr, t_ur, t_fp, t_f=None, t_other=None, t_w=None, drop=None):
+    """The forward sweep of the same composition along T directions of the leaves: t_x0 [B,T,10], t_xr [K,B,T,N+1,10], t_ur [K,B,T,N,4],
+    t_fp [K,B,T,3], ext: t_f [K,B,T,N+1,3], ndp: t_other [K,rows,T,N+1,10] and t_w [T,17859] (full-batch arrays; the ndp form's may be
+    None = 0).  Returns (dx [K,n,T,10] of x_{k+1}, du0 [K,n,T,4], dX [K,n,T,N+1,10]); rows in the order of `which`."""
+    which, K, N = sys_["which"], sys_["K"], sys_["N"]
+    n, T = len(which), t_x0.shape[1]
+    ndp = rec["other"] is not None
+    tx = np.array(t_x0[which], dtype=np.float64)
+    dx, du0, dX = np.zeros((K, n, T, 10)), np.zeros((K, n, T, 4)), np.zeros((K, n, T, N + 1, 10))
+    for k in range(K):
+        if ndp:
+            z = net_rows(rec["other"][k], rec["xr"][k], rec["idx"])[which].reshape(-1, 6)
+            tf = np.zeros((n, T, N + 1, 3))
+            for t in range(T):
+                tz = -t_xr[k][which, t][:, :, :6]
+                if t_other is not None:
+                    tz = tz + t_other[k][rec["idx"][which], t][:, :, :6]
+                tf[:, t] = MJ.jvp64(rec["blob"], z, tz.reshape(-1, 6), None if t_w is None else t_w[t])[0].reshape(n, N + 1, 3)
+            tf *= rec["open"][k][which][:, None, None, None]
+            if drop is not None:
+                tf = np.where(drop[k][which][:, None, :, None], 0.0, tf)
+        else:
+            tf = t_f[k][which]
+        for j, c in enumerate(sys_["S"][k]):
+            v = which[j]
+            for t in range(T):
+                du0[k, j, t], dX[k, j, t], _, _ = F.jvp_apply(c, tx[j, t], t_xr[k][v, t], t_ur[k][v, t], tf[j, t])
+        dx[k] = P.jvp(sys_["J"][k], tx0=tx, tu=du0[k][None], tf=t_fp[k][which][None])[0]
+        tx = dx[k]
+    return dx, du0, dX
+
+
+def rel_err(dev, ref, lead):
+    """The end-to-end measure: the worst |dev - ref| / max(1, |ref|max of the leaf's row), a row = everything behind the first `lead`
+    axes (one vehicle's share of one tick's leaf; lead = 0: the whole array, as for the weights)."""
+    dev, ref = np.asarray(dev, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    shp = ref.shape[:lead] + (-1,)
+    s = np.maximum(1.0, np.abs(ref).reshape(shp).max(axis=-1, keepdims=True))
+    return float((np.abs(dev - ref).reshape(shp) / s).max())
+
+
+# ---------------------------------------------------------------- the inputs the CPU and the device tests share
+def ext_inputs(B, K, N, seed):
+    """ext form: the mixed workload's windows at t0 = k ts_nmpc (one seed: the same figure-eights, sliding), x_0 its tick-0 state, a
+    seeded fp32 force per tick ~ N(0, 0.3) and a true force on the plant ~ N(0, 1) N."""
+    from ndp_nmpc_qd_amd import synth
+    from tests.step_deriv_emu import MIXED
+    b = [synth.make_batch(B, N=N, seed=seed, t0=k * DT, **MIXED) for k in range(K)]
+    rng = np.random.default_rng(seed + 1)
+    return dict(x0=b[0]["x0"].copy(), xr=np.stack([v["xr"] for v in b]), ur=np.stack([v["ur"] for v in b]),
+                f=rng.normal(0.0, 0.3, (K, B, N + 1, 3)).astype(np.float32), fp=rng.normal(0.0, 1.0, (K, B, 3)))
+
+
+NDP_DZ = 0.6     # see ndp_inputs
+
+
+def ndp_inputs(K, seed, pos=0.05, vel=0.1, pairs=2):
+    """ndp form (N = 20): formation_ref.workload's stacked pairs, idx = i ^ 1, other_k = xr_k (a leaf of its own), x_0 the first window's
+    node 0 plus a seeded offset (positions ~ N(0, pos), velocities ~ N(0, vel)), the shipped weights, a true force ~ N(0, 1) N.
+    The pairs fly ONE path dz apart, so every network row is (0, 0, +-dz, 0, 0, 0): the margin rule keeps all rows of a vehicle or none.
+    At the workload's default dz = 0.5 the lower vehicles' rows have margin 8.4e-5 < mlp_vjp_ref.MARGIN -- half of all rows would be left
+    out -- so the pairs are stacked NDP_DZ = 0.6 apart, where the margins are 5.2e-3 and 3.2e-3."""
+    from ndp_nmpc_qd_amd import _lib
+    from tests import formation_ref as FR
+    tr = FR.workload(pairs=pairs, dz=NDP_DZ)
+    xr, ur = FR.windows(tr, K)
+    B = xr.shape[1]
+    rng = np.random.default_rng(seed)
+    x0 = xr[0][:, 0].copy()
+    x0[:, 0:3] += rng.normal(0.0, pos, (B, 3))
+    x0[:, 3:6] += rng.normal(0.0, vel, (B, 3))
+    return dict(x0=x0, xr=np.ascontiguousarray(xr[:K]), ur=np.ascontiguousarray(ur[:K]), other=xr[:K].copy(), idx=tr["other_index"],
+                blob=_lib.load_weights(), fp=rng.normal(0.0, 1.0, (K, B, 3)))
+
+
+def upstreams(K, B, N, seed):
+    """Seeded normal (G [K,B,10], H [K,B,4], A [K,B,N+1,10])."""
+    rng = np.random.default_rng(seed)
+    return rng.normal(size=(K, B, 10)), rng.normal(size=(K, B, 4)), rng.normal(size=(K, B, N + 1, 10))
+
+
+def tangents(K, B, N, T, seed, rows=None):
+    """Seeded normal directions of every leaf as `forward` takes them: dict t_x0, t_xr, t_ur, t_fp, t_f and (rows given) t_other; the
+    weights' direction t_w [T,17859] float32 ~ N(0, 1e-2)."""
+    rng = np.random.default_rng(seed)
+    t = dict(t_x0=rng.normal(size=(B, T, 10)), t_xr=rng.normal(size=(K, B, T, N + 1, 10)), t_ur=rng.normal(size=(K, B, T, N, 4)),
+             t_fp=rng.normal(size=(K, B, T, 3)), t_f=rng.normal(size=(K, B, T, N + 1, 3)))
+    if rows is not None:
+        t["t_other"] = rng.normal(size=(K, rows, T, N + 1, 10))
+        t["t_w"] = rng.normal(0.0, 1e-2, (T, MV.mlp_frag.NPARAM)).astype(np.float32)
+    return t
