@@ -728,6 +728,49 @@ int ndp_downwash_multi_jvp_device(ndp_handle *h, const void *d_other, int other_
                                   const void *d_ego_ref, const void *d_ego_xy, int n_tan, const void *d_tz, const void *d_tw, void *d_df,
                                   void *d_f_check, void *stream);
 
+/* ---- The derivatives of the downwash force ON THE PLANT (ndp_plant_force_device / ndp_plant_force_multi_device): the link between the
+ * vehicles' actual states and the force f that ndp_plant_step_device / ndp_plant_rollout_device take as an input, whose gradient d_gf those
+ * calls return.  The derivative is that of the arithmetic ndp_plant_force_multi_device performs: per slot z = fp32 of the fp64 difference
+ * (x[o] - x[v])[0:6], the network, scale * (double)net, summed in fp64 in slot order.  The rounding of z to fp32 counts as the identity; the
+ * gate (strict, per slot, the forward's expression) is piecewise constant and contributes nothing; the ReLU masks are the forward's,
+ * recomputed with the step's own arithmetic.  d_x [B][10] fp64; d_other_index int32[B] (single forms) or [B][K] (multi forms, K outside
+ * 1..NDP_MAX_NEIGH: -2); a slot with o < 0 or o >= B is empty and never read; d_other_index NULL: nobody has a neighbour -- exact zeros in
+ * every output, no network pass, no weights needed.  The single-neighbour forms are the K = 1 case, bit for bit.
+ *
+ * Reverse mode.  d_gf [B][3] fp64 (required) is the gradient of the SUMMED force, shared by a vehicle's K slots; each open slot's upstream is
+ * fp32(scale * d_gf[v][c]), the product formed in fp64 and rounded once.  Outputs, each NULL = not computed, not both NULL:
+ *   d_gz [B][K][6] fp64 : the gradient per NETWORK INPUT ROW (as ndp_downwash*_vjp_device return it), 0 on closed and empty slots.  The
+ *                         scatter onto the states is the caller's: + d_gz[v][k] to x[o_k][0:6], - d_gz[v][k] to x[v][0:6] (torch:
+ *                         plant_force does it).  With windows other[o][n] = x[o], ego_ref[v][n] = x[v], ego_xy = x[v][0:2] and the upstream
+ *                         scale * d_gf[v] at node 0, d_gz[v][k] is bit-equal to node 0 of ndp_downwash_multi_vjp_device's d_gz.
+ *   d_gw [NDP_MLP_NPARAM] fp32, OVERWRITTEN: accumulated in registers across the launch, one partial-sum pass and one fixed-order
+ *                         reduction, no atomics: two calls are bit-identical.
+ * A vehicle whose d_gf row is not finite adds nothing to d_gw and has NaN in the d_gz of its open slots; so does a slot whose six inputs
+ * are not all finite.  Nothing of the engine's state is written.  The partial sums use the SAME workspace as ndp_downwash_vjp_device (its
+ * size caps the workgroups, the rest is a grid-stride loop): calls of these kinds on one handle must be ordered against each other -- the
+ * same stream, or streams ordered by events.
+ *
+ * Forward mode, T = n_tan directions (1..NDP_JVP_MAX_TANGENTS), not both NULL:
+ *   d_tx [B][T][10] fp64 : directions of the STATES.  The kernel gathers: a slot's input direction is the fp64 difference tx[o][t][i] -
+ *                          tx[v][t][i], i < 6, then handled as ndp_downwash_multi_jvp_device handles its d_tz -- no scatter is needed.
+ *   d_tw [T][NDP_MLP_NPARAM] fp32 : directions of the weights.
+ * Outputs:
+ *   d_df [B][T][3] fp64, required: the fp64 sum in slot order of scale * (double)tangent, the product and each sum individually rounded, the
+ *                          first open slot's value taken as it is; exactly 0 where no slot is open.
+ *   d_f_check [B][3] fp64, optional: the recomputed force, bit-equal to ndp_plant_force_multi_device's.
+ * T directions in one call equal T calls bit for bit.  No atomics, no workspace, nothing of the engine's state written.
+ *
+ * -1: NULL handle or d_x; -6: weights never set and an index given; -2 with a reason in ndp_last_error, nothing enqueued, outputs untouched:
+ * K outside 1..NDP_MAX_NEIGH, d_gf NULL, no output asked for, n_tan out of range, no tangent given, d_df NULL. */
+int ndp_plant_force_vjp_device(ndp_handle *h, const void *d_x, const void *d_other_index, int gate, double scale, const void *d_gf,
+                               void *d_gz, void *d_gw, void *stream);
+int ndp_plant_force_multi_vjp_device(ndp_handle *h, const void *d_x, const void *d_other_index, int K, int gate, double scale,
+                                     const void *d_gf, void *d_gz, void *d_gw, void *stream);
+int ndp_plant_force_jvp_device(ndp_handle *h, const void *d_x, const void *d_other_index, int gate, double scale, int n_tan,
+                               const void *d_tx, const void *d_tw, void *d_df, void *d_f_check, void *stream);
+int ndp_plant_force_multi_jvp_device(ndp_handle *h, const void *d_x, const void *d_other_index, int K, int gate, double scale, int n_tan,
+                                     const void *d_tx, const void *d_tw, void *d_df, void *d_f_check, void *stream);
+
 /* ---- Training the downwash network on the device (nn_train.py:129-157 with --SN): one full-batch Adam step followed by the spectral-norm
  * cap on every weight matrix, in ONE launch of four workgroups (one per layer) behind the weight gradient of ndp_downwash_vjp_device /
  * ndp_downwash_multi_vjp_device.  No host value changes between two steps (the step counter lives in device memory), so steps can be

@@ -69,6 +69,7 @@ EXPORTS = [
     "ndp_mlp_spectral_norms_device", "ndp_mlp_spectral_norms", "ndp_mlp_adam_sn_device",
     "ndp_mlp_rows_device", "ndp_mlp_fit_rows_device",
     "ndp_plant_rollout_device", "ndp_plant_rollout_vjp_device", "ndp_plant_rollout_jvp_device",
+    "ndp_plant_force_vjp_device", "ndp_plant_force_multi_vjp_device", "ndp_plant_force_jvp_device", "ndp_plant_force_multi_jvp_device",
 ]
 
 _lib = None
@@ -234,6 +235,10 @@ def load():
     lib.ndp_plant_rollout_device.argtypes = [vp, C.c_int, C.c_double, C.c_int] + [vp] * 5
     lib.ndp_plant_rollout_vjp_device.argtypes = [vp, C.c_int, C.c_double, C.c_int] + [vp] * 9
     lib.ndp_plant_rollout_jvp_device.argtypes = [vp, C.c_int, C.c_double, C.c_int, vp, vp, vp, C.c_int] + [vp] * 6
+    lib.ndp_plant_force_vjp_device.argtypes = [vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp]
+    lib.ndp_plant_force_multi_vjp_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp]
+    lib.ndp_plant_force_jvp_device.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp, vp]
+    lib.ndp_plant_force_multi_jvp_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 

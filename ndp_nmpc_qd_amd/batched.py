@@ -538,6 +538,105 @@ class BatchedNMPC:
             self._dptr(f_out, torch.float64, (self.B, 3)), self._dptr(xy_out, torch.float64, (self.B, 2)), self._stream(stream)),
             "ndp_plant_force_multi_device")
 
+    # ---- the derivatives of the plant force (ndp_plant_force*_vjp_device, ndp_plant_force*_jvp_device; include/ndp_nmpc.h)
+    def _slots_of(self, other_index, *shaped):
+        """K of a multi call: other_index int32[B,K], or -- other_index None -- the slot axis of the first output given (else 1)."""
+        if other_index is not None:
+            return self._dindex_multi(other_index)
+        for t, pos in shaped:
+            if t is not None and t.dim() > pos:
+                return None, int(t.shape[pos])
+        return None, 1
+
+    def plant_force_multi_vjp_device(self, x, other_index, gf, gz=None, gw=None, gate=True, scale=1.0, stream=None):
+        """Enqueues the backward pass of plant_force_multi_device on `stream` (ndp_plant_force_multi_vjp_device): x[B,10] float64,
+        other_index int32[B,K] or None, gf[B,3] float64 the gradient of the summed force.  Outputs (None = not computed, not both None):
+        gz [B,K,6] float64, the gradient per network input row, 0 on closed and empty slots -- the scatter onto the states (+gz to
+        x[o][0:6], -gz to x[v][0:6]) is the caller's (torch_layer.plant_force does it); gw [17859] float32, overwritten, two calls
+        bit-identical.  A vehicle whose gf row (or a slot whose input) is not finite adds nothing to gw and has NaN in its gz.  Shares
+        downwash_vjp_device's workspace: order the calls against each other.  The engine's state is not written.  stream None or torch's
+        default stream: as downwash_vjp_device."""
+        import torch
+        B = self.B
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        iptr, K = self._slots_of(other_index, (gz, 1))
+        d = self._dptr
+        self._check(self._lib.ndp_plant_force_multi_vjp_device(
+            self._h, d(x, torch.float64, (B, 10)), iptr, K, 1 if gate else 0, float(scale), d(gf, torch.float64, (B, 3)),
+            d(gz, torch.float64, (B, K, 6)), d(gw, torch.float32, (_lib.MLP_NPARAM,)), self._stream(stream)),
+            "ndp_plant_force_multi_vjp_device")
+
+    def plant_force_vjp_device(self, x, other_index, gf, gz=None, gw=None, gate=True, scale=1.0, stream=None):
+        """plant_force_multi_vjp_device with one neighbour per vehicle (ndp_plant_force_vjp_device): other_index int32[B] or None,
+        gz [B,6].  The K = 1 case, bit for bit."""
+        import torch
+        B = self.B
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        d = self._dptr
+        self._check(self._lib.ndp_plant_force_vjp_device(
+            self._h, d(x, torch.float64, (B, 10)), d(other_index, torch.int32, (B,)), 1 if gate else 0, float(scale),
+            d(gf, torch.float64, (B, 3)), d(gz, torch.float64, (B, 6)), d(gw, torch.float32, (_lib.MLP_NPARAM,)), self._stream(stream)),
+            "ndp_plant_force_vjp_device")
+
+    def _plant_force_tangents(self, who, tx, tw, df, n_tan):
+        """(T, tx, tw, df pointers) of a forward-mode call: T is n_tan when given, else read from the tensors; tensors without the T axis
+        mean T = 1."""
+        import torch
+        B = self.B
+        tails = ((10,), (_lib.MLP_NPARAM,), (3,))
+        lead = (1, 0, 1)                                                # dimensions in front of the T axis
+        if n_tan is None:
+            Ts = {int(t.shape[ld]) if t.dim() == ld + 1 + len(s) else 1 for t, s, ld in zip((tx, tw, df), tails, lead) if t is not None}
+            if len(Ts) > 1:
+                raise ValueError(f"{who}: tangents and output disagree on the number of directions ({sorted(Ts)})")
+            n_tan = Ts.pop() if Ts else 1
+        T = int(n_tan)
+
+        def dt(t, s, ld):
+            if t is None:
+                return None
+            head = (B,) if ld else ()
+            full = head + (T,) + s
+            if t.dim() != len(full) and T != 1:
+                raise ValueError(f"{who}: a tensor without the T axis with n_tan = {T}")
+            return self._dptr(t, torch.float32 if s is tails[1] else torch.float64, full if t.dim() == len(full) else head + s)
+        return T, dt(tx, tails[0], 1), dt(tw, tails[1], 0), dt(df, tails[2], 1)
+
+    def plant_force_multi_jvp_device(self, x, other_index, tx=None, tw=None, n_tan=None, df=None, f_check=None, gate=True, scale=1.0,
+                                     stream=None):
+        """Enqueues the forward mode of plant_force_multi_device on `stream` (ndp_plant_force_multi_jvp_device).  Directions (None = 0, not
+        both None): tx [B,T,10] float64, directions of the STATES -- the kernel gathers a slot's input direction tx[o] - tx[v], so no
+        scatter is needed; tw [T,17859] float32.  Outputs: df [B,T,3] float64, required -- the float64 sum in slot order of scale x the
+        slots' tangents, exactly 0 where no slot is open; f_check [B,3] float64, optional -- bit-equal to plant_force_multi_device's force.
+        T (1..8) is n_tan when given, else read from the tensors; tensors without the T axis mean T = 1.  T directions in one call equal T
+        calls bit for bit.  No workspace; the engine's state is not written.  stream None or torch's default stream: as
+        downwash_jvp_device."""
+        import torch
+        B = self.B
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        iptr, K = self._slots_of(other_index)
+        T, ptx, ptw, pdf = self._plant_force_tangents("plant_force_multi_jvp_device", tx, tw, df, n_tan)
+        d = self._dptr
+        self._check(self._lib.ndp_plant_force_multi_jvp_device(
+            self._h, d(x, torch.float64, (B, 10)), iptr, K, 1 if gate else 0, float(scale), T, ptx, ptw, pdf,
+            d(f_check, torch.float64, (B, 3)), self._stream(stream)), "ndp_plant_force_multi_jvp_device")
+
+    def plant_force_jvp_device(self, x, other_index, tx=None, tw=None, n_tan=None, df=None, f_check=None, gate=True, scale=1.0, stream=None):
+        """plant_force_multi_jvp_device with one neighbour per vehicle (ndp_plant_force_jvp_device): other_index int32[B] or None.  The
+        K = 1 case, bit for bit."""
+        import torch
+        B = self.B
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        T, ptx, ptw, pdf = self._plant_force_tangents("plant_force_jvp_device", tx, tw, df, n_tan)
+        d = self._dptr
+        self._check(self._lib.ndp_plant_force_jvp_device(
+            self._h, d(x, torch.float64, (B, 10)), d(other_index, torch.int32, (B,)), 1 if gate else 0, float(scale), T, ptx, ptw, pdf,
+            d(f_check, torch.float64, (B, 3)), self._stream(stream)), "ndp_plant_force_jvp_device")
+
     def rollout_formation_multi_device(self, ticks, x, other_index, log=None, log_u=None, log_f=None, worst_status=None, t0=0.0,
                                        dt=CP.ts_nmpc, substeps=4, gate=True, compensate=None, plant_scale=1.0, stream=None):
         """rollout_formation_device with K neighbours per vehicle (ndp_rollout_formation_multi_device; include/ndp_nmpc.h): other_index

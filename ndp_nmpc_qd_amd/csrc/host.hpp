@@ -20,9 +20,12 @@
 //                    spectral norms (ndp_mlp_spectral_norms*)
 //   plant_deriv.hip  the plant over a given input sequence and its derivatives (ndp_plant_rollout_device, ndp_plant_rollout_vjp_device,
 //                    ndp_plant_rollout_jvp_device); a tick's arithmetic is plant_dyn.hpp's, shared with rows.hip's plant_kernel
+//   plant_force_deriv.hip  the derivatives of the downwash force on the plant (ndp_plant_force_vjp_device, ndp_plant_force_jvp_device and
+//                    their multi forms); hosts mlp_vjp.hip's backward pass (mlp_vjp_dev.hpp, mlp_vjp_back.inc, mlp_vjp_part.inc) and
+//                    mlp_jvp.hip's direction (mlp_jvp_dev.hpp, mlp_jvp_direction.inc) behind a row loader of its own
 //   exchange.hip     peer-mapped windows (ndp_peer_*), the RCCL exchange (ndp_xchg_*) and the remote tick one control period ahead
 // A kernel sits with the host code that launches it; device code that two units' kernels inline is a header (mlp_tile.hpp, ref_point.hpp,
-// tick_wave.hpp, mlp_vjp_dev.hpp, plant_dyn.hpp), and so are the argument blocks the host fills (kern_args.hpp).
+// tick_wave.hpp, mlp_vjp_dev.hpp, mlp_jvp_dev.hpp, plant_dyn.hpp), and so are the argument blocks the host fills (kern_args.hpp).
 // The functions declared below are NDP_HIDDEN: the library exports the C-ABI of include/ndp_nmpc.h and nothing more.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -290,6 +293,8 @@ NDP_HIDDEN void make_fragments_t(const float *blob, float *frt);
 NDP_HIDDEN hipError_t mlp_vjp_prepare(void);
 // mlp_fit.hip
 NDP_HIDDEN hipError_t mlp_fit_prepare(void);
+// plant_force_deriv.hip
+NDP_HIDDEN hipError_t plant_force_deriv_prepare(void);
 // exchange.hip
 NDP_HIDDEN int peer_mapped(const void *p);
 NDP_HIDDEN void launch_pack_pv_list(const double *base, size_t pitch, int np1, double *pv, size_t B, hipStream_t s);

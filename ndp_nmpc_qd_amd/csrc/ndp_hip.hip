@@ -379,6 +379,7 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
     if ((e = mlp_vjp_prepare()) != hipSuccess) return fail("hipFuncSetAttribute(mlp_vjp_kernel)", e);
     if ((e = mlp_fit_prepare()) != hipSuccess) return fail("hipFuncSetAttribute(mlp_fit_rows_kernel)", e);
     if ((e = mlp_multi_prepare()) != hipSuccess) return fail("hipFuncSetAttribute(mlp_multi_kernel)", e);
+    if ((e = plant_force_deriv_prepare()) != hipSuccess) return fail("hipFuncSetAttribute(plant_force_vjp_kernel)", e);
     const char *what = nullptr;
     if ((e = rti_set_lds(false, lds_bytes, &what)) != hipSuccess) return fail(what, e);      // (the sensitivity kernels: ndp_sens_enable)
     launch_throttle_reset(h);

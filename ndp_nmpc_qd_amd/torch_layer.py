@@ -46,6 +46,10 @@ plant_rollout / plant_step / plant_rollout_jvp (at the end of this file) are the
 forces in one launch, differentiable in the initial state, the inputs and the forces (BatchedNMPC.plant_rollout_device,
 plant_rollout_vjp_device, plant_rollout_jvp_device).  plant_step is its one-tick case, the piece that chains with the control_step*
 Functions: u0 -> plant_step -> the next tick's x0, with the values ndp_plant_step_device gives bit for bit.
+
+plant_force / plant_force_jvp (at the end of this file) are the downwash force the neighbours' actual states put on the plant, differentiable
+in the states and the network's weights (BatchedNMPC.plant_force_multi_device, plant_force_multi_vjp_device, plant_force_multi_jvp_device):
+f = plant_force(engine, x, other_index); x = plant_step(engine, x, u, f) is a differentiable formation tick on the plant side.
 """
 import torch
 
@@ -1055,3 +1059,118 @@ def plant_rollout_jvp(engine, x0, u, tangents, f=None, dt=CP.ts_nmpc, substeps=4
     if default:
         engine.synchronize()
     return xs, dxs if had else dxs[:, :, 0]
+
+
+# ---------------------------------------------------------------------------------------------- the downwash force on the plant, differentiated
+# The force the neighbours' ACTUAL states put on the ACTUAL vehicle (ndp_plant_force_multi_device): the link between the states and the `f`
+# of plant_rollout / plant_step.  What is differentiated: scale x the fp32 network on the fp32-rounded (x[o] - x[v])[0:6] (the rounding
+# counts as the identity), summed over the slots.  What is held fixed: the r_horiz gate (piecewise constant).
+
+def _plant_index(other_index, who):
+    """other_index None, [B] or [B,K] -> None or a contiguous int32 [B,K]."""
+    if other_index is None:
+        return None
+    if other_index.dim() not in (1, 2):
+        raise ValueError(f"{who}: other_index must be int32 [B] or [B,K]")
+    idx = other_index if other_index.dim() == 2 else other_index.unsqueeze(1)
+    return idx.to(torch.int32).contiguous()
+
+
+def _scatter_gz_states(gz, x, idx):
+    """dL/dx [B,10] from g_z [B,K,6]: + g_z[v][k] on x[o_k][0:6], - g_z[v][k] on x[v][0:6], columns 6..9 zero; vehicles and slots that share
+    a neighbour add up.  A vehicle in its own slot sees z = x[v] - x[v]: its two shares cancel, so that slot is left out of both (an exactly
+    zero contribution)."""
+    B = x.shape[0]
+    g = torch.zeros_like(x)
+    own = idx == torch.arange(B, device=idx.device, dtype=idx.dtype)[:, None]
+    has = (idx >= 0) & (idx < B) & ~own
+    g[:, :6].index_add_(0, idx[has].long(), gz[has])
+    g[:, :6] -= torch.where(has[:, :, None], gz, torch.zeros_like(gz)).sum(dim=1)
+    return g
+
+
+class PlantForceFunction(torch.autograd.Function):
+    """forward(x, engine, other_index, gate, scale, weights) -> f [B,3] float64, the summed downwash force on the plant
+    (BatchedNMPC.plant_force_multi_device); backward: ONE BatchedNMPC.plant_force_multi_vjp_device call and the scatter of its g_z onto
+    the states."""
+
+    @staticmethod
+    def forward(ctx, x, engine, other_index, gate, scale, weights=None):
+        xd = x.detach().contiguous()
+        idx = _plant_index(other_index, "PlantForceFunction")
+        stream, default = _cuda_stream(xd)
+        if default:
+            stream.synchronize()
+        ctx.key = _install_weights(engine, weights, stream)
+        f = torch.empty((xd.shape[0], 3), dtype=torch.float64, device=xd.device)
+        if idx is None:
+            f.zero_()
+        else:
+            engine.plant_force_multi_device(xd, idx, f, gate=gate, scale=scale, stream=stream)
+            if default:
+                engine.synchronize()
+        ctx.engine, ctx.gate, ctx.scale = engine, gate, scale
+        ctx.have_w, ctx.have_idx = weights is not None, idx is not None
+        ctx.save_for_backward(xd, *(() if idx is None else (idx,)))
+        return f
+
+    @staticmethod
+    def backward(ctx, g_f):
+        xd, *rest = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want_w = ctx.have_w and need[5]
+        if not ctx.have_idx:          # nobody has a neighbour: the force is the constant 0
+            return (torch.zeros_like(xd) if need[0] else None, None, None, None, None,
+                    torch.zeros(17859, dtype=torch.float32, device=xd.device) if want_w else None)
+        idx = rest[0]
+        eng = ctx.engine
+        _check_installed(eng, ctx.key, "PlantForceFunction")
+        B, K = idx.shape
+        gz = torch.empty((B, K, 6), dtype=torch.float64, device=xd.device) if need[0] else None
+        gw = torch.empty(17859, dtype=torch.float32, device=xd.device) if want_w else None
+        if gz is None and gw is None:
+            return (None,) * 6
+        stream, default = _cuda_stream(xd)
+        if default:
+            stream.synchronize()
+        eng.plant_force_multi_vjp_device(xd, idx, g_f.to(torch.float64).contiguous(), gz=gz, gw=gw, gate=ctx.gate, scale=ctx.scale,
+                                         stream=stream)
+        if default:
+            eng.synchronize()
+        return (_scatter_gz_states(gz, xd, idx) if need[0] else None, None, None, None, None, gw)
+
+
+def plant_force(engine, x, other_index, gate=True, scale=1.0, weights=None):
+    """f [B,3] float64 = the downwash force the neighbours' states put on every vehicle: x [B,10] float64 the vehicles' actual states,
+    other_index int32 [B] or [B,K] (vehicle v hears x[other_index[v][k]]; < 0 or >= B: an empty slot; the same index twice counts twice;
+    None: nobody has a neighbour), each slot behind its own r_horiz gate (gate False: open), the slots' forces times `scale` summed in
+    float64 -- the values of BatchedNMPC.plant_force_multi_device, bit for bit.  Differentiable in `x` (per slot + g_z on x[o][0:6] and
+    - g_z on x[v][0:6]; columns 6..9 get 0) and `weights` (as `downwash_multi`: a float32 CUDA tensor / nn.Parameter of 17 859 in blob
+    order, installed first unless it is what was installed last; replaced before the backward: RuntimeError).  The gate is held fixed.  A
+    vehicle whose upstream gradient is not finite adds nothing to the weights' gradient and has NaN in the input gradients of its open
+    slots.  With plant_step: f = plant_force(eng, x, idx); x = plant_step(eng, x, u, f) is a differentiable formation tick on the plant
+    side."""
+    return PlantForceFunction.apply(x, engine, other_index, bool(gate), float(scale), weights)
+
+
+def plant_force_jvp(engine, x, other_index, tangents, gate=True, scale=1.0, weights=None):
+    """(f, df): plant_force's f [B,3] float64 and its first-order change df [B,T,3] float64 along tangents = (tx, tw) (forward mode:
+    BatchedNMPC.plant_force_multi_jvp_device).  tx [B,T,10] float64, directions of the states (the device gathers tx[o] - tx[v] per slot:
+    nothing is scattered here); tw [T,17859] float32, directions of the weights; each may be None (= 0, not both) and each may come without
+    the T axis -- then df is [B,3] if neither has it.  T <= 8.  The gates are held fixed.  No autograd hookup."""
+    xd = x.detach().contiguous()
+    idx = _plant_index(other_index, "plant_force_jvp")
+    (tx, tw), T, had = _with_t_axis(tangents, (2, 1), "plant_force_jvp")
+    stream, default = _cuda_stream(xd)
+    if default:
+        stream.synchronize()
+    _install_weights(engine, weights, stream)
+    B = xd.shape[0]
+    tx = None if tx is None else tx.to(torch.float64).contiguous()
+    tw = None if tw is None else tw.to(torch.float32).contiguous()
+    f = torch.empty((B, 3), dtype=torch.float64, device=xd.device)
+    df = torch.empty((B, T, 3), dtype=torch.float64, device=xd.device)
+    engine.plant_force_multi_jvp_device(xd, idx, tx=tx, tw=tw, n_tan=T, df=df, f_check=f, gate=gate, scale=scale, stream=stream)
+    if default:
+        engine.synchronize()
+    return f, df if had else df[:, 0]
