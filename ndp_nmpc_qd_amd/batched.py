@@ -27,9 +27,10 @@ class BatchedNMPC:
         # precision studies): such engines are created with ipm_refine = 0 unless the caller says otherwise (and is then told no)
         if "ipm_refine" not in cfg_overrides and (7 * int(N) - 3 > 192 or cfg_overrides.get("qp_precision", 0)):
             cfg_overrides = dict(cfg_overrides, ipm_refine=0)
+        # (r_horiz: the reference's gate radius unless the caller overrides it like any other ndp_cfg field)
         self.cfg = _lib.default_cfg(batch=int(batch), N=int(N), n_rti=int(n_rti), use_fd=int(bool(disturbance)),
-                                    qp_mode=int(qp_mode), device=int(device), dt=float(dt), r_horiz=DP.r_horiz,
-                                    **cfg_overrides)
+                                    qp_mode=int(qp_mode), device=int(device), dt=float(dt),
+                                    **{"r_horiz": DP.r_horiz, **cfg_overrides})
         self.B, self.N = int(batch), int(N)
         self.disturbance = bool(disturbance)
         self._h = C.c_void_p()

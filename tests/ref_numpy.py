@@ -11,30 +11,30 @@ G = 9.81
 MASS = 1.4844
 
 
-def f_dyn(x, u, fd=None):
-    """nmpc_body_rate_ctl.py:147-158 (+ ndp_nmpc_body_rate_ctl.py:155-157)."""
+def f_dyn(x, u, fd=None, mass=MASS, g=G):
+    """nmpc_body_rate_ctl.py:147-158 (+ ndp_nmpc_body_rate_ctl.py:155-157); mass and g: the reference's constants unless given."""
     vx, vy, vz, qw, qx, qy, qz = x[3:10]
     wx, wy, wz, c = u
     ds = np.array([
         vx, vy, vz,
         2 * (qx * qz + qw * qy) * c,
         2 * (qy * qz - qw * qx) * c,
-        (1 - 2 * qx ** 2 - 2 * qy ** 2) * c - G,
+        (1 - 2 * qx ** 2 - 2 * qy ** 2) * c - g,
         (-wx * qx - wy * qy - wz * qz) * 0.5,
         (wx * qw + wz * qy - wy * qz) * 0.5,
         (wy * qw - wz * qx + wx * qz) * 0.5,
         (wz * qw + wy * qx - wx * qy) * 0.5,
     ])
     if fd is not None:
-        ds[3:6] += np.asarray(fd) / MASS
+        ds[3:6] += np.asarray(fd) / mass
     return ds
 
 
-def rk4(x, u, fd=None, h=0.1):
-    k1 = f_dyn(x, u, fd)
-    k2 = f_dyn(x + 0.5 * h * k1, u, fd)
-    k3 = f_dyn(x + 0.5 * h * k2, u, fd)
-    k4 = f_dyn(x + h * k3, u, fd)
+def rk4(x, u, fd=None, h=0.1, mass=MASS, g=G):
+    k1 = f_dyn(x, u, fd, mass, g)
+    k2 = f_dyn(x + 0.5 * h * k1, u, fd, mass, g)
+    k3 = f_dyn(x + 0.5 * h * k2, u, fd, mass, g)
+    k4 = f_dyn(x + h * k3, u, fd, mass, g)
     return x + h / 6 * (k1 + 2 * k2 + 2 * k3 + k4)
 
 

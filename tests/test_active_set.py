@@ -16,6 +16,7 @@ import pytest
 from ndp_nmpc_qd_amd import synth
 from tests import ref_numpy as R
 from tests.emu import emu as E
+from tests.model_cases import CASES, emu_cfg, model_of, oracle_cfg
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 MIXED = dict(pos_sigma=0.5, vel_sigma=1.0, quat_sigma=0.15)        # bench.py's `mixed` workload: ~20 % of the instances hit an input bound
@@ -122,6 +123,60 @@ def test_oracle_twin_takes_the_same_sweeps(oracle):
                 np.testing.assert_allclose(u0, uo[i], rtol=0, atol=1e-6)
             X[i], U[i] = Xo[i], Uo[i]                                    # keep the pair on one trajectory
     assert swo.max() >= 3
+
+
+@pytest.mark.parametrize("N", [13, 20, 40])
+@pytest.mark.parametrize("name", list(CASES))
+def test_oracle_twin_and_certificate_at_other_models(oracle, name, N):
+    """Every model of tests/model_cases.py (cost weights, mass, gravity, input box and dt off the reference's constants), B = 12 of the
+    mixed workload with a supplied fp32 force, two ticks with the sets carried along: status, iteration word, sweeps and sets are the
+    oracle twin's at the same model, numbers to 1e-9 (test_oracle_twin_takes_the_same_sweeps' bar), and every status-0 active-set finish
+    passes the KKT certificate (tests/kkt_certificate.py) of the oracle's QP at that model at 1e-11, test_kkt_certificate.py's bar
+    (measured: 6.2e-12 at worst, at `asym_box`).  No step reports a status or has a velocity near its bound; only `stiff` reaches the
+    interior-point fallback (about half of its steps), and that fallback is held to the twin's at 1e-6."""
+    from tests.kkt_certificate import certificate, worst
+    case, B = CASES[name], 12
+    dt = model_of(case)[6]
+    cfg = emu_cfg(case, N=N, use_fd=True)
+    cfgo = oracle_cfg(oracle, case, N=N, use_fd=True)
+    cfgl = oracle_cfg(oracle, case, N=N, use_fd=True)
+    cfgo.qp_mode = 0
+    f = np.random.default_rng(300 + N).normal(0.0, 0.3, (B, N + 1, 3)).astype(np.float32)
+    f64 = f.astype(np.float64)
+    b0 = synth.make_batch(B, N=N, seed=synth.SEED0 + 7000 + N, dt=dt, **MIXED)
+    X, U = b0["xr"].copy(), b0["ur"].copy()
+    Xo, Uo = X.copy(), U.copy()
+    acts = [E.act_record(N) for _ in range(B)]
+    acto = np.zeros((B, N, 4), dtype=np.int8)
+    n_set = n_ipm = 0
+    w = 0.0
+    for t in range(2):
+        b = synth.make_batch(B, N=N, seed=synth.SEED0 + 7000 + N, dt=dt, t0=0.02 * t, **MIXED)
+        Xp, Up = X.copy(), U.copy()
+        uo, sto, ito, swo = oracle.step_batch_as(cfgo, b["x0"], b["xr"], b["ur"], f64, Xo, Uo, acto)
+        for i in range(B):
+            u0, st, it, *_ = E.rti_step(cfg, b["x0"][i], b["xr"][i], b["ur"][i], f[i], X[i], U[i], act=acts[i])
+            sw, aset = E.act_view(acts[i])
+            assert (st, it, sw) == (sto[i], ito[i], swo[i]), (t, i)
+            assert np.array_equal(aset, acto[i])
+            if it == 0:
+                np.testing.assert_allclose(X[i], Xo[i], rtol=0, atol=1e-9)
+                np.testing.assert_allclose(U[i], Uo[i], rtol=0, atol=1e-9)
+                assert np.array_equal(u0, U[i, 0])
+            else:                                                        # (the interior-point fallback: its own tests' tolerance)
+                n_ipm += 1
+                np.testing.assert_allclose(u0, uo[i], rtol=0, atol=1e-6)
+            if st == 0 and it == 0:
+                qp = oracle.linearize(cfgl, b["x0"][i], b["xr"][i], b["ur"][i], f64[i], Xp[i], Up[i])
+                c = certificate(qp, X[i] - Xp[i], U[i] - Up[i])
+                if not c["flag"]:
+                    n_set += 1
+                    w = max(w, worst(c))
+                    assert worst(c) <= 1e-11, (t, i, worst(c))
+            X[i], U[i] = Xo[i], Uo[i]                                    # keep the pair on one trajectory
+    print(f"{name} N={N}: {n_set} certified set finishes, worst residual {w:.2e}; {n_ipm} interior-point finishes")
+    assert n_set + n_ipm == 2 * B and n_set >= B // 2         # (every step status 0 and unflagged; `stiff` sends about half to the fallback)
+    assert (n_ipm > 0) == (name == "stiff")
 
 
 def test_iterate_outside_the_box_is_solved_where_the_interior_point_loop_gives_up(oracle):

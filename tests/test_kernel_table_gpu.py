@@ -89,23 +89,30 @@ def _launched(eng, rows, waves=None, fusable=None):
         assert fu == fusable, (fu, fusable)
 
 
-def _twin_cfg(oracle, N, n_rti=1, use_fd=False):
-    c = oracle.default_cfg(N=N, n_rti=n_rti, use_fd=use_fd)
+def _twin_cfg(oracle, N, n_rti=1, use_fd=False, cfg=None):
+    c = (cfg or oracle.default_cfg)(N=N, n_rti=n_rti, use_fd=use_fd)
     c.qp_mode = 0
     return c
 
 
-def _against_twin(oracle, b, Xp, Up, acto, out, f=None, n_rti=1, tol=None):
+def _against_twin(oracle, b, Xp, Up, acto, out, f=None, n_rti=1, tol=None, cfg=None, stats=None):
     """The step `out` = (u0, X, U, st, it, sw, act) of a device handle against the twin started from the same iterate and kept sets
     (acto is advanced in place); for one RTI iteration also the certificate of every status-0 instance.  Returns the number of
-    instances the certificate flagged (a velocity within 1e-6 of its bound: held to the twin only)."""
+    instances the certificate flagged (a velocity within 1e-6 of its bound: held to the twin only).  cfg: what builds the oracle's
+    cfg from (N, n_rti, use_fd) -- oracle.default_cfg unless the handle runs another model (tests/model_cases.py).  stats: a dict
+    that keeps the largest figures seen (twin: |X, U - twin's| on set finishes; set / ipm: certificate residuals), for printing."""
     u0, X, U, st, it, sw, act = out
     N = b["xr"].shape[1] - 1
     Xo, Uo = Xp.copy(), Up.copy()
-    _, sto, ito, swo = oracle.step_batch_as(_twin_cfg(oracle, N, n_rti, f is not None), b["x0"], b["xr"], b["ur"], f, Xo, Uo, acto)
+    _, sto, ito, swo = oracle.step_batch_as(_twin_cfg(oracle, N, n_rti, f is not None, cfg), b["x0"], b["xr"], b["ur"], f, Xo, Uo, acto)
     assert np.array_equal(st, sto) and np.array_equal(it, ito), (np.flatnonzero(st != sto), np.flatnonzero(it != ito))
     assert np.array_equal(sw, swo) and np.array_equal(act, acto), (np.flatnonzero(sw != swo),)
     a = it == 0                     # (an interior-point answer: 1e-6 on u0, test_interior_point_always_is_untouched's bar)
+
+    def note(key, v):
+        if stats is not None:
+            stats[key] = max(stats.get(key, 0.0), float(v))
+    note("twin", max(np.abs(X[a] - Xo[a]).max(initial=0.0), np.abs(U[a] - Uo[a]).max(initial=0.0)))
     np.testing.assert_allclose(X[a], Xo[a], rtol=0, atol=TWIN_BAR)
     np.testing.assert_allclose(U[a], Uo[a], rtol=0, atol=TWIN_BAR)
     assert _rel(U[~a][:, 0], Uo[~a][:, 0]) < 1e-6
@@ -113,16 +120,18 @@ def _against_twin(oracle, b, Xp, Up, acto, out, f=None, n_rti=1, tol=None):
     if n_rti != 1:
         return 0
     i = np.flatnonzero(st == 0)
-    cfg = oracle.default_cfg(N=N, use_fd=f is not None)
-    cs = certify_batch(oracle, cfg, b["x0"][i], b["xr"][i], b["ur"][i], None if f is None else f[i], Xp[i], Up[i], X[i], U[i])
-    tol = cfg.tol if tol is None else tol
+    ocfg = (cfg or oracle.default_cfg)(N=N, use_fd=f is not None)
+    cs = certify_batch(oracle, ocfg, b["x0"][i], b["xr"][i], b["ur"][i], None if f is None else f[i], Xp[i], Up[i], X[i], U[i])
+    tol = ocfg.tol if tol is None else tol
     flagged = 0
     for j, c in zip(i, cs):
         if c["flag"]:
             flagged += 1
         elif it[j] == 0:
+            note("set", worst(c))
             assert worst(c) <= AS_BAR, (N, j, worst(c))
         else:
+            note("ipm", worst(c))
             assert worst(c) <= IPM_BAR * tol, (N, j, worst(c))
     return flagged
 
@@ -136,19 +145,21 @@ def _step(eng, b, downwash=False, f=None):
     return (u0, X, U, st, it, sw, act), fo
 
 
-def _ticks_against_twin(ndp, oracle, N, B, n_ticks, rows, seed, waves=None, fusable=None, downwash=False, n_rti=1, **eng_kw):
+def _ticks_against_twin(ndp, oracle, N, B, n_ticks, rows, seed, waves=None, fusable=None, downwash=False, n_rti=1, cfg=None, **eng_kw):
     """n_ticks steps of one handle (the kept sets carried) against the twin; asserts the rows launched.  Returns (flagged, the last
-    step's outputs, its force, its batch)."""
+    step's outputs, its force, its batch).  cfg: as _against_twin's, for a handle whose eng_kw set another model (a dt among them
+    also spaces the batch's reference windows)."""
     eng = ndp.BatchedNMPC(B, N=N, n_rti=n_rti, disturbance=downwash, **eng_kw)
-    b = synth.make_batch(B, N=N, seed=seed, downwash=downwash, **MIXED)
+    bkw = dict(MIXED, dt=eng_kw["dt"]) if "dt" in eng_kw else MIXED
+    b = synth.make_batch(B, N=N, seed=seed, downwash=downwash, **bkw)
     eng.reset(b["xr"], b["ur"])
     Xp, Up = eng.get_iterate()
     acto = np.zeros((B, N, 4), dtype=np.int8)
     flagged = 0
     for t in range(n_ticks):
-        b = synth.make_batch(B, N=N, seed=seed, downwash=downwash, t0=0.02 * t, **MIXED)
+        b = synth.make_batch(B, N=N, seed=seed, downwash=downwash, t0=0.02 * t, **bkw)
         out, f = _step(eng, b, downwash)
-        flagged += _against_twin(oracle, b, Xp, Up, acto, out, f, n_rti)
+        flagged += _against_twin(oracle, b, Xp, Up, acto, out, f, n_rti, cfg=cfg)
         Xp, Up = out[1], out[2]
     _launched(eng, rows, waves, fusable)
     eng.close()

@@ -88,6 +88,60 @@ def test_gauss_newton_blocks(oracle):
         np.testing.assert_allclose(qp["lv"][4], -20 - X[i, 4, 3:6], atol=1e-15)
 
 
+def test_oracle_follows_a_model_other_than_the_default(oracle):
+    """The four tests above and test_oracle_plant_step_vs_numpy_rk4 at a model where nothing equals the reference's constants
+    (tests/model_cases.py: distinct weights, mass 0.9, g 7.0, dt 0.05, an asymmetric input box) and with a force: dynamics, the RK4 step
+    and its sensitivities, the Gauss-Newton blocks, defects and step bounds of linearize, and the plant step against the numpy
+    restatement with mass, g, h and W as parameters -- at those tests' bars."""
+    from tests.model_cases import DERIV_CASES, model_of, oracle_cfg
+    case = DERIV_CASES["distinct"]
+    Qd, Rd, mass, g, lbu, ubu, h = model_of(case)
+    assert (mass, g, h) == (0.9, 7.0, 0.05) and len(set(Qd)) == 10 and len(set(Rd)) == 4 and not np.array_equal(lbu[:3], -ubu[:3])
+    cfg = oracle_cfg(oracle, case, use_fd=True)
+    W = np.diag(np.concatenate([Qd, Rd]))
+    rng = np.random.default_rng(4)
+    for _ in range(10):
+        x, u = _rand_xu(rng)
+        fd = rng.normal(0, 2, 3)
+        np.testing.assert_allclose(oracle.dynamics(cfg, x, u, fd), R.f_dyn(x, u, fd, mass, g), rtol=0, atol=1e-14)
+        xn, A, B = oracle.rk4_sens(cfg, x, u, fd)
+        np.testing.assert_allclose(xn, R.rk4(x, u, fd, h, mass, g), atol=1e-13)
+        np.testing.assert_allclose(A, R.fd_jac(lambda z: R.rk4(z, u, fd, h, mass, g), x), atol=2e-8)
+        np.testing.assert_allclose(B, R.fd_jac(lambda z: R.rk4(x, z, fd, h, mass, g), u), atol=2e-8)
+        np.testing.assert_allclose(A[:, 3:6], np.vstack([h * np.eye(3), np.eye(3), np.zeros((4, 3))]), atol=1e-15)
+    assert np.abs(oracle.dynamics(cfg, x, u, fd) - R.f_dyn(x, u, fd)).max() > 0.1          # (the default model is another one)
+    N = 20
+    b = synth.make_batch(3, seed=6, dt=h)
+    X = b["xr"] + rng.normal(0, 0.05, b["xr"].shape)
+    U = b["ur"] + rng.normal(0, 0.1, b["ur"].shape)
+    f = rng.normal(0, 2, (3, N + 1, 3))
+    for i in range(3):
+        qp = oracle.linearize(cfg, b["x0"][i], b["xr"][i], b["ur"][i], f[i], X[i], U[i])
+        for k in (0, 7, 19):
+            H, gr = R.gn_blocks(X[i, k], U[i, k], b["xr"][i, k], b["ur"][i, k], W, h)
+            np.testing.assert_allclose(qp["Q"][k], H[:10, :10], atol=1e-6)
+            np.testing.assert_allclose(np.diag(qp["Rd"][k]), H[10:, 10:], atol=1e-6)
+            np.testing.assert_allclose(qp["q"][k], gr[:10], atol=1e-6)
+            np.testing.assert_allclose(qp["r"][k], gr[10:], atol=1e-6)
+            np.testing.assert_allclose(qp["b"][k], R.rk4(X[i, k], U[i, k], f[i, k], h, mass, g) - X[i, k + 1], atol=1e-13)
+        He, ge = R.gn_blocks(X[i, N], None, b["xr"][i, N], None, W[:10, :10], 1.0)        # terminal: no dt
+        np.testing.assert_allclose(qp["Q"][N], He, atol=1e-6)
+        np.testing.assert_allclose(qp["q"][N], ge, atol=1e-6)
+        np.testing.assert_allclose(qp["dx0"], b["x0"][i] - X[i, 0], atol=0)
+        np.testing.assert_allclose(qp["lu"], lbu - U[i], atol=1e-15)
+        np.testing.assert_allclose(qp["uu"], ubu - U[i], atol=1e-15)
+        np.testing.assert_allclose(qp["lv"][4], -20 - X[i, 4, 3:6], atol=1e-15)
+    # the plant step (test_relay_and_plant_rows.py's restatement): four RK4 substeps, then the quaternion renormalised
+    x, u, fp = b["x0"].copy(), b["ur"][:, 0, :].copy(), rng.normal(0, 1, (3, 3))
+    x1 = oracle.plant_step(cfg, x.copy(), u, fp, 0.02, 4)
+    for i in range(3):
+        xi = x[i].copy()
+        for _ in range(4):
+            xi = R.rk4(xi, u[i], fp[i], 0.02 / 4, mass, g)
+        xi[6:10] /= np.linalg.norm(xi[6:10])
+        np.testing.assert_allclose(x1[i], xi, atol=1e-13)
+
+
 def test_riccati_vs_dense_kkt(oracle):
     cfg = oracle.default_cfg()
     b = synth.make_batch(4, seed=11)
