@@ -630,6 +630,52 @@ int ndp_plant_rollout_jvp_device(ndp_handle *h, int ticks, double dt, int subste
                                  int n_tan, const void *d_tx0, const void *d_tu, const void *d_tf, void *d_dxs, void *d_xs_check,
                                  void *stream);
 
+/* ---- the closed loop over GIVEN reference windows and forces (the "ext" form), recorded, and its reverse mode: one call per direction
+ * instead of a host loop of control steps, plant steps, tapes and their adjoints.  What tuning the controller's weights on a closed-loop
+ * tracking loss, or shooting over x_0 and the references, calls.  Device pointers only.
+ * ndp_closed_loop_device starts from the engine's current iterate and kept sets, as a loop of ndp_step_device calls would, and for
+ * k = 0..ticks-1 runs the control step from the plant state (x_0, then xs[k-1]) with xr[k], ur[k], f[k] (u0 written straight into us[k]),
+ * then the plant tick with us[k] and fp[k] (held over the tick) into xs[k].  Everything is enqueued on `stream`, nothing is synchronised.
+ *   d_x0 [B][10] fp64; d_xr [ticks][B][N+1][10] fp64; d_ur [ticks][B][N][4] fp64
+ *   d_f  [ticks][B][N+1][3] fp32  the force the controller sees, or NULL (needs use_fd = 1)
+ *   d_fp [ticks][B][3] fp64       the force on the plant, or NULL
+ *   d_xs [ticks][B][10] x_{k+1} and d_us [ticks][B][4] u0_k, required; d_Xs [ticks][B][N+1][10] the step's predicted states, or NULL;
+ *   d_status int32 [ticks][B] the steps' status words, or NULL
+ *   d_tape: ndp_closed_loop_tape_bytes(h, ticks) bytes, or NULL = not recorded.  Slot k (ticks slots of bytes / ticks each) holds what
+ *   step k started from: X_lin [B][N+1][10] fp64 | U_lin [B][N][4] fp64 | act_lin [B][4N] int8 -- the three arrays ndp_step_vjp_device
+ *   takes, as they lie.  The tape is the caller's; x0, xr, ur, f and fp are the caller's arrays and are not copied.
+ * xs, us, Xs, the status words and the engine's iterate and kept sets afterwards are BIT-EQUAL to the loop of ndp_step_device (external
+ * force) and ndp_plant_step_device.  Two launches per tick (the step; the link: plant tick, status, tape slot k+1, Xs[k]), one more for
+ * slot 0; a step through the work list has its own three.
+ *   -1: NULL handle, d_x0, d_xr, d_ur, d_xs or d_us.  -2 with a reason in ndp_last_error, nothing enqueued: ticks < 1, substeps outside
+ *   1..NDP_PLANT_MAX_SUBSTEPS, d_f without use_fd, sensitivities on (as ndp_rollout_device).
+ * ndp_closed_loop_vjp_device: reverse mode of that flight for L = sum_k <gxs[k], x_{k+1}> + <gus[k], u0_k> + <gXs[k], X_k> -- the PARTIAL
+ * derivative every derivative here is: each tick's linearisation point (its tape slot) and final active set are held fixed.  Inputs as the
+ * forward took them, its d_xs, d_us and d_tape (required); upstreams d_gxs [ticks][B][10], d_gus [ticks][B][4], d_gXs [ticks][B][N+1][10]
+ * (NULL = 0, not all NULL); outputs, fp64, each NULL = not written, not all NULL: d_gx0 [B][10], d_gxr, d_gur as xr, ur, d_gf
+ * [ticks][B][N+1][3], d_gfp [ticks][B][3], d_gmodel [B][16]; d_status_check int32 [ticks][B] (optional) the recomputed status words.
+ * Tick by tick from the last, two launches each (the link; the step's adjoint kernel on the handle's workspace) and one behind tick 0:
+ *   lambda = gxs[k] + (gx_p + gx0)            both of tick k + 1, added to each other first; nothing at the last tick
+ *   (gx_p, gu_p, gfp[k]) = the plant tick's adjoint at (x_k, u0_k, fp_k) on lambda      (ndp_plant_rollout_vjp_device's arithmetic)
+ *   (gx0, gxr[k], gur[k], gf[k]) = the step's adjoint on tape slot k with gu0 = gus[k] + gu_p and gX = gXs[k]
+ *   d_gx0 = gx_p + gx0 of tick 0.
+ * d_gmodel: one row per vehicle, no atomics, summed last tick first: columns 0..13 sum_k dL/dQd, dL/dRd of the step (ndp_step_vjp_model_device),
+ * 14 the controller's mass share, 15 the PLANT's mass share -(1/m) sum_k <gfp[k], fp[k]> (exactly 0 with d_fp NULL).  The handle has one
+ * mass: dL/dmass = column 14 + column 15.  Gravity is not differentiated.  With d_gmodel NULL the plain adjoint kernel runs; the other
+ * outputs are bit-equal either way.  Gradients agree with chaining ndp_step_vjp_device and ndp_plant_rollout_vjp_device by hand to rounding
+ * (the plant's adjoint may round differently in the last place from one kernel to the next); forward values are bit-equal.
+ * The engine's iterate, kept sets, sensitivity buffers and the tape are never written; two calls are bit-identical; an output does not
+ * depend on which others are asked for; the workspace is the handle's (first call).  A nonzero status in tick k of vehicle v gives NaN in
+ * v's outputs of ticks <= k, in its d_gx0 and in its d_gmodel row; its later ticks and every other vehicle are unaffected, bit for bit.
+ *   -1 and -2 as the forward; -2 also: the adjoint's own refusals (n_rti != 1, qp_precision != 0, N >= 28), no upstream, no output, d_tape NULL. */
+int ndp_closed_loop_tape_bytes(ndp_handle *h, int ticks, size_t *bytes);
+int ndp_closed_loop_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_xr, const void *d_ur,
+                           const void *d_f, const void *d_fp, void *d_xs, void *d_us, void *d_Xs, void *d_status, void *d_tape, void *stream);
+int ndp_closed_loop_vjp_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_xr, const void *d_ur,
+                               const void *d_f, const void *d_fp, const void *d_xs, const void *d_us, const void *d_tape, const void *d_gxs,
+                               const void *d_gus, const void *d_gXs, void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_gfp,
+                               void *d_gmodel, void *d_status_check, void *stream);
+
 /* ---- f4, the formation form (plant = a1 dynamics + downwash model): the downwash force the neighbour's ACTUAL state
  * puts on the ACTUAL vehicle, and the closed loop around it -- the experiment the downwash prediction is for (the reference has no
  * simulator; the force model is its own network, dnwash_nn_est/downwash_nn.py:22-28, behind the gate of ndp_nmpc_leader_node.py:65-68).

@@ -432,6 +432,86 @@ class BatchedNMPC:
             d(tf, torch.float64, (K, B, T, 3)), d(dxs, torch.float64, (K, B, T, 10)), d(xs_check, torch.float64, (K, B, 10)),
             self._stream(stream)), "ndp_plant_rollout_jvp_device")
 
+    # ---- the closed loop over given windows and forces, recorded, and its reverse mode: one call per direction
+    def closed_loop_tape(self, ticks):
+        """A tape for closed_loop_device over `ticks` ticks: a uint8 CUDA tensor [ticks, slot bytes] (ndp_closed_loop_tape_bytes).  Slot k
+        holds what step k started from; closed_loop_tape_slot gives its three arrays."""
+        import torch
+        n = C.c_size_t(0)
+        self._check(self._lib.ndp_closed_loop_tape_bytes(self._h, int(ticks), C.byref(n)), "ndp_closed_loop_tape_bytes")
+        if n.value != int(ticks) * self._closed_loop_slot_bytes():
+            raise NdpError(f"closed_loop_tape: the library's tape is {n.value} bytes, this binding expects {int(ticks) * self._closed_loop_slot_bytes()}")
+        return torch.empty((int(ticks), self._closed_loop_slot_bytes()), dtype=torch.uint8, device=torch.device("cuda", self.cfg.device))
+
+    def _closed_loop_slot_bytes(self):
+        B, N = self.B, self.N
+        return (B * ((N + 1) * 10 * 8 + N * 4 * 8 + N * 4) + 255) // 256 * 256        # (closed_loop.hip: cl_slot_bytes)
+
+    def closed_loop_tape_slot(self, tape, k):
+        """(X_lin [B,N+1,10] float64, U_lin [B,N,4] float64, act_lin [B,N,4] int8): views of slot k of a tape, as record_tape returns
+        them and step_vjp_device takes them."""
+        import torch
+        B, N = self.B, self.N
+        nx, nu, na = B * (N + 1) * 10 * 8, B * N * 4 * 8, B * N * 4
+        row = tape[k]
+        return (row[:nx].view(torch.float64).view(B, N + 1, 10), row[nx:nx + nu].view(torch.float64).view(B, N, 4),
+                row[nx + nu:nx + nu + na].view(torch.int8).view(B, N, 4))
+
+    def _closed_loop_args(self, who, x0, xr, ur, f, fp):
+        import torch
+        if not (isinstance(xr, torch.Tensor) and xr.dim() == 4 and xr.shape[0] >= 1):
+            raise ValueError(f"{who}: xr must be a [ticks,B,N+1,10] tensor with ticks >= 1")
+        K, B, N, d = int(xr.shape[0]), self.B, self.N, self._dptr
+        return K, [d(x0, torch.float64, (B, 10)), d(xr, torch.float64, (K, B, N + 1, 10)), d(ur, torch.float64, (K, B, N, 4)),
+                   d(f, torch.float32, (K, B, N + 1, 3)), d(fp, torch.float64, (K, B, 3))]
+
+    def _torch_default_wait(self, stream):
+        """stream None or torch's default stream: the call goes on the engine's own stream (the C-ABI's NULL), behind a wait for torch's."""
+        import torch
+        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
+            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+
+    def closed_loop_device(self, x0, xr, ur, xs, us, f=None, fp=None, Xs=None, status=None, tape=None, dt=CP.ts_nmpc, substeps=4,
+                           stream=None):
+        """Enqueues the closed loop over given windows on `stream`, no synchronisation (ndp_closed_loop_device; include/ndp_nmpc.h): from
+        the engine's current iterate and kept sets, per tick the control step at the plant state with xr[k], ur[k] and the float32 force
+        f[k] the controller sees, then the plant tick with u0_k and the force fp[k] on the plant.  x0[B,10], xr[ticks,B,N+1,10],
+        ur[ticks,B,N,4], f[ticks,B,N+1,3] float32 or None, fp[ticks,B,3] or None; outputs xs[ticks,B,10] (x_{k+1}), us[ticks,B,4] (u0_k),
+        optional Xs[ticks,B,N+1,10], status[ticks,B] int32 and tape (closed_loop_tape(ticks): what closed_loop_vjp_device needs).  ticks is
+        read from xr.  Values, status words and the engine's state afterwards are bit-equal to the loop of update_device and
+        ndp_plant_step_device.  stream None or torch's default: the engine's own stream behind a wait for torch's."""
+        import torch
+        K, args = self._closed_loop_args("closed_loop_device", x0, xr, ur, f, fp)
+        B, N, d = self.B, self.N, self._dptr
+        self._torch_default_wait(stream)
+        self._check(self._lib.ndp_closed_loop_device(
+            self._h, K, float(dt), int(substeps), *args, d(xs, torch.float64, (K, B, 10)), d(us, torch.float64, (K, B, 4)),
+            d(Xs, torch.float64, (K, B, N + 1, 10)), d(status, torch.int32, (K, B)),
+            d(tape, torch.uint8, (K, self._closed_loop_slot_bytes())),
+            self._stream(stream)), "ndp_closed_loop_device")
+
+    def closed_loop_vjp_device(self, x0, xr, ur, xs, us, tape, f=None, fp=None, gxs=None, gus=None, gXs=None, gx0=None, gxr=None, gur=None,
+                               gf=None, gfp=None, gmodel=None, status_check=None, dt=CP.ts_nmpc, substeps=4, stream=None):
+        """Enqueues the reverse mode of closed_loop_device on `stream` (ndp_closed_loop_vjp_device; include/ndp_nmpc.h) for
+        L = sum_k <gxs[k], x_{k+1}> + <gus[k], u0_k> + <gXs[k], X_k>: the inputs as the forward took them, its xs, us and tape; upstreams
+        gxs[ticks,B,10], gus[ticks,B,4], gXs[ticks,B,N+1,10] (None = 0, not all None); float64 outputs the caller allocates (None = not
+        written, not all None): gx0[B,10], gxr, gur as xr, ur, gf[ticks,B,N+1,3], gfp[ticks,B,3], gmodel[B,16] (per vehicle, summed over
+        the ticks: dL/dQd [0:10], dL/dRd [10:14], the controller's mass share [14], the plant's [15]); status_check[ticks,B] int32.  Every
+        tick's linearisation point and final set are held fixed.  Nothing of the engine's state or the tape is written; two calls are
+        bit-identical.  stream None or torch's default: the engine's own stream behind a wait for torch's; read the outputs after
+        engine.synchronize()."""
+        import torch
+        K, args = self._closed_loop_args("closed_loop_vjp_device", x0, xr, ur, f, fp)
+        B, N, d = self.B, self.N, self._dptr
+        self._torch_default_wait(stream)
+        self._check(self._lib.ndp_closed_loop_vjp_device(
+            self._h, K, float(dt), int(substeps), *args, d(xs, torch.float64, (K, B, 10)), d(us, torch.float64, (K, B, 4)),
+            d(tape, torch.uint8, (K, self._closed_loop_slot_bytes())),
+            d(gxs, torch.float64, (K, B, 10)), d(gus, torch.float64, (K, B, 4)), d(gXs, torch.float64, (K, B, N + 1, 10)),
+            d(gx0, torch.float64, (B, 10)), d(gxr, torch.float64, (K, B, N + 1, 10)), d(gur, torch.float64, (K, B, N, 4)),
+            d(gf, torch.float64, (K, B, N + 1, 3)), d(gfp, torch.float64, (K, B, 3)), d(gmodel, torch.float64, (B, 16)),
+            d(status_check, torch.int32, (K, B)), self._stream(stream)), "ndp_closed_loop_vjp_device")
+
     @staticmethod
     def _plant_ticks(u, who):
         import torch

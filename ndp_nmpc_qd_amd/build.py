@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libndp_nmpc_hip.so")
 # the translation units (csrc/host.hpp: which one owns what); rti_kernels.hip first, it is by far the longest compile
 UNITS = ["rti_kernels.hip", "ndp_hip.hip", "downwash.hip", "rows.hip", "tick.hip", "exchange.hip", "mlp_vjp.hip", "mlp_jvp.hip", "mlp_train.hip",
-         "mlp_fit.hip", "plant_deriv.hip", "plant_force_deriv.hip"]
+         "mlp_fit.hip", "plant_deriv.hip", "plant_force_deriv.hip", "closed_loop.hip"]
 HOST_ONLY = {"tick.hip"}      # units without a kernel: compiled for the host only, so that no empty code object goes into the library
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))) + [os.path.join("..", "..", "include", "ndp_nmpc.h")]   # every header a unit can include
 # -amdgpu-mfma-vgpr-form: MFMA results go straight to VGPRs.  With the default AGPR form every accumulator that is

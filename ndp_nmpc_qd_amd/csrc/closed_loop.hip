@@ -1,0 +1,336 @@
+// closed_loop.hip -- the closed loop over GIVEN reference windows and forces (the "ext" form), recorded, and its reverse mode, each as one
+// call: ndp_closed_loop_device (control step -> plant tick -> the next tick's x0, `ticks` times, everything enqueued on one stream) and
+// ndp_closed_loop_vjp_device (the gradient of a loss on that flight in x_0, the windows, the forces and the controller's own numbers).
+//
+// The control step and its adjoint are the existing kernels, launched unchanged (enqueue_step; recompute_on_workspace with rti_vjp_kernel /
+// rti_wvjp_kernel).  What is new is everything BETWEEN two of them, one launch per tick and direction:
+//   closed_loop_fwd_link_kernel  behind step k: the plant tick (plant_tick: ndp_plant_step_device's bits) from x_k and u0_k into xs[k], the
+//                                status words into their log, and the engine's post-step iterate and kept set copied into tape slot k + 1
+//                                (and X into Xs[k]) in 16-byte pieces
+//   closed_loop_rev_link_kernel  in front of the adjoint of tick k: lambda = gxs_k + (gx_p + gx0) of tick k + 1, the plant tick's adjoint
+//                                (the arithmetic of plant_rollout_vjp_kernel's tick body), gu0 = gus_k + gu_p for the step's adjoint,
+//                                gfp[k], tick k + 1's model-gradient row folded into the total, and tape slot k copied into the adjoint's
+//                                workspace; a tail launch behind tick 0 forms gx0 = gx_p + gx0 and the last fold.  Each launch also sees
+//                                the status words tick k + 1's adjoint recomputed: where nonzero, gfp[k + 1] and the plant's mass share
+//                                become NaN (ClRev::st_prev)
+// One lane per vehicle in 64-lane workgroups for the plant (plant_deriv.hip's shape: a long serial fp64 chain per lane, spread over many
+// CUs); the copies run on further workgroups of the same launch, grid-stride.  No LDS, no atomics, no scratch.
+#include <hip/hip_runtime.h>
+
+#include "../../include/ndp_nmpc.h"
+#include "host.hpp"
+#include "plant_dyn.hpp"
+#include "plant_adj.hpp"
+
+namespace ndp {
+
+enum { CL_LANES = 64, CL_MAX_COPY_BLOCKS = 2048 };
+
+struct ClCopy {                // one contiguous run, moved in 16-byte pieces (both ends 16-byte aligned), its tail byte by byte; dst null: none
+    const unsigned char *src;
+    unsigned char *dst;
+    size_t bytes;
+};
+
+struct ClPlant {               // the plant's shape and the model's two numbers (plant_deriv.hip: PlantSeq)
+    int B, sub, plant_blocks;  // plant_blocks: the launch's first workgroups, one lane per vehicle; the rest copy
+    double h, inv_mass, g;
+};
+
+struct ClFwd {
+    ClPlant p;
+    const double *xin, *u, *fp;     // x_k [B][10], u0_k [B][4], fp_k [B][3] or null
+    double *xout;                   // xs[k]
+    const int *st_src;              // the step's status words ...
+    int *st_dst;                    // ... into d_status[k], or null
+    ClCopy cp[3];                   // iterate -> tape slot, kept set -> tape slot, X -> Xs[k]
+};
+
+struct ClRev {
+    ClPlant p;                      // plant_blocks workgroups, one lane per vehicle, in the tail launch too
+    int tail;                       // 1: the launch behind tick 0 (no plant: gx0 and the last fold)
+    const double *xin, *u, *fp;     // x_k, u0_k, fp_k (null: none)
+    const double *gxs, *gus;        // the upstreams of x_{k+1} and u0_k, or null
+    const double *c_p, *c_s;        // what tick k + 1 handed back: its plant's gx_p and its step's gx0 (null at the last tick)
+    double *gxp, *gu0;              // out: gx_p, and gu0 = gus_k + gu_p for the step's adjoint
+    double *gfp;                    // out: gfp[k], or null
+    double *gm_tot;                 // [B][16] the model gradient's total, or null
+    const double *gm_row;           // [B][16] tick k + 1's row (the step's rti_wvjp_kernel), null at the last tick
+    double *gx0;                    // tail: d_gx0, or null
+    const int *st_prev;             // tick k + 1's recomputed status words (its adjoint has run), null at the last tick: where nonzero,
+    double *gfp_prev;               // gfp[k + 1] (or null) and the plant's mass share become NaN -- the plant's adjoint alone would not
+                                    // make them so at the vehicle's LAST failed tick (the force's gradient does not read the state)
+    ClCopy cp[2];                   // tape slot k -> the adjoint's workspace: iterate, kept set
+};
+
+__device__ __forceinline__ void cl_copy(const ClCopy &c, size_t i0, size_t stride)
+{
+    if (!c.dst) return;
+    const size_t pieces = c.bytes >> 4, tail = c.bytes & 15;
+    const uint4 *s = reinterpret_cast<const uint4 *>(c.src);
+    uint4 *d = reinterpret_cast<uint4 *>(c.dst);
+    for (size_t i = i0; i < pieces; i += stride) d[i] = s[i];
+    if (i0 < tail) c.dst[(pieces << 4) + i0] = c.src[(pieces << 4) + i0];
+}
+
+__global__ __launch_bounds__(CL_LANES) void closed_loop_fwd_link_kernel(ClFwd a)
+{
+    if ((int)blockIdx.x >= a.p.plant_blocks) {
+        const size_t i0 = (size_t)((int)blockIdx.x - a.p.plant_blocks) * CL_LANES + threadIdx.x;
+        const size_t stride = (size_t)((int)gridDim.x - a.p.plant_blocks) * CL_LANES;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) cl_copy(a.cp[j], i0, stride);
+        return;
+    }
+    const int v = (int)(blockIdx.x * CL_LANES + threadIdx.x);
+    if (v >= a.p.B) return;
+    double xv[10], uv[4];
+    plant_ld_row<5>(a.xin + (size_t)v * 10, xv);
+    plant_ld_row<2>(a.u + (size_t)v * 4, uv);
+    plant_tick(xv, uv, a.fp, (size_t)v * 3, a.p.h, a.p.sub, a.p.inv_mass, a.p.g);
+    plant_st_row<5>(a.xout + (size_t)v * 10, xv);
+    if (a.st_dst) a.st_dst[v] = a.st_src[v];
+}
+
+// The additions, in this order (include/ndp_nmpc.h states it): lambda = gxs_k + (gx_p + gx0), both of tick k + 1; gu0 = gus_k + gu_p;
+// the model gradient last tick first: total = row_{K-1}, then + row_{K-2}, ... (columns 0..14), column 15 = p_{K-1} + p_{K-2} + ... with
+// p_k = -(1/m) <gfp_k, fp_k>; d_gx0 = gx_p + gx0 of tick 0.  A null upstream adds nothing (the other operand as it is).
+__global__ __launch_bounds__(CL_LANES) void closed_loop_rev_link_kernel(ClRev a)
+{
+    if ((int)blockIdx.x >= a.p.plant_blocks) {
+        const size_t i0 = (size_t)((int)blockIdx.x - a.p.plant_blocks) * CL_LANES + threadIdx.x;
+        const size_t stride = (size_t)((int)gridDim.x - a.p.plant_blocks) * CL_LANES;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) cl_copy(a.cp[j], i0, stride);
+        return;
+    }
+    const int v = (int)(blockIdx.x * CL_LANES + threadIdx.x);
+    if (v >= a.p.B) return;
+    double lam[10], gk[10];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) lam[i] = 0.0;
+    if (a.c_p) {
+        plant_ld_row<5>(a.c_p + (size_t)v * 10, lam);
+        plant_ld_row<5>(a.c_s + (size_t)v * 10, gk);
+#pragma unroll
+        for (int i = 0; i < 10; ++i) lam[i] = lam[i] + gk[i];
+    }
+    double p15 = 0.0;
+    const bool bad = a.st_prev && a.st_prev[v] != 0;
+    if (bad && a.gfp_prev) {
+        const double nan = __builtin_nan("");
+        a.gfp_prev[(size_t)v * 3] = nan; a.gfp_prev[(size_t)v * 3 + 1] = nan; a.gfp_prev[(size_t)v * 3 + 2] = nan;
+    }
+    if (a.tail) {
+        if (a.gx0) plant_st_row<5>(a.gx0 + (size_t)v * 10, lam);
+    } else {
+        double xin[10], y[10], uv[4], acc[3], guv[4] = {0.0, 0.0, 0.0, 0.0}, gacc[3] = {0.0, 0.0, 0.0};
+        plant_ld_row<5>(a.xin + (size_t)v * 10, xin);
+        plant_ld_row<2>(a.u + (size_t)v * 4, uv);
+        if (a.gxs) {
+            plant_ld_row<5>(a.gxs + (size_t)v * 10, gk);
+#pragma unroll
+            for (int i = 0; i < 10; ++i) lam[i] = gk[i] + lam[i];
+        }
+        plant_acc(a.fp, (size_t)v * 3, a.p.inv_mass, a.p.g, acc);
+#pragma unroll
+        for (int i = 0; i < 10; ++i) y[i] = xin[i];
+        for (int s = 0; s < a.p.sub; ++s) plant_rk4(y, uv, acc, a.p.h);
+        const double n = plant_renorm(y);                    // y[6..9]: the tick's output quaternion
+        const double d = y[6] * lam[6] + y[7] * lam[7] + y[8] * lam[8] + y[9] * lam[9];
+#pragma unroll
+        for (int i = 6; i < 10; ++i) lam[i] = (lam[i] - y[i] * d) / n;
+        for (int s = a.p.sub - 1; s >= 0; --s) {
+#pragma unroll
+            for (int i = 0; i < 10; ++i) y[i] = xin[i];
+            for (int j = 0; j < s; ++j) plant_rk4(y, uv, acc, a.p.h);
+            plant_rk4_vjp(y, uv, acc, a.p.h, lam, guv, gacc);
+        }
+        plant_st_row<5>(a.gxp + (size_t)v * 10, lam);
+        if (a.gus) {
+            double up[4];
+            plant_ld_row<2>(a.gus + (size_t)v * 4, up);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) guv[i] = up[i] + guv[i];
+        }
+        plant_st_row<2>(a.gu0 + (size_t)v * 4, guv);
+        const double g0 = gacc[0] * a.p.inv_mass, g1 = gacc[1] * a.p.inv_mass, g2 = gacc[2] * a.p.inv_mass;
+        if (a.gfp) { a.gfp[(size_t)v * 3] = g0; a.gfp[(size_t)v * 3 + 1] = g1; a.gfp[(size_t)v * 3 + 2] = g2; }
+        if (a.fp) p15 = -a.p.inv_mass * (g0 * a.fp[(size_t)v * 3] + g1 * a.fp[(size_t)v * 3 + 1] + g2 * a.fp[(size_t)v * 3 + 2]);
+    }
+    if (a.gm_tot) {
+        double tot[16], row[16];
+        if (a.gm_row) {
+            plant_ld_row<8>(a.gm_tot + (size_t)v * 16, tot);
+            plant_ld_row<8>(a.gm_row + (size_t)v * 16, row);
+#pragma unroll
+            for (int i = 0; i < 15; ++i) tot[i] = tot[i] + row[i];
+            tot[15] = bad ? __builtin_nan("") : tot[15] + p15;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 15; ++i) tot[i] = 0.0;
+            tot[15] = p15;
+        }
+        plant_st_row<8>(a.gm_tot + (size_t)v * 16, tot);
+    }
+}
+
+}  // namespace ndp
+
+using namespace ndp;
+
+// ---- the tape: per tick one slot = X_lin [B][N+1][10] fp64 | U_lin [B][N][4] fp64 | act_lin [B][4N] int8, padded to 256 bytes
+static size_t cl_iterate_bytes(const ndp_handle *h) { return (nxs(h) + nus(h)) * 8; }
+static size_t cl_slot_bytes(const ndp_handle *h) { return up256(cl_iterate_bytes(h) + act_bytes(h)); }
+
+static ClPlant cl_plant(const ndp_handle *h, double dt, int substeps, bool plant)
+{
+    const int B = h->cfg.batch;
+    return ClPlant{B, substeps, plant ? (B + CL_LANES - 1) / CL_LANES : 0, dt / substeps, 1.0 / h->cfg.mass, h->cfg.gravity};   // (as launch_plant, rows.hip)
+}
+
+static unsigned cl_copy_blocks(size_t bytes)
+{
+    const size_t per_block = (size_t)CL_LANES * 4 * 16;       // four pieces per lane before the grid-stride loop comes round
+    const size_t n = (bytes + per_block - 1) / per_block;
+    return (unsigned)(n < 1 ? 1 : n > CL_MAX_COPY_BLOCKS ? CL_MAX_COPY_BLOCKS : n);
+}
+
+// the refusals the two calls share, nothing enqueued: -2 with the reason in ndp_last_error
+static int cl_check(ndp_handle *h, const char *who, int ticks, int substeps, const void *d_f)
+{
+    if (h->sens_level) return sens_refuse(h, who);
+    if (ticks < 1) { h->err = std::string(who) + ": ticks must be >= 1, got " + std::to_string(ticks); return -2; }
+    if (substeps < 1 || substeps > NDP_PLANT_MAX_SUBSTEPS) {
+        h->err = std::string(who) + ": substeps must be 1..16 (NDP_PLANT_MAX_SUBSTEPS), got " + std::to_string(substeps);
+        return -2;
+    }
+    if (d_f && !h->cfg.use_fd) { h->err = std::string(who) + ": a disturbance force (d_f) needs use_fd = 1 (NDP model)"; return -2; }
+    return 0;
+}
+
+extern "C" {
+
+int ndp_closed_loop_tape_bytes(ndp_handle *h, int ticks, size_t *bytes)
+{
+    if (!h || !bytes) return -1;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (ticks < 1) { h->err = "ndp_closed_loop_tape_bytes: ticks must be >= 1, got " + std::to_string(ticks); return -2; }
+    *bytes = (size_t)ticks * cl_slot_bytes(h);
+    return 0;
+}
+
+int ndp_closed_loop_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_xr, const void *d_ur,
+                           const void *d_f, const void *d_fp, void *d_xs, void *d_us, void *d_Xs, void *d_status, void *d_tape, void *stream)
+{
+    Entry g(h, d_x0 && d_xr && d_ur && d_xs && d_us, stream);
+    if (g.rc) return g.rc;
+    int rc = cl_check(h, "ndp_closed_loop_device", ticks, substeps, d_f);
+    if (rc) return rc;
+    hipStream_t s = g.s;
+    const size_t B = h->cfg.batch, slot = cl_slot_bytes(h), itb = cl_iterate_bytes(h), ab = act_bytes(h);
+    const unsigned char *eng_it = (const unsigned char *)h->dX, *eng_act = (const unsigned char *)h->dAct;    // (dU lies right behind dX)
+    unsigned char *tape = (unsigned char *)d_tape;
+    const unsigned cb = cl_copy_blocks(itb + ab + (d_Xs ? nxs(h) * 8 : 0));
+    if (tape) {                    // slot 0: what the first step starts from
+        ClFwd a{};
+        a.p = cl_plant(h, dt, substeps, false);
+        a.cp[0] = ClCopy{eng_it, tape, itb};
+        a.cp[1] = ClCopy{eng_act, tape + itb, ab};
+        hipLaunchKernelGGL(closed_loop_fwd_link_kernel, dim3(cb), dim3(CL_LANES), 0, s, a);
+        NDP_HIP(h, hipGetLastError());
+    }
+    const double *xs = (const double *)d_xs;
+    for (int k = 0; k < ticks; ++k) {
+        const double *xk = k ? xs + (size_t)(k - 1) * B * NX : (const double *)d_x0;
+        double *u0 = (double *)d_us + (size_t)k * B * NU;
+        rc = enqueue_step(h, xk, (const double *)d_xr + (size_t)k * nxs(h), (const double *)d_ur + (size_t)k * nus(h),
+                          d_f ? (const float *)d_f + (size_t)k * nfs(h) : nullptr, Neigh{}, u0, nullptr, s);
+        if (rc) return rc;
+        ClFwd a{};
+        a.p = cl_plant(h, dt, substeps, true);
+        a.xin = xk; a.u = u0; a.fp = d_fp ? (const double *)d_fp + (size_t)k * B * 3 : nullptr;
+        a.xout = (double *)d_xs + (size_t)k * B * NX;
+        a.st_src = h->lastStatus; a.st_dst = d_status ? (int *)d_status + (size_t)k * B : nullptr;
+        if (tape && k + 1 < ticks) {
+            a.cp[0] = ClCopy{eng_it, tape + (size_t)(k + 1) * slot, itb};
+            a.cp[1] = ClCopy{eng_act, tape + (size_t)(k + 1) * slot + itb, ab};
+        }
+        if (d_Xs) a.cp[2] = ClCopy{eng_it, (unsigned char *)d_Xs + (size_t)k * nxs(h) * 8, nxs(h) * 8};
+        hipLaunchKernelGGL(closed_loop_fwd_link_kernel, dim3((unsigned)a.p.plant_blocks + cb), dim3(CL_LANES), 0, s, a);
+        NDP_HIP(h, hipGetLastError());
+    }
+    return g.noted(0);
+}
+
+int ndp_closed_loop_vjp_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_xr, const void *d_ur,
+                               const void *d_f, const void *d_fp, const void *d_xs, const void *d_us, const void *d_tape, const void *d_gxs,
+                               const void *d_gus, const void *d_gXs, void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_gfp,
+                               void *d_gmodel, void *d_status_check, void *stream)
+{
+    const char *who = "ndp_closed_loop_vjp_device";
+    Entry g(h, d_x0 && d_xr && d_ur && d_xs && d_us, stream);
+    if (g.rc) return g.rc;
+    int rc = cl_check(h, who, ticks, substeps, d_f);
+    if (rc) return rc;
+    const char *own = nullptr;
+    if (!d_tape) own = "d_tape is required (the forward's, recorded by ndp_closed_loop_device)";
+    else if (!d_gxs && !d_gus && !d_gXs) own = "no upstream gradient (d_gxs, d_gus and d_gXs all NULL)";
+    else if (!d_gx0 && !d_gxr && !d_gur && !d_gf && !d_gfp && !d_gmodel) own = "no output asked for (d_gx0, d_gxr, d_gur, d_gf, d_gfp and d_gmodel all NULL)";
+    const std::string why = recompute_refusal(h->cfg, "adjoint", Tape{d_x0, d_xr, d_ur, d_f, d_tape ? d_tape : d_x0, d_tape ? d_tape : d_x0,
+                                                                          nullptr, nullptr, nullptr}, own);
+    if (!why.empty()) { h->err = std::string(who) + ": " + why; return -2; }
+    hipStream_t s = g.s;
+    const size_t B = h->cfg.batch, slot = cl_slot_bytes(h), itb = cl_iterate_bytes(h), ab = act_bytes(h);
+    if ((rc = recompute_workspace(h))) return rc;
+    if (!h->dClWs) NDP_HIP(h, hipMalloc((void **)&h->dClWs, B * (NU + NX + NX + 16) * 8));
+    double *ws_gu0 = h->dClWs, *ws_gxp = ws_gu0 + B * NU, *ws_gx0 = ws_gxp + B * NX, *ws_gm = ws_gx0 + B * NX;
+    const unsigned char *tape = (const unsigned char *)d_tape;
+    const bool model = d_gmodel != nullptr;
+    const unsigned cb = cl_copy_blocks(itb + ab);
+    // where tick k's adjoint leaves its recomputed status words: the caller's log, or the workspace's
+    auto st_of = [&](int k) { return d_status_check ? (const int *)d_status_check + (size_t)k * B : (const int *)h->dVjpSt; };
+    for (int k = ticks - 1; k >= 0; --k) {
+        const bool last = k == ticks - 1;
+        const double *xk = k ? (const double *)d_xs + (size_t)(k - 1) * B * NX : (const double *)d_x0;
+        const double *u0 = (const double *)d_us + (size_t)k * B * NU;
+        ClRev a{};
+        a.p = cl_plant(h, dt, substeps, true);
+        a.xin = xk; a.u = u0; a.fp = d_fp ? (const double *)d_fp + (size_t)k * B * 3 : nullptr;
+        a.gxs = d_gxs ? (const double *)d_gxs + (size_t)k * B * NX : nullptr;
+        a.gus = d_gus ? (const double *)d_gus + (size_t)k * B * NU : nullptr;
+        a.c_p = last ? nullptr : ws_gxp; a.c_s = last ? nullptr : ws_gx0;
+        a.gxp = ws_gxp; a.gu0 = ws_gu0;
+        a.gfp = d_gfp ? (double *)d_gfp + (size_t)k * B * 3 : nullptr;
+        a.gm_tot = (double *)d_gmodel; a.gm_row = last ? nullptr : ws_gm;
+        a.st_prev = last ? nullptr : st_of(k + 1); a.gfp_prev = !last && d_gfp ? (double *)d_gfp + (size_t)(k + 1) * B * 3 : nullptr;
+        a.cp[0] = ClCopy{tape + (size_t)k * slot, (unsigned char *)h->dVjp, itb};
+        a.cp[1] = ClCopy{tape + (size_t)k * slot + itb, (unsigned char *)h->dVjpAct, ab};
+        hipLaunchKernelGGL(closed_loop_rev_link_kernel, dim3((unsigned)a.p.plant_blocks + cb), dim3(CL_LANES), 0, s, a);
+        NDP_HIP(h, hipGetLastError());
+        const Tape t{xk, (const double *)d_xr + (size_t)k * nxs(h), (const double *)d_ur + (size_t)k * nus(h),
+                     d_f ? (const float *)d_f + (size_t)k * nfs(h) : nullptr, nullptr, nullptr, nullptr, nullptr,
+                     d_status_check ? (int *)d_status_check + (size_t)k * B : nullptr};
+        VjpArgs va{ws_gu0, d_gXs ? (const double *)d_gXs + (size_t)k * nxs(h) : nullptr, nullptr, ws_gx0,
+                   d_gxr ? (double *)d_gxr + (size_t)k * nxs(h) : nullptr, d_gur ? (double *)d_gur + (size_t)k * nus(h) : nullptr,
+                   d_gf ? (double *)d_gf + (size_t)k * nfs(h) : nullptr};
+        double *gm = ws_gm;
+        if (model) rc = recompute_on_workspace(h, s, t, recompute_kernel(RC_WVJP, true), recompute_kernel(RC_WVJP, false), &va, &gm);
+        else rc = recompute_on_workspace(h, s, t, recompute_kernel(RC_VJP, true), recompute_kernel(RC_VJP, false), &va, nullptr);
+        if (rc) return rc;
+    }
+    if (d_gx0 || d_gfp || model) { // behind tick 0: d_gx0 = gx_p + gx0, tick 0's row into the model gradient, a failed tick 0's gfp
+        ClRev a{};
+        a.p = cl_plant(h, dt, substeps, true);
+        a.tail = 1;
+        a.c_p = ws_gxp; a.c_s = ws_gx0;
+        a.gx0 = (double *)d_gx0;
+        a.gm_tot = (double *)d_gmodel; a.gm_row = ws_gm;
+        a.st_prev = st_of(0); a.gfp_prev = (double *)d_gfp;
+        hipLaunchKernelGGL(closed_loop_rev_link_kernel, dim3((unsigned)a.p.plant_blocks), dim3(CL_LANES), 0, s, a);
+        NDP_HIP(h, hipGetLastError());
+    }
+    return g.noted(0);
+}
+
+}  // extern "C"

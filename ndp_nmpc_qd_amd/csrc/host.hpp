@@ -23,9 +23,11 @@
 //   plant_force_deriv.hip  the derivatives of the downwash force on the plant (ndp_plant_force_vjp_device, ndp_plant_force_jvp_device and
 //                    their multi forms); hosts mlp_vjp.hip's backward pass (mlp_vjp_dev.hpp, mlp_vjp_back.inc, mlp_vjp_part.inc) and
 //                    mlp_jvp.hip's direction (mlp_jvp_dev.hpp, mlp_jvp_direction.inc) behind a row loader of its own
+//   closed_loop.hip  the closed loop over given windows in one call per direction (ndp_closed_loop_device, ndp_closed_loop_vjp_device): the
+//                    step and its adjoint are the existing kernels, launched unchanged; the two link kernels between them live here
 //   exchange.hip     peer-mapped windows (ndp_peer_*), the RCCL exchange (ndp_xchg_*) and the remote tick one control period ahead
 // A kernel sits with the host code that launches it; device code that two units' kernels inline is a header (mlp_tile.hpp, ref_point.hpp,
-// tick_wave.hpp, mlp_vjp_dev.hpp, mlp_jvp_dev.hpp, plant_dyn.hpp), and so are the argument blocks the host fills (kern_args.hpp).
+// tick_wave.hpp, mlp_vjp_dev.hpp, mlp_jvp_dev.hpp, plant_dyn.hpp, plant_adj.hpp), and so are the argument blocks the host fills (kern_args.hpp).
 // The functions declared below are NDP_HIDDEN: the library exports the C-ABI of include/ndp_nmpc.h and nothing more.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -77,6 +79,9 @@ struct ndp_handle {
     double *dVjp = nullptr;
     int *dVjpSt = nullptr;
     signed char *dVjpAct = nullptr;
+    // ndp_closed_loop_vjp_device's workspace (first call), what one tick hands the next: gu0 [B][4] | gx_p [B][10] | the step's gx0 [B][10] |
+    // the step's gmodel row [B][16] (closed_loop.hip)
+    double *dClWs = nullptr;
     // mlp_vjp.hip: layers 2 and 3 transposed, one fp32 record per matrix instruction of the backward pass (FRT_TOTAL floats, written with
     // dFrag by both ndp_set_mlp_weights forms); ndp_downwash_vjp_device's per-workgroup partial weight gradients [mlp_vjp_groups][NDP_MLP_NPARAM]
     // (ndp_downwash_multi_vjp_device shares them: it never launches more workgroups than that)
@@ -241,6 +246,14 @@ struct StepOut {               // where a step's status / iteration counts go an
     const TickArgs *tick = nullptr;      // the launch is a whole control tick (rti_kernel<..., TICK>): list advance + estimator inside
 };
 
+// What the derivative kernels that recompute a recorded step share (rti_vjp_kernel, rti_wvjp_kernel, rti_jvp_kernel).  Their entries take
+// the step's inputs and the tape it started from, never written (the recompute advances a copy: two calls on one tape give the same result),
+// and optionally return the recomputed u0 and status for the caller to check against the recorded ones.
+struct Tape {
+    const void *x0, *xr, *ur, *f, *X_lin, *U_lin, *act_lin;
+    void *u0_check, *status_check;
+};
+
 enum RecomputeId { RC_WVJP, RC_JVP, RC_VJP };   // the derivative kernels that recompute a recorded step (rti_kernels.hip: recompute_kernel)
 
 // ---- host functions one unit calls in another (no locking, no sync: the caller holds h->mu).  C linkage like the entry points they
@@ -269,6 +282,8 @@ NDP_HIDDEN int launch_rti(ndp_handle *h, const double *d_x0, const double *d_xr,
 NDP_HIDDEN int enqueue_step(ndp_handle *h, const double *d_x0, const double *d_xr, const double *d_ur, const float *d_f, const Neigh &nb,
                             double *d_u0, double *d_dbg, hipStream_t s, const StepOut *so = nullptr);
 NDP_HIDDEN int ensure_slots(ndp_handle *h);
+NDP_HIDDEN int recompute_workspace(ndp_handle *h);
+NDP_HIDDEN int recompute_on_workspace(ndp_handle *h, hipStream_t s, const Tape &t, const void *fn20, const void *fn0, void *a1, void *a2);
 // downwash.hip
 NDP_HIDDEN int launch_plant_force(ndp_handle *h, const double *d_x, const int *d_index, int gate, double scale, double *d_f, double *d_xy,
                                   hipStream_t s);
@@ -299,6 +314,8 @@ NDP_HIDDEN hipError_t plant_force_deriv_prepare(void);
 NDP_HIDDEN int peer_mapped(const void *p);
 NDP_HIDDEN void launch_pack_pv_list(const double *base, size_t pitch, int np1, double *pv, size_t B, hipStream_t s);
 }  // extern "C"
+// ndp_hip.hip (C++ linkage: it returns a string)
+NDP_HIDDEN std::string recompute_refusal(const ndp_cfg &c, const char *noun, const Tape &t, const char *own);
 // tick.hip (C++ linkage: it returns a TickPre)
 NDP_HIDDEN TickPre tick_pre(const ndp_handle *h, bool adv, const double *t, double t_all, bool est, const double *x_odom, const double *vz,
                             const double *throttle, double *pv = nullptr);

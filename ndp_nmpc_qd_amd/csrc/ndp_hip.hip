@@ -206,7 +206,7 @@ int ndp_destroy(ndp_handle *h)
     h->pool.reset();
     void *ptrs[] = {h->dForceAB[0], h->dForceAB[1], h->dProto, h->dRingX, h->dTraj, h->dTables, h->dStamps, h->dRelay, h->dThr, h->sThr, h->dKC, h->dForce, h->dFrag,
                     h->dIn, h->dOut, h->sdbg, h->dQctr, h->dQids, h->dTickIndex, h->dTickThrust, h->dAct,
-                    h->dSensU0, h->dSensU, h->dSensX, h->dPSensXr, h->dPSensUr, h->dPSensF, h->dVjp, h->dVjpSt, h->dVjpAct, h->dFragT, h->dGwPart, h->dFitPart, h->dTrain};
+                    h->dSensU0, h->dSensU, h->dSensX, h->dPSensXr, h->dPSensUr, h->dPSensF, h->dVjp, h->dVjpSt, h->dVjpAct, h->dClWs, h->dFragT, h->dGwPart, h->dFitPart, h->dTrain};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &sl : h->slot) {
@@ -1091,17 +1091,11 @@ void *ndp_device_sens_f(ndp_handle *h) { return h ? h->dPSensF : nullptr; }
 // ---- adjoint of the control step (rti_vjp_kernel, RtiWave::vjp_out)
 void *ndp_device_active_set(ndp_handle *h) { return h ? h->dAct : nullptr; }
 
-// What the derivative kernels that recompute a recorded step share (rti_vjp_kernel, rti_wvjp_kernel, rti_jvp_kernel).  Their entries take
-// the step's inputs and the tape it started from, never written (the recompute advances a copy: two calls on one tape give the same result),
-// and optionally return the recomputed u0 and status for the caller to check against the recorded ones.
-struct Tape {
-    const void *x0, *xr, *ur, *f, *X_lin, *U_lin, *act_lin;
-    void *u0_check, *status_check;
-};
-
-// The refusals all of those entries make, in their order: the configuration's and the required pointers', then `own` -- the entry's
-// refusals of its own arguments, or null -- then the force's.  Empty: none.  noun: what the entry's texts call the derivative.
-static std::string recompute_refusal(const ndp_cfg &c, const char *noun, const Tape &t, const char *own)
+// The refusals all of the entries that recompute a recorded step make (struct Tape, host.hpp), in their order: the configuration's and the
+// required pointers', then `own` -- the entry's refusals of its own arguments, or null -- then the force's.  Empty: none.  noun: what the
+// entry's texts call the derivative.
+extern "C++" {
+std::string recompute_refusal(const ndp_cfg &c, const char *noun, const Tape &t, const char *own)
 {
     const std::string the = std::string("the ") + noun;
     if (c.n_rti != 1) return the + " needs n_rti = 1 (the derivative of the step's one QP)";
@@ -1112,25 +1106,26 @@ static std::string recompute_refusal(const ndp_cfg &c, const char *noun, const T
     if (t.f && !c.use_fd) return "a disturbance force needs use_fd = 1 (NDP model)";
     return "";
 }
+}  // extern "C++"
 
-// The launch: the handle's workspace (first call), the tape copied into it on the entry's stream, the step's kernel arguments on that
-// copy, then the kernel for the horizon (fn20: the compile-time N = 20, else fn0) with a1, a2 behind them (a2: null if it takes two).
-static int recompute_launch(ndp_handle *h, Entry &g, const Tape &t, const void *fn20, const void *fn0, void *a1, void *a2)
+// The launch, in two parts.  recompute_workspace: the handle's workspace (first call).  recompute_on_workspace: the step's kernel arguments
+// on the workspace's copy of the tape (t.X_lin, U_lin, act_lin are NOT read: whoever calls it has put them there on stream s), then the
+// kernel for the horizon (fn20: the compile-time N = 20, else fn0) with a1, a2 behind them (a2: null if it takes two).
+int recompute_workspace(ndp_handle *h)
+{
+    const size_t B = h->cfg.batch;
+    if (!h->dVjp) NDP_HIP(h, hipMalloc((void **)&h->dVjp, (nxs(h) + nus(h) + B * NU) * 8));
+    if (!h->dVjpSt) NDP_HIP(h, hipMalloc((void **)&h->dVjpSt, B * 2 * 4));
+    if (!h->dVjpAct) NDP_HIP(h, hipMalloc((void **)&h->dVjpAct, act_bytes(h)));
+    return 0;
+}
+
+int recompute_on_workspace(ndp_handle *h, hipStream_t s, const Tape &t, const void *fn20, const void *fn0, void *a1, void *a2)
 {
     const ndp_cfg &c = h->cfg;
     const size_t B = c.batch;
-    hipStream_t s = g.s;
-    if (!h->dVjp) {
-        NDP_HIP(h, hipMalloc((void **)&h->dVjp, (nxs(h) + nus(h) + B * NU) * 8));
-        NDP_HIP(h, hipMalloc((void **)&h->dVjpSt, B * 2 * 4));
-        NDP_HIP(h, hipMalloc((void **)&h->dVjpAct, act_bytes(h)));
-    }
     double *X = h->dVjp, *U = X + nxs(h), *u0 = U + nus(h);
     int *st = h->dVjpSt, *it = st + B;
-    NDP_HIP(h, hipMemcpyAsync(X, t.X_lin, nxs(h) * 8, hipMemcpyDeviceToDevice, s));
-    NDP_HIP(h, hipMemcpyAsync(U, t.U_lin, nus(h) * 8, hipMemcpyDeviceToDevice, s));
-    if (t.act_lin) NDP_HIP(h, hipMemcpyAsync(h->dVjpAct, t.act_lin, act_bytes(h), hipMemcpyDeviceToDevice, s));
-    else NDP_HIP(h, hipMemsetAsync(h->dVjpAct, 0, act_bytes(h), s));
     BatchPtrs bp{h->dKC, h->dTables, (const double *)t.x0, (const double *)t.xr, (const double *)t.ur, (const float *)t.f, X, U,
                  t.u0_check ? (double *)t.u0_check : u0, t.status_check ? (int *)t.status_check : st, it, nullptr, nullptr, nullptr, nullptr,
                  (size_t)(c.N + 1) * NX, (size_t)c.N * NU, (size_t)NX, nullptr, nullptr, nullptr, c.mass, 0, h->dVjpAct};
@@ -1140,6 +1135,21 @@ static int recompute_launch(ndp_handle *h, Entry &g, const Tape &t, const void *
     void *args[] = {&ka, a1, a2};
     NDP_HIP(h, hipLaunchKernel(fn, dim3((unsigned)((B + W - 1) / W)), dim3(64 * W), args, (size_t)h->lds_per_wave * sizeof(double) * W, s));
     NDP_HIP(h, hipGetLastError());
+    return 0;
+}
+
+// The entries below: the workspace, the tape copied into it on the entry's stream, the launch.
+static int recompute_launch(ndp_handle *h, Entry &g, const Tape &t, const void *fn20, const void *fn0, void *a1, void *a2)
+{
+    hipStream_t s = g.s;
+    int rc = recompute_workspace(h);
+    if (rc) return rc;
+    double *X = h->dVjp, *U = X + nxs(h);
+    NDP_HIP(h, hipMemcpyAsync(X, t.X_lin, nxs(h) * 8, hipMemcpyDeviceToDevice, s));
+    NDP_HIP(h, hipMemcpyAsync(U, t.U_lin, nus(h) * 8, hipMemcpyDeviceToDevice, s));
+    if (t.act_lin) NDP_HIP(h, hipMemcpyAsync(h->dVjpAct, t.act_lin, act_bytes(h), hipMemcpyDeviceToDevice, s));
+    else NDP_HIP(h, hipMemsetAsync(h->dVjpAct, 0, act_bytes(h), s));
+    if ((rc = recompute_on_workspace(h, s, t, fn20, fn0, a1, a2))) return rc;
     return g.noted(0);
 }
 

@@ -47,6 +47,10 @@ forces in one launch, differentiable in the initial state, the inputs and the fo
 plant_rollout_vjp_device, plant_rollout_jvp_device).  plant_step is its one-tick case, the piece that chains with the control_step*
 Functions: u0 -> plant_step -> the next tick's x0, with the values ndp_plant_step_device gives bit for bit.
 
+closed_loop (behind plant_rollout_jvp) is the whole closed loop over given windows as ONE autograd Function: control step -> plant tick -> the
+next tick's x0, `ticks` times in one call (BatchedNMPC.closed_loop_device), and one call back (closed_loop_vjp_device) for the gradients of
+x_0, the windows, both forces, Qd, Rd and the mass -- what the chain control_step_trajectory -> plant_step gives link by link.
+
 plant_force / plant_force_jvp (at the end of this file) are the downwash force the neighbours' actual states put on the plant, differentiable
 in the states and the network's weights (BatchedNMPC.plant_force_multi_device, plant_force_multi_vjp_device, plant_force_multi_jvp_device):
 f = plant_force(engine, x, other_index); x = plant_step(engine, x, u, f) is a differentiable formation tick on the plant side.
@@ -1059,6 +1063,80 @@ def plant_rollout_jvp(engine, x0, u, tangents, f=None, dt=CP.ts_nmpc, substeps=4
     if default:
         engine.synchronize()
     return xs, dxs if had else dxs[:, :, 0]
+
+
+# ---------------------------------------------------------------------------------------------- the closed loop, one call per direction
+class ClosedLoopFunction(torch.autograd.Function):
+    """forward(x0, engine, xr, ur, f, fp, Qd, Rd, mass, dt, substeps) -> (xs [ticks,B,10], us [ticks,B,4], Xs [ticks,B,N+1,10]) float64:
+    BatchedNMPC.closed_loop_device with its tape; backward: ONE BatchedNMPC.closed_loop_vjp_device call for the gradients of x0, xr, ur, f,
+    fp, Qd, Rd and mass (only those that require one are computed)."""
+
+    @staticmethod
+    def forward(ctx, x0, engine, xr, ur, f, fp, Qd, Rd, mass, dt, substeps):
+        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t  # noqa: E731
+        x0, xr, ur, fd, fpd = det(x0), det(xr), det(ur), det(f), det(fp)
+        ctx.model = _install_model(engine, Qd, Rd, mass)
+        ctx.set_materialize_grads(False)       # (an output the loss does not use arrives as None: the call's NULL upstream)
+        K, B, N = xr.shape[0], xr.shape[1], xr.shape[2] - 1
+        stream, default = _cuda_stream(x0)
+        if default:
+            stream.synchronize()
+        new = lambda *s: torch.empty(s, dtype=torch.float64, device=x0.device)  # noqa: E731
+        xs, us, Xs, tape = new(K, B, 10), new(K, B, 4), new(K, B, N + 1, 10), engine.closed_loop_tape(K)
+        engine.closed_loop_device(x0, xr, ur, xs, us, f=fd, fp=fpd, Xs=Xs, tape=tape, dt=dt, substeps=substeps, stream=stream)
+        if default:                            # torch's default stream: the loop went on the engine's own (the C-ABI's NULL)
+            engine.synchronize()
+        ctx.engine, ctx.dt, ctx.substeps = engine, dt, substeps
+        ctx.have = (fd is not None, fpd is not None)
+        ctx.f_dtype = f.dtype if isinstance(f, torch.Tensor) else None
+        ctx.like = tuple(None if not isinstance(t, torch.Tensor) else (t.shape, t.dtype, t.device) for t in (Qd, Rd, mass))
+        ctx.save_for_backward(x0, xr, ur, xs, us, tape, *(t for t in (fd, fpd) if t is not None))
+        return xs, us, Xs
+
+    @staticmethod
+    def backward(ctx, g_xs, g_us, g_Xs):
+        x0, xr, ur, xs, us, tape, *rest = ctx.saved_tensors
+        fd = rest[0] if ctx.have[0] else None
+        fpd = rest[-1] if ctx.have[1] else None
+        eng, need = ctx.engine, ctx.needs_input_grad
+        want = (need[0], need[2], need[3], need[4] and fd is not None, need[5] and fpd is not None,
+                any(n and like is not None for n, like in zip(need[6:9], ctx.like)))
+        if (g_xs is None and g_us is None and g_Xs is None) or not any(want):
+            return (None,) * 11
+        if _engine_model(eng) != ctx.model:
+            raise RuntimeError("ClosedLoopFunction: the engine's model (Qd, Rd, mass) was changed between this forward and its backward "
+                               "(the backward recomputes every step from the engine's model): run the backward before the next forward "
+                               "with other values, or set the model back first")
+        K, B, N = xr.shape[0], xr.shape[1], xr.shape[2] - 1
+        ups = tuple(None if g is None else g.to(torch.float64).contiguous() for g in (g_xs, g_us, g_Xs))
+        gx0, gxr, gur, gf, gfp, gm = (torch.empty(*s, dtype=torch.float64, device=x0.device) if w else None for w, s in zip(
+            want, ((B, 10), (K, B, N + 1, 10), (K, B, N, 4), (K, B, N + 1, 3), (K, B, 3), (B, 16))))
+        stream, default = _cuda_stream(x0)
+        eng.closed_loop_vjp_device(x0, xr, ur, xs, us, tape, f=fd, fp=fpd, gxs=ups[0], gus=ups[1], gXs=ups[2], gx0=gx0, gxr=gxr, gur=gur, gf=gf,
+                                   gfp=gfp, gmodel=gm, dt=ctx.dt, substeps=ctx.substeps, stream=stream)
+        if default:
+            eng.synchronize()
+        out = [None, None, None]
+        if gm is not None:
+            # a failed vehicle (NaN in its row) contributes nothing: control_step_tunable's convention
+            tot = torch.where(torch.isfinite(gm).all(dim=1, keepdim=True), gm, torch.zeros_like(gm)).sum(dim=0)
+            for i, (like, need_i, part) in enumerate(zip(ctx.like, need[6:9], (tot[0:10], tot[10:14], tot[14:15] + tot[15:16]))):
+                if like is not None and need_i:
+                    out[i] = part.reshape(like[0]).to(device=like[2], dtype=like[1])
+        return (gx0, None, gxr, gur, None if gf is None else gf.to(ctx.f_dtype), gfp, out[0], out[1], out[2], None, None)
+
+
+def closed_loop(engine, x0, xr, ur, f=None, fp=None, Qd=None, Rd=None, mass=None, dt=CP.ts_nmpc, substeps=4):
+    """(xs, us, Xs) = the closed loop of the engine's controller and plant over given windows, `ticks` ticks in one call: from x0 [B,10] and
+    the engine's warm start, per tick the control step with xr[k] [B,N+1,10], ur[k] [B,N,4] and the force f[k] [B,N+1,3] (float32; None:
+    none) the controller sees, then the plant tick with u0_k and the force fp[k] [B,3] (None: none) on the plant.  xs [ticks,B,10] the
+    states x_{k+1}, us [ticks,B,4] the inputs u0_k, Xs [ticks,B,N+1,10] the steps' predicted states -- the values the chain
+    control_step_trajectory -> plant_step gives, bit for bit, and like it every call advances the engine's iterate and kept sets.
+    Differentiable in x0, xr, ur, f, fp and -- given as float64 tensors, installed as control_step_tunable installs them -- the cost weights
+    Qd [10], Rd [4] and the mass (its gradient: the controller's share plus the plant's); the backward is ONE call, with every tick's
+    linearisation point and final active set held fixed as in every derivative here.  Gravity is not differentiated."""
+    return ClosedLoopFunction.apply(x0, engine, xr, ur, f, fp, Qd, Rd, mass, float(dt), int(substeps))
+
 
 
 # ---------------------------------------------------------------------------------------------- the downwash force on the plant, differentiated
