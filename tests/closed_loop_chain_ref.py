@@ -27,17 +27,18 @@ from tests import plant_deriv_ref as P
 DT, SUBSTEPS = CP.ts_nmpc, 4
 
 
-def twin_cfg(oracle, N):
-    """The oracle's twin of the device's default QP mode with the force on."""
-    cfg = oracle.default_cfg(N=N, use_fd=True)
-    cfg.qp_mode = 0
+def twin_cfg(oracle, N, cfg=None):
+    """The oracle's twin of the device's default QP mode with the force on; cfg (an OrcCfg of horizon N): at that model, else the default's."""
+    cfg = oracle.default_cfg(N=N, use_fd=True) if cfg is None else F.copy_cfg(cfg)
+    assert cfg.N == N
+    cfg.use_fd, cfg.qp_mode = 1, 0
     return cfg
 
 
-def gate_open(other_k, idx, x):
+def gate_open(other_k, idx, x, r_horiz=DP.r_horiz):
     """[B] bool: a neighbour, and its window's node 0 strictly inside r_horiz of the ego state's xy (orc_downwash's rule)."""
     d = other_k[np.clip(idx, 0, None)][:, 0, :2] - x[:, :2]
-    return (idx >= 0) & (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] < DP.r_horiz ** 2)
+    return (idx >= 0) & (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] < r_horiz ** 2)
 
 
 def net_rows(other_k, xr_k, idx):
@@ -54,28 +55,30 @@ def margins(blob, other, xr, idx):
     return np.stack(out)
 
 
-def _force(oracle, blob, other_k, xr_k, idx, x, net64):
+def _force(oracle, blob, other_k, xr_k, idx, x, net64, r_horiz=DP.r_horiz):
     """The ndp form's force [B,N+1,3] as float64 values: the oracle's fp32 network (what the device runs), or -- net64, for finite
-    differences, which fp32 rounding would drown -- the float64 network this module differentiates.  Gate on x's xy."""
+    differences, which fp32 rounding would drown -- the float64 network this module differentiates.  Gate on x's xy at r_horiz."""
     if not net64:
         return oracle.downwash_batch(np.asarray(blob, dtype=np.float32), other_k[np.clip(idx, 0, None)].copy(), xr_k, x[:, :2].copy(),
-                                     r_horiz=DP.r_horiz).astype(np.float64) * (idx >= 0)[:, None, None]
+                                     r_horiz=r_horiz).astype(np.float64) * (idx >= 0)[:, None, None]
     import torch
     z = net_rows(other_k, xr_k, idx)
     f = MV.forward64(MV.params64(blob), torch.tensor(z.reshape(-1, 6)))[0].numpy().reshape(z.shape[:2] + (3,))
-    return f * gate_open(other_k, idx, x)[:, None, None]
+    return f * gate_open(other_k, idx, x, r_horiz)[:, None, None]
 
 
-def nominal_cpu(oracle, x0, xr, ur, fp, f=None, other=None, idx=None, blob=None, net64=False, restart=None, dt=DT, substeps=SUBSTEPS):
+def nominal_cpu(oracle, x0, xr, ur, fp, f=None, other=None, idx=None, blob=None, net64=False, restart=None, dt=DT, substeps=SUBSTEPS,
+                cfg=None, r_horiz=DP.r_horiz):
     """The chain on the oracle (step_batch_as in the device's QP mode, plant_step, downwash_batch): reset to (xr_0, ur_0), one warm-up step
     on tick 0's inputs, then K ticks.  x0 [B,10], xr [K,B,N+1,10], ur [K,B,N,4], fp [K,B,3]; ext form: f [K,B,N+1,3]; ndp form: other
     [K,rows,N+1,10], idx int32 [B], blob [17859] (any float dtype; net64: see _force).  restart: a record whose pre-step iterate and kept
     set every tick starts from instead of what the tick before left (the rule of the finite-difference tests: the linearisation point does
-    not move with the perturbation).  Returns the record, a dict of arrays with the tick axis first."""
+    not move with the perturbation).  cfg: the model (an OrcCfg of this horizon; None: the default's), r_horiz: the gate's radius.
+    Returns the record, a dict of arrays with the tick axis first."""
     K, B, N = xr.shape[0], x0.shape[0], xr.shape[2] - 1
-    cfg = twin_cfg(oracle, N)
+    cfg = twin_cfg(oracle, N, cfg)
     ndp = other is not None
-    force = (lambda k, x: _force(oracle, blob, other[k], xr[k], idx, x, net64)) if ndp else (lambda k, x: np.asarray(f[k], dtype=np.float64))
+    force = (lambda k, x: _force(oracle, blob, other[k], xr[k], idx, x, net64, r_horiz)) if ndp else (lambda k, x: np.asarray(f[k], dtype=np.float64))
     X, U, act = xr[0].copy(), ur[0].copy(), np.zeros((B, N, 4), dtype=np.int8)
     if restart is None:
         oracle.step_batch_as(cfg, x0, xr[0], ur[0], force(0, x0), X, U, act)
@@ -88,7 +91,7 @@ def nominal_cpu(oracle, x0, xr, ur, fp, f=None, other=None, idx=None, blob=None,
         fk = force(k, x)
         rec["x"].append(x.copy()); rec["force"].append(fk); rec["Xpre"].append(X.copy()); rec["Upre"].append(U.copy())
         rec["act_pre"].append(act.copy())
-        rec["open"].append(gate_open(other[k], idx, x) if ndp else np.ones(B, dtype=bool))
+        rec["open"].append(gate_open(other[k], idx, x, r_horiz) if ndp else np.ones(B, dtype=bool))
         u0, st, it, _ = oracle.step_batch_as(cfg, x, xr[k], ur[k], fk, X, U, act)
         x = oracle.plant_step(cfg, x.copy(), u0, np.ascontiguousarray(fp[k]), dt, substeps)
         rec["act"].append(act.copy()); rec["u0"].append(u0); rec["X"].append(X.copy()); rec["st"].append(st); rec["it"].append(it)
@@ -109,11 +112,13 @@ def loss(rec, G, H, A):
     return (G * rec["x"][1:]).sum(axis=(0, 2)) + (H * rec["u0"]).sum(axis=(0, 2)) + (A * rec["X"]).sum(axis=(0, 2, 3))
 
 
-def systems(oracle, rec, which, dt=DT, substeps=SUBSTEPS):
+def systems(oracle, rec, which, dt=DT, substeps=SUBSTEPS, cfg=None):
     """The expensive part, once per record: per tick the plant's Jacobian [len(which), 10, 17] at (x_k, u0_k, fp_k) and per (tick,
-    vehicle) fixed_set_ref.jvp_system at the pre-step iterate with the final set.  What `reverse` and `forward` take."""
+    vehicle) fixed_set_ref.jvp_system at the pre-step iterate with the final set.  What `reverse` and `forward` take.  cfg: the model the
+    record was made at (an OrcCfg of this horizon with the force on; None: the default's)."""
     K, N = rec["xr"].shape[0], rec["xr"].shape[2] - 1
-    cfg = oracle.default_cfg(N=N, use_fd=True)
+    cfg = oracle.default_cfg(N=N, use_fd=True) if cfg is None else cfg
+    assert cfg.N == N and cfg.use_fd
     which = [int(v) for v in which]
     J = [P.jacobian(rec["x"][k][which], rec["u0"][k][which][None], rec["fp"][k][which][None], dt, substeps, cfg.mass, cfg.g)
          for k in range(K)]

@@ -59,11 +59,11 @@ def loss_at(oracle, cfg, rec, G, H, A, dt=R.DT, substeps=R.SUBSTEPS):
     return L, stable
 
 
-def model_fd(oracle, rec, G, H, A, col, rel=1e-5):
+def model_fd(oracle, rec, G, H, A, col, rel=1e-5, cfg=None, dt=R.DT, substeps=R.SUBSTEPS):
     """(fd [B], stable [B]): the central difference of loss_at in model entry col (0..9 Qd, 10..13 Rd, 14: the mass -- controller AND
-    plant, one handle has one mass), step rel x the entry."""
+    plant, one handle has one mass), step rel x the entry of the model the record was made at (cfg; None: the default's)."""
     N = rec["xr"].shape[2] - 1
-    base = R.twin_cfg(oracle, N)
+    base = R.twin_cfg(oracle, N, cfg)
     val = base.Qd[col] if col < 10 else base.Rd[col - 10] if col < 14 else base.mass
     h = rel * val
     out, stable = [], np.ones(rec["x"].shape[1], dtype=bool)
@@ -75,7 +75,7 @@ def model_fd(oracle, rec, G, H, A, col, rel=1e-5):
             c.Rd[col - 10] = val + sgn * h
         else:
             c.mass = val + sgn * h
-        L, ok = loss_at(oracle, c, rec, G, H, A)
+        L, ok = loss_at(oracle, c, rec, G, H, A, dt, substeps)
         out.append(L)
         stable &= ok
     return (out[0] - out[1]) / (2 * h), stable

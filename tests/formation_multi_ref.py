@@ -50,29 +50,29 @@ def _noise(rng, f):
     return np.where(f != 0, f + rng.uniform(-1.0, 1.0, f.shape) * NET_BAR * np.maximum(1.0, np.abs(f)), f).astype(f.dtype)
 
 
-def true_force_multi(blob, x, idx, gate=True, scale=1.0, rng=None):
+def true_force_multi(blob, x, idx, gate=True, scale=1.0, rng=None, r_horiz=DP.r_horiz):
     """The force on the plant: the fp64 sum, in slot order, of formation_ref.true_force per slot (idx int32[B, K]; < 0: empty)."""
     f = None
     for k in range(idx.shape[1]):
-        fk = _noise(rng, F.true_force(blob, x, idx[:, k], gate, scale))
+        fk = _noise(rng, F.true_force(blob, x, idx[:, k], gate, scale, r_horiz))
         f = fk if f is None else f + fk
     return f
 
 
-def oracle_prediction(blob, xr, idx1, ego_xy):
+def oracle_prediction(blob, xr, idx1, ego_xy, r_horiz=DP.r_horiz):
     """One slot's prediction (idx1 int32[B]; < 0: empty): oracle.downwash_batch of the neighbour's reference window against the ego's,
     behind the gate on (window node 0 xy, ego_xy); zeros for an empty slot.  float32 [B, N+1, 3]."""
     has = idx1 >= 0
     o = np.where(has, idx1, np.arange(len(idx1)))
-    fk = O.downwash_batch(blob, xr[o].copy(), xr, ego_xy, r_horiz=DP.r_horiz)
+    fk = O.downwash_batch(blob, xr[o].copy(), xr, ego_xy, r_horiz=r_horiz)
     return np.where(has[:, None, None], fk, np.float32(0.0)).astype(np.float32)
 
 
-def prediction_multi(blob, xr, idx, ego_xy, rng=None):
+def prediction_multi(blob, xr, idx, ego_xy, rng=None, r_horiz=DP.r_horiz):
     """The controller's prediction: the fp32 sum, in slot order, of oracle_prediction per slot, each slot behind its own gate."""
     f = None
     for k in range(idx.shape[1]):
-        fk = _noise(rng, oracle_prediction(blob, xr, idx[:, k], ego_xy))
+        fk = _noise(rng, oracle_prediction(blob, xr, idx[:, k], ego_xy, r_horiz))
         f = fk if f is None else (f + fk).astype(np.float32)
     return f
 
@@ -82,17 +82,20 @@ def pred_index(tr, mode):
     return {"blind": None, "slot0": tr["other_index"][:, :1], "all": tr["other_index"]}[mode]
 
 
-def cpu_rollout(blob, tr, xr_all, ur_all, mode, ticks=TICKS, gate=True, scale=1.0, dt=CP.ts_nmpc, substeps=4, rng=None):
-    """-> (states [ticks, B, 10], u0 [ticks, B, 4], force [ticks, B, 3], status [ticks, B]) from x = xr[0][:, 0]."""
+def cpu_rollout(blob, tr, xr_all, ur_all, mode, ticks=TICKS, gate=True, scale=1.0, dt=CP.ts_nmpc, substeps=4, rng=None, cfg=None,
+                r_horiz=DP.r_horiz, x_init=None):
+    """-> (states [ticks, B, 10], u0 [ticks, B, 4], force [ticks, B, 3], status [ticks, B]) from x = x_init (None: xr[0][:, 0]).  cfg: the model of
+    controller and plant (None: the oracle's default), r_horiz: the radius of every gate."""
     idx, pidx = tr["other_index"], pred_index(tr, mode)
-    cfg = O.default_cfg(use_fd=pidx is not None)
+    cfg = F._model(cfg)
+    cfg.use_fd = int(pidx is not None)
     X, U = xr_all[0].copy(), ur_all[0].copy()
-    x = xr_all[0][:, 0].copy()
+    x = xr_all[0][:, 0].copy() if x_init is None else np.array(x_init, dtype=np.float64)
     log, log_u, log_f, log_s = [], [], [], []
     for k in range(ticks):
         xr, ur = xr_all[k], ur_all[k]
-        f = true_force_multi(blob, x, idx, gate, scale, rng)
-        fp = None if pidx is None else prediction_multi(blob, xr, pidx, x[:, 0:2].copy() if gate else None, rng)
+        f = true_force_multi(blob, x, idx, gate, scale, rng, r_horiz)
+        fp = None if pidx is None else prediction_multi(blob, xr, pidx, x[:, 0:2].copy() if gate else None, rng, r_horiz)
         u0, st, _ = O.step_batch(cfg, x, xr, ur, fp, X, U)
         x = O.plant_step(cfg, x.copy(), u0, f, dt, substeps)
         log.append(x.copy()); log_u.append(u0); log_f.append(f); log_s.append(st)

@@ -36,38 +36,51 @@ def set_trajectory(eng, tr):
     eng.ref_set_trajectory(tr["coeff_x"], tr["coeff_y"], tr["coeff_z"], tr["coeff_yaw"], tr["time_cum"], tr["time_seg"], tr["final_pt"])
 
 
-def windows(tr, ticks, t0=0.0, dt=CP.ts_nmpc):
+def _model(cfg):
+    """cfg (an OrcCfg or None: the oracle's default) with the force off, a copy."""
+    c = O.default_cfg() if cfg is None else type(cfg).from_buffer_copy(cfg)
+    c.use_fd = 0
+    return c
+
+
+def windows(tr, ticks, t0=0.0, dt=CP.ts_nmpc, cfg=None):
     """The oracle's reference windows at t0 + k dt, k = 0 .. ticks (one more than the ticks: node 0 of window k + 1 is where the vehicle
-    should be after tick k): xr [ticks+1, B, N+1, 10], ur [ticks+1, B, N, 4]."""
+    should be after tick k): xr [ticks+1, B, N+1, 10], ur [ticks+1, B, N, 4].  cfg: the model (the flatness map reads mass and g)."""
     B = tr["coeff_x"].shape[0]
+    c = _model(cfg)
     coeff = np.concatenate([tr["coeff_" + a].reshape(B, N_SEG, -1) for a in ("x", "y", "z", "yaw")], axis=2)
-    out = [O.ref_window(coeff, tr["time_cum"], tr["time_seg"], tr["final_pt"], np.full(B, t0 + k * dt)) for k in range(ticks + 1)]
+    out = [O.ref_window(coeff, tr["time_cum"], tr["time_seg"], tr["final_pt"], np.full(B, t0 + k * dt), N=c.N, dt=c.dt, mass=c.mass, g=c.g)
+           for k in range(ticks + 1)]
     return np.stack([o[0] for o in out]), np.stack([o[1] for o in out])
 
 
-def true_force(blob, x, idx, gate=True, scale=1.0):
-    """The force on the plant: the network at the actual relative state (fp64 difference rounded to fp32), strict gate on the actual xy."""
+def true_force(blob, x, idx, gate=True, scale=1.0, r_horiz=DP.r_horiz):
+    """The force on the plant: the network at the actual relative state (fp64 difference rounded to fp32), strict gate on the actual xy
+    at r_horiz."""
     has = idx >= 0
     o = np.where(has, idx, np.arange(len(idx)))
     d = x[o] - x
     f = O.mlp_forward(blob, d[:, 0:6].astype(np.float32)).astype(np.float64) * scale
-    open_ = has & ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] < DP.r_horiz ** 2) if gate else True)
+    open_ = has & ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] < r_horiz ** 2) if gate else True)
     return np.where(open_[:, None], f, 0.0)
 
 
-def cpu_rollout(blob, tr, xr_all, ur_all, compensate, ticks=TICKS, gate=True, scale=1.0, dt=CP.ts_nmpc, substeps=4):
-    """-> (states [ticks, B, 10], u0 [ticks, B, 4], force [ticks, B, 3], status [ticks, B]) from x = xr[0][:, 0]."""
+def cpu_rollout(blob, tr, xr_all, ur_all, compensate, ticks=TICKS, gate=True, scale=1.0, dt=CP.ts_nmpc, substeps=4, cfg=None,
+                r_horiz=DP.r_horiz, x_init=None):
+    """-> (states [ticks, B, 10], u0 [ticks, B, 4], force [ticks, B, 3], status [ticks, B]) from x = x_init (None: xr[0][:, 0]).  cfg: the model of
+    controller and plant (None: the oracle's default), r_horiz: the radius of both gates."""
     idx = tr["other_index"]
-    cfg = O.default_cfg(use_fd=bool(compensate))
+    cfg = _model(cfg)
+    cfg.use_fd = int(bool(compensate))
     X, U = xr_all[0].copy(), ur_all[0].copy()
-    x = xr_all[0][:, 0].copy()
+    x = xr_all[0][:, 0].copy() if x_init is None else np.array(x_init, dtype=np.float64)
     log, log_u, log_f, log_s = [], [], [], []
     for k in range(ticks):
         xr, ur = xr_all[k], ur_all[k]
-        f = true_force(blob, x, idx, gate, scale)
+        f = true_force(blob, x, idx, gate, scale, r_horiz)
         fp = None
         if compensate:      # the reference's rule: the neighbour's window against the ego odometry (ndp_nmpc_leader_node.py:60-76)
-            fp = O.downwash_batch(blob, xr[idx].copy(), xr, x[:, 0:2].copy() if gate else None, r_horiz=DP.r_horiz)
+            fp = O.downwash_batch(blob, xr[idx].copy(), xr, x[:, 0:2].copy() if gate else None, r_horiz=r_horiz)
         u0, st, _ = O.step_batch(cfg, x, xr, ur, fp, X, U)
         x = O.plant_step(cfg, x.copy(), u0, f, dt, substeps)
         log.append(x.copy()); log_u.append(u0); log_f.append(f); log_s.append(st)

@@ -64,9 +64,9 @@ def draw_own_rows(rng, blob, B, K, np1, want_open=None, r_h=1.0):
     return z, off, int(redrawn), rounds
 
 
-def own_row_case(seed, blob, B, K, N, gates, xr=None):
+def own_row_case(seed, blob, B, K, N, gates, xr=None, r_h=1.0):
     """One own-row case: gates 'open' (no ego_xy) or 'mixed' (about a third of the slots open, every K > 1 case with instances whose slot
-    0 is closed and a later slot open).  xr: the ego windows [B,N+1,10] (None: N(0, 1)).  Returns a dict of numpy arrays: other [B K,N+1,10], index int32 [B,K] (= i K + k), xr, ego_xy or
+    0 is closed and a later slot open).  xr: the ego windows [B,N+1,10] (None: N(0, 1)); r_h: the gate's radius.  Returns a dict of numpy arrays: other [B K,N+1,10], index int32 [B,K] (= i K + k), xr, ego_xy or
     None, z [B,K,N+1,6] (what the network sees, recomputed from other - xr), open [B,K], redrawn, rounds."""
     rng = np.random.default_rng(seed)
     np1 = N + 1
@@ -75,7 +75,7 @@ def own_row_case(seed, blob, B, K, N, gates, xr=None):
         want = rng.random((B, K)) < 0.36
         if K > 1:
             want[0, 0], want[0, 1:] = False, True              # slot 0 closed, the later ones open: for certain
-    z, off, redrawn, rounds = draw_own_rows(rng, blob, B, K, np1, want)
+    z, off, redrawn, rounds = draw_own_rows(rng, blob, B, K, np1, want, r_h)
     xr = rng.normal(0.0, 1.0, (B, np1, 10)) if xr is None else np.array(xr, dtype=np.float64)
     other = rng.normal(0.0, 1.0, (B, K, np1, 10))
     other[..., :6] = xr[:, None, :, :6] + z
@@ -84,9 +84,10 @@ def own_row_case(seed, blob, B, K, N, gates, xr=None):
         ego_xy = xr[:, 0, :2] + off
         d = other[:, :, 0, :2] - ego_xy[:, None]
         d2 = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]
-        assert not ((d2 > 0.9 * 1.0) & (d2 < 1.1 * 1.0)).any()          # no gate within 10 % of r_horiz^2 (r_horiz = 1)
-        open_ = d2 < 1.0
+        r2 = r_h * r_h
+        assert not ((d2 > 0.9 * r2) & (d2 < 1.1 * r2)).any()            # no gate within 10 % of r_horiz^2
+        open_ = d2 < r2
         assert np.array_equal(open_, want)
     z = other[..., :6] - xr[:, None, :, :6]                    # as the device forms it (the sum above is rounded)
     return dict(other=other.reshape(B * K, np1, 10), index=np.arange(B * K, dtype=np.int32).reshape(B, K), xr=xr, ego_xy=ego_xy, z=z,
-                open=open_, redrawn=redrawn, rounds=rounds)
+                open=open_, redrawn=redrawn, rounds=rounds, d2=None if want is None else d2)

@@ -2,7 +2,8 @@
 case into BatchedNMPC keyword overrides (engine_kw), an oracle.OrcCfg (oracle_cfg) or an emulator NdpCfg (emu_cfg) -- all three through
 the same `_fields`, so they cannot drift apart.  A case is a dict of the entries it changes: Qd [10], Rd [4], mass, g, lbu [4], ubu [4], dt
 -- and ts_nmpc beside a dt that is no whole multiple of the default 0.02 s: ndp_create wants dt = k ts_nmpc (the reference list keeps one
-point per ts_nmpc and a window node is every k-th entry).  ts_nmpc is a field of ndp_cfg alone; the oracle has no list.
+point per ts_nmpc and a window node is every k-th entry).  ts_nmpc is a field of ndp_cfg alone; the oracle has no list.  r_horiz, the
+gate's radius, likewise: the oracle takes it as an argument of downwash_batch (radius_of hands it out).
 
 The defaults are restated here as literals (the reference's constants: nmpc_body_rate_ctl.py / params/nmpc_params.py);
 tests/test_model_envelope.py checks them against what the library, the oracle and the emulator hand out."""
@@ -11,6 +12,8 @@ import numpy as np
 QD0 = (300.0, 300.0, 400.0, 10.0, 10.0, 10.0, 0.0, 10.0, 10.0, 100.0)
 RD0 = (10.0, 10.0, 10.0, 5.0)
 MASS0, G0, DT0 = 1.4844, 9.81, 0.1
+R_HORIZ0 = 1.0
+ENGINE_ONLY = ("ts_nmpc", "r_horiz")                            # fields of ndp_cfg that OrcCfg does not have
 LBU0, UBU0 = (-6.0, -6.0, -6.0, 0.0), (6.0, 6.0, 6.0, 9.81 / 0.36)
 
 _rng = np.random.default_rng(20231213 + 7000)                   # `tuned`: one seeded draw, made at import, never again
@@ -32,14 +35,20 @@ CASES = {
 }
 # the derivative cases' first model: distinct weights and mass with the asymmetric box, dt 0.05 and g 7.0 together
 DERIV_CASES = {"distinct": dict(_DISTINCT, **_ASYM, dt=0.05, ts_nmpc=0.01, g=7.0), "zero_w": CASES["zero_w"]}
+# the plant side and the closed loop (tests/plant_side_cases.py): the models whose mass and g reach the plant's derivatives, and the
+# closed loop's -- distinct weights and mass with the asymmetric box and g 7.0 at the default dt (the one call's windows are 0.1 s apart)
+PLANT_CASES = {"light_lowg": CASES["light_lowg"], "m09": dict(mass=0.9)}
+LOOP_CASE = dict(_DISTINCT, **_ASYM, g=7.0)
+# gate radii whose squares, 0.5625 and 2.25, are exact in binary: d^2 == r^2 can be met exactly, as at r = 1
+RADII = (0.75, 1.5)
 
 
 def _fields(case, gravity_name):
     """The case's entries under the names of a cfg struct that calls gravity `gravity_name`."""
-    unknown = set(case) - {"Qd", "Rd", "mass", "g", "lbu", "ubu", "dt", "ts_nmpc"}
+    unknown = set(case) - {"Qd", "Rd", "mass", "g", "lbu", "ubu", "dt", "ts_nmpc", "r_horiz"}
     assert not unknown, unknown
-    ndp = gravity_name == "gravity"                             # (ndp_cfg's names; the oracle's OrcCfg says g and has no ts_nmpc)
-    return {(gravity_name if k == "g" else k): v for k, v in case.items() if ndp or k != "ts_nmpc"}
+    ndp = gravity_name == "gravity"                             # (ndp_cfg's names; the oracle's OrcCfg says g and has no ts_nmpc or r_horiz)
+    return {(gravity_name if k == "g" else k): v for k, v in case.items() if ndp or k not in ENGINE_ONLY}
 
 
 def _apply(cfg, case, gravity_name):
@@ -68,6 +77,11 @@ def emu_cfg(case, N=20, **kw):
     """tests.emu.emu.default_cfg(N, **kw) at the case's model."""
     from tests.emu import emu
     return _apply(emu.default_cfg(N=N, **kw), case, "gravity")
+
+
+def radius_of(case):
+    """The case's gate radius (downwash_batch's r_horiz argument; the default where the case has none)."""
+    return float(case.get("r_horiz", R_HORIZ0))
 
 
 def model_of(case):

@@ -34,9 +34,9 @@ def gather(x, idx, gate, r2=R_HORIZ * R_HORIZ):
     return z, has & ((d2 < r2) if gate else True), d2
 
 
-def force64(blob, x, idx, gate=True, scale=1.0):
-    """f [B,3] float64."""
-    z, op, _ = gather(x, idx, gate)
+def force64(blob, x, idx, gate=True, scale=1.0, r2=R_HORIZ * R_HORIZ):
+    """f [B,3] float64.  r2: the gate's squared radius, here and in everything below (the default: ndp_cfg's default radius)."""
+    z, op, _ = gather(x, idx, gate, r2)
     B, K = idx.shape
     f = R.vjp64(blob, z.reshape(-1, 6), np.zeros((B * K, 3)))[3].reshape(B, K, 3)
     return scale * (f * op[:, :, None]).sum(axis=1)
@@ -51,21 +51,21 @@ def scatter(gz, idx, B):
     return gx
 
 
-def vjp64(blob, x, idx, gf, gate=True, scale=1.0):
+def vjp64(blob, x, idx, gf, gate=True, scale=1.0, r2=R_HORIZ * R_HORIZ):
     """The adjoint of force64: gf [B,3].  -> (g_z [B,K,6] per slot, 0 on closed and empty slots; g_x [B,10], its scatter; g_w [17859];
     margin [B,K] of every slot, open or not)."""
     B, K = idx.shape
-    z, op, _ = gather(x, idx, gate)
+    z, op, _ = gather(x, idx, gate, r2)
     up = scale * np.broadcast_to(gf[:, None], (B, K, 3)) * op[:, :, None]
     gz, gw, margin, _ = R.vjp64(blob, z.reshape(-1, 6), up.reshape(-1, 3))
     gz = gz.reshape(B, K, 6)
     return gz, scatter(gz, idx, B), gw, margin.reshape(B, K)
 
 
-def jvp64(blob, x, idx, tx=None, tw=None, gate=True, scale=1.0):
+def jvp64(blob, x, idx, tx=None, tw=None, gate=True, scale=1.0, r2=R_HORIZ * R_HORIZ):
     """The tangent of force64 along tx [B,10] (None = 0) and tw [17859] (None = 0): df [B,3]."""
     B, K = idx.shape
-    z, op, _ = gather(x, idx, gate)
+    z, op, _ = gather(x, idx, gate, r2)
     tz = None
     if tx is not None:
         has = (idx >= 0) & (idx < B)
@@ -85,20 +85,19 @@ def draw_states(rng, n):
     return x
 
 
-def failing(blob, x, idx, p=None):
+def failing(blob, x, idx, p=None, r2=R_HORIZ * R_HORIZ):
     """[B,K] bool: the slots with a neighbour whose margin is below mlp_vjp_ref.MARGIN or whose gate distance is within 10 % of r_horiz^2
     (judged whether the gate is used or not: one case serves gate on and off)."""
     B, K = idx.shape
     z, has, d2 = gather(x, idx, False)
     with torch.no_grad():
         margin = R.forward64(R.params64(blob) if p is None else p, torch.tensor(z.reshape(-1, 6)))[1].numpy().reshape(B, K)
-    r2 = R_HORIZ * R_HORIZ
     return has & ((margin < R.MARGIN) | ((d2 > 0.9 * r2) & (d2 < 1.1 * r2)))
 
 
-def shared_case(seed, blob, B, K, empty=0.15):
-    """States x [B,10] and random indices int32 [B,K] (never the vehicle itself; `empty` of the slots -1), redrawn until no slot fails.
-    -> dict(x, index, rounds, redrawn)."""
+def shared_case(seed, blob, B, K, empty=0.15, r2=R_HORIZ * R_HORIZ):
+    """States x [B,10] and random indices int32 [B,K] (never the vehicle itself; `empty` of the slots -1), redrawn until no slot fails
+    at the gate radius of r2.  -> dict(x, index, rounds, redrawn)."""
     rng = np.random.default_rng(seed)
     x = draw_states(rng, B)
     idx = ((np.arange(B)[:, None] + 1 + rng.integers(0, max(B - 1, 1), (B, K))) % B).astype(np.int32)
@@ -108,7 +107,7 @@ def shared_case(seed, blob, B, K, empty=0.15):
     p = R.params64(blob)
     rounds, redrawn = 0, 0
     while True:
-        bad = failing(blob, x, idx, p).any(axis=1)
+        bad = failing(blob, x, idx, p, r2).any(axis=1)
         if not bad.any():
             break
         rounds += 1

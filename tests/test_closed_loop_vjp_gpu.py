@@ -41,11 +41,14 @@ def _np(t):
     return t.detach().cpu().numpy()
 
 
-def _engine(ndp, a, N, force=True):
-    """A fresh engine: reset to tick 0's window and one warm-up step on tick 0's inputs, so that a kept set exists."""
+def _engine(ndp, a, N, force=True, moved=None, **kw):
+    """A fresh engine: reset to tick 0's window and one warm-up step on tick 0's inputs, so that a kept set exists.  kw: ndp_cfg
+    overrides (the model); moved: (Qd, Rd, mass) installed by set_model before the reset and the warm-up step."""
     import torch
     n = a["x0"].shape[0]
-    eng = ndp.BatchedNMPC(n, N=N, disturbance=force)
+    eng = ndp.BatchedNMPC(n, N=N, disturbance=force, **kw)
+    if moved is not None:
+        eng.set_model(Qd=moved[0], Rd=moved[1], mass=moved[2])
     eng.reset(a["xr"][0], a["ur"][0])
     u0 = torch.empty(n, 4, dtype=torch.float64, device=_dev())
     torch.cuda.synchronize()
@@ -58,8 +61,8 @@ def _state(eng):
     return [_np(v) for v in eng.device_iterate()] + [eng.active_set()[1]]
 
 
-def _loop(eng, a, ticks, substeps, force=True):
-    """_plain_loop's record for any number of ticks and substeps, with or without the two forces (ext form only)."""
+def _loop(eng, a, ticks, substeps, force=True, dt=R.DT):
+    """_plain_loop's record for any number of ticks, substeps and plant tick dt, with or without the two forces (ext form only)."""
     import ctypes as C
     import torch
     n = a["x0"].shape[0]
@@ -78,7 +81,7 @@ def _loop(eng, a, ticks, substeps, force=True):
         torch.cuda.synchronize()
         st, it = eng.status()
         eng._check(eng._lib.ndp_plant_step_device(eng._h, C.c_void_p(xn.data_ptr()), C.c_void_p(u0.data_ptr()),
-                                                  None if fp is None else C.c_void_p(fp.data_ptr()), R.DT, int(substeps), None), "ndp_plant_step_device")
+                                                  None if fp is None else C.c_void_p(fp.data_ptr()), float(dt), int(substeps), None), "ndp_plant_step_device")
         eng.synchronize()
         for name, v in (("x", _np(x)), ("force", a["f"][k].astype(np.float64)), ("Xpre", _np(tape[0])), ("Upre", _np(tape[1])),
                         ("act_pre", _np(tape[2])), ("act", eng.active_set()[1]), ("u0", _np(u0)), ("X", _np(X)), ("st", st), ("it", it)):
@@ -99,21 +102,22 @@ def _guarded(*shape, dtype=None, fill=-7.0):
     return whole[:rows].view(*shape), whole
 
 
-def _forward(eng, a, N, ticks=K, substeps=R.SUBSTEPS, force=True, stream=None):
-    """closed_loop_device into guarded outputs; returns the tensors the reverse call needs and the numpy values."""
+def _forward(eng, a, N, ticks=K, substeps=R.SUBSTEPS, force=True, stream=None, dt=R.DT, tape=True):
+    """closed_loop_device into guarded outputs; returns the tensors the reverse call needs and the numpy values.  tape False: the call
+    is given no tape (the reverse call cannot follow)."""
     import torch
     n = a["x0"].shape[0]
     t = dict(x0=_t(a["x0"]), xr=_t(a["xr"][:ticks]), ur=_t(a["ur"][:ticks]), f=_t(a["f"][:ticks], torch.float32) if force else None,
              fp=_t(a["fp"][:ticks]) if force else None)
     o = dict(xs=_guarded(ticks, n, 10), us=_guarded(ticks, n, 4), Xs=_guarded(ticks, n, N + 1, 10),
              status=_guarded(ticks, n, dtype=torch.int32, fill=-7))
-    tape = eng.closed_loop_tape(ticks)
+    tape = eng.closed_loop_tape(ticks) if tape else None
     torch.cuda.synchronize()
     eng.closed_loop_device(t["x0"], t["xr"], t["ur"], o["xs"][0], o["us"][0], f=t["f"], fp=t["fp"], Xs=o["Xs"][0],
-                           status=o["status"][0].view(ticks, n), tape=tape, substeps=substeps, stream=stream)
+                           status=o["status"][0].view(ticks, n), tape=tape, dt=dt, substeps=substeps, stream=stream)
     eng.synchronize()
     torch.cuda.synchronize()
-    t.update(xs=o["xs"][0], us=o["us"][0], tape=tape, substeps=substeps)
+    t.update(xs=o["xs"][0], us=o["us"][0], tape=tape, substeps=substeps, dt=dt)
     vals = {k: _np(v[0]) for k, v in o.items()}
     vals["status"] = vals["status"].reshape(ticks, n)
     for k, v in o.items():
@@ -131,7 +135,8 @@ def _reverse(eng, t, N, ups, ask=OUTS + ("gmodel",), stream=None):
     g = [None if u is None else _t(u[:ticks]) for u in ups]
     torch.cuda.synchronize()
     eng.closed_loop_vjp_device(t["x0"], t["xr"], t["ur"], t["xs"], t["us"], t["tape"], f=t["f"], fp=t["fp"], gxs=g[0], gus=g[1], gXs=g[2],
-                               status_check=st[0].view(ticks, n), substeps=t["substeps"], stream=stream, **{k: v[0] for k, v in o.items()})
+                               status_check=st[0].view(ticks, n), dt=t.get("dt", R.DT), substeps=t["substeps"], stream=stream,
+                               **{k: v[0] for k, v in o.items()})
     eng.synchronize()
     torch.cuda.synchronize()
     for k, v in list(o.items()) + [("status_check", st)]:
