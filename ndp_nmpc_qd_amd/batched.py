@@ -19,6 +19,35 @@ class NdpError(RuntimeError):
     pass
 
 
+def _raise_status(rc):
+    # same text as nmpc_body_rate_ctl.py:109-110
+    raise Exception("acados acados_ocp_solver returned status {}. Exiting.".format(rc))
+
+
+def _t_axis_shapes(who, B, rows, n_tan=None):
+    """The T axis of a forward-mode call, from shapes alone.  rows: one (shape, tail, lead) per tangent / output -- the tensor's shape
+    (None: not given), its shape behind the T axis (a tuple), and the number of batch dimensions in front of the axis (1: [B,T,...];
+    0: [T,...], the weights' direction).  Returns (T, demanded): T is n_tan when given, else read from the shapes (a shape without the
+    axis means T = 1; nothing given: 1); demanded[i] is the shape tensor i must have (what _dptr then holds it to) -- with the axis where
+    it came with it, else without (T = 1 as it lies) -- and None for a tensor not given."""
+    if n_tan is None:
+        Ts = {int(s[lead]) if len(s) == lead + 1 + len(tail) else 1 for s, tail, lead in rows if s is not None}
+        if len(Ts) > 1:
+            raise ValueError(f"{who}: tangents and outputs disagree on the number of directions ({sorted(Ts)})")
+        n_tan = Ts.pop() if Ts else 1
+    T, heads, demanded = int(n_tan), ((), (B,)), []
+    for s, tail, lead in rows:
+        if s is not None:
+            if len(s) == lead + 1 + len(tail):
+                s = heads[lead] + (T,) + tail
+            elif T != 1:
+                raise ValueError(f"{who}: a tensor without the T axis with n_tan = {T}")
+            else:
+                s = heads[lead] + tail
+        demanded.append(s)
+    return T, demanded
+
+
 class BatchedNMPC:
     def __init__(self, batch, N=CP.N_node, disturbance=False, n_rti=1, qp_mode=_lib.QP_AUTO, device=0,
                  dt=CP.th_pred, load_mlp=None, **cfg_overrides):
@@ -84,35 +113,36 @@ class BatchedNMPC:
         xr = _lib.f64(xr, (self.B, self.N + 1, 10))
         ur = _lib.f64(ur, (self.B, self.N, 4))
         u0 = np.empty((self.B, 4), dtype=np.float64)
+        X = U = st = it = None
+        if full:
+            X, U, st, it = self._full_out()
         if f is not None and other is None and np.asarray(f).dtype == np.float64:
             # a float64 force goes to the device as it is (ndp_step_ex_f64): the reference hands acados a float64 p
-            # (ndp_nmpc_body_rate_ctl.py:97-99); DownwashNN's float32 output takes the fp32 entry below -- the same numbers
+            # (ndp_nmpc_body_rate_ctl.py:97-99); DownwashNN's float32 output takes the fp32 entries below -- the same numbers
             f64 = _lib.f64(f, (self.B, self.N + 1, 3))
-            X = U = st = it = None
-            if full:
-                X, U = np.empty((self.B, self.N + 1, 10)), np.empty((self.B, self.N, 4))
-                st, it = np.empty(self.B, dtype=np.int32), np.empty(self.B, dtype=np.int32)
             rc = self._check(self._lib.ndp_step_ex_f64(self._h, _lib.ptr(x0), _lib.ptr(xr), _lib.ptr(ur), _lib.ptr(f64), _lib.ptr(u0),
                                                        _lib.ptr(X), _lib.ptr(U), _lib.ptr(st), _lib.ptr(it)), "ndp_step_ex_f64")
-            if rc != 0 and raise_on_status:
-                raise Exception("acados acados_ocp_solver returned status {}. Exiting.".format(rc))
-            return (u0, X, U, st, it) if full else u0
-        f32 = None if f is None else np.ascontiguousarray(f, dtype=np.float32).reshape(self.B, self.N + 1, 3)
-        other = _lib.f64(other, (self.B, self.N + 1, 10))
-        ego_xy = _lib.f64(ego_xy, (self.B, 2))
-        if full:
-            X, U = np.empty((self.B, self.N + 1, 10)), np.empty((self.B, self.N, 4))
-            st, it = np.empty(self.B, dtype=np.int32), np.empty(self.B, dtype=np.int32)
-            rc = self._check(self._lib.ndp_step_ex(self._h, _lib.ptr(x0), _lib.ptr(xr), _lib.ptr(ur), _lib.ptr(f32),
-                                                   _lib.ptr(other), _lib.ptr(ego_xy), _lib.ptr(u0), _lib.ptr(X), _lib.ptr(U),
-                                                   _lib.ptr(st), _lib.ptr(it)), "ndp_step_ex")
         else:
-            rc = self._check(self._lib.ndp_step(self._h, _lib.ptr(x0), _lib.ptr(xr), _lib.ptr(ur), _lib.ptr(f32),
-                                                _lib.ptr(other), _lib.ptr(ego_xy), _lib.ptr(u0)), "ndp_step")
+            f32 = None if f is None else np.ascontiguousarray(f, dtype=np.float32).reshape(self.B, self.N + 1, 3)
+            other = _lib.f64(other, (self.B, self.N + 1, 10))
+            ego_xy = _lib.f64(ego_xy, (self.B, 2))
+            if full:
+                rc = self._check(self._lib.ndp_step_ex(self._h, _lib.ptr(x0), _lib.ptr(xr), _lib.ptr(ur), _lib.ptr(f32),
+                                                       _lib.ptr(other), _lib.ptr(ego_xy), _lib.ptr(u0), _lib.ptr(X), _lib.ptr(U),
+                                                       _lib.ptr(st), _lib.ptr(it)), "ndp_step_ex")
+            else:
+                rc = self._check(self._lib.ndp_step(self._h, _lib.ptr(x0), _lib.ptr(xr), _lib.ptr(ur), _lib.ptr(f32),
+                                                    _lib.ptr(other), _lib.ptr(ego_xy), _lib.ptr(u0)), "ndp_step")
         if rc != 0 and raise_on_status:
-            # same text as nmpc_body_rate_ctl.py:109-110
-            raise Exception("acados acados_ocp_solver returned status {}. Exiting.".format(rc))
+            _raise_status(rc)
         return (u0, X, U, st, it) if full else u0
+
+    def _full_out(self, tick=False):
+        """The outputs only full=True returns: (X, U, status, ipm_iters) of the step forms, (u0, status, ipm_iters) of the tick forms."""
+        st, it = np.empty(self.B, dtype=np.int32), np.empty(self.B, dtype=np.int32)
+        if tick:
+            return np.empty((self.B, 4)), st, it
+        return np.empty((self.B, self.N + 1, 10)), np.empty((self.B, self.N, 4)), st, it
 
     def update_begin(self, x0, xr, ur, f=None, other=None, ego_xy=None, want_iterate=False):
         """First half of update(): packs the host arrays into a page-locked mirror, enqueues ONE launch that reads the mirror over
@@ -133,14 +163,13 @@ class BatchedNMPC:
         """Second half: waits for the oldest begun step; returns u0[B,4] (full=True: (u0, X, U, status, ipm_iters); X, U only if
         that step was begun with want_iterate).  `out`: a [B,4] float64 array to write u0 into."""
         u0 = np.empty((self.B, 4), dtype=np.float64) if out is None else out
-        st = it = X = U = None
+        X = U = st = it = None
         if full:
-            X, U = np.empty((self.B, self.N + 1, 10)), np.empty((self.B, self.N, 4))
-            st, it = np.empty(self.B, dtype=np.int32), np.empty(self.B, dtype=np.int32)
+            X, U, st, it = self._full_out()
         rc = self._check(self._lib.ndp_step_end(self._h, _lib.ptr(u0), _lib.ptr(X), _lib.ptr(U), _lib.ptr(st), _lib.ptr(it)),
                          "ndp_step_end")
         if rc != 0 and raise_on_status:
-            raise Exception("acados acados_ocp_solver returned status {}. Exiting.".format(rc))
+            _raise_status(rc)
         return (u0, X, U, st, it) if full else u0
 
     def update_debug(self, x0, xr, ur, f=None, other=None, ego_xy=None):
@@ -280,6 +309,14 @@ class BatchedNMPC:
             t = _lib.f64(t, (self.B,))
         return (_lib.f64(x_odom, (self.B, 10)), t, _lib.f64(vz, (self.B,)), _lib.f64(throttle, (self.B,)), flags)
 
+    def _tick_t_device(self, t, flags):
+        """(pointer, flags) for the t of the device ticks: a CUDA tensor [B] or None as it is; a scalar is one time for every vehicle,
+        read by the call from the host (NDP_TICK_T_UNIFORM; the pointer keeps its one-element array alive)."""
+        import torch
+        if t is not None and not isinstance(t, torch.Tensor):
+            return _lib.ptr(np.array([float(t)])), flags | _lib.TICK_T_UNIFORM
+        return self._dptr(t, torch.float64, (self.B,)), flags
+
     def tick_begin(self, x_odom, t=None, vz=None, throttle=None, estimate=False, want_u0=False):
         """First half of tick(): ndp_tick_begin -- only x_odom[B,10] (+ t, vz, throttle [B]) cross PCIe; returns without waiting.
         Up to two ticks in flight."""
@@ -292,10 +329,10 @@ class BatchedNMPC:
         cmd = np.empty((self.B, 4)) if out is None else out
         u0 = st = it = None
         if full:
-            u0, st, it = np.empty((self.B, 4)), np.empty(self.B, dtype=np.int32), np.empty(self.B, dtype=np.int32)
+            u0, st, it = self._full_out(tick=True)
         rc = self._check(self._lib.ndp_tick_end(self._h, _lib.ptr(cmd), _lib.ptr(u0), _lib.ptr(st), _lib.ptr(it)), "ndp_tick_end")
         if rc != 0 and raise_on_status:
-            raise Exception("acados acados_ocp_solver returned status {}. Exiting.".format(rc))
+            _raise_status(rc)
         return (cmd, u0, st, it) if full else cmd
 
     def tick(self, x_odom, t=None, vz=None, throttle=None, estimate=False, raise_on_status=True, full=False):
@@ -306,23 +343,18 @@ class BatchedNMPC:
         cmd = np.empty((self.B, 4))
         u0 = st = it = None
         if full:
-            u0, st, it = np.empty((self.B, 4)), np.empty(self.B, dtype=np.int32), np.empty(self.B, dtype=np.int32)
+            u0, st, it = self._full_out(tick=True)
         rc = self._check(self._lib.ndp_tick(self._h, _lib.ptr(x), _lib.ptr(t), _lib.ptr(vz), _lib.ptr(th), flags, _lib.ptr(cmd),
                                             _lib.ptr(u0), _lib.ptr(st), _lib.ptr(it)), "ndp_tick")
         if rc != 0 and raise_on_status:
-            raise Exception("acados acados_ocp_solver returned status {}. Exiting.".format(rc))
+            _raise_status(rc)
         return (cmd, u0, st, it) if full else cmd
 
     def tick_device(self, x_odom, cmd_out, t=None, vz=None, throttle=None, estimate=False, u0_out=None, stream=None):
         """The tick's launches on CUDA tensors and a caller's stream (ndp_tick_device); no synchronisation."""
         import torch
         B = self.B
-        flags = _lib.TICK_ESTIMATE if estimate else 0
-        if t is not None and not isinstance(t, torch.Tensor):       # a scalar: one time for every vehicle, read by the call
-            t_host = np.array([float(t)])
-            tp, flags = _lib.ptr(t_host), flags | _lib.TICK_T_UNIFORM
-        else:
-            tp = self._dptr(t, torch.float64, (B,))
+        tp, flags = self._tick_t_device(t, _lib.TICK_ESTIMATE if estimate else 0)
         self._check(self._lib.ndp_tick_device(
             self._h, self._dptr(x_odom, torch.float64, (B, 10)), tp,
             self._dptr(vz, torch.float64, (B,)), self._dptr(throttle, torch.float64, (B,)), flags,
@@ -344,12 +376,7 @@ class BatchedNMPC:
     def tick_advance_device(self, x_odom, t=None, vz=None, throttle=None, estimate=False, stream=None):
         """Stage 1: list advance (t: scalar, CUDA tensor [B] or None) + estimator.  ndp_tick_advance_device."""
         import torch
-        flags = _lib.TICK_ESTIMATE if estimate else 0
-        if t is not None and not isinstance(t, torch.Tensor):
-            t_host = np.array([float(t)])
-            tp, flags = _lib.ptr(t_host), flags | _lib.TICK_T_UNIFORM
-        else:
-            tp = self._dptr(t, torch.float64, (self.B,))
+        tp, flags = self._tick_t_device(t, _lib.TICK_ESTIMATE if estimate else 0)
         self._check(self._lib.ndp_tick_advance_device(self._h, self._dptr(x_odom, torch.float64, (self.B, 10)), tp,
                                                       self._dptr(vz, torch.float64, (self.B,)), self._dptr(throttle, torch.float64, (self.B,)),
                                                       flags, self._stream(stream)), "ndp_tick_advance_device")
@@ -639,8 +666,7 @@ class BatchedNMPC:
         default stream: as downwash_vjp_device."""
         import torch
         B = self.B
-        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
-            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        self._torch_default_wait(stream)
         iptr, K = self._slots_of(other_index, (gz, 1))
         d = self._dptr
         self._check(self._lib.ndp_plant_force_multi_vjp_device(
@@ -653,8 +679,7 @@ class BatchedNMPC:
         gz [B,6].  The K = 1 case, bit for bit."""
         import torch
         B = self.B
-        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
-            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        self._torch_default_wait(stream)
         d = self._dptr
         self._check(self._lib.ndp_plant_force_vjp_device(
             self._h, d(x, torch.float64, (B, 10)), d(other_index, torch.int32, (B,)), 1 if gate else 0, float(scale),
@@ -662,28 +687,12 @@ class BatchedNMPC:
             "ndp_plant_force_vjp_device")
 
     def _plant_force_tangents(self, who, tx, tw, df, n_tan):
-        """(T, tx, tw, df pointers) of a forward-mode call: T is n_tan when given, else read from the tensors; tensors without the T axis
-        mean T = 1."""
+        """(T, tx, tw, df pointers) of a forward-mode call of the plant force."""
         import torch
-        B = self.B
-        tails = ((10,), (_lib.MLP_NPARAM,), (3,))
-        lead = (1, 0, 1)                                                # dimensions in front of the T axis
-        if n_tan is None:
-            Ts = {int(t.shape[ld]) if t.dim() == ld + 1 + len(s) else 1 for t, s, ld in zip((tx, tw, df), tails, lead) if t is not None}
-            if len(Ts) > 1:
-                raise ValueError(f"{who}: tangents and output disagree on the number of directions ({sorted(Ts)})")
-            n_tan = Ts.pop() if Ts else 1
-        T = int(n_tan)
-
-        def dt(t, s, ld):
-            if t is None:
-                return None
-            head = (B,) if ld else ()
-            full = head + (T,) + s
-            if t.dim() != len(full) and T != 1:
-                raise ValueError(f"{who}: a tensor without the T axis with n_tan = {T}")
-            return self._dptr(t, torch.float32 if s is tails[1] else torch.float64, full if t.dim() == len(full) else head + s)
-        return T, dt(tx, tails[0], 1), dt(tw, tails[1], 0), dt(df, tails[2], 1)
+        d = self._dptr
+        T, (stx, stw, sdf) = _t_axis_shapes(who, self.B, (
+            (getattr(tx, "shape", None), (10,), 1), (getattr(tw, "shape", None), (_lib.MLP_NPARAM,), 0), (getattr(df, "shape", None), (3,), 1)), n_tan)
+        return T, d(tx, torch.float64, stx), d(tw, torch.float32, stw), d(df, torch.float64, sdf)
 
     def plant_force_multi_jvp_device(self, x, other_index, tx=None, tw=None, n_tan=None, df=None, f_check=None, gate=True, scale=1.0,
                                      stream=None):
@@ -696,8 +705,7 @@ class BatchedNMPC:
         downwash_jvp_device."""
         import torch
         B = self.B
-        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
-            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        self._torch_default_wait(stream)
         iptr, K = self._slots_of(other_index)
         T, ptx, ptw, pdf = self._plant_force_tangents("plant_force_multi_jvp_device", tx, tw, df, n_tan)
         d = self._dptr
@@ -710,8 +718,7 @@ class BatchedNMPC:
         K = 1 case, bit for bit."""
         import torch
         B = self.B
-        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
-            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        self._torch_default_wait(stream)
         T, ptx, ptw, pdf = self._plant_force_tangents("plant_force_jvp_device", tx, tw, df, n_tan)
         d = self._dptr
         self._check(self._lib.ndp_plant_force_jvp_device(
@@ -899,8 +906,7 @@ class BatchedNMPC:
         dL/dQd [0:10], dL/dRd [10:14], dL/dmass [14], 0 [15]; NaN in all 16 where the step failed.  Sum over the batch yourself."""
         import torch
         B, N = self.B, self.N
-        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
-            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        self._torch_default_wait(stream)
         d = self._dptr
         X, U, A = tape
         args = [d(x0, torch.float64, (B, 10)), d(xr, torch.float64, (B, N + 1, 10)), d(ur, torch.float64, (B, N, 4)),
@@ -925,35 +931,34 @@ class BatchedNMPC:
         and stream: as step_vjp_device's.  Nothing of the engine's state is written."""
         import torch
         B, N = self.B, self.N
-        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
-            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        self._torch_default_wait(stream)
         tails = ((10,), (N + 1, 10), (N, 4), (N + 1, 3), (4,), (N + 1, 10), (N, 4))
-        given = [(t, s) for t, s in zip((tx0, txr, tur, tf, du0, dX, dU), tails) if t is not None]
-        Ts = {int(t.shape[1]) if t.dim() == len(s) + 2 else 1 for t, s in given}
-        if len(Ts) > 1:
-            raise ValueError(f"step_jvp_device: tangents and outputs disagree on the number of directions ({sorted(Ts)})")
-        T = Ts.pop() if Ts else 1
-        d = self._dptr
+        tans = (tx0, txr, tur, tf, du0, dX, dU)
         # (without the T axis: [B, ...] is [B, 1, ...] as it lies)
-        dt = lambda t, s: d(t, torch.float64, (B, T) + s if t is not None and t.dim() == len(s) + 2 else (B,) + s)  # noqa: E731
+        T, shapes = _t_axis_shapes("step_jvp_device", B, [(getattr(t, "shape", None), s, 1) for t, s in zip(tans, tails)])
+        d = self._dptr
         X, U, A = tape
         args = [d(x0, torch.float64, (B, 10)), d(xr, torch.float64, (B, N + 1, 10)), d(ur, torch.float64, (B, N, 4)),
                 d(f, torch.float32, (B, N + 1, 3)), d(X, torch.float64, (B, N + 1, 10)), d(U, torch.float64, (B, N, 4)),
-                d(A, torch.int8, (B, N, 4)), T, *(dt(t, s) for t, s in zip((tx0, txr, tur, tf, du0, dX, dU), tails)),
+                d(A, torch.int8, (B, N, 4)), T, *(d(t, torch.float64, s) for t, s in zip(tans, shapes)),
                 d(u0_check, torch.float64, (B, 4)), d(status_check, torch.int32, (B,)), self._stream(stream)]
         self._check(self._lib.ndp_step_jvp_device(self._h, *args), "ndp_step_jvp_device")
 
     # ------------------------------------------------------------------ backward pass of the downwash network
     def _other_ptr(self, other, other_index):
-        """(pointer, doubles per node) of neighbour windows [rows, N+1, 6 or 10] (rows = B without other_index)."""
+        """(pointer, doubles per node) of neighbour windows [rows, N+1, 6 or 10] (rows = B without other_index): a CUDA tensor, or raw
+        device memory (dist.DevWindows: e.g. another process's window buffer mapped with ndp_peer_open)."""
         import torch
-        if hasattr(other, "dev_ptr"):
-            return C.c_void_p(int(other.dev_ptr)), int(other.shape[2])
-        if not (isinstance(other, torch.Tensor) and other.is_cuda and other.is_contiguous() and other.dtype == torch.float64
-                and other.dim() == 3 and other.shape[1] == self.N + 1 and other.shape[2] in (6, 10)
-                and (other_index is not None or other.shape[0] == self.B)):
+        raw = hasattr(other, "dev_ptr")
+        shape = tuple(other.shape) if raw or isinstance(other, torch.Tensor) else ()
+        fits = len(shape) == 3 and shape[1] == self.N + 1 and shape[2] in (6, 10) and (other_index is not None or shape[0] == self.B)
+        if raw:
+            if not fits:
+                raise ValueError("other: expected device windows of shape [rows, N+1, 6 or 10]")
+            return C.c_void_p(int(other.dev_ptr)), int(shape[2])
+        if not (fits and other.is_cuda and other.is_contiguous() and other.dtype == torch.float64):
             raise ValueError("other: expected a contiguous CUDA float64 [rows, N+1, 6 or 10] tensor")
-        return C.c_void_p(other.data_ptr()), int(other.shape[2])
+        return C.c_void_p(other.data_ptr()), int(shape[2])
 
     def downwash_vjp_device(self, other, ego_ref, gf, ego_xy=None, other_index=None, gz=None, gw=None, stream=None):
         """Enqueues the backward pass of the downwash network and its gate on `stream` (ndp_downwash_vjp_device; include/ndp_nmpc.h):
@@ -966,8 +971,7 @@ class BatchedNMPC:
         on the engine's own stream behind a wait for torch's (read the outputs after engine.synchronize())."""
         import torch
         B, N = self.B, self.N
-        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
-            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        self._torch_default_wait(stream)
         optr, stride = self._other_ptr(other, other_index)
         d = self._dptr
         self._check(self._lib.ndp_downwash_vjp_device(
@@ -988,30 +992,14 @@ class BatchedNMPC:
         engine.synchronize())."""
         import torch
         B, N = self.B, self.N
-        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
-            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
-        tails = ((N + 1, 6), (_lib.MLP_NPARAM,), (N + 1, 3))
-        lead = (1, 0, 1)                                                # dimensions in front of the T axis
-        if n_tan is None:
-            Ts = {int(t.shape[ld]) if t.dim() == ld + 1 + len(s) else 1 for t, s, ld in zip((tz, tw, df), tails, lead) if t is not None}
-            if len(Ts) > 1:
-                raise ValueError(f"downwash_jvp_device: tangents and output disagree on the number of directions ({sorted(Ts)})")
-            n_tan = Ts.pop() if Ts else 1
-        T = int(n_tan)
+        self._torch_default_wait(stream)
+        T, (stz, stw, sdf) = _t_axis_shapes("downwash_jvp_device", B, (
+            (getattr(tz, "shape", None), (N + 1, 6), 1), (getattr(tw, "shape", None), (_lib.MLP_NPARAM,), 0), (getattr(df, "shape", None), (N + 1, 3), 1)), n_tan)
         d = self._dptr
-
-        def dt(t, s, ld):                                               # (without the T axis: the tensor is T = 1 as it lies)
-            if t is None:
-                return None
-            head = (B,) if ld else ()
-            full = head + (T,) + s
-            if t.dim() != len(full) and T != 1:
-                raise ValueError(f"downwash_jvp_device: a tensor without the T axis with n_tan = {T}")
-            return d(t, torch.float32 if s is tails[1] else torch.float64, full if t.dim() == len(full) else head + s)
         optr, stride = self._other_ptr(other, other_index)
         self._check(self._lib.ndp_downwash_jvp_device(
             self._h, optr, stride, d(other_index, torch.int32, (B,)), d(ego_ref, torch.float64, (B, N + 1, 10)),
-            d(ego_xy, torch.float64, (B, 2)), T, dt(tz, tails[0], 1), dt(tw, tails[1], 0), dt(df, tails[2], 1),
+            d(ego_xy, torch.float64, (B, 2)), T, d(tz, torch.float64, stz), d(tw, torch.float32, stw), d(df, torch.float64, sdf),
             d(f_check, torch.float32, (B, N + 1, 3)), self._stream(stream)), "ndp_downwash_jvp_device")
 
     # ---- the same two with K neighbours per instance (the derivatives of downwash_multi_device)
@@ -1025,8 +1013,7 @@ class BatchedNMPC:
         or torch's default stream: as downwash_vjp_device."""
         import torch
         B, N = self.B, self.N
-        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
-            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        self._torch_default_wait(stream)
         optr, stride = self._other_ptr(other, other_index)
         iptr, K = self._dindex_multi(other_index)
         d = self._dptr
@@ -1045,39 +1032,22 @@ class BatchedNMPC:
         stream: as downwash_jvp_device."""
         import torch
         B, N = self.B, self.N
-        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
-            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        self._torch_default_wait(stream)
         optr, stride = self._other_ptr(other, other_index)
         iptr, K = self._dindex_multi(other_index)
-        tails = ((K, N + 1, 6), (_lib.MLP_NPARAM,), (N + 1, 3))
-        lead = (1, 0, 1)                                                # dimensions in front of the T axis
-        if n_tan is None:
-            Ts = {int(t.shape[ld]) if t.dim() == ld + 1 + len(s) else 1 for t, s, ld in zip((tz, tw, df), tails, lead) if t is not None}
-            if len(Ts) > 1:
-                raise ValueError(f"downwash_multi_jvp_device: tangents and output disagree on the number of directions ({sorted(Ts)})")
-            n_tan = Ts.pop() if Ts else 1
-        T = int(n_tan)
+        T, (stz, stw, sdf) = _t_axis_shapes("downwash_multi_jvp_device", B, (
+            (getattr(tz, "shape", None), (K, N + 1, 6), 1), (getattr(tw, "shape", None), (_lib.MLP_NPARAM,), 0), (getattr(df, "shape", None), (N + 1, 3), 1)), n_tan)
         d = self._dptr
-
-        def dt(t, s, ld):                                               # (without the T axis: the tensor is T = 1 as it lies)
-            if t is None:
-                return None
-            head = (B,) if ld else ()
-            full = head + (T,) + s
-            if t.dim() != len(full) and T != 1:
-                raise ValueError(f"downwash_multi_jvp_device: a tensor without the T axis with n_tan = {T}")
-            return d(t, torch.float32 if s is tails[1] else torch.float64, full if t.dim() == len(full) else head + s)
         self._check(self._lib.ndp_downwash_multi_jvp_device(
             self._h, optr, stride, iptr, K, d(ego_ref, torch.float64, (B, N + 1, 10)), d(ego_xy, torch.float64, (B, 2)), T,
-            dt(tz, tails[0], 1), dt(tw, tails[1], 0), dt(df, tails[2], 1), d(f_check, torch.float32, (B, N + 1, 3)),
+            d(tz, torch.float64, stz), d(tw, torch.float32, stw), d(df, torch.float64, sdf), d(f_check, torch.float32, (B, N + 1, 3)),
             self._stream(stream)), "ndp_downwash_multi_jvp_device")
 
     def set_mlp_weights_device(self, blob, stream=None):
         """set_mlp_weights from a float32 CUDA tensor of 17859 values in blob order, enqueued on `stream` with no host synchronisation
         (ndp_set_mlp_weights_device): steps enqueued behind it on that stream use the new weights."""
         import torch
-        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
-            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        self._torch_default_wait(stream)
         self._check(self._lib.ndp_set_mlp_weights_device(self._h, self._dptr(blob, torch.float32, (_lib.MLP_NPARAM,)), self._stream(stream)),
                     "ndp_set_mlp_weights_device")
         self._mlp_installed = None          # (torch_layer._install_weights notes what IT installed, behind this call)
@@ -1106,8 +1076,7 @@ class BatchedNMPC:
         (ndp_mlp_spectral_norms_device): a direct method in fp64, accurate to the order of 1e-14 whatever the gaps between singular values.
         stream None or torch's default stream: as downwash_vjp_device."""
         import torch
-        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
-            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        self._torch_default_wait(stream)
         d = self._dptr
         self._check(self._lib.ndp_mlp_spectral_norms_device(self._h, d(w, torch.float32, (_lib.MLP_NPARAM,)), d(sigma, torch.float64, (4,)),
                                                             self._stream(stream)), "ndp_mlp_spectral_norms_device")
@@ -1123,8 +1092,7 @@ class BatchedNMPC:
         behind the step (set_mlp_weights_device on the same stream).  Never synchronises the device.  stream None or torch's default
         stream: as downwash_vjp_device."""
         import torch
-        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
-            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        self._torch_default_wait(stream)
         d, n = self._dptr, (_lib.MLP_NPARAM,)
         self._check(self._lib.ndp_mlp_adam_sn_device(
             self._h, d(w, torch.float32, n), d(g, torch.float32, n), d(m, torch.float32, n), d(v, torch.float32, n),
@@ -1147,8 +1115,7 @@ class BatchedNMPC:
         read, its f row exactly 0.  Each row is bit-equal to downwash_device's for the same six float32 inputs.  The engine's state is
         not written.  stream None or torch's default stream: as downwash_vjp_device."""
         import torch
-        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
-            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        self._torch_default_wait(stream)
         R, M = self._rows_shape(z, index, f)
         d = self._dptr
         self._check(self._lib.ndp_mlp_rows_device(self._h, d(z, torch.float32, (R, 6)), d(index, torch.int32, (M,)), R, M,
@@ -1165,8 +1132,7 @@ class BatchedNMPC:
         identical bits.  Its workspace is its own; fit calls on one engine must be ordered against each other.  The engine's state is
         not written.  stream None or torch's default stream: as downwash_vjp_device."""
         import torch
-        if stream is None or getattr(stream, "cuda_stream", stream) == 0:
-            torch.cuda.current_stream(torch.device("cuda", self.cfg.device)).synchronize()
+        self._torch_default_wait(stream)
         R, Mi = self._rows_shape(z, index, f)
         M = Mi if M is None else int(M)
         d = self._dptr
@@ -1179,11 +1145,7 @@ class BatchedNMPC:
     def device_iterate(self):
         """The engine's iterate as CUDA tensor views (no copy): (X [B,N+1,10], U [B,N,4]) float64 (ndp_device_iterate_x / _u); valid once
         the step's stream has reached them; the next step overwrites them."""
-        import torch
-        from .dist import _DevMem
-        dev = torch.device("cuda", self.cfg.device)
-        return (torch.as_tensor(_DevMem(self._lib.ndp_device_iterate_x(self._h), (self.B, self.N + 1, 10)), device=dev),
-                torch.as_tensor(_DevMem(self._lib.ndp_device_iterate_u(self._h), (self.B, self.N, 4)), device=dev))
+        return self._device_views((self._lib.ndp_device_iterate_x, (self.B, self.N + 1, 10)), (self._lib.ndp_device_iterate_u, (self.B, self.N, 4)))
 
     # ------------------------------------------------------------------ HBM-resident API (torch CUDA tensors)
     @staticmethod
@@ -1215,23 +1177,8 @@ class BatchedNMPC:
         The tensors must stay alive and in place for as long as the callable is used."""
         import torch
         B, N = self.B, self.N
-        stride = 10
-        if other is not None and hasattr(other, "dev_ptr"):
-            # raw device memory (dist.DevWindows: e.g. another process's window buffer mapped with ndp_peer_open)
-            shp = tuple(other.shape)
-            if not (len(shp) == 3 and shp[1] == N + 1 and shp[2] in (6, 10) and (other_index is not None or shp[0] == B)):
-                raise ValueError("other: expected device windows of shape [rows, N+1, 6 or 10]")
-            stride = int(shp[2])
-            optr = C.c_void_p(int(other.dev_ptr))
-        elif other is not None and (other_index is not None or (other.dim() == 3 and other.shape[2] == 6)):
-            # rows picked through other_index (any number of rows), or row i = instance i of a [B, N+1, 6] position / velocity window
-            if not (other.is_cuda and other.is_contiguous() and other.dtype == torch.float64 and other.dim() == 3
-                    and other.shape[1] == N + 1 and other.shape[2] in (6, 10) and (other_index is not None or other.shape[0] == B)):
-                raise ValueError("other: expected a contiguous CUDA float64 [rows, N+1, 6 or 10] tensor")
-            stride = int(other.shape[2])
-            optr = C.c_void_p(other.data_ptr())
-        else:
-            optr = self._dptr(other, torch.float64, (B, N + 1, 10))
+        # (rows picked through other_index -- any number of rows -- or row i = instance i of a [B, N+1, 6 or 10] window)
+        optr, stride = (None, 10) if other is None else self._other_ptr(other, other_index)
         args = (self._h, self._dptr(x0, torch.float64, (B, 10)), self._dptr(xr, torch.float64, (B, N + 1, 10)),
                 self._dptr(ur, torch.float64, (B, N, 4)), self._dptr(f, torch.float32, (B, N + 1, 3)),
                 optr, stride, self._dptr(other_index, torch.int32, (B,)), self._dptr(ego_xy, torch.float64, (B, 2)),
@@ -1248,13 +1195,7 @@ class BatchedNMPC:
         beside the control-step kernel of the current tick.  other / other_index as in update_device; ego_ref = that tick's xr."""
         import torch
         B, N = self.B, self.N
-        if hasattr(other, "dev_ptr"):
-            stride, optr = int(other.shape[2]), C.c_void_p(int(other.dev_ptr))
-        else:
-            if not (other.is_cuda and other.is_contiguous() and other.dtype == torch.float64 and other.dim() == 3
-                    and other.shape[1] == N + 1 and other.shape[2] in (6, 10) and (other_index is not None or other.shape[0] == B)):
-                raise ValueError("other: expected a contiguous CUDA float64 [rows, N+1, 6 or 10] tensor")
-            stride, optr = int(other.shape[2]), C.c_void_p(other.data_ptr())
+        optr, stride = self._other_ptr(other, other_index)
         self._check(self._lib.ndp_downwash_prefetch_device(
             self._h, optr, stride, self._dptr(other_index, torch.int32, (B,)), self._dptr(ego_ref, torch.float64, (B, N + 1, 10)),
             self._dptr(ego_xy, torch.float64, (B, 2)), self._stream(after_stream), self._stream(on_stream)),
@@ -1280,20 +1221,15 @@ class BatchedNMPC:
 
     def force_slot(self, slot):
         """The force of prediction m (slot m & 1) as a CUDA tensor view [B, N+1, 3] float32 (valid after prefetch_join / stats)."""
-        import torch
-        from .dist import _DevMem
-        ptr = self._lib.ndp_device_force_slot(self._h, int(slot))
-        if not ptr:
+        f, = self._device_views((lambda h: self._lib.ndp_device_force_slot(h, int(slot)), (self.B, self.N + 1, 3), "<f4"))
+        if f is None:
             raise NdpError("no force slots: downwash_prefetch_device was never called")
-        return torch.as_tensor(_DevMem(ptr, (self.B, self.N + 1, 3), "<f4"), device=torch.device("cuda", self.cfg.device))
+        return f
 
     def device_force(self):
         """The force the fused downwash (or ndp_downwash_device) of the last step left in HBM: CUDA tensor view [B, N+1, 3] float32
         (ndp_device_force); valid once the step's stream has reached it."""
-        import torch
-        from .dist import _DevMem
-        ptr = self._lib.ndp_device_force(self._h)
-        return torch.as_tensor(_DevMem(ptr, (self.B, self.N + 1, 3), "<f4"), device=torch.device("cuda", self.cfg.device))
+        return self._device_views((self._lib.ndp_device_force, (self.B, self.N + 1, 3), "<f4"))[0]
 
     def track_steps(self, on=True):
         """Every control step launched from now on marks an event at its completion without a packet of its own (ndp_track_steps)."""

@@ -57,7 +57,26 @@ f = plant_force(engine, x, other_index); x = plant_step(engine, x, u, f) is a di
 """
 import torch
 
+from . import _lib
 from .params import nmpc_params as CP
+
+_WHY_GATE = "the r_horiz gate is piecewise constant and is not differentiated (detach it)"
+_WHY_NETWORK = "the fused downwash network is not differentiated (detach it, or leave it out of the graph)"
+
+
+def _det(t):
+    return t.detach().contiguous() if isinstance(t, torch.Tensor) else t
+
+
+def _cast(t, dtype):
+    return None if t is None else t.to(dtype).contiguous()
+
+
+def _refuse_grad(who, name, t, why):
+    """A silent zero gradient would be wrong, not approximate: e.g. "DownwashFunction: ego_xy requires grad, but the r_horiz gate is
+    piecewise constant and is not differentiated (detach it)"."""
+    if isinstance(t, torch.Tensor) and t.requires_grad:
+        raise ValueError(f"{who}: {name} requires grad, but {why}")
 
 
 def _cuda_stream(t):
@@ -66,6 +85,17 @@ def _cuda_stream(t):
         return None, False
     s = torch.cuda.current_stream(t.device)
     return s, s.cuda_stream == 0
+
+
+def _enter(engine, t, weights=None):
+    """The prologue of an entry point whose call goes on t's current stream: (stream, default, key).  torch's default stream cannot be
+    named through the C-ABI (a NULL stream is the engine's own): there the call runs on the engine's stream, so the inputs are waited for
+    in front of it (here) and the caller waits for the engine behind it.  `weights`, when given, are installed first (_install_weights,
+    whose key this returns)."""
+    stream, default = _cuda_stream(t)
+    if default:
+        stream.synchronize()
+    return stream, default, _install_weights(engine, weights, stream)
 
 
 def _taped_step(engine, stream, default, x0, xr, ur, **kw):
@@ -99,22 +129,19 @@ class ControlStepFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, engine, xr, ur, f=None, other=None, ego_xy=None):
         params = bool(getattr(engine, "param_sensitivity_enabled", False))
-        for name, t in (("xr", xr), ("ur", ur), ("f", f), ("other", other), ("ego_xy", ego_xy)):
-            if isinstance(t, torch.Tensor) and t.requires_grad and not (params and name in ("xr", "ur", "f")):
-                why = ("the fused downwash network is not differentiated" if name in ("other", "ego_xy") else
-                       "the engine's parameter sensitivities are off (engine.enable_param_sensitivity() or ControlStep(engine, params=True))")
-                raise ValueError(f"ControlStepFunction: {name} requires grad, but {why} (detach it, or leave it out of the graph)")
+        if not params:
+            for name, t in (("xr", xr), ("ur", ur), ("f", f)):
+                _refuse_grad("ControlStepFunction", name, t, "the engine's parameter sensitivities are off (engine.enable_param_sensitivity() "
+                             "or ControlStep(engine, params=True)) (detach it, or leave it out of the graph)")
+        for name, t in (("other", other), ("ego_xy", ego_xy)):
+            _refuse_grad("ControlStepFunction", name, t, _WHY_NETWORK)
         if engine.sensitivity_level < 1:
             raise ValueError("ControlStepFunction: the engine's sensitivities are off (engine.enable_sensitivity(1) first)")
         x0 = x0.detach().contiguous()
-        det = lambda t: t.detach() if isinstance(t, torch.Tensor) else t  # noqa: E731
+        xr_d, ur_d, f_d = (t.detach() if isinstance(t, torch.Tensor) else t for t in (xr, ur, f))
         u0 = torch.empty((x0.shape[0], 4), dtype=x0.dtype, device=x0.device)
-        # torch's default stream cannot be named through the C-ABI (a NULL stream is the engine's own): there the step runs on the
-        # engine's stream, so the inputs are waited for in front of it and the step behind it
-        stream, default = _cuda_stream(x0)
-        if default:
-            stream.synchronize()
-        engine.update_device(x0, det(xr), det(ur), u0, f=det(f), other=other, ego_xy=ego_xy, stream=stream)
+        stream, default, _ = _enter(engine, x0)
+        engine.update_device(x0, xr_d, ur_d, u0, f=f_d, other=other, ego_xy=ego_xy, stream=stream)
         if default:
             engine.synchronize()
         # (copies ordered behind the step on the same stream: the engine's buffers are overwritten by its next step)
@@ -154,11 +181,8 @@ class ControlStepTrajectoryFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, engine, xr, ur, f=None, other=None, ego_xy=None):
         for name, t in (("other", other), ("ego_xy", ego_xy)):
-            if isinstance(t, torch.Tensor) and t.requires_grad:
-                raise ValueError(f"ControlStepTrajectoryFunction: {name} requires grad, but the fused downwash network is not differentiated "
-                                 "(detach it, or leave it out of the graph)")
-        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t  # noqa: E731
-        x0, xr, ur, fd = det(x0), det(xr), det(ur), det(f)
+            _refuse_grad("ControlStepTrajectoryFunction", name, t, _WHY_NETWORK)
+        x0, xr, ur, fd = _det(x0), _det(xr), _det(ur), _det(f)
         tape, u0, X, U = _taped_step(engine, *_cuda_stream(x0), x0, xr, ur, f=fd, other=other, ego_xy=ego_xy)
         force = engine.device_force().clone() if other is not None else fd
         ctx.engine = engine
@@ -193,9 +217,8 @@ def control_step_jvp(engine, x0, xr, ur, tangents, f=None):
     direction, [B,...]; None = 0).  The tape is recorded, the ordinary step runs, then the derivative on the same stream.  The outputs carry
     the tangents' T axis: a tangent without it gives du0 [B,4], dX [B,N+1,10], dU [B,N,4].  No autograd hookup: nothing here is recorded in
     a graph."""
-    det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t  # noqa: E731
-    x0, xr, ur, fd = det(x0), det(xr), det(ur), det(f)
-    tans = [None if t is None else det(t).to(torch.float64) for t in tangents]
+    x0, xr, ur, fd = _det(x0), _det(xr), _det(ur), _det(f)
+    tans = [None if t is None else _det(t).to(torch.float64) for t in tangents]
     given = [(t, n) for t, n in zip(tans, (2, 3, 3, 3)) if t is not None]
     if not given:
         raise ValueError("control_step_jvp: no tangent (tx0, txr, tur and tf all None)")
@@ -278,154 +301,57 @@ def _minus_gz(gz, like):
     return g
 
 
-class DownwashFunction(torch.autograd.Function):
-    """forward(other, engine, ego_ref, ego_xy, weights, other_index) -> f [B,N+1,3] float32, the gated downwash force (mlp_kernel);
-    backward: BatchedNMPC.downwash_vjp_device for the gradients of other, ego_ref and weights."""
+# What differs between an entry point with one neighbour per instance (other_index None or [B]) and its K-slot sibling (other_index
+# [B,K]) is held by a form: the engine's backward and forward-mode methods, the slot axis of gz / tz, the plumbing between those and the
+# windows, and the forward itself.  Every shared body below is written once against a form.
 
-    @staticmethod
-    def forward(ctx, other, engine, ego_ref, ego_xy=None, weights=None, other_index=None):
-        if isinstance(ego_xy, torch.Tensor) and ego_xy.requires_grad:
-            raise ValueError("DownwashFunction: ego_xy requires grad, but the r_horiz gate is piecewise constant and is not differentiated "
-                             "(detach it)")
-        od, ed = other.detach().contiguous(), ego_ref.detach().contiguous()
-        stream, default = _cuda_stream(od)
-        if default:
-            stream.synchronize()
-        ctx.key = _install_weights(engine, weights, stream)
-        B, np1 = ed.shape[0], ed.shape[1]
-        dense = od
-        if other_index is not None or od.shape[2] != 10:      # the stand-alone forward takes dense [B,N+1,10] windows: gather (plumbing)
-            rows = od if other_index is None else od[other_index.clamp(min=0).long()]
-            dense = torch.zeros((B, np1, 10), dtype=od.dtype, device=od.device)
-            dense[:, :, :od.shape[2]] = rows
-        f = torch.empty((B, np1, 3), dtype=torch.float32, device=od.device)
-        engine.downwash_device(dense, ed, f, ego_xy=ego_xy, stream=stream)
-        if default:
-            engine.synchronize()
-        if other_index is not None:
-            f[other_index < 0] = 0.0                          # no neighbour: no force
-        ctx.engine = engine
-        ctx.have_w = weights is not None
-        ctx.save_for_backward(od, ed, *(t for t in (ego_xy, other_index, weights) if t is not None))
-        ctx.opt = (ego_xy is not None, other_index is not None)
-        return f
-
-    @staticmethod
-    def backward(ctx, g_f):
-        od, ed, *rest = ctx.saved_tensors
-        ego_xy = rest.pop(0) if ctx.opt[0] else None
-        other_index = rest.pop(0) if ctx.opt[1] else None
-        eng = ctx.engine
-        _check_installed(eng, ctx.key, "DownwashFunction")
-        need = ctx.needs_input_grad
-        gf = g_f.to(torch.float64).contiguous()
-        B, np1 = ed.shape[0], ed.shape[1]
-        gz = torch.empty((B, np1, 6), dtype=torch.float64, device=od.device) if need[0] or need[2] else None
-        gw = torch.empty(17859, dtype=torch.float32, device=od.device) if ctx.have_w and need[4] else None
-        if gz is None and gw is None:
-            return (None,) * 6
-        stream, default = _cuda_stream(od)
-        eng.downwash_vjp_device(od, ed, gf, ego_xy=ego_xy, other_index=other_index, gz=gz, gw=gw, stream=stream)
-        if default:
-            eng.synchronize()
-        return (_scatter_gz(gz, od, other_index) if need[0] else None, None, _minus_gz(gz, ed) if need[2] else None, None, gw, None)
+def _force_single(engine, od, other_index, ed, ego_xy, stream, default):
+    """The stand-alone single-neighbour forward: downwash_device takes dense [B,N+1,10] windows, so rows are gathered (plumbing) and
+    neighbour-less instances zeroed behind it."""
+    B, np1 = ed.shape[0], ed.shape[1]
+    dense = od
+    if other_index is not None or od.shape[2] != 10:
+        rows = od if other_index is None else od[other_index.clamp(min=0).long()]
+        dense = torch.zeros((B, np1, 10), dtype=od.dtype, device=od.device)
+        dense[:, :, :od.shape[2]] = rows
+    f = torch.empty((B, np1, 3), dtype=torch.float32, device=od.device)
+    engine.downwash_device(dense, ed, f, ego_xy=ego_xy, stream=stream)
+    if default:
+        engine.synchronize()
+    if other_index is not None:
+        f[other_index < 0] = 0.0                              # no neighbour: no force
+    return f
 
 
-def downwash(engine, other, ego_ref, ego_xy=None, weights=None, other_index=None):
-    """f [B,N+1,3] float32 = the engine's gated downwash network on (other - ego_ref)[..., 0:6], differentiable in `other` (columns 0..5;
-    columns 6..9 get 0; with other_index [B] int32 the instances that share a neighbour row add up), `ego_ref` (the negative of the same
-    on columns 0..5) and `weights` (a float32 CUDA tensor / nn.Parameter of 17 859 in blob order; when given, the forward first installs
-    it in the engine unless it is what was installed last).  The gate is held fixed: ego_xy requiring grad raises.  A row whose upstream
-    gradient is not finite adds nothing to the weights' gradient and has NaN in its own input gradient."""
-    return DownwashFunction.apply(other, engine, ego_ref, ego_xy, weights, other_index)
+def _force_multi(engine, od, other_index, ed, ego_xy, stream, default):
+    f = torch.empty((ed.shape[0], ed.shape[1], 3), dtype=torch.float32, device=od.device)
+    engine.downwash_multi_device(od, other_index, ed, f, ego_xy=ego_xy, stream=stream)
+    if default:
+        engine.synchronize()
+    return f
 
 
-class ControlStepNDPFunction(torch.autograd.Function):
-    """forward(x0, engine, xr, ur, other, ego_xy, weights, other_index) -> (u0, X, U) float64: the fused control step (one launch);
-    backward: the step's adjoint (step_vjp_device) for x0, xr, ur and the force's gradient gf, then the network's backward pass on that gf
-    (downwash_vjp_device) for other, weights and xr's share (- g_z on columns 0..5)."""
-
-    @staticmethod
-    def forward(ctx, x0, engine, xr, ur, other, ego_xy=None, weights=None, other_index=None):
-        if isinstance(ego_xy, torch.Tensor) and ego_xy.requires_grad:
-            raise ValueError("ControlStepNDPFunction: ego_xy requires grad, but the r_horiz gate is piecewise constant and is not "
-                             "differentiated (detach it)")
-        det = lambda t: t.detach().contiguous()  # noqa: E731
-        x0, xr, ur, od = det(x0), det(xr), det(ur), det(other)
-        stream, default = _cuda_stream(x0)
-        if default:
-            stream.synchronize()
-        ctx.key = _install_weights(engine, weights, stream)
-        tape, u0, X, U = _taped_step(engine, stream, default, x0, xr, ur, other=od, ego_xy=ego_xy, other_index=other_index)
-        force = engine.device_force().clone()
-        ctx.engine = engine
-        ctx.have_w = weights is not None
-        ctx.opt = (ego_xy is not None, other_index is not None)
-        ctx.save_for_backward(x0, xr, ur, od, force, *tape, *(t for t in (ego_xy, other_index, weights) if t is not None))
-        return u0, X, U
-
-    @staticmethod
-    def backward(ctx, g_u0, g_X, g_U):
-        x0, xr, ur, od, force, t0, t1, t2, *rest = ctx.saved_tensors
-        ego_xy = rest.pop(0) if ctx.opt[0] else None
-        other_index = rest.pop(0) if ctx.opt[1] else None
-        eng = ctx.engine
-        if g_u0 is None and g_X is None and g_U is None:
-            return (None,) * 8
-        _check_installed(eng, ctx.key, "ControlStepNDPFunction")
-        B, N = x0.shape[0], xr.shape[1] - 1
-        need = ctx.needs_input_grad
-        net_w = ctx.have_w and need[6]
-        net = need[2] or need[4] or net_w                    # anything behind the force
-        stream, default = _cuda_stream(x0)
-        gx0, gxr, gur, gf = _taped_step_vjp(eng, x0, xr, ur, (t0, t1, t2), force, (g_u0, g_X, g_U), (need[0], need[2], need[3], net), stream)
-        g_other = gw = None
-        if net:
-            if default:
-                eng.synchronize()
-            gz = torch.empty((B, N + 1, 6), dtype=torch.float64, device=x0.device) if need[2] or need[4] else None
-            gw = torch.empty(17859, dtype=torch.float32, device=x0.device) if net_w else None
-            eng.downwash_vjp_device(od, xr, gf, ego_xy=ego_xy, other_index=other_index, gz=gz, gw=gw, stream=stream)
-        if default:
-            eng.synchronize()
-        if net and need[2]:
-            gxr[:, :, :6] -= gz
-        if net and need[4]:
-            g_other = _scatter_gz(gz, od, other_index)
-        return (gx0, None, gxr, gur, g_other, None, gw, None)
+def _step_single(engine, stream, default, x0, xr, ur, od, other_index, ego_xy):
+    """(tape, u0, X, U, force): the fused step (one launch); the force is the engine's buffer, which its next step overwrites."""
+    return (*_taped_step(engine, stream, default, x0, xr, ur, other=od, ego_xy=ego_xy, other_index=other_index), engine.device_force())
 
 
-def control_step_ndp(engine, x0, xr, ur, other, ego_xy=None, weights=None, other_index=None):
-    """(u0, X, U) = the engine's control step with the fused downwash network, differentiable with respect to x0, xr, ur, the neighbour
-    windows `other` and the network's `weights` (see downwash): the step's adjoint, then the network's backward pass on the force's
-    gradient.  Held fixed: the step's linearisation point and active set, and the gate (ego_xy requiring grad raises).  Instances whose
-    step failed (nonzero status) have NaN gradients of their own inputs and contribute nothing to the weights' gradient."""
-    return ControlStepNDPFunction.apply(x0, engine, xr, ur, other, ego_xy, weights, other_index)
+def _step_multi(engine, stream, default, x0, xr, ur, od, other_index, ego_xy):
+    """(tape, u0, X, U, force): the summed prediction into a force tensor of its own, then the external-force step."""
+    force = _force_multi(engine, od, other_index, xr, ego_xy, stream, False)
+    return (*_taped_step(engine, stream, default, x0, xr, ur, f=force), force)
 
 
-class NDPControlStep(torch.nn.Module):
-    """control_step_ndp with the network's weights as this module's nn.Parameter `weights` (float32 [17859], blob order), initialised
-    from the shipped blob on the engine's device.  forward(x0, xr, ur, other, ego_xy=None, other_index=None) -> (u0, X, U)."""
+class _Form:
+    def __init__(self, vjp, jvp, slots, fold, scatter, network_tz, force, step, own_force):
+        self.vjp, self.jvp = vjp, jvp                # (engine, other, other_index, ego_ref[, gf], **kw): the engine's backward pass / forward mode
+        self.slots = slots                           # other_index -> the slot axis of gz [B,*slots,N+1,6] and tz [B,T,*slots,N+1,6]
+        self.fold = fold                             # gz -> [B,N+1,6], ego_ref's share (negated by _minus_gz)
+        self.scatter = scatter                       # (gz, other, other_index) -> dL/d other
+        self.network_tz = network_tz                 # (t_other, t_ego, other_index) -> tz
+        self.force, self.step = force, step          # the stand-alone forward and the control step
+        self.own_force = own_force                   # the step's force is a tensor of the caller's (else the engine's buffer: clone to keep)
 
-    def __init__(self, engine, weights=None):
-        super().__init__()
-        from . import _lib
-        self.engine = engine
-        w = torch.as_tensor(_lib.load_weights() if weights is None else weights, dtype=torch.float32).clone()
-        dev = getattr(getattr(engine, "cfg", None), "device", None)
-        if dev is not None and torch.cuda.is_available():
-            w = w.to(torch.device("cuda", int(dev)))
-        self.weights = torch.nn.Parameter(w)
-
-    def forward(self, x0, xr, ur, other, ego_xy=None, other_index=None):
-        return control_step_ndp(self.engine, x0, xr, ur, other, ego_xy=ego_xy, weights=self.weights, other_index=other_index)
-
-
-# ---------------------------------------------------------------------------------------------- K neighbours per instance, differentiated
-# The K-slot siblings of the block above: the force is the sum over the slots other_index [B,K] (< 0: an empty slot) of the network on
-# (other[o_k] - ego_ref)[..., 0:6], each slot behind its own gate (BatchedNMPC.downwash_multi_device); its backward pass is one call
-# (BatchedNMPC.downwash_multi_vjp_device).  The same things are held fixed.  The fused step is single-neighbour, so control_step_ndp_multi
-# runs the summed prediction into a force tensor and then the external-force step: the route the multi-neighbour rollout takes.
 
 def _scatter_gz_multi(gz, other, other_index):
     """dL/d other from g_z [B,K,N+1,6]: columns 0..5, the rest 0; instances and slots that share a neighbour row add up."""
@@ -434,140 +360,6 @@ def _scatter_gz_multi(gz, other, other_index):
     g[:, :, :6].index_add_(0, other_index[has].long(), gz[has])
     return g
 
-
-class DownwashMultiFunction(torch.autograd.Function):
-    """forward(other, engine, other_index, ego_ref, ego_xy, weights) -> f [B,N+1,3] float32, the summed gated downwash force
-    (mlp_multi_kernel); backward: BatchedNMPC.downwash_multi_vjp_device for the gradients of other, ego_ref and weights."""
-
-    @staticmethod
-    def forward(ctx, other, engine, other_index, ego_ref, ego_xy=None, weights=None):
-        if isinstance(ego_xy, torch.Tensor) and ego_xy.requires_grad:
-            raise ValueError("DownwashMultiFunction: ego_xy requires grad, but the r_horiz gate is piecewise constant and is not "
-                             "differentiated (detach it)")
-        od, ed = other.detach().contiguous(), ego_ref.detach().contiguous()
-        stream, default = _cuda_stream(od)
-        if default:
-            stream.synchronize()
-        ctx.key = _install_weights(engine, weights, stream)
-        f = torch.empty((ed.shape[0], ed.shape[1], 3), dtype=torch.float32, device=od.device)
-        engine.downwash_multi_device(od, other_index, ed, f, ego_xy=ego_xy, stream=stream)
-        if default:
-            engine.synchronize()
-        ctx.engine = engine
-        ctx.have_w = weights is not None
-        ctx.have_xy = ego_xy is not None
-        ctx.save_for_backward(od, ed, other_index, *(t for t in (ego_xy, weights) if t is not None))
-        return f
-
-    @staticmethod
-    def backward(ctx, g_f):
-        od, ed, other_index, *rest = ctx.saved_tensors
-        ego_xy = rest.pop(0) if ctx.have_xy else None
-        eng = ctx.engine
-        _check_installed(eng, ctx.key, "DownwashMultiFunction")
-        need = ctx.needs_input_grad
-        gf = g_f.to(torch.float64).contiguous()
-        B, np1, K = ed.shape[0], ed.shape[1], other_index.shape[1]
-        gz = torch.empty((B, K, np1, 6), dtype=torch.float64, device=od.device) if need[0] or need[3] else None
-        gw = torch.empty(17859, dtype=torch.float32, device=od.device) if ctx.have_w and need[5] else None
-        if gz is None and gw is None:
-            return (None,) * 6
-        stream, default = _cuda_stream(od)
-        eng.downwash_multi_vjp_device(od, other_index, ed, gf, ego_xy=ego_xy, gz=gz, gw=gw, stream=stream)
-        if default:
-            eng.synchronize()
-        return (_scatter_gz_multi(gz, od, other_index) if need[0] else None, None, None,
-                _minus_gz(gz.sum(dim=1), ed) if need[3] else None, None, gw)
-
-
-def downwash_multi(engine, other, other_index, ego_ref, ego_xy=None, weights=None):
-    """f [B,N+1,3] float32 = the engine's summed downwash force from K neighbours per instance: other [rows,N+1,6 or 10] float64,
-    other_index int32 [B,K] the rows of `other` instance i hears (< 0: an empty slot; the same row twice counts twice), each slot behind
-    its own gate.  Differentiable in `other` (columns 0..5; instances and slots that share a row add up), `ego_ref` (minus the sum over
-    the slots on columns 0..5) and `weights` (as `downwash`: installed first unless they are what was installed last).  The gate is held
-    fixed: ego_xy requiring grad raises.  A row whose upstream gradient is not finite adds nothing to the weights' gradient and has NaN
-    in the input gradients of its open slots."""
-    return DownwashMultiFunction.apply(other, engine, other_index, ego_ref, ego_xy, weights)
-
-
-class ControlStepNDPMultiFunction(torch.autograd.Function):
-    """forward(x0, engine, xr, ur, other, other_index, ego_xy, weights) -> (u0, X, U) float64: the summed prediction (downwash_multi_device
-    with ego_ref = xr) into a force tensor, then the external-force control step; backward: the step's adjoint (step_vjp_device) for x0,
-    xr, ur and the force's gradient gf, then downwash_multi_vjp_device on that gf for other, weights and xr's share (minus the sum over
-    the slots of g_z on columns 0..5)."""
-
-    @staticmethod
-    def forward(ctx, x0, engine, xr, ur, other, other_index, ego_xy=None, weights=None):
-        if isinstance(ego_xy, torch.Tensor) and ego_xy.requires_grad:
-            raise ValueError("ControlStepNDPMultiFunction: ego_xy requires grad, but the r_horiz gate is piecewise constant and is not "
-                             "differentiated (detach it)")
-        det = lambda t: t.detach().contiguous()  # noqa: E731
-        x0, xr, ur, od = det(x0), det(xr), det(ur), det(other)
-        stream, default = _cuda_stream(x0)
-        if default:
-            stream.synchronize()
-        ctx.key = _install_weights(engine, weights, stream)
-        force = torch.empty((xr.shape[0], xr.shape[1], 3), dtype=torch.float32, device=x0.device)
-        engine.downwash_multi_device(od, other_index, xr, force, ego_xy=ego_xy, stream=stream)
-        tape, u0, X, U = _taped_step(engine, stream, default, x0, xr, ur, f=force)
-        ctx.engine = engine
-        ctx.have_w = weights is not None
-        ctx.have_xy = ego_xy is not None
-        ctx.save_for_backward(x0, xr, ur, od, other_index, force, *tape, *(t for t in (ego_xy, weights) if t is not None))
-        return u0, X, U
-
-    @staticmethod
-    def backward(ctx, g_u0, g_X, g_U):
-        x0, xr, ur, od, other_index, force, t0, t1, t2, *rest = ctx.saved_tensors
-        ego_xy = rest.pop(0) if ctx.have_xy else None
-        eng = ctx.engine
-        if g_u0 is None and g_X is None and g_U is None:
-            return (None,) * 8
-        _check_installed(eng, ctx.key, "ControlStepNDPMultiFunction")
-        B, N, K = x0.shape[0], xr.shape[1] - 1, other_index.shape[1]
-        need = ctx.needs_input_grad
-        net_w = ctx.have_w and need[7]
-        net = need[2] or need[4] or net_w                    # anything behind the force
-        stream, default = _cuda_stream(x0)
-        gx0, gxr, gur, gf = _taped_step_vjp(eng, x0, xr, ur, (t0, t1, t2), force, (g_u0, g_X, g_U), (need[0], need[2], need[3], net), stream)
-        g_other = gw = None
-        if net:
-            if default:
-                eng.synchronize()
-            gz = torch.empty((B, K, N + 1, 6), dtype=torch.float64, device=x0.device) if need[2] or need[4] else None
-            gw = torch.empty(17859, dtype=torch.float32, device=x0.device) if net_w else None
-            eng.downwash_multi_vjp_device(od, other_index, xr, gf, ego_xy=ego_xy, gz=gz, gw=gw, stream=stream)
-        if default:
-            eng.synchronize()
-        if net and need[2]:
-            gxr[:, :, :6] -= gz.sum(dim=1)
-        if net and need[4]:
-            g_other = _scatter_gz_multi(gz, od, other_index)
-        return (gx0, None, gxr, gur, g_other, None, None, gw)
-
-
-def control_step_ndp_multi(engine, x0, xr, ur, other, other_index, ego_xy=None, weights=None):
-    """(u0, X, U) = the engine's control step compensating the summed downwash of K neighbours per instance (see downwash_multi for
-    other / other_index), differentiable with respect to x0, xr, ur, `other` and the network's `weights`: the step's adjoint, then the
-    K-slot backward pass of the network on the force's gradient.  The forward is two launches (the summed prediction, then the
-    external-force step): the fused step is single-neighbour.  Held fixed: the linearisation point, the active set and the gates (ego_xy
-    requiring grad raises).  Instances whose step failed (nonzero status) have NaN gradients of their own inputs and contribute nothing
-    to the weights' gradient."""
-    return ControlStepNDPMultiFunction.apply(x0, engine, xr, ur, other, other_index, ego_xy, weights)
-
-
-class NDPControlStepMulti(NDPControlStep):
-    """control_step_ndp_multi with the network's weights as this module's nn.Parameter `weights` (see NDPControlStep).
-    forward(x0, xr, ur, other, other_index, ego_xy=None) -> (u0, X, U)."""
-
-    def forward(self, x0, xr, ur, other, other_index, ego_xy=None):
-        return control_step_ndp_multi(self.engine, x0, xr, ur, other, other_index, ego_xy=ego_xy, weights=self.weights)
-
-
-# ---------------------------------------------------------------------------------------------- the downwash network, forward mode
-# The mirror of the single-neighbour block above (BatchedNMPC.downwash_jvp_device): the first-order change of the force along directions of the neighbour
-# windows, of ego_ref and of the weights, and its composition with the step's forward mode.  Held fixed: what the backward holds fixed
-# (gate, linearisation point, active set); ego_xy has no tangent.  Plain tensors, no autograd hookup, like control_step_jvp.
 
 def _with_t_axis(tangents, dims, who):
     """The tangents (None, or tensors whose T axis -- position 0 for the weights' direction (dims 1), 1 for the others -- may be missing)
@@ -606,64 +398,6 @@ def _network_tz(t_other, t_ego, other_index):
     return None if tz is None else tz.contiguous()
 
 
-def downwash_jvp(engine, other, ego_ref, tangents, ego_xy=None, weights=None, other_index=None):
-    """(f, df): the engine's gated downwash force f [B,N+1,3] float32 on (other - ego_ref)[..., 0:6] and its first-order change df
-    [B,T,N+1,3] float64 along tangents = (t_other, t_ego_ref, t_weights) (forward mode: BatchedNMPC.downwash_jvp_device).  t_other is
-    shaped like `other` ([rows,T,N+1,6 or 10]; columns 6..9 move nothing; with other_index every instance reads its neighbour row's
-    direction), t_ego_ref like ego_ref ([B,T,N+1,10]), t_weights [T,17859] float32 in blob order; each may be None (= 0, not all three)
-    and each may come without the T axis -- then df is [B,N+1,3] if none has it.  `weights`, when given, are installed first as
-    `downwash` does.  The gate is held fixed: ego_xy has no tangent.  No autograd hookup."""
-    od, ed = other.detach().contiguous(), ego_ref.detach().contiguous()
-    (t_other, t_ego, t_w), T, had = _with_t_axis(tangents, (3, 3, 1), "downwash_jvp")
-    stream, default = _cuda_stream(od)
-    if default:
-        stream.synchronize()
-    _install_weights(engine, weights, stream)
-    B, np1 = ed.shape[0], ed.shape[1]
-    tz = _network_tz(t_other, t_ego, other_index)
-    tw = None if t_w is None else t_w.to(torch.float32).contiguous()
-    f = torch.empty((B, np1, 3), dtype=torch.float32, device=od.device)
-    df = torch.empty((B, T, np1, 3), dtype=torch.float64, device=od.device)
-    engine.downwash_jvp_device(od, ed, tz=tz, tw=tw, ego_xy=ego_xy, other_index=other_index, n_tan=T, df=df, f_check=f, stream=stream)
-    if default:
-        engine.synchronize()
-    return f, df if had else df[:, 0]
-
-
-def control_step_ndp_jvp(engine, x0, xr, ur, other, tangents, ego_xy=None, weights=None, other_index=None):
-    """(u0, X, U, du0, dX, dU): the engine's control step with the fused downwash network and its new iterate, and the first-order change
-    of all three along tangents = (tx0, txr, tur, t_other, t_weights) -- control_step_jvp with the force's tangent produced by the
-    network's forward mode instead of given.  On one stream: the taped fused step; the network's JVP with tz = t_other[other_index] -
-    txr[..., 0:6] (and t_weights), giving tf; BatchedNMPC.step_jvp_device with (tx0, txr, tur, tf) and the force the step wrote.
-    Shapes: tx0 [B,T,10], txr [B,T,N+1,10], tur [B,T,N,4], t_other like `other` with the T axis behind its first, t_weights [T,17859]
-    float32; None = 0 (not all five); each may come without the T axis, and the outputs carry it unless none does.  Held fixed: the
-    linearisation point, the active set and the gate (ego_xy has no tangent).  Instances whose step failed have NaN tangents.  No
-    autograd hookup."""
-    det = lambda t: t.detach().contiguous()  # noqa: E731
-    x0, xr, ur, od = det(x0), det(xr), det(ur), det(other)
-    (tx0, txr, tur, t_other, t_w), T, had = _with_t_axis(tangents, (2, 3, 3, 3, 1), "control_step_ndp_jvp")
-    tx0, txr, tur = (None if t is None else t.to(torch.float64).contiguous() for t in (tx0, txr, tur))
-    B, N = x0.shape[0], xr.shape[1] - 1
-    stream, default = _cuda_stream(x0)
-    if default:
-        stream.synchronize()
-    _install_weights(engine, weights, stream)
-    tape, u0, X, U = _taped_step(engine, stream, default, x0, xr, ur, other=od, ego_xy=ego_xy, other_index=other_index)
-    tz = _network_tz(t_other, txr, other_index)
-    tw = None if t_w is None else t_w.to(torch.float32).contiguous()
-    tf = None
-    if tz is not None or tw is not None:
-        tf = torch.empty((B, T, N + 1, 3), dtype=torch.float64, device=x0.device)
-        engine.downwash_jvp_device(od, xr, tz=tz, tw=tw, ego_xy=ego_xy, other_index=other_index, n_tan=T, df=tf, stream=stream)
-    du0, dX, dU = (torch.empty((B, T) + s, dtype=torch.float64, device=x0.device) for s in ((4,), (N + 1, 10), (N, 4)))
-    engine.step_jvp_device(x0, xr, ur, tape, tx0, txr, tur, tf, f=engine.device_force(), du0=du0, dX=dX, dU=dU, stream=stream)
-    if default:
-        engine.synchronize()
-    if not had:
-        du0, dX, dU = du0[:, 0], dX[:, 0], dU[:, 0]
-    return u0, X, U, du0, dX, dU
-
-
 def _network_tz_multi(t_other, t_ego, other_index):
     """tz [B,T,K,N+1,6] = t_other[other_index[:, k]] - t_ego on columns 0..5 per slot (either may be None; both None: None).  Plumbing, the
     mirror of _scatter_gz_multi; an empty slot's rows are never read by the device."""
@@ -677,26 +411,296 @@ def _network_tz_multi(t_other, t_ego, other_index):
     return None if tz is None else tz.contiguous()
 
 
+_SINGLE = _Form(
+    vjp=lambda eng, other, other_index, ego_ref, gf, **kw: eng.downwash_vjp_device(other, ego_ref, gf, other_index=other_index, **kw),
+    jvp=lambda eng, other, other_index, ego_ref, **kw: eng.downwash_jvp_device(other, ego_ref, other_index=other_index, **kw),
+    slots=lambda other_index: (), fold=lambda gz: gz, scatter=_scatter_gz, network_tz=_network_tz,
+    force=_force_single, step=_step_single, own_force=False)
+_MULTI = _Form(
+    vjp=lambda eng, other, other_index, ego_ref, gf, **kw: eng.downwash_multi_vjp_device(other, other_index, ego_ref, gf, **kw),
+    jvp=lambda eng, other, other_index, ego_ref, **kw: eng.downwash_multi_jvp_device(other, other_index, ego_ref, **kw),
+    slots=lambda other_index: (other_index.shape[1],), fold=lambda gz: gz.sum(dim=1), scatter=_scatter_gz_multi, network_tz=_network_tz_multi,
+    force=_force_multi, step=_step_multi, own_force=True)
+
+
+def _save_network(ctx, engine, key, weights, tensors, ego_xy, other_index):
+    ctx.engine, ctx.key, ctx.have_w = engine, key, weights is not None
+    ctx.opt = (ego_xy is not None, other_index is not None)
+    ctx.save_for_backward(*tensors, *(t for t in (ego_xy, other_index, weights) if t is not None))
+
+
+def _saved_network(ctx, n):
+    """(the first n saved tensors, ego_xy, other_index) of _save_network."""
+    rest = list(ctx.saved_tensors[n:])
+    ego_xy = rest.pop(0) if ctx.opt[0] else None
+    return ctx.saved_tensors[:n], ego_xy, rest.pop(0) if ctx.opt[1] else None
+
+
+def _downwash_forward(ctx, form, who, other, engine, ego_ref, ego_xy, weights, other_index):
+    _refuse_grad(who, "ego_xy", ego_xy, _WHY_GATE)
+    od, ed = other.detach().contiguous(), ego_ref.detach().contiguous()
+    stream, default, key = _enter(engine, od, weights)
+    f = form.force(engine, od, other_index, ed, ego_xy, stream, default)
+    _save_network(ctx, engine, key, weights, (od, ed), ego_xy, other_index)
+    return f
+
+
+def _downwash_backward(ctx, form, who, g_f, need):
+    """need: which of (other, ego_ref, weights) require a gradient; returns those three."""
+    (od, ed), ego_xy, other_index = _saved_network(ctx, 2)
+    eng = ctx.engine
+    _check_installed(eng, ctx.key, who)
+    gf = g_f.to(torch.float64).contiguous()
+    B, np1 = ed.shape[0], ed.shape[1]
+    gz = torch.empty((B, *form.slots(other_index), np1, 6), dtype=torch.float64, device=od.device) if need[0] or need[1] else None
+    gw = torch.empty(_lib.MLP_NPARAM, dtype=torch.float32, device=od.device) if ctx.have_w and need[2] else None
+    if gz is None and gw is None:
+        return None, None, None
+    stream, default = _cuda_stream(od)
+    form.vjp(eng, od, other_index, ed, gf, ego_xy=ego_xy, gz=gz, gw=gw, stream=stream)
+    if default:
+        eng.synchronize()
+    return form.scatter(gz, od, other_index) if need[0] else None, _minus_gz(form.fold(gz), ed) if need[1] else None, gw
+
+
+def _ndp_step_forward(ctx, form, who, x0, engine, xr, ur, other, ego_xy, weights, other_index):
+    _refuse_grad(who, "ego_xy", ego_xy, _WHY_GATE)
+    x0, xr, ur, od = _det(x0), _det(xr), _det(ur), _det(other)
+    stream, default, key = _enter(engine, x0, weights)
+    tape, u0, X, U, force = form.step(engine, stream, default, x0, xr, ur, od, other_index, ego_xy)
+    _save_network(ctx, engine, key, weights, (x0, xr, ur, od, force if form.own_force else force.clone(), *tape), ego_xy, other_index)
+    return u0, X, U
+
+
+def _ndp_step_backward(ctx, form, who, upstream, need):
+    """need: which of (x0, xr, ur, other, weights) require a gradient; returns those five."""
+    (x0, xr, ur, od, force, *tape), ego_xy, other_index = _saved_network(ctx, 8)
+    eng = ctx.engine
+    if all(g is None for g in upstream):
+        return (None,) * 5
+    _check_installed(eng, ctx.key, who)
+    B, N = x0.shape[0], xr.shape[1] - 1
+    net_w = ctx.have_w and need[4]
+    net = need[1] or need[3] or net_w                        # anything behind the force
+    stream, default = _cuda_stream(x0)
+    gx0, gxr, gur, gf = _taped_step_vjp(eng, x0, xr, ur, tuple(tape), force, upstream, (need[0], need[1], need[2], net), stream)
+    g_other = gw = None
+    if net:
+        if default:
+            eng.synchronize()
+        gz = torch.empty((B, *form.slots(other_index), N + 1, 6), dtype=torch.float64, device=x0.device) if need[1] or need[3] else None
+        gw = torch.empty(_lib.MLP_NPARAM, dtype=torch.float32, device=x0.device) if net_w else None
+        form.vjp(eng, od, other_index, xr, gf, ego_xy=ego_xy, gz=gz, gw=gw, stream=stream)
+    if default:
+        eng.synchronize()
+    if net and need[1]:
+        gxr[:, :, :6] -= form.fold(gz)
+    if net and need[3]:
+        g_other = form.scatter(gz, od, other_index)
+    return gx0, gxr, gur, g_other, gw
+
+
+def _downwash_jvp(form, who, engine, other, other_index, ego_ref, tangents, ego_xy, weights):
+    od, ed = other.detach().contiguous(), ego_ref.detach().contiguous()
+    (t_other, t_ego, t_w), T, had = _with_t_axis(tangents, (3, 3, 1), who)
+    stream, default, _ = _enter(engine, od, weights)
+    B, np1 = ed.shape[0], ed.shape[1]
+    tz = form.network_tz(t_other, t_ego, other_index)
+    f = torch.empty((B, np1, 3), dtype=torch.float32, device=od.device)
+    df = torch.empty((B, T, np1, 3), dtype=torch.float64, device=od.device)
+    form.jvp(engine, od, other_index, ed, tz=tz, tw=_cast(t_w, torch.float32), ego_xy=ego_xy, n_tan=T, df=df, f_check=f, stream=stream)
+    if default:
+        engine.synchronize()
+    return f, df if had else df[:, 0]
+
+
+def _ndp_step_jvp(form, who, engine, x0, xr, ur, other, other_index, tangents, ego_xy, weights):
+    x0, xr, ur, od = _det(x0), _det(xr), _det(ur), _det(other)
+    (tx0, txr, tur, t_other, t_w), T, had = _with_t_axis(tangents, (2, 3, 3, 3, 1), who)
+    tx0, txr, tur = (_cast(t, torch.float64) for t in (tx0, txr, tur))
+    B, N = x0.shape[0], xr.shape[1] - 1
+    stream, default, _ = _enter(engine, x0, weights)
+    tape, u0, X, U, force = form.step(engine, stream, default, x0, xr, ur, od, other_index, ego_xy)
+    tz, tw = form.network_tz(t_other, txr, other_index), _cast(t_w, torch.float32)
+    tf = None
+    if tz is not None or tw is not None:
+        tf = torch.empty((B, T, N + 1, 3), dtype=torch.float64, device=x0.device)
+        form.jvp(engine, od, other_index, xr, tz=tz, tw=tw, ego_xy=ego_xy, n_tan=T, df=tf, stream=stream)
+    du0, dX, dU = (torch.empty((B, T) + s, dtype=torch.float64, device=x0.device) for s in ((4,), (N + 1, 10), (N, 4)))
+    engine.step_jvp_device(x0, xr, ur, tape, tx0, txr, tur, tf, f=force, du0=du0, dX=dX, dU=dU, stream=stream)
+    if default:
+        engine.synchronize()
+    if not had:
+        du0, dX, dU = du0[:, 0], dX[:, 0], dU[:, 0]
+    return u0, X, U, du0, dX, dU
+
+
+class DownwashFunction(torch.autograd.Function):
+    """forward(other, engine, ego_ref, ego_xy, weights, other_index) -> f [B,N+1,3] float32, the gated downwash force (mlp_kernel);
+    backward: BatchedNMPC.downwash_vjp_device for the gradients of other, ego_ref and weights."""
+
+    @staticmethod
+    def forward(ctx, other, engine, ego_ref, ego_xy=None, weights=None, other_index=None):
+        return _downwash_forward(ctx, _SINGLE, "DownwashFunction", other, engine, ego_ref, ego_xy, weights, other_index)
+
+    @staticmethod
+    def backward(ctx, g_f):
+        need = ctx.needs_input_grad
+        g_other, g_ego, gw = _downwash_backward(ctx, _SINGLE, "DownwashFunction", g_f, (need[0], need[2], need[4]))
+        return (g_other, None, g_ego, None, gw, None)
+
+
+def downwash(engine, other, ego_ref, ego_xy=None, weights=None, other_index=None):
+    """f [B,N+1,3] float32 = the engine's gated downwash network on (other - ego_ref)[..., 0:6], differentiable in `other` (columns 0..5;
+    columns 6..9 get 0; with other_index [B] int32 the instances that share a neighbour row add up), `ego_ref` (the negative of the same
+    on columns 0..5) and `weights` (a float32 CUDA tensor / nn.Parameter of 17 859 in blob order; when given, the forward first installs
+    it in the engine unless it is what was installed last).  The gate is held fixed: ego_xy requiring grad raises.  A row whose upstream
+    gradient is not finite adds nothing to the weights' gradient and has NaN in its own input gradient."""
+    return DownwashFunction.apply(other, engine, ego_ref, ego_xy, weights, other_index)
+
+
+class ControlStepNDPFunction(torch.autograd.Function):
+    """forward(x0, engine, xr, ur, other, ego_xy, weights, other_index) -> (u0, X, U) float64: the fused control step (one launch);
+    backward: the step's adjoint (step_vjp_device) for x0, xr, ur and the force's gradient gf, then the network's backward pass on that gf
+    (downwash_vjp_device) for other, weights and xr's share (- g_z on columns 0..5)."""
+
+    @staticmethod
+    def forward(ctx, x0, engine, xr, ur, other, ego_xy=None, weights=None, other_index=None):
+        return _ndp_step_forward(ctx, _SINGLE, "ControlStepNDPFunction", x0, engine, xr, ur, other, ego_xy, weights, other_index)
+
+    @staticmethod
+    def backward(ctx, g_u0, g_X, g_U):
+        need = ctx.needs_input_grad
+        gx0, gxr, gur, g_other, gw = _ndp_step_backward(ctx, _SINGLE, "ControlStepNDPFunction", (g_u0, g_X, g_U),
+                                                        (need[0], need[2], need[3], need[4], need[6]))
+        return (gx0, None, gxr, gur, g_other, None, gw, None)
+
+
+def control_step_ndp(engine, x0, xr, ur, other, ego_xy=None, weights=None, other_index=None):
+    """(u0, X, U) = the engine's control step with the fused downwash network, differentiable with respect to x0, xr, ur, the neighbour
+    windows `other` and the network's `weights` (see downwash): the step's adjoint, then the network's backward pass on the force's
+    gradient.  Held fixed: the step's linearisation point and active set, and the gate (ego_xy requiring grad raises).  Instances whose
+    step failed (nonzero status) have NaN gradients of their own inputs and contribute nothing to the weights' gradient."""
+    return ControlStepNDPFunction.apply(x0, engine, xr, ur, other, ego_xy, weights, other_index)
+
+
+class NDPControlStep(torch.nn.Module):
+    """control_step_ndp with the network's weights as this module's nn.Parameter `weights` (float32 [17859], blob order), initialised
+    from the shipped blob on the engine's device.  forward(x0, xr, ur, other, ego_xy=None, other_index=None) -> (u0, X, U)."""
+
+    def __init__(self, engine, weights=None):
+        super().__init__()
+        self.engine = engine
+        w = torch.as_tensor(_lib.load_weights() if weights is None else weights, dtype=torch.float32).clone()
+        dev = getattr(getattr(engine, "cfg", None), "device", None)
+        if dev is not None and torch.cuda.is_available():
+            w = w.to(torch.device("cuda", int(dev)))
+        self.weights = torch.nn.Parameter(w)
+
+    def forward(self, x0, xr, ur, other, ego_xy=None, other_index=None):
+        return control_step_ndp(self.engine, x0, xr, ur, other, ego_xy=ego_xy, weights=self.weights, other_index=other_index)
+
+
+# ---------------------------------------------------------------------------------------------- K neighbours per instance, differentiated
+# The K-slot siblings of the block above: the force is the sum over the slots other_index [B,K] (< 0: an empty slot) of the network on
+# (other[o_k] - ego_ref)[..., 0:6], each slot behind its own gate (BatchedNMPC.downwash_multi_device); its backward pass is one call
+# (BatchedNMPC.downwash_multi_vjp_device).  The same things are held fixed.  The fused step is single-neighbour, so control_step_ndp_multi
+# runs the summed prediction into a force tensor and then the external-force step: the route the multi-neighbour rollout takes.
+
+class DownwashMultiFunction(torch.autograd.Function):
+    """forward(other, engine, other_index, ego_ref, ego_xy, weights) -> f [B,N+1,3] float32, the summed gated downwash force
+    (mlp_multi_kernel); backward: BatchedNMPC.downwash_multi_vjp_device for the gradients of other, ego_ref and weights."""
+
+    @staticmethod
+    def forward(ctx, other, engine, other_index, ego_ref, ego_xy=None, weights=None):
+        return _downwash_forward(ctx, _MULTI, "DownwashMultiFunction", other, engine, ego_ref, ego_xy, weights, other_index)
+
+    @staticmethod
+    def backward(ctx, g_f):
+        need = ctx.needs_input_grad
+        g_other, g_ego, gw = _downwash_backward(ctx, _MULTI, "DownwashMultiFunction", g_f, (need[0], need[3], need[5]))
+        return (g_other, None, None, g_ego, None, gw)
+
+
+def downwash_multi(engine, other, other_index, ego_ref, ego_xy=None, weights=None):
+    """f [B,N+1,3] float32 = the engine's summed downwash force from K neighbours per instance: other [rows,N+1,6 or 10] float64,
+    other_index int32 [B,K] the rows of `other` instance i hears (< 0: an empty slot; the same row twice counts twice), each slot behind
+    its own gate.  Differentiable in `other` (columns 0..5; instances and slots that share a row add up), `ego_ref` (minus the sum over
+    the slots on columns 0..5) and `weights` (as `downwash`: installed first unless they are what was installed last).  The gate is held
+    fixed: ego_xy requiring grad raises.  A row whose upstream gradient is not finite adds nothing to the weights' gradient and has NaN
+    in the input gradients of its open slots."""
+    return DownwashMultiFunction.apply(other, engine, other_index, ego_ref, ego_xy, weights)
+
+
+class ControlStepNDPMultiFunction(torch.autograd.Function):
+    """forward(x0, engine, xr, ur, other, other_index, ego_xy, weights) -> (u0, X, U) float64: the summed prediction (downwash_multi_device
+    with ego_ref = xr) into a force tensor, then the external-force control step; backward: the step's adjoint (step_vjp_device) for x0,
+    xr, ur and the force's gradient gf, then downwash_multi_vjp_device on that gf for other, weights and xr's share (minus the sum over
+    the slots of g_z on columns 0..5)."""
+
+    @staticmethod
+    def forward(ctx, x0, engine, xr, ur, other, other_index, ego_xy=None, weights=None):
+        return _ndp_step_forward(ctx, _MULTI, "ControlStepNDPMultiFunction", x0, engine, xr, ur, other, ego_xy, weights, other_index)
+
+    @staticmethod
+    def backward(ctx, g_u0, g_X, g_U):
+        need = ctx.needs_input_grad
+        gx0, gxr, gur, g_other, gw = _ndp_step_backward(ctx, _MULTI, "ControlStepNDPMultiFunction", (g_u0, g_X, g_U),
+                                                        (need[0], need[2], need[3], need[4], need[7]))
+        return (gx0, None, gxr, gur, g_other, None, None, gw)
+
+
+def control_step_ndp_multi(engine, x0, xr, ur, other, other_index, ego_xy=None, weights=None):
+    """(u0, X, U) = the engine's control step compensating the summed downwash of K neighbours per instance (see downwash_multi for
+    other / other_index), differentiable with respect to x0, xr, ur, `other` and the network's `weights`: the step's adjoint, then the
+    K-slot backward pass of the network on the force's gradient.  The forward is two launches (the summed prediction, then the
+    external-force step): the fused step is single-neighbour.  Held fixed: the linearisation point, the active set and the gates (ego_xy
+    requiring grad raises).  Instances whose step failed (nonzero status) have NaN gradients of their own inputs and contribute nothing
+    to the weights' gradient."""
+    return ControlStepNDPMultiFunction.apply(x0, engine, xr, ur, other, other_index, ego_xy, weights)
+
+
+class NDPControlStepMulti(NDPControlStep):
+    """control_step_ndp_multi with the network's weights as this module's nn.Parameter `weights` (see NDPControlStep).
+    forward(x0, xr, ur, other, other_index, ego_xy=None) -> (u0, X, U)."""
+
+    def forward(self, x0, xr, ur, other, other_index, ego_xy=None):
+        return control_step_ndp_multi(self.engine, x0, xr, ur, other, other_index, ego_xy=ego_xy, weights=self.weights)
+
+
+# ---------------------------------------------------------------------------------------------- the downwash network, forward mode
+# The mirror of the single-neighbour block above (BatchedNMPC.downwash_jvp_device): the first-order change of the force along directions of the neighbour
+# windows, of ego_ref and of the weights, and its composition with the step's forward mode.  Held fixed: what the backward holds fixed
+# (gate, linearisation point, active set); ego_xy has no tangent.  Plain tensors, no autograd hookup, like control_step_jvp.
+
+def downwash_jvp(engine, other, ego_ref, tangents, ego_xy=None, weights=None, other_index=None):
+    """(f, df): the engine's gated downwash force f [B,N+1,3] float32 on (other - ego_ref)[..., 0:6] and its first-order change df
+    [B,T,N+1,3] float64 along tangents = (t_other, t_ego_ref, t_weights) (forward mode: BatchedNMPC.downwash_jvp_device).  t_other is
+    shaped like `other` ([rows,T,N+1,6 or 10]; columns 6..9 move nothing; with other_index every instance reads its neighbour row's
+    direction), t_ego_ref like ego_ref ([B,T,N+1,10]), t_weights [T,17859] float32 in blob order; each may be None (= 0, not all three)
+    and each may come without the T axis -- then df is [B,N+1,3] if none has it.  `weights`, when given, are installed first as
+    `downwash` does.  The gate is held fixed: ego_xy has no tangent.  No autograd hookup."""
+    return _downwash_jvp(_SINGLE, "downwash_jvp", engine, other, other_index, ego_ref, tangents, ego_xy, weights)
+
+
+def control_step_ndp_jvp(engine, x0, xr, ur, other, tangents, ego_xy=None, weights=None, other_index=None):
+    """(u0, X, U, du0, dX, dU): the engine's control step with the fused downwash network and its new iterate, and the first-order change
+    of all three along tangents = (tx0, txr, tur, t_other, t_weights) -- control_step_jvp with the force's tangent produced by the
+    network's forward mode instead of given.  On one stream: the taped fused step; the network's JVP with tz = t_other[other_index] -
+    txr[..., 0:6] (and t_weights), giving tf; BatchedNMPC.step_jvp_device with (tx0, txr, tur, tf) and the force the step wrote.
+    Shapes: tx0 [B,T,10], txr [B,T,N+1,10], tur [B,T,N,4], t_other like `other` with the T axis behind its first, t_weights [T,17859]
+    float32; None = 0 (not all five); each may come without the T axis, and the outputs carry it unless none does.  Held fixed: the
+    linearisation point, the active set and the gate (ego_xy has no tangent).  Instances whose step failed have NaN tangents.  No
+    autograd hookup."""
+    return _ndp_step_jvp(_SINGLE, "control_step_ndp_jvp", engine, x0, xr, ur, other, other_index, tangents, ego_xy, weights)
+
+
 def downwash_multi_jvp(engine, other, other_index, ego_ref, tangents, ego_xy=None, weights=None):
     """(f, df): the engine's summed downwash force f [B,N+1,3] float32 from K neighbours per instance (see downwash_multi) and its
     first-order change df [B,T,N+1,3] float64 along tangents = (t_other, t_ego_ref, t_weights), shaped as downwash_jvp takes them (forward
     mode: BatchedNMPC.downwash_multi_jvp_device; every slot reads its neighbour row's direction).  The gates are held fixed.  No autograd
     hookup."""
-    od, ed = other.detach().contiguous(), ego_ref.detach().contiguous()
-    (t_other, t_ego, t_w), T, had = _with_t_axis(tangents, (3, 3, 1), "downwash_multi_jvp")
-    stream, default = _cuda_stream(od)
-    if default:
-        stream.synchronize()
-    _install_weights(engine, weights, stream)
-    B, np1 = ed.shape[0], ed.shape[1]
-    tz = _network_tz_multi(t_other, t_ego, other_index)
-    tw = None if t_w is None else t_w.to(torch.float32).contiguous()
-    f = torch.empty((B, np1, 3), dtype=torch.float32, device=od.device)
-    df = torch.empty((B, T, np1, 3), dtype=torch.float64, device=od.device)
-    engine.downwash_multi_jvp_device(od, other_index, ed, tz=tz, tw=tw, ego_xy=ego_xy, n_tan=T, df=df, f_check=f, stream=stream)
-    if default:
-        engine.synchronize()
-    return f, df if had else df[:, 0]
+    return _downwash_jvp(_MULTI, "downwash_multi_jvp", engine, other, other_index, ego_ref, tangents, ego_xy, weights)
 
 
 def control_step_ndp_multi_jvp(engine, x0, xr, ur, other, other_index, tangents, ego_xy=None, weights=None):
@@ -705,31 +709,7 @@ def control_step_ndp_multi_jvp(engine, x0, xr, ur, other, other_index, tangents,
     external-force step, the network's K-slot JVP with tz[:, :, k] = t_other[other_index[:, k]] - txr[..., 0:6] (and t_weights), giving
     tf; BatchedNMPC.step_jvp_device with (tx0, txr, tur, tf) and the same force.  Held fixed: the linearisation point, the active set and
     the gates.  Instances whose step failed have NaN tangents.  No autograd hookup."""
-    det = lambda t: t.detach().contiguous()  # noqa: E731
-    x0, xr, ur, od = det(x0), det(xr), det(ur), det(other)
-    (tx0, txr, tur, t_other, t_w), T, had = _with_t_axis(tangents, (2, 3, 3, 3, 1), "control_step_ndp_multi_jvp")
-    tx0, txr, tur = (None if t is None else t.to(torch.float64).contiguous() for t in (tx0, txr, tur))
-    B, N = x0.shape[0], xr.shape[1] - 1
-    stream, default = _cuda_stream(x0)
-    if default:
-        stream.synchronize()
-    _install_weights(engine, weights, stream)
-    force = torch.empty((B, N + 1, 3), dtype=torch.float32, device=x0.device)
-    engine.downwash_multi_device(od, other_index, xr, force, ego_xy=ego_xy, stream=stream)
-    tape, u0, X, U = _taped_step(engine, stream, default, x0, xr, ur, f=force)
-    tz = _network_tz_multi(t_other, txr, other_index)
-    tw = None if t_w is None else t_w.to(torch.float32).contiguous()
-    tf = None
-    if tz is not None or tw is not None:
-        tf = torch.empty((B, T, N + 1, 3), dtype=torch.float64, device=x0.device)
-        engine.downwash_multi_jvp_device(od, other_index, xr, tz=tz, tw=tw, ego_xy=ego_xy, n_tan=T, df=tf, stream=stream)
-    du0, dX, dU = (torch.empty((B, T) + s, dtype=torch.float64, device=x0.device) for s in ((4,), (N + 1, 10), (N, 4)))
-    engine.step_jvp_device(x0, xr, ur, tape, tx0, txr, tur, tf, f=force, du0=du0, dX=dX, dU=dU, stream=stream)
-    if default:
-        engine.synchronize()
-    if not had:
-        du0, dX, dU = du0[:, 0], dX[:, 0], dU[:, 0]
-    return u0, X, U, du0, dX, dU
+    return _ndp_step_jvp(_MULTI, "control_step_ndp_multi_jvp", engine, x0, xr, ur, other, other_index, tangents, ego_xy, weights)
 
 
 # ---------------------------------------------------------------------------------------------- the controller's own numbers, differentiated
@@ -765,8 +745,7 @@ class TunableControlStepFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, engine, xr, ur, Qd, Rd, mass=None, f=None):
-        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t  # noqa: E731
-        x0, xr, ur, fd = det(x0), det(xr), det(ur), det(f)
+        x0, xr, ur, fd = _det(x0), _det(xr), _det(ur), _det(f)
         ctx.model = _install_model(engine, Qd, Rd, mass)
         tape, u0, X, U = _taped_step(engine, *_cuda_stream(x0), x0, xr, ur, f=fd)
         ctx.engine = engine
@@ -862,8 +841,8 @@ class DownwashAdamSN(torch.optim.Optimizer):
             raise ValueError(f"DownwashAdamSN: eps = {eps} must be positive")
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, sn=float(sn), install=bool(install)))
         ps = [p for g in self.param_groups for p in g["params"]]
-        if len(ps) != 1 or ps[0].numel() != 17859 or ps[0].dim() != 1 or ps[0].dtype != torch.float32 or not ps[0].is_contiguous():
-            raise ValueError("DownwashAdamSN: expected ONE contiguous float32 parameter of 17859 values (the network's blob)")
+        if len(ps) != 1 or ps[0].numel() != _lib.MLP_NPARAM or ps[0].dim() != 1 or ps[0].dtype != torch.float32 or not ps[0].is_contiguous():
+            raise ValueError(f"DownwashAdamSN: expected ONE contiguous float32 parameter of {_lib.MLP_NPARAM} values (the network's blob)")
         self.engine = engine
 
     def _state_of(self, p):
@@ -922,10 +901,7 @@ def downwash_rows(engine, z, weights=None, index=None):
     installed first as downwash does it.  NO autograd: the result carries no graph, whatever requires grad -- this is for evaluation sets
     and the reference's force-field grids; fit through downwash_fit_rows."""
     zd = z.detach()
-    stream, default = _cuda_stream(zd)
-    if default:
-        stream.synchronize()
-    _install_weights(engine, weights, stream)
+    stream, default, _ = _enter(engine, zd, weights)
     f = torch.empty((zd.shape[0] if index is None else index.shape[0], 3), dtype=torch.float32, device=zd.device)
     engine.mlp_rows_device(zd, f, index=index, stream=stream)
     if default:
@@ -939,12 +915,9 @@ class DownwashFitRowsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, weights, engine, z, y, index, row_weight, scale, groups, info):
-        stream, default = _cuda_stream(z)
-        if default:
-            stream.synchronize()
-        _install_weights(engine, weights, stream)
+        stream, default, _ = _enter(engine, z, weights)
         loss = torch.empty(1, dtype=torch.float64, device=z.device)
-        gw = torch.empty(17859, dtype=torch.float32, device=z.device) if ctx.needs_input_grad[0] else None
+        gw = torch.empty(_lib.MLP_NPARAM, dtype=torch.float32, device=z.device) if ctx.needs_input_grad[0] else None
         engine.mlp_fit_rows_device(z, y, scale, index=index, row_weight=row_weight, groups=groups, loss=loss, gw=gw, info=info, stream=stream)
         if default:
             engine.synchronize()
@@ -982,9 +955,7 @@ class PlantRolloutFunction(torch.autograd.Function):
     def forward(ctx, x0, engine, u, f, dt, substeps):
         x0d, ud = x0.detach().contiguous(), u.detach().contiguous()
         fd = None if f is None else f.detach().contiguous()
-        stream, default = _cuda_stream(x0d)
-        if default:
-            stream.synchronize()
+        stream, default, _ = _enter(engine, x0d)
         xs = torch.empty((ud.shape[0], ud.shape[1], 10), dtype=torch.float64, device=x0d.device)
         engine.plant_rollout_device(x0d, ud, xs, f=fd, dt=dt, substeps=substeps, stream=stream)
         if default:
@@ -1003,9 +974,7 @@ class PlantRolloutFunction(torch.autograd.Function):
         K, B = ud.shape[0], ud.shape[1]
         gx0, gu, gf = (torch.empty(s, dtype=torch.float64, device=x0d.device) if n else None
                        for n, s in zip(need, ((B, 10), (K, B, 4), (K, B, 3))))
-        stream, default = _cuda_stream(x0d)
-        if default:
-            stream.synchronize()
+        stream, default, _ = _enter(ctx.engine, x0d)
         ctx.engine.plant_rollout_vjp_device(x0d, ud, xs, g_xs.to(torch.float64).contiguous(), f=fd, gx0=gx0, gu=gu, gf=gf, dt=ctx.dt,
                                             substeps=ctx.substeps, stream=stream)
         if default:
@@ -1053,9 +1022,7 @@ def plant_rollout_jvp(engine, x0, u, tangents, f=None, dt=CP.ts_nmpc, substeps=4
     if len(Ts) > 1:
         raise ValueError(f"plant_rollout_jvp: the tangents disagree on the number of directions ({sorted(Ts)})")
     T, (K, B) = Ts.pop(), ud.shape[:2]
-    stream, default = _cuda_stream(x0d)
-    if default:
-        stream.synchronize()
+    stream, default, _ = _enter(engine, x0d)
     xs = torch.empty((K, B, 10), dtype=torch.float64, device=x0d.device)
     dxs = torch.empty((K, B, T, 10), dtype=torch.float64, device=x0d.device)
     engine.plant_rollout_jvp_device(x0d, ud, dxs, f=fd, tx0=ts[0], tu=ts[1], tf=ts[2], n_tan=T, xs_check=xs, dt=dt, substeps=substeps,
@@ -1073,14 +1040,11 @@ class ClosedLoopFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, engine, xr, ur, f, fp, Qd, Rd, mass, dt, substeps):
-        det = lambda t: t.detach().contiguous() if isinstance(t, torch.Tensor) else t  # noqa: E731
-        x0, xr, ur, fd, fpd = det(x0), det(xr), det(ur), det(f), det(fp)
+        x0, xr, ur, fd, fpd = _det(x0), _det(xr), _det(ur), _det(f), _det(fp)
         ctx.model = _install_model(engine, Qd, Rd, mass)
         ctx.set_materialize_grads(False)       # (an output the loss does not use arrives as None: the call's NULL upstream)
         K, B, N = xr.shape[0], xr.shape[1], xr.shape[2] - 1
-        stream, default = _cuda_stream(x0)
-        if default:
-            stream.synchronize()
+        stream, default, _ = _enter(engine, x0)
         new = lambda *s: torch.empty(s, dtype=torch.float64, device=x0.device)  # noqa: E731
         xs, us, Xs, tape = new(K, B, 10), new(K, B, 4), new(K, B, N + 1, 10), engine.closed_loop_tape(K)
         engine.closed_loop_device(x0, xr, ur, xs, us, f=fd, fp=fpd, Xs=Xs, tape=tape, dt=dt, substeps=substeps, stream=stream)
@@ -1176,10 +1140,7 @@ class PlantForceFunction(torch.autograd.Function):
     def forward(ctx, x, engine, other_index, gate, scale, weights=None):
         xd = x.detach().contiguous()
         idx = _plant_index(other_index, "PlantForceFunction")
-        stream, default = _cuda_stream(xd)
-        if default:
-            stream.synchronize()
-        ctx.key = _install_weights(engine, weights, stream)
+        stream, default, ctx.key = _enter(engine, xd, weights)
         f = torch.empty((xd.shape[0], 3), dtype=torch.float64, device=xd.device)
         if idx is None:
             f.zero_()
@@ -1199,18 +1160,16 @@ class PlantForceFunction(torch.autograd.Function):
         want_w = ctx.have_w and need[5]
         if not ctx.have_idx:          # nobody has a neighbour: the force is the constant 0
             return (torch.zeros_like(xd) if need[0] else None, None, None, None, None,
-                    torch.zeros(17859, dtype=torch.float32, device=xd.device) if want_w else None)
+                    torch.zeros(_lib.MLP_NPARAM, dtype=torch.float32, device=xd.device) if want_w else None)
         idx = rest[0]
         eng = ctx.engine
         _check_installed(eng, ctx.key, "PlantForceFunction")
         B, K = idx.shape
         gz = torch.empty((B, K, 6), dtype=torch.float64, device=xd.device) if need[0] else None
-        gw = torch.empty(17859, dtype=torch.float32, device=xd.device) if want_w else None
+        gw = torch.empty(_lib.MLP_NPARAM, dtype=torch.float32, device=xd.device) if want_w else None
         if gz is None and gw is None:
             return (None,) * 6
-        stream, default = _cuda_stream(xd)
-        if default:
-            stream.synchronize()
+        stream, default, _ = _enter(eng, xd)
         eng.plant_force_multi_vjp_device(xd, idx, g_f.to(torch.float64).contiguous(), gz=gz, gw=gw, gate=ctx.gate, scale=ctx.scale,
                                          stream=stream)
         if default:
@@ -1239,13 +1198,9 @@ def plant_force_jvp(engine, x, other_index, tangents, gate=True, scale=1.0, weig
     xd = x.detach().contiguous()
     idx = _plant_index(other_index, "plant_force_jvp")
     (tx, tw), T, had = _with_t_axis(tangents, (2, 1), "plant_force_jvp")
-    stream, default = _cuda_stream(xd)
-    if default:
-        stream.synchronize()
-    _install_weights(engine, weights, stream)
+    stream, default, _ = _enter(engine, xd, weights)
     B = xd.shape[0]
-    tx = None if tx is None else tx.to(torch.float64).contiguous()
-    tw = None if tw is None else tw.to(torch.float32).contiguous()
+    tx, tw = _cast(tx, torch.float64), _cast(tw, torch.float32)
     f = torch.empty((B, 3), dtype=torch.float64, device=xd.device)
     df = torch.empty((B, T, 3), dtype=torch.float64, device=xd.device)
     engine.plant_force_multi_jvp_device(xd, idx, tx=tx, tw=tw, n_tan=T, df=df, f_check=f, gate=gate, scale=scale, stream=stream)
