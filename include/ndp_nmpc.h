@@ -675,6 +675,42 @@ int ndp_closed_loop_vjp_device(ndp_handle *h, int ticks, double dt, int substeps
                                const void *d_f, const void *d_fp, const void *d_xs, const void *d_us, const void *d_tape, const void *d_gxs,
                                const void *d_gus, const void *d_gXs, void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_gfp,
                                void *d_gmodel, void *d_status_check, void *stream);
+/* ndp_closed_loop_jvp_device: forward mode of that flight, T = n_tan directions (1..NDP_JVP_MAX_TANGENTS) in one call -- the same PARTIAL
+ * derivative: each tick's linearisation point (its tape slot) and final active set are held fixed.  Inputs as the forward took them, its
+ * d_xs, d_us and d_tape (required).  Directions, fp64, each NULL = 0, not all five NULL:
+ *   d_tx0 [B][T][10]; d_txr [ticks][B][T][N+1][10]; d_tur [ticks][B][T][N][4]; d_tf [ticks][B][T][N+1][3] (needs use_fd = 1; fp64 although
+ *   d_f is fp32, as ndp_step_jvp_device takes it); d_tfp [ticks][B][T][3]
+ * Outputs, fp64, OVERWRITTEN:
+ *   d_dxs [ticks][B][T][10], required: the first-order change of x_{k+1};  d_dus [ticks][B][T][4], required: that of u0_k
+ *   d_dXs [ticks][B][T][N+1][10], d_dUs [ticks][B][T][N][4], optional: those of the step's predicted states and inputs
+ *   d_status_check int32 [ticks][B], optional: the recomputed status words
+ * Nothing is repacked: dxs[k-1] is tick k's d_tx0 as ndp_step_jvp_device reads it, dus[k] is what that step writes as du0, and both are
+ * the rows of the plant's tangent.  Tick by tick from the first, two launches each and one in front of tick 0 (tape slot 0 into the
+ * workspace), everything on `stream`, nothing synchronised:
+ *   (dus[k], dXs[k], dUs[k]) = the step's forward mode on tape slot k at x_k along (d_tx0 or dxs[k-1], txr[k], tur[k], tf[k])
+ *   dxs[k] = the plant tick's tangent at (x_k, u0_k, fp_k) along (d_tx0 or dxs[k-1], dus[k], tfp[k])   (ndp_plant_rollout_jvp_device's
+ *   arithmetic, one lane per (vehicle, direction), the lane recomputes the tick's primal); the same launch copies tape slot k + 1.
+ * Tick 0's step is launched also when it receives no direction (only d_tfp given): its forward mode on four NULLs writes the zeros -- or a
+ * failed vehicle's NaNs -- and the tick's status word.
+ * The engine's iterate, kept sets, sensitivity buffers and the tape are never written.  The workspace is the handle's, shared with the
+ * adjoint calls: calls on one handle are ordered.  Two calls are bit-identical; T directions in one call equal T one-direction calls bit for
+ * bit; an output does not depend on which optional outputs are asked for.  dUs[k][.][.][0] is dus[k], bit for bit, and each step's outputs
+ * are ndp_step_jvp_device's on the same slot and directions, bit for bit; dxs agrees with ndp_plant_rollout_jvp_device(ticks = 1) to
+ * rounding (the plant's tangent may round differently in the last place from one kernel to the next).
+ * A nonzero recomputed status in tick k of vehicle v gives NaN in v's rows of dxs and dus of every tick >= k, in every direction, and in its
+ * dXs / dUs of tick k; its earlier ticks and every other vehicle are unaffected, bit for bit.  At a later tick whose own status is 0 the
+ * step's forward mode runs on a NaN tx0: its dXs are NaN (stage 0 is tx0 as given, and every later stage inherits it through the
+ * dynamics), its dUs are NaN in the free rows and exactly 0 in the rows its final set pins (the step writes a pinned row as 0 without
+ * reading the sweep); the link makes dus[k] NaN either way.
+ * Duality: <G, dxs> + <H, dus> + <A, dXs> = <gx0, tx0> + <gxr, txr> + <gur, tur> + <gf, tf> + <gfp, tfp> against
+ * ndp_closed_loop_vjp_device's gradients for the upstreams G, H, A on the same record, to rounding.
+ *   -1: NULL handle, d_x0, d_xr, d_ur, d_xs or d_us.  -2 with the call's name and a reason in ndp_last_error, nothing enqueued and no buffer
+ *   touched: the forward's refusals, the derivative's own (n_rti != 1, qp_precision != 0, N >= 28), d_tape NULL, n_tan out of range, no
+ *   direction given, d_tf or d_f without use_fd, d_dxs or d_dus NULL. */
+int ndp_closed_loop_jvp_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_xr, const void *d_ur,
+                               const void *d_f, const void *d_fp, const void *d_xs, const void *d_us, const void *d_tape, int n_tan,
+                               const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf, const void *d_tfp, void *d_dxs,
+                               void *d_dus, void *d_dXs, void *d_dUs, void *d_status_check, void *stream);
 
 /* ---- f4, the formation form (plant = a1 dynamics + downwash model): the downwash force the neighbour's ACTUAL state
  * puts on the ACTUAL vehicle, and the closed loop around it -- the experiment the downwash prediction is for (the reference has no

@@ -70,7 +70,7 @@ EXPORTS = [
     "ndp_mlp_rows_device", "ndp_mlp_fit_rows_device",
     "ndp_plant_rollout_device", "ndp_plant_rollout_vjp_device", "ndp_plant_rollout_jvp_device",
     "ndp_plant_force_vjp_device", "ndp_plant_force_multi_vjp_device", "ndp_plant_force_jvp_device", "ndp_plant_force_multi_jvp_device",
-    "ndp_closed_loop_tape_bytes", "ndp_closed_loop_device", "ndp_closed_loop_vjp_device",
+    "ndp_closed_loop_tape_bytes", "ndp_closed_loop_device", "ndp_closed_loop_vjp_device", "ndp_closed_loop_jvp_device",
 ]
 
 _lib = None
@@ -243,6 +243,7 @@ def load():
     lib.ndp_closed_loop_tape_bytes.argtypes = [vp, C.c_int, C.POINTER(C.c_size_t)]
     lib.ndp_closed_loop_device.argtypes = [vp, C.c_int, C.c_double, C.c_int] + [vp] * 11
     lib.ndp_closed_loop_vjp_device.argtypes = [vp, C.c_int, C.c_double, C.c_int] + [vp] * 19
+    lib.ndp_closed_loop_jvp_device.argtypes = [vp, C.c_int, C.c_double, C.c_int] + [vp] * 8 + [C.c_int] + [vp] * 11
     _lib = lib
     return lib
 

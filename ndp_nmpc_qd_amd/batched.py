@@ -539,6 +539,33 @@ class BatchedNMPC:
             d(gf, torch.float64, (K, B, N + 1, 3)), d(gfp, torch.float64, (K, B, 3)), d(gmodel, torch.float64, (B, 16)),
             d(status_check, torch.int32, (K, B)), self._stream(stream)), "ndp_closed_loop_vjp_device")
 
+    def closed_loop_jvp_device(self, x0, xr, ur, xs, us, tape, dxs, dus, f=None, fp=None, tx0=None, txr=None, tur=None, tf=None, tfp=None,
+                               dXs=None, dUs=None, status_check=None, n_tan=None, dt=CP.ts_nmpc, substeps=4, stream=None):
+        """Enqueues the forward mode of closed_loop_device on `stream` (ndp_closed_loop_jvp_device; include/ndp_nmpc.h): the inputs as the
+        forward took them, its xs, us and tape.  Directions (None = 0, not all None), float64: tx0[B,T,10], txr[ticks,B,T,N+1,10],
+        tur[ticks,B,T,N,4], tf[ticks,B,T,N+1,3], tfp[ticks,B,T,3].  Outputs the caller allocates, float64, overwritten: dxs[ticks,B,T,10]
+        and dus[ticks,B,T,4], required -- the first-order change of x_{k+1} and of u0_k; dXs[ticks,B,T,N+1,10], dUs[ticks,B,T,N,4] and
+        status_check[ticks,B] int32, optional.  T (1..8) is n_tan when given, else read from dxs.  Every tick's linearisation point and
+        final set are held fixed.  Nothing of the engine's state or the tape is written; T directions in one call equal T calls bit for
+        bit.  stream None or torch's default: the engine's own stream behind a wait for torch's; read the outputs after
+        engine.synchronize()."""
+        import torch
+        K, args = self._closed_loop_args("closed_loop_jvp_device", x0, xr, ur, f, fp)
+        if n_tan is None:
+            if not (isinstance(dxs, torch.Tensor) and dxs.dim() == 4):
+                raise ValueError("closed_loop_jvp_device: dxs must be a [ticks,B,T,10] tensor")
+            n_tan = dxs.shape[2]
+        B, N, T, d = self.B, self.N, int(n_tan), self._dptr
+        self._torch_default_wait(stream)
+        self._check(self._lib.ndp_closed_loop_jvp_device(
+            self._h, K, float(dt), int(substeps), *args, d(xs, torch.float64, (K, B, 10)), d(us, torch.float64, (K, B, 4)),
+            d(tape, torch.uint8, (K, self._closed_loop_slot_bytes())), T,
+            d(tx0, torch.float64, (B, T, 10)), d(txr, torch.float64, (K, B, T, N + 1, 10)), d(tur, torch.float64, (K, B, T, N, 4)),
+            d(tf, torch.float64, (K, B, T, N + 1, 3)), d(tfp, torch.float64, (K, B, T, 3)),
+            d(dxs, torch.float64, (K, B, T, 10)), d(dus, torch.float64, (K, B, T, 4)), d(dXs, torch.float64, (K, B, T, N + 1, 10)),
+            d(dUs, torch.float64, (K, B, T, N, 4)), d(status_check, torch.int32, (K, B)), self._stream(stream)),
+            "ndp_closed_loop_jvp_device")
+
     @staticmethod
     def _plant_ticks(u, who):
         import torch

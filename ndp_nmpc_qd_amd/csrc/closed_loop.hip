@@ -1,9 +1,10 @@
-// closed_loop.hip -- the closed loop over GIVEN reference windows and forces (the "ext" form), recorded, and its reverse mode, each as one
-// call: ndp_closed_loop_device (control step -> plant tick -> the next tick's x0, `ticks` times, everything enqueued on one stream) and
-// ndp_closed_loop_vjp_device (the gradient of a loss on that flight in x_0, the windows, the forces and the controller's own numbers).
+// closed_loop.hip -- the closed loop over GIVEN reference windows and forces (the "ext" form), recorded, and its two derivative modes, each as
+// one call: ndp_closed_loop_device (control step -> plant tick -> the next tick's x0, `ticks` times, everything enqueued on one stream),
+// ndp_closed_loop_vjp_device (the gradient of a loss on that flight in x_0, the windows, the forces and the controller's own numbers) and
+// ndp_closed_loop_jvp_device (the tangents of that flight along directions of x_0, the windows and the forces).
 //
-// The control step and its adjoint are the existing kernels, launched unchanged (enqueue_step; recompute_on_workspace with rti_vjp_kernel /
-// rti_wvjp_kernel).  What is new is everything BETWEEN two of them, one launch per tick and direction:
+// The control step and its derivatives are the existing kernels, launched unchanged (enqueue_step; recompute_on_workspace with rti_vjp_kernel
+// / rti_wvjp_kernel / rti_jvp_kernel).  What is new is everything BETWEEN two of them, one launch per tick and direction:
 //   closed_loop_fwd_link_kernel  behind step k: the plant tick (plant_tick: ndp_plant_step_device's bits) from x_k and u0_k into xs[k], the
 //                                status words into their log, and the engine's post-step iterate and kept set copied into tape slot k + 1
 //                                (and X into Xs[k]) in 16-byte pieces
@@ -13,6 +14,11 @@
 //                                workspace; a tail launch behind tick 0 forms gx0 = gx_p + gx0 and the last fold.  Each launch also sees
 //                                the status words tick k + 1's adjoint recomputed: where nonzero, gfp[k + 1] and the plant's mass share
 //                                become NaN (ClRev::st_prev)
+//   closed_loop_tan_link_kernel  behind the forward mode of step k: the plant tick's tangent (the arithmetic of plant_rollout_jvp_kernel's
+//                                tick body) at (x_k, u0_k, fp_k) along (dxs[k-1], dus[k], tfp[k]) into dxs[k], one lane per (vehicle,
+//                                direction), and tape slot k + 1 copied into the forward mode's workspace; a head launch copies slot 0.
+//                                The launch sees tick k's recomputed status words: where nonzero, or where the incoming tangent is NaN
+//                                (an earlier tick failed), dxs[k] and dus[k] become NaN (a pinned row of the step's du0 would stay 0)
 // One lane per vehicle in 64-lane workgroups for the plant (plant_deriv.hip's shape: a long serial fp64 chain per lane, spread over many
 // CUs); the copies run on further workgroups of the same launch, grid-stride.  No LDS, no atomics, no scratch.
 #include <hip/hip_runtime.h>
@@ -21,6 +27,7 @@
 #include "host.hpp"
 #include "plant_dyn.hpp"
 #include "plant_adj.hpp"
+#include "plant_tan.hpp"
 
 namespace ndp {
 
@@ -61,6 +68,17 @@ struct ClRev {
     double *gfp_prev;               // gfp[k + 1] (or null) and the plant's mass share become NaN -- the plant's adjoint alone would not
                                     // make them so at the vehicle's LAST failed tick (the force's gradient does not read the state)
     ClCopy cp[2];                   // tape slot k -> the adjoint's workspace: iterate, kept set
+};
+
+struct ClTan {
+    ClPlant p;                      // plant_blocks workgroups, one lane per (vehicle, direction): lane i = v T + t (B: the vehicles)
+    int T;
+    const double *xin, *u, *fp;     // x_k [B][10], u0_k [B][4], fp_k [B][3] or null
+    const double *tx, *tfp;         // the tangent of x_k [B][T][10] (d_tx0, then dxs[k-1]; null: 0) and of fp_k [B][T][3] (null: 0)
+    double *du;                     // dus[k] [B][T][4]: the step's du0 as rti_jvp_kernel left it, read; NaN written where the tick failed
+    double *dx;                     // out: dxs[k] [B][T][10]
+    const int *st;                  // tick k's recomputed status words (its forward mode has run)
+    ClCopy cp[2];                   // tape slot k + 1 -> the forward mode's workspace: iterate, kept set
 };
 
 __device__ __forceinline__ void cl_copy(const ClCopy &c, size_t i0, size_t stride)
@@ -173,6 +191,55 @@ __global__ __launch_bounds__(CL_LANES) void closed_loop_rev_link_kernel(ClRev a)
         }
         plant_st_row<8>(a.gm_tot + (size_t)v * 16, tot);
     }
+}
+
+// The plant tick's tangent, plant_rollout_jvp_kernel's tick body: a lane carries the vehicle's primal (recomputed from x_k) and ONE tangent,
+// so its arithmetic does not know T.  failed: the tick's status word is nonzero, or the incoming tangent holds a NaN (an earlier tick of
+// this vehicle failed) -- then the lane's rows of dxs[k] and dus[k] are NaN, whatever the step's forward mode left in a pinned row.
+__global__ __launch_bounds__(CL_LANES) void closed_loop_tan_link_kernel(ClTan a)
+{
+    if ((int)blockIdx.x >= a.p.plant_blocks) {
+        const size_t i0 = (size_t)((int)blockIdx.x - a.p.plant_blocks) * CL_LANES + threadIdx.x;
+        const size_t stride = (size_t)((int)gridDim.x - a.p.plant_blocks) * CL_LANES;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) cl_copy(a.cp[j], i0, stride);
+        return;
+    }
+    const size_t lanes = (size_t)a.p.B * a.T, i = (size_t)blockIdx.x * CL_LANES + threadIdx.x;
+    if (i >= lanes) return;
+    const size_t v = i / (size_t)a.T;
+    double xv[10], y[10], dx[10], uv[4], du[4], acc[3], dacc[3] = {0.0, 0.0, 0.0};
+    plant_ld_row<5>(a.xin + v * 10, xv);
+    plant_ld_row<2>(a.u + v * 4, uv);
+    plant_ld_row<2>(a.du + i * 4, du);
+#pragma unroll
+    for (int j = 0; j < 10; ++j) dx[j] = 0.0;
+    if (a.tx) plant_ld_row<5>(a.tx + i * 10, dx);
+    bool failed = a.st[v] != 0;
+#pragma unroll
+    for (int j = 0; j < 10; ++j) failed = failed || dx[j] != dx[j];
+    if (a.tfp) { dacc[0] = a.tfp[i * 3] * a.p.inv_mass; dacc[1] = a.tfp[i * 3 + 1] * a.p.inv_mass; dacc[2] = a.tfp[i * 3 + 2] * a.p.inv_mass; }
+    plant_acc(a.fp, v * 3, a.p.inv_mass, a.p.g, acc);
+#pragma unroll
+    for (int j = 0; j < 10; ++j) y[j] = xv[j];
+    for (int s = 0; s < a.p.sub; ++s) {
+        plant_rk4_jvp(y, uv, acc, a.p.h, dx, du, dacc);
+        plant_rk4(y, uv, acc, a.p.h);
+    }
+    plant_tick(xv, uv, a.fp, v * 3, a.p.h, a.p.sub, a.p.inv_mass, a.p.g);      // (y renormalised is xv: the same operations)
+    const double n = sqrt(y[6] * y[6] + y[7] * y[7] + y[8] * y[8] + y[9] * y[9]);
+    const double d = xv[6] * dx[6] + xv[7] * dx[7] + xv[8] * dx[8] + xv[9] * dx[9];
+#pragma unroll
+    for (int j = 6; j < 10; ++j) dx[j] = (dx[j] - xv[j] * d) / n;
+    if (failed) {
+        const double nan = __builtin_nan("");
+#pragma unroll
+        for (int j = 0; j < 10; ++j) dx[j] = nan;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) du[j] = nan;
+        plant_st_row<2>(a.du + i * 4, du);
+    }
+    plant_st_row<5>(a.dx + i * 10, dx);
 }
 
 }  // namespace ndp
@@ -328,6 +395,72 @@ int ndp_closed_loop_vjp_device(ndp_handle *h, int ticks, double dt, int substeps
         a.gm_tot = (double *)d_gmodel; a.gm_row = ws_gm;
         a.st_prev = st_of(0); a.gfp_prev = (double *)d_gfp;
         hipLaunchKernelGGL(closed_loop_rev_link_kernel, dim3((unsigned)a.p.plant_blocks), dim3(CL_LANES), 0, s, a);
+        NDP_HIP(h, hipGetLastError());
+    }
+    return g.noted(0);
+}
+
+int ndp_closed_loop_jvp_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_xr, const void *d_ur,
+                               const void *d_f, const void *d_fp, const void *d_xs, const void *d_us, const void *d_tape, int n_tan,
+                               const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf, const void *d_tfp, void *d_dxs,
+                               void *d_dus, void *d_dXs, void *d_dUs, void *d_status_check, void *stream)
+{
+    const char *who = "ndp_closed_loop_jvp_device";
+    Entry g(h, d_x0 && d_xr && d_ur && d_xs && d_us, stream);
+    if (g.rc) return g.rc;
+    int rc = cl_check(h, who, ticks, substeps, d_f);
+    if (rc) return rc;
+    const char *own = nullptr;
+    if (!d_tape) own = "d_tape is required (the forward's, recorded by ndp_closed_loop_device)";
+    else if (n_tan < 1 || n_tan > NDP_JVP_MAX_TANGENTS) own = "n_tan must be 1..8 (directions per call)";
+    else if (!d_tx0 && !d_txr && !d_tur && !d_tf && !d_tfp) own = "no tangent given (d_tx0, d_txr, d_tur, d_tf and d_tfp all NULL)";
+    else if (d_tf && !h->cfg.use_fd) own = "a force tangent (d_tf) needs use_fd = 1 (NDP model)";
+    else if (!d_dxs || !d_dus) own = "d_dxs and d_dus are required (the tangents of the two logs)";
+    const std::string why = recompute_refusal(h->cfg, "derivative", Tape{d_x0, d_xr, d_ur, d_f, d_tape ? d_tape : d_x0, d_tape ? d_tape : d_x0,
+                                                                             nullptr, nullptr, nullptr}, own);
+    if (!why.empty()) { h->err = std::string(who) + ": " + why; return -2; }
+    hipStream_t s = g.s;
+    const size_t B = h->cfg.batch, T = (size_t)n_tan, slot = cl_slot_bytes(h), itb = cl_iterate_bytes(h), ab = act_bytes(h);
+    if ((rc = recompute_workspace(h))) return rc;
+    const unsigned char *tape = (const unsigned char *)d_tape;
+    const unsigned cb = cl_copy_blocks(itb + ab), pb = (unsigned)((B * T + CL_LANES - 1) / CL_LANES);
+    auto slot_into_workspace = [&](ClTan &a, int k) {
+        a.cp[0] = ClCopy{tape + (size_t)k * slot, (unsigned char *)h->dVjp, itb};
+        a.cp[1] = ClCopy{tape + (size_t)k * slot + itb, (unsigned char *)h->dVjpAct, ab};
+    };
+    {                              // the head: slot 0 into the workspace
+        ClTan a{};
+        a.p = cl_plant(h, dt, substeps, false);
+        slot_into_workspace(a, 0);
+        hipLaunchKernelGGL(closed_loop_tan_link_kernel, dim3(cb), dim3(CL_LANES), 0, s, a);
+        NDP_HIP(h, hipGetLastError());
+    }
+    double *dxs = (double *)d_dxs, *dus = (double *)d_dus;
+    for (int k = 0; k < ticks; ++k) {
+        const double *xk = k ? (const double *)d_xs + (size_t)(k - 1) * B * NX : (const double *)d_x0;
+        const double *tx = k ? dxs + (size_t)(k - 1) * B * T * NX : (const double *)d_tx0;
+        double *du = dus + (size_t)k * B * T * NU;
+        int *st = d_status_check ? (int *)d_status_check + (size_t)k * B : nullptr;
+        // (tick 0 with no direction of the step's -- only d_tfp given -- is launched like every other: it recomputes the tick's status word,
+        // and jvp_out with all four NULL writes the zeros, or the NaNs of a failed vehicle, that this tick's link reads)
+        const Tape t{xk, (const double *)d_xr + (size_t)k * nxs(h), (const double *)d_ur + (size_t)k * nus(h),
+                     d_f ? (const float *)d_f + (size_t)k * nfs(h) : nullptr, nullptr, nullptr, nullptr, nullptr, st};
+        JvpArgs ja{tx, d_txr ? (const double *)d_txr + (size_t)k * T * nxs(h) : nullptr,
+                   d_tur ? (const double *)d_tur + (size_t)k * T * nus(h) : nullptr, d_tf ? (const double *)d_tf + (size_t)k * T * nfs(h) : nullptr,
+                   du, d_dXs ? (double *)d_dXs + (size_t)k * T * nxs(h) : nullptr, d_dUs ? (double *)d_dUs + (size_t)k * T * nus(h) : nullptr,
+                   n_tan};
+        if ((rc = recompute_on_workspace(h, s, t, recompute_kernel(RC_JVP, true), recompute_kernel(RC_JVP, false), &ja, nullptr))) return rc;
+        ClTan a{};
+        a.p = cl_plant(h, dt, substeps, true);
+        a.p.plant_blocks = (int)pb;
+        a.T = n_tan;
+        a.xin = xk; a.u = (const double *)d_us + (size_t)k * B * NU; a.fp = d_fp ? (const double *)d_fp + (size_t)k * B * 3 : nullptr;
+        a.tx = tx; a.tfp = d_tfp ? (const double *)d_tfp + (size_t)k * B * T * 3 : nullptr;
+        a.du = du; a.dx = dxs + (size_t)k * B * T * NX;
+        a.st = st ? st : h->dVjpSt;
+        const bool more = k + 1 < ticks;
+        if (more) slot_into_workspace(a, k + 1);
+        hipLaunchKernelGGL(closed_loop_tan_link_kernel, dim3(pb + (more ? cb : 0u)), dim3(CL_LANES), 0, s, a);
         NDP_HIP(h, hipGetLastError());
     }
     return g.noted(0);

@@ -23,11 +23,12 @@
 //   plant_force_deriv.hip  the derivatives of the downwash force on the plant (ndp_plant_force_vjp_device, ndp_plant_force_jvp_device and
 //                    their multi forms); hosts mlp_vjp.hip's backward pass (mlp_vjp_dev.hpp, mlp_vjp_back.inc, mlp_vjp_part.inc) and
 //                    mlp_jvp.hip's direction (mlp_jvp_dev.hpp, mlp_jvp_direction.inc) behind a row loader of its own
-//   closed_loop.hip  the closed loop over given windows in one call per direction (ndp_closed_loop_device, ndp_closed_loop_vjp_device): the
-//                    step and its adjoint are the existing kernels, launched unchanged; the two link kernels between them live here
+//   closed_loop.hip  the closed loop over given windows in one call per direction (ndp_closed_loop_device, ndp_closed_loop_vjp_device,
+//                    ndp_closed_loop_jvp_device): the step, its adjoint and its forward mode are the existing kernels, launched unchanged;
+//                    the three link kernels between them live here
 //   exchange.hip     peer-mapped windows (ndp_peer_*), the RCCL exchange (ndp_xchg_*) and the remote tick one control period ahead
 // A kernel sits with the host code that launches it; device code that two units' kernels inline is a header (mlp_tile.hpp, ref_point.hpp,
-// tick_wave.hpp, mlp_vjp_dev.hpp, mlp_jvp_dev.hpp, plant_dyn.hpp, plant_adj.hpp), and so are the argument blocks the host fills (kern_args.hpp).
+// tick_wave.hpp, mlp_vjp_dev.hpp, mlp_jvp_dev.hpp, plant_dyn.hpp, plant_adj.hpp, plant_tan.hpp), and so are the argument blocks the host fills (kern_args.hpp).
 // The functions declared below are NDP_HIDDEN: the library exports the C-ABI of include/ndp_nmpc.h and nothing more.
 #pragma once
 #include <hip/hip_runtime.h>

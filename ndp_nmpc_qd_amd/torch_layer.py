@@ -50,6 +50,9 @@ Functions: u0 -> plant_step -> the next tick's x0, with the values ndp_plant_ste
 closed_loop (behind plant_rollout_jvp) is the whole closed loop over given windows as ONE autograd Function: control step -> plant tick -> the
 next tick's x0, `ticks` times in one call (BatchedNMPC.closed_loop_device), and one call back (closed_loop_vjp_device) for the gradients of
 x_0, the windows, both forces, Qd, Rd and the mass -- what the chain control_step_trajectory -> plant_step gives link by link.
+closed_loop_jvp (behind it) is the same flight with its forward mode: that one call forward with a tape, then one call
+(closed_loop_jvp_device) for the tangents of x_{k+1}, u0_k and X_k along T directions of x_0, the windows and both forces -- what the chain
+control_step_jvp -> plant_rollout_jvp(ticks = 1) gives tick by tick.  No autograd hookup.
 
 plant_force / plant_force_jvp (at the end of this file) are the downwash force the neighbours' actual states put on the plant, differentiable
 in the states and the network's weights (BatchedNMPC.plant_force_multi_device, plant_force_multi_vjp_device, plant_force_multi_jvp_device):
@@ -1100,6 +1103,45 @@ def closed_loop(engine, x0, xr, ur, f=None, fp=None, Qd=None, Rd=None, mass=None
     Qd [10], Rd [4] and the mass (its gradient: the controller's share plus the plant's); the backward is ONE call, with every tick's
     linearisation point and final active set held fixed as in every derivative here.  Gravity is not differentiated."""
     return ClosedLoopFunction.apply(x0, engine, xr, ur, f, fp, Qd, Rd, mass, float(dt), int(substeps))
+
+
+def closed_loop_jvp(engine, x0, xr, ur, tangents, f=None, fp=None, dt=CP.ts_nmpc, substeps=4):
+    """(xs, us, Xs, dxs, dus, dXs): closed_loop's values and their first-order change along tangents = (tx0, txr, tur, tf, tfp) (forward
+    mode: ONE BatchedNMPC.closed_loop_device call with a tape, then ONE BatchedNMPC.closed_loop_jvp_device call).  tx0 [B,T,10], txr
+    [ticks,B,T,N+1,10], tur [ticks,B,T,N,4], tf [ticks,B,T,N+1,3] (the direction of the force the controller sees, float64; it needs a
+    use_fd engine), tfp [ticks,B,T,3]; each may be None (= 0, not all five) and each may come without the T axis -- then dxs [ticks,B,10],
+    dus [ticks,B,4] and dXs [ticks,B,N+1,10] come without it if none has it, else dxs [ticks,B,T,10], dus [ticks,B,T,4], dXs
+    [ticks,B,T,N+1,10].  T <= 8.  Every tick's linearisation point and final active set are held fixed, as in every derivative here.  No
+    autograd hookup.  Like closed_loop, every call advances the engine's iterate and kept sets."""
+    x0d, xrd, urd, fd, fpd = _det(x0), _det(xr), _det(ur), _det(f), _det(fp)
+    ts, Ts, had = [], set(), False
+    for t, n, axis in zip(tangents, (2, 4, 4, 4, 3), (1, 2, 2, 2, 2)):   # (dimensions without the T axis, and where it sits)
+        if t is not None:
+            t = t.detach().to(torch.float64)
+            if t.dim() == n:
+                t = t.unsqueeze(axis)
+            elif t.dim() == n + 1:
+                had = True
+            else:
+                raise ValueError(f"closed_loop_jvp: a tangent has {t.dim()} dimensions, expected {n} or {n + 1}")
+            Ts.add(int(t.shape[axis]))
+            t = t.contiguous()
+        ts.append(t)
+    if not Ts:
+        raise ValueError("closed_loop_jvp: no tangent (all None)")
+    if len(Ts) > 1:
+        raise ValueError(f"closed_loop_jvp: the tangents disagree on the number of directions ({sorted(Ts)})")
+    T, K, B, N = Ts.pop(), xrd.shape[0], xrd.shape[1], xrd.shape[2] - 1
+    stream, default, _ = _enter(engine, x0d)
+    new = lambda *s: torch.empty(s, dtype=torch.float64, device=x0d.device)  # noqa: E731
+    xs, us, Xs, tape = new(K, B, 10), new(K, B, 4), new(K, B, N + 1, 10), engine.closed_loop_tape(K)
+    dxs, dus, dXs = new(K, B, T, 10), new(K, B, T, 4), new(K, B, T, N + 1, 10)
+    engine.closed_loop_device(x0d, xrd, urd, xs, us, f=fd, fp=fpd, Xs=Xs, tape=tape, dt=dt, substeps=substeps, stream=stream)
+    engine.closed_loop_jvp_device(x0d, xrd, urd, xs, us, tape, dxs, dus, f=fd, fp=fpd, tx0=ts[0], txr=ts[1], tur=ts[2], tf=ts[3], tfp=ts[4],
+                                  dXs=dXs, n_tan=T, dt=dt, substeps=substeps, stream=stream)
+    if default:
+        engine.synchronize()
+    return (xs, us, Xs) + ((dxs, dus, dXs) if had else (dxs[:, :, 0], dus[:, :, 0], dXs[:, :, 0]))
 
 
 
