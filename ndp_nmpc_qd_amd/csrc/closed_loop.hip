@@ -21,6 +21,8 @@
 //                                (an earlier tick failed), dxs[k] and dus[k] become NaN (a pinned row of the step's du0 would stay 0)
 // One lane per vehicle in 64-lane workgroups for the plant (plant_deriv.hip's shape: a long serial fp64 chain per lane, spread over many
 // CUs); the copies run on further workgroups of the same launch, grid-stride.  No LDS, no atomics, no scratch.
+// Host side: ClView (tick k's slices, its tape slot, a link's two copies), cl_check (the refusals of all three calls, around plant_deriv.hip's
+// plant_seq_check), cl_deriv_begin (what the two derivative calls share before they enqueue); the three launch loops read top to bottom.
 #include <hip/hip_runtime.h>
 
 #include "../../include/ndp_nmpc.h"
@@ -253,7 +255,8 @@ static size_t cl_slot_bytes(const ndp_handle *h) { return up256(cl_iterate_bytes
 static ClPlant cl_plant(const ndp_handle *h, double dt, int substeps, bool plant)
 {
     const int B = h->cfg.batch;
-    return ClPlant{B, substeps, plant ? (B + CL_LANES - 1) / CL_LANES : 0, dt / substeps, 1.0 / h->cfg.mass, h->cfg.gravity};   // (as launch_plant, rows.hip)
+    const PlantNum n = plant_num(h, dt, substeps);
+    return ClPlant{B, substeps, plant ? (B + CL_LANES - 1) / CL_LANES : 0, n.h, n.inv_mass, n.g};
 }
 
 static unsigned cl_copy_blocks(size_t bytes)
@@ -263,17 +266,63 @@ static unsigned cl_copy_blocks(size_t bytes)
     return (unsigned)(n < 1 ? 1 : n > CL_MAX_COPY_BLOCKS ? CL_MAX_COPY_BLOCKS : n);
 }
 
-// the refusals the two calls share, nothing enqueued: -2 with the reason in ndp_last_error
+template <class T> static T *cl_at(T *p, int k, size_t n) { return p ? p + (size_t)k * n : nullptr; }      // tick k of n per tick; null stays null
+
+// A call's view of the flight, built once (host only): tick k's slices of the arrays all three entries take, and a link's two tape copies
+struct ClView {
+    const ndp_handle *h;
+    const double *x0, *xr, *ur;
+    const float *f;
+    const double *fp, *xs, *us;
+    unsigned char *tape;                     // (written by the forward only, where null means unrecorded)
+    size_t B, slot, itb, ab;                 // vehicles; the bytes of a tape slot, of its iterate, of its kept set
+    const double *x(int k) const { return k ? xs + (size_t)(k - 1) * B * NX : x0; }      // x_k: the call's x0, then the log's rows
+    const double *u0(int k) const { return cl_at(us, k, B * NU); }
+    const double *xrk(int k) const { return cl_at(xr, k, nxs(h)); }
+    const double *urk(int k) const { return cl_at(ur, k, nus(h)); }
+    const float *fk(int k) const { return cl_at(f, k, nfs(h)); }
+    const double *fpk(int k) const { return cl_at(fp, k, B * 3); }
+    // tick k's step as the recompute takes it (its tape is the workspace's copy), its status words to st (null: the workspace's)
+    Tape step(int k, int *st) const { return Tape{x(k), xrk(k), urk(k), fk(k), nullptr, nullptr, nullptr, nullptr, st}; }
+    void record(int k, ClCopy *cp) const     // the engine's pair into tape slot k (dU lies right behind dX)
+    {
+        cp[0] = ClCopy{(const unsigned char *)h->dX, tape + (size_t)k * slot, itb};
+        cp[1] = ClCopy{(const unsigned char *)h->dAct, tape + (size_t)k * slot + itb, ab};
+    }
+    void replay(int k, ClCopy *cp) const     // tape slot k into the workspace the derivative kernels recompute on
+    {
+        cp[0] = ClCopy{tape + (size_t)k * slot, (unsigned char *)h->dVjp, itb};
+        cp[1] = ClCopy{tape + (size_t)k * slot + itb, (unsigned char *)h->dVjpAct, ab};
+    }
+};
+static ClView cl_view(const ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f, const void *d_fp,
+                      const void *d_xs, const void *d_us, const void *d_tape)
+{
+    return ClView{h, (const double *)d_x0, (const double *)d_xr, (const double *)d_ur, (const float *)d_f, (const double *)d_fp, (const double *)d_xs,
+                  (const double *)d_us, (unsigned char *)d_tape, (size_t)h->cfg.batch, cl_slot_bytes(h), cl_iterate_bytes(h), act_bytes(h)};
+}
+
+// the refusals the three calls share, nothing enqueued: -2 with the reason in ndp_last_error
 static int cl_check(ndp_handle *h, const char *who, int ticks, int substeps, const void *d_f)
 {
     if (h->sens_level) return sens_refuse(h, who);
-    if (ticks < 1) { h->err = std::string(who) + ": ticks must be >= 1, got " + std::to_string(ticks); return -2; }
-    if (substeps < 1 || substeps > NDP_PLANT_MAX_SUBSTEPS) {
-        h->err = std::string(who) + ": substeps must be 1..16 (NDP_PLANT_MAX_SUBSTEPS), got " + std::to_string(substeps);
-        return -2;
-    }
+    int rc = plant_seq_check(h, who, ticks, substeps);
+    if (rc) return rc;
     if (d_f && !h->cfg.use_fd) { h->err = std::string(who) + ": a disturbance force (d_f) needs use_fd = 1 (NDP model)"; return -2; }
     return 0;
+}
+
+// What the two derivative calls do behind their frame and before they enqueue: cl_check, the recompute's refusals (noun: what it calls the
+// derivative) around the entry's own -- a missing tape in front of `own`, the entry's others -- and the recompute's workspace.
+static int cl_deriv_begin(ndp_handle *h, const char *who, const char *noun, int ticks, int substeps, const ClView &v, const char *own)
+{
+    int rc = cl_check(h, who, ticks, substeps, v.f);
+    if (rc) return rc;
+    if (!v.tape) own = "d_tape is required (the forward's, recorded by ndp_closed_loop_device)";
+    const void *lin = v.tape ? (const void *)v.tape : (const void *)v.x0;       // (a missing tape is refused by `own`, not as a missing iterate)
+    const std::string why = recompute_refusal(h->cfg, noun, Tape{v.x0, v.xr, v.ur, v.f, lin, lin, nullptr, nullptr, nullptr}, own);
+    if (!why.empty()) { h->err = std::string(who) + ": " + why; return -2; }
+    return recompute_workspace(h);
 }
 
 extern "C" {
@@ -295,35 +344,26 @@ int ndp_closed_loop_device(ndp_handle *h, int ticks, double dt, int substeps, co
     int rc = cl_check(h, "ndp_closed_loop_device", ticks, substeps, d_f);
     if (rc) return rc;
     hipStream_t s = g.s;
-    const size_t B = h->cfg.batch, slot = cl_slot_bytes(h), itb = cl_iterate_bytes(h), ab = act_bytes(h);
-    const unsigned char *eng_it = (const unsigned char *)h->dX, *eng_act = (const unsigned char *)h->dAct;    // (dU lies right behind dX)
-    unsigned char *tape = (unsigned char *)d_tape;
-    const unsigned cb = cl_copy_blocks(itb + ab + (d_Xs ? nxs(h) * 8 : 0));
-    if (tape) {                    // slot 0: what the first step starts from
+    const ClView v = cl_view(h, d_x0, d_xr, d_ur, d_f, d_fp, d_xs, d_us, d_tape);
+    const size_t B = v.B;
+    const unsigned cb = cl_copy_blocks(v.itb + v.ab + (d_Xs ? nxs(h) * 8 : 0));
+    if (v.tape) {                  // slot 0: what the first step starts from
         ClFwd a{};
         a.p = cl_plant(h, dt, substeps, false);
-        a.cp[0] = ClCopy{eng_it, tape, itb};
-        a.cp[1] = ClCopy{eng_act, tape + itb, ab};
+        v.record(0, a.cp);
         hipLaunchKernelGGL(closed_loop_fwd_link_kernel, dim3(cb), dim3(CL_LANES), 0, s, a);
         NDP_HIP(h, hipGetLastError());
     }
-    const double *xs = (const double *)d_xs;
     for (int k = 0; k < ticks; ++k) {
-        const double *xk = k ? xs + (size_t)(k - 1) * B * NX : (const double *)d_x0;
-        double *u0 = (double *)d_us + (size_t)k * B * NU;
-        rc = enqueue_step(h, xk, (const double *)d_xr + (size_t)k * nxs(h), (const double *)d_ur + (size_t)k * nus(h),
-                          d_f ? (const float *)d_f + (size_t)k * nfs(h) : nullptr, Neigh{}, u0, nullptr, s);
-        if (rc) return rc;
+        double *u0 = cl_at((double *)d_us, k, B * NU);
+        if ((rc = enqueue_step(h, v.x(k), v.xrk(k), v.urk(k), v.fk(k), Neigh{}, u0, nullptr, s))) return rc;
         ClFwd a{};
         a.p = cl_plant(h, dt, substeps, true);
-        a.xin = xk; a.u = u0; a.fp = d_fp ? (const double *)d_fp + (size_t)k * B * 3 : nullptr;
-        a.xout = (double *)d_xs + (size_t)k * B * NX;
-        a.st_src = h->lastStatus; a.st_dst = d_status ? (int *)d_status + (size_t)k * B : nullptr;
-        if (tape && k + 1 < ticks) {
-            a.cp[0] = ClCopy{eng_it, tape + (size_t)(k + 1) * slot, itb};
-            a.cp[1] = ClCopy{eng_act, tape + (size_t)(k + 1) * slot + itb, ab};
-        }
-        if (d_Xs) a.cp[2] = ClCopy{eng_it, (unsigned char *)d_Xs + (size_t)k * nxs(h) * 8, nxs(h) * 8};
+        a.xin = v.x(k); a.u = u0; a.fp = v.fpk(k);
+        a.xout = cl_at((double *)d_xs, k, B * NX);
+        a.st_src = h->lastStatus; a.st_dst = cl_at((int *)d_status, k, B);
+        if (v.tape && k + 1 < ticks) v.record(k + 1, a.cp);
+        if (d_Xs) a.cp[2] = ClCopy{(const unsigned char *)h->dX, (unsigned char *)d_Xs + (size_t)k * nxs(h) * 8, nxs(h) * 8};
         hipLaunchKernelGGL(closed_loop_fwd_link_kernel, dim3((unsigned)a.p.plant_blocks + cb), dim3(CL_LANES), 0, s, a);
         NDP_HIP(h, hipGetLastError());
     }
@@ -335,53 +375,41 @@ int ndp_closed_loop_vjp_device(ndp_handle *h, int ticks, double dt, int substeps
                                const void *d_gus, const void *d_gXs, void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_gfp,
                                void *d_gmodel, void *d_status_check, void *stream)
 {
-    const char *who = "ndp_closed_loop_vjp_device";
     Entry g(h, d_x0 && d_xr && d_ur && d_xs && d_us, stream);
     if (g.rc) return g.rc;
-    int rc = cl_check(h, who, ticks, substeps, d_f);
-    if (rc) return rc;
     const char *own = nullptr;
-    if (!d_tape) own = "d_tape is required (the forward's, recorded by ndp_closed_loop_device)";
-    else if (!d_gxs && !d_gus && !d_gXs) own = "no upstream gradient (d_gxs, d_gus and d_gXs all NULL)";
+    if (!d_gxs && !d_gus && !d_gXs) own = "no upstream gradient (d_gxs, d_gus and d_gXs all NULL)";
     else if (!d_gx0 && !d_gxr && !d_gur && !d_gf && !d_gfp && !d_gmodel) own = "no output asked for (d_gx0, d_gxr, d_gur, d_gf, d_gfp and d_gmodel all NULL)";
-    const std::string why = recompute_refusal(h->cfg, "adjoint", Tape{d_x0, d_xr, d_ur, d_f, d_tape ? d_tape : d_x0, d_tape ? d_tape : d_x0,
-                                                                          nullptr, nullptr, nullptr}, own);
-    if (!why.empty()) { h->err = std::string(who) + ": " + why; return -2; }
+    const ClView v = cl_view(h, d_x0, d_xr, d_ur, d_f, d_fp, d_xs, d_us, d_tape);
+    int rc = cl_deriv_begin(h, "ndp_closed_loop_vjp_device", "adjoint", ticks, substeps, v, own);
+    if (rc) return rc;
     hipStream_t s = g.s;
-    const size_t B = h->cfg.batch, slot = cl_slot_bytes(h), itb = cl_iterate_bytes(h), ab = act_bytes(h);
-    if ((rc = recompute_workspace(h))) return rc;
+    const size_t B = v.B;
     if (!h->dClWs) NDP_HIP(h, hipMalloc((void **)&h->dClWs, B * (NU + NX + NX + 16) * 8));
     double *ws_gu0 = h->dClWs, *ws_gxp = ws_gu0 + B * NU, *ws_gx0 = ws_gxp + B * NX, *ws_gm = ws_gx0 + B * NX;
-    const unsigned char *tape = (const unsigned char *)d_tape;
     const bool model = d_gmodel != nullptr;
-    const unsigned cb = cl_copy_blocks(itb + ab);
+    const unsigned cb = cl_copy_blocks(v.itb + v.ab);
     // where tick k's adjoint leaves its recomputed status words: the caller's log, or the workspace's
     auto st_of = [&](int k) { return d_status_check ? (const int *)d_status_check + (size_t)k * B : (const int *)h->dVjpSt; };
     for (int k = ticks - 1; k >= 0; --k) {
         const bool last = k == ticks - 1;
-        const double *xk = k ? (const double *)d_xs + (size_t)(k - 1) * B * NX : (const double *)d_x0;
-        const double *u0 = (const double *)d_us + (size_t)k * B * NU;
         ClRev a{};
         a.p = cl_plant(h, dt, substeps, true);
-        a.xin = xk; a.u = u0; a.fp = d_fp ? (const double *)d_fp + (size_t)k * B * 3 : nullptr;
-        a.gxs = d_gxs ? (const double *)d_gxs + (size_t)k * B * NX : nullptr;
-        a.gus = d_gus ? (const double *)d_gus + (size_t)k * B * NU : nullptr;
+        a.xin = v.x(k); a.u = v.u0(k); a.fp = v.fpk(k);
+        a.gxs = cl_at((const double *)d_gxs, k, B * NX);
+        a.gus = cl_at((const double *)d_gus, k, B * NU);
         a.c_p = last ? nullptr : ws_gxp; a.c_s = last ? nullptr : ws_gx0;
         a.gxp = ws_gxp; a.gu0 = ws_gu0;
-        a.gfp = d_gfp ? (double *)d_gfp + (size_t)k * B * 3 : nullptr;
+        a.gfp = cl_at((double *)d_gfp, k, B * 3);
         a.gm_tot = (double *)d_gmodel; a.gm_row = last ? nullptr : ws_gm;
-        a.st_prev = last ? nullptr : st_of(k + 1); a.gfp_prev = !last && d_gfp ? (double *)d_gfp + (size_t)(k + 1) * B * 3 : nullptr;
-        a.cp[0] = ClCopy{tape + (size_t)k * slot, (unsigned char *)h->dVjp, itb};
-        a.cp[1] = ClCopy{tape + (size_t)k * slot + itb, (unsigned char *)h->dVjpAct, ab};
+        a.st_prev = last ? nullptr : st_of(k + 1); a.gfp_prev = last ? nullptr : cl_at((double *)d_gfp, k + 1, B * 3);
+        v.replay(k, a.cp);
         hipLaunchKernelGGL(closed_loop_rev_link_kernel, dim3((unsigned)a.p.plant_blocks + cb), dim3(CL_LANES), 0, s, a);
         NDP_HIP(h, hipGetLastError());
-        const Tape t{xk, (const double *)d_xr + (size_t)k * nxs(h), (const double *)d_ur + (size_t)k * nus(h),
-                     d_f ? (const float *)d_f + (size_t)k * nfs(h) : nullptr, nullptr, nullptr, nullptr, nullptr,
-                     d_status_check ? (int *)d_status_check + (size_t)k * B : nullptr};
-        VjpArgs va{ws_gu0, d_gXs ? (const double *)d_gXs + (size_t)k * nxs(h) : nullptr, nullptr, ws_gx0,
-                   d_gxr ? (double *)d_gxr + (size_t)k * nxs(h) : nullptr, d_gur ? (double *)d_gur + (size_t)k * nus(h) : nullptr,
-                   d_gf ? (double *)d_gf + (size_t)k * nfs(h) : nullptr};
+        VjpArgs va{ws_gu0, cl_at((const double *)d_gXs, k, nxs(h)), nullptr, ws_gx0, cl_at((double *)d_gxr, k, nxs(h)),
+                   cl_at((double *)d_gur, k, nus(h)), cl_at((double *)d_gf, k, nfs(h))};
         double *gm = ws_gm;
+        const Tape t = v.step(k, cl_at((int *)d_status_check, k, B));
         if (model) rc = recompute_on_workspace(h, s, t, recompute_kernel(RC_WVJP, true), recompute_kernel(RC_WVJP, false), &va, &gm);
         else rc = recompute_on_workspace(h, s, t, recompute_kernel(RC_VJP, true), recompute_kernel(RC_VJP, false), &va, nullptr);
         if (rc) return rc;
@@ -405,61 +433,47 @@ int ndp_closed_loop_jvp_device(ndp_handle *h, int ticks, double dt, int substeps
                                const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf, const void *d_tfp, void *d_dxs,
                                void *d_dus, void *d_dXs, void *d_dUs, void *d_status_check, void *stream)
 {
-    const char *who = "ndp_closed_loop_jvp_device";
     Entry g(h, d_x0 && d_xr && d_ur && d_xs && d_us, stream);
     if (g.rc) return g.rc;
-    int rc = cl_check(h, who, ticks, substeps, d_f);
-    if (rc) return rc;
     const char *own = nullptr;
-    if (!d_tape) own = "d_tape is required (the forward's, recorded by ndp_closed_loop_device)";
-    else if (n_tan < 1 || n_tan > NDP_JVP_MAX_TANGENTS) own = "n_tan must be 1..8 (directions per call)";
+    if (n_tan < 1 || n_tan > NDP_JVP_MAX_TANGENTS) own = "n_tan must be 1..8 (directions per call)";
     else if (!d_tx0 && !d_txr && !d_tur && !d_tf && !d_tfp) own = "no tangent given (d_tx0, d_txr, d_tur, d_tf and d_tfp all NULL)";
     else if (d_tf && !h->cfg.use_fd) own = "a force tangent (d_tf) needs use_fd = 1 (NDP model)";
     else if (!d_dxs || !d_dus) own = "d_dxs and d_dus are required (the tangents of the two logs)";
-    const std::string why = recompute_refusal(h->cfg, "derivative", Tape{d_x0, d_xr, d_ur, d_f, d_tape ? d_tape : d_x0, d_tape ? d_tape : d_x0,
-                                                                             nullptr, nullptr, nullptr}, own);
-    if (!why.empty()) { h->err = std::string(who) + ": " + why; return -2; }
+    const ClView v = cl_view(h, d_x0, d_xr, d_ur, d_f, d_fp, d_xs, d_us, d_tape);
+    int rc = cl_deriv_begin(h, "ndp_closed_loop_jvp_device", "derivative", ticks, substeps, v, own);
+    if (rc) return rc;
     hipStream_t s = g.s;
-    const size_t B = h->cfg.batch, T = (size_t)n_tan, slot = cl_slot_bytes(h), itb = cl_iterate_bytes(h), ab = act_bytes(h);
-    if ((rc = recompute_workspace(h))) return rc;
-    const unsigned char *tape = (const unsigned char *)d_tape;
-    const unsigned cb = cl_copy_blocks(itb + ab), pb = (unsigned)((B * T + CL_LANES - 1) / CL_LANES);
-    auto slot_into_workspace = [&](ClTan &a, int k) {
-        a.cp[0] = ClCopy{tape + (size_t)k * slot, (unsigned char *)h->dVjp, itb};
-        a.cp[1] = ClCopy{tape + (size_t)k * slot + itb, (unsigned char *)h->dVjpAct, ab};
-    };
+    const size_t B = v.B, T = (size_t)n_tan;
+    const unsigned cb = cl_copy_blocks(v.itb + v.ab), pb = (unsigned)((B * T + CL_LANES - 1) / CL_LANES);
     {                              // the head: slot 0 into the workspace
         ClTan a{};
         a.p = cl_plant(h, dt, substeps, false);
-        slot_into_workspace(a, 0);
+        v.replay(0, a.cp);
         hipLaunchKernelGGL(closed_loop_tan_link_kernel, dim3(cb), dim3(CL_LANES), 0, s, a);
         NDP_HIP(h, hipGetLastError());
     }
     double *dxs = (double *)d_dxs, *dus = (double *)d_dus;
     for (int k = 0; k < ticks; ++k) {
-        const double *xk = k ? (const double *)d_xs + (size_t)(k - 1) * B * NX : (const double *)d_x0;
         const double *tx = k ? dxs + (size_t)(k - 1) * B * T * NX : (const double *)d_tx0;
         double *du = dus + (size_t)k * B * T * NU;
-        int *st = d_status_check ? (int *)d_status_check + (size_t)k * B : nullptr;
+        int *st = cl_at((int *)d_status_check, k, B);
         // (tick 0 with no direction of the step's -- only d_tfp given -- is launched like every other: it recomputes the tick's status word,
         // and jvp_out with all four NULL writes the zeros, or the NaNs of a failed vehicle, that this tick's link reads)
-        const Tape t{xk, (const double *)d_xr + (size_t)k * nxs(h), (const double *)d_ur + (size_t)k * nus(h),
-                     d_f ? (const float *)d_f + (size_t)k * nfs(h) : nullptr, nullptr, nullptr, nullptr, nullptr, st};
-        JvpArgs ja{tx, d_txr ? (const double *)d_txr + (size_t)k * T * nxs(h) : nullptr,
-                   d_tur ? (const double *)d_tur + (size_t)k * T * nus(h) : nullptr, d_tf ? (const double *)d_tf + (size_t)k * T * nfs(h) : nullptr,
-                   du, d_dXs ? (double *)d_dXs + (size_t)k * T * nxs(h) : nullptr, d_dUs ? (double *)d_dUs + (size_t)k * T * nus(h) : nullptr,
+        JvpArgs ja{tx, cl_at((const double *)d_txr, k, T * nxs(h)), cl_at((const double *)d_tur, k, T * nus(h)),
+                   cl_at((const double *)d_tf, k, T * nfs(h)), du, cl_at((double *)d_dXs, k, T * nxs(h)), cl_at((double *)d_dUs, k, T * nus(h)),
                    n_tan};
-        if ((rc = recompute_on_workspace(h, s, t, recompute_kernel(RC_JVP, true), recompute_kernel(RC_JVP, false), &ja, nullptr))) return rc;
+        if ((rc = recompute_on_workspace(h, s, v.step(k, st), recompute_kernel(RC_JVP, true), recompute_kernel(RC_JVP, false), &ja, nullptr))) return rc;
         ClTan a{};
         a.p = cl_plant(h, dt, substeps, true);
         a.p.plant_blocks = (int)pb;
         a.T = n_tan;
-        a.xin = xk; a.u = (const double *)d_us + (size_t)k * B * NU; a.fp = d_fp ? (const double *)d_fp + (size_t)k * B * 3 : nullptr;
-        a.tx = tx; a.tfp = d_tfp ? (const double *)d_tfp + (size_t)k * B * T * 3 : nullptr;
+        a.xin = v.x(k); a.u = v.u0(k); a.fp = v.fpk(k);
+        a.tx = tx; a.tfp = cl_at((const double *)d_tfp, k, B * T * 3);
         a.du = du; a.dx = dxs + (size_t)k * B * T * NX;
         a.st = st ? st : h->dVjpSt;
         const bool more = k + 1 < ticks;
-        if (more) slot_into_workspace(a, k + 1);
+        if (more) v.replay(k + 1, a.cp);
         hipLaunchKernelGGL(closed_loop_tan_link_kernel, dim3(pb + (more ? cb : 0u)), dim3(CL_LANES), 0, s, a);
         NDP_HIP(h, hipGetLastError());
     }

@@ -6,6 +6,7 @@
 //   plant_force_kernel : f4, the downwash force on the plant from the vehicles' actual states, one row per vehicle (ndp_plant_force*).
 //   mlp_multi_kernel / plant_force_multi_kernel : the prediction and the plant force with K neighbours per vehicle, forces summed
 //                 (ndp_downwash_multi*, ndp_plant_force_multi*).
+// Host side: launch_plant_force launches either force kernel; plant_force_host / downwash_host: the host-array entries, single and multi.
 // (The fused form runs inside the control step: rti_kernels.hip.  The backward pass: mlp_vjp.hip.)
 #include <hip/hip_runtime.h>
 
@@ -565,42 +566,24 @@ int ndp_debug_downwash_stream_device(ndp_handle *h, const void *d_other, const v
     return g.noted(0);
 }
 
-// ---- f4: the downwash force on the plant (plant_force_kernel).  No locking, no sync; d_index null: no network pass, no weights needed.
-int launch_plant_force(ndp_handle *h, const double *d_x, const int *d_index, int gate, double scale, double *d_f, double *d_xy, hipStream_t s)
+// ---- f4: the downwash force on the plant, single form (K = 0, d_index int32[B]: plant_force_kernel) and K neighbours per vehicle (d_index
+// int32[B][K]: plant_force_multi_kernel).  No locking, no sync, K not checked (check_neigh).  d_index null: nobody has a neighbour -- the
+// single kernel with a null index writes the zeros, no network pass, no weights needed.
+int launch_plant_force(ndp_handle *h, const double *d_x, const int *d_index, int K, int gate, double scale, double *d_f, double *d_xy,
+                       hipStream_t s)
 {
     if (d_index && !h->have_mlp) { h->err = "downwash requested but ndp_set_mlp_weights was never called"; return -6; }
     const int B = h->cfg.batch, ntiles = (B + 31) / 32;
     const int nw = ntiles < 4 ? ntiles : 4;          // waves per workgroup: no idle wave in a batch of up to 96 vehicles
-    hipLaunchKernelGGL(plant_force_kernel, dim3((ntiles + nw - 1) / nw), dim3(64 * nw), 0, s, (const float *)h->dFrag, d_x, d_index, d_f, d_xy, B,
-                       h->cfg.r_horiz * h->cfg.r_horiz, gate ? 1 : 0, scale);
+    const dim3 grid((ntiles + nw - 1) / nw), block(64 * nw);
+    const double r2 = h->cfg.r_horiz * h->cfg.r_horiz;
+    if (d_index && K) hipLaunchKernelGGL(plant_force_multi_kernel, grid, block, 0, s, (const float *)h->dFrag, d_x, d_index, K, d_f, d_xy, B, r2, gate ? 1 : 0, scale);
+    else hipLaunchKernelGGL(plant_force_kernel, grid, block, 0, s, (const float *)h->dFrag, d_x, d_index, d_f, d_xy, B, r2, gate ? 1 : 0, scale);
     NDP_HIP(h, hipGetLastError());
     return 0;
 }
 
-int ndp_plant_force_device(ndp_handle *h, const void *d_x, const void *d_other_index, int gate, double scale, void *d_f, void *d_xy,
-                           void *stream)
-{
-    Entry g(h, d_x && d_f, stream);
-    if (g.rc) return g.rc;
-    return g.noted(launch_plant_force(h, (const double *)d_x, (const int *)d_other_index, gate, scale, (double *)d_f, (double *)d_xy, g.s));
-}
-
-int ndp_plant_force(ndp_handle *h, const double *x, const int32_t *other_index, int gate, double scale, double *f)
-{
-    Entry g(h, x && f);
-    if (g.rc) return g.rc;
-    const size_t B = h->cfg.batch;
-    hipStream_t s = h->stream;
-    int *d_index = reinterpret_cast<int *>(h->sThr + 3 * B);          // sThr: f [B][3] | index int32[B]
-    NDP_HIP(h, hipMemcpyAsync(h->sx0, x, B * NX * 8, hipMemcpyHostToDevice, s));
-    if (other_index) NDP_HIP(h, hipMemcpyAsync(d_index, other_index, B * 4, hipMemcpyHostToDevice, s));
-    int rc = launch_plant_force(h, h->sx0, other_index ? d_index : nullptr, gate, scale, h->sThr, nullptr, s);
-    if (rc) return rc;
-    NDP_HIP(h, hipMemcpyAsync(f, h->sThr, B * 3 * 8, hipMemcpyDeviceToHost, s));
-    return g.synced(0);
-}
-
-// ---- K neighbours per vehicle (mlp_multi_kernel, plant_force_multi_kernel).  No locking, no sync.
+// ---- K neighbours per vehicle (mlp_multi_kernel).  No locking, no sync.
 // allow mlp_multi_kernel's dynamic-LDS launch (ndp_create)
 hipError_t mlp_multi_prepare(void)
 {
@@ -628,51 +611,21 @@ int launch_mlp_multi(ndp_handle *h, const double *d_other, int other_stride, con
     return 0;
 }
 
-int launch_plant_force_multi(ndp_handle *h, const double *d_x, const int *d_index, int K, int gate, double scale, double *d_f, double *d_xy,
-                             hipStream_t s)
+// What a multi entry tries first, behind its frame: K (-2) IN FRONT OF the -1 of a missing argument (an index array of K = 0 may well be NULL).
+// The single forms have no K and give their -1 in the frame.
+static int neigh_args(ndp_handle *h, const char *who, int K, bool args)
 {
-    if (!d_index) return launch_plant_force(h, d_x, nullptr, gate, scale, d_f, d_xy, s);      // nobody has a neighbour: zeros, no weights needed
-    if (!h->have_mlp) { h->err = "downwash requested but ndp_set_mlp_weights was never called"; return -6; }
-    const int B = h->cfg.batch, ntiles = (B + 31) / 32;
-    const int nw = ntiles < 4 ? ntiles : 4;
-    hipLaunchKernelGGL(plant_force_multi_kernel, dim3((ntiles + nw - 1) / nw), dim3(64 * nw), 0, s, (const float *)h->dFrag, d_x, d_index, K, d_f,
-                       d_xy, B, h->cfg.r_horiz * h->cfg.r_horiz, gate ? 1 : 0, scale);
-    NDP_HIP(h, hipGetLastError());
-    return 0;
+    const int rc = check_neigh(h, who, K);
+    return rc ? rc : args ? 0 : -1;
 }
 
-int ndp_downwash_multi_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index, int K, const void *d_ego_ref,
-                              const void *d_ego_xy, void *d_f_out, void *stream)
+// ---- the device-pointer entries
+int ndp_plant_force_device(ndp_handle *h, const void *d_x, const void *d_other_index, int gate, double scale, void *d_f, void *d_xy,
+                           void *stream)
 {
-    Entry g(h, true, stream);
+    Entry g(h, d_x && d_f, stream);
     if (g.rc) return g.rc;
-    int rc = check_neigh(h, "ndp_downwash_multi_device", K);      // (in front of the arguments: an index array of K = 0 may well be NULL)
-    if (rc) return rc;
-    if (!(d_other && d_other_index && d_ego_ref && d_f_out)) return -1;
-    if (other_stride != 10 && other_stride != 6) { h->err = "ndp_downwash_multi_device: other_stride must be 10 or 6"; return -13; }
-    return g.noted(launch_mlp_multi(h, (const double *)d_other, other_stride, (const int *)d_other_index, K, (const double *)d_ego_ref,
-                                    (const double *)d_ego_xy, (float *)d_f_out, g.s));
-}
-
-int ndp_downwash_multi(ndp_handle *h, const double *other, const int32_t *other_index, int K, const double *ego_ref, const double *ego_xy,
-                       float *f_out)
-{
-    Entry g(h, true);
-    if (g.rc) return g.rc;
-    int rc = check_neigh(h, "ndp_downwash_multi", K);
-    if (rc) return rc;
-    if (!(other && other_index && ego_ref && f_out)) return -1;
-    const size_t B = h->cfg.batch;
-    hipStream_t s = h->stream;
-    int *d_index = reinterpret_cast<int *>(h->sThr);                  // sThr: index int32[B][K] (at most 4 B doubles)
-    NDP_HIP(h, hipMemcpyAsync(h->sother, other, nxs(h) * 8, hipMemcpyHostToDevice, s));
-    NDP_HIP(h, hipMemcpyAsync(h->sxr, ego_ref, nxs(h) * 8, hipMemcpyHostToDevice, s));
-    NDP_HIP(h, hipMemcpyAsync(d_index, other_index, B * K * 4, hipMemcpyHostToDevice, s));
-    if (ego_xy) NDP_HIP(h, hipMemcpyAsync(h->sego, ego_xy, B * 2 * 8, hipMemcpyHostToDevice, s));
-    rc = launch_mlp_multi(h, h->sother, NX, d_index, K, h->sxr, ego_xy ? h->sego : nullptr, h->dForce, s);
-    if (rc) return rc;
-    NDP_HIP(h, hipMemcpyAsync(f_out, h->dForce, nfs(h) * 4, hipMemcpyDeviceToHost, s));
-    return g.synced(0);
+    return g.noted(launch_plant_force(h, (const double *)d_x, (const int *)d_other_index, 0, gate, scale, (double *)d_f, (double *)d_xy, g.s));
 }
 
 int ndp_plant_force_multi_device(ndp_handle *h, const void *d_x, const void *d_other_index, int K, int gate, double scale, void *d_f,
@@ -680,44 +633,87 @@ int ndp_plant_force_multi_device(ndp_handle *h, const void *d_x, const void *d_o
 {
     Entry g(h, true, stream);
     if (g.rc) return g.rc;
-    int rc = check_neigh(h, "ndp_plant_force_multi_device", K);
+    const int rc = neigh_args(h, "ndp_plant_force_multi_device", K, d_x && d_f);
     if (rc) return rc;
-    if (!(d_x && d_f)) return -1;
-    return g.noted(launch_plant_force_multi(h, (const double *)d_x, (const int *)d_other_index, K, gate, scale, (double *)d_f, (double *)d_xy, g.s));
+    return g.noted(launch_plant_force(h, (const double *)d_x, (const int *)d_other_index, K, gate, scale, (double *)d_f, (double *)d_xy, g.s));
+}
+
+int ndp_downwash_multi_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index, int K, const void *d_ego_ref,
+                              const void *d_ego_xy, void *d_f_out, void *stream)
+{
+    Entry g(h, true, stream);
+    if (g.rc) return g.rc;
+    const int rc = neigh_args(h, "ndp_downwash_multi_device", K, d_other && d_other_index && d_ego_ref && d_f_out);
+    if (rc) return rc;
+    if (other_stride != 10 && other_stride != 6) { h->err = "ndp_downwash_multi_device: other_stride must be 10 or 6"; return -13; }
+    return g.noted(launch_mlp_multi(h, (const double *)d_other, other_stride, (const int *)d_other_index, K, (const double *)d_ego_ref,
+                                    (const double *)d_ego_xy, (float *)d_f_out, g.s));
+}
+
+// ---- the host-array entries, one body per single / multi pair (who: the multi entry's name, null: the single form, K not read).  What
+// they stage in sThr (11 B doubles), written once:
+//   the plant force   f fp64 [B][3] | index int32 [B][K]   3 B + K B / 2 doubles: 7 B at K = NDP_MAX_NEIGH = 8
+//   the prediction    index int32 [B][K]                   K B / 2 doubles: 4 B at K = 8 (the force is h->dForce)
+static int *sthr_force_index(const ndp_handle *h) { return reinterpret_cast<int *>(h->sThr + 3 * (size_t)h->cfg.batch); }
+static int *sthr_index(const ndp_handle *h) { return reinterpret_cast<int *>(h->sThr); }
+
+static int plant_force_host(ndp_handle *h, const char *who, const double *x, const int32_t *other_index, int K, int gate, double scale, double *f)
+{
+    Entry g(h, who || (x && f));
+    if (g.rc) return g.rc;
+    int rc;
+    if (who && (rc = neigh_args(h, who, K, x && f))) return rc;
+    const size_t B = h->cfg.batch;
+    hipStream_t s = h->stream;
+    int *d_index = sthr_force_index(h);
+    NDP_HIP(h, hipMemcpyAsync(h->sx0, x, B * NX * 8, hipMemcpyHostToDevice, s));
+    if (other_index) NDP_HIP(h, hipMemcpyAsync(d_index, other_index, B * (who ? K : 1) * 4, hipMemcpyHostToDevice, s));
+    if ((rc = launch_plant_force(h, h->sx0, other_index ? d_index : nullptr, who ? K : 0, gate, scale, h->sThr, nullptr, s))) return rc;
+    NDP_HIP(h, hipMemcpyAsync(f, h->sThr, B * 3 * 8, hipMemcpyDeviceToHost, s));
+    return g.synced(0);
+}
+
+int ndp_plant_force(ndp_handle *h, const double *x, const int32_t *other_index, int gate, double scale, double *f)
+{
+    return plant_force_host(h, nullptr, x, other_index, 0, gate, scale, f);
 }
 
 int ndp_plant_force_multi(ndp_handle *h, const double *x, const int32_t *other_index, int K, int gate, double scale, double *f)
 {
-    Entry g(h, true);
+    return plant_force_host(h, "ndp_plant_force_multi", x, other_index, K, gate, scale, f);
+}
+
+static int downwash_host(ndp_handle *h, const char *who, const double *other, const int32_t *other_index, int K, const double *ego_ref,
+                         const double *ego_xy, float *f_out)
+{
+    Entry g(h, who || (other && ego_ref && f_out));
     if (g.rc) return g.rc;
-    int rc = check_neigh(h, "ndp_plant_force_multi", K);
-    if (rc) return rc;
-    if (!(x && f)) return -1;
+    int rc;
+    if (who && (rc = neigh_args(h, who, K, other && other_index && ego_ref && f_out))) return rc;      // (multi: the index is required)
     const size_t B = h->cfg.batch;
     hipStream_t s = h->stream;
-    int *d_index = reinterpret_cast<int *>(h->sThr + 3 * B);          // sThr: f [B][3] | index int32[B][K] (at most 4 B doubles)
-    NDP_HIP(h, hipMemcpyAsync(h->sx0, x, B * NX * 8, hipMemcpyHostToDevice, s));
-    if (other_index) NDP_HIP(h, hipMemcpyAsync(d_index, other_index, B * K * 4, hipMemcpyHostToDevice, s));
-    rc = launch_plant_force_multi(h, h->sx0, other_index ? d_index : nullptr, K, gate, scale, h->sThr, nullptr, s);
+    NDP_HIP(h, hipMemcpyAsync(h->sother, other, nxs(h) * 8, hipMemcpyHostToDevice, s));
+    NDP_HIP(h, hipMemcpyAsync(h->sxr, ego_ref, nxs(h) * 8, hipMemcpyHostToDevice, s));
+    if (who) NDP_HIP(h, hipMemcpyAsync(sthr_index(h), other_index, B * K * 4, hipMemcpyHostToDevice, s));
+    if (ego_xy) NDP_HIP(h, hipMemcpyAsync(h->sego, ego_xy, B * 2 * 8, hipMemcpyHostToDevice, s));
+    Neigh nb;
+    nb.other = h->sother; nb.ego_xy = ego_xy ? h->sego : nullptr;
+    if (who) rc = launch_mlp_multi(h, nb.other, NX, sthr_index(h), K, h->sxr, nb.ego_xy, h->dForce, s);
+    else rc = launch_mlp(h, nb, h->sxr, h->dForce, s);
     if (rc) return rc;
-    NDP_HIP(h, hipMemcpyAsync(f, h->sThr, B * 3 * 8, hipMemcpyDeviceToHost, s));
+    NDP_HIP(h, hipMemcpyAsync(f_out, h->dForce, nfs(h) * 4, hipMemcpyDeviceToHost, s));
     return g.synced(0);
 }
 
 int ndp_downwash(ndp_handle *h, const double *other, const double *ego_ref, const double *ego_xy, float *f_out)
 {
-    Entry g(h, other && ego_ref && f_out);
-    if (g.rc) return g.rc;
-    hipStream_t s = h->stream;
-    NDP_HIP(h, hipMemcpyAsync(h->sother, other, nxs(h) * 8, hipMemcpyHostToDevice, s));
-    NDP_HIP(h, hipMemcpyAsync(h->sxr, ego_ref, nxs(h) * 8, hipMemcpyHostToDevice, s));
-    if (ego_xy) NDP_HIP(h, hipMemcpyAsync(h->sego, ego_xy, (size_t)h->cfg.batch * 2 * 8, hipMemcpyHostToDevice, s));
-    Neigh nb;
-    nb.other = h->sother; nb.ego_xy = ego_xy ? h->sego : nullptr;
-    int rc = launch_mlp(h, nb, h->sxr, h->dForce, s);
-    if (rc) return rc;
-    NDP_HIP(h, hipMemcpyAsync(f_out, h->dForce, nfs(h) * 4, hipMemcpyDeviceToHost, s));
-    return g.synced(0);
+    return downwash_host(h, nullptr, other, nullptr, 0, ego_ref, ego_xy, f_out);
+}
+
+int ndp_downwash_multi(ndp_handle *h, const double *other, const int32_t *other_index, int K, const double *ego_ref, const double *ego_xy,
+                       float *f_out)
+{
+    return downwash_host(h, "ndp_downwash_multi", other, other_index, K, ego_ref, ego_xy, f_out);
 }
 
 }  // extern "C"

@@ -7,25 +7,31 @@
 //   ndp_hip.hip      the handle's runtime: pack threads, create / destroy, every step form (enqueue_step, launch_rti, rti_pick), the
 //                    host-array step, timing, the sensitivities, the adjoint / forward-mode entry points, ndp_set_model, the debug hooks
 //   downwash.hip     the downwash network's forward entry points, mlp_stream_kernel + the prefetch protocol, ndp_set_mlp_weights,
-//                    plant_force_kernel (f4: the downwash force on the plant), mlp_multi_kernel / plant_force_multi_kernel (K neighbours)
+//                    plant_force_kernel (f4: the downwash force on the plant), mlp_multi_kernel / plant_force_multi_kernel (K neighbours);
+//                    one launcher for both force kernels (launch_plant_force), one host-array body per single / K pair (plant_force_host,
+//                    downwash_host) over one statement of what they stage in sThr
 //   rows.hip         the rows f1 - f4: reference window and list, follower relay, throttle estimator, actuator command, plant, rollouts
+//                    (rollout_head: what all three start with; rollout_formation: the body of both formation rollouts)
 //   tick.hip         the control tick's host side (ndp_tick*); no kernel: compiled for the host only
-//   mlp_vjp.hip      the downwash network's backward pass (ndp_downwash_vjp_device, ndp_downwash_multi_vjp_device) and its weights set from
-//                    device memory
+//   mlp_vjp.hip      the downwash network's backward pass (ndp_downwash_vjp_device, ndp_downwash_multi_vjp_device: one body, downwash_vjp)
+//                    and its weights set from device memory
 //   mlp_fit.hip      the downwash network on sample rows: the forward (ndp_mlp_rows_device) and the fit's loss and weight gradient in one
 //                    pass (ndp_mlp_fit_rows_device); shares mlp_vjp.hip's device functions (mlp_vjp_dev.hpp) and the text of its rounds
 //                    (mlp_vjp_back.inc, mlp_vjp_part.inc)
-//   mlp_jvp.hip      the downwash network's forward mode (ndp_downwash_jvp_device, ndp_downwash_multi_jvp_device)
+//   mlp_jvp.hip      the downwash network's forward mode (ndp_downwash_jvp_device, ndp_downwash_multi_jvp_device: one body, downwash_jvp)
 //   mlp_train.hip    the downwash network's optimiser step: Adam + spectral-norm cap in one launch (ndp_mlp_adam_sn_device), the layers'
 //                    spectral norms (ndp_mlp_spectral_norms*)
 //   plant_deriv.hip  the plant over a given input sequence and its derivatives (ndp_plant_rollout_device, ndp_plant_rollout_vjp_device,
-//                    ndp_plant_rollout_jvp_device); a tick's arithmetic is plant_dyn.hpp's, shared with rows.hip's plant_kernel
+//                    ndp_plant_rollout_jvp_device); a tick's arithmetic is plant_dyn.hpp's, shared with rows.hip's plant_kernel; the
+//                    ticks / substeps refusals of these and of closed_loop.hip's calls (plant_seq_check).  The plant's three numbers
+//                    every launcher of it passes: plant_num, below
 //   plant_force_deriv.hip  the derivatives of the downwash force on the plant (ndp_plant_force_vjp_device, ndp_plant_force_jvp_device and
 //                    their multi forms); hosts mlp_vjp.hip's backward pass (mlp_vjp_dev.hpp, mlp_vjp_back.inc, mlp_vjp_part.inc) and
 //                    mlp_jvp.hip's direction (mlp_jvp_dev.hpp, mlp_jvp_direction.inc) behind a row loader of its own
 //   closed_loop.hip  the closed loop over given windows in one call per direction (ndp_closed_loop_device, ndp_closed_loop_vjp_device,
 //                    ndp_closed_loop_jvp_device): the step, its adjoint and its forward mode are the existing kernels, launched unchanged;
-//                    the three link kernels between them live here
+//                    the three link kernels between them live here.  Host side: ClView hands out tick k's slices and tape slot,
+//                    cl_deriv_begin is what the two derivative calls do before they enqueue
 //   exchange.hip     peer-mapped windows (ndp_peer_*), the RCCL exchange (ndp_xchg_*) and the remote tick one control period ahead
 // A kernel sits with the host code that launches it; device code that two units' kernels inline is a header (mlp_tile.hpp, ref_point.hpp,
 // tick_wave.hpp, mlp_vjp_dev.hpp, mlp_jvp_dev.hpp, plant_dyn.hpp, plant_adj.hpp, plant_tan.hpp), and so are the argument blocks the host fills (kern_args.hpp).
@@ -225,6 +231,10 @@ static inline void copy_ipm_iters(int32_t *dst, const int32_t *src, size_t n)
     for (size_t i = 0; i < n; ++i) dst[i] = src[i] & ITERS_IPM_MASK;
 }
 
+// the numbers every launch of the plant takes (plant_kernel, PlantSeq, ClPlant): the substep dt / substeps, 1 / mass, g
+struct PlantNum { double h, inv_mass, g; };
+static inline PlantNum plant_num(const ndp_handle *h, double dt, int substeps) { return PlantNum{dt / substeps, 1.0 / h->cfg.mass, h->cfg.gravity}; }
+
 struct Neigh {                 // neighbour windows of a step (device pointers)
     const double *other = nullptr;
     int stride = NX;           // doubles per node: 10 or 6
@@ -285,16 +295,14 @@ NDP_HIDDEN int enqueue_step(ndp_handle *h, const double *d_x0, const double *d_x
 NDP_HIDDEN int ensure_slots(ndp_handle *h);
 NDP_HIDDEN int recompute_workspace(ndp_handle *h);
 NDP_HIDDEN int recompute_on_workspace(ndp_handle *h, hipStream_t s, const Tape &t, const void *fn20, const void *fn0, void *a1, void *a2);
-// downwash.hip
-NDP_HIDDEN int launch_plant_force(ndp_handle *h, const double *d_x, const int *d_index, int gate, double scale, double *d_f, double *d_xy,
-                                  hipStream_t s);
-// ... and with K neighbours per vehicle, d_index int32[B][K] (check_neigh: -2 unless 1 <= K <= NDP_MAX_NEIGH; the launchers do not check)
+// downwash.hip.  launch_plant_force: K = 0 the single form, d_index int32[B]; else K neighbours per vehicle, d_index int32[B][K]
+// (check_neigh: -2 unless 1 <= K <= NDP_MAX_NEIGH; the launchers do not check)
+NDP_HIDDEN int launch_plant_force(ndp_handle *h, const double *d_x, const int *d_index, int K, int gate, double scale, double *d_f,
+                                  double *d_xy, hipStream_t s);
 NDP_HIDDEN hipError_t mlp_multi_prepare(void);
 NDP_HIDDEN int check_neigh(ndp_handle *h, const char *who, int K);
 NDP_HIDDEN int launch_mlp_multi(ndp_handle *h, const double *d_other, int other_stride, const int *d_index, int K, const double *d_ego,
                                 const double *d_ego_xy, float *d_f, hipStream_t s);
-NDP_HIDDEN int launch_plant_force_multi(ndp_handle *h, const double *d_x, const int *d_index, int K, int gate, double scale, double *d_f,
-                                        double *d_xy, hipStream_t s);
 // rows.hip
 NDP_HIDDEN ThrCfg thr_cfg(const ndp_handle *h);
 NDP_HIDDEN RefCfg ref_cfg(const ndp_handle *h, double toff);
@@ -311,6 +319,8 @@ NDP_HIDDEN hipError_t mlp_vjp_prepare(void);
 NDP_HIDDEN hipError_t mlp_fit_prepare(void);
 // plant_force_deriv.hip
 NDP_HIDDEN hipError_t plant_force_deriv_prepare(void);
+// plant_deriv.hip.  The refusals of every call that takes `ticks` ticks of `substeps` substeps (closed_loop.hip's too): -2 with the reason
+NDP_HIDDEN int plant_seq_check(ndp_handle *h, const char *who, int ticks, int substeps);
 // exchange.hip
 NDP_HIDDEN int peer_mapped(const void *p);
 NDP_HIDDEN void launch_pack_pv_list(const double *base, size_t pitch, int np1, double *pv, size_t B, hipStream_t s);

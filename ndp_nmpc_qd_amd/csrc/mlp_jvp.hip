@@ -210,53 +210,51 @@ __global__ __launch_bounds__(256) void mlp_jvp_multi_kernel(MlpJvpArgs A, int K)
 
 using namespace ndp;
 
-extern "C" {
-
-int ndp_downwash_jvp_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index, const void *d_ego_ref,
-                            const void *d_ego_xy, int n_tan, const void *d_tz, const void *d_tw, void *d_df, void *d_f_check, void *stream)
+// The body of ndp_downwash_jvp_device (multi false: d_other_index optional, K not read) and ndp_downwash_multi_jvp_device (K slots, the index
+// required): the refusals under `who`, the argument block, the grid (the real rows in both forms), the launch.  multi: as downwash_vjp's.
+static int downwash_jvp(ndp_handle *h, const char *who, bool multi, const void *d_other, int other_stride, const void *d_other_index, int K,
+                        const void *d_ego_ref, const void *d_ego_xy, int n_tan, const void *d_tz, const void *d_tw, void *d_df,
+                        void *d_f_check, void *stream)
 {
     Entry g(h, d_other && d_ego_ref, stream);
     if (g.rc) return g.rc;
     const char *why = nullptr;
-    if (!h->have_mlp) { h->err = "ndp_downwash_jvp_device: ndp_set_mlp_weights was never called"; return -6; }
-    if (other_stride != 6 && other_stride != NX) why = "ndp_downwash_jvp_device: other_stride must be 6 or 10";
-    else if (n_tan < 1 || n_tan > NDP_JVP_MAX_TANGENTS) why = "ndp_downwash_jvp_device: n_tan must be 1..8 (directions per call)";
-    else if (!d_tz && !d_tw) why = "ndp_downwash_jvp_device: no tangent given (d_tz and d_tw both NULL)";
-    else if (!d_df) why = "ndp_downwash_jvp_device: d_df is required (the tangent of the force)";
-    if (why) { h->err = why; return -2; }
+    // (the weights in front of K here; plant_force_deriv.hip's plant_force_jvp checks K first)
+    if (!h->have_mlp) { h->err = std::string(who) + ": ndp_set_mlp_weights was never called"; return -6; }
+    if (multi && (K < 1 || K > NDP_MAX_NEIGH)) why = ": K must be 1..8 (NDP_MAX_NEIGH neighbours per vehicle)";
+    else if (multi && !d_other_index) why = ": d_other_index is required (int32 [B][K])";
+    else if (other_stride != 6 && other_stride != NX) why = ": other_stride must be 6 or 10";
+    else if (n_tan < 1 || n_tan > NDP_JVP_MAX_TANGENTS) why = ": n_tan must be 1..8 (directions per call)";
+    else if (!d_tz && !d_tw) why = ": no tangent given (d_tz and d_tw both NULL)";
+    // (the two forms word the force differently)
+    else if (!d_df) why = multi ? ": d_df is required (the tangent of the summed force)" : ": d_df is required (the tangent of the force)";
+    if (why) { h->err = std::string(who) + why; return -2; }
     const int np1 = h->cfg.N + 1, rows = h->cfg.batch * np1;
     const int ntiles = (rows + 31) / 32;
     MlpJvpArgs a{h->dFrag, (const double *)d_other, (const double *)d_ego_ref, (const double *)d_ego_xy, (const double *)d_tz,
                  (const float *)d_tw, (double *)d_df, (float *)d_f_check, rows, np1, n_tan, h->cfg.r_horiz * h->cfg.r_horiz, other_stride,
                  (const int *)d_other_index, peer_mapped(d_other), (size_t)np1 * other_stride, (size_t)np1 * NX, (size_t)2};
-    hipLaunchKernelGGL(mlp_jvp_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, g.s, a);
+    if (multi) hipLaunchKernelGGL(mlp_jvp_multi_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, g.s, a, K);
+    else hipLaunchKernelGGL(mlp_jvp_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, g.s, a);
     NDP_HIP(h, hipGetLastError());
     return g.noted(0);
+}
+
+extern "C" {
+
+int ndp_downwash_jvp_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index, const void *d_ego_ref,
+                            const void *d_ego_xy, int n_tan, const void *d_tz, const void *d_tw, void *d_df, void *d_f_check, void *stream)
+{
+    return downwash_jvp(h, "ndp_downwash_jvp_device", false, d_other, other_stride, d_other_index, 0, d_ego_ref, d_ego_xy, n_tan, d_tz, d_tw,
+                        d_df, d_f_check, stream);
 }
 
 int ndp_downwash_multi_jvp_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index, int K,
                                   const void *d_ego_ref, const void *d_ego_xy, int n_tan, const void *d_tz, const void *d_tw, void *d_df,
                                   void *d_f_check, void *stream)
 {
-    Entry g(h, d_other && d_ego_ref, stream);
-    if (g.rc) return g.rc;
-    const char *why = nullptr;
-    if (!h->have_mlp) { h->err = "ndp_downwash_multi_jvp_device: ndp_set_mlp_weights was never called"; return -6; }
-    if (K < 1 || K > NDP_MAX_NEIGH) why = "ndp_downwash_multi_jvp_device: K must be 1..8 (NDP_MAX_NEIGH neighbours per vehicle)";
-    else if (!d_other_index) why = "ndp_downwash_multi_jvp_device: d_other_index is required (int32 [B][K])";
-    else if (other_stride != 6 && other_stride != NX) why = "ndp_downwash_multi_jvp_device: other_stride must be 6 or 10";
-    else if (n_tan < 1 || n_tan > NDP_JVP_MAX_TANGENTS) why = "ndp_downwash_multi_jvp_device: n_tan must be 1..8 (directions per call)";
-    else if (!d_tz && !d_tw) why = "ndp_downwash_multi_jvp_device: no tangent given (d_tz and d_tw both NULL)";
-    else if (!d_df) why = "ndp_downwash_multi_jvp_device: d_df is required (the tangent of the summed force)";
-    if (why) { h->err = why; return -2; }
-    const int np1 = h->cfg.N + 1, rows = h->cfg.batch * np1;
-    const int ntiles = (rows + 31) / 32;
-    MlpJvpArgs a{h->dFrag, (const double *)d_other, (const double *)d_ego_ref, (const double *)d_ego_xy, (const double *)d_tz,
-                 (const float *)d_tw, (double *)d_df, (float *)d_f_check, rows, np1, n_tan, h->cfg.r_horiz * h->cfg.r_horiz, other_stride,
-                 (const int *)d_other_index, peer_mapped(d_other), (size_t)np1 * other_stride, (size_t)np1 * NX, (size_t)2};
-    hipLaunchKernelGGL(mlp_jvp_multi_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, g.s, a, K);
-    NDP_HIP(h, hipGetLastError());
-    return g.noted(0);
+    return downwash_jvp(h, "ndp_downwash_multi_jvp_device", true, d_other, other_stride, d_other_index, K, d_ego_ref, d_ego_xy, n_tan, d_tz,
+                        d_tw, d_df, d_f_check, stream);
 }
 
 }  // extern "C"

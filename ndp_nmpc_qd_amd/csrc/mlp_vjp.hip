@@ -130,6 +130,41 @@ __global__ __launch_bounds__(256) void mlp_vjp_reduce_kernel(const float *__rest
 
 using namespace ndp;
 
+// The body of ndp_downwash_vjp_device (multi false: d_other_index optional, K not read) and ndp_downwash_multi_vjp_device (K slots, the index
+// required): the refusals under the entry's name `who`, the argument block, the grid, the launch, the reduce launch.  (multi is a flag of
+// its own, not "K != 0": the multi form has to refuse K = 0 under its own name, behind the weights.)
+static int downwash_vjp(ndp_handle *h, const char *who, bool multi, const void *d_other, int other_stride, const void *d_other_index, int K,
+                        const void *d_ego_ref, const void *d_ego_xy, const void *d_gf, void *d_gz, void *d_gw, void *stream)
+{
+    Entry g(h, d_other && d_ego_ref, stream);
+    if (g.rc) return g.rc;
+    const char *why = nullptr;
+    // (the weights in front of K here; plant_force_deriv.hip's plant_force_vjp checks K first)
+    if (!h->have_mlp) { h->err = std::string(who) + ": ndp_set_mlp_weights was never called"; return -6; }
+    if (multi && (K < 1 || K > NDP_MAX_NEIGH)) why = ": K must be 1..8 (NDP_MAX_NEIGH neighbours per vehicle)";
+    else if (multi && !d_other_index) why = ": d_other_index is required (int32 [B][K])";
+    else if (other_stride != 6 && other_stride != NX) why = ": other_stride must be 6 or 10";
+    // (the two forms word the force differently)
+    else if (!d_gf) why = multi ? ": d_gf is required (the upstream gradient of the summed force)" : ": d_gf is required (the upstream gradient of the force)";
+    else if (!d_gz && !d_gw) why = ": no output asked for (d_gz and d_gw both NULL)";
+    if (why) { h->err = std::string(who) + why; return -2; }
+    const int np1 = h->cfg.N + 1, rows = h->cfg.batch * (multi ? K : 1) * np1;        // K slots: virtual rows
+    // the workspace dGwPart has mlp_vjp_groups rows, one per 128 rows of the single form: never more workgroups than that (the grid-stride
+    // loop takes the rest); the single form's grid is exactly that, and so is the K = 1 grid, hence its summation order
+    const int ngroups = ((rows + 31) / 32 + 3) / 4, cap = mlp_vjp_groups(h), G = ngroups < cap ? ngroups : cap;
+    MlpVjpArgs a{h->dFrag, h->dFragT, (const double *)d_other, (const double *)d_ego_ref, (const double *)d_ego_xy, (const double *)d_gf,
+                 (double *)d_gz, d_gw ? h->dGwPart : nullptr, rows, np1, h->cfg.r_horiz * h->cfg.r_horiz, other_stride,
+                 (const int *)d_other_index, peer_mapped(d_other), (size_t)np1 * other_stride, (size_t)np1 * NX, (size_t)2};
+    if (multi) hipLaunchKernelGGL(mlp_vjp_multi_kernel, dim3(G), dim3(256), VJ_LDS_FLOATS * sizeof(float), g.s, a, K);
+    else hipLaunchKernelGGL(mlp_vjp_kernel, dim3(G), dim3(256), VJ_LDS_FLOATS * sizeof(float), g.s, a);
+    NDP_HIP(h, hipGetLastError());
+    if (d_gw) {
+        hipLaunchKernelGGL(mlp_vjp_reduce_kernel, dim3((PTOTAL + 255) / 256), dim3(256), 0, g.s, (const float *)h->dGwPart, G, (float *)d_gw);
+        NDP_HIP(h, hipGetLastError());
+    }
+    return g.noted(0);
+}
+
 extern "C" {
 
 void make_fragments_t(const float *blob, float *frt)
@@ -147,55 +182,15 @@ hipError_t mlp_vjp_prepare(void)
 int ndp_downwash_vjp_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index, const void *d_ego_ref,
                             const void *d_ego_xy, const void *d_gf, void *d_gz, void *d_gw, void *stream)
 {
-    Entry g(h, d_other && d_ego_ref, stream);
-    if (g.rc) return g.rc;
-    const char *why = nullptr;
-    if (!h->have_mlp) { h->err = "ndp_downwash_vjp_device: ndp_set_mlp_weights was never called"; return -6; }
-    if (other_stride != 6 && other_stride != NX) why = "ndp_downwash_vjp_device: other_stride must be 6 or 10";
-    else if (!d_gf) why = "ndp_downwash_vjp_device: d_gf is required (the upstream gradient of the force)";
-    else if (!d_gz && !d_gw) why = "ndp_downwash_vjp_device: no output asked for (d_gz and d_gw both NULL)";
-    if (why) { h->err = why; return -2; }
-    const int np1 = h->cfg.N + 1, rows = h->cfg.batch * np1;
-    const int G = mlp_vjp_groups(h);
-    MlpVjpArgs a{h->dFrag, h->dFragT, (const double *)d_other, (const double *)d_ego_ref, (const double *)d_ego_xy, (const double *)d_gf,
-                 (double *)d_gz, d_gw ? h->dGwPart : nullptr, rows, np1, h->cfg.r_horiz * h->cfg.r_horiz, other_stride,
-                 (const int *)d_other_index, peer_mapped(d_other), (size_t)np1 * other_stride, (size_t)np1 * NX, (size_t)2};
-    hipLaunchKernelGGL(mlp_vjp_kernel, dim3(G), dim3(256), VJ_LDS_FLOATS * sizeof(float), g.s, a);
-    NDP_HIP(h, hipGetLastError());
-    if (d_gw) {
-        hipLaunchKernelGGL(mlp_vjp_reduce_kernel, dim3((PTOTAL + 255) / 256), dim3(256), 0, g.s, (const float *)h->dGwPart, G, (float *)d_gw);
-        NDP_HIP(h, hipGetLastError());
-    }
-    return g.noted(0);
+    return downwash_vjp(h, "ndp_downwash_vjp_device", false, d_other, other_stride, d_other_index, 0, d_ego_ref, d_ego_xy, d_gf, d_gz, d_gw,
+                        stream);
 }
 
 int ndp_downwash_multi_vjp_device(ndp_handle *h, const void *d_other, int other_stride, const void *d_other_index, int K,
                                   const void *d_ego_ref, const void *d_ego_xy, const void *d_gf, void *d_gz, void *d_gw, void *stream)
 {
-    Entry g(h, d_other && d_ego_ref, stream);
-    if (g.rc) return g.rc;
-    const char *why = nullptr;
-    if (!h->have_mlp) { h->err = "ndp_downwash_multi_vjp_device: ndp_set_mlp_weights was never called"; return -6; }
-    if (K < 1 || K > NDP_MAX_NEIGH) why = "ndp_downwash_multi_vjp_device: K must be 1..8 (NDP_MAX_NEIGH neighbours per vehicle)";
-    else if (!d_other_index) why = "ndp_downwash_multi_vjp_device: d_other_index is required (int32 [B][K])";
-    else if (other_stride != 6 && other_stride != NX) why = "ndp_downwash_multi_vjp_device: other_stride must be 6 or 10";
-    else if (!d_gf) why = "ndp_downwash_multi_vjp_device: d_gf is required (the upstream gradient of the summed force)";
-    else if (!d_gz && !d_gw) why = "ndp_downwash_multi_vjp_device: no output asked for (d_gz and d_gw both NULL)";
-    if (why) { h->err = why; return -2; }
-    const int np1 = h->cfg.N + 1, rows = h->cfg.batch * K * np1;          // virtual rows
-    // the workspace is ndp_downwash_vjp_device's, [mlp_vjp_groups][NDP_MLP_NPARAM]: never more workgroups than it has rows (the grid-stride
-    // loop takes the rest); at K = 1 this is ndp_downwash_vjp_device's grid, hence its summation order
-    const int ngroups = ((rows + 31) / 32 + 3) / 4, cap = mlp_vjp_groups(h), G = ngroups < cap ? ngroups : cap;
-    MlpVjpArgs a{h->dFrag, h->dFragT, (const double *)d_other, (const double *)d_ego_ref, (const double *)d_ego_xy, (const double *)d_gf,
-                 (double *)d_gz, d_gw ? h->dGwPart : nullptr, rows, np1, h->cfg.r_horiz * h->cfg.r_horiz, other_stride,
-                 (const int *)d_other_index, peer_mapped(d_other), (size_t)np1 * other_stride, (size_t)np1 * NX, (size_t)2};
-    hipLaunchKernelGGL(mlp_vjp_multi_kernel, dim3(G), dim3(256), VJ_LDS_FLOATS * sizeof(float), g.s, a, K);
-    NDP_HIP(h, hipGetLastError());
-    if (d_gw) {
-        hipLaunchKernelGGL(mlp_vjp_reduce_kernel, dim3((PTOTAL + 255) / 256), dim3(256), 0, g.s, (const float *)h->dGwPart, G, (float *)d_gw);
-        NDP_HIP(h, hipGetLastError());
-    }
-    return g.noted(0);
+    return downwash_vjp(h, "ndp_downwash_multi_vjp_device", true, d_other, other_stride, d_other_index, K, d_ego_ref, d_ego_xy, d_gf, d_gz,
+                        d_gw, stream);
 }
 
 int ndp_set_mlp_weights_device(ndp_handle *h, const void *d_blob, void *stream)

@@ -2,7 +2,7 @@
 // inputs u and forces f in one launch, the state in registers from the first tick to the last), ndp_plant_rollout_vjp_device (reverse mode)
 // and ndp_plant_rollout_jvp_device (forward mode).  One lane per vehicle (forward mode: per vehicle and direction), 64-lane workgroups:
 // every lane runs one long serial fp64 chain, so what a small batch needs is to be spread over many CUs.  No LDS, no atomics, no
-// workspace, no scratch.
+// workspace, no scratch.  plant_seq_check, the ticks / substeps refusals, is shared with closed_loop.hip (host.hpp).
 //
 // What is differentiated is the arithmetic of a tick as plant_tick (plant_dyn.hpp) performs it: acc = f / mass - g held over the tick, the
 // RK4 substeps with u and acc held, then q / |q| applied ONCE to the un-normalised end state.  The primal values every kernel here writes
@@ -134,8 +134,16 @@ __global__ __launch_bounds__(PLANT_LANES) void plant_rollout_jvp_kernel(PlantSeq
 
 using namespace ndp;
 
-// the refusals the three calls share, nothing enqueued: -2 with the reason in ndp_last_error
-static int plant_seq_check(ndp_handle *h, const char *who, int ticks, int substeps)
+static PlantSeq plant_seq(const ndp_handle *h, int ticks, double dt, int substeps)
+{
+    const PlantNum n = plant_num(h, dt, substeps);
+    return PlantSeq{ticks, substeps, h->cfg.batch, n.h, n.inv_mass, n.g};
+}
+
+extern "C" {
+
+// the refusals the three calls here and closed_loop.hip's three share, nothing enqueued: -2 with the reason in ndp_last_error
+int plant_seq_check(ndp_handle *h, const char *who, int ticks, int substeps)
 {
     if (ticks < 1) { h->err = std::string(who) + ": ticks must be >= 1, got " + std::to_string(ticks); return -2; }
     if (substeps < 1 || substeps > NDP_PLANT_MAX_SUBSTEPS) {
@@ -144,13 +152,6 @@ static int plant_seq_check(ndp_handle *h, const char *who, int ticks, int subste
     }
     return 0;
 }
-
-static PlantSeq plant_seq(const ndp_handle *h, int ticks, double dt, int substeps)
-{
-    return PlantSeq{ticks, substeps, h->cfg.batch, dt / substeps, 1.0 / h->cfg.mass, h->cfg.gravity};       // (as launch_plant, rows.hip)
-}
-
-extern "C" {
 
 int ndp_plant_rollout_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_u, const void *d_f,
                              void *d_xs, void *stream)

@@ -1,6 +1,7 @@
 // rows.hip -- the rows either side of the control step, kernels and entry points: f1 the reference window and the reference's sliding
 // list (ref_window_kernel, ref_list_*_kernel), f2 the follower relay, f3 the hover-throttle estimator and the actuator command, f4 the
-// plant and the closed-loop rollouts (the formation rollout's force on the plant: downwash.hip, plant_force_kernel).  (A reference point itself, the list store and the estimator's update: ref_point.hpp.)
+// plant and the closed-loop rollouts (rollout_head: what all three start with; rollout_formation: both formation rollouts; their force on the
+// plant: downwash.hip).  (A reference point itself, the list store and the estimator's update: ref_point.hpp.)
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -606,8 +607,8 @@ int ndp_ref_list_window(ndp_handle *h, const double *t, double *xr, double *ur)
 // ---- f4: plant step
 static int launch_plant(ndp_handle *h, double *d_x, const double *d_u, const double *d_f, double dt, int substeps, hipStream_t s)
 {
-    hipLaunchKernelGGL(plant_kernel, dim3((h->cfg.batch + 255) / 256), dim3(256), 0, s, d_x, d_u, d_f, dt / substeps, substeps,
-                       1.0 / h->cfg.mass, h->cfg.gravity, h->cfg.batch);
+    const PlantNum p = plant_num(h, dt, substeps);
+    hipLaunchKernelGGL(plant_kernel, dim3((h->cfg.batch + 255) / 256), dim3(256), 0, s, d_x, d_u, d_f, p.h, substeps, p.inv_mass, p.g, h->cfg.batch);
     NDP_HIP(h, hipGetLastError());
     return 0;
 }
@@ -633,6 +634,18 @@ int ndp_plant_step(ndp_handle *h, double *x, const double *u, const double *f, d
     return g.synced(0);
 }
 
+// ---- f4: the rollouts.  Their head: the first tick's reference window and reset(xr, ur) on it; clear_act: the kept active sets emptied too
+// (the formation rollouts do, ndp_rollout_device does not -- kept as it is)
+static int rollout_head(ndp_handle *h, double t0, bool clear_act, hipStream_t s)
+{
+    int rc = launch_ref_window(h, nullptr, t0, h->sxr, h->sur, s);
+    if (rc) return rc;
+    NDP_HIP(h, hipMemcpyAsync(h->dX, h->sxr, nxs(h) * 8, hipMemcpyDefault, s));
+    NDP_HIP(h, hipMemcpyAsync(h->dU, h->sur, nus(h) * 8, hipMemcpyDefault, s));
+    if (clear_act) NDP_HIP(h, hipMemsetAsync(h->dAct, 0, act_bytes(h), s));
+    return 0;
+}
+
 // ---- f4: closed-loop rollout, everything enqueued back to back on one stream, nothing returns to the host in between
 int ndp_rollout_device(ndp_handle *h, int ticks, double t0, double dt_tick, int substeps, void *d_x, void *d_log, void *stream)
 {
@@ -642,10 +655,8 @@ int ndp_rollout_device(ndp_handle *h, int ticks, double t0, double dt_tick, int 
     if (h->cfg.use_fd) { h->err = "ndp_rollout_device: the rollout drives the NMPC model (use_fd = 0)"; return -8; }
     const size_t B = h->cfg.batch;
     double *x = (double *)d_x, *log = (double *)d_log;
-    int rc = launch_ref_window(h, nullptr, t0, h->sxr, h->sur, s);     // reset(xr, ur) at the first tick's reference
+    int rc = rollout_head(h, t0, false, s);
     if (rc) return rc;
-    NDP_HIP(h, hipMemcpyAsync(h->dX, h->sxr, nxs(h) * 8, hipMemcpyDefault, s));
-    NDP_HIP(h, hipMemcpyAsync(h->dU, h->sur, nus(h) * 8, hipMemcpyDefault, s));
     for (int k = 0; k < ticks; ++k) {
         if (k > 0 && (rc = launch_ref_window(h, nullptr, t0 + k * dt_tick, h->sxr, h->sur, s))) return rc;
         if ((rc = launch_rti(h, x, h->sxr, h->sur, nullptr, h->su0, nullptr, s))) return rc;
@@ -655,37 +666,46 @@ int ndp_rollout_device(ndp_handle *h, int ticks, double t0, double dt_tick, int 
     return g.noted(0);
 }
 
-// ---- f4: closed-loop FORMATION rollout: the rollout above with the downwash acting on the plant.  Per tick: reference window -> the force the
-// neighbour's actual state puts on the actual vehicle, + the ego xy (plant_force_kernel, from the states BEFORE the tick's plant step) ->
-// control step (NDP_FORM_COMPENSATE: the fused step of ndp_step_device_ex against this tick's reference windows of the whole batch; else
-// the plain step, blind) -> plant step with that force, held over the tick.  u0 and the force are written straight into their log slots
-// when those are given.  Refused (-8) before anything is enqueued.
-int ndp_rollout_formation_device(ndp_handle *h, int ticks, double t0, double dt_tick, int substeps, const void *d_other_index, int flags,
-                                 double plant_scale, void *d_x, void *d_log, void *d_log_u, void *d_log_f, void *d_worst_status, void *stream)
+// ---- f4: closed-loop FORMATION rollout: the rollout above with the downwash acting on the plant, one body for ndp_rollout_formation_device
+// (multi false: other_index int32[B], K not read) and ndp_rollout_formation_multi_device (multi: K neighbours per vehicle, forces superposed,
+// other_index int32[B][K]), `who` the entry's name.  Per tick: reference window -> the force the neighbours' actual states put on the actual
+// vehicle, + the ego xy (launch_plant_force, from the states BEFORE the tick's plant step) -> control step -> plant step with that force,
+// held over the tick.  The control step with NDP_FORM_COMPENSATE and an index:
+//   single  the fused step of ndp_step_device_ex against this tick's reference windows of the whole batch
+//   multi   mlp_multi_kernel on those windows into the handle's force buffer, then the step of ndp_step_device with that force as its
+//           external force (no control-step kernel knows about K)
+// else the plain step, blind.  u0 and the force are written straight into their log slots when those are given.  Refused (-2: K, multi only;
+// then -8) before anything is enqueued.
+static int rollout_formation(ndp_handle *h, const char *who, bool multi, int ticks, double t0, double dt_tick, int substeps,
+                             const void *d_other_index, int K, int flags, double plant_scale, void *d_x, void *d_log, void *d_log_u,
+                             void *d_log_f, void *d_worst_status, void *stream)
 {
-    Entry g(h, ticks >= 1 && substeps >= 1 && d_x && !(flags & ~(NDP_FORM_GATE | NDP_FORM_COMPENSATE)), stream, "ndp_rollout_formation_device");
+    Entry g(h, ticks >= 1 && substeps >= 1 && d_x && !(flags & ~(NDP_FORM_GATE | NDP_FORM_COMPENSATE)), stream, who);
     if (g.rc) return g.rc;
     hipStream_t s = g.s;
     const bool comp = (flags & NDP_FORM_COMPENSATE) != 0, gate = (flags & NDP_FORM_GATE) != 0;
     const int *idx = (const int *)d_other_index;
-    if (comp && !h->cfg.use_fd) { h->err = "ndp_rollout_formation_device: NDP_FORM_COMPENSATE needs use_fd = 1 (NDP model)"; return -8; }
-    if (idx && !h->have_mlp) { h->err = "ndp_rollout_formation_device: ndp_set_mlp_weights was never called (the force on the plant is the network's)"; return -8; }
-    if (!h->dTraj) { h->err = "ndp_rollout_formation_device: ndp_ref_set_trajectory was never called"; return -8; }
+    int rc;
+    if (multi && (rc = check_neigh(h, who, K))) return rc;      // (also without an index: an index array of K = 0 may well be NULL)
+    const char *why = nullptr;
+    if (comp && !h->cfg.use_fd) why = ": NDP_FORM_COMPENSATE needs use_fd = 1 (NDP model)";
+    else if (idx && !h->have_mlp) why = ": ndp_set_mlp_weights was never called (the force on the plant is the network's)";
+    else if (!h->dTraj) why = ": ndp_ref_set_trajectory was never called";
+    if (why) { h->err = std::string(who) + why; return -8; }
     const size_t B = h->cfg.batch;
     double *x = (double *)d_x, *log = (double *)d_log, *log_u = (double *)d_log_u, *log_f = (double *)d_log_f;
     double *xy = h->sThr + 3 * B;                                      // sThr: f [B][3] | xy [B][2]
-    Neigh nb;
+    Neigh nb;                                                          // (the single form's fused step)
     nb.other = h->sxr; nb.index = idx; nb.ego_xy = gate ? xy : nullptr;
-    int rc = launch_ref_window(h, nullptr, t0, h->sxr, h->sur, s);     // reset(xr, ur) at the first tick's reference
-    if (rc) return rc;
-    NDP_HIP(h, hipMemcpyAsync(h->dX, h->sxr, nxs(h) * 8, hipMemcpyDefault, s));
-    NDP_HIP(h, hipMemcpyAsync(h->dU, h->sur, nus(h) * 8, hipMemcpyDefault, s));
-    NDP_HIP(h, hipMemsetAsync(h->dAct, 0, act_bytes(h), s));
+    if ((rc = rollout_head(h, t0, true, s))) return rc;
     for (int k = 0; k < ticks; ++k) {
         double *f = log_f ? log_f + (size_t)k * B * 3 : h->sThr, *u = log_u ? log_u + (size_t)k * B * NU : h->su0;
         if (k > 0 && (rc = launch_ref_window(h, nullptr, t0 + k * dt_tick, h->sxr, h->sur, s))) return rc;
-        if ((rc = launch_plant_force(h, x, idx, gate, plant_scale, f, xy, s))) return rc;
-        if (comp && idx) rc = enqueue_step(h, x, h->sxr, h->sur, nullptr, nb, u, nullptr, s);
+        if ((rc = launch_plant_force(h, x, idx, multi ? K : 0, gate, plant_scale, f, xy, s))) return rc;
+        if (comp && idx && multi) {
+            if ((rc = launch_mlp_multi(h, h->sxr, NX, idx, K, h->sxr, nb.ego_xy, h->dForce, s))) return rc;
+            rc = enqueue_step(h, x, h->sxr, h->sur, h->dForce, Neigh{}, u, nullptr, s);
+        } else if (comp && idx) rc = enqueue_step(h, x, h->sxr, h->sur, nullptr, nb, u, nullptr, s);
         else rc = launch_rti(h, x, h->sxr, h->sur, nullptr, u, nullptr, s);
         if (rc) return rc;
         if (d_worst_status) {
@@ -698,49 +718,19 @@ int ndp_rollout_formation_device(ndp_handle *h, int ticks, double t0, double dt_
     return g.noted(0);
 }
 
-// ---- f4: the formation rollout with K neighbours per vehicle, forces superposed (other_index int32[B][K]).  Per tick: reference window ->
-// plant_force_multi_kernel (the summed force from the states BEFORE the tick's plant step, + the ego xy) -> NDP_FORM_COMPENSATE:
-// mlp_multi_kernel on this tick's reference windows of the whole batch into the handle's force buffer, then the control step with that force
-// as its external force (the step of ndp_step_device with d_f: no control-step kernel knows about K); else the plain step, blind -> plant
-// step with the plant force, held over the tick.  Refused (-8 / -2) before anything is enqueued.
+int ndp_rollout_formation_device(ndp_handle *h, int ticks, double t0, double dt_tick, int substeps, const void *d_other_index, int flags,
+                                 double plant_scale, void *d_x, void *d_log, void *d_log_u, void *d_log_f, void *d_worst_status, void *stream)
+{
+    return rollout_formation(h, "ndp_rollout_formation_device", false, ticks, t0, dt_tick, substeps, d_other_index, 0, flags, plant_scale, d_x,
+                             d_log, d_log_u, d_log_f, d_worst_status, stream);
+}
+
 int ndp_rollout_formation_multi_device(ndp_handle *h, int ticks, double t0, double dt_tick, int substeps, const void *d_other_index, int K,
                                        int flags, double plant_scale, void *d_x, void *d_log, void *d_log_u, void *d_log_f,
                                        void *d_worst_status, void *stream)
 {
-    Entry g(h, ticks >= 1 && substeps >= 1 && d_x && !(flags & ~(NDP_FORM_GATE | NDP_FORM_COMPENSATE)), stream, "ndp_rollout_formation_multi_device");
-    if (g.rc) return g.rc;
-    hipStream_t s = g.s;
-    const bool comp = (flags & NDP_FORM_COMPENSATE) != 0, gate = (flags & NDP_FORM_GATE) != 0;
-    const int *idx = (const int *)d_other_index;
-    int rc = check_neigh(h, "ndp_rollout_formation_multi_device", K);      // (also without an index: an index array of K = 0 may well be NULL)
-    if (rc) return rc;
-    if (comp && !h->cfg.use_fd) { h->err = "ndp_rollout_formation_multi_device: NDP_FORM_COMPENSATE needs use_fd = 1 (NDP model)"; return -8; }
-    if (idx && !h->have_mlp) { h->err = "ndp_rollout_formation_multi_device: ndp_set_mlp_weights was never called (the force on the plant is the network's)"; return -8; }
-    if (!h->dTraj) { h->err = "ndp_rollout_formation_multi_device: ndp_ref_set_trajectory was never called"; return -8; }
-    const size_t B = h->cfg.batch;
-    double *x = (double *)d_x, *log = (double *)d_log, *log_u = (double *)d_log_u, *log_f = (double *)d_log_f;
-    double *xy = h->sThr + 3 * B;                                      // sThr: f [B][3] | xy [B][2]
-    if ((rc = launch_ref_window(h, nullptr, t0, h->sxr, h->sur, s))) return rc;     // reset(xr, ur) at the first tick's reference
-    NDP_HIP(h, hipMemcpyAsync(h->dX, h->sxr, nxs(h) * 8, hipMemcpyDefault, s));
-    NDP_HIP(h, hipMemcpyAsync(h->dU, h->sur, nus(h) * 8, hipMemcpyDefault, s));
-    NDP_HIP(h, hipMemsetAsync(h->dAct, 0, act_bytes(h), s));
-    for (int k = 0; k < ticks; ++k) {
-        double *f = log_f ? log_f + (size_t)k * B * 3 : h->sThr, *u = log_u ? log_u + (size_t)k * B * NU : h->su0;
-        if (k > 0 && (rc = launch_ref_window(h, nullptr, t0 + k * dt_tick, h->sxr, h->sur, s))) return rc;
-        if ((rc = launch_plant_force_multi(h, x, idx, K, gate, plant_scale, f, xy, s))) return rc;
-        if (comp && idx) {
-            if ((rc = launch_mlp_multi(h, h->sxr, NX, idx, K, h->sxr, gate ? xy : nullptr, h->dForce, s))) return rc;
-            rc = enqueue_step(h, x, h->sxr, h->sur, h->dForce, Neigh{}, u, nullptr, s);
-        } else rc = launch_rti(h, x, h->sxr, h->sur, nullptr, u, nullptr, s);
-        if (rc) return rc;
-        if (d_worst_status) {
-            hipLaunchKernelGGL(status_max_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, h->lastStatus, (int *)d_worst_status, k == 0, (int)B);
-            NDP_HIP(h, hipGetLastError());
-        }
-        if ((rc = launch_plant(h, x, u, f, dt_tick, substeps, s))) return rc;
-        if (log) NDP_HIP(h, hipMemcpyAsync(log + (size_t)k * B * NX, x, B * NX * 8, hipMemcpyDeviceToDevice, s));
-    }
-    return g.noted(0);
+    return rollout_formation(h, "ndp_rollout_formation_multi_device", true, ticks, t0, dt_tick, substeps, d_other_index, K, flags, plant_scale,
+                             d_x, d_log, d_log_u, d_log_f, d_worst_status, stream);
 }
 
 }  // extern "C"
