@@ -712,6 +712,72 @@ int ndp_closed_loop_jvp_device(ndp_handle *h, int ticks, double dt, int substeps
                                const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf, const void *d_tfp, void *d_dxs,
                                void *d_dus, void *d_dXs, void *d_dUs, void *d_status_check, void *stream);
 
+/* ---- the closed loop of a FORMATION in one call per direction: ndp_closed_loop_device with the force on the plant made inside the loop
+ * from the neighbours' actual states (ndp_plant_force_multi_device), and its reverse mode across the vehicles.  The controller keeps
+ * seeing a given d_f (the "ext" form): the step and its derivative kernels run unchanged.  Device pointers only.
+ * ndp_closed_loop_formation_config(h, other_index, K): other_index a HOST array int32 [B][K], 1 <= K <= NDP_MAX_NEIGH (else -2 with a
+ *   reason); NULL clears the configuration (K not read).  Synchronous set-up, as ndp_tick_config: waits for the handle's work, then keeps
+ *   on the handle a device copy of the index and its reverse lists offset int32 [B+1], edge int32 [offset[B]]: vehicle v's list
+ *   edge[offset[v] .. offset[v+1]) holds e = w K + j for every slot with other_index[w][j] == v, in ascending e.  Empty slots (o < 0 or
+ *   o >= B) and self slots (o == w: their two shares cancel exactly) are in no list.  The lists are built on the host.
+ * ndp_plant_force_scatter_device(h, d_gz, d_gx, stream): ndp_plant_force_multi_vjp_device's g_z [B][K][6] fp64 (K the configured one) onto
+ *   the states, d_gx [B][10] fp64, OVERWRITTEN.  One lane per vehicle, a gather, no atomics:
+ *     d_gx[v][0:6] = (sum over v's list, in list order, of gz[e]) - (sum in slot order of gz[v K + j] over v's own slots that are neither
+ *     empty nor self); each of the two sums starts from its first term as it is (an empty sum is +0), then one subtraction.
+ *   Columns 6..9 are exactly 0.  -1: NULL handle, d_gz or d_gx; -2: nothing configured.
+ * ndp_closed_loop_formation_device: ndp_closed_loop_device, except that the plant force is an OUTPUT log d_fps [ticks][B][3] fp64
+ *   (required).  Per tick: fps[k] = ndp_plant_force_multi_device(x_k, the configured index, K, gate, plant_scale) from the states of that
+ *   tick before any of them moves (ndp_rollout_formation_multi_device's rule); the step from x_k with xr[k], ur[k], f[k]; the link with
+ *   fps[k] held over the tick.  Three launches per tick (the force, the step, the link), no new kernel.  Everything it writes -- xs, us,
+ *   fps, Xs, the status words, the tape, the engine's iterate and kept sets -- is BIT-EQUAL to the host loop of
+ *   ndp_plant_force_multi_device, ndp_step_device and ndp_plant_step_device.  The tape's layout and ndp_closed_loop_tape_bytes are those of
+ *   ndp_closed_loop_device.  With every slot empty it is ndp_closed_loop_device with d_fp NULL, bit for bit, and fps is exact zeros.
+ *   -1: NULL handle, d_x0, d_xr, d_ur, d_xs, d_us or d_fps.  -2, nothing enqueued: ndp_closed_loop_device's refusals, then nothing
+ *   configured.  -6: ndp_set_mlp_weights was never called (as the force call).
+ * ndp_closed_loop_formation_vjp_device: reverse mode of that flight for
+ *     L = sum_k <gxs[k], x_{k+1}> + <gus[k], u0_k> + <gXs[k], X_k> + <gfps[k], fps[k]>
+ *   -- ndp_closed_loop_vjp_device's PARTIAL derivative (linearisation points and final sets held fixed), the force's gates held fixed too
+ *   (ndp_plant_force_multi_vjp_device).  Inputs as the forward took them, its d_xs, d_us, d_fps and d_tape (required); upstreams NULL = 0,
+ *   not all four NULL; outputs each NULL = not written, not all NULL: d_gx0, d_gxr, d_gur, d_gf, d_gmodel as ndp_closed_loop_vjp_device's
+ *   (column 15 of d_gmodel: -(1/m) sum_k <gfp_k, fps[k]> with gfp_k the plant's own share, without gfps[k]), d_gw [NDP_MLP_NPARAM] fp32,
+ *   OVERWRITTEN: the gradient in the network's weights.  d_gfp is gone: its role is taken by d_gfps (upstream) and d_gw.
+ *   Tick by tick from the last, four launches each (the link; the force's adjoint and, with d_gw, its reduction; the step's adjoint) and
+ *   one behind tick 0:
+ *     lambda = gxs[k] + ((gx_p + gx0) + gx_f)    the three of tick k + 1; gx_f = the gather of ndp_plant_force_scatter_device over tick
+ *                                                k + 1's g_z, formed inside the link's launch; a vehicle that hears nobody and is heard by
+ *                                                nobody adds no gx_f at all; nothing at the last tick
+ *     (gx_p, gu_p, gfp_k) = the plant tick's adjoint at (x_k, u0_k, fps[k]) on lambda, gF_k = gfps[k] + gfp_k
+ *     (g_z, g_w of the tick) = ndp_plant_force_multi_vjp_device at x_k on gF_k
+ *     (gx0, gxr[k], gur[k], gf[k]) = the step's adjoint, as in ndp_closed_loop_vjp_device
+ *     d_gx0 = (gx_p + gx0) + gx_f of tick 0.
+ *   d_gw: the ticks' fp32 g_w are added into an fp64 accumulator, last tick first (the first as it is), by spare workgroups of the next
+ *   link's launch; the tail launch rounds the sum once to fp32.  No atomics: two calls are bit-identical.
+ *   With every slot empty every output is bit-equal to ndp_closed_loop_vjp_device with d_fp = zeros, and d_gw is exact zeros.
+ *   The engine's iterate, kept sets and the tape are never written; an output does not depend on which others are asked for; the
+ *   workspaces are the handle's (first call), shared with the other derivative calls: calls on one handle are ordered.
+ *   Failed steps: a nonzero recomputed status in tick k of vehicle v gives NaN in v's outputs of ticks <= k, as in
+ *   ndp_closed_loop_vjp_device; through the coupling the NaN then goes wherever the arithmetic carries it (v's g_z of tick k reaches its
+ *   neighbours' lambda of tick k - 1).  A vehicle in a component of the index graph with no failed member is unaffected, bit for bit.
+ *   A vehicle that hears a non-finite relative state (x[o] - x[v])[0:6] through an open slot flew under a meaningless force -- the
+ *   network's ReLU swallows a NaN, so fps[k] may well be finite -- and its gF_k is made NaN.  d_gw leaves out the vehicles whose gF is
+ *   not finite (the force adjoint's rule).  With the gate OFF a triple one of whose members has a NaN state at every tick therefore adds
+ *   nothing to d_gw: it equals the call with that triple's upstreams zeroed.  With the gate ON this does NOT hold: a NaN position closes
+ *   every slot that names the vehicle (the comparison is false), its neighbours fly on without hearing it, as in the forward, and keep
+ *   feeding d_gw.  Per-tick chains of ndp_plant_force_multi_vjp_device do not have the rule: behind a failed vehicle their g_w keeps the
+ *   rows of its neighbours' other slots, so the two routes' g_w differ there (and only there).  What a vehicle's ticks behind its last
+ *   failed one gave stays in.  d_status_check tells.
+ *   -1, -2, -6 as the forward; -2 also: the adjoint's own refusals, d_tape NULL, no upstream, no output. */
+int ndp_closed_loop_formation_config(ndp_handle *h, const int32_t *other_index, int K);
+int ndp_plant_force_scatter_device(ndp_handle *h, const void *d_gz, void *d_gx, void *stream);
+int ndp_closed_loop_formation_device(ndp_handle *h, int ticks, double dt, int substeps, int gate, double plant_scale, const void *d_x0,
+                                     const void *d_xr, const void *d_ur, const void *d_f, void *d_xs, void *d_us, void *d_fps, void *d_Xs,
+                                     void *d_status, void *d_tape, void *stream);
+int ndp_closed_loop_formation_vjp_device(ndp_handle *h, int ticks, double dt, int substeps, int gate, double plant_scale, const void *d_x0,
+                                         const void *d_xr, const void *d_ur, const void *d_f, const void *d_xs, const void *d_us,
+                                         const void *d_fps, const void *d_tape, const void *d_gxs, const void *d_gus, const void *d_gXs,
+                                         const void *d_gfps, void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_gw, void *d_gmodel,
+                                         void *d_status_check, void *stream);
+
 /* ---- f4, the formation form (plant = a1 dynamics + downwash model): the downwash force the neighbour's ACTUAL state
  * puts on the ACTUAL vehicle, and the closed loop around it -- the experiment the downwash prediction is for (the reference has no
  * simulator; the force model is its own network, dnwash_nn_est/downwash_nn.py:22-28, behind the gate of ndp_nmpc_leader_node.py:65-68).

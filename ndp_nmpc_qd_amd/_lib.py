@@ -71,6 +71,8 @@ EXPORTS = [
     "ndp_plant_rollout_device", "ndp_plant_rollout_vjp_device", "ndp_plant_rollout_jvp_device",
     "ndp_plant_force_vjp_device", "ndp_plant_force_multi_vjp_device", "ndp_plant_force_jvp_device", "ndp_plant_force_multi_jvp_device",
     "ndp_closed_loop_tape_bytes", "ndp_closed_loop_device", "ndp_closed_loop_vjp_device", "ndp_closed_loop_jvp_device",
+    "ndp_closed_loop_formation_config", "ndp_plant_force_scatter_device", "ndp_closed_loop_formation_device",
+    "ndp_closed_loop_formation_vjp_device",
 ]
 
 _lib = None
@@ -244,6 +246,10 @@ def load():
     lib.ndp_closed_loop_device.argtypes = [vp, C.c_int, C.c_double, C.c_int] + [vp] * 11
     lib.ndp_closed_loop_vjp_device.argtypes = [vp, C.c_int, C.c_double, C.c_int] + [vp] * 19
     lib.ndp_closed_loop_jvp_device.argtypes = [vp, C.c_int, C.c_double, C.c_int] + [vp] * 8 + [C.c_int] + [vp] * 11
+    lib.ndp_closed_loop_formation_config.argtypes = [vp, vp, C.c_int]
+    lib.ndp_plant_force_scatter_device.argtypes = [vp] * 4
+    lib.ndp_closed_loop_formation_device.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double] + [vp] * 11
+    lib.ndp_closed_loop_formation_vjp_device.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double] + [vp] * 20
     _lib = lib
     return lib
 

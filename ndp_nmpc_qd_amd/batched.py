@@ -67,6 +67,7 @@ class BatchedNMPC:
         if rc != 0:
             self._h = None
             raise NdpError(f"ndp_create failed ({rc}): {self._lib.ndp_last_error(None).decode()}")
+        self._form_K = self._form_index = None      # closed_loop_formation_config: what is configured (K, a host copy of the index)
         if load_mlp is None:
             load_mlp = self.disturbance
         if load_mlp:
@@ -565,6 +566,67 @@ class BatchedNMPC:
             d(dxs, torch.float64, (K, B, T, 10)), d(dus, torch.float64, (K, B, T, 4)), d(dXs, torch.float64, (K, B, T, N + 1, 10)),
             d(dUs, torch.float64, (K, B, T, N, 4)), d(status_check, torch.int32, (K, B)), self._stream(stream)),
             "ndp_closed_loop_jvp_device")
+
+    # ---- the closed loop of a formation: the plant force made inside the loop from the configured index, and its reverse mode
+    def closed_loop_formation_config(self, other_index):
+        """Configures the formation of closed_loop_formation_device (ndp_closed_loop_formation_config; include/ndp_nmpc.h): other_index a
+        HOST int32 [B,K] array, 1 <= K <= 8 (< 0 or >= B: an empty slot); None clears it.  Synchronous: the handle keeps a device copy of
+        the index and its reverse lists (who hears vehicle v), built on the host."""
+        self._form_K = self._form_index = None
+        if other_index is None:
+            self._check(self._lib.ndp_closed_loop_formation_config(self._h, None, 0), "ndp_closed_loop_formation_config")
+            return
+        oi, K = self._index_multi(other_index)
+        self._check(self._lib.ndp_closed_loop_formation_config(self._h, _lib.ptr(oi), K), "ndp_closed_loop_formation_config")
+        self._form_K, self._form_index = K, oi.copy()       # (what is configured: torch_layer configures only what is not)
+
+    def plant_force_scatter_device(self, gz, gx, stream=None):
+        """Enqueues the scatter of plant_force_multi_vjp_device's gz[B,K,6] (K the configured one) onto the states, gx[B,10] float64,
+        overwritten (ndp_plant_force_scatter_device): per vehicle the sum over the slots that hear it, in ascending slot number, minus the
+        sum over its own slots; empty and self slots left out; columns 6..9 exactly 0.  A gather: no atomics, two calls bit-identical."""
+        import torch
+        # (nothing configured: any K lets the call through to the library, which refuses it with its reason)
+        K = self._form_K or (gz.shape[1] if isinstance(gz, torch.Tensor) and gz.dim() == 3 else 1)
+        self._check(self._lib.ndp_plant_force_scatter_device(
+            self._h, self._dptr(gz, torch.float64, (self.B, K, 6)), self._dptr(gx, torch.float64, (self.B, 10)), self._stream(stream)),
+            "ndp_plant_force_scatter_device")
+
+    def closed_loop_formation_device(self, x0, xr, ur, xs, us, fps, f=None, Xs=None, status=None, tape=None, gate=True, plant_scale=1.0,
+                                     dt=CP.ts_nmpc, substeps=4, stream=None):
+        """closed_loop_device with the force on the plant made inside the loop (ndp_closed_loop_formation_device; include/ndp_nmpc.h): per
+        tick fps[k] = plant_force_multi_device(x_k, the configured index, gate, plant_scale), the control step with xr[k], ur[k] and the
+        given f[k], the plant tick with fps[k].  fps[ticks,B,3] float64 is an output, required; the others as closed_loop_device.
+        Everything written is bit-equal to the loop of plant_force_multi_device, update_device and ndp_plant_step_device."""
+        import torch
+        K, args = self._closed_loop_args("closed_loop_formation_device", x0, xr, ur, f, None)
+        B, N, d = self.B, self.N, self._dptr
+        self._torch_default_wait(stream)
+        self._check(self._lib.ndp_closed_loop_formation_device(
+            self._h, K, float(dt), int(substeps), 1 if gate else 0, float(plant_scale), *args[:4], d(xs, torch.float64, (K, B, 10)),
+            d(us, torch.float64, (K, B, 4)), d(fps, torch.float64, (K, B, 3)), d(Xs, torch.float64, (K, B, N + 1, 10)),
+            d(status, torch.int32, (K, B)), d(tape, torch.uint8, (K, self._closed_loop_slot_bytes())), self._stream(stream)),
+            "ndp_closed_loop_formation_device")
+
+    def closed_loop_formation_vjp_device(self, x0, xr, ur, xs, us, fps, tape, f=None, gxs=None, gus=None, gXs=None, gfps=None, gx0=None,
+                                         gxr=None, gur=None, gf=None, gw=None, gmodel=None, status_check=None, gate=True, plant_scale=1.0,
+                                         dt=CP.ts_nmpc, substeps=4, stream=None):
+        """Enqueues the reverse mode of closed_loop_formation_device on `stream` (ndp_closed_loop_formation_vjp_device) for
+        L = sum_k <gxs[k], x_{k+1}> + <gus[k], u0_k> + <gXs[k], X_k> + <gfps[k], fps[k]>: the inputs as the forward took them, its xs, us,
+        fps and tape; upstreams None = 0, not all None; outputs as closed_loop_vjp_device's, with gw[17859] float32 (overwritten: the
+        gradient in the network's weights, summed over the ticks in float64 and rounded once) in place of gfp.  Linearisation points, final
+        sets and gates are held fixed; gradients cross the vehicles through a gather on the device, no atomics, two calls bit-identical."""
+        import torch
+        K, args = self._closed_loop_args("closed_loop_formation_vjp_device", x0, xr, ur, f, None)
+        B, N, d = self.B, self.N, self._dptr
+        self._torch_default_wait(stream)
+        self._check(self._lib.ndp_closed_loop_formation_vjp_device(
+            self._h, K, float(dt), int(substeps), 1 if gate else 0, float(plant_scale), *args[:4], d(xs, torch.float64, (K, B, 10)),
+            d(us, torch.float64, (K, B, 4)), d(fps, torch.float64, (K, B, 3)), d(tape, torch.uint8, (K, self._closed_loop_slot_bytes())),
+            d(gxs, torch.float64, (K, B, 10)), d(gus, torch.float64, (K, B, 4)), d(gXs, torch.float64, (K, B, N + 1, 10)),
+            d(gfps, torch.float64, (K, B, 3)), d(gx0, torch.float64, (B, 10)), d(gxr, torch.float64, (K, B, N + 1, 10)),
+            d(gur, torch.float64, (K, B, N, 4)), d(gf, torch.float64, (K, B, N + 1, 3)), d(gw, torch.float32, (_lib.MLP_NPARAM,)),
+            d(gmodel, torch.float64, (B, 16)), d(status_check, torch.int32, (K, B)), self._stream(stream)),
+            "ndp_closed_loop_formation_vjp_device")
 
     @staticmethod
     def _plant_ticks(u, who):

@@ -2,6 +2,15 @@
 // one call: ndp_closed_loop_device (control step -> plant tick -> the next tick's x0, `ticks` times, everything enqueued on one stream),
 // ndp_closed_loop_vjp_device (the gradient of a loss on that flight in x_0, the windows, the forces and the controller's own numbers) and
 // ndp_closed_loop_jvp_device (the tangents of that flight along directions of x_0, the windows and the forces).
+// And the FORMATION's form of the first two, with the force on the plant made inside the loop from the vehicles' actual states:
+// ndp_closed_loop_formation_config (the index and its reverse lists, built on the host), ndp_closed_loop_formation_device (the existing
+// force launch in front of each step; no new kernel), ndp_closed_loop_formation_vjp_device and ndp_plant_force_scatter_device:
+//   closed_loop_formation_rev_link_kernel  closed_loop_rev_link_kernel's lane body (closed_loop_rev_lane.inc, shared as text) with two
+//                                hooks: gx_f -- the gather of tick k + 1's g_z over the vehicle's list and its own slots (cl_gather) --
+//                                into lambda, and gF_k = gfps[k] + gfp_k out to the force's adjoint (plant_force_vjp_kernel, unchanged),
+//                                which runs between the link and the step's adjoint; spare workgroups add tick k + 1's fp32 g_w into an
+//                                fp64 accumulator, the tail launch rounds it once
+//   closed_loop_scatter_kernel   cl_gather alone: g_z per slot onto the states, one lane per vehicle, no atomics
 //
 // The control step and its derivatives are the existing kernels, launched unchanged (enqueue_step; recompute_on_workspace with rti_vjp_kernel
 // / rti_wvjp_kernel / rti_jvp_kernel).  What is new is everything BETWEEN two of them, one launch per tick and direction:
@@ -22,7 +31,8 @@
 // One lane per vehicle in 64-lane workgroups for the plant (plant_deriv.hip's shape: a long serial fp64 chain per lane, spread over many
 // CUs); the copies run on further workgroups of the same launch, grid-stride.  No LDS, no atomics, no scratch.
 // Host side: ClView (tick k's slices, its tape slot, a link's two copies), cl_check (the refusals of all three calls, around plant_deriv.hip's
-// plant_seq_check), cl_deriv_begin (what the two derivative calls share before they enqueue); the three launch loops read top to bottom.
+// plant_seq_check), cl_deriv_begin (what the derivative calls share before they enqueue); one body per direction for the ext form and the
+// formation's (cl_forward, cl_reverse: a ClFormation or null), the forward mode's launch loop in its entry; each reads top to bottom.
 #include <hip/hip_runtime.h>
 
 #include "../../include/ndp_nmpc.h"
@@ -30,6 +40,7 @@
 #include "plant_dyn.hpp"
 #include "plant_adj.hpp"
 #include "plant_tan.hpp"
+#include "mlp_common.hpp"
 
 namespace ndp {
 
@@ -70,6 +81,43 @@ struct ClRev {
     double *gfp_prev;               // gfp[k + 1] (or null) and the plant's mass share become NaN -- the plant's adjoint alone would not
                                     // make them so at the vehicle's LAST failed tick (the force's gradient does not read the state)
     ClCopy cp[2];                   // tape slot k -> the adjoint's workspace: iterate, kept set
+};
+
+// The formation's reverse lists (ndp_closed_loop_formation_config): vehicle v is heard through the edges edge[offset[v] .. offset[v+1]),
+// e = w K + j with index[w][j] == v, ascending; empty (o < 0 or o >= B) and self (o == w) slots are in no list
+struct ClGather {
+    const int *index, *offset, *edge;   // [B][K], [B+1], [offset[B]]
+    const double *gz;                   // [B][K][6] the force adjoint's gradient per slot, or null: nothing to gather
+    int B, K;
+};
+
+struct ClForm {                     // the formation: what the force's adjoint hands over, and what it is handed
+    ClGather g;                     // tick k + 1's g_z (the force adjoint has run)
+    const double *gfps;             // [B][3] the upstream of fps[k], or null
+    double *gF;                     // out [B][3]: gfps[k] + gfp_k, the upstream of tick k's force adjoint
+    const double *x;                // x_k [B][10], and the gate as the force took it: a vehicle that hears a non-finite state through an
+    int gate;                       // open slot gets gF = NaN (ClForm::force)
+    double r2;
+    __device__ __forceinline__ void incoming(int v, double *lam) const;
+    __device__ __forceinline__ void force(int v, double g0, double g1, double g2) const;
+};
+
+struct ClAcc {                      // the weight gradient over the ticks, last tick first: acc = gw (first) or acc + gw, in fp64
+    const float *gw;                // [NDP_MLP_NPARAM] tick k + 1's, or null: none
+    double *acc;
+    float *out;                     // the tail: the sum rounded once, or null
+    int first;
+};
+
+struct ClRevF {
+    ClRev r;
+    ClForm f;
+    ClAcc acc;
+};
+
+struct ClScatter {
+    ClGather g;
+    double *gx;                     // out [B][10]
 };
 
 struct ClTan {
@@ -126,73 +174,113 @@ __global__ __launch_bounds__(CL_LANES) void closed_loop_rev_link_kernel(ClRev a)
     }
     const int v = (int)(blockIdx.x * CL_LANES + threadIdx.x);
     if (v >= a.p.B) return;
-    double lam[10], gk[10];
+#define CL_REV_INCOMING(v, lam)
+#define CL_REV_FORCE(v, g0, g1, g2)
+#include "closed_loop_rev_lane.inc"
+#undef CL_REV_INCOMING
+#undef CL_REV_FORCE
+}
+
+// gx_f of vehicle v, the first six columns: (the sum over v's list, in list order, of gz[e]) - (the sum in slot order of v's own slots
+// that are neither empty nor self).  Each sum starts from its first term as it is (an empty one is +0), then one subtraction.  A gather:
+// every lane reads, none writes another's row.  False: v hears nobody and nobody hears v (out is +0).
+__device__ __forceinline__ bool cl_gather(const ClGather &c, int v, double *out)
+{
+    double in[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, own[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    bool any_in = false, any_own = false;
+    const int e1 = c.offset[v + 1];
+    for (int q = c.offset[v]; q < e1; ++q) {
+        const double *g = c.gz + (size_t)c.edge[q] * 6;
 #pragma unroll
-    for (int i = 0; i < 10; ++i) lam[i] = 0.0;
-    if (a.c_p) {
-        plant_ld_row<5>(a.c_p + (size_t)v * 10, lam);
-        plant_ld_row<5>(a.c_s + (size_t)v * 10, gk);
-#pragma unroll
-        for (int i = 0; i < 10; ++i) lam[i] = lam[i] + gk[i];
+        for (int i = 0; i < 6; ++i) in[i] = any_in ? in[i] + g[i] : g[i];
+        any_in = true;
     }
-    double p15 = 0.0;
-    const bool bad = a.st_prev && a.st_prev[v] != 0;
-    if (bad && a.gfp_prev) {
-        const double nan = __builtin_nan("");
-        a.gfp_prev[(size_t)v * 3] = nan; a.gfp_prev[(size_t)v * 3 + 1] = nan; a.gfp_prev[(size_t)v * 3 + 2] = nan;
+    for (int j = 0; j < c.K; ++j) {
+        const int o = c.index[(size_t)v * c.K + j];
+        if (o < 0 || o >= c.B || o == v) continue;
+        const double *g = c.gz + ((size_t)v * c.K + j) * 6;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) own[i] = any_own ? own[i] + g[i] : g[i];
+        any_own = true;
     }
-    if (a.tail) {
-        if (a.gx0) plant_st_row<5>(a.gx0 + (size_t)v * 10, lam);
-    } else {
-        double xin[10], y[10], uv[4], acc[3], guv[4] = {0.0, 0.0, 0.0, 0.0}, gacc[3] = {0.0, 0.0, 0.0};
-        plant_ld_row<5>(a.xin + (size_t)v * 10, xin);
-        plant_ld_row<2>(a.u + (size_t)v * 4, uv);
-        if (a.gxs) {
-            plant_ld_row<5>(a.gxs + (size_t)v * 10, gk);
 #pragma unroll
-            for (int i = 0; i < 10; ++i) lam[i] = gk[i] + lam[i];
-        }
-        plant_acc(a.fp, (size_t)v * 3, a.p.inv_mass, a.p.g, acc);
+    for (int i = 0; i < 6; ++i) out[i] = in[i] - own[i];
+    return any_in || any_own;
+}
+
+// lambda's share through the neighbours: (gx_p + gx0) + gx_f.  A vehicle outside every list and with no slot of its own adds nothing
+// (its lambda is the "ext" form's, bit for bit)
+__device__ __forceinline__ void ClForm::incoming(int v, double *lam) const
+{
+    if (!g.gz) return;
+    double gxf[6];
+    if (!cl_gather(g, v, gxf)) return;
 #pragma unroll
-        for (int i = 0; i < 10; ++i) y[i] = xin[i];
-        for (int s = 0; s < a.p.sub; ++s) plant_rk4(y, uv, acc, a.p.h);
-        const double n = plant_renorm(y);                    // y[6..9]: the tick's output quaternion
-        const double d = y[6] * lam[6] + y[7] * lam[7] + y[8] * lam[8] + y[9] * lam[9];
+    for (int i = 0; i < 6; ++i) lam[i] = lam[i] + gxf[i];
+}
+
+__device__ __forceinline__ void ClForm::force(int v, double g0, double g1, double g2) const
+{
+    if (gfps) { g0 = gfps[(size_t)v * 3] + g0; g1 = gfps[(size_t)v * 3 + 1] + g1; g2 = gfps[(size_t)v * 3 + 2] + g2; }
+    // A vehicle that hears a non-finite relative state through an open slot flew under a meaningless force (the network's ReLU swallows
+    // a NaN, so fps[k] may well be finite): its gF is NaN -- the force's adjoint then leaves the vehicle out of g_w and gives NaN in the
+    // g_z of its open slots, as for any non-finite upstream
+    const double *xe = x + (size_t)v * 10;
+    bool lost = false;
+    for (int j = 0; j < g.K; ++j) {
+        const int o = g.index[(size_t)v * g.K + j];
+        if (o < 0 || o >= g.B || o == v) continue;
+        const double *xo = x + (size_t)o * 10;
+        if (gate && !gate_open(xo, xe, r2)) continue;
 #pragma unroll
-        for (int i = 6; i < 10; ++i) lam[i] = (lam[i] - y[i] * d) / n;
-        for (int s = a.p.sub - 1; s >= 0; --s) {
-#pragma unroll
-            for (int i = 0; i < 10; ++i) y[i] = xin[i];
-            for (int j = 0; j < s; ++j) plant_rk4(y, uv, acc, a.p.h);
-            plant_rk4_vjp(y, uv, acc, a.p.h, lam, guv, gacc);
-        }
-        plant_st_row<5>(a.gxp + (size_t)v * 10, lam);
-        if (a.gus) {
-            double up[4];
-            plant_ld_row<2>(a.gus + (size_t)v * 4, up);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) guv[i] = up[i] + guv[i];
-        }
-        plant_st_row<2>(a.gu0 + (size_t)v * 4, guv);
-        const double g0 = gacc[0] * a.p.inv_mass, g1 = gacc[1] * a.p.inv_mass, g2 = gacc[2] * a.p.inv_mass;
-        if (a.gfp) { a.gfp[(size_t)v * 3] = g0; a.gfp[(size_t)v * 3 + 1] = g1; a.gfp[(size_t)v * 3 + 2] = g2; }
-        if (a.fp) p15 = -a.p.inv_mass * (g0 * a.fp[(size_t)v * 3] + g1 * a.fp[(size_t)v * 3 + 1] + g2 * a.fp[(size_t)v * 3 + 2]);
+        for (int i = 0; i < 6; ++i) lost = lost || !__builtin_isfinite(xo[i] - xe[i]);
     }
-    if (a.gm_tot) {
-        double tot[16], row[16];
-        if (a.gm_row) {
-            plant_ld_row<8>(a.gm_tot + (size_t)v * 16, tot);
-            plant_ld_row<8>(a.gm_row + (size_t)v * 16, row);
-#pragma unroll
-            for (int i = 0; i < 15; ++i) tot[i] = tot[i] + row[i];
-            tot[15] = bad ? __builtin_nan("") : tot[15] + p15;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 15; ++i) tot[i] = 0.0;
-            tot[15] = p15;
-        }
-        plant_st_row<8>(a.gm_tot + (size_t)v * 16, tot);
+    if (lost) g0 = g1 = g2 = __builtin_nan("");
+    gF[(size_t)v * 3] = g0; gF[(size_t)v * 3 + 1] = g1; gF[(size_t)v * 3 + 2] = g2;
+}
+
+__device__ __forceinline__ void cl_accumulate(const ClAcc &c, size_t i0, size_t stride)
+{
+    if (!c.gw) return;
+    for (size_t i = i0; i < (size_t)NDP_MLP_NPARAM; i += stride) {
+        const double t = c.first ? (double)c.gw[i] : c.acc[i] + (double)c.gw[i];
+        if (c.out) c.out[i] = (float)t;
+        else c.acc[i] = t;
     }
+}
+
+// closed_loop_rev_link_kernel with the vehicles coupled through the plant force: the same lane body (closed_loop_rev_lane.inc), ClForm's
+// two hooks in it; the spare
+// workgroups also add tick k + 1's weight gradient into the fp64 accumulator (the tail: and round it)
+__global__ __launch_bounds__(CL_LANES) void closed_loop_formation_rev_link_kernel(ClRevF A)
+{
+    if ((int)blockIdx.x >= A.r.p.plant_blocks) {
+        const size_t i0 = (size_t)((int)blockIdx.x - A.r.p.plant_blocks) * CL_LANES + threadIdx.x;
+        const size_t stride = (size_t)((int)gridDim.x - A.r.p.plant_blocks) * CL_LANES;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) cl_copy(A.r.cp[j], i0, stride);
+        cl_accumulate(A.acc, i0, stride);
+        return;
+    }
+    const int v = (int)(blockIdx.x * CL_LANES + threadIdx.x);
+    if (v >= A.r.p.B) return;
+    const ClRev &a = A.r;
+#define CL_REV_INCOMING(v, lam) A.f.incoming(v, lam);
+#define CL_REV_FORCE(v, g0, g1, g2) A.f.force(v, g0, g1, g2);
+#include "closed_loop_rev_lane.inc"
+#undef CL_REV_INCOMING
+#undef CL_REV_FORCE
+}
+
+// ndp_plant_force_scatter_device: g_z per slot onto the states, as a gather
+__global__ __launch_bounds__(CL_LANES) void closed_loop_scatter_kernel(ClScatter a)
+{
+    const int v = (int)(blockIdx.x * CL_LANES + threadIdx.x);
+    if (v >= a.g.B) return;
+    double o[10];
+    cl_gather(a.g, v, o);
+    o[6] = o[7] = o[8] = o[9] = 0.0;
+    plant_st_row<5>(a.gx + (size_t)v * 10, o);
 }
 
 // The plant tick's tangent, plant_rollout_jvp_kernel's tick body: a lane carries the vehicle's primal (recomputed from x_k) and ONE tangent,
@@ -312,17 +400,161 @@ static int cl_check(ndp_handle *h, const char *who, int ticks, int substeps, con
     return 0;
 }
 
-// What the two derivative calls do behind their frame and before they enqueue: cl_check, the recompute's refusals (noun: what it calls the
+// the formation calls' own two, behind cl_check: -2 not configured, -6 no weights (as the force call)
+static int cl_form_check(ndp_handle *h, const char *who)
+{
+    if (!h->dFormIndex) { h->err = std::string(who) + ": no formation configured (ndp_closed_loop_formation_config)"; return -2; }
+    if (!h->have_mlp) { h->err = std::string(who) + ": ndp_set_mlp_weights was never called"; return -6; }
+    return 0;
+}
+
+static ClGather cl_gather_of(const ndp_handle *h, const double *gz)
+{
+    const int B = h->cfg.batch, K = h->form_K;
+    return ClGather{h->dFormIndex, h->dFormIndex + (size_t)B * K, h->dFormIndex + (size_t)B * K + B + 1, gz, B, K};
+}
+
+// What the derivative calls do behind their frame and before they enqueue: cl_check, the recompute's refusals (noun: what it calls the
 // derivative) around the entry's own -- a missing tape in front of `own`, the entry's others -- and the recompute's workspace.
-static int cl_deriv_begin(ndp_handle *h, const char *who, const char *noun, int ticks, int substeps, const ClView &v, const char *own)
+static int cl_deriv_begin(ndp_handle *h, const char *who, const char *noun, int ticks, int substeps, const ClView &v, const char *own,
+                          bool formation = false)
 {
     int rc = cl_check(h, who, ticks, substeps, v.f);
     if (rc) return rc;
-    if (!v.tape) own = "d_tape is required (the forward's, recorded by ndp_closed_loop_device)";
+    if (formation && (rc = cl_form_check(h, who))) return rc;
+    if (!v.tape) own = formation ? "d_tape is required (the forward's, recorded by ndp_closed_loop_formation_device)"
+                                 : "d_tape is required (the forward's, recorded by ndp_closed_loop_device)";
     const void *lin = v.tape ? (const void *)v.tape : (const void *)v.x0;       // (a missing tape is refused by `own`, not as a missing iterate)
     const std::string why = recompute_refusal(h->cfg, noun, Tape{v.x0, v.xr, v.ur, v.f, lin, lin, nullptr, nullptr, nullptr}, own);
     if (!why.empty()) { h->err = std::string(who) + ": " + why; return -2; }
     return recompute_workspace(h);
+}
+
+// What the formation's calls add to the "ext" form's (null: the ext form): the gate and scale of the force on the plant, which the
+// forward makes from the states into v.fp (its log d_fps); the reverse call's upstream on that log and its weight gradient
+struct ClFormation {
+    int gate;
+    double scale;
+    const void *d_gfps;
+    void *d_gw;
+};
+
+// The forward of both forms, behind the entry's frame: the refusals, then everything enqueued on g.s
+static int cl_forward(ndp_handle *h, Entry &g, const char *who, int ticks, double dt, int substeps, const ClView &v, void *d_xs, void *d_us,
+                      void *d_Xs, void *d_status, const ClFormation *form)
+{
+    int rc = cl_check(h, who, ticks, substeps, v.f);
+    if (rc) return rc;
+    if (form && (rc = cl_form_check(h, who))) return rc;
+    hipStream_t s = g.s;
+    const size_t B = v.B;
+    const unsigned cb = cl_copy_blocks(v.itb + v.ab + (d_Xs ? nxs(h) * 8 : 0));
+    if (v.tape) {                  // slot 0: what the first step starts from
+        ClFwd a{};
+        a.p = cl_plant(h, dt, substeps, false);
+        v.record(0, a.cp);
+        hipLaunchKernelGGL(closed_loop_fwd_link_kernel, dim3(cb), dim3(CL_LANES), 0, s, a);
+        NDP_HIP(h, hipGetLastError());
+    }
+    for (int k = 0; k < ticks; ++k) {
+        double *u0 = cl_at((double *)d_us, k, B * NU);
+        // the formation: the force from the states of this tick, before any of them moves (ndp_rollout_formation_multi_device's rule)
+        if (form && (rc = launch_plant_force(h, v.x(k), h->dFormIndex, h->form_K, form->gate, form->scale, const_cast<double *>(v.fpk(k)),
+                                             nullptr, s))) return rc;
+        if ((rc = enqueue_step(h, v.x(k), v.xrk(k), v.urk(k), v.fk(k), Neigh{}, u0, nullptr, s))) return rc;
+        ClFwd a{};
+        a.p = cl_plant(h, dt, substeps, true);
+        a.xin = v.x(k); a.u = u0; a.fp = v.fpk(k);
+        a.xout = cl_at((double *)d_xs, k, B * NX);
+        a.st_src = h->lastStatus; a.st_dst = cl_at((int *)d_status, k, B);
+        if (v.tape && k + 1 < ticks) v.record(k + 1, a.cp);
+        if (d_Xs) a.cp[2] = ClCopy{(const unsigned char *)h->dX, (unsigned char *)d_Xs + (size_t)k * nxs(h) * 8, nxs(h) * 8};
+        hipLaunchKernelGGL(closed_loop_fwd_link_kernel, dim3((unsigned)a.p.plant_blocks + cb), dim3(CL_LANES), 0, s, a);
+        NDP_HIP(h, hipGetLastError());
+    }
+    return g.noted(0);
+}
+
+// The reverse sweep of both forms, behind the entry's frame.  own: the entry's refusal (no upstream, no output) or null.  The ext form
+// launches closed_loop_rev_link_kernel on the ClRev alone; the formation wraps the same ClRev into a ClRevF and runs the force's adjoint
+// between the link and the step's adjoint.  d_gfp: the ext form's output (null in the formation, where the force is no leaf).
+static int cl_reverse(ndp_handle *h, Entry &g, const char *who, int ticks, double dt, int substeps, const ClView &v, const char *own,
+                      const void *d_gxs, const void *d_gus, const void *d_gXs, void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_gfp,
+                      void *d_gmodel, void *d_status_check, const ClFormation *form)
+{
+    int rc = cl_deriv_begin(h, who, "adjoint", ticks, substeps, v, own, form != nullptr);
+    if (rc) return rc;
+    hipStream_t s = g.s;
+    const size_t B = v.B;
+    if (!h->dClWs) NDP_HIP(h, hipMalloc((void **)&h->dClWs, B * (NU + NX + NX + 16) * 8));
+    double *ws_gu0 = h->dClWs, *ws_gxp = ws_gu0 + B * NU, *ws_gx0 = ws_gxp + B * NX, *ws_gm = ws_gx0 + B * NX;
+    double *ws_gF = nullptr, *ws_gz = nullptr, *ws_acc = nullptr;
+    float *ws_gw = nullptr;
+    if (form) {
+        const size_t np2 = ((size_t)NDP_MLP_NPARAM + 1) / 2;       // a tick's fp32 g_w, in doubles
+        if (!h->dFormWs) NDP_HIP(h, hipMalloc((void **)&h->dFormWs, (B * 3 + B * NDP_MAX_NEIGH * 6 + NDP_MLP_NPARAM + np2) * 8));
+        ws_gF = h->dFormWs; ws_gz = ws_gF + B * 3; ws_acc = ws_gz + B * NDP_MAX_NEIGH * 6;
+        if (form->d_gw) ws_gw = (float *)(ws_acc + NDP_MLP_NPARAM);
+    }
+    const bool model = d_gmodel != nullptr;
+    const unsigned cb = cl_copy_blocks(v.itb + v.ab);
+    // where tick k's adjoint leaves its recomputed status words: the caller's log, or the workspace's
+    auto st_of = [&](int k) { return d_status_check ? (const int *)d_status_check + (size_t)k * B : (const int *)h->dVjpSt; };
+    // one link launch: the plain kernel, or the formation's around the same ClRev (gz: the g_z it gathers, null: none)
+    auto link = [&](const ClRev &r, unsigned blocks, const double *gz, const double *gfps, const double *x, const ClAcc &acc) {
+        if (!form) {
+            hipLaunchKernelGGL(closed_loop_rev_link_kernel, dim3(blocks), dim3(CL_LANES), 0, s, r);
+            return;
+        }
+        ClRevF a{};
+        a.r = r;
+        a.f.g = cl_gather_of(h, gz);
+        a.f.gfps = gfps; a.f.gF = ws_gF;
+        a.f.x = x; a.f.gate = form->gate ? 1 : 0; a.f.r2 = h->cfg.r_horiz * h->cfg.r_horiz;
+        a.acc = acc;
+        hipLaunchKernelGGL(closed_loop_formation_rev_link_kernel, dim3(blocks), dim3(CL_LANES), 0, s, a);
+    };
+    for (int k = ticks - 1; k >= 0; --k) {
+        const bool last = k == ticks - 1;
+        ClRev a{};
+        a.p = cl_plant(h, dt, substeps, true);
+        a.xin = v.x(k); a.u = v.u0(k); a.fp = v.fpk(k);
+        a.gxs = cl_at((const double *)d_gxs, k, B * NX);
+        a.gus = cl_at((const double *)d_gus, k, B * NU);
+        a.c_p = last ? nullptr : ws_gxp; a.c_s = last ? nullptr : ws_gx0;
+        a.gxp = ws_gxp; a.gu0 = ws_gu0;
+        a.gfp = cl_at((double *)d_gfp, k, B * 3);
+        a.gm_tot = (double *)d_gmodel; a.gm_row = last ? nullptr : ws_gm;
+        a.st_prev = last ? nullptr : st_of(k + 1); a.gfp_prev = last ? nullptr : cl_at((double *)d_gfp, k + 1, B * 3);
+        v.replay(k, a.cp);
+        link(a, (unsigned)a.p.plant_blocks + cb, last ? nullptr : ws_gz, form ? cl_at((const double *)form->d_gfps, k, B * 3) : nullptr, v.x(k),
+             ClAcc{last ? nullptr : ws_gw, ws_acc, nullptr, k == ticks - 2});
+        NDP_HIP(h, hipGetLastError());
+        // the formation: the force's adjoint at x_k on gF_k -- g_z per slot for the next link's gather, this tick's fp32 g_w
+        if (form && (rc = launch_plant_force_vjp(h, who, v.x(k), h->dFormIndex, h->form_K, form->gate, form->scale, ws_gF, ws_gz, ws_gw, s)))
+            return rc;
+        VjpArgs va{ws_gu0, cl_at((const double *)d_gXs, k, nxs(h)), nullptr, ws_gx0, cl_at((double *)d_gxr, k, nxs(h)),
+                   cl_at((double *)d_gur, k, nus(h)), cl_at((double *)d_gf, k, nfs(h))};
+        double *gm = ws_gm;
+        const Tape t = v.step(k, cl_at((int *)d_status_check, k, B));
+        if (model) rc = recompute_on_workspace(h, s, t, recompute_kernel(RC_WVJP, true), recompute_kernel(RC_WVJP, false), &va, &gm);
+        else rc = recompute_on_workspace(h, s, t, recompute_kernel(RC_VJP, true), recompute_kernel(RC_VJP, false), &va, nullptr);
+        if (rc) return rc;
+    }
+    // behind tick 0: d_gx0 = gx_p + gx0 (the formation: + gx_f), tick 0's row into the model gradient, a failed tick 0's gfp, d_gw rounded once
+    if (d_gx0 || d_gfp || ws_gw || model) {
+        ClRev a{};
+        a.p = cl_plant(h, dt, substeps, true);
+        a.tail = 1;
+        a.c_p = ws_gxp; a.c_s = ws_gx0;
+        a.gx0 = (double *)d_gx0;
+        a.gm_tot = (double *)d_gmodel; a.gm_row = ws_gm;
+        a.st_prev = st_of(0); a.gfp_prev = (double *)d_gfp;
+        const unsigned ab = ws_gw ? cl_copy_blocks((size_t)NDP_MLP_NPARAM * 8) : 0u;
+        link(a, (unsigned)a.p.plant_blocks + ab, ws_gz, nullptr, nullptr, ClAcc{ws_gw, ws_acc, form ? (float *)form->d_gw : nullptr, ticks == 1});
+        NDP_HIP(h, hipGetLastError());
+    }
+    return g.noted(0);
 }
 
 extern "C" {
@@ -341,33 +573,8 @@ int ndp_closed_loop_device(ndp_handle *h, int ticks, double dt, int substeps, co
 {
     Entry g(h, d_x0 && d_xr && d_ur && d_xs && d_us, stream);
     if (g.rc) return g.rc;
-    int rc = cl_check(h, "ndp_closed_loop_device", ticks, substeps, d_f);
-    if (rc) return rc;
-    hipStream_t s = g.s;
-    const ClView v = cl_view(h, d_x0, d_xr, d_ur, d_f, d_fp, d_xs, d_us, d_tape);
-    const size_t B = v.B;
-    const unsigned cb = cl_copy_blocks(v.itb + v.ab + (d_Xs ? nxs(h) * 8 : 0));
-    if (v.tape) {                  // slot 0: what the first step starts from
-        ClFwd a{};
-        a.p = cl_plant(h, dt, substeps, false);
-        v.record(0, a.cp);
-        hipLaunchKernelGGL(closed_loop_fwd_link_kernel, dim3(cb), dim3(CL_LANES), 0, s, a);
-        NDP_HIP(h, hipGetLastError());
-    }
-    for (int k = 0; k < ticks; ++k) {
-        double *u0 = cl_at((double *)d_us, k, B * NU);
-        if ((rc = enqueue_step(h, v.x(k), v.xrk(k), v.urk(k), v.fk(k), Neigh{}, u0, nullptr, s))) return rc;
-        ClFwd a{};
-        a.p = cl_plant(h, dt, substeps, true);
-        a.xin = v.x(k); a.u = u0; a.fp = v.fpk(k);
-        a.xout = cl_at((double *)d_xs, k, B * NX);
-        a.st_src = h->lastStatus; a.st_dst = cl_at((int *)d_status, k, B);
-        if (v.tape && k + 1 < ticks) v.record(k + 1, a.cp);
-        if (d_Xs) a.cp[2] = ClCopy{(const unsigned char *)h->dX, (unsigned char *)d_Xs + (size_t)k * nxs(h) * 8, nxs(h) * 8};
-        hipLaunchKernelGGL(closed_loop_fwd_link_kernel, dim3((unsigned)a.p.plant_blocks + cb), dim3(CL_LANES), 0, s, a);
-        NDP_HIP(h, hipGetLastError());
-    }
-    return g.noted(0);
+    return cl_forward(h, g, "ndp_closed_loop_device", ticks, dt, substeps, cl_view(h, d_x0, d_xr, d_ur, d_f, d_fp, d_xs, d_us, d_tape), d_xs, d_us,
+                      d_Xs, d_status, nullptr);
 }
 
 int ndp_closed_loop_vjp_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_xr, const void *d_ur,
@@ -380,52 +587,8 @@ int ndp_closed_loop_vjp_device(ndp_handle *h, int ticks, double dt, int substeps
     const char *own = nullptr;
     if (!d_gxs && !d_gus && !d_gXs) own = "no upstream gradient (d_gxs, d_gus and d_gXs all NULL)";
     else if (!d_gx0 && !d_gxr && !d_gur && !d_gf && !d_gfp && !d_gmodel) own = "no output asked for (d_gx0, d_gxr, d_gur, d_gf, d_gfp and d_gmodel all NULL)";
-    const ClView v = cl_view(h, d_x0, d_xr, d_ur, d_f, d_fp, d_xs, d_us, d_tape);
-    int rc = cl_deriv_begin(h, "ndp_closed_loop_vjp_device", "adjoint", ticks, substeps, v, own);
-    if (rc) return rc;
-    hipStream_t s = g.s;
-    const size_t B = v.B;
-    if (!h->dClWs) NDP_HIP(h, hipMalloc((void **)&h->dClWs, B * (NU + NX + NX + 16) * 8));
-    double *ws_gu0 = h->dClWs, *ws_gxp = ws_gu0 + B * NU, *ws_gx0 = ws_gxp + B * NX, *ws_gm = ws_gx0 + B * NX;
-    const bool model = d_gmodel != nullptr;
-    const unsigned cb = cl_copy_blocks(v.itb + v.ab);
-    // where tick k's adjoint leaves its recomputed status words: the caller's log, or the workspace's
-    auto st_of = [&](int k) { return d_status_check ? (const int *)d_status_check + (size_t)k * B : (const int *)h->dVjpSt; };
-    for (int k = ticks - 1; k >= 0; --k) {
-        const bool last = k == ticks - 1;
-        ClRev a{};
-        a.p = cl_plant(h, dt, substeps, true);
-        a.xin = v.x(k); a.u = v.u0(k); a.fp = v.fpk(k);
-        a.gxs = cl_at((const double *)d_gxs, k, B * NX);
-        a.gus = cl_at((const double *)d_gus, k, B * NU);
-        a.c_p = last ? nullptr : ws_gxp; a.c_s = last ? nullptr : ws_gx0;
-        a.gxp = ws_gxp; a.gu0 = ws_gu0;
-        a.gfp = cl_at((double *)d_gfp, k, B * 3);
-        a.gm_tot = (double *)d_gmodel; a.gm_row = last ? nullptr : ws_gm;
-        a.st_prev = last ? nullptr : st_of(k + 1); a.gfp_prev = last ? nullptr : cl_at((double *)d_gfp, k + 1, B * 3);
-        v.replay(k, a.cp);
-        hipLaunchKernelGGL(closed_loop_rev_link_kernel, dim3((unsigned)a.p.plant_blocks + cb), dim3(CL_LANES), 0, s, a);
-        NDP_HIP(h, hipGetLastError());
-        VjpArgs va{ws_gu0, cl_at((const double *)d_gXs, k, nxs(h)), nullptr, ws_gx0, cl_at((double *)d_gxr, k, nxs(h)),
-                   cl_at((double *)d_gur, k, nus(h)), cl_at((double *)d_gf, k, nfs(h))};
-        double *gm = ws_gm;
-        const Tape t = v.step(k, cl_at((int *)d_status_check, k, B));
-        if (model) rc = recompute_on_workspace(h, s, t, recompute_kernel(RC_WVJP, true), recompute_kernel(RC_WVJP, false), &va, &gm);
-        else rc = recompute_on_workspace(h, s, t, recompute_kernel(RC_VJP, true), recompute_kernel(RC_VJP, false), &va, nullptr);
-        if (rc) return rc;
-    }
-    if (d_gx0 || d_gfp || model) { // behind tick 0: d_gx0 = gx_p + gx0, tick 0's row into the model gradient, a failed tick 0's gfp
-        ClRev a{};
-        a.p = cl_plant(h, dt, substeps, true);
-        a.tail = 1;
-        a.c_p = ws_gxp; a.c_s = ws_gx0;
-        a.gx0 = (double *)d_gx0;
-        a.gm_tot = (double *)d_gmodel; a.gm_row = ws_gm;
-        a.st_prev = st_of(0); a.gfp_prev = (double *)d_gfp;
-        hipLaunchKernelGGL(closed_loop_rev_link_kernel, dim3((unsigned)a.p.plant_blocks), dim3(CL_LANES), 0, s, a);
-        NDP_HIP(h, hipGetLastError());
-    }
-    return g.noted(0);
+    return cl_reverse(h, g, "ndp_closed_loop_vjp_device", ticks, dt, substeps, cl_view(h, d_x0, d_xr, d_ur, d_f, d_fp, d_xs, d_us, d_tape), own,
+                      d_gxs, d_gus, d_gXs, d_gx0, d_gxr, d_gur, d_gf, d_gfp, d_gmodel, d_status_check, nullptr);
 }
 
 int ndp_closed_loop_jvp_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_xr, const void *d_ur,
@@ -478,6 +641,88 @@ int ndp_closed_loop_jvp_device(ndp_handle *h, int ticks, double dt, int substeps
         NDP_HIP(h, hipGetLastError());
     }
     return g.noted(0);
+}
+
+// ---- the formation: the plant force made from the states inside the loop, and the reverse sweep across the vehicles
+int ndp_closed_loop_formation_config(ndp_handle *h, const int32_t *other_index, int K)
+{
+    Entry g(h, true);
+    if (g.rc) return g.rc;
+    int rc = wait_all(h);
+    if (rc) return rc;
+    if (!other_index) {
+        if (h->dFormIndex) (void)hipFree(h->dFormIndex);
+        h->dFormIndex = nullptr;
+        h->form_K = h->form_edges = 0;
+        return 0;
+    }
+    if ((rc = check_neigh(h, "ndp_closed_loop_formation_config", K))) return rc;
+    const int B = h->cfg.batch;
+    const size_t slots = (size_t)B * K;
+    auto heard = [&](size_t e) { const int o = other_index[e]; return o >= 0 && o < B && o != (int)(e / K) ? o : -1; };
+    // index | offset | edge in one host block: a counting pass, then the edges in ascending e (each list comes out ascending)
+    std::vector<int32_t> blk(slots + B + 1, 0);
+    int32_t *off = blk.data() + slots;
+    for (size_t e = 0; e < slots; ++e) {
+        blk[e] = other_index[e];
+        if (heard(e) >= 0) ++off[heard(e) + 1];
+    }
+    for (int v = 0; v < B; ++v) off[v + 1] += off[v];
+    const int edges = off[B];
+    blk.resize(slots + B + 1 + (size_t)edges);
+    off = blk.data() + slots;
+    std::vector<int32_t> fill(off, off + B);
+    for (size_t e = 0; e < slots; ++e)
+        if (heard(e) >= 0) blk[slots + B + 1 + (size_t)fill[heard(e)]++] = (int32_t)e;
+    if (h->dFormIndex) (void)hipFree(h->dFormIndex);
+    h->dFormIndex = nullptr;
+    h->form_K = h->form_edges = 0;
+    int *d_blk = nullptr;
+    NDP_HIP(h, hipMalloc((void **)&d_blk, blk.size() * 4));
+    const hipError_t e = hipMemcpy(d_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) (void)hipFree(d_blk);         // (nothing stays configured behind a failed copy)
+    NDP_HIP(h, e);
+    h->dFormIndex = d_blk; h->form_K = K; h->form_edges = edges;
+    return 0;
+}
+
+int ndp_plant_force_scatter_device(ndp_handle *h, const void *d_gz, void *d_gx, void *stream)
+{
+    Entry g(h, d_gz && d_gx, stream);
+    if (g.rc) return g.rc;
+    if (!h->dFormIndex) { h->err = "ndp_plant_force_scatter_device: no formation configured (ndp_closed_loop_formation_config)"; return -2; }
+    ClScatter a{cl_gather_of(h, (const double *)d_gz), (double *)d_gx};
+    hipLaunchKernelGGL(closed_loop_scatter_kernel, dim3((unsigned)((a.g.B + CL_LANES - 1) / CL_LANES)), dim3(CL_LANES), 0, g.s, a);
+    NDP_HIP(h, hipGetLastError());
+    return g.noted(0);
+}
+
+int ndp_closed_loop_formation_device(ndp_handle *h, int ticks, double dt, int substeps, int gate, double plant_scale, const void *d_x0,
+                                     const void *d_xr, const void *d_ur, const void *d_f, void *d_xs, void *d_us, void *d_fps, void *d_Xs,
+                                     void *d_status, void *d_tape, void *stream)
+{
+    Entry g(h, d_x0 && d_xr && d_ur && d_xs && d_us && d_fps, stream);
+    if (g.rc) return g.rc;
+    const ClFormation form{gate, plant_scale, nullptr, nullptr};
+    return cl_forward(h, g, "ndp_closed_loop_formation_device", ticks, dt, substeps, cl_view(h, d_x0, d_xr, d_ur, d_f, d_fps, d_xs, d_us, d_tape),
+                      d_xs, d_us, d_Xs, d_status, &form);
+}
+
+int ndp_closed_loop_formation_vjp_device(ndp_handle *h, int ticks, double dt, int substeps, int gate, double plant_scale, const void *d_x0,
+                                         const void *d_xr, const void *d_ur, const void *d_f, const void *d_xs, const void *d_us,
+                                         const void *d_fps, const void *d_tape, const void *d_gxs, const void *d_gus, const void *d_gXs,
+                                         const void *d_gfps, void *d_gx0, void *d_gxr, void *d_gur, void *d_gf, void *d_gw, void *d_gmodel,
+                                         void *d_status_check, void *stream)
+{
+    Entry g(h, d_x0 && d_xr && d_ur && d_xs && d_us && d_fps, stream);
+    if (g.rc) return g.rc;
+    const char *own = nullptr;
+    if (!d_gxs && !d_gus && !d_gXs && !d_gfps) own = "no upstream gradient (d_gxs, d_gus, d_gXs and d_gfps all NULL)";
+    else if (!d_gx0 && !d_gxr && !d_gur && !d_gf && !d_gw && !d_gmodel) own = "no output asked for (d_gx0, d_gxr, d_gur, d_gf, d_gw and d_gmodel all NULL)";
+    const ClFormation form{gate, plant_scale, d_gfps, d_gw};
+    return cl_reverse(h, g, "ndp_closed_loop_formation_vjp_device", ticks, dt, substeps,
+                      cl_view(h, d_x0, d_xr, d_ur, d_f, d_fps, d_xs, d_us, d_tape), own, d_gxs, d_gus, d_gXs, d_gx0, d_gxr, d_gur, d_gf, nullptr,
+                      d_gmodel, d_status_check, &form);
 }
 
 }  // extern "C"

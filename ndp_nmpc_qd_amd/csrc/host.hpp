@@ -31,7 +31,9 @@
 //   closed_loop.hip  the closed loop over given windows in one call per direction (ndp_closed_loop_device, ndp_closed_loop_vjp_device,
 //                    ndp_closed_loop_jvp_device): the step, its adjoint and its forward mode are the existing kernels, launched unchanged;
 //                    the three link kernels between them live here.  Host side: ClView hands out tick k's slices and tape slot,
-//                    cl_deriv_begin is what the two derivative calls do before they enqueue
+//                    cl_deriv_begin is what the derivative calls do before they enqueue.  Also the formation's form, with the force on
+//                    the plant made inside the loop (ndp_closed_loop_formation_config / _device / _vjp_device,
+//                    ndp_plant_force_scatter_device): the reverse link's lane body is closed_loop_rev_lane.inc, shared by both link kernels
 //   exchange.hip     peer-mapped windows (ndp_peer_*), the RCCL exchange (ndp_xchg_*) and the remote tick one control period ahead
 // A kernel sits with the host code that launches it; device code that two units' kernels inline is a header (mlp_tile.hpp, ref_point.hpp,
 // tick_wave.hpp, mlp_vjp_dev.hpp, mlp_jvp_dev.hpp, plant_dyn.hpp, plant_adj.hpp, plant_tan.hpp), and so are the argument blocks the host fills (kern_args.hpp).
@@ -89,6 +91,13 @@ struct ndp_handle {
     // ndp_closed_loop_vjp_device's workspace (first call), what one tick hands the next: gu0 [B][4] | gx_p [B][10] | the step's gx0 [B][10] |
     // the step's gmodel row [B][16] (closed_loop.hip)
     double *dClWs = nullptr;
+    // ndp_closed_loop_formation_config: one allocation, int32: the index [B][K] | the reverse lists' offset [B+1] | edge [form_edges]
+    // (closed_loop.hip: ClGather); null: not configured
+    int *dFormIndex = nullptr;
+    int form_K = 0, form_edges = 0;
+    // ndp_closed_loop_formation_vjp_device's workspace (first call; the largest K: sized for NDP_MAX_NEIGH): gF [B][3] | g_z [B][8][6] |
+    // the weight gradient's fp64 accumulator [NDP_MLP_NPARAM], then a tick's fp32 g_w [NDP_MLP_NPARAM]
+    double *dFormWs = nullptr;
     // mlp_vjp.hip: layers 2 and 3 transposed, one fp32 record per matrix instruction of the backward pass (FRT_TOTAL floats, written with
     // dFrag by both ndp_set_mlp_weights forms); ndp_downwash_vjp_device's per-workgroup partial weight gradients [mlp_vjp_groups][NDP_MLP_NPARAM]
     // (ndp_downwash_multi_vjp_device shares them: it never launches more workgroups than that)
@@ -319,6 +328,8 @@ NDP_HIDDEN hipError_t mlp_vjp_prepare(void);
 NDP_HIDDEN hipError_t mlp_fit_prepare(void);
 // plant_force_deriv.hip
 NDP_HIDDEN hipError_t plant_force_deriv_prepare(void);
+NDP_HIDDEN int launch_plant_force_vjp(ndp_handle *h, const char *who, const void *d_x, const void *d_index, int K, int gate, double scale,
+                                      const void *d_gf, void *d_gz, void *d_gw, hipStream_t s);
 // plant_deriv.hip.  The refusals of every call that takes `ticks` ticks of `substeps` substeps (closed_loop.hip's too): -2 with the reason
 NDP_HIDDEN int plant_seq_check(ndp_handle *h, const char *who, int ticks, int substeps);
 // exchange.hip

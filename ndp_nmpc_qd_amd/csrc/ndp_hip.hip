@@ -206,7 +206,7 @@ int ndp_destroy(ndp_handle *h)
     h->pool.reset();
     void *ptrs[] = {h->dForceAB[0], h->dForceAB[1], h->dProto, h->dRingX, h->dTraj, h->dTables, h->dStamps, h->dRelay, h->dThr, h->sThr, h->dKC, h->dForce, h->dFrag,
                     h->dIn, h->dOut, h->sdbg, h->dQctr, h->dQids, h->dTickIndex, h->dTickThrust, h->dAct,
-                    h->dSensU0, h->dSensU, h->dSensX, h->dPSensXr, h->dPSensUr, h->dPSensF, h->dVjp, h->dVjpSt, h->dVjpAct, h->dClWs, h->dFragT, h->dGwPart, h->dFitPart, h->dTrain};
+                    h->dSensU0, h->dSensU, h->dSensX, h->dPSensXr, h->dPSensUr, h->dPSensF, h->dVjp, h->dVjpSt, h->dVjpAct, h->dClWs, h->dFormIndex, h->dFormWs, h->dFragT, h->dGwPart, h->dFitPart, h->dTrain};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &sl : h->slot) {

@@ -246,9 +246,10 @@ hipError_t plant_force_deriv_prepare(void)
     return hipFuncSetAttribute((const void *)plant_force_vjp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(VJ_LDS_FLOATS * sizeof(float)));
 }
 
-// Both reverse forms; K was checked by the caller.  -6, then the -2 refusals, before anything is enqueued.
-static int plant_force_vjp(ndp_handle *h, const char *who, Entry &g, const void *d_x, const void *d_index, int K, int gate, double scale,
-                           const void *d_gf, void *d_gz, void *d_gw)
+// The reverse launches of both forms and of closed_loop.hip's formation sweep: the refusals (-6, then -2 under `who`) before anything is
+// enqueued.  No locking, no sync, K not checked (check_neigh).
+int launch_plant_force_vjp(ndp_handle *h, const char *who, const void *d_x, const void *d_index, int K, int gate, double scale,
+                           const void *d_gf, void *d_gz, void *d_gw, hipStream_t s)
 {
     if (d_index && !h->have_mlp) { h->err = std::string(who) + ": ndp_set_mlp_weights was never called"; return -6; }
     const char *why = nullptr;
@@ -257,22 +258,29 @@ static int plant_force_vjp(ndp_handle *h, const char *who, Entry &g, const void 
     if (why) { h->err = std::string(who) + why; return -2; }
     const int B = h->cfg.batch, rows = B * K;
     if (!d_index) {      // nobody has a neighbour: exact zeros, no network pass, no weights needed
-        if (d_gz) NDP_HIP(h, hipMemsetAsync(d_gz, 0, (size_t)rows * 6 * 8, g.s));
-        if (d_gw) NDP_HIP(h, hipMemsetAsync(d_gw, 0, (size_t)NDP_MLP_NPARAM * 4, g.s));
-        return g.noted(0);
+        if (d_gz) NDP_HIP(h, hipMemsetAsync(d_gz, 0, (size_t)rows * 6 * 8, s));
+        if (d_gw) NDP_HIP(h, hipMemsetAsync(d_gw, 0, (size_t)NDP_MLP_NPARAM * 4, s));
+        return 0;
     }
     // the workspace is ndp_downwash_vjp_device's, [mlp_vjp_groups][NDP_MLP_NPARAM]: never more workgroups than it has rows (the grid-stride
     // loop takes the rest)
     const int ngroups = ((rows + 31) / 32 + 3) / 4, cap = mlp_vjp_groups(h), G = ngroups < cap ? ngroups : cap;
     PlantForceVjpArgs a{h->dFrag, h->dFragT, (const double *)d_x, (const int *)d_index, (const double *)d_gf, (double *)d_gz,
                         d_gw ? h->dGwPart : nullptr, B, K, gate ? 1 : 0, h->cfg.r_horiz * h->cfg.r_horiz, scale};
-    hipLaunchKernelGGL(plant_force_vjp_kernel, dim3(G), dim3(256), VJ_LDS_FLOATS * sizeof(float), g.s, a);
+    hipLaunchKernelGGL(plant_force_vjp_kernel, dim3(G), dim3(256), VJ_LDS_FLOATS * sizeof(float), s, a);
     NDP_HIP(h, hipGetLastError());
     if (d_gw) {
-        hipLaunchKernelGGL(plant_force_reduce_kernel, dim3((PTOTAL + 255) / 256), dim3(256), 0, g.s, (const float *)h->dGwPart, G, (float *)d_gw);
+        hipLaunchKernelGGL(plant_force_reduce_kernel, dim3((PTOTAL + 255) / 256), dim3(256), 0, s, (const float *)h->dGwPart, G, (float *)d_gw);
         NDP_HIP(h, hipGetLastError());
     }
-    return g.noted(0);
+    return 0;
+}
+
+// Both reverse forms; K was checked by the caller.
+static int plant_force_vjp(ndp_handle *h, const char *who, Entry &g, const void *d_x, const void *d_index, int K, int gate, double scale,
+                           const void *d_gf, void *d_gz, void *d_gw)
+{
+    return g.noted(launch_plant_force_vjp(h, who, d_x, d_index, K, gate, scale, d_gf, d_gz, d_gw, g.s));
 }
 
 static int plant_force_jvp(ndp_handle *h, const char *who, Entry &g, const void *d_x, const void *d_index, int K, int gate, double scale,

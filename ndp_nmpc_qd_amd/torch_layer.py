@@ -53,6 +53,10 @@ x_0, the windows, both forces, Qd, Rd and the mass -- what the chain control_ste
 closed_loop_jvp (behind it) is the same flight with its forward mode: that one call forward with a tape, then one call
 (closed_loop_jvp_device) for the tangents of x_{k+1}, u0_k and X_k along T directions of x_0, the windows and both forces -- what the chain
 control_step_jvp -> plant_rollout_jvp(ticks = 1) gives tick by tick.  No autograd hookup.
+closed_loop_formation (at the end of this file) is closed_loop for a formation: the force on the plant is made inside the loop from the
+vehicles' actual states (plant_force's values at every tick), and the one call back (closed_loop_formation_vjp_device) carries the gradients
+across the vehicles on the device and returns the network's weight gradient summed over the ticks -- what the chain plant_force ->
+control_step_trajectory -> plant_step gives link by link.
 
 plant_force / plant_force_jvp (at the end of this file) are the downwash force the neighbours' actual states put on the plant, differentiable
 in the states and the network's weights (BatchedNMPC.plant_force_multi_device, plant_force_multi_vjp_device, plant_force_multi_jvp_device):
@@ -1249,3 +1253,93 @@ def plant_force_jvp(engine, x, other_index, tangents, gate=True, scale=1.0, weig
     if default:
         engine.synchronize()
     return f, df if had else df[:, 0]
+
+
+# ---------------------------------------------------------------------------------------------- the formation's closed loop, one call per direction
+def _configure_formation(engine, index):
+    """Configures `index` (a host int32 [B,K] array) on the engine unless it is what is configured (the configuration is synchronous)."""
+    have = engine._form_index
+    if have is None or have.shape != index.shape or not (have == index).all():
+        engine.closed_loop_formation_config(index)
+
+
+class ClosedLoopFormationFunction(torch.autograd.Function):
+    """forward(x0, engine, xr, ur, other_index, f, weights, Qd, Rd, mass, gate, scale, dt, substeps) -> (xs, us, Xs, fps) float64:
+    BatchedNMPC.closed_loop_formation_device with its tape; backward: ONE BatchedNMPC.closed_loop_formation_vjp_device call for the
+    gradients of x0, xr, ur, f, the weights, Qd, Rd and mass (only those that require one are computed)."""
+
+    @staticmethod
+    def forward(ctx, x0, engine, xr, ur, other_index, f, weights, Qd, Rd, mass, gate, scale, dt, substeps):
+        x0, xr, ur, fd = _det(x0), _det(xr), _det(ur), _det(f)
+        idx = _plant_index(other_index, "ClosedLoopFormationFunction")
+        if idx is None:
+            raise ValueError("ClosedLoopFormationFunction: other_index is required (closed_loop is the form without neighbours)")
+        ctx.model = _install_model(engine, Qd, Rd, mass)
+        ctx.set_materialize_grads(False)
+        K, B, N = xr.shape[0], xr.shape[1], xr.shape[2] - 1
+        stream, default, ctx.key = _enter(engine, x0, weights)
+        ctx.index = idx.cpu().numpy()
+        _configure_formation(engine, ctx.index)
+        new = lambda *s: torch.empty(s, dtype=torch.float64, device=x0.device)  # noqa: E731
+        xs, us, Xs, fps, tape = new(K, B, 10), new(K, B, 4), new(K, B, N + 1, 10), new(K, B, 3), engine.closed_loop_tape(K)
+        engine.closed_loop_formation_device(x0, xr, ur, xs, us, fps, f=fd, Xs=Xs, tape=tape, gate=gate, plant_scale=scale, dt=dt,
+                                            substeps=substeps, stream=stream)
+        if default:
+            engine.synchronize()
+        ctx.engine, ctx.dt, ctx.substeps, ctx.gate, ctx.scale = engine, dt, substeps, gate, scale
+        ctx.have_w = weights is not None
+        ctx.f_dtype = f.dtype if isinstance(f, torch.Tensor) else None
+        ctx.like = tuple(None if not isinstance(t, torch.Tensor) else (t.shape, t.dtype, t.device) for t in (Qd, Rd, mass))
+        ctx.save_for_backward(x0, xr, ur, xs, us, fps, tape, *(() if fd is None else (fd,)))
+        return xs, us, Xs, fps
+
+    @staticmethod
+    def backward(ctx, g_xs, g_us, g_Xs, g_fps):
+        x0, xr, ur, xs, us, fps, tape, *rest = ctx.saved_tensors
+        fd = rest[0] if rest else None
+        eng, need = ctx.engine, ctx.needs_input_grad
+        want = (need[0], need[2], need[3], need[5] and fd is not None, need[6] and ctx.have_w,
+                any(n and like is not None for n, like in zip(need[7:10], ctx.like)))
+        if (g_xs is None and g_us is None and g_Xs is None and g_fps is None) or not any(want):
+            return (None,) * 14
+        if _engine_model(eng) != ctx.model:
+            raise RuntimeError("ClosedLoopFormationFunction: the engine's model (Qd, Rd, mass) was changed between this forward and its "
+                               "backward (the backward recomputes every step from the engine's model): run the backward before the next "
+                               "forward with other values, or set the model back first")
+        _check_installed(eng, ctx.key, "ClosedLoopFormationFunction")
+        K, B, N = xr.shape[0], xr.shape[1], xr.shape[2] - 1
+        ups = tuple(None if g is None else g.to(torch.float64).contiguous() for g in (g_xs, g_us, g_Xs, g_fps))
+        gx0, gxr, gur, gf, gw, gm = (torch.empty(*s, dtype=dt, device=x0.device) if w else None for w, s, dt in zip(
+            want, ((B, 10), (K, B, N + 1, 10), (K, B, N, 4), (K, B, N + 1, 3), (_lib.MLP_NPARAM,), (B, 16)),
+            (torch.float64,) * 4 + (torch.float32, torch.float64)))
+        stream, default = _cuda_stream(x0)
+        _configure_formation(eng, ctx.index)             # (another formation may have been configured since the forward)
+        eng.closed_loop_formation_vjp_device(x0, xr, ur, xs, us, fps, tape, f=fd, gxs=ups[0], gus=ups[1], gXs=ups[2], gfps=ups[3], gx0=gx0,
+                                             gxr=gxr, gur=gur, gf=gf, gw=gw, gmodel=gm, gate=ctx.gate, plant_scale=ctx.scale, dt=ctx.dt,
+                                             substeps=ctx.substeps, stream=stream)
+        if default:
+            eng.synchronize()
+        out = [None, None, None]
+        if gm is not None:
+            # a failed vehicle (NaN in its row) contributes nothing: control_step_tunable's convention
+            tot = torch.where(torch.isfinite(gm).all(dim=1, keepdim=True), gm, torch.zeros_like(gm)).sum(dim=0)
+            for i, (like, need_i, part) in enumerate(zip(ctx.like, need[7:10], (tot[0:10], tot[10:14], tot[14:15] + tot[15:16]))):
+                if like is not None and need_i:
+                    out[i] = part.reshape(like[0]).to(device=like[2], dtype=like[1])
+        return (gx0, None, gxr, gur, None, None if gf is None else gf.to(ctx.f_dtype), gw, out[0], out[1], out[2], None, None, None, None)
+
+
+def closed_loop_formation(engine, x0, xr, ur, other_index, f=None, weights=None, Qd=None, Rd=None, mass=None, gate=True, scale=1.0,
+                          dt=CP.ts_nmpc, substeps=4):
+    """(xs, us, Xs, fps) = closed_loop with the downwash force on the plant made inside the loop from the vehicles' actual states: per tick
+    fps[k] [B,3] = plant_force(engine, x_k, other_index, gate, scale) from the states of that tick before any of them moves, the control
+    step with xr[k], ur[k] and the given force f[k] the controller sees (None: none), the plant tick with fps[k] held over the tick -- the
+    values of the chain plant_force -> control_step_trajectory -> plant_step, bit for bit, in one call.  other_index int32 [B] or [B,K]
+    (< 0 or >= B: an empty slot); it is configured on the engine (BatchedNMPC.closed_loop_formation_config: a host copy, synchronous).
+    Differentiable in x0, xr, ur, f, `weights` (installed as plant_force installs them; replaced before the backward: RuntimeError) and
+    Qd / Rd / mass (as closed_loop); the backward is ONE call that carries the gradients across the vehicles on the device.  Held fixed:
+    every tick's linearisation point and final active set, and the r_horiz gates.  `scale` is not differentiated.  Behind a failed vehicle
+    (a NaN state) the weights' gradient leaves out every vehicle that hears it through an open slot, which the per-tick chain does not
+    (include/ndp_nmpc.h): the two routes' weight gradients differ there, and nowhere else by more than the summation's rounding."""
+    return ClosedLoopFormationFunction.apply(x0, engine, xr, ur, other_index, f, weights, Qd, Rd, mass, bool(gate), float(scale), float(dt),
+                                             int(substeps))
