@@ -56,8 +56,8 @@ def windows(tr, ticks, t0=0.0, dt=CP.ts_nmpc, cfg=None):
 
 def true_force(blob, x, idx, gate=True, scale=1.0, r_horiz=DP.r_horiz):
     """The force on the plant: the network at the actual relative state (fp64 difference rounded to fp32), strict gate on the actual xy
-    at r_horiz."""
-    has = idx >= 0
+    at r_horiz.  idx < 0 or >= B: an empty slot (the device's rule)."""
+    has = (idx >= 0) & (idx < len(idx))
     o = np.where(has, idx, np.arange(len(idx)))
     d = x[o] - x
     f = O.mlp_forward(blob, d[:, 0:6].astype(np.float32)).astype(np.float64) * scale

@@ -41,12 +41,12 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.int64 if a.dtype == np.float64 else np.int32)
 
 
-def _engine(ndp, a, N, index="own", load_mlp=True):
+def _engine(ndp, a, N, index="own", load_mlp=True, **kw):
     """A fresh engine: reset to tick 0's window, one warm-up step on tick 0's inputs (a kept set exists), the formation configured
-    (index "own": the inputs'; None: not configured)."""
+    (index "own": the inputs'; None: not configured).  kw: ndp_cfg overrides (the model, r_horiz)."""
     import torch
     n = a["x0"].shape[0]
-    eng = ndp.BatchedNMPC(n, N=N, disturbance=True, load_mlp=load_mlp)
+    eng = ndp.BatchedNMPC(n, N=N, disturbance=True, load_mlp=load_mlp, **kw)
     eng.reset(a["xr"][0], a["ur"][0])
     u0 = torch.empty(n, 4, dtype=torch.float64, device=_dev())
     torch.cuda.synchronize()
@@ -61,7 +61,7 @@ def _state(eng):
     return [_np(v) for v in eng.device_iterate()] + [eng.active_set()[1]]
 
 
-def _loop(eng, a, index, ticks=K, gate=True, scale=1.0):
+def _loop(eng, a, index, ticks=K, gate=True, scale=1.0, dt=R.DT, substeps=R.SUBSTEPS):
     """The host loop of the three existing calls -- plant_force_multi_device, update_device, ndp_plant_step_device -- and its record
     (closed_loop_formation_ref's layout: fp = the forces the device made)."""
     import torch
@@ -80,7 +80,7 @@ def _loop(eng, a, index, ticks=K, gate=True, scale=1.0):
         torch.cuda.synchronize()
         st, it = eng.status()
         eng._check(eng._lib.ndp_plant_step_device(eng._h, Ct.c_void_p(xn.data_ptr()), Ct.c_void_p(u0.data_ptr()), Ct.c_void_p(fp.data_ptr()),
-                                                  R.DT, R.SUBSTEPS, None), "ndp_plant_step_device")
+                                                  float(dt), int(substeps), None), "ndp_plant_step_device")
         eng.synchronize()
         for name, v in (("x", _np(x)), ("force", a["f"][k].astype(np.float64)), ("Xpre", _np(tape[0])), ("Upre", _np(tape[1])),
                         ("act_pre", _np(tape[2])), ("act", eng.active_set()[1]), ("u0", _np(u0)), ("X", _np(X)), ("st", st), ("it", it),
@@ -102,7 +102,7 @@ def _guarded(*shape, dtype=None, fill=-7.0):
     return whole[:rows].view(*shape), whole
 
 
-def _forward(eng, a, N, ticks=K, optional=True, stream=None, gate=True, scale=1.0):
+def _forward(eng, a, N, ticks=K, optional=True, stream=None, gate=True, scale=1.0, dt=R.DT, substeps=R.SUBSTEPS):
     """closed_loop_formation_device into guarded outputs; optional False: d_Xs, d_status and d_tape NULL."""
     import torch
     n = a["x0"].shape[0]
@@ -114,10 +114,10 @@ def _forward(eng, a, N, ticks=K, optional=True, stream=None, gate=True, scale=1.
     torch.cuda.synchronize()
     eng.closed_loop_formation_device(t["x0"], t["xr"], t["ur"], o["xs"][0], o["us"][0], o["fps"][0], f=t["f"],
                                      Xs=o["Xs"][0] if optional else None, status=o["status"][0].view(ticks, n) if optional else None,
-                                     tape=tape, gate=gate, plant_scale=scale, stream=stream)
+                                     tape=tape, gate=gate, plant_scale=scale, dt=dt, substeps=substeps, stream=stream)
     eng.synchronize()
     torch.cuda.synchronize()
-    t.update(xs=o["xs"][0], us=o["us"][0], fps=o["fps"][0], tape=tape, gate=gate, scale=scale)
+    t.update(xs=o["xs"][0], us=o["us"][0], fps=o["fps"][0], tape=tape, gate=gate, scale=scale, dt=dt, substeps=substeps)
     vals = {k: _np(v[0]) for k, v in o.items()}
     if optional:
         vals["status"] = vals["status"].reshape(ticks, n)
@@ -137,7 +137,7 @@ def _reverse(eng, t, N, ups, ask=OUTS, stream=None):
     torch.cuda.synchronize()
     eng.closed_loop_formation_vjp_device(t["x0"], t["xr"], t["ur"], t["xs"], t["us"], t["fps"], t["tape"], f=t["f"], gxs=g[0], gus=g[1],
                                          gXs=g[2], gfps=g[3], status_check=st[0].view(ticks, n), gate=t["gate"], plant_scale=t["scale"],
-                                         stream=stream, **{k: v[0] for k, v in o.items()})
+                                         dt=t["dt"], substeps=t["substeps"], stream=stream, **{k: v[0] for k, v in o.items()})
     eng.synchronize()
     torch.cuda.synchronize()
     for k, v in list(o.items()) + [("status_check", st)]:
@@ -147,9 +147,9 @@ def _reverse(eng, t, N, ups, ask=OUTS, stream=None):
     return out
 
 
-def _ups(n, N, seed=31):
-    G, H, A = R.upstreams(K, n, N, seed=seed)
-    return G, H, A, np.random.default_rng(seed + 1).normal(size=(K, n, 3))
+def _ups(n, N, seed=31, ticks=K):
+    G, H, A = R.upstreams(ticks, n, N, seed=seed)
+    return G, H, A, np.random.default_rng(seed + 1).normal(size=(ticks, n, 3))
 
 
 @pytest.fixture(scope="module")
@@ -188,12 +188,15 @@ def full(ndp, oracle, name, cache):
 
 
 def _errors(g, ref, which, with_w):
-    """{bar: {leaf: rel_err}}: the last tick's gxr, gur, gf under "ext", everything else (and g_w) under "ndp"."""
-    last = K - 1
+    """{bar: {leaf: rel_err}}: the last tick's gxr, gur, gf under "ext", everything else (and g_w) under "ndp"; the ticks are the
+    reference's (one tick: there are no earlier ticks' leaves)."""
+    last = ref["xr"].shape[0] - 1
     ext = dict(xr_last=R.rel_err(g["gxr"][last][which], ref["xr"][last], 1), ur_last=R.rel_err(g["gur"][last][which], ref["ur"][last], 1),
                f_last=R.rel_err(g["gf"][last][which], ref["f"][last], 1))
-    net = dict(x0=R.rel_err(g["gx0"][which], ref["x0"], 1), xr=R.rel_err(g["gxr"][:last, which], ref["xr"][:last], 2),
-               ur=R.rel_err(g["gur"][:last, which], ref["ur"][:last], 2), f=R.rel_err(g["gf"][:last, which], ref["f"][:last], 2))
+    net = dict(x0=R.rel_err(g["gx0"][which], ref["x0"], 1))
+    if last:
+        net.update(xr=R.rel_err(g["gxr"][:last, which], ref["xr"][:last], 2), ur=R.rel_err(g["gur"][:last, which], ref["ur"][:last], 2),
+                   f=R.rel_err(g["gf"][:last, which], ref["f"][:last], 2))
     if with_w:
         net["w"] = R.rel_err(g["gw"], ref["w"], 0)
     return dict(ext=ext, ndp=net)
