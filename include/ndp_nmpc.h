@@ -382,6 +382,28 @@ int ndp_step_jvp_device(ndp_handle *h, const void *d_x0, const void *d_xr, const
                         const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf,
                         void *d_du0, void *d_dX, void *d_dU, void *d_u0_check, void *d_status_check, void *stream);
 
+/* Forward mode along directions of the controller's own numbers as well: the cost weights Qd [10], Rd [4] and the mass -- the transpose of
+ * ndp_step_vjp_model_device's d_gmodel.  ndp_step_jvp_device's arguments, meaning, tape, workspace, outputs and NaN rule, plus
+ *   d_tmodel [B][T][16] fp64, required (-2 without it: "without it: ndp_step_jvp_device"): per instance and direction, columns 0..9 Qd',
+ *   10..13 Rd', 14 mass', 15 not read by the step (the closed loop's plant share, ndp_closed_loop_jvp_model_device).
+ * The four data tangents may all be NULL here.  The model direction ADDS to the data direction (the tangent is linear), so both may be given
+ * together.  Same QP, same blocks, pins held at 0, dx_0 = tx0 or 0; with rho the residual of the NEW iterate (x+ - xr; attitude: E(qr) q+;
+ * inputs: u+ - ur) and s = dt (stage N: 1) the added data are
+ *   gradient rows r < 6: + s Qd'[r] rho_k[r];  attitude rows: + s (E(qr_k)' diag(Qd'[7], Qd'[8], Qd'[9]) E(qr_k) q+_k)[row - 6];
+ *   input rows: + dt Rd'[i] rho_u,k[i] (pinned: 0);  defects, k < N: -(mass' / m^2) [h^2/2 f_k; h f_k; 0] with the fp32 force the step read.
+ * Qd'[6] enters nowhere (its residual is the constant 0): a direction in column 6 alone gives exact zeros, and so does a mass direction
+ * when the step read no force.  T directions in one call are T calls of one, bit for bit.
+ * With d_tmodel all zeros the outputs EQUAL ndp_step_jvp_device's on the same data tangents as numbers, not bit for bit: the added terms are
+ * zeros added to the data entries, which can turn a -0.0 entry into +0.0, so the sign of a zero may differ; no nonzero value differs.
+ * Duality: <gu0, du0> + <gX, dX> + <gU, dU> = <gx0, tx0> + <gxr, txr> + <gur, tur> + <gf, tf> + sum_{j<15} gmodel[j] tmodel[j] against
+ * ndp_step_vjp_model_device on the same tape, to rounding.
+ * Refusals (-2, nothing launched): ndp_step_jvp_device's but for "no tangent"; d_tmodel NULL.  Kernels of their own (rti_mjvp_kernel, N = 20
+ * and the run-time horizon): ndp_step_jvp_device launches what it launched. */
+int ndp_step_jvp_model_device(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
+                              const void *d_X_lin, const void *d_U_lin, const void *d_act_lin, int n_tan,
+                              const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf, const void *d_tmodel,
+                              void *d_du0, void *d_dX, void *d_dU, void *d_u0_check, void *d_status_check, void *stream);
+
 /* Changes the model of a live handle: Qd [10] replaces ndp_cfg.Qd (nmpc_body_rate_ctl.py:48), Rd [4] ndp_cfg.Rd (nmpc_body_rate_ctl.py:49),
  * mass ndp_cfg.mass (fhnp_params.py:9).  Qd / Rd NULL = keep; mass <= 0 or NaN = keep.  Refused with -2 and a reason in ndp_last_error,
  * changing nothing: a non-finite entry, a negative Qd, a non-positive Rd, an infinite mass, and -- with as_iter_max > 0 -- an Rd that breaks
@@ -711,6 +733,21 @@ int ndp_closed_loop_jvp_device(ndp_handle *h, int ticks, double dt, int substeps
                                const void *d_f, const void *d_fp, const void *d_xs, const void *d_us, const void *d_tape, int n_tan,
                                const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf, const void *d_tfp, void *d_dxs,
                                void *d_dus, void *d_dXs, void *d_dUs, void *d_status_check, void *stream);
+/* ndp_closed_loop_jvp_model_device: the same forward mode along directions of the model as well -- how the flight changes with the cost
+ * weights and the mass, the transpose of ndp_closed_loop_vjp_device's d_gmodel.  ndp_closed_loop_jvp_device's arguments, plus
+ *   d_tmodel [B][T][16] fp64, required: per vehicle and direction, constant over the ticks; columns 0..9 Qd', 10..13 Rd', 14 the
+ *   CONTROLLER's mass', 15 the PLANT's mass'.  The handle has one mass: a direction of it goes into both columns; column 15 alone is a
+ *   model mismatch of the plant.  The five data directions may all be NULL.
+ * Per tick the step's forward mode is ndp_step_jvp_model_device's (rti_mjvp_kernel) along (tx, txr[k], tur[k], tf[k], tmodel), and the
+ * plant tick's tangent is taken along tfp[k] - (tmodel[15] / m) fp_k: the plant sees the mass only as fp / m (with d_fp NULL column 15
+ * moves nothing).  The same launches per tick, the same workspace, NaN rule and refusals (but for "no tangent"; -2 also: d_tmodel NULL).
+ * Duality: <G, dxs> + <H, dus> + <A, dXs> = ndp_closed_loop_jvp_device's right side + sum_v <gmodel[v], tmodel[v]> (all 16 columns) against
+ * ndp_closed_loop_vjp_device's d_gmodel on the same record, to rounding. */
+int ndp_closed_loop_jvp_model_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_xr, const void *d_ur,
+                                     const void *d_f, const void *d_fp, const void *d_xs, const void *d_us, const void *d_tape, int n_tan,
+                                     const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf, const void *d_tfp,
+                                     const void *d_tmodel, void *d_dxs, void *d_dus, void *d_dXs, void *d_dUs, void *d_status_check,
+                                     void *stream);
 
 /* ---- the closed loop of a FORMATION in one call per direction: ndp_closed_loop_device with the force on the plant made inside the loop
  * from the neighbours' actual states (ndp_plant_force_multi_device), and its reverse mode across the vehicles.  The controller keeps

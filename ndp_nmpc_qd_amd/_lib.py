@@ -73,6 +73,7 @@ EXPORTS = [
     "ndp_closed_loop_tape_bytes", "ndp_closed_loop_device", "ndp_closed_loop_vjp_device", "ndp_closed_loop_jvp_device",
     "ndp_closed_loop_formation_config", "ndp_plant_force_scatter_device", "ndp_closed_loop_formation_device",
     "ndp_closed_loop_formation_vjp_device",
+    "ndp_step_jvp_model_device", "ndp_closed_loop_jvp_model_device",
 ]
 
 _lib = None
@@ -158,6 +159,7 @@ def load():
     lib.ndp_step_vjp_device.argtypes = [vp] * 18
     lib.ndp_step_vjp_model_device.argtypes = [vp] * 19
     lib.ndp_step_jvp_device.argtypes = [vp] * 8 + [C.c_int] + [vp] * 10
+    lib.ndp_step_jvp_model_device.argtypes = [vp] * 8 + [C.c_int] + [vp] * 11
     lib.ndp_set_model.argtypes = [vp, vp, vp, C.c_double]
     lib.ndp_downwash_vjp_device.argtypes = [vp, vp, C.c_int] + [vp] * 7
     lib.ndp_downwash_jvp_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 5
@@ -246,6 +248,7 @@ def load():
     lib.ndp_closed_loop_device.argtypes = [vp, C.c_int, C.c_double, C.c_int] + [vp] * 11
     lib.ndp_closed_loop_vjp_device.argtypes = [vp, C.c_int, C.c_double, C.c_int] + [vp] * 19
     lib.ndp_closed_loop_jvp_device.argtypes = [vp, C.c_int, C.c_double, C.c_int] + [vp] * 8 + [C.c_int] + [vp] * 11
+    lib.ndp_closed_loop_jvp_model_device.argtypes = [vp, C.c_int, C.c_double, C.c_int] + [vp] * 8 + [C.c_int] + [vp] * 12
     lib.ndp_closed_loop_formation_config.argtypes = [vp, vp, C.c_int]
     lib.ndp_plant_force_scatter_device.argtypes = [vp] * 4
     lib.ndp_closed_loop_formation_device.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double] + [vp] * 11

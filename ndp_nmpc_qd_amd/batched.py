@@ -541,7 +541,7 @@ class BatchedNMPC:
             d(status_check, torch.int32, (K, B)), self._stream(stream)), "ndp_closed_loop_vjp_device")
 
     def closed_loop_jvp_device(self, x0, xr, ur, xs, us, tape, dxs, dus, f=None, fp=None, tx0=None, txr=None, tur=None, tf=None, tfp=None,
-                               dXs=None, dUs=None, status_check=None, n_tan=None, dt=CP.ts_nmpc, substeps=4, stream=None):
+                               dXs=None, dUs=None, status_check=None, n_tan=None, dt=CP.ts_nmpc, substeps=4, stream=None, tmodel=None):
         """Enqueues the forward mode of closed_loop_device on `stream` (ndp_closed_loop_jvp_device; include/ndp_nmpc.h): the inputs as the
         forward took them, its xs, us and tape.  Directions (None = 0, not all None), float64: tx0[B,T,10], txr[ticks,B,T,N+1,10],
         tur[ticks,B,T,N,4], tf[ticks,B,T,N+1,3], tfp[ticks,B,T,3].  Outputs the caller allocates, float64, overwritten: dxs[ticks,B,T,10]
@@ -549,7 +549,9 @@ class BatchedNMPC:
         status_check[ticks,B] int32, optional.  T (1..8) is n_tan when given, else read from dxs.  Every tick's linearisation point and
         final set are held fixed.  Nothing of the engine's state or the tape is written; T directions in one call equal T calls bit for
         bit.  stream None or torch's default: the engine's own stream behind a wait for torch's; read the outputs after
-        engine.synchronize()."""
+        engine.synchronize().
+        tmodel [B,T,16] float64 (given: the call is ndp_closed_loop_jvp_model_device, and the data directions may all be None): the
+        model's direction, constant over the ticks: Qd' [0:10], Rd' [10:14], the controller's mass' [14], the plant's mass' [15]."""
         import torch
         K, args = self._closed_loop_args("closed_loop_jvp_device", x0, xr, ur, f, fp)
         if n_tan is None:
@@ -558,14 +560,15 @@ class BatchedNMPC:
             n_tan = dxs.shape[2]
         B, N, T, d = self.B, self.N, int(n_tan), self._dptr
         self._torch_default_wait(stream)
-        self._check(self._lib.ndp_closed_loop_jvp_device(
+        name = "ndp_closed_loop_jvp_device" if tmodel is None else "ndp_closed_loop_jvp_model_device"
+        model = () if tmodel is None else (d(tmodel, torch.float64, (B, T, 16)),)      # (behind tfp)
+        self._check(getattr(self._lib, name)(
             self._h, K, float(dt), int(substeps), *args, d(xs, torch.float64, (K, B, 10)), d(us, torch.float64, (K, B, 4)),
             d(tape, torch.uint8, (K, self._closed_loop_slot_bytes())), T,
             d(tx0, torch.float64, (B, T, 10)), d(txr, torch.float64, (K, B, T, N + 1, 10)), d(tur, torch.float64, (K, B, T, N, 4)),
-            d(tf, torch.float64, (K, B, T, N + 1, 3)), d(tfp, torch.float64, (K, B, T, 3)),
+            d(tf, torch.float64, (K, B, T, N + 1, 3)), d(tfp, torch.float64, (K, B, T, 3)), *model,
             d(dxs, torch.float64, (K, B, T, 10)), d(dus, torch.float64, (K, B, T, 4)), d(dXs, torch.float64, (K, B, T, N + 1, 10)),
-            d(dUs, torch.float64, (K, B, T, N, 4)), d(status_check, torch.int32, (K, B)), self._stream(stream)),
-            "ndp_closed_loop_jvp_device")
+            d(dUs, torch.float64, (K, B, T, N, 4)), d(status_check, torch.int32, (K, B)), self._stream(stream)), name)
 
     # ---- the closed loop of a formation: the plant force made inside the loop from the configured index, and its reverse mode
     def closed_loop_formation_config(self, other_index):
@@ -1011,18 +1014,25 @@ class BatchedNMPC:
         self._check(getattr(self._lib, name)(self._h, *args), name)
 
     def step_jvp_device(self, x0, xr, ur, tape, tx0=None, txr=None, tur=None, tf=None, f=None, du0=None, dX=None, dU=None,
-                        u0_check=None, status_check=None, stream=None):
+                        u0_check=None, status_check=None, stream=None, tmodel=None):
         """Enqueues the forward-mode derivative of one recorded step on `stream` (ndp_step_jvp_device; include/ndp_nmpc.h): the step is
         recomputed from `tape`, x0, xr, ur and f as step_vjp_device does, and the first-order change of its output along T directions
         (tx0 [B,T,10], txr [B,T,N+1,10], tur [B,T,N,4], tf [B,T,N+1,3]; float64 CUDA tensors, None = 0, not all None) is written into
         du0 [B,T,4], dX [B,T,N+1,10], dU [B,T,N,4] (float64 CUDA tensors the caller allocates; None = not written, not all None).  T
         (1..8) is read from the tangents' second dimension; tangents and outputs without that axis mean T = 1.  u0_check, status_check
-        and stream: as step_vjp_device's.  Nothing of the engine's state is written."""
+        and stream: as step_vjp_device's.  Nothing of the engine's state is written.
+        tmodel [B,T,16] float64 (given: the call is ndp_step_jvp_model_device, and the data tangents may all be None): per instance and
+        direction Qd' [0:10], Rd' [10:14], mass' [14], [15] not read; it adds to the data tangents' direction."""
         import torch
         B, N = self.B, self.N
         self._torch_default_wait(stream)
-        tails = ((10,), (N + 1, 10), (N, 4), (N + 1, 3), (4,), (N + 1, 10), (N, 4))
-        tans = (tx0, txr, tur, tf, du0, dX, dU)
+        tails = [(10,), (N + 1, 10), (N, 4), (N + 1, 3), (4,), (N + 1, 10), (N, 4)]
+        tans = [tx0, txr, tur, tf, du0, dX, dU]
+        name = "ndp_step_jvp_device"
+        if tmodel is not None:
+            tans.insert(4, tmodel)                                      # (behind tf)
+            tails.insert(4, (16,))
+            name = "ndp_step_jvp_model_device"
         # (without the T axis: [B, ...] is [B, 1, ...] as it lies)
         T, shapes = _t_axis_shapes("step_jvp_device", B, [(getattr(t, "shape", None), s, 1) for t, s in zip(tans, tails)])
         d = self._dptr
@@ -1031,7 +1041,7 @@ class BatchedNMPC:
                 d(f, torch.float32, (B, N + 1, 3)), d(X, torch.float64, (B, N + 1, 10)), d(U, torch.float64, (B, N, 4)),
                 d(A, torch.int8, (B, N, 4)), T, *(d(t, torch.float64, s) for t, s in zip(tans, shapes)),
                 d(u0_check, torch.float64, (B, 4)), d(status_check, torch.int32, (B,)), self._stream(stream)]
-        self._check(self._lib.ndp_step_jvp_device(self._h, *args), "ndp_step_jvp_device")
+        self._check(getattr(self._lib, name)(self._h, *args), name)
 
     # ------------------------------------------------------------------ backward pass of the downwash network
     def _other_ptr(self, other, other_index):

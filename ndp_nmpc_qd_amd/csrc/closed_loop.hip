@@ -125,6 +125,7 @@ struct ClTan {
     int T;
     const double *xin, *u, *fp;     // x_k [B][10], u0_k [B][4], fp_k [B][3] or null
     const double *tx, *tfp;         // the tangent of x_k [B][T][10] (d_tx0, then dxs[k-1]; null: 0) and of fp_k [B][T][3] (null: 0)
+    const double *tm;               // the model direction [B][T][16] or null: column 15, the plant's mass, moves the force as -(m' / m) fp_k
     double *du;                     // dus[k] [B][T][4]: the step's du0 as rti_jvp_kernel left it, read; NaN written where the tick failed
     double *dx;                     // out: dxs[k] [B][T][10]
     const int *st;                  // tick k's recomputed status words (its forward mode has run)
@@ -309,6 +310,11 @@ __global__ __launch_bounds__(CL_LANES) void closed_loop_tan_link_kernel(ClTan a)
 #pragma unroll
     for (int j = 0; j < 10; ++j) failed = failed || dx[j] != dx[j];
     if (a.tfp) { dacc[0] = a.tfp[i * 3] * a.p.inv_mass; dacc[1] = a.tfp[i * 3 + 1] * a.p.inv_mass; dacc[2] = a.tfp[i * 3 + 2] * a.p.inv_mass; }
+    if (a.tm && a.fp) {            // the plant sees the mass only as fp / m (plant_acc): along tfp - (m' / m) fp_k
+        const double c = a.tm[i * 16 + 15] * a.p.inv_mass;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) dacc[j] = ((a.tfp ? a.tfp[i * 3 + j] : 0.0) - c * a.fp[v * 3 + j]) * a.p.inv_mass;
+    }
     plant_acc(a.fp, v * 3, a.p.inv_mass, a.p.g, acc);
 #pragma unroll
     for (int j = 0; j < 10; ++j) y[j] = xv[j];
@@ -591,21 +597,24 @@ int ndp_closed_loop_vjp_device(ndp_handle *h, int ticks, double dt, int substeps
                       d_gxs, d_gus, d_gXs, d_gx0, d_gxr, d_gur, d_gf, d_gfp, d_gmodel, d_status_check, nullptr);
 }
 
-int ndp_closed_loop_jvp_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_xr, const void *d_ur,
-                               const void *d_f, const void *d_fp, const void *d_xs, const void *d_us, const void *d_tape, int n_tan,
-                               const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf, const void *d_tfp, void *d_dxs,
-                               void *d_dus, void *d_dXs, void *d_dUs, void *d_status_check, void *stream)
+}  // extern "C"
+
+// model: the entry is ndp_closed_loop_jvp_model_device (rti_mjvp_kernel per tick along the constant d_tmodel [B][T][16], required; its
+// column 15 in the link), else ndp_closed_loop_jvp_device (rti_jvp_kernel)
+static int cl_tangent(ndp_handle *h, Entry &g, const char *name, int ticks, double dt, int substeps, const ClView &v, int n_tan,
+                      const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf, const void *d_tfp, bool model,
+                      const void *d_tmodel, void *d_dxs, void *d_dus, void *d_dXs, void *d_dUs, void *d_status_check)
 {
-    Entry g(h, d_x0 && d_xr && d_ur && d_xs && d_us, stream);
-    if (g.rc) return g.rc;
     const char *own = nullptr;
     if (n_tan < 1 || n_tan > NDP_JVP_MAX_TANGENTS) own = "n_tan must be 1..8 (directions per call)";
-    else if (!d_tx0 && !d_txr && !d_tur && !d_tf && !d_tfp) own = "no tangent given (d_tx0, d_txr, d_tur, d_tf and d_tfp all NULL)";
+    else if (model && !d_tmodel) own = "d_tmodel is required (without it: ndp_closed_loop_jvp_device)";
+    else if (!model && !d_tx0 && !d_txr && !d_tur && !d_tf && !d_tfp) own = "no tangent given (d_tx0, d_txr, d_tur, d_tf and d_tfp all NULL)";
     else if (d_tf && !h->cfg.use_fd) own = "a force tangent (d_tf) needs use_fd = 1 (NDP model)";
     else if (!d_dxs || !d_dus) own = "d_dxs and d_dus are required (the tangents of the two logs)";
-    const ClView v = cl_view(h, d_x0, d_xr, d_ur, d_f, d_fp, d_xs, d_us, d_tape);
-    int rc = cl_deriv_begin(h, "ndp_closed_loop_jvp_device", "derivative", ticks, substeps, v, own);
+    int rc = cl_deriv_begin(h, name, "derivative", ticks, substeps, v, own);
     if (rc) return rc;
+    const RecomputeId kid = model ? RC_MJVP : RC_JVP;
+    const double *tm = (const double *)d_tmodel;
     hipStream_t s = g.s;
     const size_t B = v.B, T = (size_t)n_tan;
     const unsigned cb = cl_copy_blocks(v.itb + v.ab), pb = (unsigned)((B * T + CL_LANES - 1) / CL_LANES);
@@ -626,13 +635,15 @@ int ndp_closed_loop_jvp_device(ndp_handle *h, int ticks, double dt, int substeps
         JvpArgs ja{tx, cl_at((const double *)d_txr, k, T * nxs(h)), cl_at((const double *)d_tur, k, T * nus(h)),
                    cl_at((const double *)d_tf, k, T * nfs(h)), du, cl_at((double *)d_dXs, k, T * nxs(h)), cl_at((double *)d_dUs, k, T * nus(h)),
                    n_tan};
-        if ((rc = recompute_on_workspace(h, s, v.step(k, st), recompute_kernel(RC_JVP, true), recompute_kernel(RC_JVP, false), &ja, nullptr))) return rc;
+        if ((rc = recompute_on_workspace(h, s, v.step(k, st), recompute_kernel(kid, true), recompute_kernel(kid, false), &ja, model ? &tm : nullptr)))
+            return rc;
         ClTan a{};
         a.p = cl_plant(h, dt, substeps, true);
         a.p.plant_blocks = (int)pb;
         a.T = n_tan;
         a.xin = v.x(k); a.u = v.u0(k); a.fp = v.fpk(k);
         a.tx = tx; a.tfp = cl_at((const double *)d_tfp, k, B * T * 3);
+        a.tm = tm;
         a.du = du; a.dx = dxs + (size_t)k * B * T * NX;
         a.st = st ? st : h->dVjpSt;
         const bool more = k + 1 < ticks;
@@ -641,6 +652,31 @@ int ndp_closed_loop_jvp_device(ndp_handle *h, int ticks, double dt, int substeps
         NDP_HIP(h, hipGetLastError());
     }
     return g.noted(0);
+}
+
+extern "C" {
+
+int ndp_closed_loop_jvp_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_xr, const void *d_ur,
+                               const void *d_f, const void *d_fp, const void *d_xs, const void *d_us, const void *d_tape, int n_tan,
+                               const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf, const void *d_tfp, void *d_dxs,
+                               void *d_dus, void *d_dXs, void *d_dUs, void *d_status_check, void *stream)
+{
+    Entry g(h, d_x0 && d_xr && d_ur && d_xs && d_us, stream);
+    if (g.rc) return g.rc;
+    return cl_tangent(h, g, "ndp_closed_loop_jvp_device", ticks, dt, substeps, cl_view(h, d_x0, d_xr, d_ur, d_f, d_fp, d_xs, d_us, d_tape), n_tan,
+                      d_tx0, d_txr, d_tur, d_tf, d_tfp, false, nullptr, d_dxs, d_dus, d_dXs, d_dUs, d_status_check);
+}
+
+int ndp_closed_loop_jvp_model_device(ndp_handle *h, int ticks, double dt, int substeps, const void *d_x0, const void *d_xr, const void *d_ur,
+                                     const void *d_f, const void *d_fp, const void *d_xs, const void *d_us, const void *d_tape, int n_tan,
+                                     const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf, const void *d_tfp,
+                                     const void *d_tmodel, void *d_dxs, void *d_dus, void *d_dXs, void *d_dUs, void *d_status_check,
+                                     void *stream)
+{
+    Entry g(h, d_x0 && d_xr && d_ur && d_xs && d_us, stream);
+    if (g.rc) return g.rc;
+    return cl_tangent(h, g, "ndp_closed_loop_jvp_model_device", ticks, dt, substeps, cl_view(h, d_x0, d_xr, d_ur, d_f, d_fp, d_xs, d_us, d_tape),
+                      n_tan, d_tx0, d_txr, d_tur, d_tf, d_tfp, true, d_tmodel, d_dxs, d_dus, d_dXs, d_dUs, d_status_check);
 }
 
 // ---- the formation: the plant force made from the states inside the loop, and the reverse sweep across the vehicles

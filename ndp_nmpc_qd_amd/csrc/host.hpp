@@ -274,7 +274,7 @@ struct Tape {
     void *u0_check, *status_check;
 };
 
-enum RecomputeId { RC_WVJP, RC_JVP, RC_VJP };   // the derivative kernels that recompute a recorded step (rti_kernels.hip: recompute_kernel)
+enum RecomputeId { RC_WVJP, RC_JVP, RC_VJP, RC_MJVP };   // the derivative kernels that recompute a recorded step (rti_kernels.hip: recompute_kernel)
 
 // ---- host functions one unit calls in another (no locking, no sync: the caller holds h->mu).  C linkage like the entry points they
 // sit beside; hidden, so not exported.

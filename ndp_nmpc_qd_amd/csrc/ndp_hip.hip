@@ -1189,24 +1189,44 @@ int ndp_step_vjp_model_device(ndp_handle *h, const void *d_x0, const void *d_xr,
 }
 
 // ---- forward mode of the control step (rti_jvp_kernel, RtiWave::jvp_out): the adjoint's recompute, workspace and tape rules
+// model: the entry is ndp_step_jvp_model_device (rti_mjvp_kernel; d_tmodel required, the data tangents may all be NULL), else
+// ndp_step_jvp_device (rti_jvp_kernel)
+static int step_jvp(ndp_handle *h, const Tape &t, int n_tan, const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf,
+                    void *d_du0, void *d_dX, void *d_dU, void *stream, bool model, const void *d_tmodel)
+{
+    Entry g(h, true, stream);
+    if (g.rc) return g.rc;
+    const char *own = nullptr;
+    if (n_tan < 1 || n_tan > NDP_JVP_MAX_TANGENTS) own = "n_tan must be 1..8 (directions per call)";
+    else if (!model && !d_tx0 && !d_txr && !d_tur && !d_tf) own = "no tangent (tx0, txr, tur and tf all NULL)";
+    else if (!d_du0 && !d_dX && !d_dU) own = "no output asked for (du0, dX and dU all NULL)";
+    std::string why = recompute_refusal(h->cfg, "derivative", t, own);
+    if (why.empty() && d_tf && !h->cfg.use_fd) why = "a force tangent needs use_fd = 1 (NDP model)";
+    if (why.empty() && model && !d_tmodel) why = "tmodel is required (without it: ndp_step_jvp_device)";
+    if (!why.empty()) { h->err = std::string(model ? "ndp_step_jvp_model_device: " : "ndp_step_jvp_device: ") + why; return -2; }
+    JvpArgs ja{(const double *)d_tx0, (const double *)d_txr, (const double *)d_tur, (const double *)d_tf, (double *)d_du0, (double *)d_dX,
+               (double *)d_dU, n_tan};
+    const double *tm = (const double *)d_tmodel;
+    if (model) return recompute_launch(h, g, t, recompute_kernel(RC_MJVP, true), recompute_kernel(RC_MJVP, false), &ja, &tm);
+    return recompute_launch(h, g, t, recompute_kernel(RC_JVP, true), recompute_kernel(RC_JVP, false), &ja, nullptr);
+}
+
 int ndp_step_jvp_device(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
                         const void *d_X_lin, const void *d_U_lin, const void *d_act_lin, int n_tan,
                         const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf,
                         void *d_du0, void *d_dX, void *d_dU, void *d_u0_check, void *d_status_check, void *stream)
 {
-    Entry g(h, true, stream);
-    if (g.rc) return g.rc;
-    const Tape t{d_x0, d_xr, d_ur, d_f, d_X_lin, d_U_lin, d_act_lin, d_u0_check, d_status_check};
-    const char *own = nullptr;
-    if (n_tan < 1 || n_tan > NDP_JVP_MAX_TANGENTS) own = "n_tan must be 1..8 (directions per call)";
-    else if (!d_tx0 && !d_txr && !d_tur && !d_tf) own = "no tangent (tx0, txr, tur and tf all NULL)";
-    else if (!d_du0 && !d_dX && !d_dU) own = "no output asked for (du0, dX and dU all NULL)";
-    std::string why = recompute_refusal(h->cfg, "derivative", t, own);
-    if (why.empty() && d_tf && !h->cfg.use_fd) why = "a force tangent needs use_fd = 1 (NDP model)";
-    if (!why.empty()) { h->err = "ndp_step_jvp_device: " + why; return -2; }
-    JvpArgs ja{(const double *)d_tx0, (const double *)d_txr, (const double *)d_tur, (const double *)d_tf, (double *)d_du0, (double *)d_dX,
-               (double *)d_dU, n_tan};
-    return recompute_launch(h, g, t, recompute_kernel(RC_JVP, true), recompute_kernel(RC_JVP, false), &ja, nullptr);
+    return step_jvp(h, Tape{d_x0, d_xr, d_ur, d_f, d_X_lin, d_U_lin, d_act_lin, d_u0_check, d_status_check}, n_tan, d_tx0, d_txr, d_tur, d_tf,
+                    d_du0, d_dX, d_dU, stream, false, nullptr);
+}
+
+int ndp_step_jvp_model_device(ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f,
+                              const void *d_X_lin, const void *d_U_lin, const void *d_act_lin, int n_tan,
+                              const void *d_tx0, const void *d_txr, const void *d_tur, const void *d_tf, const void *d_tmodel,
+                              void *d_du0, void *d_dX, void *d_dU, void *d_u0_check, void *d_status_check, void *stream)
+{
+    return step_jvp(h, Tape{d_x0, d_xr, d_ur, d_f, d_X_lin, d_U_lin, d_act_lin, d_u0_check, d_status_check}, n_tan, d_tx0, d_txr, d_tur, d_tf,
+                    d_du0, d_dX, d_dU, stream, true, d_tmodel);
 }
 
 // ---- the model of a live handle: cost weights and mass

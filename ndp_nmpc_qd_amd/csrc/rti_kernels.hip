@@ -5,7 +5,8 @@
 //                 QMODE 1 / 2: producer / consumer of the work list (instances whose QP needs the interior point).
 //                 TICK: a whole control tick of ndp_tick in the one launch (tick_wave.hpp).
 //   rti_sens_kernel / rti_psens_kernel : the step with its initial-state / parameter sensitivities
-//   rti_vjp_kernel / rti_wvjp_kernel / rti_jvp_kernel : the step recomputed from a tape, then its adjoint / forward-mode derivative
+//   rti_vjp_kernel / rti_wvjp_kernel / rti_jvp_kernel / rti_mjvp_kernel : the step recomputed from a tape, then its adjoint / forward-mode
+//                 derivative (w, m: with the cost weights and the mass)
 // This unit is by far the longest compile of the library, and host code elsewhere does not name a kernel of it: a table row (RtiId,
 // rti_table.hpp) goes through launch_kern, a derivative kernel through recompute_kernel, so an edit of the host's units leaves it alone.
 #include <hip/hip_runtime.h>
@@ -167,6 +168,23 @@ __global__ __launch_bounds__(256) void rti_jvp_kernel(KernArgs ka, JvpArgs ja)
     double x0v;
     Prog::issue_first(P, io, inb, x0v);
     Prog::template run<false, true, false, false, false, false, true>(P, io, lds, inb, x0v, nullptr, nullptr, nullptr, nullptr, &jo);
+}
+
+// Forward mode with directions of the cost weights and the mass beside the data's (ndp_step_jvp_model_device, RtiWave::jvp_out<true>):
+// tmodel [B][T][16] = q' [10] | r' [4] | m' | (15: not read by the step), instance-major like the other tangents.  Kernels of their own,
+// so that rti_jvp_kernel stays the code it was.
+template <int NC>
+__global__ __launch_bounds__(256) void rti_mjvp_kernel(KernArgs ka, JvpArgs ja, const double *tmodel)
+{
+    NDP_RECOMPUTE_PROLOGUE
+    const size_t i = (size_t)inst * (size_t)ja.T, nx = (size_t)(N + 1) * NX, nu = (size_t)N * NU, nf = (size_t)(N + 1) * 3;
+    const JvpIo jo{ja.tx0 ? ja.tx0 + i * NX : nullptr, ja.txr ? ja.txr + i * nx : nullptr, ja.tur ? ja.tur + i * nu : nullptr,
+                   ja.tf ? ja.tf + i * nf : nullptr, ja.du0 ? ja.du0 + i * NU : nullptr, ja.dX ? ja.dX + i * nx : nullptr,
+                   ja.dU ? ja.dU + i * nu : nullptr, ja.T, tmodel + i * 16};
+    typename Prog::InBuf inb;
+    double x0v;
+    Prog::issue_first(P, io, inb, x0v);
+    Prog::template run<false, true, false, false, false, false, true, true>(P, io, lds, inb, x0v, nullptr, nullptr, nullptr, nullptr, &jo);
 }
 
 #undef NDP_RECOMPUTE_PROLOGUE
@@ -388,10 +406,15 @@ void launch_kern(const ndp_handle *h, RtiId id, hipStream_t s, KernArgs &ka, Sen
 }
 
 // The derivative kernels that recompute a recorded step (ndp_hip.hip: recompute_launch), by RecomputeId; n20: the compile-time N = 20.
+// lds: the dynamic-LDS ceiling to set instead of the creating handle's own bytes.  The attribute belongs to the function, not to a handle: set
+// to the most any handle asks for (ndp_create halves the waves until a workgroup fits 160 KiB), a handle of a short horizon created after one
+// of a long horizon cannot lower it under the first one's launches of the shared <0> kernel.
+// (The order of the rows is RecomputeId's.)
 static const struct { const void *fn20, *fn0; int lds; const char *set; } k_recompute[] = {
     {(const void *)rti_wvjp_kernel<20>, (const void *)rti_wvjp_kernel<0>, 160 * 1024, "hipFuncSetAttribute(rti_wvjp_kernel)"},   // (ndp_step_vjp_model_device)
     {(const void *)rti_jvp_kernel<20>, (const void *)rti_jvp_kernel<0>, 0, "hipFuncSetAttribute(rti_jvp_kernel)"},                // (forward mode: ndp_step_jvp_device)
     {(const void *)rti_vjp_kernel<20>, (const void *)rti_vjp_kernel<0>, 0, "hipFuncSetAttribute(rti_vjp_kernel)"},                // (the adjoint: ndp_step_vjp_device)
+    {(const void *)rti_mjvp_kernel<20>, (const void *)rti_mjvp_kernel<0>, 160 * 1024, "hipFuncSetAttribute(rti_mjvp_kernel)"},    // (ndp_step_jvp_model_device)
 };
 const void *recompute_kernel(RecomputeId id, bool n20) { return n20 ? k_recompute[id].fn20 : k_recompute[id].fn0; }
 

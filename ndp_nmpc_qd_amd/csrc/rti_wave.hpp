@@ -178,11 +178,13 @@ struct VjpIo {
 };
 // Forward-mode derivative (Jacobian-vector product) of the step's QP (RtiWave::jvp_out), one instance's views, T directions per call.
 // Tangents: tx0 [T][10], txr [T][N+1][10], tur [T][N][4], tf [T][N+1][3] (null = 0); outputs: du0 [T][4], dX [T][N+1][10], dU [T][N][4]
-// (null = not written).
+// (null = not written).  tmodel [T][16]: the directions of the cost weights and the mass, q' [10] | r' [4] | m' | (15: not read); read by
+// jvp_out<true> (rti_mjvp_kernel) only.
 struct JvpIo {
     const double *tx0, *txr, *tur, *tf;
     double *du0, *dX, *dU;
     int T;
+    const double *tmodel = nullptr;
 };
 // *RtiIo::iters = interior-point iterations of the step (low half) + Riccati sweeps its QP_AUTO solves took before them (high half);
 // COND_ACCEPTED in the sweep count (config 5's study): a condensed solve's result was kept
@@ -1985,7 +1987,9 @@ struct RtiWave {
     // VJP (rti_vjp_kernel): after the step, the adjoint of its last QP contracted with an upstream gradient (vjp_out) into *vjp.
     // WVJP (rti_wvjp_kernel, with VJP): the same pass also gives the gradient in the cost weights and the mass into gmodel [16].
     // JVP (rti_jvp_kernel): after the step, the directional derivatives of its last QP along the caller's tangents (jvp_out) into *jvp.
-    template <bool DEFER, bool IPM_RARE = false, bool SENS = false, bool PSENS = false, bool VJP = false, bool WVJP = false, bool JVP = false>
+    // MJVP (rti_mjvp_kernel, with JVP): the directions carry one of the cost weights and the mass as well (jvp_out<true>, jvp->tmodel).
+    template <bool DEFER, bool IPM_RARE = false, bool SENS = false, bool PSENS = false, bool VJP = false, bool WVJP = false, bool JVP = false,
+              bool MJVP = false>
     static NDP_D bool run(const RtiParams &P, const RtiIo &io, lp lds, InBuf &inb, vd x0v, const SensIo *sens = nullptr,
                           const PSensIo *psens = nullptr, const VjpIo *vjp = nullptr, double *gmodel = nullptr,
                           [[maybe_unused]] const JvpIo *jvp = nullptr)
@@ -2213,7 +2217,8 @@ struct RtiWave {
             else if (vjp) vjp_out(P, m, T, lds, io, A, zlast, status != 0, *vjp);
         }
         if constexpr (JVP) {
-            if (jvp) jvp_out(P, m, T, lds, io, A, zlast, status != 0, *jvp);
+            if constexpr (MJVP) { if (jvp) jvp_out<true>(P, m, T, lds, io, A, zlast, status != 0, *jvp); }
+            else if (jvp) jvp_out(P, m, T, lds, io, A, zlast, status != 0, *jvp);
         }
         if (io.f_late) W::late_publish(late_prev, io.late_gsize, io.late_done_word);
         return false;
@@ -2646,6 +2651,16 @@ struct RtiWave {
     // directions in one call are T calls of one, bit for bit.
     // LDS after the commit: qr and q+ in rows 0..3 / 6..9 of XI (as vjp_out), formed before the first tangent sweep overwrites ZX|ZU; the
     // final set in AS.  A nonzero status or a failed factorisation: NaN in every output.
+    // MD (rti_mjvp_kernel): direction d also carries theta' = jo.tmodel[d] = q' [10] | r' [4] | m' of the cost weights and the mass (entry 15 is
+    // not read), which ADDS to the data above -- the transposes of vjp_out<true>'s terms.  The cost is linear in the weights and the force
+    // enters as f / m only, so with rho = x+ - xr, u+ - ur the residual of the NEW iterate:
+    //     gradient rows r < 6: + s q'_r rho_k[r];  attitude rows: + s (E(qr_k)' diag(q'_7, q'_8, q'_9) E(qr_k) q+_k)[row - 6]  (q'_6 enters nowhere);
+    //     input rows: + dt r'_i rho_u,k[i] (pinned: 0);  defects: - (m' / m^2) [h^2/2 f_k; h f_k; 0] (the fp32 force the step read; none: nothing).
+    // rho is formed while XI|UI and the step still stand (as WM forms it) and parked where no tangent sweep writes: rho_x in CX, rho_u in CU
+    // (after an interior-point finish that is the step itself: overwritten element by element, in place); f is the caller's array, read again
+    // in every round.  No value rides in registers across the sweeps, and every round reads the same parked values, so T directions stay T
+    // calls of one.
+    template <bool MD = false>
     static NDP_D void jvp_out(const RtiParams &P, const LdsMap &m, const Tables &T, lp lds, const RtiIo &io, const ActSet &A, int zsrc,
                               bool bad, const JvpIo &jo)
     {
@@ -2667,6 +2682,26 @@ struct RtiWave {
             }
         };
         if (bad) { nan_out(); return; }
+        [[maybe_unused]] const bool have_f = P.use_fd && io.f;
+        if constexpr (MD) {
+            // rho = x+ - xr (rows 0..5) into CX and u+ - ur into CU, while XI|UI and the step still stand.  Element by element and in place
+            // where the step is CX|CU itself: a lane reads the element it writes, and only the lane that owns the element writes it (a
+            // clipped lane of a later round would read rho for the step).  Rows 6..9 of the step stay: the parking below reads them.
+            NDP_KEEP_LOOP
+            for (int t = 0; t * 64 < nxr; ++t) {
+                vi e = W::imin(lane + 64 * t, nxr - 1);
+                vi k = (e * 6554) >> 16, row = e - k * 10;     // e / 10, e < 16 384
+                vd rho = W::ld(lds, e + m.XI) + W::ld(lds, e + zsrc) - W::gldu(io.xr, e);
+                W::stp(lds, e + m.CX, rho, row < 6 && lane + 64 * t < nxr);
+            }
+            NDP_KEEP_LOOP
+            for (int t = 0; t * 64 < nur; ++t) {
+                vi e = W::imin(lane + 64 * t, nur - 1);
+                vd rho = W::ld(lds, e + m.UI) + W::ld(lds, e + (zsrc + nxr)) - W::gldu(io.ur, e);
+                W::stp(lds, e + m.CU, rho, lane + 64 * t < nur);
+            }
+            W::sync();
+        }
         // (psens_out's parking of the set and of qr, q+, repeated as text here and in vjp_out: keep the three in step; why, there)
         for (int t = 0; t < RUA; ++t) {                        // the final set, 0 / 1 per input bound
             vi e = a_elem(P, lane, t);
@@ -2707,9 +2742,18 @@ struct RtiWave {
                 for (int a = 0; a < 3; ++a) att = att + (tc[a] * ev[a] + ec[a] * tv[a]) * P.Qd[7 + a];
                 const vd s = W::sel(k < N, vd(h), vd(1.0));
                 const vd qd = W::ld(lds, row + (m.KC + int(KC_QD)));
-                W::st(lds, k * int(CB_STRIDE) + row + (m.CB + int(CB_QE)), W::sel(row < 6, vd(0.0) - tr * qd * s, att * s));
+                vd qe = W::sel(row < 6, vd(0.0) - tr * qd * s, att * s);
+                if constexpr (MD) {                            // + s q'_row rho_k[row]; attitude rows: + s (E' diag(q'_7..9) E q+)[row - 6]
+                    vd ma = vd(0.0);
+                    for (int a = 0; a < 3; ++a) ma = ma + ec[a] * ev[a] * W::gldu(jo.tmodel, vi(7 + a + d * 16));
+                    qe = qe + W::sel(row < 6, W::gldu(jo.tmodel, row + d * 16) * W::ld(lds, e + m.CX), ma) * s;
+                }
+                W::st(lds, k * int(CB_STRIDE) + row + (m.CB + int(CB_QE)), qe);
                 const vi c3 = W::sel(row < 3, row, W::sel(row < 6, row - 3, vi(0))), kf = W::imin(k, vi(N - 1));
-                const vd tf = jo.tf ? W::gldu(jo.tf, kf * 3 + c3 + d * nf) * P.inv_mass : vd(0.0);
+                vd tf = jo.tf ? W::gldu(jo.tf, kf * 3 + c3 + d * nf) * P.inv_mass : vd(0.0);
+                if constexpr (MD) {                            // - (m' / m^2) f_k
+                    if (have_f) tf = tf - W::gldfu(io.f, kf * 3 + c3) * (P.inv_mass * P.inv_mass) * W::gldu(jo.tmodel, vi(14 + d * 16));
+                }
                 W::stp(lds, kf * int(MB_STRIDE) + row + (m.MB + int(MB_B)),
                        W::sel(row < 3, tf * (0.5 * h * h), W::sel(row < 6, tf * h, vd(0.0))), k < N);
             }
@@ -2719,7 +2763,9 @@ struct RtiWave {
                 const vd tu = jo.tur ? W::gldu(jo.tur, e + d * nur) : vd(0.0);
                 const vb pin = !(W::ld(lds, e + m.AS) == 0.0);
                 const vd rd = W::ld(lds, (e & 3) + (m.KC + int(KC_RD)));
-                W::st(lds, (e >> 2) * int(CB_STRIDE) + (e & 3) + (m.CB + int(CB_RE)), W::sel(pin, vd(0.0), vd(0.0) - tu * rd * h));
+                vd re = vd(0.0) - tu * rd * h;
+                if constexpr (MD) re = re + W::gldu(jo.tmodel, (e & 3) + (10 + d * 16)) * W::ld(lds, e + m.CU) * h;   // + dt r'_i rho_u,k[i]
+                W::st(lds, (e >> 2) * int(CB_STRIDE) + (e & 3) + (m.CB + int(CB_RE)), W::sel(pin, vd(0.0), re));
             }
             {
                 const vi r = W::imin(ln, vi(NX - 1));

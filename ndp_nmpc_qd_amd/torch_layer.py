@@ -218,25 +218,72 @@ def control_step_trajectory(engine, x0, xr, ur, f=None, other=None, ego_xy=None)
     return ControlStepTrajectoryFunction.apply(x0, engine, xr, ur, f, other, ego_xy)
 
 
-def control_step_jvp(engine, x0, xr, ur, tangents, f=None):
+def model_tangent(tQd=None, tRd=None, tmass=None):
+    """A direction of the model as the forward-mode calls take it (tmodel): [..., 16] float64 = tQd [..., 10] | tRd [..., 4] | tmass [...]
+    twice -- column 14 is the controller's mass, column 15 the plant's, and an engine has one mass, so its direction goes into both.
+    Each part may be None (= 0, not all three); the leading dimensions ([], [T] or [B,T]) must agree."""
+    parts = [None if t is None else torch.as_tensor(t).detach().to(torch.float64) for t in (tQd, tRd, tmass)]
+    leads = {tuple(p.shape[:-1]) if n else tuple(p.shape) for p, n in zip(parts, (10, 4, 0)) if p is not None}
+    if len(leads) != 1:
+        raise ValueError("model_tangent: " + ("no part given (tQd, tRd and tmass all None)" if not leads else
+                                              f"the parts disagree on the leading dimensions ({sorted(leads)})"))
+    first = next(p for p in parts if p is not None)
+    out = torch.zeros(leads.pop() + (16,), dtype=torch.float64, device=first.device)
+    if parts[0] is not None:
+        out[..., 0:10] = parts[0]
+    if parts[1] is not None:
+        out[..., 10:14] = parts[1]
+    if parts[2] is not None:
+        out[..., 14] = parts[2]
+        out[..., 15] = parts[2]
+    return out
+
+
+def _model_direction(who, tmodel, B, T, device):
+    """tmodel [16], [T,16] or [B,T,16] as the contiguous float64 [B,T,16] the device calls take (T None: read from tmodel, 1 for [16]).
+    Returns (tensor, whether it came with the T axis)."""
+    tm = torch.as_tensor(tmodel).detach().to(device=device, dtype=torch.float64)
+    if tm.dim() not in (1, 2, 3) or tm.shape[-1] != 16 or (tm.dim() == 3 and tm.shape[0] != B):
+        raise ValueError(f"{who}: tmodel must be [16], [T,16] or [B,T,16], got {tuple(tm.shape)}")
+    had = tm.dim() > 1
+    Tm = int(tm.shape[-2]) if had else (1 if T is None else T)
+    if T is not None and Tm != T:
+        raise ValueError(f"{who}: tmodel has {Tm} directions, the other tangents {T}")
+    return tm.expand(B, Tm, 16).contiguous(), had
+
+
+def control_step_jvp(engine, x0, xr, ur, tangents, f=None, tmodel=None):
     """(u0, X, U, du0, dX, dU): the engine's control step at x0 with its new iterate, and the first-order change of all three along the
     directions tangents = (tx0, txr, tur, tf) (forward mode: BatchedNMPC.step_jvp_device; float64 CUDA tensors [B,T,...] or, for one
     direction, [B,...]; None = 0).  The tape is recorded, the ordinary step runs, then the derivative on the same stream.  The outputs carry
     the tangents' T axis: a tangent without it gives du0 [B,4], dX [B,N+1,10], dU [B,N,4].  No autograd hookup: nothing here is recorded in
-    a graph."""
+    a graph.
+    tmodel ([16], [T,16] or [B,T,16]; model_tangent builds one): the direction of the cost weights and the mass, added to the data's
+    (ndp_step_jvp_model_device); with it `tangents` may be all None, and [16] counts as a direction without the T axis."""
     x0, xr, ur, fd = _det(x0), _det(xr), _det(ur), _det(f)
     tans = [None if t is None else _det(t).to(torch.float64) for t in tangents]
     given = [(t, n) for t, n in zip(tans, (2, 3, 3, 3)) if t is not None]
-    if not given:
+    if not given and tmodel is None:
         raise ValueError("control_step_jvp: no tangent (tx0, txr, tur and tf all None)")
     B, N = x0.shape[0], xr.shape[1] - 1
     lead = (B,) + tuple({int(t.shape[1]) for t, n in given if t.dim() == n + 1})[:1]
+    tm = None
+    if tmodel is not None:
+        # every tensor of this call gets the T axis; the outputs lose it again if no direction came with it
+        tm, had = _model_direction("control_step_jvp", tmodel, B, lead[1] if len(lead) > 1 else (1 if given else None), x0.device)
+        tans = [None if t is None else (t.unsqueeze(1) if t.dim() == n else t).contiguous() for t, n in zip(tans, (2, 3, 3, 3))]
+        squeeze, lead = len(lead) == 1 and not had, (B, int(tm.shape[1]))
     stream, default = _cuda_stream(x0)
     tape, u0, X, U = _taped_step(engine, stream, default, x0, xr, ur, f=fd)
     du0, dX, dU = (torch.empty(lead + s, dtype=torch.float64, device=x0.device) for s in ((4,), (N + 1, 10), (N, 4)))
-    engine.step_jvp_device(x0, xr, ur, tape, *tans, f=fd, du0=du0, dX=dX, dU=dU, stream=stream)
+    if tm is None:
+        engine.step_jvp_device(x0, xr, ur, tape, *tans, f=fd, du0=du0, dX=dX, dU=dU, stream=stream)
+    else:
+        engine.step_jvp_device(x0, xr, ur, tape, *tans, f=fd, du0=du0, dX=dX, dU=dU, stream=stream, tmodel=tm)
     if default:
         engine.synchronize()
+    if tm is not None and squeeze:
+        du0, dX, dU = du0[:, 0], dX[:, 0], dU[:, 0]
     return u0, X, U, du0, dX, dU
 
 
@@ -1109,14 +1156,17 @@ def closed_loop(engine, x0, xr, ur, f=None, fp=None, Qd=None, Rd=None, mass=None
     return ClosedLoopFunction.apply(x0, engine, xr, ur, f, fp, Qd, Rd, mass, float(dt), int(substeps))
 
 
-def closed_loop_jvp(engine, x0, xr, ur, tangents, f=None, fp=None, dt=CP.ts_nmpc, substeps=4):
+def closed_loop_jvp(engine, x0, xr, ur, tangents, f=None, fp=None, dt=CP.ts_nmpc, substeps=4, tmodel=None):
     """(xs, us, Xs, dxs, dus, dXs): closed_loop's values and their first-order change along tangents = (tx0, txr, tur, tf, tfp) (forward
     mode: ONE BatchedNMPC.closed_loop_device call with a tape, then ONE BatchedNMPC.closed_loop_jvp_device call).  tx0 [B,T,10], txr
     [ticks,B,T,N+1,10], tur [ticks,B,T,N,4], tf [ticks,B,T,N+1,3] (the direction of the force the controller sees, float64; it needs a
     use_fd engine), tfp [ticks,B,T,3]; each may be None (= 0, not all five) and each may come without the T axis -- then dxs [ticks,B,10],
     dus [ticks,B,4] and dXs [ticks,B,N+1,10] come without it if none has it, else dxs [ticks,B,T,10], dus [ticks,B,T,4], dXs
     [ticks,B,T,N+1,10].  T <= 8.  Every tick's linearisation point and final active set are held fixed, as in every derivative here.  No
-    autograd hookup.  Like closed_loop, every call advances the engine's iterate and kept sets."""
+    autograd hookup.  Like closed_loop, every call advances the engine's iterate and kept sets.
+    tmodel ([16], [T,16] or [B,T,16]; model_tangent builds one): the direction of the cost weights and the mass, constant over the ticks and
+    added to the data's (ndp_closed_loop_jvp_model_device: column 14 the controller's mass, 15 the plant's); with it `tangents` may be all
+    None, and [16] counts as a direction without the T axis."""
     x0d, xrd, urd, fd, fpd = _det(x0), _det(xr), _det(ur), _det(f), _det(fp)
     ts, Ts, had = [], set(), False
     for t, n, axis in zip(tangents, (2, 4, 4, 4, 3), (1, 2, 2, 2, 2)):   # (dimensions without the T axis, and where it sits)
@@ -1131,18 +1181,22 @@ def closed_loop_jvp(engine, x0, xr, ur, tangents, f=None, fp=None, dt=CP.ts_nmpc
             Ts.add(int(t.shape[axis]))
             t = t.contiguous()
         ts.append(t)
-    if not Ts:
+    if not Ts and tmodel is None:
         raise ValueError("closed_loop_jvp: no tangent (all None)")
     if len(Ts) > 1:
         raise ValueError(f"closed_loop_jvp: the tangents disagree on the number of directions ({sorted(Ts)})")
-    T, K, B, N = Ts.pop(), xrd.shape[0], xrd.shape[1], xrd.shape[2] - 1
+    K, B, N = xrd.shape[0], xrd.shape[1], xrd.shape[2] - 1
+    T, kw = (Ts.pop() if Ts else None), {}
+    if tmodel is not None:
+        kw["tmodel"], had_m = _model_direction("closed_loop_jvp", tmodel, B, T, x0d.device)
+        T, had = int(kw["tmodel"].shape[1]), had or had_m
     stream, default, _ = _enter(engine, x0d)
     new = lambda *s: torch.empty(s, dtype=torch.float64, device=x0d.device)  # noqa: E731
     xs, us, Xs, tape = new(K, B, 10), new(K, B, 4), new(K, B, N + 1, 10), engine.closed_loop_tape(K)
     dxs, dus, dXs = new(K, B, T, 10), new(K, B, T, 4), new(K, B, T, N + 1, 10)
     engine.closed_loop_device(x0d, xrd, urd, xs, us, f=fd, fp=fpd, Xs=Xs, tape=tape, dt=dt, substeps=substeps, stream=stream)
     engine.closed_loop_jvp_device(x0d, xrd, urd, xs, us, tape, dxs, dus, f=fd, fp=fpd, tx0=ts[0], txr=ts[1], tur=ts[2], tf=ts[3], tfp=ts[4],
-                                  dXs=dXs, n_tan=T, dt=dt, substeps=substeps, stream=stream)
+                                  dXs=dXs, n_tan=T, dt=dt, substeps=substeps, stream=stream, **kw)
     if default:
         engine.synchronize()
     return (xs, us, Xs) + ((dxs, dus, dXs) if had else (dxs[:, :, 0], dus[:, :, 0], dXs[:, :, 0]))
