@@ -300,29 +300,37 @@ def _params(test):
 
 
 def test_every_recompute_kernel_has_a_device_case_at_every_wave_count_it_reaches():
-    """RECOMPUTE_CASES of the device module: the six recompute kernels (rti_vjp_kernel, rti_wvjp_kernel, rti_jvp_kernel, each for N = 20
-    and for the run-time horizon) at every instances-per-workgroup count ndp_create gives their horizons -- N = 20: 4, and 2 under
-    NDP_DEV_WAVES; the run-time horizons: 4 (N <= 19), 2 (N = 21..27), and 1 under NDP_DEV_WAVES -- each with a test that exists."""
-    kernels = [f"{k}<{nc}>" for k in ("rti_vjp_kernel", "rti_wvjp_kernel", "rti_jvp_kernel") for nc in (20, 0)]
+    """RECOMPUTE_CASES of the device module: the eight recompute kernels (rti_vjp_kernel, rti_wvjp_kernel, rti_jvp_kernel, rti_mjvp_kernel,
+    each for N = 20 and for the run-time horizon) at every instances-per-workgroup count ndp_create gives their horizons -- N = 20: 4, and
+    2 under NDP_DEV_WAVES; the run-time horizons: 4 (N <= 19), 2 (N = 21..27), and 1 under NDP_DEV_WAVES -- each with a test that exists,
+    in the device module or (rti_mjvp_kernel's reference rows) in tests/test_step_model_jvp_edges_gpu.py."""
+    import importlib
+    M = importlib.import_module(G.MJVP_MODULE)
+    recompute = ("rti_vjp_kernel", "rti_wvjp_kernel", "rti_jvp_kernel", "rti_mjvp_kernel")
+    kernels = [f"{k}<{nc}>" for k in recompute for nc in (20, 0)]
     want = {(k, w) for k in kernels for w in ((4, 2) if k.endswith("<20>") else (4, 2, 1))}
     assert set(G.RECOMPUTE_CASES) == want, (want - set(G.RECOMPUTE_CASES), set(G.RECOMPUTE_CASES) - want)
-    assert len(want) == 15
-    tests = {n for n in dir(G) if n.startswith("test_")}
-    assert set(G.RECOMPUTE_CASES.values()) <= tests, set(G.RECOMPUTE_CASES.values()) - tests
+    assert len(kernels) == 8 and len(want) == 20
+    where = {name: (M if k.startswith("rti_mjvp_kernel<0>") and w > 1 else G) for (k, w), name in G.RECOMPUTE_CASES.items()}
+    assert sum(mod is M for mod in where.values()) == 1                   # (the two reference rows of rti_mjvp_kernel<0>: one test)
+    missing = {name for name, mod in where.items() if not (name.startswith("test_") and callable(getattr(mod, name, None)))}
+    assert not missing, missing
     assert K.geometry(20)[0] == 4 and {K.geometry(N)[0] for N in DERIV_EDGE_N if N < 20} == {4}
     assert {K.geometry(N)[0] for N in DERIV_EDGE_N if N > 20} == {2}
     # the horizons the rows rest on: the reference tests run the whole list (<0> at 4 and at 2), the lowered-waves test <20> at 2 against 4
     # and <0> at 1 against 4 and against 2, and the older modules hold <20> at its default 4 to the dense references
     for name in set(G.RECOMPUTE_CASES.values()) - {"test_lowered_waves_equal_the_default_launch_bit_for_bit"}:
-        assert tuple(_params(getattr(G, name))["N"]) == DERIV_EDGE_N, name
+        assert tuple(_params(getattr(where[name], name))["N"]) == DERIV_EDGE_N, name
+    assert M.pytestmark.name == "gpu" and M.SEEDS is G.SEEDS
     assert _params(G.test_lowered_waves_equal_the_default_launch_bit_for_bit)["N,waves"] == [(20, 2), (13, 1), (27, 1)] == list(G.LOWERED)
     assert (G.LOWERED_B, G.POINTERS_B, list(G.POINTERS)) == (5, 8, [20, 17])
-    from tests import test_model_grad_gpu, test_step_jvp_gpu, test_step_vjp_gpu
+    from tests import test_model_grad_gpu, test_step_jvp_gpu, test_step_model_jvp_gpu, test_step_vjp_gpu
     for test in (test_step_vjp_gpu.test_full_trajectory_upstream_matches_the_dense_reference,
                  test_model_grad_gpu.test_device_model_gradient_matches_the_dense_reference,
-                 test_step_jvp_gpu.test_three_directions_match_the_dense_reference):
+                 test_step_jvp_gpu.test_three_directions_match_the_dense_reference,
+                 test_step_model_jvp_gpu.test_three_directions_match_the_dense_reference):
         assert 20 in _params(test)["N"], test.__name__
     from ndp_nmpc_qd_amd import _lib, build, isa_inspect
     build.build()
-    names = [n for n in isa_inspect.CodeObject(_lib.LIB_PATH).kernels() if any(k in n for k in ("rti_vjp_kernel", "rti_wvjp_kernel", "rti_jvp_kernel"))]
-    assert len(names) == 6, names
+    names = [n for n in isa_inspect.CodeObject(_lib.LIB_PATH).kernels() if any(k in n for k in recompute)]
+    assert len(names) == 8, names

@@ -1,14 +1,14 @@
 """The control step's derivative kernels on the device at the horizons where their passes change shape (tests/deriv_edges.py: DERIV_EDGE_N;
 run with -m gpu): the adjoint with and without the model gradient, forward mode, the level-2 and the parameter sensitivities against the
 dense fixed-set references (tests/fixed_set_ref.py), duality of forward mode against the adjoint, the facts that hold exactly, guard rows
-behind a ragged batch; the recompute kernels at lowered instances per workgroup against the default launch; and every optional pointer
-of the two recompute entries.  CPU side (the list, the seeds, the ledger, the host emulator): tests/test_deriv_edges.py."""
+behind a ragged batch; the recompute kernels (rti_mjvp_kernel among them) at lowered instances per workgroup against the default launch;
+and every optional pointer of the recompute entries, the model forward mode's included.  CPU side (the list, the seeds, the ledger, the host emulator): tests/test_deriv_edges.py."""
 import numpy as np
 import pytest
 
 from ndp_nmpc_qd_amd import synth
 from tests.deriv_edges import DERIV_EDGE_N, DEVICE_B, device_case, pick, small_case
-from tests.deriv_gpu import _dev, _jvp, _recorded_step, _t, _tangents, _tt, _vjp, ndp  # noqa: F401
+from tests.deriv_gpu import _dev, _jvp, _mjvp, _recorded_step, _t, _tangents, _tt, _vjp, ndp  # noqa: F401
 from tests.fixed_set_ref import jvp_apply, jvp_system, model_grad_ref, psens_apply, scale, sens_ref, vjp_apply
 from tests.test_kernel_table_gpu import SENS_BAR, geometry
 
@@ -44,24 +44,33 @@ POINTERS_B = 8
 # horizon, bit for bit: (<20>, 2) to (<20>, 4) and (<0>, 1) to (<0>, 4) at N = 13 and to (<0>, 2) at N = 27.  For the (<20>, 4) rows it is
 # that baseline only; the <20> kernels at their default 4 are held to the dense references by the older modules
 # (test_step_vjp_gpu.test_full_trajectory_upstream_matches_the_dense_reference,
-# test_model_grad_gpu.test_device_model_gradient_matches_the_dense_reference and
-# test_step_jvp_gpu.test_three_directions_match_the_dense_reference, each at N = 20; tests/test_deriv_edges.py checks that they are there).
+# test_model_grad_gpu.test_device_model_gradient_matches_the_dense_reference,
+# test_step_jvp_gpu.test_three_directions_match_the_dense_reference and
+# test_step_model_jvp_gpu.test_three_directions_match_the_dense_reference, each at N = 20; tests/test_deriv_edges.py checks that they are
+# there).  rti_mjvp_kernel's reference rows (<0> at 4 and at 2) name a test of tests/test_step_model_jvp_edges_gpu.py (MJVP_MODULE), which
+# runs the same list of horizons.
+MJVP_MODULE = "tests.test_step_model_jvp_edges_gpu"
 RECOMPUTE_CASES = {
     ("rti_vjp_kernel<20>", 4): "test_lowered_waves_equal_the_default_launch_bit_for_bit",
     ("rti_wvjp_kernel<20>", 4): "test_lowered_waves_equal_the_default_launch_bit_for_bit",
     ("rti_jvp_kernel<20>", 4): "test_lowered_waves_equal_the_default_launch_bit_for_bit",
+    ("rti_mjvp_kernel<20>", 4): "test_lowered_waves_equal_the_default_launch_bit_for_bit",
     ("rti_vjp_kernel<20>", 2): "test_lowered_waves_equal_the_default_launch_bit_for_bit",
     ("rti_wvjp_kernel<20>", 2): "test_lowered_waves_equal_the_default_launch_bit_for_bit",
     ("rti_jvp_kernel<20>", 2): "test_lowered_waves_equal_the_default_launch_bit_for_bit",
+    ("rti_mjvp_kernel<20>", 2): "test_lowered_waves_equal_the_default_launch_bit_for_bit",
     ("rti_vjp_kernel<0>", 4): "test_adjoint_and_model_gradient_match_the_dense_references",
     ("rti_wvjp_kernel<0>", 4): "test_adjoint_and_model_gradient_match_the_dense_references",
     ("rti_jvp_kernel<0>", 4): "test_forward_mode_matches_the_dense_reference_and_the_adjoint",
+    ("rti_mjvp_kernel<0>", 4): "test_model_directions_match_the_dense_reference_at_the_edge_horizons",
     ("rti_vjp_kernel<0>", 2): "test_adjoint_and_model_gradient_match_the_dense_references",
     ("rti_wvjp_kernel<0>", 2): "test_adjoint_and_model_gradient_match_the_dense_references",
     ("rti_jvp_kernel<0>", 2): "test_forward_mode_matches_the_dense_reference_and_the_adjoint",
+    ("rti_mjvp_kernel<0>", 2): "test_model_directions_match_the_dense_reference_at_the_edge_horizons",
     ("rti_vjp_kernel<0>", 1): "test_lowered_waves_equal_the_default_launch_bit_for_bit",
     ("rti_wvjp_kernel<0>", 1): "test_lowered_waves_equal_the_default_launch_bit_for_bit",
     ("rti_jvp_kernel<0>", 1): "test_lowered_waves_equal_the_default_launch_bit_for_bit",
+    ("rti_mjvp_kernel<0>", 1): "test_lowered_waves_equal_the_default_launch_bit_for_bit",
 }
 
 
@@ -331,12 +340,14 @@ def test_lowered_waves_equal_the_default_launch_bit_for_bit(ndp, monkeypatch, N,
     """NDP_DEV_WAVES (read by ndp_create) lowers the instances per workgroup; the recompute kernels launch with the handle's count.  B = 5:
     the adjoint, the adjoint with the model gradient and forward mode of a lowered handle equal those of a default handle on the same
     inputs, tape and upstreams, bit for bit (an instance is one wave; the kernel binary is the same), and nothing is written behind the
-    batch.  The default launch of N = 20 is the <20> kernels' four-wave case."""
+    batch; so does forward mode with a seeded model direction beside the data tangents (rti_mjvp_kernel).  The default launch of N = 20 is
+    the <20> kernels' four-wave case."""
     B = LOWERED_B
     b, f = small_case(N, LOWERED[N, waves], B)
     rng = np.random.default_rng(N)
     gt = dict(gu0=_t(rng.normal(size=(B, 4))), gX=_t(rng.normal(size=(B, N + 1, 10))), gU=_t(rng.normal(size=(B, N, 4))))
     tan = _tt(_tangents(N + 1, B, N, T))
+    tm = np.random.default_rng(N + 5).normal(size=(B, T, 16))
     dflt = _recorded_step(ndp, b, f=f)
     assert dflt["eng"].debug_rti_launched()[1] == geometry(N)[0] > waves
     monkeypatch.setenv("NDP_DEV_WAVES", str(waves))
@@ -347,9 +358,9 @@ def test_lowered_waves_equal_the_default_launch_bit_for_bit(ndp, monkeypatch, N,
     for r in (dflt, low):                                  # (both on the default handle's tape)
         a = (r["eng"], r["t"]["x0"], r["t"]["xr"], r["t"]["ur"], dflt["tape"])
         outs.append(_vjp(*a, f=r["force"], guard=GUARD, **gt) + _vjp(*a, f=r["force"], model=True, guard=GUARD, **gt)
-                    + _jvp(*a, T, f=r["force"], guard=GUARD, **tan))
+                    + _jvp(*a, T, f=r["force"], guard=GUARD, **tan) + _mjvp(*a, tm, f=r["force"], guard=GUARD, **tan))
         r["eng"].close()
-    assert len(outs[0]) == 6 + 7 + 5
+    assert len(outs[0]) == 6 + 7 + 5 + 5
     for x, y in zip(*outs):
         assert np.array_equal(x, y, equal_nan=True)
     assert _guards_intact(outs[1], B)
@@ -374,7 +385,10 @@ def _sums_to(parts, whole, what):
 def test_every_optional_pointer_of_the_recompute_entries(ndp, N):
     """B = 8 at N = 20 and N = 17.  Outputs: a call with only one of gx0, gxr, gur, gf (du0, dX, dU) non-null writes what the full call
     writes there, bit for bit.  Inputs: the three calls with only gu0, only gX and only gU (the four with one tangent each) sum to the
-    full call within 1e-10 of max(1, |value|max): the derivative is linear in them."""
+    full call within 1e-10 of max(1, |value|max): the derivative is linear in them.  The model entry (ndp_step_jvp_model_device): du0, dX
+    and dU alone equal the full call's, bit for bit; the call with tmodel alone plus the call with the data tangents alone (tmodel zero)
+    sum to the mixed call, and the 15 unit columns of the model (two calls, of 8 and of 7 directions) weighted by the direction's entries
+    sum to the call along the full model direction, both within 1e-10."""
     import torch
     B = POINTERS_B
     b, f = small_case(N, POINTERS[N], B)
@@ -398,7 +412,23 @@ def test_every_optional_pointer_of_the_recompute_entries(ndp, N):
         assert np.array_equal(one.cpu().numpy(), full_j[k], equal_nan=True), name
     parts_v = [_vjp(eng, *a, f=r["force"], **{k: v})[:4] for k, v in gt.items()]
     parts_j = [_jvp(eng, *a, T, f=r["force"], **{k: v})[:3] for k, v in tan.items()]
+    tm = rng.normal(size=(B, T, 16))
+    full_m = _mjvp(eng, *a, tm, f=r["force"], **tan)
+    for k, (name, shape) in enumerate((("du0", (B, T, 4)), ("dX", (B, T, N + 1, 10)), ("dU", (B, T, N, 4)))):
+        one = z(*shape)
+        eng.step_jvp_device(*a, f=r["force"], tmodel=_t(tm), **tan, **{name: one})
+        torch.cuda.synchronize()
+        assert np.array_equal(one.cpu().numpy(), full_m[k], equal_nan=True), name
+    alone_m = _mjvp(eng, *a, tm, f=r["force"])
+    parts_m = [alone_m[:3], _mjvp(eng, *a, np.zeros((B, T, 16)), f=r["force"], **tan)[:3]]
+    eye = np.eye(16)
+    cols = [_mjvp(eng, *a, np.ascontiguousarray(np.broadcast_to(eye[lo:hi][None], (B, hi - lo, 16))), f=r["force"])[:3]
+            for lo, hi in ((0, 8), (8, 15))]
+    unit = [np.concatenate([c[k] for c in cols], axis=1) for k in range(3)]          # [B,15,...]: the tangent along each unit column
+    parts_c = [[np.einsum("btj,bj...->bt...", tm[:, :, :15], u) for u in unit]]
     eng.close()
     assert _finishes(r)[0].all()                                         # (as the twin has it: every instance is held, to the one bar)
     wv, wj = _sums_to(parts_v, full_v[:4], "adjoint"), _sums_to(parts_j, full_j[:3], "forward mode")
-    print(f"N={N}: single upstreams / tangents against the full call, worst {wv:.3e} / {wj:.3e}")
+    wm, wc = _sums_to(parts_m, full_m[:3], "model and data directions"), _sums_to(parts_c, alone_m[:3], "the model's unit columns")
+    print(f"N={N}: single upstreams / tangents against the full call, worst {wv:.3e} / {wj:.3e}; tmodel alone + data alone against the "
+          f"mixed call {wm:.3e}; the 15 unit columns against the full model direction {wc:.3e}")

@@ -15,7 +15,7 @@ import pytest
 from ndp_nmpc_qd_amd import synth
 from tests import model_jvp_ref as MR
 from tests.deriv_edges import DEVICE_B, device_case
-from tests.deriv_gpu import MIXED, _dev, _jvp, _recorded_step, _t, _tangents, _tt, _vjp, ndp  # noqa: F401
+from tests.deriv_gpu import MIXED, _dev, _jvp, _mjvp, _recorded_step, _t, _tangents, _tt, _vjp, ndp  # noqa: F401
 from tests.fixed_set_ref import scale
 
 pytestmark = pytest.mark.gpu
@@ -24,21 +24,6 @@ SEED = synth.SEED0 + 300
 HORIZONS = (20, 13, 2, 27)
 T = 3
 WHO = "ndp_step_jvp_model_device"
-
-
-def _mjvp(eng, x0, xr, ur, tape, tm, f=None, tx0=None, txr=None, tur=None, tf=None, guard=0):
-    """step_jvp_device with tmodel ([B,T,16] numpy) on torch tensors with -7.0-filled outputs; returns numpy (du0 [B,T,4], dX, dU,
-    u0_check, status_check).  guard: the outputs are the first B rows of buffers with that many rows more, returned whole."""
-    import torch
-    B, N, nt = eng.B, eng.N, tm.shape[1]
-    R = B + guard
-    z = lambda *s: torch.full(s, -7.0, dtype=torch.float64, device=_dev())  # noqa: E731
-    out = (z(R, nt, 4), z(R, nt, N + 1, 10), z(R, nt, N, 4), z(R, 4))
-    st = torch.full((R,), -1, dtype=torch.int32, device=_dev())
-    eng.step_jvp_device(x0, xr, ur, tape, tx0=tx0, txr=txr, tur=tur, tf=tf, f=f, du0=out[0][:B], dX=out[1][:B], dU=out[2][:B],
-                        u0_check=out[3][:B], status_check=st[:B], tmodel=_t(tm))
-    torch.cuda.synchronize()
-    return tuple(t.cpu().numpy() for t in out) + (st.cpu().numpy(),)
 
 
 def _state(eng):
