@@ -1159,6 +1159,10 @@ int ndp_debug_host_info(ndp_handle *h, int32_t *out3);
  * counts once, at capture.  out3 (or NULL) = {rows of the table, instances per workgroup, 1 if the downwash network can run inside
  * the control step's launch (else a separate launch first)}. */
 int ndp_debug_rti_launched(ndp_handle *h, uint64_t *mask, int32_t *out3);
+/* Test hook: how many HIP resources the library holds in this process right now -- device buffers, page-locked host blocks, events
+ * and streams of every handle and exchange alive (memory handed to the caller by ndp_peer_alloc is not counted).  Back at its earlier
+ * value once whatever was created since has been destroyed: nothing leaked. */
+long long ndp_debug_live_resources(void);
 int ndp_step_debug(ndp_handle *h, const double *x0, const double *xr, const double *ur, const float *f,
                    const double *other, const double *ego_xy, double *u0, double *lds_dump);
 

@@ -74,6 +74,7 @@ EXPORTS = [
     "ndp_closed_loop_formation_config", "ndp_plant_force_scatter_device", "ndp_closed_loop_formation_device",
     "ndp_closed_loop_formation_vjp_device",
     "ndp_step_jvp_model_device", "ndp_closed_loop_jvp_model_device",
+    "ndp_debug_live_resources",
 ]
 
 _lib = None
@@ -167,6 +168,8 @@ def load():
     lib.ndp_debug_mlp_fragments.argtypes = [vp] * 3
     lib.ndp_debug_host_info.argtypes = [vp, vp]
     lib.ndp_debug_rti_launched.argtypes = [vp, C.POINTER(C.c_uint64), vp]
+    lib.ndp_debug_live_resources.argtypes = []
+    lib.ndp_debug_live_resources.restype = C.c_longlong
     lib.ndp_ref_list_reset.argtypes = [vp]
     lib.ndp_ref_list_fix_pt.argtypes = [vp, vp, C.c_int]
     lib.ndp_ref_list_window.argtypes = [vp] * 4

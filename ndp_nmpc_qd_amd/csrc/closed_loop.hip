@@ -381,12 +381,12 @@ struct ClView {
     void record(int k, ClCopy *cp) const     // the engine's pair into tape slot k (dU lies right behind dX)
     {
         cp[0] = ClCopy{(const unsigned char *)h->dX, tape + (size_t)k * slot, itb};
-        cp[1] = ClCopy{(const unsigned char *)h->dAct, tape + (size_t)k * slot + itb, ab};
+        cp[1] = ClCopy{(const unsigned char *)h->dAct.get(), tape + (size_t)k * slot + itb, ab};
     }
     void replay(int k, ClCopy *cp) const     // tape slot k into the workspace the derivative kernels recompute on
     {
-        cp[0] = ClCopy{tape + (size_t)k * slot, (unsigned char *)h->dVjp, itb};
-        cp[1] = ClCopy{tape + (size_t)k * slot + itb, (unsigned char *)h->dVjpAct, ab};
+        cp[0] = ClCopy{tape + (size_t)k * slot, (unsigned char *)h->dVjp.get(), itb};
+        cp[1] = ClCopy{tape + (size_t)k * slot + itb, (unsigned char *)h->dVjpAct.get(), ab};
     }
 };
 static ClView cl_view(const ndp_handle *h, const void *d_x0, const void *d_xr, const void *d_ur, const void *d_f, const void *d_fp,
@@ -492,13 +492,13 @@ static int cl_reverse(ndp_handle *h, Entry &g, const char *who, int ticks, doubl
     if (rc) return rc;
     hipStream_t s = g.s;
     const size_t B = v.B;
-    if (!h->dClWs) NDP_HIP(h, hipMalloc((void **)&h->dClWs, B * (NU + NX + NX + 16) * 8));
+    NDP_HIP(h, h->dClWs.ensure(B * (NU + NX + NX + 16) * 8));
     double *ws_gu0 = h->dClWs, *ws_gxp = ws_gu0 + B * NU, *ws_gx0 = ws_gxp + B * NX, *ws_gm = ws_gx0 + B * NX;
     double *ws_gF = nullptr, *ws_gz = nullptr, *ws_acc = nullptr;
     float *ws_gw = nullptr;
     if (form) {
         const size_t np2 = ((size_t)NDP_MLP_NPARAM + 1) / 2;       // a tick's fp32 g_w, in doubles
-        if (!h->dFormWs) NDP_HIP(h, hipMalloc((void **)&h->dFormWs, (B * 3 + B * NDP_MAX_NEIGH * 6 + NDP_MLP_NPARAM + np2) * 8));
+        NDP_HIP(h, h->dFormWs.ensure((B * 3 + B * NDP_MAX_NEIGH * 6 + NDP_MLP_NPARAM + np2) * 8));
         ws_gF = h->dFormWs; ws_gz = ws_gF + B * 3; ws_acc = ws_gz + B * NDP_MAX_NEIGH * 6;
         if (form->d_gw) ws_gw = (float *)(ws_acc + NDP_MLP_NPARAM);
     }
@@ -687,8 +687,7 @@ int ndp_closed_loop_formation_config(ndp_handle *h, const int32_t *other_index, 
     int rc = wait_all(h);
     if (rc) return rc;
     if (!other_index) {
-        if (h->dFormIndex) (void)hipFree(h->dFormIndex);
-        h->dFormIndex = nullptr;
+        h->dFormIndex.reset();
         h->form_K = h->form_edges = 0;
         return 0;
     }
@@ -710,15 +709,12 @@ int ndp_closed_loop_formation_config(ndp_handle *h, const int32_t *other_index, 
     std::vector<int32_t> fill(off, off + B);
     for (size_t e = 0; e < slots; ++e)
         if (heard(e) >= 0) blk[slots + B + 1 + (size_t)fill[heard(e)]++] = (int32_t)e;
-    if (h->dFormIndex) (void)hipFree(h->dFormIndex);
-    h->dFormIndex = nullptr;
+    h->dFormIndex.reset();
     h->form_K = h->form_edges = 0;
-    int *d_blk = nullptr;
-    NDP_HIP(h, hipMalloc((void **)&d_blk, blk.size() * 4));
-    const hipError_t e = hipMemcpy(d_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) (void)hipFree(d_blk);         // (nothing stays configured behind a failed copy)
-    NDP_HIP(h, e);
-    h->dFormIndex = d_blk; h->form_K = K; h->form_edges = edges;
+    DevBuf<int> d_blk;                                 // (local until the copy is in: nothing stays configured behind a failed one)
+    NDP_HIP(h, d_blk.alloc(blk.size() * 4));
+    NDP_HIP(h, hipMemcpy(d_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice));
+    h->dFormIndex = std::move(d_blk); h->form_K = K; h->form_edges = edges;
     return 0;
 }
 

@@ -453,12 +453,12 @@ static int ensure_prefetch(ndp_handle *h)
     if (!h->have_mlp) { h->err = "downwash requested but ndp_set_mlp_weights was never called"; return -6; }
     // (h->aux, created last, marks completion; members a failed earlier call did allocate are reused, not allocated again)
     for (int i = 0; i < 2; ++i) {
-        if (!h->dForceAB[i]) NDP_HIP(h, hipMalloc((void **)&h->dForceAB[i], nfs(h) * 4));
+        NDP_HIP(h, h->dForceAB[i].ensure(nfs(h) * 4));
         NDP_HIP(h, hipMemset(h->dForceAB[i], 0, nfs(h) * 4));
     }
     h->pf_ntiles = (unsigned)((h->cfg.batch * (h->cfg.N + 1) + 31) / 32);
     const size_t proto_words = (size_t)PF_EPOCH + 2 * (size_t)h->pf_ntiles;
-    if (!h->dProto) NDP_HIP(h, hipMalloc((void **)&h->dProto, proto_words * 8));
+    NDP_HIP(h, h->dProto.ensure(proto_words * 8));
     NDP_HIP(h, hipMemset(h->dProto, 0, proto_words * 8));
     {
         const unsigned grid_rti = (unsigned)((h->cfg.batch + h->waves - 1) / h->waves);
@@ -468,9 +468,9 @@ static int ensure_prefetch(ndp_handle *h)
     // queue would execute behind it).  Streams of another priority level get queues of their own.
     int lo = 0, hi = 0;
     NDP_HIP(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
-    if (!h->evFork) NDP_HIP(h, hipEventCreateWithFlags(&h->evFork, hipEventDisableTiming));
-    if (!h->evJoin) NDP_HIP(h, hipEventCreateWithFlags(&h->evJoin, hipEventDisableTiming));
-    NDP_HIP(h, hipStreamCreateWithPriority(&h->aux, hipStreamNonBlocking, hi));
+    NDP_HIP(h, h->evFork.ensure(hipEventDisableTiming));
+    NDP_HIP(h, h->evJoin.ensure(hipEventDisableTiming));
+    NDP_HIP(h, h->aux.ensure(hipStreamNonBlocking, hi));
     return 0;
 }
 
@@ -655,7 +655,7 @@ int ndp_downwash_multi_device(ndp_handle *h, const void *d_other, int other_stri
 //   the plant force   f fp64 [B][3] | index int32 [B][K]   3 B + K B / 2 doubles: 7 B at K = NDP_MAX_NEIGH = 8
 //   the prediction    index int32 [B][K]                   K B / 2 doubles: 4 B at K = 8 (the force is h->dForce)
 static int *sthr_force_index(const ndp_handle *h) { return reinterpret_cast<int *>(h->sThr + 3 * (size_t)h->cfg.batch); }
-static int *sthr_index(const ndp_handle *h) { return reinterpret_cast<int *>(h->sThr); }
+static int *sthr_index(const ndp_handle *h) { return reinterpret_cast<int *>(h->sThr.get()); }
 
 static int plant_force_host(ndp_handle *h, const char *who, const double *x, const int32_t *other_index, int K, int gate, double scale, double *f)
 {

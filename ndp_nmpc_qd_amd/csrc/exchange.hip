@@ -218,8 +218,8 @@ int ndp_track_steps(ndp_handle *h, int on)
     if (!h) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
     NDP_HIP(h, hipSetDevice(h->cfg.device));
-    if (on && !h->stepDone[0])
-        for (auto &e : h->stepDone) NDP_HIP(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (on)
+        for (Event &e : h->stepDone) NDP_HIP(h, e.ensure(hipEventDisableTiming));
     h->track_steps = on != 0;
     return 0;
 }
@@ -279,14 +279,15 @@ int rccl_bind(const char *path)
 struct ndp_xchg {
     int device = 0, rank = 0, world = 1;
     void *comm = nullptr;
-    hipStream_t cs = nullptr;                 // the exchange's own stream (another priority level: its own hardware queue)
-    hipEvent_t evReady = nullptr, evDone = nullptr;
-    double *send = nullptr;                   // packed windows of this rank
-    size_t send_doubles = 0;
+    Stream cs;                                // the exchange's own stream (another priority level: its own hardware queue); declared in
+                                              // front of the events and the buffer: destroyed behind them
+    Event evReady, evDone;
+    DevBuf<double> send;                      // packed windows of this rank
+    size_t send_doubles = 0;                  // its capacity
     // the remote tick with the exchange ahead of the control steps (ndp_xchg_tick_begin / _step): begins are numbered 1, 2, ...; begin n
     // lives in slot n % 3 (at most two are ahead of the steps, and step k consumes begin k) and fills whichever gather buffer the
     // caller names -- two buffers (begin i+1 behind step i) or three (begin i+2 behind step i: the gather then never waits for a step)
-    hipEvent_t evGather[3] = {nullptr, nullptr, nullptr};     // slot's gather is complete
+    Event evGather[3];                               // slot's gather is complete
     unsigned long long win_n[3] = {0, 0, 0};         // the list position its windows belong to
     const void *buf[3] = {nullptr, nullptr, nullptr};   // the gather buffer it fills
     struct Reader { const void *ptr = nullptr; unsigned seq = 0; hipStream_t stream = nullptr; unsigned age = 0; };
@@ -342,17 +343,31 @@ int ndp_xchg_create(int device, int rank, int world, const unsigned char *id128,
     memcpy(u.internal, id128, 128);
     if (g_rccl.init(&x->comm, world, u, rank) != 0) return -22;      // collective: every rank calls it
     int lo = 0, hi = 0;
-    if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess || hipStreamCreateWithPriority(&x->cs, hipStreamNonBlocking, hi) != hipSuccess ||
-        hipEventCreateWithFlags(&x->evReady, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x->evDone, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x->evGather[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x->evGather[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x->evGather[2], hipEventDisableTiming) != hipSuccess) {
+    if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess || x->cs.ensure(hipStreamNonBlocking, hi) != hipSuccess ||
+        x->evReady.ensure(hipEventDisableTiming) != hipSuccess || x->evDone.ensure(hipEventDisableTiming) != hipSuccess ||
+        x->evGather[0].ensure(hipEventDisableTiming) != hipSuccess || x->evGather[1].ensure(hipEventDisableTiming) != hipSuccess ||
+        x->evGather[2].ensure(hipEventDisableTiming) != hipSuccess) {
         (void)ndp_xchg_destroy(x.release());      // (releases whatever exists: communicator, stream, events)
         return -3;
     }
     *out = x.release();
     return 0;
+}
+
+// the send buffer holds `rows` rows of 6 doubles: grown behind whatever may still read the old one -- the exchange's thread's pending
+// launches, the exchange's stream and `also` (the caller's stream when it carries the pack / gather, else null)
+static hipError_t grow_send(ndp_xchg *x, size_t rows, hipStream_t also)
+{
+    if (x->send_doubles >= rows * 6) return hipSuccess;
+    while (x->done.load(std::memory_order_acquire) != x->posted.load(std::memory_order_relaxed)) __builtin_ia32_pause();
+    if (x->send) {
+        (void)hipStreamSynchronize(x->cs);
+        if (also) (void)hipStreamSynchronize(also);
+    }
+    x->send_doubles = 0;
+    const hipError_t e = x->send.alloc(rows * 6 * sizeof(double));
+    if (e == hipSuccess) x->send_doubles = rows * 6;
+    return e;
 }
 
 // rows = B_local * (N + 1) windows rows of d_xr ([rows][10] doubles) -> d_gathered ([world * rows][6]); everything `after_stream`
@@ -361,11 +376,7 @@ int ndp_xchg_begin(ndp_xchg *x, const void *d_xr, size_t rows, void *d_gathered,
 {
     if (!x || !d_xr || !d_gathered || rows == 0) return -1;
     if (hipSetDevice(x->device) != hipSuccess) return -2;
-    if (x->send_doubles < rows * 6) {
-        if (x->send) { (void)hipStreamSynchronize(x->cs); (void)hipFree(x->send); x->send = nullptr; }
-        if (hipMalloc((void **)&x->send, rows * 6 * sizeof(double)) != hipSuccess) return -3;
-        x->send_doubles = rows * 6;
-    }
+    if (grow_send(x, rows, nullptr) != hipSuccess) return -3;
     // (every event operation is a packet the queue's command processor retires in order: ~3 us each on the stream that also
     // carries the control steps -- callers whose windows are in place already pass no stream)
     if (after_stream && (hipEventRecord(x->evReady, (hipStream_t)after_stream) != hipSuccess || hipStreamWaitEvent(x->cs, x->evReady, 0) != hipSuccess))
@@ -421,11 +432,6 @@ int ndp_xchg_destroy(ndp_xchg *x)
     (void)hipSetDevice(x->device);
     if (x->cs) (void)hipStreamSynchronize(x->cs);
     if (x->comm) (void)g_rccl.destroy(x->comm);
-    if (x->send) (void)hipFree(x->send);
-    if (x->evReady) (void)hipEventDestroy(x->evReady);
-    if (x->evDone) (void)hipEventDestroy(x->evDone);
-    for (hipEvent_t e : x->evGather) if (e) (void)hipEventDestroy(e);
-    if (x->cs) (void)hipStreamDestroy(x->cs);
     delete x;
     return 0;
 }
@@ -457,11 +463,7 @@ int ndp_xchg_tick_windows(ndp_xchg *x, ndp_handle *h, void *d_gathered, void *st
     if (!h->dRingX) { h->err = "ndp_xchg_tick_windows: no reference list"; return -11; }
     const RingGeom rg = ring_geom(h);
     const size_t B = h->cfg.batch, rows = B * (size_t)(h->cfg.N + 1);
-    if (x->send_doubles < rows * 6) {
-        if (x->send) { (void)hipStreamSynchronize(x->cs); (void)hipStreamSynchronize(s); (void)hipFree(x->send); x->send = nullptr; }
-        NDP_HIP(h, hipMalloc((void **)&x->send, rows * 6 * sizeof(double)));
-        x->send_doubles = rows * 6;
-    }
+    NDP_HIP(h, grow_send(x, rows, s));
     launch_pack_pv_list(h->dRingX + rg.slot(h->list_n) * 10, rg.px(), h->cfg.N + 1, x->send, B, s);
     NDP_HIP(h, hipGetLastError());
     const int r = g_rccl.allgather(x->send, d_gathered, rows * 6, /* ncclFloat64 */ 8, x->comm, s);
@@ -539,12 +541,7 @@ int ndp_xchg_tick_begin(ndp_xchg *x, ndp_handle *h, const void *d_t, int flags, 
     // run: with step 2 that entry lands in the same residue class as the window, i.e. on one of its nodes (RingGeom::slot)
     if (d_t && x->ahead == 1 && rg.step < 3) { h->err = "ndp_xchg_tick_begin: the list's entries are two per node spacing -- a second begin ahead would overwrite the window the step before it may be reading (one begin ahead only: the two-buffer form)"; return -17; }
     const size_t B = h->cfg.batch, rows = B * (size_t)(h->cfg.N + 1);
-    if (x->send_doubles < rows * 6) {
-        while (x->done.load(std::memory_order_acquire) != x->posted.load(std::memory_order_relaxed)) __builtin_ia32_pause();
-        if (x->send) { (void)hipStreamSynchronize(x->cs); (void)hipFree(x->send); x->send = nullptr; }
-        NDP_HIP(h, hipMalloc((void **)&x->send, rows * 6 * sizeof(double)));
-        x->send_doubles = rows * 6;
-    }
+    NDP_HIP(h, grow_send(x, rows, nullptr));
     const unsigned n_job = x->posted.load(std::memory_order_relaxed) + 1;
     const int p = (int)(n_job % 3u);
     ndp_xchg::Job &j = x->job[p];                  // (free: at most two are ahead, and a step waits for its begin's launches)

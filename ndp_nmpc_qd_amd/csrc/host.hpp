@@ -38,6 +38,9 @@
 // A kernel sits with the host code that launches it; device code that two units' kernels inline is a header (mlp_tile.hpp, ref_point.hpp,
 // tick_wave.hpp, mlp_vjp_dev.hpp, mlp_jvp_dev.hpp, plant_dyn.hpp, plant_adj.hpp, plant_tan.hpp), and so are the argument blocks the host fills (kern_args.hpp).
 // The functions declared below are NDP_HIDDEN: the library exports the C-ABI of include/ndp_nmpc.h and nothing more.
+// Ownership: whatever the handle or an exchange got from the HIP runtime -- device and page-locked memory, events, streams -- is a member
+// of a hip_own.hpp type (DevBuf, PinnedBuf, Event, Stream) and is released by that member's destructor; every raw pointer, hipEvent_t or
+// hipStream_t is a view into an owner's block or the caller's.  A new workspace is one such member and an ensure() at its first use.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,12 +55,16 @@
 #include "cfg_params.hpp"
 #include "kern_args.hpp"
 #include "rti_table.hpp"
+#include "hip_own.hpp"
 
 #define NDP_HIDDEN __attribute__((visibility("hidden")))
 
 using namespace ndp;
 
 struct ndp_handle {
+    // the handle's stream, and the downwash prefetch's (ensure_prefetch).  Declared first: members are destroyed in reverse order, the
+    // streams after every buffer and event
+    Stream stream, aux;
     ndp_cfg cfg;
     RtiParams P;
     int lds_per_wave = 0;      // doubles
@@ -68,71 +75,77 @@ struct ndp_handle {
     bool use_queue = false;    // interior-point solves through the work list: producer + consumer launch per step (QueueArgs)
     // cfg.work_queue = 0 at (N, n_rti) = (20, 1), batch >= 2 instances per SIMD: the list is switched by what the steps do (queue_policy)
     bool queue_auto = false;
-    unsigned long long *hIpm = nullptr;      // page-locked [2]: the device's monotonic counts (interior-point instances, steps executed),
+    PinnedBuf<unsigned long long> hIpm;      // page-locked [2]: the device's monotonic counts (interior-point instances, steps executed),
                                              // copied behind every QP_WINDOW-th launch
     unsigned long long ipm_seen = 0, steps_seen = 0;   // the snapshot the last decision was taken on
     unsigned queue_launches = 0;             // launches since the last copy was enqueued
-    hipStream_t stream = nullptr;
-    // persistent device state
+    // Views, not owners.  Into dOut: su0 | dStatus | dIters (the small outputs), then the persistent iterate dX | dU.  Into dIn: sx0, sxr,
+    // sur, sf, sother, sego (staging of the f1-f4 host entry points).  dRingU: behind dRingX in its allocation.  lastStatus / lastIters:
+    // where the last step wrote them (dStatus / dIters or a slot's output mirror).  tick_remote and HostSlot::dump are the caller's.
     double *dX = nullptr, *dU = nullptr;
-    float *dForce = nullptr, *dFrag = nullptr;
-    double *dKC = nullptr;     // constants block of the LDS image (fill_kc)
-    int *dTables = nullptr;    // per-lane index tables of the Riccati sweep (fill_tables)
-    signed char *dAct = nullptr;   // [B][act_pitch(N)] QP_AUTO's active sets, kept between control steps (RtiIo::act); emptied by reset / set_iterate
+    double *sx0 = nullptr, *sxr = nullptr, *sur = nullptr, *sother = nullptr, *sego = nullptr, *su0 = nullptr;
+    float *sf = nullptr;
+    int *dStatus = nullptr, *dIters = nullptr;
+    const int *lastStatus = nullptr, *lastIters = nullptr;
+    double *dRingU = nullptr;
+    // persistent device state
+    DevBuf<float> dForce, dFrag;
+    DevBuf<double> dKC;        // constants block of the LDS image (fill_kc)
+    DevBuf<int> dTables;       // per-lane index tables of the Riccati sweep (fill_tables)
+    DevBuf<signed char> dAct;      // [B][act_pitch(N)] QP_AUTO's active sets, kept between control steps (RtiIo::act); emptied by reset / set_iterate
     // ndp_sens_enable: initial-state sensitivities of every step's QP (rti_sens_kernel): level 0 off, 1 du0/dx0, 2 also dU/dx0 and dX/dx0
     int sens_level = 0;
-    double *dSensU0 = nullptr, *dSensU = nullptr, *dSensX = nullptr;   // [B][4][10], [B][N][4][10], [B][N+1][10][10] (the last two: level 2)
+    DevBuf<double> dSensU0, dSensU, dSensX;   // [B][4][10], [B][N][4][10], [B][N+1][10][10] (the last two: level 2)
     // ndp_sens_params_enable: du0/dxr [B][4][N+1][10], du0/dur [B][4][N][4], du0/df [B][4][N+1][3] (rti_psens_kernel); null: off
-    double *dPSensXr = nullptr, *dPSensUr = nullptr, *dPSensF = nullptr;
+    DevBuf<double> dPSensXr, dPSensUr, dPSensF;
     // ndp_step_vjp_device's workspace (first call): the tape's iterate X | U, then u0 [B][4]; status | iterations [B] each; kept sets
-    double *dVjp = nullptr;
-    int *dVjpSt = nullptr;
-    signed char *dVjpAct = nullptr;
+    DevBuf<double> dVjp;
+    DevBuf<int> dVjpSt;
+    DevBuf<signed char> dVjpAct;
     // ndp_closed_loop_vjp_device's workspace (first call), what one tick hands the next: gu0 [B][4] | gx_p [B][10] | the step's gx0 [B][10] |
     // the step's gmodel row [B][16] (closed_loop.hip)
-    double *dClWs = nullptr;
+    DevBuf<double> dClWs;
     // ndp_closed_loop_formation_config: one allocation, int32: the index [B][K] | the reverse lists' offset [B+1] | edge [form_edges]
     // (closed_loop.hip: ClGather); null: not configured
-    int *dFormIndex = nullptr;
+    DevBuf<int> dFormIndex;
     int form_K = 0, form_edges = 0;
     // ndp_closed_loop_formation_vjp_device's workspace (first call; the largest K: sized for NDP_MAX_NEIGH): gF [B][3] | g_z [B][8][6] |
     // the weight gradient's fp64 accumulator [NDP_MLP_NPARAM], then a tick's fp32 g_w [NDP_MLP_NPARAM]
-    double *dFormWs = nullptr;
+    DevBuf<double> dFormWs;
     // mlp_vjp.hip: layers 2 and 3 transposed, one fp32 record per matrix instruction of the backward pass (FRT_TOTAL floats, written with
     // dFrag by both ndp_set_mlp_weights forms); ndp_downwash_vjp_device's per-workgroup partial weight gradients [mlp_vjp_groups][NDP_MLP_NPARAM]
     // (ndp_downwash_multi_vjp_device shares them: it never launches more workgroups than that)
-    float *dFragT = nullptr, *dGwPart = nullptr;
+    DevBuf<float> dFragT, dGwPart;
     // ndp_mlp_fit_rows_device's partials, a workspace of its own (its size does not follow the batch shape): gradients
     // [NDP_FIT_MAX_GROUPS][NDP_MLP_NPARAM] fp32 | losses [NDP_FIT_MAX_GROUPS] fp64 | rows used, skipped [NDP_FIT_MAX_GROUPS][2] int32
-    float *dFitPart = nullptr;
+    DevBuf<float> dFitPart;
     // mlp_train.hip: word 0 = the ticket of ndp_mlp_adam_sn_device's four workgroups (0 between launches), then 4 doubles and a blob's
     // floats: the staging of the host form ndp_mlp_spectral_norms (TRAIN_WS_BYTES)
-    unsigned long long *dTrain = nullptr;
-    double *dThr = nullptr;    // hover-throttle estimator state, SoA [8][B]
-    double *dStamps = nullptr; // [B][NDP_NSTAMP] whole-batch phase stamps (ndp_debug_stamps)
-    double *dTraj = nullptr;   // f1: the trajectories and the tick's caches (layout: TrajView)
+    DevBuf<unsigned long long> dTrain;
+    DevBuf<double> dThr;       // hover-throttle estimator state, SoA [8][B]
+    DevBuf<double> dStamps;    // [B][NDP_NSTAMP] whole-batch phase stamps (ndp_debug_stamps)
+    DevBuf<double> dTraj;      // f1: the trajectories and the tick's caches (layout: TrajView)
     int traj_seg = 0;
-    double *dRingX = nullptr, *dRingU = nullptr;   // f1: the reference's sliding list of reference points, phase-major (RingGeom), one allocation (first use)
+    DevBuf<double> dRingX;     // f1: the reference's sliding list of reference points, phase-major (RingGeom), one allocation (first use): X, then dRingU
     unsigned long long list_n = 0;                 // absolute index of the list's oldest entry = control ticks since the list was built
     int segc_par = 0;                              // which copy of the one-launch tick's segment cache the NEXT tick reads (tick_cache_store)
     int list_step = 5;
     // ndp_tick: the node's control tick on the device (rti_kernel<..., TICK>; other shapes: tick_pre_kernel + the control step)
-    int *dTickIndex = nullptr;       // [B] neighbour instance of every vehicle (< 0: none), or null: no vehicle has one
-    double *dTickThrust = nullptr;   // [B] the thrust command of the previous tick (what hover_throttle_callback reads off body_rate_cmd)
+    DevBuf<int> dTickIndex;          // [B] neighbour instance of every vehicle (< 0: none), or null: no vehicle has one
+    DevBuf<double> dTickThrust;      // [B] the thrust command of the previous tick (what hover_throttle_callback reads off body_rate_cmd)
     bool tick_gate = true;           // gate the downwash on |neighbour window node 0 xy - ego odometry xy| < r_horiz (ndp_nmpc_leader_node.py:65-74)
     const double *tick_remote = nullptr;   // ndp_tick_config_remote: the neighbours' windows are rows of the CALLER's buffer (an exchange's gathered /
     int tick_remote_stride = 6;            // peer-mapped windows, [rows][N+1][stride]) instead of this handle's own list
     struct TickSlot { bool busy = false, want_u0 = false; } tslot[2];
-    double *dRelay = nullptr;  // follower relay: [B][4] = filtered offset xyz + initialised flag
-    double *sThr = nullptr;    // staging of the f1-f4 host entry points: 11 B doubles
-    // downwash one tick ahead on a second stream (LateArgs): force slots, protocol words, the stream, its fork / join events
-    float *dForceAB[2] = {nullptr, nullptr};
-    unsigned long long *dProto = nullptr;
-    hipStream_t aux = nullptr;
-    hipEvent_t evFork = nullptr, evJoin = nullptr;
+    DevBuf<double> dRelay;     // follower relay: [B][4] = filtered offset xyz + initialised flag
+    DevBuf<double> sThr;       // staging of the f1-f4 host entry points: 11 B doubles
+    // downwash one tick ahead on a second stream (aux; LateArgs): force slots, protocol words, the stream's fork / join events
+    DevBuf<float> dForceAB[2];
+    DevBuf<unsigned long long> dProto;
+    Event evFork, evJoin;
     unsigned prefetch_timeout_us = 100000, pf_groups_rti = 1, pf_ntiles = 1;
-    unsigned *dQctr = nullptr; // work list: entry count | B instance ids
-    int *dQids = nullptr;
+    DevBuf<unsigned> dQctr;    // work list: entry count | B instance ids
+    DevBuf<int> dQids;
     bool have_mlp = false;
     // Host-pointer entry points.  ONE block holds every input of a step (x0 | xr | ur | f | other | ego_xy, each 256-byte
     // aligned) and one its outputs (u0 | status | iters | X | U).  Two slots of page-locked host mirrors of both (HostSlot,
@@ -144,16 +157,13 @@ struct ndp_handle {
     // With two slots the packing of step i+1 runs while step i's kernel does (ndp_step_begin / ndp_step_end).
     // The persistent iterate dX | dU always lives in HBM.  dIn / dOut: device-side staging of the f1-f4 host entry points
     // (views sx0 ..) and the small outputs of device-pointer steps.
-    unsigned char *dIn = nullptr, *dOut = nullptr;
+    DevBuf<unsigned char> dIn, dOut;
     size_t off_x0 = 0, off_xr = 0, off_ur = 0, off_f = 0, off_other = 0, off_ego = 0, in_bytes = 0;
     size_t off_u0 = 0, off_st = 0, off_it = 0, out_bytes = 0, out_all = 0;
-    double *sx0 = nullptr, *sxr = nullptr, *sur = nullptr, *sother = nullptr, *sego = nullptr, *su0 = nullptr, *sdbg = nullptr;
-    float *sf = nullptr;
-    int *dStatus = nullptr, *dIters = nullptr;
-    const int *lastStatus = nullptr, *lastIters = nullptr;   // where the last step wrote them (dStatus / dIters or a slot's output mirror)
+    DevBuf<double> sdbg;       // the LDS dump of ndp_step_debug
     struct HostSlot {
-        unsigned char *hIn = nullptr, *hOut = nullptr;
-        hipEvent_t evOut = nullptr;                          // the step that uses the slot has completed
+        PinnedBuf<unsigned char> hIn, hOut;
+        Event evOut;                                         // the step that uses the slot has completed
         bool busy = false, want_iter = false;
         double *dump = nullptr;
     } slot[2];
@@ -163,20 +173,20 @@ struct ndp_handle {
     bool track_steps = false;
     bool last_step_tracked = false;   // does stepDone[step_seq & 3] belong to the control step launched LAST?
     bool track_pending = false;       // a tracked step on a caller's stream has not been waited for (wait_all)
-    hipEvent_t stepDone[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event stepDone[4];
     unsigned step_seq = 0;
     double host_us[4] = {0, 0, 0, 0};   // last host step: packing | enqueue | wait for the results | copy-out  (ndp_debug_host_timing)
     int host_cores = 0, pack_threads = 0;   // what ensure_slots found and started (ndp_debug_host_info)
     int slot_head = 0, slot_tail = 0, slots_busy = 0;   // begin fills slot_head, end drains slot_tail
     std::unique_ptr<struct PackPool> pool;
     // the last foreign stream a *_device call enqueued on: the getters wait for it (hipEvent)
-    hipEvent_t evLast = nullptr;
+    Event evLast;
     bool ev_pending = false;
     // timing
     int timing = 0;            // 0 off, n > 0: bracket every n-th launch of each kernel with HIP events
     int64_t launch_no[2] = {0, 0};
     bool timing_open = false;
-    struct Ev { hipEvent_t a, b; int kind; };
+    struct Ev { Event a, b; int kind = 0; };
     std::vector<Ev> events;
     std::mutex mu;
     std::string err;

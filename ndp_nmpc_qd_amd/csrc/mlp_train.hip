@@ -276,7 +276,7 @@ int ndp_mlp_spectral_norms(ndp_handle *h, const float *blob, double *sigma4)
 {
     Entry g(h, blob && sigma4);
     if (g.rc) return g.rc;
-    double *d_sigma = reinterpret_cast<double *>(reinterpret_cast<char *>(h->dTrain) + 64);
+    double *d_sigma = reinterpret_cast<double *>(reinterpret_cast<char *>(h->dTrain.get()) + 64);
     float *d_w = reinterpret_cast<float *>(d_sigma + 4);
     NDP_HIP(h, hipMemcpyAsync(d_w, blob, (size_t)NDP_MLP_NPARAM * 4, hipMemcpyHostToDevice, h->stream));
     TrainArgs a{};
@@ -300,7 +300,7 @@ int ndp_mlp_adam_sn_device(ndp_handle *h, void *d_w, const void *d_g, void *d_m,
     else if (sn_cap != sn_cap) why = "ndp_mlp_adam_sn_device: sn_cap is NaN (<= 0 switches the cap off)";
     if (why) { h->err = why; return -2; }
     TrainArgs a{(float *)d_w, (const float *)d_g, (float *)d_m, (float *)d_v, (long long *)d_step, lr, beta1, beta2, eps, sn_cap,
-                (double *)d_sigma, (int *)d_info, reinterpret_cast<unsigned *>(h->dTrain)};
+                (double *)d_sigma, (int *)d_info, reinterpret_cast<unsigned *>(h->dTrain.get())};
     hipLaunchKernelGGL(mlp_train_kernel<true>, dim3(4), dim3(256), 0, g.s, a);
     NDP_HIP(h, hipGetLastError());
     const int rc = g.noted(0);

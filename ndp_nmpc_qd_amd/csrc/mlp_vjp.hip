@@ -197,7 +197,7 @@ int ndp_set_mlp_weights_device(ndp_handle *h, const void *d_blob, void *stream)
 {
     Entry g(h, d_blob != nullptr, stream);
     if (g.rc) return g.rc;
-    hipLaunchKernelGGL(mlp_frag_kernel, dim3((frag::TOTAL + 255) / 256), dim3(256), 0, g.s, (const float *)d_blob, (unsigned *)h->dFrag, h->dFragT);
+    hipLaunchKernelGGL(mlp_frag_kernel, dim3((frag::TOTAL + 255) / 256), dim3(256), 0, g.s, (const float *)d_blob, (unsigned *)h->dFrag.get(), h->dFragT);
     NDP_HIP(h, hipGetLastError());
     h->have_mlp = true;
     return g.noted(0);

@@ -198,30 +198,14 @@ int ndp_destroy(ndp_handle *h)
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->ev_pending) (void)hipEventSynchronize(h->evLast);
-    for (auto &e : h->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    if (h->evLast) (void)hipEventDestroy(h->evLast);
-    if (h->aux) { (void)hipStreamSynchronize(h->aux); (void)hipStreamDestroy(h->aux); }
-    for (hipEvent_t e : {h->evFork, h->evJoin, h->stepDone[0], h->stepDone[1], h->stepDone[2], h->stepDone[3]})
-        if (e) (void)hipEventDestroy(e);
-    h->pool.reset();
-    void *ptrs[] = {h->dForceAB[0], h->dForceAB[1], h->dProto, h->dRingX, h->dTraj, h->dTables, h->dStamps, h->dRelay, h->dThr, h->sThr, h->dKC, h->dForce, h->dFrag,
-                    h->dIn, h->dOut, h->sdbg, h->dQctr, h->dQids, h->dTickIndex, h->dTickThrust, h->dAct,
-                    h->dSensU0, h->dSensU, h->dSensX, h->dPSensXr, h->dPSensUr, h->dPSensF, h->dVjp, h->dVjpSt, h->dVjpAct, h->dClWs, h->dFormIndex, h->dFormWs, h->dFragT, h->dGwPart, h->dFitPart, h->dTrain};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    for (auto &sl : h->slot) {
-        if (sl.hIn) (void)hipHostFree(sl.hIn);
-        if (sl.hOut) (void)hipHostFree(sl.hOut);
-        if (sl.evOut) (void)hipEventDestroy(sl.evOut);
-    }
-    if (h->hIpm) {                          // (a copy into it may still be queued on a caller's stream)
-        (void)hipDeviceSynchronize();
-        (void)hipHostFree(h->hIpm);
-    }
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    if (h->aux) (void)hipStreamSynchronize(h->aux);
+    h->pool.reset();                        // the pack threads stop before the page-locked mirrors go
+    if (h->hIpm) (void)hipDeviceSynchronize();      // (a copy into it may still be queued on a caller's stream)
+    delete h;                               // every member releases what it owns (hip_own.hpp), the streams last
     return 0;
 }
+
+long long ndp_debug_live_resources(void) { return live_resources.load(std::memory_order_relaxed); }
 
 // a pin is the weight as_gamma on its input: far below the input weights it holds nothing, yet as_check still writes the input onto
 // its bound -- a wrong step with status 0 (NDP_AS_GAMMA_FLOOR in the header).  ndp_create's rule, and ndp_set_model's for a new Rd.
@@ -312,36 +296,13 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
     h->queue_auto = cfg->work_queue == 0 && queue_shape(h) && cfg->qp_mode == NDP_QP_AUTO && cfg->N == 20 && cfg->batch >= 2 * h->n_simd;
     h->use_queue = cfg->work_queue == 1 || (cfg->work_queue == 0 && queue_shape(h) && cfg->qp_mode == NDP_QP_AUTO && cfg->N == 40);
     if (h->queue_auto) {
-        if ((e = hipHostMalloc((void **)&h->hIpm, 64, hipHostMallocDefault)) != hipSuccess) return fail("hipHostMalloc (work-list counter)", e);
+        if ((e = h->hIpm.alloc(64)) != hipSuccess) return fail("hipHostMalloc (work-list counter)", e);
         h->hIpm[0] = h->hIpm[1] = 0;
     }
-    if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return fail("hipStreamCreate", e);
-    if ((e = hipEventCreateWithFlags(&h->evLast, hipEventDisableTiming)) != hipSuccess) return fail("hipEventCreate", e);
+    if ((e = h->stream.ensure(hipStreamNonBlocking)) != hipSuccess) return fail("hipStreamCreate", e);
+    if ((e = h->evLast.ensure(hipEventDisableTiming)) != hipSuccess) return fail("hipEventCreate", e);
     const size_t B = cfg->batch;
-#define ALLOC(p, n)                                                                      \
-    if ((e = hipMalloc((void **)&(p), (n))) != hipSuccess) return fail("hipMalloc " #p, e)
-    ALLOC(h->dForce, nfs(h) * 4); ALLOC(h->dFrag, FR_TOTAL * 4); ALLOC(h->dFragT, FRT_TOTAL * 4); ALLOC(h->dGwPart, (size_t)mlp_vjp_groups(h) * NDP_MLP_NPARAM * 4); ALLOC(h->dKC, KC_HOST * 8);
-    ALLOC(h->dThr, B * 8 * 8); ALLOC(h->sThr, B * 11 * 8);
-    ALLOC(h->dRelay, B * 4 * 8);
-    ALLOC(h->dQctr, 256); ALLOC(h->dQids, B * 4);
-    ALLOC(h->dAct, B * (size_t)act_pitch(cfg->N));
-    (void)hipMemsetAsync(h->dAct, 0, B * (size_t)act_pitch(cfg->N), h->stream);
-    (void)hipMemsetAsync(h->dRelay, 0, B * 4 * 8, h->stream);
-    (void)hipMemsetAsync(h->dQctr, 0, 256, h->stream);
-    ALLOC(h->dTrain, TRAIN_WS_BYTES);
-    (void)hipMemsetAsync(h->dTrain, 0, 64, h->stream);
-    ALLOC(h->dFitPart, FIT_WS_BYTES);      // (every entry a call reads is written by that call: no memset)
-    {
-        double kc[KC_HOST];
-        fill_kc(h->P, kc);
-        if ((e = hipMemcpyAsync(h->dKC, kc, sizeof(kc), hipMemcpyHostToDevice, h->stream)) != hipSuccess) return fail("hipMemcpy kc", e);
-        ALLOC(h->dTables, TB_WORDS * 4);
-        std::vector<int> tb(TB_WORDS);
-        fill_tables(cfg->N, tb.data(), (cfg->qp_precision == 3 || cfg->qp_precision == 4) ? 1 : 0);   // the fp32 / bf16 sweeps keep a different column per lane
-        if ((e = hipMemcpyAsync(h->dTables, tb.data(), TB_WORDS * 4, hipMemcpyHostToDevice, h->stream)) != hipSuccess) return fail("hipMemcpy tables", e);
-        if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("hipStreamSynchronize", e);
-    }
-    {   // input / output blocks and their views
+    {   // input / output blocks
         size_t o = 0;
         h->off_x0 = o; o += up256(B * NX * 8);
         h->off_xr = o; o += up256(nxs(h) * 8);
@@ -359,16 +320,40 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
         // in ONE copy when a caller asks for the iterate as well (ndp_step_ex).  All of it is HBM; the page-locked host
         // mirrors of the host-array entry points are allocated by their first call (ensure_slots).
         h->out_all = h->out_bytes + (nxs(h) + nus(h)) * 8;
-        ALLOC(h->dIn, h->in_bytes);
-        ALLOC(h->dOut, h->out_all);
-        h->dX = (double *)(h->dOut + h->out_bytes); h->dU = h->dX + nxs(h);
-        h->sx0 = (double *)(h->dIn + h->off_x0); h->sxr = (double *)(h->dIn + h->off_xr); h->sur = (double *)(h->dIn + h->off_ur);
-        h->sf = (float *)(h->dIn + h->off_f); h->sother = (double *)(h->dIn + h->off_other); h->sego = (double *)(h->dIn + h->off_ego);
-        h->su0 = (double *)(h->dOut + h->off_u0); h->dStatus = (int *)(h->dOut + h->off_st); h->dIters = (int *)(h->dOut + h->off_it);
-        h->lastStatus = h->dStatus; h->lastIters = h->dIters;
-        ALLOC(h->sdbg, (size_t)(lds_doubles(cfg->N) + DBG_EXTRA) * 8);
     }
-#undef ALLOC
+    std::string what;
+    auto dev = [&](auto &buf, size_t bytes, const char *name) {
+        if ((e = buf.alloc(bytes)) != hipSuccess) what = std::string("hipMalloc ") + name;
+        return e == hipSuccess;
+    };
+    if (!dev(h->dForce, nfs(h) * 4, "dForce") || !dev(h->dFrag, FR_TOTAL * 4, "dFrag") || !dev(h->dFragT, FRT_TOTAL * 4, "dFragT") ||
+        !dev(h->dGwPart, (size_t)mlp_vjp_groups(h) * NDP_MLP_NPARAM * 4, "dGwPart") || !dev(h->dKC, KC_HOST * 8, "dKC") ||
+        !dev(h->dThr, B * 8 * 8, "dThr") || !dev(h->sThr, B * 11 * 8, "sThr") || !dev(h->dRelay, B * 4 * 8, "dRelay") ||
+        !dev(h->dQctr, 256, "dQctr") || !dev(h->dQids, B * 4, "dQids") || !dev(h->dAct, act_bytes(h), "dAct") ||
+        !dev(h->dTrain, TRAIN_WS_BYTES, "dTrain") ||
+        !dev(h->dFitPart, FIT_WS_BYTES, "dFitPart") ||      // (every entry a call reads is written by that call: no memset)
+        !dev(h->dTables, TB_WORDS * 4, "dTables") || !dev(h->dIn, h->in_bytes, "dIn") || !dev(h->dOut, h->out_all, "dOut") ||
+        !dev(h->sdbg, (size_t)(lds_doubles(cfg->N) + DBG_EXTRA) * 8, "sdbg"))
+        return fail(what.c_str(), e);
+    // the views into dIn / dOut
+    h->dX = (double *)(h->dOut + h->out_bytes); h->dU = h->dX + nxs(h);
+    h->sx0 = (double *)(h->dIn + h->off_x0); h->sxr = (double *)(h->dIn + h->off_xr); h->sur = (double *)(h->dIn + h->off_ur);
+    h->sf = (float *)(h->dIn + h->off_f); h->sother = (double *)(h->dIn + h->off_other); h->sego = (double *)(h->dIn + h->off_ego);
+    h->su0 = (double *)(h->dOut + h->off_u0); h->dStatus = (int *)(h->dOut + h->off_st); h->dIters = (int *)(h->dOut + h->off_it);
+    h->lastStatus = h->dStatus; h->lastIters = h->dIters;
+    (void)hipMemsetAsync(h->dAct, 0, act_bytes(h), h->stream);
+    (void)hipMemsetAsync(h->dRelay, 0, B * 4 * 8, h->stream);
+    (void)hipMemsetAsync(h->dQctr, 0, 256, h->stream);
+    (void)hipMemsetAsync(h->dTrain, 0, 64, h->stream);
+    {
+        double kc[KC_HOST];
+        fill_kc(h->P, kc);
+        if ((e = hipMemcpyAsync(h->dKC, kc, sizeof(kc), hipMemcpyHostToDevice, h->stream)) != hipSuccess) return fail("hipMemcpy kc", e);
+        std::vector<int> tb(TB_WORDS);
+        fill_tables(cfg->N, tb.data(), (cfg->qp_precision == 3 || cfg->qp_precision == 4) ? 1 : 0);   // the fp32 / bf16 sweeps keep a different column per lane
+        if ((e = hipMemcpyAsync(h->dTables, tb.data(), TB_WORDS * 4, hipMemcpyHostToDevice, h->stream)) != hipSuccess) return fail("hipMemcpy tables", e);
+        if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("hipStreamSynchronize", e);
+    }
     (void)hipMemsetAsync(h->dX, 0, nxs(h) * 8, h->stream);
     (void)hipMemsetAsync(h->dU, 0, nus(h) * 8, h->stream);
     (void)hipMemsetAsync(h->dOut, 0, h->out_bytes, h->stream);
@@ -380,8 +365,8 @@ int ndp_create(const ndp_cfg *cfg, ndp_handle **out)
     if ((e = mlp_fit_prepare()) != hipSuccess) return fail("hipFuncSetAttribute(mlp_fit_rows_kernel)", e);
     if ((e = mlp_multi_prepare()) != hipSuccess) return fail("hipFuncSetAttribute(mlp_multi_kernel)", e);
     if ((e = plant_force_deriv_prepare()) != hipSuccess) return fail("hipFuncSetAttribute(plant_force_vjp_kernel)", e);
-    const char *what = nullptr;
-    if ((e = rti_set_lds(false, lds_bytes, &what)) != hipSuccess) return fail(what, e);      // (the sensitivity kernels: ndp_sens_enable)
+    const char *attr = nullptr;
+    if ((e = rti_set_lds(false, lds_bytes, &attr)) != hipSuccess) return fail(attr, e);      // (the sensitivity kernels: ndp_sens_enable)
     launch_throttle_reset(h);
     if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("hipStreamSynchronize", e);
     *out = h;
@@ -398,9 +383,9 @@ int begin_timing(ndp_handle *h, hipStream_t s, int kind, bool defer)
     if (!h->timing || (h->launch_no[kind]++ % h->timing) != 0) return 0;
     h->timing_open = true;
     ndp_handle::Ev ev; ev.kind = kind;
-    NDP_HIP(h, hipEventCreate(&ev.a)); NDP_HIP(h, hipEventCreate(&ev.b));
+    NDP_HIP(h, ev.a.ensure(hipEventDefault)); NDP_HIP(h, ev.b.ensure(hipEventDefault));
     if (!defer) NDP_HIP(h, hipEventRecord(ev.a, s));
-    h->events.push_back(ev);
+    h->events.push_back(std::move(ev));
     return 0;
 }
 int end_timing(ndp_handle *h, hipStream_t s)
@@ -575,7 +560,7 @@ int launch_rti(ndp_handle *h, const double *d_x0, const double *d_xr, const doub
         if (h->cfg.n_rti == 1 && h->cfg.as_iter_max <= 0) kc.P.qp_mode = QP_IPM_ALWAYS;
         launch_kern(h, rti_pick(h, fused, tick1, prefetched, 2), s, kc, sa);
         NDP_HIP(h, hipGetLastError());
-        if (stop) hipExtLaunchKernelGGL(queue_reset_kernel, dim3(1), dim3(64), 0, s, nullptr, stop, 0, h->dQctr, qa.ipm_total);
+        if (stop) hipExtLaunchKernelGGL(queue_reset_kernel, dim3(1), dim3(64), 0, s, nullptr, stop, 0, h->dQctr.get(), qa.ipm_total);
         else hipLaunchKernelGGL(queue_reset_kernel, dim3(1), dim3(64), 0, s, h->dQctr, qa.ipm_total);
         NDP_HIP(h, hipGetLastError());
     } else if (pr && stop) NDP_HIP(h, hipEventRecord(stop, s));
@@ -661,13 +646,13 @@ int ensure_slots(ndp_handle *h)
     if (h->slots_ready) return 0;
     for (int i = 0; i < 2; ++i) {
         ndp_handle::HostSlot &sl = h->slot[i];
-        // (only what is missing: a call that failed part-way left the members it did allocate, and they are reused -- ndp_destroy frees them)
-        if (!sl.hIn) NDP_HIP(h, hipHostMalloc((void **)&sl.hIn, h->in_bytes, hipHostMallocDefault));
+        // (only what is missing: a call that failed part-way left the members it did allocate, and they are reused)
+        NDP_HIP(h, sl.hIn.ensure(h->in_bytes));
         if (!sl.hOut) {
-            NDP_HIP(h, hipHostMalloc((void **)&sl.hOut, h->out_all, hipHostMallocDefault));
+            NDP_HIP(h, sl.hOut.alloc(h->out_all));
             memset(sl.hOut, 0, h->out_bytes);
         }
-        if (!sl.evOut) NDP_HIP(h, hipEventCreateWithFlags(&sl.evOut, hipEventDisableTiming));
+        NDP_HIP(h, sl.evOut.ensure(hipEventDisableTiming));
     }
     // pack threads: NDP_PACK_THREADS, else half the cores this process may really use, at most 8; the caller packs too, so small blocks
     // need none.  (Rounds 3-5 counted the machine's hardware threads: in a container whose CPU quota is a fraction of the machine that
@@ -964,12 +949,9 @@ int ndp_debug_stamps(ndp_handle *h, int enable, double *out)
     const size_t bytes = (size_t)h->cfg.batch * NDP_NSTAMP * 8;
     if (out && h->dStamps) NDP_HIP(h, hipMemcpy(out, h->dStamps, bytes, hipMemcpyDeviceToHost));
     if (enable && !h->dStamps) {
-        NDP_HIP(h, hipMalloc((void **)&h->dStamps, bytes));
+        NDP_HIP(h, h->dStamps.alloc(bytes));
         NDP_HIP(h, hipMemset(h->dStamps, 0, bytes));
-    } else if (!enable && h->dStamps) {
-        (void)hipFree(h->dStamps);
-        h->dStamps = nullptr;
-    }
+    } else if (!enable) h->dStamps.reset();
     return 0;
 }
 
@@ -979,14 +961,13 @@ void *ndp_device_force(ndp_handle *h) { return h ? h->dForce : nullptr; }
 int ndp_work_queue_enabled(ndp_handle *h) { return h ? (int)h->use_queue : -1; }
 
 // ---- the sensitivity buffers: created on enabling, NaN until a step has written them
-static int nan_buffer(ndp_handle *h, double *&p, size_t n)
+static int nan_buffer(ndp_handle *h, DevBuf<double> &p, size_t n)
 {
     if (p) return 0;
-    NDP_HIP(h, hipMalloc((void **)&p, n * 8));
+    NDP_HIP(h, p.alloc(n * 8));
     NDP_HIP(h, hipMemsetAsync(p, 0xff, n * 8, h->stream));
     return 0;
 }
-static void drop_buffer(double *&p) { if (p) (void)hipFree(p); p = nullptr; }
 static int copy_out(ndp_handle *h, double *dst, const double *src, size_t n)
 {
     if (dst) NDP_HIP(h, hipMemcpy(dst, src, n * 8, hipMemcpyDeviceToHost));
@@ -1010,8 +991,8 @@ int ndp_sens_enable(ndp_handle *h, int level)
     if (rc) return rc;
     const size_t B = h->cfg.batch, N = h->cfg.N;
     const size_t n0 = B * (size_t)sens_u0_pitch(), nu = B * (size_t)sens_u_pitch((int)N), nx = B * (size_t)sens_x_pitch((int)N);
-    if (level < 2) { drop_buffer(h->dSensU); drop_buffer(h->dSensX); }
-    if (level == 0) { for (double **p : {&h->dSensU0, &h->dPSensXr, &h->dPSensUr, &h->dPSensF}) drop_buffer(*p); h->sens_level = 0; return 0; }
+    if (level < 2) { h->dSensU.reset(); h->dSensX.reset(); }
+    if (level == 0) { for (DevBuf<double> *p : {&h->dSensU0, &h->dPSensXr, &h->dPSensUr, &h->dPSensF}) p->reset(); h->sens_level = 0; return 0; }
     if ((rc = nan_buffer(h, h->dSensU0, n0))) return rc;
     if (level == 2 && ((rc = nan_buffer(h, h->dSensU, nu)) || (rc = nan_buffer(h, h->dSensX, nx)))) return rc;
     const char *what = nullptr;
@@ -1055,7 +1036,7 @@ int ndp_sens_params_enable(ndp_handle *h, int on)
     int rc = wait_all(h);                 // (steps in flight may still write the buffers)
     if (rc) return rc;
     if (!on) {
-        for (double **p : {&h->dPSensXr, &h->dPSensUr, &h->dPSensF}) drop_buffer(*p);
+        for (DevBuf<double> *p : {&h->dPSensXr, &h->dPSensUr, &h->dPSensF}) p->reset();
         return 0;
     }
     const size_t B = h->cfg.batch;
@@ -1114,9 +1095,9 @@ std::string recompute_refusal(const ndp_cfg &c, const char *noun, const Tape &t,
 int recompute_workspace(ndp_handle *h)
 {
     const size_t B = h->cfg.batch;
-    if (!h->dVjp) NDP_HIP(h, hipMalloc((void **)&h->dVjp, (nxs(h) + nus(h) + B * NU) * 8));
-    if (!h->dVjpSt) NDP_HIP(h, hipMalloc((void **)&h->dVjpSt, B * 2 * 4));
-    if (!h->dVjpAct) NDP_HIP(h, hipMalloc((void **)&h->dVjpAct, act_bytes(h)));
+    NDP_HIP(h, h->dVjp.ensure((nxs(h) + nus(h) + B * NU) * 8));
+    NDP_HIP(h, h->dVjpSt.ensure(B * 2 * 4));
+    NDP_HIP(h, h->dVjpAct.ensure(act_bytes(h)));
     return 0;
 }
 
@@ -1278,7 +1259,6 @@ int ndp_timing_enable(ndp_handle *h, int on)
 {
     if (!h) return -1;
     std::lock_guard<std::mutex> lk(h->mu);
-    for (auto &e : h->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     h->events.clear();
     h->timing = on > 0 ? on : 0;
     h->launch_no[0] = h->launch_no[1] = 0;

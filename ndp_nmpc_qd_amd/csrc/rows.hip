@@ -456,8 +456,7 @@ int ndp_ref_set_trajectory(ndp_handle *h, int n_seg, const double *coeff_x, cons
     for (double *c : v.segc) memset(c, 0xFF, B * SEGC_PER * 8);
     int rc = wait_all(h);
     if (rc) return rc;
-    if (h->dTraj) { (void)hipFree(h->dTraj); h->dTraj = nullptr; }
-    NDP_HIP(h, hipMalloc((void **)&h->dTraj, v.doubles * 8));
+    NDP_HIP(h, h->dTraj.alloc(v.doubles * 8));
     NDP_HIP(h, hipMemcpy(h->dTraj, host.data(), v.doubles * 8, hipMemcpyHostToDevice));
     h->segc_par = 0;
     h->traj_seg = n_seg;
@@ -507,7 +506,7 @@ static int list_alloc(ndp_handle *h)
 {
     if (h->dRingX) return 0;
     const RingGeom rg = ring_geom(h);
-    NDP_HIP(h, hipMalloc((void **)&h->dRingX, (size_t)h->cfg.batch * (rg.px() + rg.pu()) * 8));
+    NDP_HIP(h, h->dRingX.alloc((size_t)h->cfg.batch * (rg.px() + rg.pu()) * 8));
     h->dRingU = h->dRingX + (size_t)h->cfg.batch * rg.px();
     return 0;
 }

@@ -440,31 +440,27 @@ extern "C" {
 
 int ndp_debug_mfma_probe(const double *a, const double *b, const double *c, double *d)
 {
-    double *da = nullptr, *db = nullptr, *dc = nullptr, *dd = nullptr;
-    if (hipMalloc((void **)&da, 64 * 8) != hipSuccess || hipMalloc((void **)&db, 64 * 8) != hipSuccess ||
-        hipMalloc((void **)&dc, 256 * 8) != hipSuccess || hipMalloc((void **)&dd, 832 * 8) != hipSuccess)
+    DevBuf<double> da, db, dc, dd;
+    if (da.alloc(64 * 8) != hipSuccess || db.alloc(64 * 8) != hipSuccess || dc.alloc(256 * 8) != hipSuccess || dd.alloc(832 * 8) != hipSuccess)
         return -1;
     (void)hipMemcpy(da, a, 64 * 8, hipMemcpyHostToDevice);
     (void)hipMemcpy(db, b, 64 * 8, hipMemcpyHostToDevice);
     (void)hipMemcpy(dc, c, 256 * 8, hipMemcpyHostToDevice);
     hipLaunchKernelGGL(mfma_probe_kernel, dim3(1), dim3(64), 0, 0, da, db, dc, dd);
     const hipError_t e = hipMemcpy(d, dd, 832 * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dc); (void)hipFree(dd);
     return e == hipSuccess ? 0 : -2;
 }
 
 int ndp_debug_mfma_probe_f32(const float *a, const float *b, const float *c, float *d, int mode)
 {
-    float *da = nullptr, *db = nullptr, *dc = nullptr, *dd = nullptr;
-    if (hipMalloc((void **)&da, 256 * 4) != hipSuccess || hipMalloc((void **)&db, 256 * 4) != hipSuccess ||
-        hipMalloc((void **)&dc, 256 * 4) != hipSuccess || hipMalloc((void **)&dd, 320 * 4) != hipSuccess)
+    DevBuf<float> da, db, dc, dd;
+    if (da.alloc(256 * 4) != hipSuccess || db.alloc(256 * 4) != hipSuccess || dc.alloc(256 * 4) != hipSuccess || dd.alloc(320 * 4) != hipSuccess)
         return -1;
     (void)hipMemcpy(da, a, 256 * 4, hipMemcpyHostToDevice);
     (void)hipMemcpy(db, b, 256 * 4, hipMemcpyHostToDevice);
     (void)hipMemcpy(dc, c, 256 * 4, hipMemcpyHostToDevice);
     hipLaunchKernelGGL(mfma_probe32_kernel, dim3(1), dim3(64), 0, 0, da, db, dc, dd, mode);
     const hipError_t e = hipMemcpy(d, dd, 320 * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dc); (void)hipFree(dd);
     return e == hipSuccess ? 0 : -2;
 }
 

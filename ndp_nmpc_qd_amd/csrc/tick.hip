@@ -29,7 +29,7 @@ extern "C" {
 int ensure_tick(ndp_handle *h)
 {
     if (h->dTickThrust) return 0;
-    NDP_HIP(h, hipMalloc((void **)&h->dTickThrust, (size_t)h->cfg.batch * 8));
+    NDP_HIP(h, h->dTickThrust.alloc((size_t)h->cfg.batch * 8));
     NDP_HIP(h, hipMemsetAsync(h->dTickThrust, 0, (size_t)h->cfg.batch * 8, h->stream));     // AttitudeTarget(): thrust 0 (nmpc_node.py:104)
     NDP_HIP(h, hipStreamSynchronize(h->stream));
     return 0;
@@ -52,12 +52,9 @@ int ndp_tick_config(ndp_handle *h, const int32_t *other_index, int gate_on_odome
     if (any && !h->cfg.use_fd) { h->err = "ndp_tick_config: neighbours (downwash) need use_fd = 1 (NDP model)"; return -8; }
     if (any && !h->have_mlp) { h->err = "ndp_tick_config: neighbours given but ndp_set_mlp_weights was never called"; return -6; }
     if (any) {
-        if (!h->dTickIndex) NDP_HIP(h, hipMalloc((void **)&h->dTickIndex, B * 4));
+        NDP_HIP(h, h->dTickIndex.ensure(B * 4));
         NDP_HIP(h, hipMemcpy(h->dTickIndex, other_index, B * 4, hipMemcpyHostToDevice));
-    } else if (h->dTickIndex) {
-        (void)hipFree(h->dTickIndex);
-        h->dTickIndex = nullptr;
-    }
+    } else h->dTickIndex.reset();
     h->tick_gate = gate_on_odometry != 0;
     h->tick_remote = nullptr;
     return 0;
@@ -84,7 +81,7 @@ int ndp_tick_config_remote(ndp_handle *h, const void *d_windows, int stride, int
     const size_t B = h->cfg.batch;
     for (size_t i = 0; i < B; ++i)
         if ((int64_t)other_index[i] >= rows) { h->err = "ndp_tick_config_remote: other_index names a row outside the window buffer"; return -2; }
-    if (!h->dTickIndex) NDP_HIP(h, hipMalloc((void **)&h->dTickIndex, B * 4));
+    NDP_HIP(h, h->dTickIndex.ensure(B * 4));
     NDP_HIP(h, hipMemcpy(h->dTickIndex, other_index, B * 4, hipMemcpyHostToDevice));
     h->tick_gate = gate_on_odometry != 0;
     h->tick_remote = (const double *)d_windows;
